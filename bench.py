@@ -22,7 +22,13 @@ rank the run goes on without the gather and the line says so; `--comm torch` is 
 `python bench.py --gpus N` with N > 1 and no launcher (no WORLD_SIZE in the environment) starts the N ranks itself, one process
 per GPU, exactly as the driver's `torch.distributed.run` line would; it refuses to run when the box has fewer GPUs.
 
-Prints ONE JSON line on rank 0 (see the driver contract), with
+Prints ONE JSON line on rank 0 (see the driver contract).  A plain run sets up, warms up (`--warmup` steps), times
+EXACTLY `--steps` steps in one bracket (the host enqueues them back to back and synchronizes once; `--min-seconds` repeats
+the bracket until that much time is covered) and prints metric / value / unit / ms_per_step (the bracket's time over its
+steps; the median bracket when there are several) / dtype and the workload.  `--dump-outputs DIR` then writes the 12 output
+arrays of the last timed step, as a caller of the path receives them ([levels][columns], float64), to DIR/<name>.npy: the
+inputs are seeded, so two builds can be compared output for output; past 64 MB in all a fixed, seeded sample of the
+columns is written (the same columns for every array).  Everything below is measured only with `--full`:
   roofline     : dominant kernel = the solve kernel (SW or LW) that takes longer WITH THE GPU TO ITSELF (HIP events around its
                  launches on the stream it runs on, rrtmg_hip_kernel_ms; that is also the order of the kernels' shares in
                  profiles/*_kernel_stats.txt); achieved = its ALGORITHMIC bytes per launch (SW (34L+11)*8 B, LW (56L+22)*8 B
@@ -45,6 +51,8 @@ Prints ONE JSON line on rank 0 (see the driver contract), with
   cpu_baseline : the reference Fortran (see above).
   extra        : (N=1) the end-to-end rates that include PCIe: the host-pointer C-ABI and the drop-in component classes on a
                  sympl-style state; the model step resident on the device.
+  config       : ms_per_step_median / ms_per_step_p10_p90 from a separate bracket with a synchronize after every step.
+  gather_modes : (N>1) every mode of --gather-modes beside the headline mode, and the communicator self-test (comm_selftest).
 """
 import argparse
 import json
@@ -73,6 +81,7 @@ N_SIMD, CLOCK_HZ = 1024, 2.4e9      # 256 CUs x 4 SIMDs; peak engine clock (MI35
 # what holds each solve kernel (measured: docs/EXPERIMENTS.md B-D), printed as roofline.limiter
 LIMITER = {"sw": "valu-issue (FP64): a workgroup is alone on its CU and its 4 waves per SIMD issue VALU instructions for ~63 % of its lifetime; the kernel's time follows its VALU instruction count as long as nothing spills; its scratch slab, partial planes and prep rows cost it 0-3 % (clean ablations, round 6: docs/EXPERIMENTS.md E)",
          "lw": "latency of a layer's four dependent memory trips at 2 waves per SIMD (VALU issue 27 %; a third wave per SIMD adds nothing: round 6) + its scratch-slab STORES (1.1 GB per launch) in the same in-order vector-memory path: they cost 17 % of the kernel and 8.5 % of the step, the reads nothing; held in the L2 instead of HBM they still cost 12 % (clean ablations: profiles/r06_ab_clean_ablations.txt)"}
+SEED = 20260927      # the synthetic columns of rank r: make_columns(..., seed=SEED + r), the same in every run
 FLAGS = dict(icld=1, iaer=0, dyofyr=1, scon=1367.0, isolvar=0, inflg=2, iceflg=1, liqflg=1, irng=0, permuteseed=684)
 
 
@@ -163,6 +172,25 @@ def _profile_json(name):
         return {}
 
 
+DUMP_LIMIT = 64 * 10 ** 6      # bytes --dump-outputs may write in all
+
+
+def dump_outputs(outdir, arrays, limit=DUMP_LIMIT, seed=0):
+    """--dump-outputs: name -> [levels][columns] array, written as outdir/<name>.npy in float64.  When the whole grid would
+    exceed `limit` bytes (npy headers included), the same fixed, seeded sample of columns, in ascending order, is written for
+    every array.  -> the sampled column indices, or None when every column was written."""
+    os.makedirs(outdir, exist_ok=True)
+    ncol = next(iter(arrays.values())).shape[1]
+    per_column = 8 * sum(v.shape[0] for v in arrays.values())
+    cols = None
+    if per_column * ncol + 256 * len(arrays) > limit:
+        keep = (limit - 256 * len(arrays)) // per_column
+        cols = np.sort(np.random.default_rng(seed).choice(ncol, keep, replace=False))
+    for k, v in arrays.items():
+        np.save(os.path.join(outdir, k + ".npy"), np.ascontiguousarray(v if cols is None else v[:, cols], dtype=np.float64))
+    return cols
+
+
 class _NoComm:
     """What is left when librccl could not be brought up on every rank: no gather (the line says so), compute still measured."""
     kind, stream = "none", None
@@ -210,7 +238,7 @@ def spawn_ranks(n):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=None, help="timed steps (default: enough for >= 1 s of timed region)")
+    ap.add_argument("--steps", type=int, default=None, help="timed steps (default: enough for about 3 s of timed region)")
     ap.add_argument("--warmup", type=int, default=None)
     ap.add_argument("--config", type=int, default=2, choices=[2, 3, 4, 5], help="BASELINE.json configs[] index + 1 (2 clear, 3 McICA, 4 / 5 the 8-GPU grids' per-GPU shard)")
     ap.add_argument("--columns", type=int, default=None, help="columns per GPU (overrides the preset)")
@@ -242,7 +270,12 @@ def main():
     ap.add_argument("--contract-arrays", action="store_true", help="N=1: also hand over the band arrays SURVEY 8(d)'s contract bytes count and the synthetic columns "
                     "do not have -- zero `taucld` (LW 16 x L, SW 14 x L) and LW `tauaer` (16 x L) device arrays -- so that the kernels really read them")
     ap.add_argument("--no-comm-selftest", action="store_true", help="N>1: skip the communicator self-test (every gather mode once on a 1 KB pattern, checked on every rank, before the brackets)")
-    ap.add_argument("--min-seconds", type=float, default=3.0, help="timed region: brackets of K steps are repeated until this much time is covered")
+    ap.add_argument("--min-seconds", type=float, default=0.0, help="timed region: brackets of K steps are repeated until this much time is covered "
+                    "(default 0: one bracket, exactly --steps timed steps)")
+    ap.add_argument("--full", action="store_true", help="also measure everything beyond the headline: roofline, McICA co-headline, CPU baseline, "
+                    "end-to-end extras, per-step latency, every gather mode and the communicator self-test (N>1)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the outputs of the last timed step to DIR/<name>.npy (float64, at most 64 MB: "
+                    "a fixed, seeded sample of the columns beyond that)")
     a = ap.parse_args()
     preset = {2: (8192, 60, False), 3: (8192, 60, True), 4: (16384, 60, True), 5: (129600, 100, True)}[a.config]
     N = a.columns or preset[0]
@@ -302,7 +335,7 @@ def main():
         ctx.set_column_sort(True)
 
     def columns(ncol, nlay, cld):
-        c = make_columns(ncol, nlay, cloudy=cld, seed=20260927 + rank)
+        c = make_columns(ncol, nlay, cloudy=cld, seed=SEED + rank)
         if cld and a.clear_every > 0:
             free = (np.arange(ncol) // 64) % a.clear_every == 0
             for k in ("cldfr", "cicewp", "cliqwp"):
@@ -326,8 +359,9 @@ def main():
             dev[name].zero()
         return dict(inp, taucld=dev["taucld_sw"].ptr), dict(inp, taucld=dev["taucld_lw"].ptr, tauaer=dev["tauaer_lw"].ptr)
 
-    def device_run(ncol, nlay, cld, steps, warmup, serial):
-        """Single-GPU device-resident loop: -> (ms per step from the whole region, per-step ms list, kernel ms lists)."""
+    def device_run(ncol, nlay, cld, steps, warmup, serial, dump=False):
+        """Single-GPU device-resident loop: -> (ms per step from the whole region, the last timed step's outputs if `dump`;
+        with --full also the per-step ms list and kernel ms lists)."""
         c = columns(ncol, nlay, cld)
         dev, inp = resident(c)
         inp_sw, inp_lw = contract_inputs(dev, inp) if a.contract_arrays else (inp, inp)
@@ -377,6 +411,15 @@ def main():
             brackets.append((time.perf_counter() - t0) * 1e3 / steps)
             covered += brackets[-1] * steps * 1e-3
         ms = float(np.median(brackets))
+        outputs = None
+        if dump:
+            h = flat.download()
+            outputs, off = {}, 0
+            for k, s in sizes:
+                outputs[k] = h[off:off + s].reshape(s // ncol, ncol)
+                off += s
+        if not a.full:
+            return dict(ms=ms, brackets=brackets, c=c, outputs=outputs)
         # per-step latency, host enqueue time and the event-timed kernel durations: a bracket with a host synchronize after
         # every step (an enqueue behind a full queue would measure the GPU, not the host)
         _hip.synchronize()
@@ -398,24 +441,29 @@ def main():
             ssw.append(ctx.kernel_ms("sw", cloudy=cld))
             slw.append(ctx.kernel_ms("lw", cloudy=cld))
         n_all = max(1, enq[2])
-        return dict(ms=ms, per=per, ksw=ksw, klw=klw, ssw=ssw, slw=slw, enq_sw=enq[0] * 1e3 / n_all, enq=enq[1] * 1e3 / n_all, c=c, brackets=brackets, synced_ms=synced[0])
+        return dict(ms=ms, per=per, ksw=ksw, klw=klw, ssw=ssw, slw=slw, enq_sw=enq[0] * 1e3 / n_all, enq=enq[1] * 1e3 / n_all, c=c, brackets=brackets,
+                    synced_ms=synced[0], outputs=outputs)
 
     def pick_steps(ncol, nlay, cld):
-        """Steps per bracket: about 1.5 s worth (estimated from the large-grid rates of DESIGN.md 5); brackets repeat to --min-seconds."""
+        """Steps per bracket: about 3 s worth (estimated from the large-grid rates of DESIGN.md 5); brackets repeat to --min-seconds."""
         est = ncol * (nlay / 60.0) / (2.7e6 if cld else 5.4e6)
-        return max(10, int(np.ceil(min(a.min_seconds, 1.5) * 1.1 / est)))
+        return max(10, int(np.ceil(3.0 / est)))
 
     steps = a.steps if a.steps is not None else pick_steps(N, L, cloudy)
     warmup = a.warmup if a.warmup is not None else max(2, min(10, steps // 20))
     comm_note, comm_kind, host_wait = "", None, False
+    dump = a.dump_outputs is not None and rank == 0
 
     if not multi:
-        r = device_run(N, L, cloudy, steps, warmup, a.serial)
-        ms, per = r["ms"], r["per"]
+        r = device_run(N, L, cloudy, steps, warmup, a.serial, dump=dump)
+        ms, per, outputs = r["ms"], r.get("per"), r["outputs"]
     else:
         import torch
         from climt_amd.distributed import GATHER_MODES, RcclComm, ShardedRadiation
-        modes = [m for m in a.gather_modes.split(",") if m in GATHER_MODES]
+        # a plain run measures the headline mode only (auto: the two it chooses from); --full every mode of --gather-modes
+        modes = [m for m in a.gather_modes.split(",") if m in GATHER_MODES] if a.full else []
+        if a.gather == "auto" and not a.full:
+            modes = ["all", "direct"]
         if a.gather != "auto" and a.gather not in modes:
             modes.append(a.gather)
         if a.gather == "auto" and not ({"all", "direct"} & set(modes)):
@@ -472,7 +520,7 @@ def main():
         # every word) and is checked on every rank; the line says per mode and rank what happened -- so that the first run on
         # more than one GPU names the collective that misbehaved instead of only "gather switched off"
         comm_selftest_result = None
-        if comm.kind != "none" and not a.no_comm_selftest:
+        if comm.kind != "none" and a.full and not a.no_comm_selftest:
             from climt_amd.distributed import comm_selftest
             try:
                 mine = comm_selftest(comm, alloc=alloc, check_untouched=comm.kind == "rccl")
@@ -533,8 +581,9 @@ def main():
                 brackets.append(bracket_ms(sr, step))
                 covered += brackets[-1] * steps * 1e-3
             fence(sr)
+            outputs = sr.gathered_host((sr.i - 1) % sr.nbuf) if dump else None      # the last timed step's buffer
             per, ksw, klw = [], [], []
-            for _ in range(min(steps, 200)):      # per-step latency and kernel durations: synchronized steps, outside the brackets
+            for _ in range(min(steps, 200) if a.full else 0):      # per-step latency and kernel durations: synchronized steps, outside the brackets
                 t = time.perf_counter()
                 step()
                 per.append((time.perf_counter() - t) * 1e3)
@@ -542,7 +591,7 @@ def main():
                 klw.append(ctx.kernel_ms("lw", cloudy=cloudy))
             fence(sr)
             return dict(mode=mode, ms=float(np.median(brackets)), brackets=brackets, per=per, ksw=ksw, klw=klw, sr=sr, host_wait=hw,
-                        gathered=bool(sr.do_gather), ingress=planned, error=err[0] if err else None, unpack=bool(sr.unpack))
+                        gathered=bool(sr.do_gather), ingress=planned, error=err[0] if err else None, unpack=bool(sr.unpack), outputs=outputs)
         got = {}
         for m in modes:
             got[m] = measure(m)
@@ -557,7 +606,7 @@ def main():
             head = a.gather if a.gather in got else modes[0]
         a.gather = head
         h = got[head]
-        ms, per, host_wait = h["ms"], h["per"], h["host_wait"]
+        ms, per, host_wait, outputs = h["ms"], h["per"], h["host_wait"], h["outputs"]
         ms_none = got["none"]["ms"] if "none" in got else None
         gather_modes = {}
         for m, g in got.items():
@@ -575,16 +624,17 @@ def main():
                                  "needed = the same bytes / the `none` step time, i.e. the rate at which the gather would be free")
         gather_none = dict(gather_modes["none"], note="the brackets without the output gather: value / this value = what the gather costs") if "none" in got else None
         # the two solve kernels with the GPU to themselves (synchronous SW then LW calls on this rank's block)
-        fence(last)
-        ctx.set_deferred(False)
-        sw_o, lw_o = last._out(0)
         ssw, slw = [], []
-        for _ in range(3):
-            ctx.sw_fluxes(last.inp, mcica=cloudy, out=sw_o, memspace=1)
-            ctx.lw_fluxes(last.inp, mcica=cloudy, out=lw_o, memspace=1)
-            ssw.append(ctx.kernel_ms("sw", cloudy=cloudy))
-            slw.append(ctx.kernel_ms("lw", cloudy=cloudy))
-        fence(last)
+        if a.full:
+            fence(last)
+            ctx.set_deferred(False)
+            sw_o, lw_o = last._out(0)
+            for _ in range(3):
+                ctx.sw_fluxes(last.inp, mcica=cloudy, out=sw_o, memspace=1)
+                ctx.lw_fluxes(last.inp, mcica=cloudy, out=lw_o, memspace=1)
+                ssw.append(ctx.kernel_ms("sw", cloudy=cloudy))
+                slw.append(ctx.kernel_ms("lw", cloudy=cloudy))
+            fence(last)
         r = dict(ksw=h["ksw"], klw=h["klw"], ssw=ssw, slw=slw, enq_sw=0.0, enq=0.0, brackets=h["brackets"], gather_none=gather_none,
                  gather_modes=gather_modes, unpack=h["unpack"], gathered=h["gathered"])
         if h["error"]:
@@ -690,8 +740,8 @@ def main():
                             "step_frac is quoted on the contract's bytes, step_frac_on_shipped_bytes on the arrays this run really hands over.  traffic / step_traffic = measured HBM-side bytes (2 x FETCH_SIZE + WRITE_SIZE, PMC "
                             "passes of this command committed under profiles/); step_hbm_side_frac = step_traffic / ms_per_step / 6.3 TB/s (a read stream's rate), "
                             "step_hbm_side_frac_of_mixed_rate = the same / 5.3 TB/s (what copy kernels and the slab's own write-then-read pattern reach on this part)"}
-        launches = max(1, ctx.kernel_launches("sw", cloudy=cloudy))      # column chunks per call: one launch of each solve kernel per chunk
-        roofline = roofline_block(N, L, cloudy, r, ms, launches)
+        if dump:
+            dump_outputs(a.dump_outputs, outputs)
         par = "columns sharded x%d" % world
         if world > 1:
             par += {"all": " + RCCL all-gather of the outputs (one flat buffer, double-buffered: runs under the next step's kernels)",
@@ -710,24 +760,28 @@ def main():
                        "timed_region_s": float(np.sum(r["brackets"])) * steps * 1e-3, "brackets": len(r["brackets"]),
                        "bracket_note": "ms_per_step = median over `brackets` timed regions of exactly `steps` steps each (max over ranks per bracket)",
                        "host_sync": ("after every step" if (a.serial or a.sync_every_step or (multi and host_wait)) else
-                                     "one per bracket: the host enqueues the K steps back to back (each stream orders step i+1 behind step i) and synchronizes once; ms_per_step_median / p10_p90 below come from a separate bracket with a synchronize after every step"),
-                       "ms_per_step_median": float(np.median(per)),
-                       "ms_per_step_p10_p90": [float(np.percentile(per, 10)), float(np.percentile(per, 90))],
+                                     "one per bracket: the host enqueues the K steps back to back (each stream orders step i+1 behind step i) and synchronizes once" +
+                                     ("; ms_per_step_median / p10_p90 below come from a separate bracket with a synchronize after every step" if a.full else "")),
                        "lw_k_tables": "synthetic (reference LW data file missing)", "sw_k_tables": "reference"},
-            "roofline": roofline,
         }
-        res["cpu_baseline"] = None
+        if a.full:
+            launches = max(1, ctx.kernel_launches("sw", cloudy=cloudy))      # column chunks per call: one launch of each solve kernel per chunk
+            res["config"]["ms_per_step_median"] = float(np.median(per))
+            res["config"]["ms_per_step_p10_p90"] = [float(np.percentile(per, 10)), float(np.percentile(per, 90))]
+            res["roofline"] = roofline_block(N, L, cloudy, r, ms, launches)
+            res["cpu_baseline"] = None
         if multi:
             res["config"]["rccl_max_channels"] = os.environ.get("NCCL_MAX_NCHANNELS")
             res["config"]["gathered_layout"] = ("boundary [array][level][column] (block-copy kernel behind the gather)" if r["unpack"] else
                                                 "collective [rank][array][level][local column]") if r["gathered"] else None
             res["config"]["gather_mode"] = a.gather
+        if multi and a.full:
             res["comm_selftest"] = comm_selftest_result
             res["gather_modes"] = r.get("gather_modes")
             res["extra"] = {"gather_none": r.get("gather_none"),
                             "how_to_scale": "per-GPU work is fixed (weak scaling): `--config 4` = 512x256x60 over 8 GPUs (16384 columns each), `--config 5` = "
                                             "1440x720x100 (129600 columns x 100 levels each); `--gather auto|all|direct|root|none` (headline mode; every mode in --gather-modes is measured), `--no-unpack`, `--rccl-channels N`"}
-        if world == 1 and not multi and not cloudy and a.config == 2 and not (a.columns or a.levels) and not a.no_mcica:
+        if a.full and world == 1 and not multi and not cloudy and a.config == 2 and not (a.columns or a.levels) and not a.no_mcica:
             # CO-HEADLINE: BASELINE.json configs[2] -- McICA liquid+ice clouds (kissvec), 128x64x60 -- in the same run with the
             # same discipline as the headline: K-step brackets (the same K) repeated until --min-seconds are covered, the
             # median bracket; its own roofline object at the top level
@@ -742,7 +796,7 @@ def main():
                                            "cloud fraction 0 / 0.3 / 0.6 / 1 by region (SURVEY.md 8d config 3)",
                             "ratio_to_clear_sky": m["ms"] / ms}
             res["roofline_mcica"] = roofline_block(8192, 60, True, m, m["ms"], m_launches)
-        if world == 1 and not multi:
+        if a.full and world == 1 and not multi:
             if not a.no_extra:
                 extra = {}
                 # (a) configs[2] is a co-headline of the default run (see below); kept here as a pointer for older readers

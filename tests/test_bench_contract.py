@@ -26,8 +26,37 @@ def test_more_gpus_than_the_box_has_is_refused():
 def test_help_names_the_multi_gpu_knobs():
     p = _run(["--help"])
     assert p.returncode == 0
-    for flag in ("--gpus", "--gather", "--no-unpack", "--rccl-channels", "--min-seconds", "--config"):
+    for flag in ("--gpus", "--gather", "--no-unpack", "--rccl-channels", "--min-seconds", "--config", "--full", "--dump-outputs"):
         assert flag in p.stdout, flag
+
+
+def _bench_module():
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("_bench", os.path.join(ROOT, "bench.py"))
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    return mod
+
+
+def test_dump_outputs_writes_float64_and_samples_columns_past_the_limit(tmp_path):
+    """--dump-outputs: every array as <name>.npy in float64; past the size limit the same seeded columns for every array,
+    the same from call to call, and the files stay under the limit."""
+    import numpy as np
+    bench = _bench_module()
+    rng = np.random.default_rng(3)
+    arrays = {"a": rng.standard_normal((61, 1000)), "b": rng.standard_normal((60, 1000))}
+    assert bench.dump_outputs(str(tmp_path / "whole"), arrays) is None
+    for k, v in arrays.items():
+        got = np.load(str(tmp_path / "whole" / (k + ".npy")))
+        assert got.dtype == np.float64 and np.array_equal(got, v)
+    limit = 200000
+    cols = bench.dump_outputs(str(tmp_path / "s1"), arrays, limit=limit)
+    again = bench.dump_outputs(str(tmp_path / "s2"), arrays, limit=limit)
+    assert cols is not None and np.array_equal(cols, again) and np.all(np.diff(cols) > 0)
+    assert sum(os.path.getsize(str(tmp_path / "s1" / (k + ".npy"))) for k in arrays) <= limit
+    for k, v in arrays.items():
+        got = np.load(str(tmp_path / "s1" / (k + ".npy")))
+        assert np.array_equal(got, v[:, cols]) and np.array_equal(got, np.load(str(tmp_path / "s2" / (k + ".npy"))))
 
 
 def test_spawned_ranks_fail_fast_and_print_no_line_without_a_gpu():
@@ -65,11 +94,37 @@ import pytest  # noqa: E402
 
 
 @pytest.mark.gpu
+def test_plain_run_times_exactly_its_steps_and_dumps_the_last_one(tmp_path, gpu_ctx):
+    """A plain run: one bracket of exactly --steps steps, the headline fields and nothing measured beyond them (those need
+    --full); --dump-outputs writes the 12 arrays of the last timed step, and they are what a direct call computes on the
+    same seeded columns."""
+    import numpy as np
+    from climt_amd._lib import LW_OUT, SW_OUT
+    from climt_amd.synthetic import make_columns
+    j = _line(_run(["--gpus", "1", "--steps", "5", "--warmup", "1", "--dump-outputs", str(tmp_path / "out")]))
+    assert j["steps"] == 5 and j["warmup"] == 1 and j["config"]["brackets"] == 1
+    assert abs(j["config"]["timed_region_s"] - 5 * j["ms_per_step"] * 1e-3) < 1e-9
+    assert j["unit"] == "columns/s" and j["higher_is_better"] is True and j["dtype"] == "f64" and j["metric"]
+    assert abs(j["value"] - 8192 / (j["ms_per_step"] * 1e-3)) < 1e-6 * j["value"]
+    assert not {"roofline", "mcica", "roofline_mcica", "cpu_baseline", "extra"} & set(j)
+    bench = _bench_module()
+    c = make_columns(8192, 60, cloudy=False, seed=bench.SEED)
+    c.update(bench.FLAGS)
+    c.pop("lat")
+    want = dict(gpu_ctx.sw_fluxes(c, mcica=False), **gpu_ctx.lw_fluxes(c, mcica=False))
+    assert sorted(f[:-4] for f in os.listdir(str(tmp_path / "out"))) == sorted(k for k, _ in SW_OUT + LW_OUT)
+    for k, lev in SW_OUT + LW_OUT:
+        got = np.load(str(tmp_path / "out" / (k + ".npy")))
+        assert got.dtype == np.float64 and got.shape == (60 + lev, 8192), k
+        assert np.abs(got - want[k]).max() <= 1e-9 * max(1.0, np.abs(want[k]).max()), k
+
+
+@pytest.mark.gpu
 def test_line_carries_issue_fraction_bound_and_the_mcica_co_headline():
     """VERDICT r4 #2a / #5: `roofline.bound` stays the contract's roofline (hbm: what achieved / peak / frac are quoted against),
     `limiter` says what actually holds the kernel, every solve kernel has its VALU issue fraction, and configs[2] (McICA) is measured with the headline's
     own bracket discipline and has a top-level roofline object."""
-    j = _line(_run(["--steps", "6", "--warmup", "1", "--min-seconds", "0.3", "--no-cpu-baseline", "--no-extra"]))
+    j = _line(_run(["--full", "--steps", "6", "--warmup", "1", "--min-seconds", "0.3", "--no-cpu-baseline", "--no-extra"]))
     r = j["roofline"]
     assert j["n_gpus"] == 1 and j["steps"] == 6 and j["dtype"] == "f64" and j["config"]["workload"] == "rrtmg_lw+sw_clear_sky_8192col_x_60lev_per_gpu"
     assert r["bound"] == "hbm" and "valu" in r["limiter"].lower() and r["unit"] == "GB/s" and abs(r["frac"] - r["achieved"] / r["peak"]) < 1e-12
@@ -93,7 +148,7 @@ def test_one_run_measures_every_gather_mode():
     """VERDICT r4 #3b: the N>1 code path (forced with one rank on a one-GPU box) prints, from ONE run, columns/s per gather
     mode -- ncclAllGather, the direct grouped send/recv exchange, gather to root, none -- with the bytes a GPU receives per step,
     the rate achieved and the rate the compute alone would need."""
-    j = _line(_run(["--force-dist", "--steps", "6", "--warmup", "1", "--min-seconds", "0.3", "--no-cpu-baseline", "--no-extra"]))
+    j = _line(_run(["--full", "--force-dist", "--steps", "6", "--warmup", "1", "--min-seconds", "0.3", "--no-cpu-baseline", "--no-extra"]))
     g = j["gather_modes"]
     assert {"all", "direct", "root", "none"} <= set(g)
     for m in ("all", "direct", "root", "none"):
@@ -110,7 +165,7 @@ def test_two_self_spawned_ranks_share_the_gpu_and_print_one_line():
     """`--gpus 2` without a launcher: bench.py starts its two ranks itself (here both on GPU 0, over torch/gloo with the testing
     communicator, because RCCL refuses two ranks on one device): ONE JSON line, n_gpus 2, value = columns of both ranks / the
     slowest rank's time, every gather mode measured with the bytes a rank receives per step (one peer's block)."""
-    p = _run(["--gpus", "2", "--share-device", "--dist-backend", "gloo", "--comm", "torch", "--steps", "4", "--warmup", "1", "--min-seconds", "0.2",
+    p = _run(["--full", "--gpus", "2", "--share-device", "--dist-backend", "gloo", "--comm", "torch", "--steps", "4", "--warmup", "1", "--min-seconds", "0.2",
               "--no-cpu-baseline", "--no-extra"])
     lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, (p.returncode, p.stderr[-600:])

@@ -1,6 +1,6 @@
 # development: the one-rank distributed code path of bench.py against the plain single-GPU loop (same kernels, same streams)
 export RRTMG_HIP_ALLOW_SYNTHETIC_LW=1
-F="--steps 200 --no-extra --no-cpu-baseline"
+F="--full --steps 200 --no-extra --no-cpu-baseline"
 show() { python -c "
 import json,sys
 for l in sys.stdin:

@@ -20,22 +20,22 @@ for sec in "$@"; do
     smoke)
       timeout 300 python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | tail -3 ;;
     bench)
-      timeout 600 python bench.py > $O/${R}_bench_default.log 2>&1; grep "^{" $O/${R}_bench_default.log | tail -1 > $O/${R}_bench_default.json; cut -c1-600 $O/${R}_bench_default.json
-      timeout 600 python bench.py --cloudy > $O/${R}_bench_default_cloudy.log 2>&1; grep "^{" $O/${R}_bench_default_cloudy.log | tail -1 > $O/${R}_bench_default_cloudy.json; cut -c1-400 $O/${R}_bench_default_cloudy.json ;;
+      timeout 600 python bench.py --full > $O/${R}_bench_default.log 2>&1; grep "^{" $O/${R}_bench_default.log | tail -1 > $O/${R}_bench_default.json; cut -c1-600 $O/${R}_bench_default.json
+      timeout 600 python bench.py --full --cloudy > $O/${R}_bench_default_cloudy.log 2>&1; grep "^{" $O/${R}_bench_default_cloudy.log | tail -1 > $O/${R}_bench_default_cloudy.json; cut -c1-400 $O/${R}_bench_default_cloudy.json ;;
     dist)
       # ONE run measures every gather mode (bench.py: gather_modes); the second line: two ranks on this one GPU over torch/gloo (testing communicator)
-      timeout 400 python bench.py --force-dist --no-cpu-baseline --no-extra --steps 100 > $O/${R}_dist_modes.log 2>&1; echo "dist rc=$?"; grep "^{" $O/${R}_dist_modes.log | tail -1 > $O/${R}_dist_modes.json
+      timeout 400 python bench.py --full --force-dist --no-cpu-baseline --no-extra --steps 100 > $O/${R}_dist_modes.log 2>&1; echo "dist rc=$?"; grep "^{" $O/${R}_dist_modes.log | tail -1 > $O/${R}_dist_modes.json
       python -c "
 import json
 j=json.load(open('$O/${R}_dist_modes.json')); print('headline', j['config']['gather_mode'], round(j['value']), j['ms_per_step'], j['config']['communicator'])
 for m,g in j['gather_modes'].items():
     if m[0] != '_': print('  %-7s %9d col/s %7.3f ms  ingress %.1f MB/step  achieved %.1f GB/s  ran=%s err=%s' % (m, g['value'], g['ms_per_step'], g['ingress_bytes_per_gpu_per_step']/1e6, g['ingress_GBps_per_gpu_achieved'], g['gather_ran'], g['error']))" || tail -5 $O/${R}_dist_modes.log
-      timeout 300 python bench.py --gpus 2 --share-device --dist-backend gloo --comm torch --no-cpu-baseline --no-extra --steps 50 --min-seconds 1 > $O/${R}_dist_torch.log 2>&1; grep "^{" $O/${R}_dist_torch.log | tail -1 | cut -c1-300 ;;
+      timeout 300 python bench.py --full --gpus 2 --share-device --dist-backend gloo --comm torch --no-cpu-baseline --no-extra --steps 50 --min-seconds 1 > $O/${R}_dist_torch.log 2>&1; grep "^{" $O/${R}_dist_torch.log | tail -1 | cut -c1-300 ;;
     sizes)
       for c in 4 5; do
-        timeout 600 python bench.py --config $c --no-cpu-baseline --no-extra > $O/${R}_bench_config$c.log 2>&1; grep "^{" $O/${R}_bench_config$c.log | tail -1 > $O/${R}_bench_config$c.json; cut -c1-300 $O/${R}_bench_config$c.json
+        timeout 600 python bench.py --full --config $c --no-cpu-baseline --no-extra > $O/${R}_bench_config$c.log 2>&1; grep "^{" $O/${R}_bench_config$c.log | tail -1 > $O/${R}_bench_config$c.json; cut -c1-300 $O/${R}_bench_config$c.json
       done
-      timeout 600 python bench.py --columns 131072 --no-cpu-baseline --no-extra > $O/${R}_bench_clear131072.log 2>&1; grep "^{" $O/${R}_bench_clear131072.log | tail -1 > $O/${R}_bench_clear131072.json; cut -c1-300 $O/${R}_bench_clear131072.json ;;
+      timeout 600 python bench.py --full --columns 131072 --no-cpu-baseline --no-extra > $O/${R}_bench_clear131072.log 2>&1; grep "^{" $O/${R}_bench_clear131072.log | tail -1 > $O/${R}_bench_clear131072.json; cut -c1-300 $O/${R}_bench_clear131072.json ;;
     ab:*)
       # entries: <lib>[+ENV=VALUE[+ENV=VALUE...]]; AB_MODES="clear" | "cloudy" | "clear cloudy" (default both)
       for ent in $(echo ${sec#ab:} | tr , ' '); do
@@ -43,7 +43,7 @@ for m,g in j['gather_modes'].items():
         for m in ${AB_MODES:-clear cloudy}; do
           mode=""; [ $m = cloudy ] && mode="--cloudy"
           L=$PWD/climt_amd/_lib/ab/$lib; [ $lib = product ] && L=$PWD/climt_amd/_lib/librrtmg_hip.so
-          env $envs RRTMG_HIP_LIB=$L timeout 200 python bench.py --no-cpu-baseline --no-extra --no-mcica --steps 150 $mode 2>&1 | tail -1 | python -c "
+          env $envs RRTMG_HIP_LIB=$L timeout 200 python bench.py --full --no-cpu-baseline --no-extra --no-mcica --steps 150 $mode 2>&1 | tail -1 | python -c "
 import json,sys
 try:
     j=json.loads(sys.stdin.read()); r=j['roofline']
@@ -60,7 +60,7 @@ except Exception as e:
         for ent in $(echo ${sec#absize:} | tr , ' '); do
           lib=${ent%%+*}; envs=""; [ "$ent" != "$lib" ] && envs=$(echo ${ent#*+} | tr + ' ')
           L=$PWD/climt_amd/_lib/ab/$lib; [ $lib = product ] && L=$PWD/climt_amd/_lib/librrtmg_hip.so
-          env $envs RRTMG_HIP_LIB=$L timeout 300 python bench.py --no-cpu-baseline --no-extra --no-mcica --min-seconds 1.5 $spec 2>&1 | tail -1 | python -c "
+          env $envs RRTMG_HIP_LIB=$L timeout 300 python bench.py --full --no-cpu-baseline --no-extra --no-mcica --min-seconds 1.5 $spec 2>&1 | tail -1 | python -c "
 import json,sys
 try:
     j=json.loads(sys.stdin.read()); r=j['roofline']
@@ -81,14 +81,14 @@ except Exception as e:
                  "SQ_INSTS_LDS SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_WAIT_INST_LDS SQ_INSTS_VMEM SQ_INST_LEVEL_VMEM SQ_INST_LEVEL_LDS" \
                  "SQC_ICACHE_REQ SQC_ICACHE_HITS SQC_ICACHE_MISSES SQ_IFETCH SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_BRANCH SQ_INSTS_SMEM"; do
           i=$((i+1)); out=$O/pmcab_$i; rm -rf $out
-          RRTMG_HIP_LIB=$L timeout 300 rocprofv3 --kernel-trace --pmc $P -d $out -- python bench.py --no-cpu-baseline --no-extra --no-mcica --serial --steps 3 --warmup 1 --min-seconds 0 > $out.log 2>&1
+          RRTMG_HIP_LIB=$L timeout 300 rocprofv3 --kernel-trace --pmc $P -d $out -- python bench.py --full --no-cpu-baseline --no-extra --no-mcica --serial --steps 3 --warmup 1 --min-seconds 0 > $out.log 2>&1
           f=$(find $out -name "*.db" | head -1); [ -n "$f" ] && python tools/rocpd_pmc.py $f ${PMC_FILTER:-lw_solve_all_kernel} | sed "s/^/$lib /" >> $O/${R}_pmcab.txt; rm -rf $out
         done
       done; cat $O/${R}_pmcab.txt ;;
     phases)
       # the diagnostic build with phase timers in the longwave sweeps (climt_amd/_lib/lib_profile.so: RRTMG_HIP_BUILD_FLAGS=-DRRTMG_PROFILE RRTMG_HIP_BUILD_OUT=.../lib_profile.so python climt_amd/build.py --force)
       for mode in "" "--cloudy"; do
-        RRTMG_HIP_LIB=$PWD/climt_amd/_lib/lib_profile.so timeout 200 python bench.py --no-cpu-baseline --no-extra --serial --steps 2 --warmup 1 --min-seconds 0 $mode 2>&1 | grep -A1 "lw phases" | tail -2 | tee -a $O/${R}_lw_phases.txt
+        RRTMG_HIP_LIB=$PWD/climt_amd/_lib/lib_profile.so timeout 200 python bench.py --full --no-cpu-baseline --no-extra --serial --steps 2 --warmup 1 --min-seconds 0 $mode 2>&1 | grep -A1 "lw phases" | tail -2 | tee -a $O/${R}_lw_phases.txt
       done ;;
     prof)
       for mode in clear cloudy; do
@@ -96,7 +96,7 @@ except Exception as e:
         for variant in overlap serial; do
           vf=""; [ $variant = serial ] && vf="--serial"
           out=$O/prof_${mode}_$variant; rm -rf $out
-          timeout 240 rocprofv3 --kernel-trace --stats -d $out -- python bench.py --no-cpu-baseline --no-extra --no-mcica --steps 40 --warmup 3 $flag $vf > $out.log 2>&1
+          timeout 240 rocprofv3 --kernel-trace --stats -d $out -- python bench.py --full --no-cpu-baseline --no-extra --no-mcica --steps 40 --warmup 3 $flag $vf > $out.log 2>&1
           grep "^{" $out.log | tail -1 > $O/${R}_bench_${mode}_$variant.json
           stats $out $O/${R}_bench_${mode}_${variant}_kernel_stats.txt
         done
@@ -106,7 +106,7 @@ except Exception as e:
       for spec in "config4:--config 4 --steps 12" "config5:--config 5 --steps 3" "clear131072:--columns 131072 --steps 6"; do
         tag=${spec%%:*}; args=${spec#*:}
         out=$O/prof_$tag; rm -rf $out
-        timeout 400 rocprofv3 --kernel-trace --stats -d $out -- python bench.py --no-cpu-baseline --no-extra --no-mcica --warmup 2 --min-seconds 0 $args > $out.log 2>&1
+        timeout 400 rocprofv3 --kernel-trace --stats -d $out -- python bench.py --full --no-cpu-baseline --no-extra --no-mcica --warmup 2 --min-seconds 0 $args > $out.log 2>&1
         grep "^{" $out.log | tail -1 > $O/${R}_bench_${tag}_profiled.json
         stats $out $O/${R}_bench_${tag}_kernel_stats.txt; head -8 $O/${R}_bench_${tag}_kernel_stats.txt
       done ;;
@@ -116,7 +116,7 @@ except Exception as e:
         flag=""; [ $mode = cloudy ] && flag="--cloudy"
         for c in FETCH_SIZE WRITE_SIZE; do
           out=$O/pmc_${mode}_$c$tag; rm -rf $out
-          timeout 300 rocprofv3 --kernel-trace --pmc $c -d $out -- python bench.py --columns $n --no-cpu-baseline --no-extra --no-mcica --serial --steps 3 --warmup 1 --min-seconds 0 $flag > $out.log 2>&1
+          timeout 300 rocprofv3 --kernel-trace --pmc $c -d $out -- python bench.py --full --columns $n --no-cpu-baseline --no-extra --no-mcica --serial --steps 3 --warmup 1 --min-seconds 0 $flag > $out.log 2>&1
           pmc $out $O/${R}_pmc_${mode}_$c$tag.txt; cat $O/${R}_pmc_${mode}_$c$tag.txt
         done
       done ;;
@@ -126,7 +126,7 @@ except Exception as e:
         i=0
         for P in "SQ_INSTS_VALU SQ_INSTS_VALU_FMA_F64 SQ_INSTS_VALU_MUL_F64 SQ_INSTS_VALU_ADD_F64 SQ_INSTS_VALU_TRANS_F64 SQ_INSTS_SALU SQ_INSTS_VMEM_RD SQ_INSTS_LDS" "SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_BUSY_CYCLES GRBM_GUI_ACTIVE SQ_WAVES"; do
           i=$((i+1)); out=$O/sq_${mode}_$i; rm -rf $out
-          timeout 300 rocprofv3 --kernel-trace --pmc $P -d $out -- python bench.py --no-cpu-baseline --no-extra --no-mcica --serial --steps 3 --warmup 1 --min-seconds 0 $flag > $out.log 2>&1
+          timeout 300 rocprofv3 --kernel-trace --pmc $P -d $out -- python bench.py --full --no-cpu-baseline --no-extra --no-mcica --serial --steps 3 --warmup 1 --min-seconds 0 $flag > $out.log 2>&1
           pmc $out $O/${R}_sq_${mode}_$i.txt
         done
         cat $O/${R}_sq_${mode}_1.txt $O/${R}_sq_${mode}_2.txt > $O/${R}_pmc_${mode}_sq.txt
