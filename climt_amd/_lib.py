@@ -39,6 +39,16 @@ class SwArgs(C.Structure):
                 + [(n, _f64) for n in _SCALES])
 
 
+# members of rrtmg_sw_components (include/rrtmg_hip.h), in order: downward direct / diffuse flux, all bands, UV/visible
+# bands, near-IR bands (all sky), and all bands clear sky
+SW_COMPONENTS = ("dirdflx", "difdflx", "dirdnuv", "difdnuv", "dirdnir", "difdnir", "dirdflxc", "difdflxc")
+
+
+class SwComponents(C.Structure):
+    """mirrors `rrtmg_sw_components` (include/rrtmg_hip.h), field for field"""
+    _fields_ = [("struct_size", _i32), ("reserved", _i32)] + [(n, _vp) for n in SW_COMPONENTS]
+
+
 class LwArgs(C.Structure):
     _fields_ = ([(n, _i32) for n in ("ncol nlay memspace mcica icld idrv inflglw iceflglw liqflglw irng permuteseed "
                                      "shard_col0 shard_ncol struct_size").split()]
@@ -82,6 +92,7 @@ def load_library():
     lib.rrtmg_hip_lw_init.argtypes = [_vp, _f64, C.c_char_p]
     lib.rrtmg_hip_sw_fluxes.argtypes = [_vp, C.POINTER(SwArgs)]
     lib.rrtmg_hip_lw_fluxes.argtypes = [_vp, C.POINTER(LwArgs)]
+    lib.rrtmg_hip_sw_fluxes_components.argtypes = [_vp, C.POINTER(SwArgs), C.POINTER(SwComponents)]
     lib.rrtmg_hip_get_table.restype = C.c_long
     lib.rrtmg_hip_get_table.argtypes = [_vp, C.c_char_p, _vp, C.c_long]
     lib.rrtmg_hip_lw_tables_synthetic.argtypes = [_vp]
@@ -342,7 +353,10 @@ class Context:
                 setattr(a, f, arr.ctypes.data)
 
     @_locked
-    def sw_fluxes(self, inp, mcica=False, out=None, memspace=0):
+    def sw_fluxes(self, inp, mcica=False, out=None, memspace=0, components=None):
+        """`components`: None, or a dict SW_COMPONENTS name -> output (a C-contiguous float64 [nlay+1][ncol] array, or a device
+        pointer with memspace=1) that the call fills as well (rrtmg_hip_sw_fluxes_components); the names left out are not
+        computed."""
         nlay, ncol = (inp["nlay"], inp["ncol"]) if memspace else inp["play"].shape
         a = SwArgs()
         a.struct_size = C.sizeof(SwArgs)
@@ -356,7 +370,21 @@ class Context:
         for k, _ in SW_OUT:
             v = out[k]
             setattr(a, k, int(v) if isinstance(v, (int, np.integer)) else v.ctypes.data)
-        self._ck(self.lib.rrtmg_hip_sw_fluxes(self.h, C.byref(a)))
+        if components is None:
+            self._ck(self.lib.rrtmg_hip_sw_fluxes(self.h, C.byref(a)))
+            return out
+        c = SwComponents()
+        c.struct_size = C.sizeof(SwComponents)
+        for k, v in components.items():
+            if k not in SW_COMPONENTS:
+                raise KeyError("unknown shortwave flux component %r (one of %s)" % (k, ", ".join(SW_COMPONENTS)))
+            if isinstance(v, (int, np.integer)):
+                setattr(c, k, int(v))
+                continue
+            if not (isinstance(v, np.ndarray) and v.dtype == np.float64 and v.flags.c_contiguous and v.size == (nlay + 1) * ncol):
+                raise ValueError("component %r: the library writes it in place: a C-contiguous float64 array of %d x %d" % (k, nlay + 1, ncol))
+            setattr(c, k, v.ctypes.data)
+        self._ck(self.lib.rrtmg_hip_sw_fluxes_components(self.h, C.byref(a), C.byref(c)))
         return out
 
     @_locked

@@ -470,6 +470,15 @@ long rrtmg_hip_get_table(rrtmg_ctx *ctx, const char *name, double *out, long cap
 
 int rrtmg_hip_sw_fluxes(rrtmg_ctx *ctx, const rrtmg_sw_args *a) { return checked_call(ctx, a, "rrtmg_sw", sw_fluxes_impl); }
 int rrtmg_hip_lw_fluxes(rrtmg_ctx *ctx, const rrtmg_lw_args *a) { return checked_call(ctx, a, "rrtmg_lw", lw_fluxes_impl); }
+int rrtmg_hip_sw_fluxes_components(rrtmg_ctx *ctx, const rrtmg_sw_args *a, const rrtmg_sw_components *c) {
+  if (!ctx) return RRTMG_ERR_ARG;
+  if (c && (size_t)c->struct_size != sizeof(rrtmg_sw_components))
+    return ctx->fail(RRTMG_ERR_ARG, "rrtmg_sw_components: struct_size %d is not sizeof(rrtmg_sw_components) = %zu of this library: set it to sizeof of the struct",
+                     (int)c->struct_size, sizeof(rrtmg_sw_components));
+  if (!c || !(c->dirdflx || c->difdflx || c->dirdnuv || c->difdnuv || c->dirdnir || c->difdnir || c->dirdflxc || c->difdflxc))
+    return rrtmg_hip_sw_fluxes(ctx, a);
+  return checked_call(ctx, a, "rrtmg_sw", [c](rrtmg_ctx *x, const rrtmg_sw_args *b) { return sw_fluxes_components_impl(x, b, c); });
+}
 int rrtmg_hip_abi_version(void) { return RRTMG_HIP_ABI_VERSION; }
 
 int rrtmg_hip_mcica_mask(rrtmg_ctx *ctx, int which, int ncol, int nlay, int icld, int permuteseed, int irng,

@@ -54,9 +54,11 @@ struct rrtmg_ctx {
   // (spectrum, tiles, layers, kind of grid) and kept: no hipMemGetInfo per call, and a hint that flips back and forth re-uses
   // the two plans it has; ctx->buf never shrinks, so the footprint is the largest plan's (INTEGRATION.md states it).
   size_t max_scratch_bytes = 0;      // 0: device_mem / 8
-  struct ChunkPlan { int ntile = -1, nlay = -1, base = -1, chunk = 0; };
+  struct ChunkPlan { int ntile = -1, nlay = -1, base = -1, chunk = 0; size_t bytes = 0; };
   ChunkPlan plans[2][2];             // [sw|lw][grid of one kind | mixed]
-  // -> tiles per chunk.  chunk_tiles = the chunk a grid of one kind gets (128, or 64 for a deep cloudy grid)
+  // -> tiles per chunk.  chunk_tiles = the chunk a grid of one kind gets (128, or 64 for a deep cloudy grid); bytes_per_tile =
+  // the work space a mixed grid's chunk grows by per tile (a plan is kept per value: a shortwave call with flux components
+  // counts its direct-beam partial planes too)
   int plan_chunks(int which, int chunk_tiles, int ntile, int nlay, int hint_cloudy, size_t bytes_per_tile, const char *scratch) {
     bool mixed = false;
     if (chunk_auto && hint_cloudy >= 0 && ntile > chunk_tiles) {
@@ -64,7 +66,7 @@ struct rrtmg_ctx {
       mixed = 16 * fewer >= ntile;
     }
     ChunkPlan &p = plans[which][mixed ? 1 : 0];
-    if (p.ntile == ntile && p.nlay == nlay && p.base == chunk_tiles) return p.chunk;
+    if (p.ntile == ntile && p.nlay == nlay && p.base == chunk_tiles && p.bytes == bytes_per_tile) return p.chunk;
     int chunk = chunk_tiles;
     if (mixed) {
       size_t budget = max_scratch_bytes ? max_scratch_bytes : device_mem / 8, free_b = 0, total_b = 0;
@@ -77,7 +79,7 @@ struct rrtmg_ctx {
       if (cap > 2048) cap = 2048;
       if (cap > chunk_tiles) chunk = (int)cap;
     }
-    p.ntile = ntile; p.nlay = nlay; p.base = chunk_tiles; p.chunk = chunk;
+    p.ntile = ntile; p.nlay = nlay; p.base = chunk_tiles; p.chunk = chunk; p.bytes = bytes_per_tile;
     return chunk;
   }
   // What the PREVIOUS call of a spectrum [sw|lw] found -- tiles, layers, tiles with a cloud -- for sizing and ordering the
@@ -195,6 +197,7 @@ std::string default_blob_path(const char *which);
 void free_sw_desc(rrtmg_ctx *ctx);
 void free_lw_desc(rrtmg_ctx *ctx);
 int sw_fluxes_impl(rrtmg_ctx *ctx, const rrtmg_sw_args *a);
+int sw_fluxes_components_impl(rrtmg_ctx *ctx, const rrtmg_sw_args *a, const rrtmg_sw_components *c);
 int lw_fluxes_impl(rrtmg_ctx *ctx, const rrtmg_lw_args *a);
 int sw_init_impl(rrtmg_ctx *ctx, double cpdair, const char *blob);
 int lw_init_impl(rrtmg_ctx *ctx, double cpdair, const char *blob);

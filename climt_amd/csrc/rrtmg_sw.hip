@@ -15,6 +15,9 @@
 //                         work wherever cloud-free and cloudy tiles interleave (every fourth tile cloud-free: 6 of 8 and
 //                         4 of 16 wavefronts otherwise, in workgroups that hold a whole CU either way)
 //     sw_fluxheat_kernel  <<<(tiles, levels/15), 16 waves>>>  g-point sum per interface + heating rates
+//   With components requested (rrtmg_hip_sw_fluxes_components): the solve variants sw_solve_all_dir_kernel<false> and
+//   sw_solve_cloudy_dir_kernel instead, which also write the direct-beam partial planes, and sw_components_kernel
+//   <<<(tiles, levels/4), 4 waves>>> behind sw_fluxheat_kernel: direct / diffuse, UV-visible / near-IR sums per interface
 #include <future>
 
 #include "rrtmg_ctx.h"
@@ -112,8 +115,9 @@ __device__ __forceinline__ void sw_stage_slice(const SwTab &T, int item, double 
 // Two kernels are launched back to back: this one handles the cloud-free tiles with the cloud code compiled out
 // (CLD = false: no spills, chunks of 4 g-points), sw_solve_cloudy_kernel the tiles flagged by sw_prep_kernel; a
 // wavefront whose tile belongs to the other kernel exits at once.
-template <bool CLD>
-__global__ void __launch_bounds__(64 * kSwWgWaves) __attribute__((amdgpu_waves_per_eu(4))) sw_solve_all_kernel(SwDev d, SwTab T, int tile0, int ntile) {   // tiles tile0 .. tile0 + ntile - 1 (one column chunk)
+// The body of sw_solve_all_kernel and sw_solve_all_dir_kernel: make_sink(slot, col) -> the flux sink of the lane.
+template <bool CLD, class MakeSink>
+__device__ __forceinline__ void sw_solve_all_body(const SwDev &d, const SwTab &T, int tile0, MakeSink make_sink) {
   // Launch order: BLOCKS of kSwGroupsPerBlock tile groups (128 tiles); within a block work items heaviest first, tile groups
   // fastest -- a block's prep rows (58 MB at 60 layers) are read by its 32 work items while they are still cached, however many
   // tiles the launch covers (a large chunk of a grid with both kinds of tiles: 2048 tiles are 0.94 GB of prep rows, re-read
@@ -147,8 +151,17 @@ __global__ void __launch_bounds__(64 * kSwWgWaves) __attribute__((amdgpu_waves_p
   const int col = tile * 64 + (threadIdx.x & 63);
   if (col >= d.ncol) return;
   double *scr = d.scratch + ((long)ctile * kSwNGpt + item_iw0(item)) * (long)F_NTOT * d.nlay * 64 + (threadIdx.x & 63) * 2;
-  SwPartSink sink = sw_part_sink(d, slot, col);
+  auto sink = make_sink(slot, col);
   sw_solve_item<CLD, kLdsK>(d, T, sh_exp, item, col, scr, 64, sink, sh_k);
+}
+template <bool CLD>
+__global__ void __launch_bounds__(64 * kSwWgWaves) __attribute__((amdgpu_waves_per_eu(4))) sw_solve_all_kernel(SwDev d, SwTab T, int tile0, int ntile) {   // tiles tile0 .. tile0 + ntile - 1 (one column chunk)
+  sw_solve_all_body<CLD>(d, T, tile0, [&](int slot, int col) { return sw_part_sink(d, slot, col); });
+}
+// The components path (rrtmg_hip_sw_fluxes_components): the same, plus the direct-beam sums into partdir (SwPartDirSink).
+template <bool CLD>
+__global__ void __launch_bounds__(64 * kSwWgWaves) __attribute__((amdgpu_waves_per_eu(4))) sw_solve_all_dir_kernel(SwDev d, SwTab T, int tile0, int ntile, double *partdir) {
+  sw_solve_all_body<CLD>(d, T, tile0, [&](int slot, int col) { return sw_part_dir_sink(d, partdir, slot, col); });
 }
 
 
@@ -160,6 +173,8 @@ __global__ void __launch_bounds__(64 * kSwWgWaves) __attribute__((amdgpu_waves_p
 // flux kernel added the pair slots of the round-1 kernel: bit-identical, half the partial-plane traffic.
 constexpr int kC4Waves = 8;
 constexpr int kC4GroupsPerBlock = 16;   // x 8 tiles = 128 tiles per block of the launch order
+// (sw_solve_cloudy_body below is a copy of this kernel's body for sw_solve_cloudy_dir_kernel: a change to the tile mapping,
+//  launch order or staging here is made there too -- tests/test_sw_components.py checks that the two bodies agree)
 __global__ void __launch_bounds__(64 * kC4Waves) __attribute__((amdgpu_waves_per_eu(2, 2))) sw_solve_cloudy_kernel(SwDev d, SwTab T, int tile0, int ntile) {
   const int nmine = d.tcnt[1];   // the cloudy tiles, compacted (SwDev::tlist); the workgroups with work first and dense: see sw_solve_all_kernel
   const int ngrp = (nmine + kC4Waves - 1) / kC4Waves;
@@ -183,6 +198,37 @@ __global__ void __launch_bounds__(64 * kC4Waves) __attribute__((amdgpu_waves_per
   double *scr = d.scratch + ((long)ctile * kSwNGpt + item_iw0(item)) * (long)F_NTOT * d.nlay * 64 + lane * 2;
   SwPartSink sink = sw_part_sink(d, slot, col);
   sw_solve_item<true, true>(d, T, sh_exp, item, col, scr, 64, sink, sh_k);
+}
+// The body of sw_solve_cloudy_dir_kernel: sw_solve_cloudy_kernel's with the sink made by make_sink (see sw_solve_all_body).
+// (sw_solve_cloudy_kernel keeps its own copy: routed through this template, its register assignment moved -- the same
+// instructions with permuted operands -- and its ISA is what the profiles and resource figures refer to.)
+template <class MakeSink>
+__device__ __forceinline__ void sw_solve_cloudy_body(const SwDev &d, const SwTab &T, int tile0, MakeSink make_sink) {
+  const int nmine = d.tcnt[1];   // the cloudy tiles, compacted (SwDev::tlist); the workgroups with work first and dense: see sw_solve_all_kernel
+  const int ngrp = (nmine + kC4Waves - 1) / kC4Waves;
+  const int q = blockIdx.x, per = kC4GroupsPerBlock * T.nitem, nfull = ngrp / kC4GroupsPerBlock;      // blocks of 128 tiles
+  if (q >= ngrp * T.nitem) return;
+  const int gpb = q < nfull * per ? kC4GroupsPerBlock : ngrp - nfull * kC4GroupsPerBlock, r = q < nfull * per ? q % per : q - nfull * per;
+  const int grp = (q < nfull * per ? q / per : nfull) * kC4GroupsPerBlock + r % gpb, first = grp * kC4Waves, k = r / gpb;
+  RRTMG_PROFILE_ONLY_ITEM(d, k)
+  const int id = T.sched[k], item = T.item[id], slot = id;      // one slot per chunk
+  __shared__ __attribute__((aligned(16))) double sh_k[kSwSlabMaxRows * 4];
+  sw_stage_slice(T, item, sh_k, 64 * kC4Waves);
+  __shared__ double sh_exp[kExpTblN];
+  for (int i = threadIdx.x; i < kExpTblN; i += 64 * kC4Waves) sh_exp[i] = T.t[T.exp_tbl + i];
+  __syncthreads();
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  if (first + wave >= nmine) return;
+  const int ctile = d.tlist[d.tcap + first + wave], tile = tile0 + ctile;
+  const int lane = threadIdx.x & 63;
+  const int col = tile * 64 + lane;
+  if (col >= d.ncol) return;
+  double *scr = d.scratch + ((long)ctile * kSwNGpt + item_iw0(item)) * (long)F_NTOT * d.nlay * 64 + lane * 2;
+  auto sink = make_sink(slot, col);
+  sw_solve_item<true, true>(d, T, sh_exp, item, col, scr, 64, sink, sh_k);
+}
+__global__ void __launch_bounds__(64 * kC4Waves) __attribute__((amdgpu_waves_per_eu(2, 2))) sw_solve_cloudy_dir_kernel(SwDev d, SwTab T, int tile0, int ntile, double *partdir) {
+  sw_solve_cloudy_body(d, T, tile0, [&](int slot, int col) { return sw_part_dir_sink(d, partdir, slot, col); });
 }
 
 // Spectral integration AND heating rates in one launch: a workgroup = one tile x kFluxLev layers; wave j sums the partial
@@ -213,6 +259,17 @@ __global__ void __launch_bounds__(64 * (kFluxLev + 1)) sw_fluxheat_kernel(SwDev 
     d.swhrc[o0] = (netc[j + 1][lane] - netc[j][lane]) * zdpgcp;
     d.swhr[o0] = (net[j + 1][lane] - net[j][lane]) * zdpgcp;
   }
+}
+
+// Components (rrtmg_hip_sw_fluxes_components), launched per column chunk behind sw_fluxheat_kernel (part and partdir are per
+// chunk): one thread per (column, interface level), the g-point sums of sw_components_level.  It reads the fd / cd partial
+// planes once more after sw_fluxheat_kernel has (~4 GB at 131 072 x 60, most of the components' +6 % on the call): folding
+// the components into sw_fluxheat_kernel's pass is where that cost would be recovered.
+constexpr int kCompLev = 4;
+__global__ void __launch_bounds__(64 * kCompLev) sw_components_kernel(SwDev d, SwTab T, int tile0, const double *partdir, SwCompOut o) {
+  const int tile = tile0 + blockIdx.x, col = tile * 64 + (threadIdx.x & 63), lev = blockIdx.y * kCompLev + (threadIdx.x >> 6);
+  if (col >= d.ncol || lev > d.nlay) return;
+  sw_components_level(d, T, partdir, o, col, lev, d.tile_cld[tile] != 0);
 }
 
 void free_sw_desc(rrtmg_ctx *ctx) {
@@ -318,8 +375,10 @@ static int sw_sorted_call(rrtmg_ctx *ctx, const rrtmg_sw_args *a) {
   return RRTMG_OK;
 }
 
-int sw_fluxes_impl(rrtmg_ctx *ctx, const rrtmg_sw_args *a) {
-  if (ctx->sw_ready && a && ctx->sort_columns && !ctx->sorting && a->memspace == 1 && a->icld != 0 && a->cldfr && a->ncol >= 128 && a->nlay > 0 && a->nlay <= 256 &&
+// cp: the components requested (at least one member set), or nullptr for the plain call.  A call with components is never
+// sorted: its outputs would need a scatter of their own.
+static int sw_fluxes_run(rrtmg_ctx *ctx, const rrtmg_sw_args *a, const rrtmg_sw_components *cp) {
+  if (!cp && ctx->sw_ready && a && ctx->sort_columns && !ctx->sorting && a->memspace == 1 && a->icld != 0 && a->cldfr && a->ncol >= 128 && a->nlay > 0 && a->nlay <= 256 &&
       !(a->mcica && a->irng != 0))
     return sw_sorted_call(ctx, a);
   if (!ctx->sw_ready) return ctx->fail(RRTMG_ERR_NOT_INITIALISED, "rrtmg_hip_sw_init has not been called");
@@ -407,13 +466,27 @@ int sw_fluxes_impl(rrtmg_ctx *ctx, const rrtmg_sw_args *a) {
   const int hint_cloudy = (ctx->hint[0].ntile == ntile && ctx->hint[0].nlay == L) ? ctx->hint[0].ncloudy : -1;
   int chunk_tiles = ctx->chunk_tiles;
   if (ctx->chunk_auto && L > 80 && hint_cloudy >= 0 && 10 * hint_cloudy >= 9 * ntile) chunk_tiles = 64;   // deep cloudy grid: DESIGN.md 5
-  chunk_tiles = ctx->plan_chunks(0, chunk_tiles, ntile, L, (clouds && !ctx->sorting) ? hint_cloudy : -1,   /* (a sorted grid keeps the small chunks: its tiles are segregated by kind, every chunk but one is of one kind) */ (size_t)kSwNGpt * F_NTOT * L * 64 * sizeof(double), "sw.w.scratch");
+  // (work space per tile of a mixed grid's chunk: the scratch slab, and with components the direct-beam partial planes -- half
+  //  again the size of `part`, about 4 GB more on a 2048-tile chunk at 60 layers)
+  const size_t tile_bytes = ((size_t)kSwNGpt * F_NTOT * L + (cp ? (size_t)kSwNSlot * 2 * (L + 1) : 0)) * 64 * sizeof(double);
+  chunk_tiles = ctx->plan_chunks(0, chunk_tiles, ntile, L, (clouds && !ctx->sorting) ? hint_cloudy : -1,   /* (a sorted grid keeps the small chunks: its tiles are segregated by kind, every chunk but one is of one kind) */ tile_bytes, "sw.w.scratch");
   const int ctile = ntile < chunk_tiles ? ntile : chunk_tiles;   // tiles per solve chunk
   int32_t *tlist = (int32_t *)ctx->buf("sw.w.tilelist", (size_t)(2 * ctile + 2) * 4);
   if (!tlist) ok = false;
   d.tcap = ctile; d.tlist = tlist; d.tcnt = tlist ? tlist + 2 * d.tcap : nullptr;
   d.scratch = wd("scratch", (size_t)ctile * kSwNGpt * F_NTOT * L * 64);
   d.part = wd("part", (size_t)kSwNSlot * 4 * (L + 1) * ctile * 64);
+  // components: the direct-beam partial planes [slot][2][nlay+1][pcols] (SwPartDirSink) and the outputs
+  double *partdir = cp ? wd("partdir", (size_t)kSwNSlot * 2 * (L + 1) * ctile * 64) : nullptr;
+  SwCompOut co{};
+  double *cpo[8] = {};   // the caller's arrays, in SwCompOut's order
+  double **coo[8] = {&co.dirdflx, &co.difdflx, &co.dirdnuv, &co.difdnuv, &co.dirdnir, &co.difdnir, &co.dirdflxc, &co.difdflxc};
+  if (cp) {
+    static const char *const names[8] = {"o.dirdflx", "o.difdflx", "o.dirdnuv", "o.difdnuv", "o.dirdnir", "o.difdnir", "o.dirdflxc", "o.difdflxc"};
+    double *const req[8] = {cp->dirdflx, cp->difdflx, cp->dirdnuv, cp->difdnuv, cp->dirdnir, cp->difdnir, cp->dirdflxc, cp->difdflxc};
+    for (int k = 0; k < 8; ++k)
+      if ((cpo[k] = req[k])) *coo[k] = a->memspace == 1 ? req[k] : wd(names[k], nl1);
+  }
   if (!svar_col.empty()) {   // per-column solar-variability multipliers (rare: facular/sunspot amplitudes != 1)
     double *p = wd("svarcol", svar_col.size());
     if (!ok) return ctx->status;
@@ -476,12 +549,15 @@ int sw_fluxes_impl(rrtmg_ctx *ctx, const rrtmg_sw_args *a) {
     const int ci = t0 / ctile;
     auto clear_variant = [&]() {
       (void)hipEventRecord(ctx->chunk_event(0, ci, 0), s);
-      hipLaunchKernelGGL(sw_solve_all_kernel<false>, dim3(ngrp * T.nitem), wg, 0, s, d, T, t0, nt);
+      if (partdir) hipLaunchKernelGGL(sw_solve_all_dir_kernel<false>, dim3(ngrp * T.nitem), wg, 0, s, d, T, t0, nt, partdir);
+      else hipLaunchKernelGGL(sw_solve_all_kernel<false>, dim3(ngrp * T.nitem), wg, 0, s, d, T, t0, nt);
       (void)hipEventRecord(ctx->chunk_event(0, ci, 1), s);
     };
     auto cloudy_variant = [&]() {
       (void)hipEventRecord(ctx->chunk_event(2, ci, 0), s);
-      hipLaunchKernelGGL(sw_solve_cloudy_kernel, dim3((nt + kC4Waves - 1) / kC4Waves * T.nitem), dim3(64 * kC4Waves), 0, s, d, T, t0, nt);
+      const dim3 gc((nt + kC4Waves - 1) / kC4Waves * T.nitem), bc(64 * kC4Waves);
+      if (partdir) hipLaunchKernelGGL(sw_solve_cloudy_dir_kernel, gc, bc, 0, s, d, T, t0, nt, partdir);
+      else hipLaunchKernelGGL(sw_solve_cloudy_kernel, gc, bc, 0, s, d, T, t0, nt);
       (void)hipEventRecord(ctx->chunk_event(2, ci, 1), s);
     };
     // the variant expected to find nothing goes first (order is speed only: each tile belongs to exactly one of them)
@@ -492,6 +568,7 @@ int sw_fluxes_impl(rrtmg_ctx *ctx, const rrtmg_sw_args *a) {
     else { clear_variant(); if (clouds) cloudy_variant(); }
     d.hint_out = t0 + ctile >= ntile ? (int32_t *)&ctx->hint[0].ncloudy : nullptr;
     hipLaunchKernelGGL(sw_fluxheat_kernel, dim3(nt, (L + kFluxLev) / kFluxLev), dim3(64 * (kFluxLev + 1)), 0, s, d, T, t0);
+    if (partdir) hipLaunchKernelGGL(sw_components_kernel, dim3(nt, (L + kCompLev) / kCompLev), dim3(64 * kCompLev), 0, s, d, T, t0, partdir, co);
   }
   ctx->hint[0].ntile = ntile; ctx->hint[0].nlay = L;
   ctx->ev_chunks[0] = (ntile + ctile - 1) / ctile; ctx->ev_chunks[2] = clouds ? ctx->ev_chunks[0] : 0;
@@ -501,9 +578,13 @@ int sw_fluxes_impl(rrtmg_ctx *ctx, const rrtmg_sw_args *a) {
   if (ctx->deferred && a->memspace == 1) { ctx->pending[0] = true; ctx->status = 0; return RRTMG_OK; }
   int herr = 0;
   if (a->memspace == 0) {
-    const OutCopy oc[6] = {{a->swuflx, d.swuflx, nl1}, {a->swdflx, d.swdflx, nl1}, {a->swuflxc, d.swuflxc, nl1}, {a->swdflxc, d.swdflxc, nl1},
-                           {a->swhr, d.swhr, nl}, {a->swhrc, d.swhrc, nl}};
-    rc = copy_out(ctx, s, oc, 6, d.err, &herr);
+    OutCopy oc[14] = {{a->swuflx, d.swuflx, nl1}, {a->swdflx, d.swdflx, nl1}, {a->swuflxc, d.swuflxc, nl1}, {a->swdflxc, d.swdflxc, nl1},
+                      {a->swhr, d.swhr, nl}, {a->swhrc, d.swhrc, nl}};
+    int nout = 6;
+    if (cp)   // the requested components, behind the same synchronise
+      for (int k = 0; k < 8; ++k)
+        if (cpo[k]) oc[nout++] = {cpo[k], *coo[k], nl1};
+    rc = copy_out(ctx, s, oc, nout, d.err, &herr);
     if (rc) return rc;
   } else {
     RRTMG_HIP_CHECK(ctx, hipMemcpyAsync(&herr, d.err, sizeof(int), hipMemcpyDeviceToHost, s));
@@ -513,5 +594,8 @@ int sw_fluxes_impl(rrtmg_ctx *ctx, const rrtmg_sw_args *a) {
   ctx->status = 0;
   return RRTMG_OK;
 }
+
+int sw_fluxes_impl(rrtmg_ctx *ctx, const rrtmg_sw_args *a) { return sw_fluxes_run(ctx, a, nullptr); }
+int sw_fluxes_components_impl(rrtmg_ctx *ctx, const rrtmg_sw_args *a, const rrtmg_sw_components *c) { return sw_fluxes_run(ctx, a, c); }
 
 }  // namespace rrtmg

@@ -895,6 +895,30 @@ RRTMG_HD SwPartSink sw_part_sink(const SwDev &d, int slot, int col) {
   return s;
 }
 
+// Flux sink of the components path (rrtmg_hip_sw_fluxes_components): SwPartSink, plus the weighted direct-beam sums of the
+// item (all sky, clear sky; pair sums first, as fd / cd) into partdir[slot][2][level][column].  kDirect is the trait that
+// makes sw_solve_thread emit them; a sink without it (SwPartSink) compiles to the path without them.  The clear-sky
+// variant writes plane 0 only (clear sky == total there).
+struct SwPartDirSink : SwPartSink {
+  static constexpr bool kDirect = true;
+  double *pdir, *pdirc;
+  RRTMG_HD void emit_dir(int lev, double dir, double dirc) {
+    const long o = (long)lev * N;
+    part_store(pdir + o, dir); part_store(pdirc + o, dirc);
+  }
+  RRTMG_HD void emit_dir_clear(int lev, double dir) { part_store(pdir + (long)lev * N, dir); }
+};
+RRTMG_HD SwPartDirSink sw_part_dir_sink(const SwDev &d, double *partdir, int slot, int col) {
+  SwPartDirSink s;
+  static_cast<SwPartSink &>(s) = sw_part_sink(d, slot, col);
+  const long N = d.pcols, L1 = d.nlay + 1;
+  s.pdir = partdir + (((long)slot * 2 + 0) * L1) * N + (col - d.col0);
+  s.pdirc = partdir + (((long)slot * 2 + 1) * L1) * N + (col - d.col0);
+  return s;
+}
+template <class S, class = void> struct sink_emits_direct { static constexpr bool value = false; };
+template <class S> struct sink_emits_direct<S, decltype((void)S::kDirect)> { static constexpr bool value = S::kDirect; };
+
 // per-thread constants of a (column, work item)
 template <int G> struct SwThreadCtx {
   int b, iw0, ig0, laytrop;
@@ -1129,6 +1153,28 @@ RRTMG_HD void sw_solve_thread(const SwDev &d, const SwTab &T, const double *exp_
     } else {
       sink.emit_clear(lev, sfu[0], sfd[0]);
     }
+    if constexpr (sink_emits_direct<Sink>::value) {
+      // direct beam at this interface (rrtmg_sw_spcvrt.f90:623-658, idelm = 1): the total-sky beam of a g-point is tdbt where
+      // its (sub-)column is cloudy and tdbtc elsewhere -- the choice fd makes above; formed from the live transmittances,
+      // summed as sfd / scd are
+      double sdir[G / 2], sdirc[G / 2];
+#pragma unroll
+      for (int h = 0; h < G / 2; ++h) { sdir[h] = 0.0; sdirc[h] = 0.0; }
+#pragma unroll
+      for (int g = 0; g < G; ++g) {
+        const double tb = (CLD && c.cloudy[g]) ? tdbt[g] : tdbtc[g];
+        const int h = g >> 1;
+#if defined(__HIP_DEVICE_COMPILE__)
+        sdir[h] = sdir[h] + tb; sdirc[h] = sdirc[h] + tdbtc[g];
+#else
+        sdir[h] = sdir[h] + zinc[g] * tb; sdirc[h] = sdirc[h] + zinc[g] * tdbtc[g];
+#endif
+      }
+      if constexpr (CLD && G == 4) sink.emit_dir(lev, sdir[0] + sdir[1], sdirc[0] + sdirc[1]);
+      else if constexpr (CLD) sink.emit_dir(lev, sdir[0], sdirc[0]);
+      else if constexpr (G == 4) sink.emit_dir_clear(lev, sdir[0] + sdir[1]);
+      else sink.emit_dir_clear(lev, sdir[0]);
+    }
     if (lev > 0) {
       const int l = lev - 1;
       auto down = [&](int g, const SwLayerOpt &oc, const SwLayerOpt &ot) {
@@ -1196,6 +1242,36 @@ RRTMG_HD void sw_flux_sums(const SwDev &d, const SwTab &T, int col, int lev, boo
     if (cld) { cu = cu + part_load(p + 2 * st); cd = cd + part_load(p + 3 * st); }
   }
   if (!cld) { cu = fu; cd = fd; }
+}
+// Outputs of rrtmg_hip_sw_fluxes_components, [nlay+1][ncol] like swdflx; a NULL member is not written.
+struct SwCompOut { double *dirdflx, *difdflx, *dirdnuv, *difdnuv, *dirdnir, *difdnir, *dirdflxc, *difdflxc; };
+// Direct / diffuse and UV-visible / near-IR split of one (column, level) from the partial planes of SwPartDirSink
+// (rrtmg_sw_rad.nomcica.f90:773-794).  fd and cd are summed in the order of sw_flux_sums, so difdflx == swdflx - dirdflx
+// to the bit.  Items are band-pure: the band of item c decides its bucket (bands 10-13 UV/vis, 1-9 and 14 near-IR, as
+// the albedo choice of sw_solve_thread).
+RRTMG_HD void sw_components_level(const SwDev &d, const SwTab &T, const double *partdir, const SwCompOut &o, int col, int lev, bool cld) {
+  const int L = d.nlay, P = d.pcols;
+  const long st = (long)(L + 1) * P, slot = 4 * st, dslot = 2 * st, off = (long)lev * P + (col - d.col0);
+  double fd = 0.0, cd = 0.0, dir = 0.0, dirc = 0.0, uvd = 0.0, uvdir = 0.0, nid = 0.0, nidir = 0.0;
+  for (int c = 0; c < T.nitem; ++c) {
+    const double *p = d.part + (long)c * slot + off, *q = partdir + (long)c * dslot + off;
+    const double f = part_load(p + st), b = part_load(q);
+    fd = fd + f; dir = dir + b;
+    if (cld) { cd = cd + part_load(p + 3 * st); dirc = dirc + part_load(q + st); }
+    const int band = item_band(T.item[c]);
+    if (band >= 9 && band <= 12) { uvd = uvd + f; uvdir = uvdir + b; }
+    else { nid = nid + f; nidir = nidir + b; }
+  }
+  if (!cld) { cd = fd; dirc = dir; }
+  const long i = (long)lev * d.ncol + col;
+  if (o.dirdflx) o.dirdflx[i] = dir;
+  if (o.difdflx) o.difdflx[i] = fd - dir;
+  if (o.dirdnuv) o.dirdnuv[i] = uvdir;
+  if (o.difdnuv) o.difdnuv[i] = uvd - uvdir;
+  if (o.dirdnir) o.dirdnir[i] = nidir;
+  if (o.difdnir) o.difdnir[i] = nid - nidir;
+  if (o.dirdflxc) o.dirdflxc[i] = dirc;
+  if (o.difdflxc) o.difdflxc[i] = cd - dirc;
 }
 RRTMG_HD void sw_flux_level(const SwDev &d, const SwTab &T, int col, int lev, bool cld) {
   double fu, fd, cu, cd;

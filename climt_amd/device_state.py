@@ -275,11 +275,20 @@ def shortwave_device_call(self, ds):
     hr, hrc = w("swhr", ml, ("mid_levels", "*"), "degK day^-1"), w("swhrc", ml, ("mid_levels", "*"), "degK day^-1")
     out = {k: v.ptr for k, v in fl.items()}
     out.update(swhr=hr.ptr, swhrc=hrc.ptr)
-    ds.ctx.sw_fluxes(inp, mcica=self._mcica, out=out, memspace=1)
+    comps = None
+    if getattr(self, "_flux_components", False):
+        from .rrtmg.shortwave import FLUX_COMPONENT_DIAGNOSTICS
+        comps = {c: w(c, il, ("interface_levels", "*"), "W m^-2") for c in FLUX_COMPONENT_DIAGNOSTICS.values()}
+    if comps:
+        ds.ctx.sw_fluxes(inp, mcica=self._mcica, out=out, memspace=1, components={c: q.ptr for c, q in comps.items()})
+    else:
+        ds.ctx.sw_fluxes(inp, mcica=self._mcica, out=out, memspace=1)
     diagnostics = {
         "upwelling_shortwave_flux_in_air": fl["swuflx"], "downwelling_shortwave_flux_in_air": fl["swdflx"],
         "upwelling_shortwave_flux_in_air_assuming_clear_sky": fl["swuflxc"], "downwelling_shortwave_flux_in_air_assuming_clear_sky": fl["swdflxc"],
         "air_temperature_tendency_from_shortwave_assuming_clear_sky": hrc, "air_temperature_tendency_from_shortwave": hr}
+    if comps:
+        diagnostics.update({k: comps[c] for k, c in FLUX_COMPONENT_DIAGNOSTICS.items()})
     return {"air_temperature": hr}, diagnostics
 
 

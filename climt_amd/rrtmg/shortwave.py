@@ -21,6 +21,19 @@ _CLD = ["mid_levels", "*", "num_shortwave_bands"]
 _AER = ["num_shortwave_bands", "mid_levels", "*"]
 
 
+# the diagnostics of RRTMGShortwave(flux_components=True) -> member of rrtmg_sw_components (include/rrtmg_hip.h)
+FLUX_COMPONENT_DIAGNOSTICS = {
+    "downwelling_direct_shortwave_flux_in_air": "dirdflx",
+    "downwelling_diffuse_shortwave_flux_in_air": "difdflx",
+    "downwelling_direct_shortwave_flux_in_air_assuming_clear_sky": "dirdflxc",
+    "downwelling_diffuse_shortwave_flux_in_air_assuming_clear_sky": "difdflxc",
+    "downwelling_direct_ultraviolet_and_visible_flux_in_air": "dirdnuv",
+    "downwelling_diffuse_ultraviolet_and_visible_flux_in_air": "difdnuv",
+    "downwelling_direct_near_infrared_flux_in_air": "dirdnir",
+    "downwelling_diffuse_near_infrared_flux_in_air": "difdnir",
+}
+
+
 class RRTMGShortwave(TendencyComponent):
     """The Rapid Radiative Transfer Model (RRTMG), shortwave, on AMD MI355X."""
 
@@ -75,13 +88,26 @@ class RRTMGShortwave(TendencyComponent):
         "air_temperature_tendency_from_shortwave": _prop(_ML, "degK day^-1"),
     }
 
+    @classmethod
+    def diagnostic_properties_for(cls, flux_components=False):
+        """The diagnostic_properties of an instance made with that `flux_components`: the class dict itself, or a new dict of
+        it plus the eight flux components (interface levels, W m^-2)."""
+        if not flux_components:
+            return cls.diagnostic_properties
+        return dict(cls.diagnostic_properties, **{k: _prop(_IL, "W m^-2") for k in FLUX_COMPONENT_DIAGNOSTICS})
+
     def __init__(self, cloud_overlap_method=None, cloud_optical_properties="liquid_and_ice_clouds",
                  cloud_ice_properties="ebert_curry_two", cloud_liquid_water_properties="radius_dependent_absorption",
                  solar_variability_method=0, use_solar_constant_from_fortran=False, ignore_day_of_year=False,
                  facular_sunspot_amplitude=None, solar_variability_by_band=None, aerosol_type="no_aerosol", mcica=False,
-                 random_number_generator="mersenne_twister", device=0, **kwargs):
-        """Same keyword arguments and defaults as climt.RRTMGShortwave (sw/component.py:179-194); `device`
-        (GPU ordinal) is the one addition."""
+                 random_number_generator="mersenne_twister", device=0, flux_components=False, **kwargs):
+        """Same keyword arguments and defaults as climt.RRTMGShortwave (sw/component.py:179-194); the additions are `device`
+        (GPU ordinal) and `flux_components`: True adds the downward flux split into direct and diffuse parts -- all bands,
+        UV/visible bands, near-IR bands, and all bands clear sky (FLUX_COMPONENT_DIAGNOSTICS) -- to this instance's
+        diagnostics; the class attributes are unchanged."""
+        self._flux_components = bool(flux_components)
+        if self._flux_components:
+            self.diagnostic_properties = self.diagnostic_properties_for(True)
         self._mcica = mcica
         if mcica:
             self._permute_seed = None
@@ -181,6 +207,10 @@ class RRTMGShortwave(TendencyComponent):
             swdflxc=diagnostics["downwelling_shortwave_flux_in_air_assuming_clear_sky"],
             swhrc=diagnostics["air_temperature_tendency_from_shortwave_assuming_clear_sky"])
         self._input_staging.wait()
-        self._ctx.sw_fluxes(inp, mcica=self._mcica, out=out)
+        if self._flux_components:
+            comps = {c: diagnostics[k] for k, c in FLUX_COMPONENT_DIAGNOSTICS.items()}
+            self._ctx.sw_fluxes(inp, mcica=self._mcica, out=out, components=comps)
+        else:
+            self._ctx.sw_fluxes(inp, mcica=self._mcica, out=out)
         diagnostics["air_temperature_tendency_from_shortwave"][:] = tendencies["air_temperature"]
         return tendencies, diagnostics

@@ -118,7 +118,8 @@ int rrtmg_hip_set_deferred(rrtmg_ctx *ctx, int on);
  * per column: a cloudy column's results are the same bits as without the sort; a cloud-free column that used to sit in a cloudy
  * tile now runs in the clear-sky variant, whose shortwave differs from the cloudy variant's clear-sky stream by ~1e-12 W m^-2 --
  * which is why this is not the default (tile-aligned shards == the whole grid bit for bit only when a column's variant is a
- * function of its tile).  Calls with the Mersenne twister (one positional stream) and host-pointer calls are not sorted. */
+ * function of its tile).  Calls with the Mersenne twister (one positional stream) and host-pointer calls are not sorted,
+ * nor are calls that request flux components (rrtmg_hip_sw_fluxes_components). */
 int rrtmg_hip_set_column_sort(rrtmg_ctx *ctx, int on);
 /* Duration (ms, HIP events recorded on the stream the kernel is launched on) of a solve kernel in the last completed call:
  * which = 0 -> sw_solve_all_kernel<false> (clear-sky tiles), 1 -> lw_solve_all_kernel<false,..>, 2 -> sw_solve_cloudy_kernel,
@@ -247,6 +248,30 @@ typedef struct rrtmg_sw_args {
 } rrtmg_sw_args;
 
 int rrtmg_hip_sw_fluxes(rrtmg_ctx *ctx, const rrtmg_sw_args *a);
+
+/* Shortwave flux COMPONENTS: the downward flux split into direct and diffuse parts, and into UV/visible (bands 10-13, the
+ * bands that take asdir / asdif) and near-IR (bands 1-9 and 14: aldir / aldif) parts -- the dirdflux, difdflux, dirdnuv,
+ * difdnuv, dirdnir, difdnir of rrtmg_sw_rad.nomcica.f90:773-794 / rrtmg_sw_rad.f90:798-819, which the reference computes and
+ * does not return.  Every member is [nlay+1][ncol], W m^-2, level 0 = surface like swdflx, in the memspace of the
+ * rrtmg_sw_args; NULL = not wanted.  Direct = the delta-scaled direct beam (idelm = 1); diffuse = total - direct:
+ *   dirdflx, difdflx    all sky, all bands (difdflx == swdflx - dirdflx, bit for bit)
+ *   dirdnuv, difdnuv    all sky, UV/visible bands;   dirdnir, difdnir   all sky, near-IR bands
+ *   dirdflxc, difdflxc  clear sky, all bands (difdflxc == swdflxc - dirdflxc)
+ * The versioned structs and RRTMG_HIP_ABI_VERSION are unchanged by this struct: it checks its own struct_size, and a caller
+ * probes for the feature by the presence of the symbol rrtmg_hip_sw_fluxes_components (dlsym). */
+typedef struct rrtmg_sw_components {
+  int32_t struct_size;                 /* sizeof(rrtmg_sw_components) of the caller's header: required */
+  int32_t reserved;                    /* 0 */
+  double *dirdflx, *difdflx;           /* [nlay+1][ncol], same memspace as the rrtmg_sw_args; NULL = not wanted */
+  double *dirdnuv, *difdnuv, *dirdnir, *difdnir;
+  double *dirdflxc, *difdflxc;
+} rrtmg_sw_components;
+/* rrtmg_hip_sw_fluxes plus the requested components.  c == NULL, or every member NULL, is exactly rrtmg_hip_sw_fluxes(ctx, a);
+ * a struct_size that is not sizeof(rrtmg_sw_components) is refused (RRTMG_ERR_ARG) before anything is enqueued.  The six
+ * outputs of the plain call are the same bits with or without components.  Host pointers: the components are downloaded
+ * behind the same synchronise as the six outputs; device pointers in deferred mode: the call returns once enqueued.  A call
+ * with components is never column-sorted (rrtmg_hip_set_column_sort). */
+int rrtmg_hip_sw_fluxes_components(rrtmg_ctx *ctx, const rrtmg_sw_args *a, const rrtmg_sw_components *c);
 
 /* ---- longwave ------------------------------------------------------------------------- */
 typedef struct rrtmg_lw_args {
