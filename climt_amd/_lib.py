@@ -49,6 +49,42 @@ class SwComponents(C.Structure):
     _fields_ = [("struct_size", _i32), ("reserved", _i32)] + [(n, _vp) for n in SW_COMPONENTS]
 
 
+# members of rrtmg_sw_band_fluxes / rrtmg_lw_band_fluxes (include/rrtmg_hip.h), in order, and their number of bands
+SW_BAND_FLUXES = ("up", "dn", "upc", "dnc", "dndir", "dndirc")
+LW_BAND_FLUXES = ("up", "dn", "upc", "dnc")
+SW_NBAND, LW_NBAND = 14, 16
+BAND_LEVELS = {"all": 0, "boundaries": 1}   # rows of a band array: every interface level, or surface and top
+
+
+class SwBandFluxes(C.Structure):
+    """mirrors `rrtmg_sw_band_fluxes` (include/rrtmg_hip.h), field for field"""
+    _fields_ = [("struct_size", _i32), ("levels", _i32)] + [(n, _vp) for n in SW_BAND_FLUXES]
+
+
+class LwBandFluxes(C.Structure):
+    """mirrors `rrtmg_lw_band_fluxes` (include/rrtmg_hip.h), field for field"""
+    _fields_ = [("struct_size", _i32), ("levels", _i32)] + [(n, _vp) for n in LW_BAND_FLUXES]
+
+
+def _band_struct(cls, names, nband, bands, band_levels, nlay, ncol):
+    """The filled struct of a `bands=` request (Context.sw_fluxes / lw_fluxes)."""
+    if band_levels not in BAND_LEVELS:
+        raise ValueError("band_levels %r: one of %s" % (band_levels, ", ".join(repr(k) for k in BAND_LEVELS)))
+    b = cls()
+    b.struct_size, b.levels = C.sizeof(cls), BAND_LEVELS[band_levels]
+    nrow = 2 if b.levels else nlay + 1
+    for k, v in bands.items():
+        if k not in names:
+            raise KeyError("unknown band flux %r (one of %s)" % (k, ", ".join(names)))
+        if isinstance(v, (int, np.integer)):
+            setattr(b, k, int(v))
+            continue
+        if not (isinstance(v, np.ndarray) and v.dtype == np.float64 and v.flags.c_contiguous and v.size == nband * nrow * ncol):
+            raise ValueError("band flux %r: the library writes it in place: a C-contiguous float64 array of %d x %d x %d" % (k, nband, nrow, ncol))
+        setattr(b, k, v.ctypes.data)
+    return b
+
+
 class LwArgs(C.Structure):
     _fields_ = ([(n, _i32) for n in ("ncol nlay memspace mcica icld idrv inflglw iceflglw liqflglw irng permuteseed "
                                      "shard_col0 shard_ncol struct_size").split()]
@@ -93,6 +129,9 @@ def load_library():
     lib.rrtmg_hip_sw_fluxes.argtypes = [_vp, C.POINTER(SwArgs)]
     lib.rrtmg_hip_lw_fluxes.argtypes = [_vp, C.POINTER(LwArgs)]
     lib.rrtmg_hip_sw_fluxes_components.argtypes = [_vp, C.POINTER(SwArgs), C.POINTER(SwComponents)]
+    lib.rrtmg_hip_sw_fluxes_bands.argtypes = [_vp, C.POINTER(SwArgs), C.POINTER(SwComponents), C.POINTER(SwBandFluxes)]
+    lib.rrtmg_hip_lw_fluxes_bands.argtypes = [_vp, C.POINTER(LwArgs), C.POINTER(LwBandFluxes)]
+    lib.rrtmg_hip_band_limits.argtypes = [C.c_int, _vp, _vp]
     lib.rrtmg_hip_get_table.restype = C.c_long
     lib.rrtmg_hip_get_table.argtypes = [_vp, C.c_char_p, _vp, C.c_long]
     lib.rrtmg_hip_lw_tables_synthetic.argtypes = [_vp]
@@ -151,6 +190,17 @@ def _locked(fn):
         with self._lock:
             return fn(self, *args, **kwargs)
     return wrapper
+
+
+def band_limits(spectrum):
+    """-> (lo, hi): the band limits in cm^-1 of "sw" (14 bands, RRTMG bands 16..29 in the order of the band arrays: band 29,
+    820-2600 cm^-1, is last) or "lw" (16 bands)."""
+    lib = load_library()
+    n = {"sw": SW_NBAND, "lw": LW_NBAND}[spectrum]
+    lo, hi = np.zeros(n), np.zeros(n)
+    if lib.rrtmg_hip_band_limits(0 if spectrum == "sw" else 1, lo.ctypes.data, hi.ctypes.data) != n:
+        raise RuntimeError("rrtmg_hip_band_limits(%s) failed" % spectrum)
+    return lo, hi
 
 
 class Context:
@@ -353,10 +403,11 @@ class Context:
                 setattr(a, f, arr.ctypes.data)
 
     @_locked
-    def sw_fluxes(self, inp, mcica=False, out=None, memspace=0, components=None):
+    def sw_fluxes(self, inp, mcica=False, out=None, memspace=0, components=None, bands=None, band_levels="all"):
         """`components`: None, or a dict SW_COMPONENTS name -> output (a C-contiguous float64 [nlay+1][ncol] array, or a device
         pointer with memspace=1) that the call fills as well (rrtmg_hip_sw_fluxes_components); the names left out are not
-        computed."""
+        computed.  `bands`: None, or a dict SW_BAND_FLUXES name -> output [14][nrow][ncol] in the same way
+        (rrtmg_hip_sw_fluxes_bands); `band_levels`: "all" (nrow = nlay+1) or "boundaries" (nrow = 2: surface, top)."""
         nlay, ncol = (inp["nlay"], inp["ncol"]) if memspace else inp["play"].shape
         a = SwArgs()
         a.struct_size = C.sizeof(SwArgs)
@@ -370,8 +421,12 @@ class Context:
         for k, _ in SW_OUT:
             v = out[k]
             setattr(a, k, int(v) if isinstance(v, (int, np.integer)) else v.ctypes.data)
-        if components is None:
+        if components is None and bands is None:
             self._ck(self.lib.rrtmg_hip_sw_fluxes(self.h, C.byref(a)))
+            return out
+        b = None if bands is None else _band_struct(SwBandFluxes, SW_BAND_FLUXES, SW_NBAND, bands, band_levels, nlay, ncol)
+        if components is None:
+            self._ck(self.lib.rrtmg_hip_sw_fluxes_bands(self.h, C.byref(a), None, C.byref(b)))
             return out
         c = SwComponents()
         c.struct_size = C.sizeof(SwComponents)
@@ -384,11 +439,17 @@ class Context:
             if not (isinstance(v, np.ndarray) and v.dtype == np.float64 and v.flags.c_contiguous and v.size == (nlay + 1) * ncol):
                 raise ValueError("component %r: the library writes it in place: a C-contiguous float64 array of %d x %d" % (k, nlay + 1, ncol))
             setattr(c, k, v.ctypes.data)
+        if b is not None:
+            self._ck(self.lib.rrtmg_hip_sw_fluxes_bands(self.h, C.byref(a), C.byref(c), C.byref(b)))
+            return out
         self._ck(self.lib.rrtmg_hip_sw_fluxes_components(self.h, C.byref(a), C.byref(c)))
         return out
 
     @_locked
-    def lw_fluxes(self, inp, mcica=False, out=None, memspace=0):
+    def lw_fluxes(self, inp, mcica=False, out=None, memspace=0, bands=None, band_levels="all"):
+        """`bands`: None, or a dict LW_BAND_FLUXES name -> output (a C-contiguous float64 [16][nrow][ncol] array, or a device
+        pointer with memspace=1) that the call fills as well (rrtmg_hip_lw_fluxes_bands); `band_levels`: "all" (nrow =
+        nlay+1) or "boundaries" (nrow = 2: surface, top)."""
         nlay, ncol = (inp["nlay"], inp["ncol"]) if memspace else inp["play"].shape
         a = LwArgs()
         a.struct_size = C.sizeof(LwArgs)
@@ -404,7 +465,11 @@ class Context:
         for k in out:
             v = out[k]
             setattr(a, k, int(v) if isinstance(v, (int, np.integer)) else v.ctypes.data)
-        self._ck(self.lib.rrtmg_hip_lw_fluxes(self.h, C.byref(a)))
+        if bands is None:
+            self._ck(self.lib.rrtmg_hip_lw_fluxes(self.h, C.byref(a)))
+            return out
+        b = _band_struct(LwBandFluxes, LW_BAND_FLUXES, LW_NBAND, bands, band_levels, nlay, ncol)
+        self._ck(self.lib.rrtmg_hip_lw_fluxes_bands(self.h, C.byref(a), C.byref(b)))
         return out
 
     @_locked

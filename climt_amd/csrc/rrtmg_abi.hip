@@ -72,7 +72,7 @@ int ctx_prepare_device(rrtmg_ctx *ctx) {
 int copy_out(rrtmg_ctx *ctx, hipStream_t s, const OutCopy *o, int count, int *herr_dev, int *herr_host) {
   // A destination that is page-locked memory the runtime knows (hipHostMalloc / hipHostRegister: the components' output pool
   // hands such arrays out) takes its copy directly; the others go through the staging buffer.
-  constexpr int kMaxOut = 16;
+  constexpr int kMaxOut = 24;   // shortwave: 6 outputs + 8 components + 6 band arrays
   if (count > kMaxOut) return ctx->fail(RRTMG_ERR_ARG, "copy_out: %d output arrays (at most %d)", count, kMaxOut);
   bool direct[kMaxOut];
   size_t total = 0;
@@ -478,6 +478,44 @@ int rrtmg_hip_sw_fluxes_components(rrtmg_ctx *ctx, const rrtmg_sw_args *a, const
   if (!c || !(c->dirdflx || c->difdflx || c->dirdnuv || c->difdnuv || c->dirdnir || c->difdnir || c->dirdflxc || c->difdflxc))
     return rrtmg_hip_sw_fluxes(ctx, a);
   return checked_call(ctx, a, "rrtmg_sw", [c](rrtmg_ctx *x, const rrtmg_sw_args *b) { return sw_fluxes_components_impl(x, b, c); });
+}
+// band fluxes: the struct checks (size, levels) come before anything is enqueued; a request without a member is the call without bands
+int rrtmg_hip_sw_fluxes_bands(rrtmg_ctx *ctx, const rrtmg_sw_args *a, const rrtmg_sw_components *c, const rrtmg_sw_band_fluxes *b) {
+  if (!ctx) return RRTMG_ERR_ARG;
+  if (b && (size_t)b->struct_size != sizeof(rrtmg_sw_band_fluxes))
+    return ctx->fail(RRTMG_ERR_ARG, "rrtmg_sw_band_fluxes: struct_size %d is not sizeof(rrtmg_sw_band_fluxes) = %zu of this library: set it to sizeof of the struct",
+                     (int)b->struct_size, sizeof(rrtmg_sw_band_fluxes));
+  if (b && b->levels != 0 && b->levels != 1) return ctx->fail(RRTMG_ERR_ARG, "rrtmg_sw_band_fluxes: levels %d is neither 0 (all interface levels) nor 1 (surface and top)", (int)b->levels);
+  if (!b || !(b->up || b->dn || b->upc || b->dnc || b->dndir || b->dndirc)) return rrtmg_hip_sw_fluxes_components(ctx, a, c);
+  if (c && (size_t)c->struct_size != sizeof(rrtmg_sw_components))
+    return ctx->fail(RRTMG_ERR_ARG, "rrtmg_sw_components: struct_size %d is not sizeof(rrtmg_sw_components) = %zu of this library: set it to sizeof of the struct",
+                     (int)c->struct_size, sizeof(rrtmg_sw_components));
+  if (c && !(c->dirdflx || c->difdflx || c->dirdnuv || c->difdnuv || c->dirdnir || c->difdnir || c->dirdflxc || c->difdflxc)) c = nullptr;
+  return checked_call(ctx, a, "rrtmg_sw", [c, b](rrtmg_ctx *x, const rrtmg_sw_args *y) { return sw_fluxes_bands_impl(x, y, c, b); });
+}
+int rrtmg_hip_lw_fluxes_bands(rrtmg_ctx *ctx, const rrtmg_lw_args *a, const rrtmg_lw_band_fluxes *b) {
+  if (!ctx) return RRTMG_ERR_ARG;
+  if (b && (size_t)b->struct_size != sizeof(rrtmg_lw_band_fluxes))
+    return ctx->fail(RRTMG_ERR_ARG, "rrtmg_lw_band_fluxes: struct_size %d is not sizeof(rrtmg_lw_band_fluxes) = %zu of this library: set it to sizeof of the struct",
+                     (int)b->struct_size, sizeof(rrtmg_lw_band_fluxes));
+  if (b && b->levels != 0 && b->levels != 1) return ctx->fail(RRTMG_ERR_ARG, "rrtmg_lw_band_fluxes: levels %d is neither 0 (all interface levels) nor 1 (surface and top)", (int)b->levels);
+  if (!b || !(b->up || b->dn || b->upc || b->dnc)) return rrtmg_hip_lw_fluxes(ctx, a);
+  return checked_call(ctx, a, "rrtmg_lw", [b](rrtmg_ctx *x, const rrtmg_lw_args *y) { return lw_fluxes_bands_impl(x, y, b); });
+}
+// band limits, cm^-1: shortwave bands 16..29 (wavenum1 / wavenum2 of rrtmg_sw_init.f90, band 29 last), longwave bands 1..16
+// (rrtmg_lw_init.f90:196-204; hi - lo == delwave)
+int rrtmg_hip_band_limits(int spectrum, double *lo, double *hi) {
+  static const double sw_lo[14] = {2600., 3250., 4000., 4650., 5150., 6150., 7700., 8050., 12850., 16000., 22650., 29000., 38000., 820.};
+  static const double sw_hi[14] = {3250., 4000., 4650., 5150., 6150., 7700., 8050., 12850., 16000., 22650., 29000., 38000., 50000., 2600.};
+  static const double lw_lo[16] = {10., 350., 500., 630., 700., 820., 980., 1080., 1180., 1390., 1480., 1800., 2080., 2250., 2380., 2600.};
+  static const double lw_hi[16] = {350., 500., 630., 700., 820., 980., 1080., 1180., 1390., 1480., 1800., 2080., 2250., 2380., 2600., 3250.};
+  if (spectrum != 0 && spectrum != 1) return -1;
+  const int n = spectrum ? 16 : 14;
+  for (int i = 0; i < n; ++i) {
+    if (lo) lo[i] = spectrum ? lw_lo[i] : sw_lo[i];
+    if (hi) hi[i] = spectrum ? lw_hi[i] : sw_hi[i];
+  }
+  return n;
 }
 int rrtmg_hip_abi_version(void) { return RRTMG_HIP_ABI_VERSION; }
 

@@ -198,7 +198,9 @@ void free_sw_desc(rrtmg_ctx *ctx);
 void free_lw_desc(rrtmg_ctx *ctx);
 int sw_fluxes_impl(rrtmg_ctx *ctx, const rrtmg_sw_args *a);
 int sw_fluxes_components_impl(rrtmg_ctx *ctx, const rrtmg_sw_args *a, const rrtmg_sw_components *c);
+int sw_fluxes_bands_impl(rrtmg_ctx *ctx, const rrtmg_sw_args *a, const rrtmg_sw_components *c, const rrtmg_sw_band_fluxes *b);
 int lw_fluxes_impl(rrtmg_ctx *ctx, const rrtmg_lw_args *a);
+int lw_fluxes_bands_impl(rrtmg_ctx *ctx, const rrtmg_lw_args *a, const rrtmg_lw_band_fluxes *b);
 int sw_init_impl(rrtmg_ctx *ctx, double cpdair, const char *blob);
 int lw_init_impl(rrtmg_ctx *ctx, double cpdair, const char *blob);
 int mcica_mask_impl(rrtmg_ctx *ctx, int which, int ncol, int nlay, int icld, int permuteseed, int irng,

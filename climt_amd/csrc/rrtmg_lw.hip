@@ -162,6 +162,17 @@ __global__ void __launch_bounds__(64 * (kFluxLev + 1)) lw_fluxheat_kernel(LwDev 
   }
 }
 
+// Band fluxes (rrtmg_hip_lw_fluxes_bands), launched per column chunk behind lw_fluxheat_kernel: one thread per (column,
+// level), lane = column, the per-band sums of lw_band_level (see sw_bandflux_kernel).  levels = 0: every interface level;
+// 1: a workgroup of two waves, row 0 = surface, row 1 = top.
+constexpr int kBandLev = 4;
+__global__ void __launch_bounds__(64 * kBandLev) lw_bandflux_kernel(LwDev d, LwTab T, int tile0, LwBandOut o, int levels) {
+  const int tile = tile0 + blockIdx.x, col = tile * 64 + (threadIdx.x & 63), row = blockIdx.y * kBandLev + (threadIdx.x >> 6);
+  const int lev = levels ? (row ? d.nlay : 0) : row;
+  if (col >= d.ncol || row > (levels ? 1 : d.nlay)) return;
+  lw_band_level(d, T, o, col, lev, row, levels ? 2 : d.nlay + 1, d.tile_cld[tile] != 0);
+}
+
 void free_lw_desc(rrtmg_ctx *ctx) {
   delete (LwTab *)ctx->lw_desc;
   ctx->lw_desc = nullptr;
@@ -189,6 +200,7 @@ int lw_init_impl(rrtmg_ctx *ctx, double cpdair, const char *blob_path) {
   return RRTMG_OK;
 }
 
+static int lw_fluxes_run(rrtmg_ctx *ctx, const rrtmg_lw_args *a, const rrtmg_lw_band_fluxes *bp);
 // the call on an internal copy of its inputs, cloud-free columns first (rrtmg_sort.h; see sw_sorted_call)
 static int lw_sorted_call(rrtmg_ctx *ctx, const rrtmg_lw_args *a) {
   int rc = ctx_prepare_device(ctx);
@@ -220,7 +232,7 @@ static int lw_sorted_call(rrtmg_ctx *ctx, const rrtmg_lw_args *a) {
   if (dr && (!a->duflx_dt || !a->duflxc_dt)) return ctx->fail(RRTMG_ERR_ARG, "idrv=1 needs duflx_dt/duflxc_dt");
   b.uflx = o[0]; b.dflx = o[1]; b.hr = o[2]; b.uflxc = o[3]; b.dflxc = o[4]; b.hrc = o[5]; b.duflx_dt = o[6]; b.duflxc_dt = o[7];
   ctx->sorting = true;
-  rc = lw_fluxes_impl(ctx, &b);
+  rc = lw_fluxes_run(ctx, &b, nullptr);
   ctx->sorting = false;
   if (rc) return rc;
   double *u[8] = {a->uflx, a->dflx, a->hr, a->uflxc, a->dflxc, a->hrc, a->duflx_dt, a->duflxc_dt};
@@ -230,8 +242,10 @@ static int lw_sorted_call(rrtmg_ctx *ctx, const rrtmg_lw_args *a) {
   return RRTMG_OK;
 }
 
-int lw_fluxes_impl(rrtmg_ctx *ctx, const rrtmg_lw_args *a) {
-  if (ctx->lw_ready && a && ctx->sort_columns && !ctx->sorting && a->memspace == 1 && a->icld != 0 && a->cldfr && a->ncol >= 128 && a->nlay > 0 && a->nlay <= 256 &&
+// bp: the band fluxes requested (at least one member set, levels 0 or 1), or nullptr for the plain call.  A call with bands
+// is never sorted: its outputs would need a scatter of their own.
+static int lw_fluxes_run(rrtmg_ctx *ctx, const rrtmg_lw_args *a, const rrtmg_lw_band_fluxes *bp) {
+  if (!bp && ctx->lw_ready && a && ctx->sort_columns && !ctx->sorting && a->memspace == 1 && a->icld != 0 && a->cldfr && a->ncol >= 128 && a->nlay > 0 && a->nlay <= 256 &&
       !(a->mcica && a->irng != 0))
     return lw_sorted_call(ctx, a);
   if (!ctx->lw_ready) return ctx->fail(RRTMG_ERR_NOT_INITIALISED, "rrtmg_hip_lw_init has not been called");
@@ -320,6 +334,18 @@ int lw_fluxes_impl(rrtmg_ctx *ctx, const rrtmg_lw_args *a) {
     d.dflxc = wd("o.dflxc", nl1); d.hrc = wd("o.hrc", nl);
     if (d.idrv) { d.duflx_dt = wd("o.du", nl1); d.duflxc_dt = wd("o.duc", nl1); }
   }
+  // band fluxes: [16][nrow][ncol] per requested member
+  LwBandOut bo{};
+  double *bpo[4] = {};   // the caller's arrays, in LwBandOut's order
+  double **boo[4] = {&bo.up, &bo.dn, &bo.upc, &bo.dnc};
+  const int brow = bp && bp->levels ? 2 : L + 1;
+  const size_t nband = (size_t)kLwNBand * brow * N;
+  if (bp) {
+    static const char *const names[4] = {"ob.up", "ob.dn", "ob.upc", "ob.dnc"};
+    double *const req[4] = {bp->up, bp->dn, bp->upc, bp->dnc};
+    for (int k = 0; k < 4; ++k)
+      if ((bpo[k] = req[k])) *boo[k] = a->memspace == 1 ? req[k] : wd(names[k], nband);
+  }
   if (!ok) return ctx->status;
 #ifdef RRTMG_PROFILE
   d.phase = (unsigned long long *)ctx->buf("lw.w.phase", 16 * 8);
@@ -391,6 +417,10 @@ int lw_fluxes_impl(rrtmg_ctx *ctx, const rrtmg_lw_args *a) {
     else { clear_variant(); if (clouds) cloudy_variant(); }
     d.hint_out = t0 + ctile >= ntile ? (int32_t *)&ctx->hint[1].ncloudy : nullptr;
     hipLaunchKernelGGL(lw_fluxheat_kernel, dim3(nt, (L + kFluxLev) / kFluxLev), dim3(64 * (kFluxLev + 1)), 0, s, d, T, t0);
+    if (bp) {
+      if (bp->levels) hipLaunchKernelGGL(lw_bandflux_kernel, dim3(nt, 1), dim3(64 * 2), 0, s, d, T, t0, bo, 1);
+      else hipLaunchKernelGGL(lw_bandflux_kernel, dim3(nt, (L + kBandLev) / kBandLev), dim3(64 * kBandLev), 0, s, d, T, t0, bo, 0);
+    }
   }
   ctx->hint[1].ntile = ntile; ctx->hint[1].nlay = L;
   ctx->ev_chunks[1] = (ntile + ctile - 1) / ctile; ctx->ev_chunks[3] = clouds ? ctx->ev_chunks[1] : 0;
@@ -413,9 +443,13 @@ int lw_fluxes_impl(rrtmg_ctx *ctx, const rrtmg_lw_args *a) {
   if (ctx->deferred && a->memspace == 1) { ctx->pending[1] = true; ctx->status = 0; return RRTMG_OK; }
   int herr = 0;
   if (a->memspace == 0) {
-    const OutCopy oc[8] = {{a->uflx, d.uflx, nl1}, {a->dflx, d.dflx, nl1}, {a->uflxc, d.uflxc, nl1}, {a->dflxc, d.dflxc, nl1},
-                           {a->hr, d.hr, nl}, {a->hrc, d.hrc, nl}, {a->duflx_dt, d.duflx_dt, nl1}, {a->duflxc_dt, d.duflxc_dt, nl1}};
-    rc = copy_out(ctx, s, oc, d.idrv ? 8 : 6, d.err, &herr);
+    OutCopy oc[12] = {{a->uflx, d.uflx, nl1}, {a->dflx, d.dflx, nl1}, {a->uflxc, d.uflxc, nl1}, {a->dflxc, d.dflxc, nl1},
+                      {a->hr, d.hr, nl}, {a->hrc, d.hrc, nl}, {a->duflx_dt, d.duflx_dt, nl1}, {a->duflxc_dt, d.duflxc_dt, nl1}};
+    int nout = d.idrv ? 8 : 6;
+    if (bp)   // the requested band fluxes, behind the same synchronise
+      for (int k = 0; k < 4; ++k)
+        if (bpo[k]) oc[nout++] = {bpo[k], *boo[k], nband};
+    rc = copy_out(ctx, s, oc, nout, d.err, &herr);
     if (rc) return rc;
   } else {
     RRTMG_HIP_CHECK(ctx, hipMemcpyAsync(&herr, d.err, sizeof(int), hipMemcpyDeviceToHost, s));
@@ -425,5 +459,8 @@ int lw_fluxes_impl(rrtmg_ctx *ctx, const rrtmg_lw_args *a) {
   ctx->status = 0;
   return RRTMG_OK;
 }
+
+int lw_fluxes_impl(rrtmg_ctx *ctx, const rrtmg_lw_args *a) { return lw_fluxes_run(ctx, a, nullptr); }
+int lw_fluxes_bands_impl(rrtmg_ctx *ctx, const rrtmg_lw_args *a, const rrtmg_lw_band_fluxes *b) { return lw_fluxes_run(ctx, a, b); }
 
 }  // namespace rrtmg

@@ -1381,6 +1381,35 @@ RRTMG_HD void lw_flux_sums(const LwDev &d, int col, int lev, int nparts, bool cl
   out[0] = t0 * d.fluxfac; out[1] = t1 * d.fluxfac; out[2] = t2 * d.fluxfac; out[3] = t3 * d.fluxfac;
   out[4] = t4 * d.fluxfac; out[5] = t5 * d.fluxfac;
 }
+// Outputs of rrtmg_hip_lw_fluxes_bands, [16][nrow][ncol] (nrow = nlay+1, or 2: surface and top); a NULL member is not
+// written and its planes are not read.
+struct LwBandOut { double *up, *dn, *upc, *dnc; };
+// Fluxes BY BAND of one (column, level) -> row `row` of the outputs: the walk of lw_flux_sums over the items, with the sums
+// started at 0.0 for every band, and scaled by fluxfac and stored where the band changes (items are band-pure and
+// band-contiguous in slot order: build_lw_tab checks it).  cld = false: see lw_flux_sums.
+RRTMG_HD void lw_band_level(const LwDev &d, const LwTab &T, const LwBandOut &o, int col, int lev, int row, int nrow, bool cld) {
+  const int L = d.nlay;
+  const int nk = d.idrv ? 6 : 4;
+  const long st = (long)(L + 1) * d.pcols;
+  const bool ru = o.up || (o.upc && !cld), rd = o.dn || (o.dnc && !cld), rcu = o.upc && cld, rcd = o.dnc && cld;
+  double t0 = 0.0, t1 = 0.0, t2 = 0.0, t3 = 0.0;
+  for (int iw = 0; iw < T.nitem; ++iw) {
+    const double *p = d.part + ((long)iw * nk * (L + 1) + lev) * d.pcols + (col - d.col0);
+    if (ru) t0 = t0 + part_load(p);
+    if (rd) t1 = t1 + part_load(p + st);
+    if (rcu) t2 = t2 + part_load(p + 2 * st);
+    if (rcd) t3 = t3 + part_load(p + 3 * st);
+    const int band = T.item[iw] & 0xff;
+    if (iw + 1 < T.nitem && (T.item[iw + 1] & 0xff) == band) continue;
+    if (!cld) { t2 = t0; t3 = t1; }
+    const long i = ((long)band * nrow + row) * d.ncol + col;
+    if (o.up) o.up[i] = t0 * d.fluxfac;
+    if (o.dn) o.dn[i] = t1 * d.fluxfac;
+    if (o.upc) o.upc[i] = t2 * d.fluxfac;
+    if (o.dnc) o.dnc[i] = t3 * d.fluxfac;
+    t0 = 0.0; t1 = 0.0; t2 = 0.0; t3 = 0.0;
+  }
+}
 RRTMG_HD void lw_flux_level(const LwDev &d, const LwTab &T, int col, int lev, int nparts, bool cld) {
   (void)T;
   double f[6];

@@ -18,6 +18,8 @@
 //   With components requested (rrtmg_hip_sw_fluxes_components): the solve variants sw_solve_all_dir_kernel<false> and
 //   sw_solve_cloudy_dir_kernel instead, which also write the direct-beam partial planes, and sw_components_kernel
 //   <<<(tiles, levels/4), 4 waves>>> behind sw_fluxheat_kernel: direct / diffuse, UV-visible / near-IR sums per interface
+//   With band fluxes requested (rrtmg_hip_sw_fluxes_bands): sw_bandflux_kernel <<<(tiles, levels/4), 4 waves>>> (or the two
+//   boundary levels only) behind them, and the *_dir solve variants where a direct-beam member is set
 #include <future>
 
 #include "rrtmg_ctx.h"
@@ -272,6 +274,18 @@ __global__ void __launch_bounds__(64 * kCompLev) sw_components_kernel(SwDev d, S
   sw_components_level(d, T, partdir, o, col, lev, d.tile_cld[tile] != 0);
 }
 
+// Band fluxes (rrtmg_hip_sw_fluxes_bands), launched per column chunk behind sw_fluxheat_kernel (and sw_components_kernel):
+// one thread per (column, level), lane = column, the per-band sums of sw_band_level.  levels = 0: every interface level, row
+// = level; 1: a workgroup of two waves, row 0 = surface, row 1 = top.  A streaming kernel: it reads the requested partial
+// planes once more (see sw_components_kernel) and writes 14 rows per member.
+constexpr int kBandLev = 4;
+__global__ void __launch_bounds__(64 * kBandLev) sw_bandflux_kernel(SwDev d, SwTab T, int tile0, const double *partdir, SwBandOut o, int levels) {
+  const int tile = tile0 + blockIdx.x, col = tile * 64 + (threadIdx.x & 63), row = blockIdx.y * kBandLev + (threadIdx.x >> 6);
+  const int lev = levels ? (row ? d.nlay : 0) : row;
+  if (col >= d.ncol || row > (levels ? 1 : d.nlay)) return;
+  sw_band_level(d, T, partdir, o, col, lev, row, levels ? 2 : d.nlay + 1, d.tile_cld[tile] != 0);
+}
+
 void free_sw_desc(rrtmg_ctx *ctx) {
   delete (SwTab *)ctx->sw_desc;
   ctx->sw_desc = nullptr;
@@ -375,10 +389,11 @@ static int sw_sorted_call(rrtmg_ctx *ctx, const rrtmg_sw_args *a) {
   return RRTMG_OK;
 }
 
-// cp: the components requested (at least one member set), or nullptr for the plain call.  A call with components is never
-// sorted: its outputs would need a scatter of their own.
-static int sw_fluxes_run(rrtmg_ctx *ctx, const rrtmg_sw_args *a, const rrtmg_sw_components *cp) {
-  if (!cp && ctx->sw_ready && a && ctx->sort_columns && !ctx->sorting && a->memspace == 1 && a->icld != 0 && a->cldfr && a->ncol >= 128 && a->nlay > 0 && a->nlay <= 256 &&
+// cp: the components requested (at least one member set), or nullptr; bp: the band fluxes requested (at least one member
+// set, levels 0 or 1), or nullptr; both nullptr: the plain call.  A call with components or bands is never sorted: its
+// outputs would need a scatter of their own.
+static int sw_fluxes_run(rrtmg_ctx *ctx, const rrtmg_sw_args *a, const rrtmg_sw_components *cp, const rrtmg_sw_band_fluxes *bp) {
+  if (!cp && !bp && ctx->sw_ready && a && ctx->sort_columns && !ctx->sorting && a->memspace == 1 && a->icld != 0 && a->cldfr && a->ncol >= 128 && a->nlay > 0 && a->nlay <= 256 &&
       !(a->mcica && a->irng != 0))
     return sw_sorted_call(ctx, a);
   if (!ctx->sw_ready) return ctx->fail(RRTMG_ERR_NOT_INITIALISED, "rrtmg_hip_sw_init has not been called");
@@ -468,7 +483,8 @@ static int sw_fluxes_run(rrtmg_ctx *ctx, const rrtmg_sw_args *a, const rrtmg_sw_
   if (ctx->chunk_auto && L > 80 && hint_cloudy >= 0 && 10 * hint_cloudy >= 9 * ntile) chunk_tiles = 64;   // deep cloudy grid: DESIGN.md 5
   // (work space per tile of a mixed grid's chunk: the scratch slab, and with components the direct-beam partial planes -- half
   //  again the size of `part`, about 4 GB more on a 2048-tile chunk at 60 layers)
-  const size_t tile_bytes = ((size_t)kSwNGpt * F_NTOT * L + (cp ? (size_t)kSwNSlot * 2 * (L + 1) : 0)) * 64 * sizeof(double);
+  const bool need_dir = cp || (bp && (bp->dndir || bp->dndirc));   // the *_dir solve variants and their partdir planes
+  const size_t tile_bytes = ((size_t)kSwNGpt * F_NTOT * L + (need_dir ? (size_t)kSwNSlot * 2 * (L + 1) : 0)) * 64 * sizeof(double);
   chunk_tiles = ctx->plan_chunks(0, chunk_tiles, ntile, L, (clouds && !ctx->sorting) ? hint_cloudy : -1,   /* (a sorted grid keeps the small chunks: its tiles are segregated by kind, every chunk but one is of one kind) */ tile_bytes, "sw.w.scratch");
   const int ctile = ntile < chunk_tiles ? ntile : chunk_tiles;   // tiles per solve chunk
   int32_t *tlist = (int32_t *)ctx->buf("sw.w.tilelist", (size_t)(2 * ctile + 2) * 4);
@@ -477,7 +493,7 @@ static int sw_fluxes_run(rrtmg_ctx *ctx, const rrtmg_sw_args *a, const rrtmg_sw_
   d.scratch = wd("scratch", (size_t)ctile * kSwNGpt * F_NTOT * L * 64);
   d.part = wd("part", (size_t)kSwNSlot * 4 * (L + 1) * ctile * 64);
   // components: the direct-beam partial planes [slot][2][nlay+1][pcols] (SwPartDirSink) and the outputs
-  double *partdir = cp ? wd("partdir", (size_t)kSwNSlot * 2 * (L + 1) * ctile * 64) : nullptr;
+  double *partdir = need_dir ? wd("partdir", (size_t)kSwNSlot * 2 * (L + 1) * ctile * 64) : nullptr;
   SwCompOut co{};
   double *cpo[8] = {};   // the caller's arrays, in SwCompOut's order
   double **coo[8] = {&co.dirdflx, &co.difdflx, &co.dirdnuv, &co.difdnuv, &co.dirdnir, &co.difdnir, &co.dirdflxc, &co.difdflxc};
@@ -486,6 +502,18 @@ static int sw_fluxes_run(rrtmg_ctx *ctx, const rrtmg_sw_args *a, const rrtmg_sw_
     double *const req[8] = {cp->dirdflx, cp->difdflx, cp->dirdnuv, cp->difdnuv, cp->dirdnir, cp->difdnir, cp->dirdflxc, cp->difdflxc};
     for (int k = 0; k < 8; ++k)
       if ((cpo[k] = req[k])) *coo[k] = a->memspace == 1 ? req[k] : wd(names[k], nl1);
+  }
+  // band fluxes: [14][nrow][ncol] per requested member
+  SwBandOut bo{};
+  double *bpo[6] = {};   // the caller's arrays, in SwBandOut's order
+  double **boo[6] = {&bo.up, &bo.dn, &bo.upc, &bo.dnc, &bo.dndir, &bo.dndirc};
+  const int brow = bp && bp->levels ? 2 : L + 1;
+  const size_t nband = (size_t)kSwNBand * brow * N;
+  if (bp) {
+    static const char *const names[6] = {"ob.up", "ob.dn", "ob.upc", "ob.dnc", "ob.dndir", "ob.dndirc"};
+    double *const req[6] = {bp->up, bp->dn, bp->upc, bp->dnc, bp->dndir, bp->dndirc};
+    for (int k = 0; k < 6; ++k)
+      if ((bpo[k] = req[k])) *boo[k] = a->memspace == 1 ? req[k] : wd(names[k], nband);
   }
   if (!svar_col.empty()) {   // per-column solar-variability multipliers (rare: facular/sunspot amplitudes != 1)
     double *p = wd("svarcol", svar_col.size());
@@ -568,7 +596,11 @@ static int sw_fluxes_run(rrtmg_ctx *ctx, const rrtmg_sw_args *a, const rrtmg_sw_
     else { clear_variant(); if (clouds) cloudy_variant(); }
     d.hint_out = t0 + ctile >= ntile ? (int32_t *)&ctx->hint[0].ncloudy : nullptr;
     hipLaunchKernelGGL(sw_fluxheat_kernel, dim3(nt, (L + kFluxLev) / kFluxLev), dim3(64 * (kFluxLev + 1)), 0, s, d, T, t0);
-    if (partdir) hipLaunchKernelGGL(sw_components_kernel, dim3(nt, (L + kCompLev) / kCompLev), dim3(64 * kCompLev), 0, s, d, T, t0, partdir, co);
+    if (cp) hipLaunchKernelGGL(sw_components_kernel, dim3(nt, (L + kCompLev) / kCompLev), dim3(64 * kCompLev), 0, s, d, T, t0, partdir, co);
+    if (bp) {
+      if (bp->levels) hipLaunchKernelGGL(sw_bandflux_kernel, dim3(nt, 1), dim3(64 * 2), 0, s, d, T, t0, partdir, bo, 1);
+      else hipLaunchKernelGGL(sw_bandflux_kernel, dim3(nt, (L + kBandLev) / kBandLev), dim3(64 * kBandLev), 0, s, d, T, t0, partdir, bo, 0);
+    }
   }
   ctx->hint[0].ntile = ntile; ctx->hint[0].nlay = L;
   ctx->ev_chunks[0] = (ntile + ctile - 1) / ctile; ctx->ev_chunks[2] = clouds ? ctx->ev_chunks[0] : 0;
@@ -578,12 +610,15 @@ static int sw_fluxes_run(rrtmg_ctx *ctx, const rrtmg_sw_args *a, const rrtmg_sw_
   if (ctx->deferred && a->memspace == 1) { ctx->pending[0] = true; ctx->status = 0; return RRTMG_OK; }
   int herr = 0;
   if (a->memspace == 0) {
-    OutCopy oc[14] = {{a->swuflx, d.swuflx, nl1}, {a->swdflx, d.swdflx, nl1}, {a->swuflxc, d.swuflxc, nl1}, {a->swdflxc, d.swdflxc, nl1},
+    OutCopy oc[20] = {{a->swuflx, d.swuflx, nl1}, {a->swdflx, d.swdflx, nl1}, {a->swuflxc, d.swuflxc, nl1}, {a->swdflxc, d.swdflxc, nl1},
                       {a->swhr, d.swhr, nl}, {a->swhrc, d.swhrc, nl}};
     int nout = 6;
     if (cp)   // the requested components, behind the same synchronise
       for (int k = 0; k < 8; ++k)
         if (cpo[k]) oc[nout++] = {cpo[k], *coo[k], nl1};
+    if (bp)
+      for (int k = 0; k < 6; ++k)
+        if (bpo[k]) oc[nout++] = {bpo[k], *boo[k], nband};
     rc = copy_out(ctx, s, oc, nout, d.err, &herr);
     if (rc) return rc;
   } else {
@@ -595,7 +630,8 @@ static int sw_fluxes_run(rrtmg_ctx *ctx, const rrtmg_sw_args *a, const rrtmg_sw_
   return RRTMG_OK;
 }
 
-int sw_fluxes_impl(rrtmg_ctx *ctx, const rrtmg_sw_args *a) { return sw_fluxes_run(ctx, a, nullptr); }
-int sw_fluxes_components_impl(rrtmg_ctx *ctx, const rrtmg_sw_args *a, const rrtmg_sw_components *c) { return sw_fluxes_run(ctx, a, c); }
+int sw_fluxes_impl(rrtmg_ctx *ctx, const rrtmg_sw_args *a) { return sw_fluxes_run(ctx, a, nullptr, nullptr); }
+int sw_fluxes_components_impl(rrtmg_ctx *ctx, const rrtmg_sw_args *a, const rrtmg_sw_components *c) { return sw_fluxes_run(ctx, a, c, nullptr); }
+int sw_fluxes_bands_impl(rrtmg_ctx *ctx, const rrtmg_sw_args *a, const rrtmg_sw_components *c, const rrtmg_sw_band_fluxes *b) { return sw_fluxes_run(ctx, a, c, b); }
 
 }  // namespace rrtmg

@@ -1273,6 +1273,40 @@ RRTMG_HD void sw_components_level(const SwDev &d, const SwTab &T, const double *
   if (o.dirdflxc) o.dirdflxc[i] = dirc;
   if (o.difdflxc) o.difdflxc[i] = cd - dirc;
 }
+// Outputs of rrtmg_hip_sw_fluxes_bands, [14][nrow][ncol] (nrow = nlay+1, or 2: surface and top); a NULL member is not
+// written and its planes are not read.
+struct SwBandOut { double *up, *dn, *upc, *dnc, *dndir, *dndirc; };
+// Fluxes BY BAND of one (column, level) -> row `row` of the outputs: the walk of sw_flux_sums over the slots (g-point
+// order), with the sums started at 0.0 for every band and stored where item_band changes (items are band-pure and
+// band-contiguous in slot order: build_sw_tab checks it).  partdir (SwPartDirSink) is read only where a direct-beam member
+// is set.  cld = false: the tile ran the clear-sky variant, the clear-sky outputs are the all-sky sums (see sw_flux_sums).
+RRTMG_HD void sw_band_level(const SwDev &d, const SwTab &T, const double *partdir, const SwBandOut &o, int col, int lev, int row, int nrow, bool cld) {
+  const int L = d.nlay, P = d.pcols;
+  const long st = (long)(L + 1) * P, slot = 4 * st, dslot = 2 * st, off = (long)lev * P + (col - d.col0);
+  const bool ru = o.up || (o.upc && !cld), rd = o.dn || (o.dnc && !cld), rcu = o.upc && cld, rcd = o.dnc && cld;
+  const bool rb = o.dndir || (o.dndirc && !cld), rcb = o.dndirc && cld;
+  double fu = 0.0, fd = 0.0, cu = 0.0, cd = 0.0, db = 0.0, dbc = 0.0;
+  for (int c = 0; c < T.nitem; ++c) {
+    const double *p = d.part + (long)c * slot + off;
+    if (ru) fu = fu + part_load(p);
+    if (rd) fd = fd + part_load(p + st);
+    if (rcu) cu = cu + part_load(p + 2 * st);
+    if (rcd) cd = cd + part_load(p + 3 * st);
+    if (rb) db = db + part_load(partdir + (long)c * dslot + off);
+    if (rcb) dbc = dbc + part_load(partdir + (long)c * dslot + st + off);
+    const int band = item_band(T.item[c]);
+    if (c + 1 < T.nitem && item_band(T.item[c + 1]) == band) continue;
+    if (!cld) { cu = fu; cd = fd; dbc = db; }
+    const long i = ((long)band * nrow + row) * d.ncol + col;
+    if (o.up) o.up[i] = fu;
+    if (o.dn) o.dn[i] = fd;
+    if (o.upc) o.upc[i] = cu;
+    if (o.dnc) o.dnc[i] = cd;
+    if (o.dndir) o.dndir[i] = db;
+    if (o.dndirc) o.dndirc[i] = dbc;
+    fu = 0.0; fd = 0.0; cu = 0.0; cd = 0.0; db = 0.0; dbc = 0.0;
+  }
+}
 RRTMG_HD void sw_flux_level(const SwDev &d, const SwTab &T, int col, int lev, bool cld) {
   double fu, fd, cu, cd;
   sw_flux_sums(d, T, col, lev, cld, fu, fd, cu, cd);

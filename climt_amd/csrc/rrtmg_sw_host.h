@@ -101,6 +101,15 @@ inline bool build_sw_tab(TableSet &ts, SwTab &T, std::string &err) {
     }
     for (int i = 1; i < n; ++i)   // stable insertion sort, descending cost
       for (int j = i; j > 0 && cost[T.sched[j]] > cost[T.sched[j - 1]]; --j) { const int t = T.sched[j]; T.sched[j] = T.sched[j - 1]; T.sched[j - 1] = t; }
+    // sw_band_level walks the slots in order and closes a band's sum where item_band changes: every band's items must be
+    // consecutive slots, bands in order, none missing
+    int prev = -1;
+    for (int i = 0; i < n; ++i) {
+      const int b = item_band(T.item[i]);
+      if (b != prev && b != prev + 1) { err = "work items are not band-contiguous in slot order"; return false; }
+      prev = b;
+    }
+    if (prev != kSwNBand - 1) { err = "work items do not cover every band"; return false; }
   }
   return err.empty();
 }

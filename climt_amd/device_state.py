@@ -279,8 +279,13 @@ def shortwave_device_call(self, ds):
     if getattr(self, "_flux_components", False):
         from .rrtmg.shortwave import FLUX_COMPONENT_DIAGNOSTICS
         comps = {c: w(c, il, ("interface_levels", "*"), "W m^-2") for c in FLUX_COMPONENT_DIAGNOSTICS.values()}
-    if comps:
-        ds.ctx.sw_fluxes(inp, mcica=self._mcica, out=out, memspace=1, components={c: q.ptr for c, q in comps.items()})
+    bands = None
+    if getattr(self, "_band_fluxes", False):
+        from .rrtmg.shortwave import BAND_FLUX_DIAGNOSTICS
+        bands = {b: w("band." + b, (14,) + il, ("num_shortwave_bands", "interface_levels", "*"), "W m^-2") for b in BAND_FLUX_DIAGNOSTICS.values()}
+    if comps or bands:
+        ds.ctx.sw_fluxes(inp, mcica=self._mcica, out=out, memspace=1, components={c: q.ptr for c, q in comps.items()} if comps else None,
+                         bands={b: q.ptr for b, q in bands.items()} if bands else None)
     else:
         ds.ctx.sw_fluxes(inp, mcica=self._mcica, out=out, memspace=1)
     diagnostics = {
@@ -289,6 +294,8 @@ def shortwave_device_call(self, ds):
         "air_temperature_tendency_from_shortwave_assuming_clear_sky": hrc, "air_temperature_tendency_from_shortwave": hr}
     if comps:
         diagnostics.update({k: comps[c] for k, c in FLUX_COMPONENT_DIAGNOSTICS.items()})
+    if bands:
+        diagnostics.update({k: bands[b] for k, b in BAND_FLUX_DIAGNOSTICS.items()})
     return {"air_temperature": hr}, diagnostics
 
 
@@ -327,12 +334,21 @@ def longwave_device_call(self, ds):
         du, duc = w("duflx_dt", il, ("interface_levels", "*"), "W m^-2 K^-1"), w("duflxc_dt", il, ("interface_levels", "*"), "W m^-2 K^-1")
         out.update(duflx_dt=du.ptr, duflxc_dt=duc.ptr)
         self.change_in_upward_flux_with_surface_temperature, self.change_in_clear_sky_upward_flux_with_surface_temperature = du, duc
-    ds.ctx.lw_fluxes(inp, mcica=self._mcica, out=out, memspace=1)
+    bands = None
+    if getattr(self, "_band_fluxes", False):
+        from .rrtmg.longwave import BAND_FLUX_DIAGNOSTICS
+        bands = {b: w("band." + b, (16,) + il, ("num_longwave_bands", "interface_levels", "*"), "W m^-2") for b in BAND_FLUX_DIAGNOSTICS.values()}
+    if bands:
+        ds.ctx.lw_fluxes(inp, mcica=self._mcica, out=out, memspace=1, bands={b: q.ptr for b, q in bands.items()})
+    else:
+        ds.ctx.lw_fluxes(inp, mcica=self._mcica, out=out, memspace=1)
     ds._lw_inflight = True      # consumers on the main stream (tendency sum, slab, the next derived fields) join first: join_streams()
     diagnostics = {
         "upwelling_longwave_flux_in_air": fl["uflx"], "downwelling_longwave_flux_in_air": fl["dflx"],
         "upwelling_longwave_flux_in_air_assuming_clear_sky": fl["uflxc"], "downwelling_longwave_flux_in_air_assuming_clear_sky": fl["dflxc"],
         "air_temperature_tendency_from_longwave_assuming_clear_sky": hrc, "air_temperature_tendency_from_longwave": hr}
+    if bands:
+        diagnostics.update({k: bands[b] for k, b in BAND_FLUX_DIAGNOSTICS.items()})
     return {"air_temperature": hr}, diagnostics
 
 

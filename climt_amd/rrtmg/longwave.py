@@ -26,6 +26,17 @@ def _prop(dims, units):
 _ML, _IL = ["mid_levels", "*"], ["interface_levels", "*"]
 
 
+# the diagnostics of RRTMGLongwave(band_fluxes=True) -> member of rrtmg_lw_band_fluxes: the broadband names with _by_band
+# appended; dims [num_longwave_bands, interface_levels, *], bands 1..16
+BAND_FLUX_DIAGNOSTICS = {
+    "upwelling_longwave_flux_in_air_by_band": "up",
+    "downwelling_longwave_flux_in_air_by_band": "dn",
+    "upwelling_longwave_flux_in_air_assuming_clear_sky_by_band": "upc",
+    "downwelling_longwave_flux_in_air_assuming_clear_sky_by_band": "dnc",
+}
+_BIL = ["num_longwave_bands", "interface_levels", "*"]
+
+
 class RRTMGLongwave(TendencyComponent):
     """The Rapid Radiative Transfer Model (RRTMG), longwave, on AMD MI355X."""
 
@@ -70,12 +81,25 @@ class RRTMGLongwave(TendencyComponent):
         "air_temperature_tendency_from_longwave": _prop(_ML, "degK day^-1"),
     }
 
+    @classmethod
+    def diagnostic_properties_for(cls, band_fluxes=False):
+        """The diagnostic_properties of an instance made with that `band_fluxes`: the class dict itself, or a new dict of it
+        plus the four band fluxes (bands x interface levels, W m^-2)."""
+        if not band_fluxes:
+            return cls.diagnostic_properties
+        return dict(cls.diagnostic_properties, **{k: _prop(_BIL, "W m^-2") for k in BAND_FLUX_DIAGNOSTICS})
+
     def __init__(self, calculate_change_up_flux=False, cloud_overlap_method=None, cloud_optical_properties="liquid_and_ice_clouds",
                  cloud_ice_properties="ebert_curry_two", cloud_liquid_water_properties="radius_dependent_absorption",
                  calculate_interface_temperature=True, mcica=False, random_number_generator="mersenne_twister", device=0,
-                 allow_synthetic_tables=False, **kwargs):
+                 allow_synthetic_tables=False, band_fluxes=False, **kwargs):
         """Same keyword arguments and defaults as climt.RRTMGLongwave (lw/component.py:167-178); additions: `device`
-        (GPU ordinal) and `allow_synthetic_tables` (see the module docstring)."""
+        (GPU ordinal), `allow_synthetic_tables` (see the module docstring) and `band_fluxes`: True adds the up / down fluxes
+        (all sky, clear sky) by spectral band (BAND_FLUX_DIAGNOSTICS) to this instance's diagnostics; the class attributes are
+        unchanged."""
+        self._band_fluxes = bool(band_fluxes)
+        if self._band_fluxes:
+            self.diagnostic_properties = self.diagnostic_properties_for(True)
         self.input_properties = RRTMGLongwave.input_properties.copy()
         self._calc_dflxdt = 1 if calculate_change_up_flux else 0
         self._mcica = mcica
@@ -175,7 +199,11 @@ class RRTMGLongwave(TendencyComponent):
             for key in ("duflx_dt", "duflxc_dt"):
                 out[key] = self._pool.zeros_like_fresh(key, (n_layers + 1, n_columns))
         self._input_staging.wait()
-        self._ctx.lw_fluxes(inp, mcica=self._mcica, out=out)
+        if self._band_fluxes:
+            bands = {b: diagnostics[k] for k, b in BAND_FLUX_DIAGNOSTICS.items()}
+            self._ctx.lw_fluxes(inp, mcica=self._mcica, out=out, bands=bands)
+        else:
+            self._ctx.lw_fluxes(inp, mcica=self._mcica, out=out)
         if self._calc_dflxdt:
             self.change_in_upward_flux_with_surface_temperature = out["duflx_dt"]
             self.change_in_clear_sky_upward_flux_with_surface_temperature = out["duflxc_dt"]

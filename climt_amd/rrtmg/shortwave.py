@@ -34,6 +34,20 @@ FLUX_COMPONENT_DIAGNOSTICS = {
 }
 
 
+# the diagnostics of RRTMGShortwave(band_fluxes=True) -> member of rrtmg_sw_band_fluxes: the broadband names with _by_band
+# appended, plus the direct beam; dims [num_shortwave_bands, interface_levels, *], bands in the order of the reference's
+# per-band inputs (RRTMG bands 16..29: the 820-2600 cm^-1 band is last)
+BAND_FLUX_DIAGNOSTICS = {
+    "upwelling_shortwave_flux_in_air_by_band": "up",
+    "downwelling_shortwave_flux_in_air_by_band": "dn",
+    "upwelling_shortwave_flux_in_air_assuming_clear_sky_by_band": "upc",
+    "downwelling_shortwave_flux_in_air_assuming_clear_sky_by_band": "dnc",
+    "downwelling_direct_shortwave_flux_in_air_by_band": "dndir",
+    "downwelling_direct_shortwave_flux_in_air_assuming_clear_sky_by_band": "dndirc",
+}
+_BIL = ["num_shortwave_bands", "interface_levels", "*"]
+
+
 class RRTMGShortwave(TendencyComponent):
     """The Rapid Radiative Transfer Model (RRTMG), shortwave, on AMD MI355X."""
 
@@ -89,25 +103,35 @@ class RRTMGShortwave(TendencyComponent):
     }
 
     @classmethod
-    def diagnostic_properties_for(cls, flux_components=False):
-        """The diagnostic_properties of an instance made with that `flux_components`: the class dict itself, or a new dict of
-        it plus the eight flux components (interface levels, W m^-2)."""
-        if not flux_components:
+    def diagnostic_properties_for(cls, flux_components=False, band_fluxes=False):
+        """The diagnostic_properties of an instance made with these options: the class dict itself, or a new dict of it plus
+        the eight flux components (interface levels, W m^-2) and / or the six band fluxes (bands x interface levels)."""
+        if not flux_components and not band_fluxes:
             return cls.diagnostic_properties
-        return dict(cls.diagnostic_properties, **{k: _prop(_IL, "W m^-2") for k in FLUX_COMPONENT_DIAGNOSTICS})
+        props = dict(cls.diagnostic_properties)
+        if flux_components:
+            props.update({k: _prop(_IL, "W m^-2") for k in FLUX_COMPONENT_DIAGNOSTICS})
+        if band_fluxes:
+            props.update({k: _prop(_BIL, "W m^-2") for k in BAND_FLUX_DIAGNOSTICS})
+        return props
 
     def __init__(self, cloud_overlap_method=None, cloud_optical_properties="liquid_and_ice_clouds",
                  cloud_ice_properties="ebert_curry_two", cloud_liquid_water_properties="radius_dependent_absorption",
                  solar_variability_method=0, use_solar_constant_from_fortran=False, ignore_day_of_year=False,
                  facular_sunspot_amplitude=None, solar_variability_by_band=None, aerosol_type="no_aerosol", mcica=False,
-                 random_number_generator="mersenne_twister", device=0, flux_components=False, **kwargs):
+                 random_number_generator="mersenne_twister", device=0, flux_components=False, band_fluxes=False,
+                 **kwargs):
         """Same keyword arguments and defaults as climt.RRTMGShortwave (sw/component.py:179-194); the additions are `device`
         (GPU ordinal) and `flux_components`: True adds the downward flux split into direct and diffuse parts -- all bands,
         UV/visible bands, near-IR bands, and all bands clear sky (FLUX_COMPONENT_DIAGNOSTICS) -- to this instance's
-        diagnostics; the class attributes are unchanged."""
+        diagnostics; `band_fluxes`: True adds the up / down fluxes (all sky, clear sky) and the direct beam by spectral
+        band (BAND_FLUX_DIAGNOSTICS); the class attributes are unchanged."""
         self._flux_components = bool(flux_components)
+        self._band_fluxes = bool(band_fluxes)
         if self._flux_components:
             self.diagnostic_properties = self.diagnostic_properties_for(True)
+        if self._band_fluxes:
+            self.diagnostic_properties = self.diagnostic_properties_for(self._flux_components, band_fluxes=True)
         self._mcica = mcica
         if mcica:
             self._permute_seed = None
@@ -207,9 +231,10 @@ class RRTMGShortwave(TendencyComponent):
             swdflxc=diagnostics["downwelling_shortwave_flux_in_air_assuming_clear_sky"],
             swhrc=diagnostics["air_temperature_tendency_from_shortwave_assuming_clear_sky"])
         self._input_staging.wait()
-        if self._flux_components:
-            comps = {c: diagnostics[k] for k, c in FLUX_COMPONENT_DIAGNOSTICS.items()}
-            self._ctx.sw_fluxes(inp, mcica=self._mcica, out=out, components=comps)
+        if self._flux_components or self._band_fluxes:
+            comps = {c: diagnostics[k] for k, c in FLUX_COMPONENT_DIAGNOSTICS.items()} if self._flux_components else None
+            bands = {b: diagnostics[k] for k, b in BAND_FLUX_DIAGNOSTICS.items()} if self._band_fluxes else None
+            self._ctx.sw_fluxes(inp, mcica=self._mcica, out=out, components=comps, bands=bands)
         else:
             self._ctx.sw_fluxes(inp, mcica=self._mcica, out=out)
         diagnostics["air_temperature_tendency_from_shortwave"][:] = tendencies["air_temperature"]

@@ -32,7 +32,7 @@ def main():
     a = ap.parse_args()
 
     sun = climt_amd.Instellation()
-    lw = climt_amd.UpdateFrequencyWrapper(climt_amd.RRTMGLongwave(allow_synthetic_tables=True), timedelta(hours=1))
+    lw = climt_amd.UpdateFrequencyWrapper(climt_amd.RRTMGLongwave(allow_synthetic_tables=True, band_fluxes=True), timedelta(hours=1))
     sw = climt_amd.UpdateFrequencyWrapper(climt_amd.RRTMGShortwave(), timedelta(hours=1))
     slab = climt_amd.SlabSurface()
 
@@ -60,6 +60,13 @@ def main():
             asr = (host("downwelling_shortwave_flux_in_air")[-1] - host("upwelling_shortwave_flux_in_air")[-1]).mean()
             print("%s  OLR %7.2f  absorbed solar %7.2f  Ts %7.3f  T(lowest) %7.3f" % (
                 state["time"], olr, asr, host("surface_temperature").mean(), host("air_temperature")[0].mean()))
+    # outgoing longwave radiation by spectral band (RRTMGLongwave(band_fluxes=True)): [band][interface level][...], top = last level
+    from climt_amd._lib import band_limits
+    lo, hi = band_limits("lw")
+    olr_band = host("upwelling_longwave_flux_in_air_by_band")[:, -1].reshape(16, -1).mean(axis=1)
+    for b in range(16):
+        print("  band %2d  %5.0f-%5.0f cm^-1  OLR %7.3f W m^-2" % (b + 1, lo[b], hi[b], olr_band[b]))
+    print("  sum of bands %7.3f" % olr_band.sum())
 
 
 if __name__ == "__main__":

@@ -119,7 +119,7 @@ int rrtmg_hip_set_deferred(rrtmg_ctx *ctx, int on);
  * tile now runs in the clear-sky variant, whose shortwave differs from the cloudy variant's clear-sky stream by ~1e-12 W m^-2 --
  * which is why this is not the default (tile-aligned shards == the whole grid bit for bit only when a column's variant is a
  * function of its tile).  Calls with the Mersenne twister (one positional stream) and host-pointer calls are not sorted,
- * nor are calls that request flux components (rrtmg_hip_sw_fluxes_components). */
+ * nor are calls that request flux components or band fluxes (rrtmg_hip_sw_fluxes_components, rrtmg_hip_*_fluxes_bands). */
 int rrtmg_hip_set_column_sort(rrtmg_ctx *ctx, int on);
 /* Duration (ms, HIP events recorded on the stream the kernel is launched on) of a solve kernel in the last completed call:
  * which = 0 -> sw_solve_all_kernel<false> (clear-sky tiles), 1 -> lw_solve_all_kernel<false,..>, 2 -> sw_solve_cloudy_kernel,
@@ -273,6 +273,33 @@ typedef struct rrtmg_sw_components {
  * with components is never column-sorted (rrtmg_hip_set_column_sort). */
 int rrtmg_hip_sw_fluxes_components(rrtmg_ctx *ctx, const rrtmg_sw_args *a, const rrtmg_sw_components *c);
 
+/* Shortwave fluxes BY BAND: the sums that rrtmg_hip_sw_fluxes forms over all 112 g-points, closed per band instead (what the
+ * reference's spcvrt_sw / spcvmc_sw return for istart = iend = band, iout = band).  Band index 0..13 is the reference's
+ * band order, RRTMG bands 16..29: band 29 (820-2600 cm^-1) is LAST, out of wavenumber order; rrtmg_hip_band_limits gives
+ * the limits.  Every member is [14][nrow][ncol], W m^-2, in the memspace of the rrtmg_sw_args; NULL = not wanted (not
+ * computed, its partial sums not read):
+ *   levels == 0: nrow = nlay+1, row = interface level (0 = surface, like swdflx)
+ *   levels == 1: nrow = 2, row 0 = surface, row 1 = top of the atmosphere (the same bits as rows 0 and nlay of levels == 0)
+ *   up, dn, upc, dnc   all-sky / clear-sky upward / downward flux;  dndir, dndirc   delta-scaled direct beam, all / clear sky
+ * The sum over the bands equals the broadband output within 256 * 2^-53 * F (another association of the same terms).
+ * The versioned structs and RRTMG_HIP_ABI_VERSION are unchanged: the struct checks its own struct_size, and a caller probes
+ * for the feature by the presence of the symbol rrtmg_hip_sw_fluxes_bands (dlsym). */
+typedef struct rrtmg_sw_band_fluxes {
+  int32_t struct_size;                 /* sizeof(rrtmg_sw_band_fluxes) of the caller's header: required */
+  int32_t levels;                      /* 0: [14][nlay+1][ncol]   1: [14][2][ncol] (surface, top) */
+  double *up, *dn, *upc, *dnc;
+  double *dndir, *dndirc;
+} rrtmg_sw_band_fluxes;
+/* rrtmg_hip_sw_fluxes_components plus the requested band fluxes (c may be NULL).  b == NULL, or every member NULL, is exactly
+ * rrtmg_hip_sw_fluxes_components(ctx, a, c); a struct_size that is not sizeof(rrtmg_sw_band_fluxes), or levels not 0 or 1, is
+ * refused (RRTMG_ERR_ARG) before anything is enqueued.  The six outputs of the plain call (and the components) are the same
+ * bits with or without bands.  Host pointers: downloaded behind the same synchronise as the six outputs; device pointers
+ * in deferred mode: the call returns once enqueued.  A call with bands is never column-sorted. */
+int rrtmg_hip_sw_fluxes_bands(rrtmg_ctx *ctx, const rrtmg_sw_args *a, const rrtmg_sw_components *c, const rrtmg_sw_band_fluxes *b);
+/* Band limits in cm^-1: spectrum 0 = shortwave (14 values each, bands 16..29 in that order), 1 = longwave (16 values, bands
+ * 1..16; hi - lo is the longwave's delwave).  Host arrays; either may be NULL.  Returns the number of bands, or -1 for another spectrum. */
+int rrtmg_hip_band_limits(int spectrum, double *wavenumber_lo, double *wavenumber_hi);
+
 /* ---- longwave ------------------------------------------------------------------------- */
 typedef struct rrtmg_lw_args {
   int32_t ncol, nlay;
@@ -299,6 +326,17 @@ typedef struct rrtmg_lw_args {
 } rrtmg_lw_args;
 
 int rrtmg_hip_lw_fluxes(rrtmg_ctx *ctx, const rrtmg_lw_args *a);
+
+/* Longwave fluxes BY BAND (see rrtmg_sw_band_fluxes): [16][nrow][ncol], band index 0..15 = bands 1..16, what the reference's
+ * rtrn / rtrnmc / rtrnmr return for istart = iend = band, iout = band.  The surface-temperature derivatives (idrv) have no
+ * per-band output. */
+typedef struct rrtmg_lw_band_fluxes {
+  int32_t struct_size;                 /* sizeof(rrtmg_lw_band_fluxes) of the caller's header: required */
+  int32_t levels;                      /* 0: [16][nlay+1][ncol]   1: [16][2][ncol] (surface, top) */
+  double *up, *dn, *upc, *dnc;         /* all-sky / clear-sky upward / downward flux, W m^-2; NULL = not wanted */
+} rrtmg_lw_band_fluxes;
+/* rrtmg_hip_lw_fluxes plus the requested band fluxes: the rules of rrtmg_hip_sw_fluxes_bands. */
+int rrtmg_hip_lw_fluxes_bands(rrtmg_ctx *ctx, const rrtmg_lw_args *a, const rrtmg_lw_band_fluxes *b);
 
 /* sub-column generators on their own (mcica_subcol_gen_{sw,lw}.f90); host pointers.
  * which: 0 = SW (112 sub-columns), 1 = LW (140).  cldfmcl out: [nlay][ncol][ngpt] of 0/1. */
