@@ -61,6 +61,35 @@ class SwBandFluxes(C.Structure):
     _fields_ = [("struct_size", _i32), ("levels", _i32)] + [(n, _vp) for n in SW_BAND_FLUXES]
 
 
+# members of rrtmg_sw_surface (include/rrtmg_hip.h): the surface albedo by band for the direct beam / for diffuse radiation
+SW_SURFACE = ("albdir", "albdif")
+
+
+class SwSurface(C.Structure):
+    """mirrors `rrtmg_sw_surface` (include/rrtmg_hip.h), field for field"""
+    _fields_ = [("struct_size", _i32), ("reserved", _i32)] + [(n, _vp) for n in SW_SURFACE]
+
+
+def _surface_struct(surface, ncol, keep):
+    """The filled struct of a `surface=` input (Context.sw_fluxes): arrays [14][ncol] (kept alive in `keep`) or device pointers."""
+    s = SwSurface()
+    s.struct_size = C.sizeof(SwSurface)
+    for k, v in surface.items():
+        if k not in SW_SURFACE:
+            raise KeyError("unknown surface input %r (one of %s)" % (k, ", ".join(SW_SURFACE)))
+        if v is None:
+            continue
+        if isinstance(v, (int, np.integer)):
+            setattr(s, k, int(v))
+            continue
+        arr = np.ascontiguousarray(v, dtype=np.float64)
+        if arr.shape != (SW_NBAND, ncol):
+            raise ValueError("surface input %r: an array of %d x %d (band, column), not %r" % (k, SW_NBAND, ncol, arr.shape))
+        keep.append(arr)
+        setattr(s, k, arr.ctypes.data)
+    return s
+
+
 class LwBandFluxes(C.Structure):
     """mirrors `rrtmg_lw_band_fluxes` (include/rrtmg_hip.h), field for field"""
     _fields_ = [("struct_size", _i32), ("levels", _i32)] + [(n, _vp) for n in LW_BAND_FLUXES]
@@ -130,6 +159,8 @@ def load_library():
     lib.rrtmg_hip_lw_fluxes.argtypes = [_vp, C.POINTER(LwArgs)]
     lib.rrtmg_hip_sw_fluxes_components.argtypes = [_vp, C.POINTER(SwArgs), C.POINTER(SwComponents)]
     lib.rrtmg_hip_sw_fluxes_bands.argtypes = [_vp, C.POINTER(SwArgs), C.POINTER(SwComponents), C.POINTER(SwBandFluxes)]
+    if hasattr(lib, "rrtmg_hip_sw_fluxes_surface"):      # (a library named by RRTMG_HIP_LIB may predate it: probed by the symbol)
+        lib.rrtmg_hip_sw_fluxes_surface.argtypes = [_vp, C.POINTER(SwArgs), C.POINTER(SwSurface), C.POINTER(SwComponents), C.POINTER(SwBandFluxes)]
     lib.rrtmg_hip_lw_fluxes_bands.argtypes = [_vp, C.POINTER(LwArgs), C.POINTER(LwBandFluxes)]
     lib.rrtmg_hip_band_limits.argtypes = [C.c_int, _vp, _vp]
     lib.rrtmg_hip_get_table.restype = C.c_long
@@ -403,8 +434,12 @@ class Context:
                 setattr(a, f, arr.ctypes.data)
 
     @_locked
-    def sw_fluxes(self, inp, mcica=False, out=None, memspace=0, components=None, bands=None, band_levels="all"):
-        """`components`: None, or a dict SW_COMPONENTS name -> output (a C-contiguous float64 [nlay+1][ncol] array, or a device
+    def sw_fluxes(self, inp, mcica=False, out=None, memspace=0, components=None, bands=None, band_levels="all", surface=None):
+        """`surface`: None, or a dict with "albdir" and / or "albdif": the surface albedo by band for the direct beam / for
+        diffuse radiation, [14][ncol] arrays (device pointers with memspace=1), bands in the order of band_limits("sw")
+        (rrtmg_hip_sw_fluxes_surface); the one left out follows from asdir / aldir (asdif / aldif) by the reference driver's band
+        rule, and with both given those four are not read.  The keys "albdir" / "albdif" of `inp` mean the same.
+        `components`: None, or a dict SW_COMPONENTS name -> output (a C-contiguous float64 [nlay+1][ncol] array, or a device
         pointer with memspace=1) that the call fills as well (rrtmg_hip_sw_fluxes_components); the names left out are not
         computed.  `bands`: None, or a dict SW_BAND_FLUXES name -> output [14][nrow][ncol] in the same way
         (rrtmg_hip_sw_fluxes_bands); `band_levels`: "all" (nrow = nlay+1) or "boundaries" (nrow = 2: surface, top)."""
@@ -421,13 +456,31 @@ class Context:
         for k, _ in SW_OUT:
             v = out[k]
             setattr(a, k, int(v) if isinstance(v, (int, np.integer)) else v.ctypes.data)
-        if components is None and bands is None:
+        if surface is None and (inp.get("albdir") is not None or inp.get("albdif") is not None):
+            surface = {k: inp.get(k) for k in SW_SURFACE}
+        if components is None and bands is None and surface is None:
             self._ck(self.lib.rrtmg_hip_sw_fluxes(self.h, C.byref(a)))
             return out
         b = None if bands is None else _band_struct(SwBandFluxes, SW_BAND_FLUXES, SW_NBAND, bands, band_levels, nlay, ncol)
+        if surface is not None:
+            if not hasattr(self.lib, "rrtmg_hip_sw_fluxes_surface"):
+                raise RRTMGError(4, "this librrtmg_hip.so has no rrtmg_hip_sw_fluxes_surface (surface albedo by band)")
+            sf = _surface_struct(surface, ncol, keep)
+            c = None if components is None else self._components_struct(components, nlay, ncol)
+            self._ck(self.lib.rrtmg_hip_sw_fluxes_surface(self.h, C.byref(a), C.byref(sf), None if c is None else C.byref(c), None if b is None else C.byref(b)))
+            return out
         if components is None:
             self._ck(self.lib.rrtmg_hip_sw_fluxes_bands(self.h, C.byref(a), None, C.byref(b)))
             return out
+        c = self._components_struct(components, nlay, ncol)
+        if b is not None:
+            self._ck(self.lib.rrtmg_hip_sw_fluxes_bands(self.h, C.byref(a), C.byref(c), C.byref(b)))
+            return out
+        self._ck(self.lib.rrtmg_hip_sw_fluxes_components(self.h, C.byref(a), C.byref(c)))
+        return out
+
+    @staticmethod
+    def _components_struct(components, nlay, ncol):
         c = SwComponents()
         c.struct_size = C.sizeof(SwComponents)
         for k, v in components.items():
@@ -439,11 +492,7 @@ class Context:
             if not (isinstance(v, np.ndarray) and v.dtype == np.float64 and v.flags.c_contiguous and v.size == (nlay + 1) * ncol):
                 raise ValueError("component %r: the library writes it in place: a C-contiguous float64 array of %d x %d" % (k, nlay + 1, ncol))
             setattr(c, k, v.ctypes.data)
-        if b is not None:
-            self._ck(self.lib.rrtmg_hip_sw_fluxes_bands(self.h, C.byref(a), C.byref(c), C.byref(b)))
-            return out
-        self._ck(self.lib.rrtmg_hip_sw_fluxes_components(self.h, C.byref(a), C.byref(c)))
-        return out
+        return c
 
     @_locked
     def lw_fluxes(self, inp, mcica=False, out=None, memspace=0, bands=None, band_levels="all"):

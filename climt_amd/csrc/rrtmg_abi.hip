@@ -493,6 +493,24 @@ int rrtmg_hip_sw_fluxes_bands(rrtmg_ctx *ctx, const rrtmg_sw_args *a, const rrtm
   if (c && !(c->dirdflx || c->difdflx || c->dirdnuv || c->difdnuv || c->dirdnir || c->difdnir || c->dirdflxc || c->difdflxc)) c = nullptr;
   return checked_call(ctx, a, "rrtmg_sw", [c, b](rrtmg_ctx *x, const rrtmg_sw_args *y) { return sw_fluxes_bands_impl(x, y, c, b); });
 }
+// surface albedo by band: the three struct checks come before anything is enqueued; without a member it is the call without the struct
+int rrtmg_hip_sw_fluxes_surface(rrtmg_ctx *ctx, const rrtmg_sw_args *a, const rrtmg_sw_surface *sf, const rrtmg_sw_components *c, const rrtmg_sw_band_fluxes *b) {
+  if (!ctx) return RRTMG_ERR_ARG;
+  if (sf && (size_t)sf->struct_size != sizeof(rrtmg_sw_surface))
+    return ctx->fail(RRTMG_ERR_ARG, "rrtmg_sw_surface: struct_size %d is not sizeof(rrtmg_sw_surface) = %zu of this library: set it to sizeof of the struct",
+                     (int)sf->struct_size, sizeof(rrtmg_sw_surface));
+  if (!sf || !(sf->albdir || sf->albdif)) return rrtmg_hip_sw_fluxes_bands(ctx, a, c, b);
+  if (b && (size_t)b->struct_size != sizeof(rrtmg_sw_band_fluxes))
+    return ctx->fail(RRTMG_ERR_ARG, "rrtmg_sw_band_fluxes: struct_size %d is not sizeof(rrtmg_sw_band_fluxes) = %zu of this library: set it to sizeof of the struct",
+                     (int)b->struct_size, sizeof(rrtmg_sw_band_fluxes));
+  if (b && b->levels != 0 && b->levels != 1) return ctx->fail(RRTMG_ERR_ARG, "rrtmg_sw_band_fluxes: levels %d is neither 0 (all interface levels) nor 1 (surface and top)", (int)b->levels);
+  if (b && !(b->up || b->dn || b->upc || b->dnc || b->dndir || b->dndirc)) b = nullptr;
+  if (c && (size_t)c->struct_size != sizeof(rrtmg_sw_components))
+    return ctx->fail(RRTMG_ERR_ARG, "rrtmg_sw_components: struct_size %d is not sizeof(rrtmg_sw_components) = %zu of this library: set it to sizeof of the struct",
+                     (int)c->struct_size, sizeof(rrtmg_sw_components));
+  if (c && !(c->dirdflx || c->difdflx || c->dirdnuv || c->difdnuv || c->dirdnir || c->difdnir || c->dirdflxc || c->difdflxc)) c = nullptr;
+  return checked_call(ctx, a, "rrtmg_sw", [sf, c, b](rrtmg_ctx *x, const rrtmg_sw_args *y) { return sw_fluxes_surface_impl(x, y, sf, c, b); });
+}
 int rrtmg_hip_lw_fluxes_bands(rrtmg_ctx *ctx, const rrtmg_lw_args *a, const rrtmg_lw_band_fluxes *b) {
   if (!ctx) return RRTMG_ERR_ARG;
   if (b && (size_t)b->struct_size != sizeof(rrtmg_lw_band_fluxes))

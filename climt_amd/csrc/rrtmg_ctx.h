@@ -199,6 +199,7 @@ void free_lw_desc(rrtmg_ctx *ctx);
 int sw_fluxes_impl(rrtmg_ctx *ctx, const rrtmg_sw_args *a);
 int sw_fluxes_components_impl(rrtmg_ctx *ctx, const rrtmg_sw_args *a, const rrtmg_sw_components *c);
 int sw_fluxes_bands_impl(rrtmg_ctx *ctx, const rrtmg_sw_args *a, const rrtmg_sw_components *c, const rrtmg_sw_band_fluxes *b);
+int sw_fluxes_surface_impl(rrtmg_ctx *ctx, const rrtmg_sw_args *a, const rrtmg_sw_surface *sf, const rrtmg_sw_components *c, const rrtmg_sw_band_fluxes *b);
 int lw_fluxes_impl(rrtmg_ctx *ctx, const rrtmg_lw_args *a);
 int lw_fluxes_bands_impl(rrtmg_ctx *ctx, const rrtmg_lw_args *a, const rrtmg_lw_band_fluxes *b);
 int sw_init_impl(rrtmg_ctx *ctx, double cpdair, const char *blob);

@@ -20,6 +20,8 @@
 //   <<<(tiles, levels/4), 4 waves>>> behind sw_fluxheat_kernel: direct / diffuse, UV-visible / near-IR sums per interface
 //   With band fluxes requested (rrtmg_hip_sw_fluxes_bands): sw_bandflux_kernel <<<(tiles, levels/4), 4 waves>>> (or the two
 //   boundary levels only) behind them, and the *_dir solve variants where a direct-beam member is set
+//   With the surface albedo by band (rrtmg_hip_sw_fluxes_surface): the same launches; the solve reads its two albedos from
+//   the caller's [band][column] rows (SwDev::albdir / albdif) instead of the four broadband arrays
 #include <future>
 
 #include "rrtmg_ctx.h"
@@ -390,10 +392,11 @@ static int sw_sorted_call(rrtmg_ctx *ctx, const rrtmg_sw_args *a) {
 }
 
 // cp: the components requested (at least one member set), or nullptr; bp: the band fluxes requested (at least one member
-// set, levels 0 or 1), or nullptr; both nullptr: the plain call.  A call with components or bands is never sorted: its
-// outputs would need a scatter of their own.
-static int sw_fluxes_run(rrtmg_ctx *ctx, const rrtmg_sw_args *a, const rrtmg_sw_components *cp, const rrtmg_sw_band_fluxes *bp) {
-  if (!cp && !bp && ctx->sw_ready && a && ctx->sort_columns && !ctx->sorting && a->memspace == 1 && a->icld != 0 && a->cldfr && a->ncol >= 128 && a->nlay > 0 && a->nlay <= 256 &&
+// set, levels 0 or 1), or nullptr; sp: the surface albedo by band (at least one member set), or nullptr; all nullptr: the
+// plain call.  A call with components or bands is never sorted: its outputs would need a scatter of their own; nor is one with
+// a surface struct: its rows would need a gather of their own.
+static int sw_fluxes_run(rrtmg_ctx *ctx, const rrtmg_sw_args *a, const rrtmg_sw_components *cp, const rrtmg_sw_band_fluxes *bp, const rrtmg_sw_surface *sp = nullptr) {
+  if (!cp && !bp && !sp && ctx->sw_ready && a && ctx->sort_columns && !ctx->sorting && a->memspace == 1 && a->icld != 0 && a->cldfr && a->ncol >= 128 && a->nlay > 0 && a->nlay <= 256 &&
       !(a->mcica && a->irng != 0))
     return sw_sorted_call(ctx, a);
   if (!ctx->sw_ready) return ctx->fail(RRTMG_ERR_NOT_INITIALISED, "rrtmg_hip_sw_init has not been called");
@@ -434,8 +437,12 @@ static int sw_fluxes_run(rrtmg_ctx *ctx, const rrtmg_sw_args *a, const rrtmg_sw_
   hi.add(&d.h2o, a->h2ovmr, nl, "h2o", true, InPolicy::Plain, a->h2o_mul, a->h2o_div); hi.add(&d.o3, a->o3vmr, nl, "o3", true);
   hi.add(&d.co2, a->co2vmr, nl, "co2", true); hi.add(&d.ch4, a->ch4vmr, nl, "ch4", true); hi.add(&d.n2o, a->n2ovmr, nl, "n2o", true);
   hi.add(&d.o2, a->o2vmr, nl, "o2", true);
-  hi.add(&d.asdir, a->asdir, N, "asdir", true); hi.add(&d.asdif, a->asdif, N, "asdif", true);
-  hi.add(&d.aldir, a->aldir, N, "aldir", true); hi.add(&d.aldif, a->aldif, N, "aldif", true);
+  // (a broadband pair is read only where its per-band array is not given)
+  const bool bdir = sp && sp->albdir, bdif = sp && sp->albdif;
+  if (!bdir) { hi.add(&d.asdir, a->asdir, N, "asdir", true); hi.add(&d.aldir, a->aldir, N, "aldir", true); }
+  if (!bdif) { hi.add(&d.asdif, a->asdif, N, "asdif", true); hi.add(&d.aldif, a->aldif, N, "aldif", true); }
+  if (bdir) hi.add(&d.albdir, sp->albdir, (size_t)kSwNBand * N, "albdir", true);
+  if (bdif) hi.add(&d.albdif, sp->albdif, (size_t)kSwNBand * N, "albdif", true);
   hi.add(&d.coszen, a->coszen, N, "coszen", true);
   const bool clouds = d.icld >= 1;
   if (clouds) {
@@ -633,5 +640,6 @@ static int sw_fluxes_run(rrtmg_ctx *ctx, const rrtmg_sw_args *a, const rrtmg_sw_
 int sw_fluxes_impl(rrtmg_ctx *ctx, const rrtmg_sw_args *a) { return sw_fluxes_run(ctx, a, nullptr, nullptr); }
 int sw_fluxes_components_impl(rrtmg_ctx *ctx, const rrtmg_sw_args *a, const rrtmg_sw_components *c) { return sw_fluxes_run(ctx, a, c, nullptr); }
 int sw_fluxes_bands_impl(rrtmg_ctx *ctx, const rrtmg_sw_args *a, const rrtmg_sw_components *c, const rrtmg_sw_band_fluxes *b) { return sw_fluxes_run(ctx, a, c, b); }
+int sw_fluxes_surface_impl(rrtmg_ctx *ctx, const rrtmg_sw_args *a, const rrtmg_sw_surface *sf, const rrtmg_sw_components *c, const rrtmg_sw_band_fluxes *b) { return sw_fluxes_run(ctx, a, c, b, sf); }
 
 }  // namespace rrtmg

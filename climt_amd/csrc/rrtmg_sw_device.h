@@ -107,6 +107,9 @@ struct SwDev {
   int *err;
   // outputs
   double *swuflx, *swdflx, *swhr, *swuflxc, *swdflxc, *swhrc;
+  // surface albedo by band [14][col] (rrtmg_sw_surface), or null: the band rule on asdir / aldir (asdif / aldif); each on its own.
+  // (last: the offsets of the fields above are those of a library without them)
+  const double *albdir, *albdif;
 };
 
 enum { SP_H2O = 0, SP_CO2 = 1, SP_O3 = 2, SP_CH4 = 3, SP_O2 = 4 };
@@ -1038,10 +1041,13 @@ RRTMG_HD void sw_solve_thread(const SwDev &d, const SwTab &T, const double *exp_
   c.prmu0 = d.cossza[col];
   c.rmu0 = 1.0 / c.prmu0;
   c.laytrop = d.laytrop[col];
-  // albedo by band: bands 1-9 and 14 near-IR, 10-13 UV/vis (rrtmg_sw_rad.nomcica.f90:648-659)
+  // albedo by band: the caller's [band][column] rows where given (spcvrt_sw's albdir / albdif, one value per band), else the
+  // reference driver's rule: bands 1-9 and 14 near-IR, 10-13 UV/vis (rrtmg_sw_rad.nomcica.f90:648-659).  Either way one load.
   const bool vis = (c.b >= 9 && c.b <= 12);
-  const double albp = vis ? d.asdir[col] : d.aldir[col];
-  const double albd = vis ? d.asdif[col] : d.aldif[col];
+  const double *palbp = d.albdir ? d.albdir + (long)c.b * N : (vis ? d.asdir : d.aldir);
+  const double *palbd = d.albdif ? d.albdif + (long)c.b * N : (vis ? d.asdif : d.aldif);
+  const double albp = palbp[col];
+  const double albd = palbd[col];
   c.any_cloudy = false;
   c.mword = -1;
 #pragma unroll

@@ -249,8 +249,6 @@ def shortwave_device_call(self, ds):
         ncol=ncol, nlay=nlay, play=g("air_pressure"), plev=g("air_pressure_on_interface_levels"), tlay=g("air_temperature"), tlev=der["tint"].ptr,
         tsfc=g("surface_temperature"), h2o=der["h2o"].ptr, o3=g("mole_fraction_of_ozone_in_air"), co2=g("mole_fraction_of_carbon_dioxide_in_air"),
         ch4=g("mole_fraction_of_methane_in_air"), n2o=g("mole_fraction_of_nitrous_oxide_in_air"), o2=g("mole_fraction_of_oxygen_in_air"),
-        asdir=g("surface_albedo_for_direct_shortwave"), asdif=g("surface_albedo_for_diffuse_shortwave"),
-        aldir=g("surface_albedo_for_direct_near_infrared"), aldif=g("surface_albedo_for_diffuse_near_infrared"),
         coszen=der["coszen"].ptr, cldfr=g("cloud_area_fraction_in_atmosphere_layer"),
         taucld=g("shortwave_optical_thickness_due_to_cloud"), ssacld=g("single_scattering_albedo_due_to_cloud"),
         asmcld=g("cloud_asymmetry_parameter"), fsfcld=g("cloud_forward_scattering_fraction"),
@@ -262,6 +260,13 @@ def shortwave_device_call(self, ds):
         icld=self._cloud_overlap, iaer=self._aerosol_type, inflg=self._cloud_optics, iceflg=self._ice_props, liqflg=self._liq_props,
         dyofyr=day_of_year, isolvar=self._solar_var_flag, scon=float(self._solar_const),
         adjes=ds.scalars["flux_adjustment_for_earth_sun_distance"], solcycfrac=ds.scalars["solar_cycle_fraction"])
+    surface = None
+    if getattr(self, "_spectral_albedo", False):      # the resident [band][column] arrays, read in place
+        from .rrtmg.shortwave import SPECTRAL_ALBEDO_INPUTS
+        surface = {m: g(k) for k, m in SPECTRAL_ALBEDO_INPUTS.items()}
+    else:
+        inp.update(asdir=g("surface_albedo_for_direct_shortwave"), asdif=g("surface_albedo_for_diffuse_shortwave"),
+                   aldir=g("surface_albedo_for_direct_near_infrared"), aldif=g("surface_albedo_for_diffuse_near_infrared"))
     if self._mcica:
         if self._random_number_generator == 0:
             self._permute_seed = np.random.randint(0, 1024)
@@ -283,9 +288,9 @@ def shortwave_device_call(self, ds):
     if getattr(self, "_band_fluxes", False):
         from .rrtmg.shortwave import BAND_FLUX_DIAGNOSTICS
         bands = {b: w("band." + b, (14,) + il, ("num_shortwave_bands", "interface_levels", "*"), "W m^-2") for b in BAND_FLUX_DIAGNOSTICS.values()}
-    if comps or bands:
+    if comps or bands or surface:
         ds.ctx.sw_fluxes(inp, mcica=self._mcica, out=out, memspace=1, components={c: q.ptr for c, q in comps.items()} if comps else None,
-                         bands={b: q.ptr for b, q in bands.items()} if bands else None)
+                         bands={b: q.ptr for b, q in bands.items()} if bands else None, surface=surface)
     else:
         ds.ctx.sw_fluxes(inp, mcica=self._mcica, out=out, memspace=1)
     diagnostics = {

@@ -44,7 +44,7 @@ COLUMN_AXIS = dict(
     play=1, plev=1, tlay=1, tlev=1, h2o=1, o3=1, co2=1, ch4=1, n2o=1, o2=1, cfc11=1, cfc12=1, cfc22=1, ccl4=1,
     cldfr=1, cicewp=1, cliqwp=1, reice=1, reliq=1,                       # [layer][column]
     tsfc=0, asdir=0, asdif=0, aldir=0, aldif=0, coszen=0, lat=0,          # [column]
-    emis=1,                                                               # [band][column]
+    emis=1, albdir=1, albdif=1,                                           # [band][column]
     taucld=1, ssacld=1, asmcld=1, fsfcld=1, cldfmcl=1,                    # [layer][column][band | g-point]
     tauaer=2, ssaaer=2, asmaer=2, ecaer=2,                                # [band | type][layer][column]
     bndsolvar=None, indsolvar=None,

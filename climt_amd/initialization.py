@@ -308,6 +308,19 @@ def _shortwave_band_defaults(grid):
     return out
 
 
+def _shortwave_albedo_by_band(grid):
+    """The inputs of RRTMGShortwave(spectral_surface_albedo=True): the defaults of the four broadband albedos, spread over
+    the bands by the rule of the reference's driver (climt_amd.rrtmg.shortwave.SPECTRAL_ALBEDO_BAND_RULE)."""
+    from .rrtmg.shortwave import SPECTRAL_ALBEDO_BAND_RULE, SPECTRAL_ALBEDO_INPUTS
+    h, hd = tuple(grid["latitude"].shape), tuple(grid["latitude"].dims)
+    out = {}
+    for name, member in SPECTRAL_ALBEDO_INPUTS.items():
+        per_band = np.array([_DEFAULTS[src][0] for src in SPECTRAL_ALBEDO_BAND_RULE[member]], dtype=np.float64)
+        out[name] = _quantity(np.ascontiguousarray(np.broadcast_to(per_band.reshape((-1,) + (1,) * len(h)), (per_band.size,) + h)),
+                              "dimensionless", ("num_shortwave_bands",) + hd)
+    return out
+
+
 _LW_BAND_NAMES = ("surface_longwave_emissivity", "longwave_optical_thickness_due_to_cloud", "longwave_optical_thickness_due_to_aerosol")
 _SW_BAND_NAMES = ("shortwave_optical_thickness_due_to_cloud", "cloud_asymmetry_parameter", "cloud_forward_scattering_fraction",
                   "single_scattering_albedo_due_to_cloud", "shortwave_optical_thickness_due_to_aerosol", "aerosol_asymmetry_parameter",
@@ -315,6 +328,7 @@ _SW_BAND_NAMES = ("shortwave_optical_thickness_due_to_cloud", "cloud_asymmetry_p
 _COMPUTED = {"longwave_optical_depth_on_interface_levels": _gray_longwave_depth, "mole_fraction_of_ozone_in_air": _ozone}
 _COMPUTED.update({n: _longwave_band_defaults for n in _LW_BAND_NAMES})
 _COMPUTED.update({n: _shortwave_band_defaults for n in _SW_BAND_NAMES})
+_COMPUTED.update({n: _shortwave_albedo_by_band for n in ("surface_albedo_for_direct_shortwave_by_band", "surface_albedo_for_diffuse_shortwave_by_band")})
 _SUFFIX = "_on_interface_levels"
 
 

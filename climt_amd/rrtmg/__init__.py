@@ -1,4 +1,4 @@
 from .longwave import RRTMGLongwave
-from .shortwave import RRTMGShortwave
+from .shortwave import RRTMGShortwave, band_albedo
 
-__all__ = ("RRTMGShortwave", "RRTMGLongwave")
+__all__ = ("RRTMGShortwave", "RRTMGLongwave", "band_albedo")

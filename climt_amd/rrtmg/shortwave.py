@@ -47,6 +47,59 @@ BAND_FLUX_DIAGNOSTICS = {
 }
 _BIL = ["num_shortwave_bands", "interface_levels", "*"]
 
+# the inputs of RRTMGShortwave(spectral_surface_albedo=True) -> member of rrtmg_sw_surface: one albedo per band (bands in the
+# order of the band fluxes) in place of the four broadband ones, which the reference's driver spreads over the bands by a
+# fixed rule (SPECTRAL_ALBEDO_BAND_RULE: band -> the broadband input it takes; rrtmg_sw_rad.nomcica.f90:648-659)
+SPECTRAL_ALBEDO_INPUTS = {
+    "surface_albedo_for_direct_shortwave_by_band": "albdir",
+    "surface_albedo_for_diffuse_shortwave_by_band": "albdif",
+}
+BROADBAND_ALBEDO_INPUTS = ("surface_albedo_for_direct_shortwave", "surface_albedo_for_direct_near_infrared",
+                           "surface_albedo_for_diffuse_near_infrared", "surface_albedo_for_diffuse_shortwave")
+_VISIBLE_BANDS = (9, 10, 11, 12)   # band index 0..13; the others take the near-IR pair
+SPECTRAL_ALBEDO_BAND_RULE = {
+    "albdir": tuple("surface_albedo_for_direct_shortwave" if b in _VISIBLE_BANDS else "surface_albedo_for_direct_near_infrared" for b in range(14)),
+    "albdif": tuple("surface_albedo_for_diffuse_shortwave" if b in _VISIBLE_BANDS else "surface_albedo_for_diffuse_near_infrared" for b in range(14)),
+}
+
+
+def albedo_by_band_rule(asdir, asdif, aldir, aldif):
+    """-> (albdir, albdif), [14][ncol]: the four broadband albedos [ncol] spread over the bands as the reference's driver does."""
+    vis = np.zeros(14, dtype=bool)
+    vis[list(_VISIBLE_BANDS)] = True
+    pick = lambda s, l: np.where(vis[:, None], np.asarray(s, dtype=np.float64)[None, :], np.asarray(l, dtype=np.float64)[None, :])
+    return np.ascontiguousarray(pick(asdir, aldir)), np.ascontiguousarray(pick(asdif, aldif))
+
+
+def band_albedo(wavenumber_cm1, albedo):
+    """A spectral albedo curve -> the per-band input of `surface_albedo_for_*_shortwave_by_band` / rrtmg_sw_surface.
+
+    `wavenumber_cm1`: [n], increasing; `albedo`: [n] or [n][ncol].  -> [14] or [14][ncol]: for each band (limits and order of
+    rrtmg_hip_band_limits: RRTMG bands 16..29, the 820-2600 cm^-1 band last) the mean over the band's wavenumber interval of
+    the piecewise-linear curve through the points, held constant beyond its end points.  This is a FLAT average over
+    wavenumber, NOT weighted by the solar spectrum: within a wide band (8050-12850 cm^-1, say) a surface whose albedo varies
+    strongly is better represented by an average weighted with the incoming flux, which this helper does not attempt."""
+    from .._lib import band_limits
+    x = np.asarray(wavenumber_cm1, dtype=np.float64)
+    a = np.asarray(albedo, dtype=np.float64)
+    if x.ndim != 1 or x.size < 1 or a.shape[:1] != x.shape or a.ndim > 2 or np.any(np.diff(x) <= 0.0):
+        raise ValueError("band_albedo: wavenumber_cm1 [n] strictly increasing, albedo [n] or [n][ncol]")
+    lo, hi = band_limits("sw")
+    a2 = a.reshape(x.size, -1)
+
+    def curve(q):   # the curve at the points q, [len(q)][ncol]
+        i = np.clip(np.searchsorted(x, q), 1, max(x.size - 1, 1))
+        if x.size == 1:
+            return np.repeat(a2[:1], len(q), axis=0)
+        t = np.clip((q - x[i - 1]) / (x[i] - x[i - 1]), 0.0, 1.0)[:, None]
+        return a2[i - 1] * (1.0 - t) + a2[i] * t
+    out = np.empty((lo.size, a2.shape[1]))
+    for b in range(lo.size):
+        q = np.concatenate(([lo[b]], x[(x > lo[b]) & (x < hi[b])], [hi[b]]))
+        v = curve(q)
+        out[b] = (0.5 * (v[1:] + v[:-1]) * np.diff(q)[:, None]).sum(axis=0) / (hi[b] - lo[b])
+    return out[:, 0] if a.ndim == 1 else out
+
 
 class RRTMGShortwave(TendencyComponent):
     """The Rapid Radiative Transfer Model (RRTMG), shortwave, on AMD MI355X."""
@@ -115,17 +168,32 @@ class RRTMGShortwave(TendencyComponent):
             props.update({k: _prop(_BIL, "W m^-2") for k in BAND_FLUX_DIAGNOSTICS})
         return props
 
+    @classmethod
+    def input_properties_for(cls, spectral_surface_albedo=False):
+        """The input_properties of an instance made with this option: the class dict itself, or a new dict of it with the two
+        albedos by band (bands x columns, dimensionless) in place of the four broadband ones."""
+        if not spectral_surface_albedo:
+            return cls.input_properties
+        props = {k: v for k, v in cls.input_properties.items() if k not in BROADBAND_ALBEDO_INPUTS}
+        props.update({k: _prop(["num_shortwave_bands", "*"], "dimensionless") for k in SPECTRAL_ALBEDO_INPUTS})
+        return props
+
     def __init__(self, cloud_overlap_method=None, cloud_optical_properties="liquid_and_ice_clouds",
                  cloud_ice_properties="ebert_curry_two", cloud_liquid_water_properties="radius_dependent_absorption",
                  solar_variability_method=0, use_solar_constant_from_fortran=False, ignore_day_of_year=False,
                  facular_sunspot_amplitude=None, solar_variability_by_band=None, aerosol_type="no_aerosol", mcica=False,
                  random_number_generator="mersenne_twister", device=0, flux_components=False, band_fluxes=False,
-                 **kwargs):
+                 spectral_surface_albedo=False, **kwargs):
         """Same keyword arguments and defaults as climt.RRTMGShortwave (sw/component.py:179-194); the additions are `device`
         (GPU ordinal) and `flux_components`: True adds the downward flux split into direct and diffuse parts -- all bands,
         UV/visible bands, near-IR bands, and all bands clear sky (FLUX_COMPONENT_DIAGNOSTICS) -- to this instance's
         diagnostics; `band_fluxes`: True adds the up / down fluxes (all sky, clear sky) and the direct beam by spectral
-        band (BAND_FLUX_DIAGNOSTICS); the class attributes are unchanged."""
+        band (BAND_FLUX_DIAGNOSTICS); `spectral_surface_albedo`: True replaces, in this instance's inputs, the four broadband
+        surface albedos by one direct and one diffuse albedo per band (SPECTRAL_ALBEDO_INPUTS; band_albedo() makes them from
+        a spectral curve); the class attributes are unchanged."""
+        self._spectral_albedo = bool(spectral_surface_albedo)
+        if self._spectral_albedo:
+            self.input_properties = self.input_properties_for(True)
         self._flux_components = bool(flux_components)
         self._band_fluxes = bool(band_fluxes)
         if self._flux_components:
@@ -203,8 +271,6 @@ class RRTMGShortwave(TendencyComponent):
             tsfc=state["surface_temperature"], h2o=Q, o3=state["mole_fraction_of_ozone_in_air"],
             co2=state["mole_fraction_of_carbon_dioxide_in_air"], ch4=state["mole_fraction_of_methane_in_air"],
             n2o=state["mole_fraction_of_nitrous_oxide_in_air"], o2=state["mole_fraction_of_oxygen_in_air"],
-            asdir=state["surface_albedo_for_direct_shortwave"], asdif=state["surface_albedo_for_diffuse_shortwave"],
-            aldir=state["surface_albedo_for_direct_near_infrared"], aldif=state["surface_albedo_for_diffuse_near_infrared"],
             coszen=np.cos(state["zenith_angle"]), cldfr=state["cloud_area_fraction_in_atmosphere_layer"],
             taucld=state["shortwave_optical_thickness_due_to_cloud"], ssacld=state["single_scattering_albedo_due_to_cloud"],
             asmcld=state["cloud_asymmetry_parameter"], fsfcld=state["cloud_forward_scattering_fraction"],
@@ -218,6 +284,12 @@ class RRTMGShortwave(TendencyComponent):
             liqflg=self._liq_props, dyofyr=day_of_year, isolvar=self._solar_var_flag, scon=float(self._solar_const),
             adjes=state["flux_adjustment_for_earth_sun_distance"].item(), solcycfrac=state["solar_cycle_fraction"].item(), **scales
         )
+        if self._spectral_albedo:
+            surface = {m: state[k] for k, m in SPECTRAL_ALBEDO_INPUTS.items()}
+        else:
+            surface = None
+            inp.update(asdir=state["surface_albedo_for_direct_shortwave"], asdif=state["surface_albedo_for_diffuse_shortwave"],
+                       aldir=state["surface_albedo_for_direct_near_infrared"], aldif=state["surface_albedo_for_diffuse_near_infrared"])
         if self._mcica:
             # a fresh seed on every call, drawn exactly as the reference does (sw/component.py:537-545)
             if self._random_number_generator == 0:
@@ -234,7 +306,9 @@ class RRTMGShortwave(TendencyComponent):
         if self._flux_components or self._band_fluxes:
             comps = {c: diagnostics[k] for k, c in FLUX_COMPONENT_DIAGNOSTICS.items()} if self._flux_components else None
             bands = {b: diagnostics[k] for k, b in BAND_FLUX_DIAGNOSTICS.items()} if self._band_fluxes else None
-            self._ctx.sw_fluxes(inp, mcica=self._mcica, out=out, components=comps, bands=bands)
+            self._ctx.sw_fluxes(inp, mcica=self._mcica, out=out, components=comps, bands=bands, surface=surface)
+        elif surface is not None:
+            self._ctx.sw_fluxes(inp, mcica=self._mcica, out=out, surface=surface)
         else:
             self._ctx.sw_fluxes(inp, mcica=self._mcica, out=out)
         diagnostics["air_temperature_tendency_from_shortwave"][:] = tendencies["air_temperature"]

@@ -296,6 +296,27 @@ typedef struct rrtmg_sw_band_fluxes {
  * bits with or without bands.  Host pointers: downloaded behind the same synchronise as the six outputs; device pointers
  * in deferred mode: the call returns once enqueued.  A call with bands is never column-sorted. */
 int rrtmg_hip_sw_fluxes_bands(rrtmg_ctx *ctx, const rrtmg_sw_args *a, const rrtmg_sw_components *c, const rrtmg_sw_band_fluxes *b);
+/* Shortwave SURFACE ALBEDO BY BAND: what the reference's solver takes (spcvrt_sw / spcvmc_sw: albdir(nbndsw), albdif(nbndsw)),
+ * where rrtmg_sw_args carries the four broadband numbers of the reference's driver, which spreads them over the bands by a
+ * fixed rule (rrtmg_sw_rad.nomcica.f90:648-659: bands 10-13 asdir / asdif, bands 1-9 and 14 aldir / aldif).  Both members are
+ * [14][ncol], dimensionless, band index 0..13 = the reference's band order (RRTMG bands 16..29: band 29, 820-2600 cm^-1, is
+ * LAST; rrtmg_hip_band_limits), in the memspace of the rrtmg_sw_args; NULL = not given.  Each member stands alone: without
+ * albdir the direct albedo is asdir / aldir by the band rule, without albdif the diffuse albedo is asdif / aldif.  With both
+ * given the four broadband pointers of the rrtmg_sw_args are not read and may be NULL.  The values are not range-checked (the
+ * reference has no check).  Per-band arrays filled by the band rule give the bits of the call without them.
+ * The versioned structs and RRTMG_HIP_ABI_VERSION are unchanged: the struct checks its own struct_size, and a caller probes
+ * for the feature by the presence of the symbol rrtmg_hip_sw_fluxes_surface (dlsym). */
+typedef struct rrtmg_sw_surface {
+  int32_t struct_size;                 /* sizeof(rrtmg_sw_surface) of the caller's header: required */
+  int32_t reserved;                    /* 0 */
+  const double *albdir, *albdif;       /* [14][ncol]; NULL = not given */
+} rrtmg_sw_surface;
+/* rrtmg_hip_sw_fluxes_bands with the surface albedo by band (c and b may be NULL).  surface == NULL, or both members NULL, is
+ * exactly rrtmg_hip_sw_fluxes_bands(ctx, a, c, b); a struct_size that is not sizeof(rrtmg_sw_surface) is refused
+ * (RRTMG_ERR_ARG) before anything is enqueued.  Host pointers are uploaded like every other input; device pointers are read
+ * in place, and in deferred mode the call returns once enqueued.  A call with a surface struct is never column-sorted. */
+int rrtmg_hip_sw_fluxes_surface(rrtmg_ctx *ctx, const rrtmg_sw_args *a, const rrtmg_sw_surface *surface, const rrtmg_sw_components *c,
+                                const rrtmg_sw_band_fluxes *b);
 /* Band limits in cm^-1: spectrum 0 = shortwave (14 values each, bands 16..29 in that order), 1 = longwave (16 values, bands
  * 1..16; hi - lo is the longwave's delwave).  Host arrays; either may be NULL.  Returns the number of bands, or -1 for another spectrum. */
 int rrtmg_hip_band_limits(int spectrum, double *wavenumber_lo, double *wavenumber_hi);

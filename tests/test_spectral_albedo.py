@@ -1,0 +1,336 @@
+"""CPU tests of the shortwave surface albedo by band (rrtmg_hip_sw_fluxes_surface, Context.sw_fluxes(surface=...),
+RRTMGShortwave(spectral_surface_albedo=True), climt_amd.rrtmg.band_albedo): the reference driver shim against the reference
+binder, the committed fixtures against a fresh run of the reference, the device functions (host emulation,
+tests/emu_albedo) against the fixtures, the C entry point's struct rules, the helper's values, the instance properties and
+defaults, and the column slicing."""
+import ctypes as C
+import json
+import os
+import re
+import shutil
+import subprocess
+
+import numpy as np
+import pytest
+
+import albedo_cases as A
+import band_cases as B
+from helpers import CPDAIR, GOLDEN, SW_DATA, SwArgs, _CONST_VEC, _SW_FIELDS, _SW_FLAGS, _fill, maxdiff
+from climt_amd._lib import SW_OUT, SwBandFluxes, SwSurface
+
+ROOT = A.ROOT
+TIGHT = 5.0e-9       # the project's bound for committed fixtures, fluxes and heating rates alike (tests/test_gpu_parity.py:61)
+EMU = os.path.join(ROOT, "tests", "_emu_albedo", "librrtmg_emu_albedo.so")
+FC = os.environ.get("FC", "/opt/rocm/lib/llvm/bin/flang")
+RRTMG_ERR_ARG = 4
+
+
+def _reference_present():
+    from oracle import ref_driver
+    return ref_driver.available("sw") and shutil.which(FC) is not None
+
+
+needs_reference = pytest.mark.skipif(not _reference_present(), reason="oracle/_ref (the reference Fortran) or flang not present")
+
+
+@pytest.fixture(scope="module")
+def shim():
+    subprocess.check_call([os.path.join(ROOT, "tests", "refshim", "build_albedo.sh")])
+    assert A.shim_available()
+
+
+@needs_reference
+@pytest.mark.parametrize("case", list(A.CASES))
+def test_shim_with_the_band_rule_is_the_binder(shim, case):
+    """albdir / albdif filled by the driver's band rule from the four broadband values: the shim's six outputs == the
+    binder's, bit for bit -- and with the case's free albedos they are not."""
+    _, binder, ruled, free = A.reference(case)
+    for k in A.OUTPUTS:
+        assert np.array_equal(ruled[k], binder[k]), (case, k, maxdiff(ruled[k], binder[k]))
+    assert maxdiff(free["swuflx"], binder["swuflx"]) > 1.0e-3 or case == "lowsun_night"
+
+
+@needs_reference
+@pytest.mark.parametrize("case", list(A.CASES))
+def test_fixtures_regenerate_bit_for_bit(shim, case):
+    fresh = A.fixture_arrays(case)
+    z = np.load(os.path.join(GOLDEN, "ref_albedo_%s.npz" % case))
+    assert sorted(z.files) == sorted(fresh), case
+    for k in z.files:
+        assert np.array_equal(z[k], fresh[k]), (case, k)
+
+
+def test_fixtures_hold_what_the_cases_ask_for():
+    assert {A.load_case(c)[0]["play"].shape[0] for c in A.CASES} == {60, 100}
+    for case in A.CASES:
+        assert os.path.getsize(os.path.join(GOLDEN, "ref_albedo_%s.npz" % case)) <= 200729, case
+        c, _, exp = A.load_case(case)
+        nlay, ncol = c["play"].shape
+        assert set(exp) == set(A.OUTPUTS) and exp["swuflx"].shape == (nlay + 1, ncol) and exp["swhr"].shape == (nlay, ncol)
+        for k in ("albdir", "albdif"):
+            v = c[k]
+            assert v.shape == (14, ncol) and v.min() >= 0.02 and v.max() <= 0.95
+            assert all(len(set(col)) == 14 for col in v.T), (case, k)      # different in every band
+        assert np.all(c["albdir"] != c["albdif"])
+        snow = c["albdir"][:, -1]
+        assert snow[9:13].min() > 0.85 and snow[0:5].max() < 0.2
+    assert tuple(A.load_case("lowsun_night")[0]["coszen"][:3]) == B.LOW_SUN
+
+
+def emu_surface(inp, mcica, surface, bands=False, struct_size=None):
+    """The device functions with SwDev::albdir / albdif set from `surface` (None, or a dict of [14][ncol] arrays / None), run
+    on the host -> (rc, message, plain outputs, band arrays or None)."""
+    csrc = os.path.join(ROOT, "climt_amd", "csrc")
+    if not os.path.exists(EMU) or os.path.getmtime(EMU) < max(os.path.getmtime(os.path.join(csrc, f)) for f in os.listdir(csrc)):
+        subprocess.check_call([os.path.join(ROOT, "tests", "emu_albedo", "build.sh")])
+    lib = C.CDLL(EMU)
+    nlay, ncol = inp["play"].shape
+    keep = []
+    a = SwArgs()
+    a.ncol, a.nlay, a.memspace, a.mcica = ncol, nlay, 0, int(bool(mcica))
+    a.icld, a.inflgsw, a.iceflgsw, a.liqflgsw, a.dyofyr = 1, 2, 1, 1, 1
+    a.adjes, a.scon, a.solcycfrac = float(inp.get("adjes", 1.0)), float(inp.get("scon", 1367.0)), float(inp.get("solcycfrac", 0.0))
+    _fill(a, inp, _SW_FIELDS, _SW_FLAGS, keep)
+    out = {k: np.zeros((nlay + lev, ncol)) for k, lev in SW_OUT}
+    for k, _ in SW_OUT:
+        setattr(a, k, out[k].ctypes.data)
+    sf = None
+    if surface is not None:
+        sf = SwSurface()
+        sf.struct_size = C.sizeof(SwSurface) if struct_size is None else struct_size
+        for k, v in surface.items():
+            if v is not None:
+                keep.append(np.ascontiguousarray(v, dtype=np.float64))
+                setattr(sf, k, keep[-1].ctypes.data)
+    band, b = None, None
+    if bands:
+        band = B.band_arrays("sw", nlay, ncol)
+        b = SwBandFluxes()
+        b.struct_size, b.levels = C.sizeof(b), 0
+        for k, v in band.items():
+            setattr(b, k, v.ctypes.data)
+    eb = C.create_string_buffer(512)
+    rc = lib.emu_sw_surface(C.byref(a), C.byref(sf) if sf is not None else None, C.byref(b) if b is not None else None, SW_DATA.encode(),
+                            C.c_double(CPDAIR), _CONST_VEC.ctypes.data_as(C.c_void_p), eb, 512)
+    return rc, eb.value.decode(), out, band
+
+
+@pytest.mark.parametrize("case", list(A.CASES))
+def test_emulated_surface_matches_reference(case):
+    """sw_solve_thread's per-band albedo load on the host against the reference's solver with the same per-band albedos."""
+    c, mcica, exp = A.load_case(case)
+    plain, surface = A.split_surface(c)
+    rc, msg, out, _ = emu_surface(plain, mcica, surface)
+    assert rc == 0, msg
+    for k in A.OUTPUTS:
+        d = maxdiff(out[k], exp[k])
+        print(case, k, d)
+        assert d <= TIGHT, (case, k, d)
+
+
+@pytest.mark.parametrize("case", ["clear_L60", "overcast_L60", "mcica_kiss_maxrand"])
+def test_emulated_struct_rules(case):
+    """A NULL struct and a struct without members are the plain call; per-band arrays filled by the band rule give its bits;
+    each member falls back on its own; with both members the four broadband pointers may be NULL; a wrong struct_size is
+    RRTMG_ERR_ARG."""
+    c, mcica, _ = A.load_case(case)
+    plain, surface = A.split_surface(c)
+    rc, msg, base, base_b = emu_surface(plain, mcica, None, bands=True)
+    assert rc == 0, msg
+    ruled = dict(zip(("albdir", "albdif"), A.band_rule(plain)))
+
+    def same(surf, inp=plain):
+        rc, msg, out, band = emu_surface(inp, mcica, surf, bands=True)
+        assert rc == 0, msg
+        return all(np.array_equal(out[k], base[k]) for k in base) and all(np.array_equal(band[m], base_b[m]) for m in base_b)
+    assert same({"albdir": None, "albdif": None})
+    assert same(ruled)
+    assert same({"albdir": ruled["albdir"], "albdif": None}) and same({"albdir": None, "albdif": ruled["albdif"]})
+    no_broadband = {k: v for k, v in plain.items() if k not in ("asdir", "asdif", "aldir", "aldif")}
+    assert same(ruled, no_broadband)
+    # one member free, the other by the rule: the free one is used, the missing one falls back
+    rc, msg, one, _ = emu_surface(plain, mcica, {"albdir": surface["albdir"], "albdif": None})
+    assert rc == 0, msg
+    rc, msg, want, _ = emu_surface(no_broadband, mcica, {"albdir": surface["albdir"], "albdif": ruled["albdif"]})
+    assert rc == 0, msg
+    assert all(np.array_equal(one[k], want[k]) for k in want) and not np.array_equal(one["swuflx"], base["swuflx"])
+    # a member missing AND its broadband pair missing: refused
+    rc, msg, _, _ = emu_surface(no_broadband, mcica, {"albdir": surface["albdir"], "albdif": None})
+    assert rc == RRTMG_ERR_ARG, (rc, msg)
+    rc, msg, _, _ = emu_surface(plain, mcica, surface, struct_size=C.sizeof(SwSurface) - 8)
+    assert rc == RRTMG_ERR_ARG and "struct_size" in msg
+
+
+def test_emulated_band_independence_and_surface_closure():
+    """Changing band k's albedo leaves every other band's rows bit-identical; at the surface, per band,
+    up == albdir * dndir + albdif * (dn - dndir) within the rounding bound (clear-sky stream; all sky on overcast columns)."""
+    for case, members in (("clear_L60", ("upc", "dnc", "dndirc")), ("overcast_L60", ("up", "dn", "dndir")), ("lowsun_night", ("upc", "dnc", "dndirc"))):
+        c, mcica, _ = A.load_case(case)
+        plain, surface = A.split_surface(c)
+        rc, msg, _, band = emu_surface(plain, mcica, surface, bands=True)
+        assert rc == 0, msg
+        up, dn, dr = (band[m][:, 0] for m in members)
+        want = surface["albdir"] * dr + surface["albdif"] * (dn - dr)
+        ok = up > 1.0e-6
+        assert ok.sum() >= 14 and np.all(np.abs(up - want)[ok] <= B.SUM_BOUND * up[ok]), (case, (np.abs(up - want)[ok] / up[ok]).max() / B.EPS)
+    c, mcica, _ = A.load_case("overcast_L60")
+    plain, surface = A.split_surface(c)
+    _, _, _, base = emu_surface(plain, mcica, surface, bands=True)
+    for k in (0, 8, 10, 13):
+        s2 = {m: v.copy() for m, v in surface.items()}
+        s2["albdir"][k] = 0.5 * s2["albdir"][k] + 0.01
+        s2["albdif"][k] = 0.5 * s2["albdif"][k] + 0.01
+        _, _, _, band = emu_surface(plain, mcica, s2, bands=True)
+        others = [b for b in range(14) if b != k]
+        for m in ("up", "dn", "dndir", "upc", "dnc", "dndirc"):
+            assert np.array_equal(band[m][others], base[m][others]), (k, m)
+        assert np.all(band["up"][k, 0] != base["up"][k, 0]) or base["up"][k, 0].max() == 0.0, k
+
+
+def test_struct_mirror_matches_the_header(tmp_path):
+    cc = shutil.which("cc") or shutil.which("gcc") or shutil.which("clang") or "/opt/rocm/lib/llvm/bin/clang"
+    fields = ("struct_size", "reserved", "albdir", "albdif")
+    prints = ['printf("%zu\\n", sizeof(rrtmg_sw_surface));'] + ['printf("%%zu\\n", offsetof(rrtmg_sw_surface, %s));' % f for f in fields]
+    src = tmp_path / "sizes.c"
+    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "rrtmg_hip.h"\nint main(void) { %s return 0; }\n' % " ".join(prints))
+    exe = tmp_path / "sizes"
+    subprocess.check_call([cc, "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)])
+    got = [int(x) for x in subprocess.run([str(exe)], capture_output=True, text=True, check=True).stdout.split()]
+    assert got == [C.sizeof(SwSurface)] + [getattr(SwSurface, f).offset for f in fields]
+    assert [n for n, _ in SwSurface._fields_] == list(fields)
+
+
+def test_library_exports_the_entry_and_checks_struct_size_first():
+    """The symbol is exported and RRTMG_HIP_ABI_VERSION unchanged; a wrong struct_size is RRTMG_ERR_ARG before anything else
+    is looked at -- on a context that has no tables, and on a machine without a GPU."""
+    from climt_amd._lib import LIB_PATH, load_library
+    assert os.path.exists(LIB_PATH)
+    syms = subprocess.run(["nm", "-D", "--defined-only", LIB_PATH], capture_output=True, text=True, check=True).stdout
+    assert " rrtmg_hip_sw_fluxes_surface\n" in syms
+    hdr = open(os.path.join(ROOT, "include", "rrtmg_hip.h")).read()
+    assert "typedef struct rrtmg_sw_surface" in hdr and re.search(r"#define RRTMG_HIP_ABI_VERSION 5\b", hdr)
+    lib = load_library()
+    h = C.c_void_p()
+    lib.rrtmg_hip_create(C.byref(h), 0)      # (without a GPU: an error status, and a context that can report errors)
+    assert h.value
+    try:
+        a = SwArgs(); a.struct_size = C.sizeof(SwArgs)
+        bad = SwSurface(); bad.struct_size = C.sizeof(SwSurface) + 8
+        assert lib.rrtmg_hip_sw_fluxes_surface(h, C.byref(a), C.byref(bad), None, None) == RRTMG_ERR_ARG
+        assert "rrtmg_sw_surface: struct_size" in lib.rrtmg_hip_last_error(h).decode()
+        ok = SwSurface(); ok.struct_size = C.sizeof(SwSurface)      # no member: the plain call's own refusal (no tables)
+        rc = lib.rrtmg_hip_sw_fluxes_surface(h, C.byref(a), C.byref(ok), None, None)
+        assert rc != 0 and "struct_size" not in lib.rrtmg_hip_last_error(h).decode()
+    finally:
+        lib.rrtmg_hip_destroy(h)
+
+
+def test_python_layer_checks_the_surface_dict():
+    from climt_amd._lib import _surface_struct
+    keep = []
+    s = _surface_struct({"albdir": np.full((14, 3), 0.2), "albdif": 4096}, 3, keep)
+    assert s.struct_size == C.sizeof(SwSurface) and s.albdir == keep[0].ctypes.data and s.albdif == 4096
+    assert not _surface_struct({"albdir": None}, 3, keep).albdir
+    with pytest.raises(KeyError):
+        _surface_struct({"albedo": np.zeros((14, 3))}, 3, keep)
+    with pytest.raises(ValueError):
+        _surface_struct({"albdir": np.zeros((3, 14))}, 3, keep)
+
+
+def test_band_albedo_values():
+    from climt_amd._lib import band_limits
+    from climt_amd.rrtmg import band_albedo
+    lo, hi = band_limits("sw")
+    # a constant curve: that constant in every band (one point, two points, many points)
+    for x in ([10000.0], [5000.0, 20000.0], np.linspace(500.0, 60000.0, 97)):
+        assert np.allclose(band_albedo(x, np.full(len(x), 0.37)), 0.37, rtol=0, atol=1e-15)
+    # a step at 14500 cm^-1 (0.1 below, 0.8 above): band 9 (12850-16000) holds it
+    eps = 1.0e-6
+    got = band_albedo([800.0, 14500.0 - eps, 14500.0 + eps, 50000.0], [0.1, 0.1, 0.8, 0.8])
+    k = int(np.flatnonzero((lo < 14500.0) & (hi > 14500.0))[0])
+    assert k == 8 and (lo[k], hi[k]) == (12850.0, 16000.0)
+    frac = (16000.0 - 14500.0) / (16000.0 - 12850.0)
+    assert abs(got[k] - (0.1 + 0.7 * frac)) <= 1e-9
+    assert np.allclose(got[hi <= 14500.0], 0.1, atol=1e-15) and np.allclose(got[lo >= 14500.0], 0.8, atol=1e-15)
+    assert got[13] == pytest.approx(0.1, abs=1e-15)      # band 29 (820-2600) is last
+    # a ramp: the mean of a linear curve over a band is its value at the band's centre; held constant beyond the end points
+    ramp = band_albedo([2600.0, 12850.0], [0.0, 1.0])
+    for b in range(8):
+        assert ramp[b] == pytest.approx((0.5 * (lo[b] + hi[b]) - 2600.0) / 10250.0, abs=1e-14)
+    assert np.allclose(ramp[8:13], 1.0) and ramp[13] == 0.0
+    # columns: [n][ncol] -> [14][ncol], column by column
+    two = band_albedo([2600.0, 12850.0], np.array([[0.0, 0.3], [1.0, 0.3]]))
+    assert two.shape == (14, 2) and np.array_equal(two[:, 0], ramp) and np.allclose(two[:, 1], 0.3, atol=1e-15)
+    assert "NOT weighted by the solar spectrum" in band_albedo.__doc__
+    with pytest.raises(ValueError):
+        band_albedo([2.0, 1.0], [0.1, 0.2])
+
+
+NEW_INPUTS = ("surface_albedo_for_direct_shortwave_by_band", "surface_albedo_for_diffuse_shortwave_by_band")
+OLD_INPUTS = ("surface_albedo_for_direct_shortwave", "surface_albedo_for_direct_near_infrared",
+              "surface_albedo_for_diffuse_near_infrared", "surface_albedo_for_diffuse_shortwave")
+
+
+def test_spectral_albedo_properties():
+    from climt_amd.rrtmg import shortwave
+    cls = shortwave.RRTMGShortwave
+    ref = json.load(open(os.path.join(GOLDEN, "reference_interface.json")))
+    before = cls.input_properties
+    assert cls.input_properties_for() is before and cls.input_properties_for(False) is before
+    props = cls.input_properties_for(True)
+    assert set(props) == (set(before) - set(OLD_INPUTS)) | set(NEW_INPUTS)
+    for k in NEW_INPUTS:
+        assert props[k] == {"dims": ["num_shortwave_bands", "*"], "units": "dimensionless"}
+    for k, v in props.items():
+        assert k in NEW_INPUTS or v is before[k]
+    assert cls.input_properties is before and json.loads(json.dumps(before)) == ref["RRTMGShortwave"]["input_properties"]
+    assert set(shortwave.SPECTRAL_ALBEDO_INPUTS) == set(NEW_INPUTS) and set(shortwave.BROADBAND_ALBEDO_INPUTS) == set(OLD_INPUTS)
+    rule = shortwave.SPECTRAL_ALBEDO_BAND_RULE
+    assert [("near_infrared" not in n) for n in rule["albdir"]] == [b in A.VISIBLE for b in range(14)]
+    assert [("near_infrared" not in n) for n in rule["albdif"]] == [b in A.VISIBLE for b in range(14)]
+    c = dict(asdir=np.array([0.1, 0.2]), asdif=np.array([0.3, 0.4]), aldir=np.array([0.5, 0.6]), aldif=np.array([0.7, 0.8]))
+    got = shortwave.albedo_by_band_rule(c["asdir"], c["asdif"], c["aldir"], c["aldif"])
+    want = A.band_rule(c)
+    assert np.array_equal(got[0], want[0]) and np.array_equal(got[1], want[1])
+
+
+def test_spectral_albedo_default_state():
+    """get_default_state for an object with the spectral instance's input_properties: the two quantities by band, filled by
+    the band rule from the defaults of the four broadband ones (no instance is made here: that needs a GPU)."""
+    import climt_amd
+    from climt_amd.initialization import _DEFAULTS
+    from climt_amd.rrtmg.shortwave import RRTMGShortwave
+
+    class Stub:
+        input_properties = RRTMGShortwave.input_properties_for(True)
+    state = climt_amd.get_default_state([Stub()])
+    ncolumn = int(np.prod(state["latitude"].shape))
+    for k in NEW_INPUTS:
+        q = state[k]
+        assert q.dims[0] == "num_shortwave_bands" and q.shape[0] == 14 and int(np.prod(q.shape[1:])) == ncolumn
+        assert q.attrs["units"] == "dimensionless"
+        assert np.all(q.values == _DEFAULTS["surface_albedo_for_direct_shortwave"][0])      # the four defaults are one number today
+    for k in OLD_INPUTS:
+        assert k not in state
+    # the rule itself, with four different defaults
+    saved = {k: _DEFAULTS[k] for k in OLD_INPUTS}
+    try:
+        for i, k in enumerate(OLD_INPUTS):
+            _DEFAULTS[k] = ((0.1, 0.2, 0.3, 0.4)[i],) + tuple(saved[k][1:])
+        state = climt_amd.get_default_state([Stub()])
+        vis = np.array([b in A.VISIBLE for b in range(14)])
+        d = state[NEW_INPUTS[0]].values.reshape(14, -1)
+        assert np.all(d[vis] == 0.1) and np.all(d[~vis] == 0.2)
+        f = state[NEW_INPUTS[1]].values.reshape(14, -1)
+        assert np.all(f[vis] == 0.4) and np.all(f[~vis] == 0.3)
+    finally:
+        _DEFAULTS.update(saved)
+
+
+def test_slice_columns_knows_the_albedo_arrays():
+    from climt_amd.distributed import COLUMN_AXIS, slice_columns
+    assert COLUMN_AXIS["albdir"] == 1 and COLUMN_AXIS["albdif"] == 1
+    inp = dict(albdir=np.arange(14 * 10, dtype=float).reshape(14, 10), albdif=-np.arange(14 * 10, dtype=float).reshape(14, 10), asdir=np.arange(10.0))
+    out = slice_columns(inp, 3, 7)
+    assert np.array_equal(out["albdir"], inp["albdir"][:, 3:7]) and np.array_equal(out["albdif"], inp["albdif"][:, 3:7])
+    assert out["albdir"].flags.c_contiguous and np.array_equal(out["asdir"], inp["asdir"][3:7])
