@@ -328,6 +328,32 @@ static int checked_call(rrtmg_ctx *ctx, const Args *a, const char *what, Impl im
   return impl(ctx, &own);
 }
 
+// The optional structs of the flux calls are checked before anything is enqueued: 0, or the status ctx->fail returned.
+template <class S>
+static int check_struct(rrtmg_ctx *ctx, const S *p, const char *name) {
+  if (p && (size_t)p->struct_size != sizeof(S))
+    return ctx->fail(RRTMG_ERR_ARG, "%s: struct_size %d is not sizeof(%s) = %zu of this library: set it to sizeof of the struct", name, (int)p->struct_size, name, sizeof(S));
+  return 0;
+}
+template <class S>
+static int check_band_struct(rrtmg_ctx *ctx, const S *b, const char *name) {
+  if (int rc = check_struct(ctx, b, name)) return rc;
+  if (b && b->levels != 0 && b->levels != 1) return ctx->fail(RRTMG_ERR_ARG, "%s: levels %d is neither 0 (all interface levels) nor 1 (surface and top)", name, (int)b->levels);
+  return 0;
+}
+
+// Every shortwave flux entry point: sf, then b (size, then levels), then c; a struct without a member set is the call without it.
+static int sw_fluxes_checked(rrtmg_ctx *ctx, const rrtmg_sw_args *a, const rrtmg_sw_surface *sf, const rrtmg_sw_components *c, const rrtmg_sw_band_fluxes *b) {
+  if (!ctx) return RRTMG_ERR_ARG;
+  if (int rc = check_struct(ctx, sf, "rrtmg_sw_surface")) return rc;
+  if (sf && !(sf->albdir || sf->albdif)) sf = nullptr;
+  if (int rc = check_band_struct(ctx, b, "rrtmg_sw_band_fluxes")) return rc;
+  if (b && !(b->up || b->dn || b->upc || b->dnc || b->dndir || b->dndirc)) b = nullptr;
+  if (int rc = check_struct(ctx, c, "rrtmg_sw_components")) return rc;
+  if (c && !(c->dirdflx || c->difdflx || c->dirdnuv || c->difdnuv || c->dirdnir || c->difdnir || c->dirdflxc || c->difdflxc)) c = nullptr;
+  return checked_call(ctx, a, "rrtmg_sw", [sf, c, b](rrtmg_ctx *x, const rrtmg_sw_args *y) { return sw_fluxes_impl(x, y, sf, c, b); });
+}
+
 extern "C" {
 
 #ifndef RRTMG_SRC_HASH
@@ -468,55 +494,14 @@ long rrtmg_hip_get_table(rrtmg_ctx *ctx, const char *name, double *out, long cap
   return n;
 }
 
-int rrtmg_hip_sw_fluxes(rrtmg_ctx *ctx, const rrtmg_sw_args *a) { return checked_call(ctx, a, "rrtmg_sw", sw_fluxes_impl); }
+int rrtmg_hip_sw_fluxes(rrtmg_ctx *ctx, const rrtmg_sw_args *a) { return sw_fluxes_checked(ctx, a, nullptr, nullptr, nullptr); }
 int rrtmg_hip_lw_fluxes(rrtmg_ctx *ctx, const rrtmg_lw_args *a) { return checked_call(ctx, a, "rrtmg_lw", lw_fluxes_impl); }
-int rrtmg_hip_sw_fluxes_components(rrtmg_ctx *ctx, const rrtmg_sw_args *a, const rrtmg_sw_components *c) {
-  if (!ctx) return RRTMG_ERR_ARG;
-  if (c && (size_t)c->struct_size != sizeof(rrtmg_sw_components))
-    return ctx->fail(RRTMG_ERR_ARG, "rrtmg_sw_components: struct_size %d is not sizeof(rrtmg_sw_components) = %zu of this library: set it to sizeof of the struct",
-                     (int)c->struct_size, sizeof(rrtmg_sw_components));
-  if (!c || !(c->dirdflx || c->difdflx || c->dirdnuv || c->difdnuv || c->dirdnir || c->difdnir || c->dirdflxc || c->difdflxc))
-    return rrtmg_hip_sw_fluxes(ctx, a);
-  return checked_call(ctx, a, "rrtmg_sw", [c](rrtmg_ctx *x, const rrtmg_sw_args *b) { return sw_fluxes_components_impl(x, b, c); });
-}
-// band fluxes: the struct checks (size, levels) come before anything is enqueued; a request without a member is the call without bands
-int rrtmg_hip_sw_fluxes_bands(rrtmg_ctx *ctx, const rrtmg_sw_args *a, const rrtmg_sw_components *c, const rrtmg_sw_band_fluxes *b) {
-  if (!ctx) return RRTMG_ERR_ARG;
-  if (b && (size_t)b->struct_size != sizeof(rrtmg_sw_band_fluxes))
-    return ctx->fail(RRTMG_ERR_ARG, "rrtmg_sw_band_fluxes: struct_size %d is not sizeof(rrtmg_sw_band_fluxes) = %zu of this library: set it to sizeof of the struct",
-                     (int)b->struct_size, sizeof(rrtmg_sw_band_fluxes));
-  if (b && b->levels != 0 && b->levels != 1) return ctx->fail(RRTMG_ERR_ARG, "rrtmg_sw_band_fluxes: levels %d is neither 0 (all interface levels) nor 1 (surface and top)", (int)b->levels);
-  if (!b || !(b->up || b->dn || b->upc || b->dnc || b->dndir || b->dndirc)) return rrtmg_hip_sw_fluxes_components(ctx, a, c);
-  if (c && (size_t)c->struct_size != sizeof(rrtmg_sw_components))
-    return ctx->fail(RRTMG_ERR_ARG, "rrtmg_sw_components: struct_size %d is not sizeof(rrtmg_sw_components) = %zu of this library: set it to sizeof of the struct",
-                     (int)c->struct_size, sizeof(rrtmg_sw_components));
-  if (c && !(c->dirdflx || c->difdflx || c->dirdnuv || c->difdnuv || c->dirdnir || c->difdnir || c->dirdflxc || c->difdflxc)) c = nullptr;
-  return checked_call(ctx, a, "rrtmg_sw", [c, b](rrtmg_ctx *x, const rrtmg_sw_args *y) { return sw_fluxes_bands_impl(x, y, c, b); });
-}
-// surface albedo by band: the three struct checks come before anything is enqueued; without a member it is the call without the struct
-int rrtmg_hip_sw_fluxes_surface(rrtmg_ctx *ctx, const rrtmg_sw_args *a, const rrtmg_sw_surface *sf, const rrtmg_sw_components *c, const rrtmg_sw_band_fluxes *b) {
-  if (!ctx) return RRTMG_ERR_ARG;
-  if (sf && (size_t)sf->struct_size != sizeof(rrtmg_sw_surface))
-    return ctx->fail(RRTMG_ERR_ARG, "rrtmg_sw_surface: struct_size %d is not sizeof(rrtmg_sw_surface) = %zu of this library: set it to sizeof of the struct",
-                     (int)sf->struct_size, sizeof(rrtmg_sw_surface));
-  if (!sf || !(sf->albdir || sf->albdif)) return rrtmg_hip_sw_fluxes_bands(ctx, a, c, b);
-  if (b && (size_t)b->struct_size != sizeof(rrtmg_sw_band_fluxes))
-    return ctx->fail(RRTMG_ERR_ARG, "rrtmg_sw_band_fluxes: struct_size %d is not sizeof(rrtmg_sw_band_fluxes) = %zu of this library: set it to sizeof of the struct",
-                     (int)b->struct_size, sizeof(rrtmg_sw_band_fluxes));
-  if (b && b->levels != 0 && b->levels != 1) return ctx->fail(RRTMG_ERR_ARG, "rrtmg_sw_band_fluxes: levels %d is neither 0 (all interface levels) nor 1 (surface and top)", (int)b->levels);
-  if (b && !(b->up || b->dn || b->upc || b->dnc || b->dndir || b->dndirc)) b = nullptr;
-  if (c && (size_t)c->struct_size != sizeof(rrtmg_sw_components))
-    return ctx->fail(RRTMG_ERR_ARG, "rrtmg_sw_components: struct_size %d is not sizeof(rrtmg_sw_components) = %zu of this library: set it to sizeof of the struct",
-                     (int)c->struct_size, sizeof(rrtmg_sw_components));
-  if (c && !(c->dirdflx || c->difdflx || c->dirdnuv || c->difdnuv || c->dirdnir || c->difdnir || c->dirdflxc || c->difdflxc)) c = nullptr;
-  return checked_call(ctx, a, "rrtmg_sw", [sf, c, b](rrtmg_ctx *x, const rrtmg_sw_args *y) { return sw_fluxes_surface_impl(x, y, sf, c, b); });
-}
+int rrtmg_hip_sw_fluxes_components(rrtmg_ctx *ctx, const rrtmg_sw_args *a, const rrtmg_sw_components *c) { return sw_fluxes_checked(ctx, a, nullptr, c, nullptr); }
+int rrtmg_hip_sw_fluxes_bands(rrtmg_ctx *ctx, const rrtmg_sw_args *a, const rrtmg_sw_components *c, const rrtmg_sw_band_fluxes *b) { return sw_fluxes_checked(ctx, a, nullptr, c, b); }
+int rrtmg_hip_sw_fluxes_surface(rrtmg_ctx *ctx, const rrtmg_sw_args *a, const rrtmg_sw_surface *sf, const rrtmg_sw_components *c, const rrtmg_sw_band_fluxes *b) { return sw_fluxes_checked(ctx, a, sf, c, b); }
 int rrtmg_hip_lw_fluxes_bands(rrtmg_ctx *ctx, const rrtmg_lw_args *a, const rrtmg_lw_band_fluxes *b) {
   if (!ctx) return RRTMG_ERR_ARG;
-  if (b && (size_t)b->struct_size != sizeof(rrtmg_lw_band_fluxes))
-    return ctx->fail(RRTMG_ERR_ARG, "rrtmg_lw_band_fluxes: struct_size %d is not sizeof(rrtmg_lw_band_fluxes) = %zu of this library: set it to sizeof of the struct",
-                     (int)b->struct_size, sizeof(rrtmg_lw_band_fluxes));
-  if (b && b->levels != 0 && b->levels != 1) return ctx->fail(RRTMG_ERR_ARG, "rrtmg_lw_band_fluxes: levels %d is neither 0 (all interface levels) nor 1 (surface and top)", (int)b->levels);
+  if (int rc = check_band_struct(ctx, b, "rrtmg_lw_band_fluxes")) return rc;
   if (!b || !(b->up || b->dn || b->upc || b->dnc)) return rrtmg_hip_lw_fluxes(ctx, a);
   return checked_call(ctx, a, "rrtmg_lw", [b](rrtmg_ctx *x, const rrtmg_lw_args *y) { return lw_fluxes_bands_impl(x, y, b); });
 }

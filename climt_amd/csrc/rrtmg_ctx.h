@@ -196,10 +196,9 @@ int ctx_prepare_device(rrtmg_ctx *ctx);   // hipSetDevice + lazy stream / error-
 std::string default_blob_path(const char *which);
 void free_sw_desc(rrtmg_ctx *ctx);
 void free_lw_desc(rrtmg_ctx *ctx);
-int sw_fluxes_impl(rrtmg_ctx *ctx, const rrtmg_sw_args *a);
-int sw_fluxes_components_impl(rrtmg_ctx *ctx, const rrtmg_sw_args *a, const rrtmg_sw_components *c);
-int sw_fluxes_bands_impl(rrtmg_ctx *ctx, const rrtmg_sw_args *a, const rrtmg_sw_components *c, const rrtmg_sw_band_fluxes *b);
-int sw_fluxes_surface_impl(rrtmg_ctx *ctx, const rrtmg_sw_args *a, const rrtmg_sw_surface *sf, const rrtmg_sw_components *c, const rrtmg_sw_band_fluxes *b);
+// (sf, c, b: what rrtmg_hip_sw_fluxes_surface takes, each checked and with at least one member set, or nullptr)
+int sw_fluxes_impl(rrtmg_ctx *ctx, const rrtmg_sw_args *a, const rrtmg_sw_surface *sf = nullptr, const rrtmg_sw_components *c = nullptr,
+                   const rrtmg_sw_band_fluxes *b = nullptr);
 int lw_fluxes_impl(rrtmg_ctx *ctx, const rrtmg_lw_args *a);
 int lw_fluxes_bands_impl(rrtmg_ctx *ctx, const rrtmg_lw_args *a, const rrtmg_lw_band_fluxes *b);
 int sw_init_impl(rrtmg_ctx *ctx, double cpdair, const char *blob);

@@ -395,7 +395,7 @@ static int sw_sorted_call(rrtmg_ctx *ctx, const rrtmg_sw_args *a) {
 // set, levels 0 or 1), or nullptr; sp: the surface albedo by band (at least one member set), or nullptr; all nullptr: the
 // plain call.  A call with components or bands is never sorted: its outputs would need a scatter of their own; nor is one with
 // a surface struct: its rows would need a gather of their own.
-static int sw_fluxes_run(rrtmg_ctx *ctx, const rrtmg_sw_args *a, const rrtmg_sw_components *cp, const rrtmg_sw_band_fluxes *bp, const rrtmg_sw_surface *sp = nullptr) {
+int sw_fluxes_impl(rrtmg_ctx *ctx, const rrtmg_sw_args *a, const rrtmg_sw_surface *sp, const rrtmg_sw_components *cp, const rrtmg_sw_band_fluxes *bp) {
   if (!cp && !bp && !sp && ctx->sw_ready && a && ctx->sort_columns && !ctx->sorting && a->memspace == 1 && a->icld != 0 && a->cldfr && a->ncol >= 128 && a->nlay > 0 && a->nlay <= 256 &&
       !(a->mcica && a->irng != 0))
     return sw_sorted_call(ctx, a);
@@ -636,10 +636,5 @@ static int sw_fluxes_run(rrtmg_ctx *ctx, const rrtmg_sw_args *a, const rrtmg_sw_
   ctx->status = 0;
   return RRTMG_OK;
 }
-
-int sw_fluxes_impl(rrtmg_ctx *ctx, const rrtmg_sw_args *a) { return sw_fluxes_run(ctx, a, nullptr, nullptr); }
-int sw_fluxes_components_impl(rrtmg_ctx *ctx, const rrtmg_sw_args *a, const rrtmg_sw_components *c) { return sw_fluxes_run(ctx, a, c, nullptr); }
-int sw_fluxes_bands_impl(rrtmg_ctx *ctx, const rrtmg_sw_args *a, const rrtmg_sw_components *c, const rrtmg_sw_band_fluxes *b) { return sw_fluxes_run(ctx, a, c, b); }
-int sw_fluxes_surface_impl(rrtmg_ctx *ctx, const rrtmg_sw_args *a, const rrtmg_sw_surface *sf, const rrtmg_sw_components *c, const rrtmg_sw_band_fluxes *b) { return sw_fluxes_run(ctx, a, c, b, sf); }
 
 }  // namespace rrtmg

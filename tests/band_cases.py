@@ -1,7 +1,7 @@
 """Cases of the fluxes by band (rrtmg_hip_sw_fluxes_bands, rrtmg_hip_lw_fluxes_bands) and their reference values.
 
-The expected values come from our drivers of the reference's own procedures (tests/refshim/sw_bands_shim.f90 and
-lw_bands_shim.f90, built by tests/refshim/build_bands.sh against oracle/_ref): the reference's transfer routines take a
+The expected values come from our drivers of the reference's own procedures (tests/refshim/sw_shim.f90 and
+lw_bands_shim.f90, built by tests/refshim/build.sh against oracle/_ref): the reference's transfer routines take a
 band range and restart the g-point counter per band (istart = iend = iout = band), but its driver pins them to all bands.
 tests/golden/make_band_fluxes.py writes one fixture per case, tests/golden/ref_bands_<case>.npz: gen/ (climt_amd.synthetic.
 make_columns), flag/ (options), in/ (inputs given directly), pin (input hash), bb/ (the binder's broadband fluxes) and band/
@@ -12,10 +12,10 @@ import os
 
 import numpy as np
 
-from helpers import GOLDEN, LW_DATA, input_hash
+from helpers import GOLDEN, LW_DATA, SW_SHIM, band_rule, input_hash, sw_shim
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SHIM = {w: os.path.join(ROOT, "tests", "_refshim", "lib%s_bands_shim.so" % w) for w in ("sw", "lw")}
+SHIM = {"sw": SW_SHIM, "lw": os.path.join(ROOT, "tests", "_refshim", "liblw_bands_shim.so")}
 MEMBERS = {"sw": ("up", "dn", "upc", "dnc", "dndir", "dndirc"), "lw": ("up", "dn", "upc", "dnc")}
 NBAND = {"sw": 14, "lw": 16}
 # the broadband output each band member sums to (dndir / dndirc: none among the plain outputs)
@@ -73,36 +73,15 @@ def shims_available():
 
 def _reference_sw(c, mcica):
     from oracle import ref_driver
-    from oracle.ref_driver import _cd, _d, _rd, _ri
     ref = ref_driver.RefSW()
     ref.init()
     subcol = ref.subcol(c) if mcica else None
     if mcica:
         c["cldfmcl"] = np.ascontiguousarray(subcol["cldfmcl"])
     binder = ref.fluxes(c, mcica=mcica, subcol=subcol)
-    nlay, ncol = c["play"].shape
-    g = lambda k: _cd(c[k])
-    l2 = lambda k, v: _cd(c[k]) if k in c else np.full((nlay, ncol), v)
-    d3 = lambda k, v: _cd(c[k]) if k in c else np.full((nlay, ncol, 14), v)
-    aer = lambda k, v: _cd(c[k]) if k in c else np.full((14, nlay, ncol), v)
-    keep = [aer("tauaer", 0.0), aer("ssaaer", 1.0), aer("asmaer", 0.0), np.ones(16), np.ones(2)]
-    out = np.zeros((15, 6, nlay + 1, ncol))
-    head = [_ri(ncol), _ri(nlay), _ri(c["icld"]), _ri(c["iaer"]),
-            _d(g("play")), _d(g("plev")), _d(g("tlay")), _d(g("tlev")), _d(g("tsfc")),
-            _d(g("h2o")), _d(g("o3")), _d(g("co2")), _d(g("ch4")), _d(g("n2o")), _d(g("o2")),
-            _d(g("asdir")), _d(g("asdif")), _d(g("aldir")), _d(g("aldif")), _d(g("coszen")),
-            _rd(c["adjes"]), _ri(c["dyofyr"]), _rd(c["scon"]), _ri(c["isolvar"]), _ri(c["inflg"]), _ri(c["iceflg"]), _ri(c["liqflg"])]
-    tail = [_d(keep[0]), _d(keep[1]), _d(keep[2]), _d(keep[3]), _d(keep[4]), _rd(0.0), _d(out)]
-    lib = C.CDLL(SHIM["sw"], mode=C.RTLD_LOCAL)
-    if mcica:
-        s = {k: _cd(v) for k, v in subcol.items()}
-        lib.sw_bands_mcica(*(head + [_d(s["cldfmcl"]), _d(s["taucmcl"]), _d(s["ssacmcl"]), _d(s["asmcmcl"]), _d(s["fsfcmcl"]),
-                                     _d(s["ciwpmcl"]), _d(s["clwpmcl"]), _d(l2("reice", 20.0)), _d(l2("reliq", 10.0))] + tail))
-    else:
-        cld = [l2("cldfr", 0.0), d3("taucld", 0.0), d3("ssacld", 1.0), d3("asmcld", 0.0), d3("fsfcld", 0.0),
-               l2("cicewp", 0.0), l2("cliqwp", 0.0), l2("reice", 20.0), l2("reliq", 10.0)]
-        lib.sw_bands_nomcica(*(head + [_d(x) for x in cld] + tail))
-    return binder, out
+    albedo = band_rule(c)
+    # the first six rows are the six members; slot 0 = the full band range, slots 1..14 = one call per band
+    return binder, np.stack([sw_shim(c, mcica, *albedo, subcol=subcol, band=kb)[0][:len(MEMBERS["sw"])] for kb in range(1 + NBAND["sw"])])
 
 
 def _reference_lw(c, mcica):

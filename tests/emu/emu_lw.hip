@@ -33,7 +33,8 @@ static void emu_lw_solve(const LwDev &d, const LwTab &T) {
     }
 }
 
-extern "C" int emu_lw_fluxes(const rrtmg_lw_args *a, const char *blob_path, double cpdair, const double *consts, char *errbuf, int errlen) {
+// bp: the band fluxes requested (rrtmg_hip_lw_fluxes_bands), or NULL
+extern "C" int emu_lw_fluxes(const rrtmg_lw_args *a, const rrtmg_lw_band_fluxes *bp, const char *blob_path, double cpdair, const double *consts, char *errbuf, int errlen) {
   auto fail = [&](int code, const std::string &m) { if (errbuf) { strncpy(errbuf, m.c_str(), errlen - 1); errbuf[errlen - 1] = 0; } return code; };
   Blob blob;
   std::string err;
@@ -115,6 +116,12 @@ extern "C" int emu_lw_fluxes(const rrtmg_lw_args *a, const char *blob_path, doub
   emu_lw_solve(d, T);
   for (int lev = 0; lev <= L; ++lev) for (int c = 0; c < N; ++c) lw_flux_level(d, T, c, lev, T.nitem, emu_lw_cloudy(d, c));
   for (int l = 0; l < L; ++l) for (int c = 0; c < N; ++c) lw_heat_layer(d, T, c, l);
+  if (bp) {   // as lw_bandflux_kernel maps its threads: every interface level, or the two boundary levels
+    const LwBandOut o{bp->up, bp->dn, bp->upc, bp->dnc};
+    const int nrow = bp->levels ? 2 : L + 1;
+    for (int row = 0; row < nrow; ++row)
+      for (int c = 0; c < N; ++c) lw_band_level(d, T, o, c, bp->levels ? (row ? L : 0) : row, row, nrow, emu_lw_cloudy(d, c));
+  }
   if (errflag) return fail(errflag, "device-side error flag " + std::to_string(errflag));
   return 0;
 }

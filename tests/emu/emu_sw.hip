@@ -2,9 +2,11 @@
 //
 // Runs the very same __host__ __device__ per-thread functions the gfx950 kernels run
 // (climt_amd/csrc/rrtmg_sw_device.h), thread by thread on the CPU, so the device arithmetic can be
-// parity-checked in the build container (which has no GPU).  It is compiled into
-// tests/_emu/librrtmg_emu.so by tests/emu/build.sh, is never loaded by the product, and is not a
-// fallback: librrtmg_hip.so fails loudly without a GPU.
+// parity-checked in the build container (which has no GPU): the plain outputs, the flux components
+// (sw_components_level), the band fluxes (sw_band_level) and the surface albedo by band, through ONE
+// driver that mirrors sw_fluxes_impl.  It is compiled into tests/_emu/librrtmg_emu.so by
+// tests/emu/build.sh, is never loaded by the product, and is not a fallback: librrtmg_hip.so fails
+// loudly without a GPU.
 #include <cstdlib>
 #include <cstring>
 #include <string>
@@ -21,21 +23,26 @@ namespace rrtmg {
 void mt_mask_host(int ncol, int nlay, int nsub, int icld, int seed, const double *cldfr, std::vector<uint64_t> &mask, int nw, int col0 = 0, int ncol_total = 0);
 }
 
-static void emu_solve(const SwDev &d, const SwTab &T) {
+// the clear-sky variant for cloud-free columns, as the device picks it per tile (here: per column)
+template <class Sink>
+static void emu_solve_item(const SwDev &d, const SwTab &T, int i, int col, double *scr, Sink sink) {
+  if (d.anycld[col] != 0) sw_solve_item<true>(d, T, T.t + T.exp_tbl, T.item[i], col, scr, 1, sink);
+  else sw_solve_item<false>(d, T, T.t + T.exp_tbl, T.item[i], col, scr, 1, sink);
+}
+// partdir: the direct-beam partial planes of the *_dir solve variants (SwPartDirSink), or nullptr (SwPartSink)
+static void emu_solve(const SwDev &d, const SwTab &T, double *partdir) {
   std::vector<double> scr((size_t)F_NTOT * d.nlay * 4);
-  for (int col = 0; col < d.ncol; ++col) {
-    // the clear-sky variant for cloud-free columns, as the device picks it per tile
-    const bool cld = d.anycld[col] != 0;
+  for (int col = 0; col < d.ncol; ++col)
     for (int i = 0; i < T.nitem; ++i) {
-      const int item = T.item[i];
-      SwPartSink sink = sw_part_sink(d, i, col);
-      if (cld) sw_solve_item<true>(d, T, T.t + T.exp_tbl, item, col, scr.data(), 1, sink);
-      else sw_solve_item<false>(d, T, T.t + T.exp_tbl, item, col, scr.data(), 1, sink);
+      if (partdir) emu_solve_item(d, T, i, col, scr.data(), sw_part_dir_sink(d, partdir, i, col));
+      else emu_solve_item(d, T, i, col, scr.data(), sw_part_sink(d, i, col));
     }
-  }
 }
 
-extern "C" int emu_sw_fluxes(const rrtmg_sw_args *a, const char *blob_path, double cpdair, const double *consts, char *errbuf, int errlen) {
+// The widest shortwave entry point (rrtmg_hip_sw_fluxes_surface), as sw_fluxes_impl runs it: sf (surface albedo by band),
+// cp (flux components) and bp (band fluxes) may each be NULL.
+extern "C" int emu_sw_fluxes(const rrtmg_sw_args *a, const rrtmg_sw_surface *sf, const rrtmg_sw_components *cp, const rrtmg_sw_band_fluxes *bp,
+                             const char *blob_path, double cpdair, const double *consts, char *errbuf, int errlen) {
   auto fail = [&](int code, const std::string &m) { if (errbuf) { strncpy(errbuf, m.c_str(), errlen - 1); errbuf[errlen - 1] = 0; } return code; };
   Blob blob;
   std::string err;
@@ -63,8 +70,14 @@ extern "C" int emu_sw_fluxes(const rrtmg_sw_args *a, const char *blob_path, doub
   if (!svar_col.empty()) d.svar_col = svar_col.data();
   if (rc) return fail(rc, err);
   d.play = a->play; d.plev = a->plev; d.tlay = a->tlay; d.h2o = a->h2ovmr; d.o3 = a->o3vmr; d.co2 = a->co2vmr;
-  d.ch4 = a->ch4vmr; d.n2o = a->n2ovmr; d.o2 = a->o2vmr; d.asdir = a->asdir; d.asdif = a->asdif; d.aldir = a->aldir;
-  d.aldif = a->aldif; d.coszen = a->coszen;
+  d.ch4 = a->ch4vmr; d.n2o = a->n2ovmr; d.o2 = a->o2vmr; d.coszen = a->coszen;
+  // the surface albedo as sw_fluxes_impl sets it up: a broadband pair is read only where its per-band array is not given
+  if (sf && (size_t)sf->struct_size != sizeof(rrtmg_sw_surface)) return fail(RRTMG_ERR_ARG, "rrtmg_sw_surface: struct_size");
+  const bool bdir = sf && sf->albdir, bdif = sf && sf->albdif;
+  if (!bdir) { d.asdir = a->asdir; d.aldir = a->aldir; if (!d.asdir || !d.aldir) return fail(RRTMG_ERR_ARG, "required array 'asdir' / 'aldir' is NULL"); }
+  if (!bdif) { d.asdif = a->asdif; d.aldif = a->aldif; if (!d.asdif || !d.aldif) return fail(RRTMG_ERR_ARG, "required array 'asdif' / 'aldif' is NULL"); }
+  if (bdir) d.albdir = sf->albdir;
+  if (bdif) d.albdif = sf->albdif;
   if (d.icld >= 1) {
     d.cldfr = a->cldfr; d.taucld = a->taucld; d.ssacld = a->ssacld; d.asmcld = a->asmcld; d.fsfcld = a->fsfcld;
     d.cicewp = a->cicewp; d.cliqwp = a->cliqwp; d.reice = a->reice; d.reliq = a->reliq;
@@ -80,6 +93,8 @@ extern "C" int emu_sw_fluxes(const rrtmg_sw_args *a, const char *blob_path, doub
   std::vector<uint64_t> mask;
   d.col0 = 0; d.pcols = N;
   d.part = wd((size_t)kSwNSlot * 4 * nl1);
+  const bool need_dir = cp || (bp && (bp->dndir || bp->dndirc));   // as sw_fluxes_impl: the *_dir solve variants and their planes
+  double *partdir = need_dir ? wd((size_t)kSwNSlot * 2 * nl1) : nullptr;
   d.swuflx = a->swuflx; d.swdflx = a->swdflx; d.swhr = a->swhr; d.swuflxc = a->swuflxc; d.swdflxc = a->swdflxc; d.swhrc = a->swhrc;
   int errflag = 0;
   d.err = &errflag;
@@ -117,9 +132,19 @@ extern "C" int emu_sw_fluxes(const rrtmg_sw_args *a, const char *blob_path, doub
       }
     }
   }
-  emu_solve(d, T);
+  emu_solve(d, T, partdir);
   for (int lev = 0; lev <= L; ++lev) for (int c = 0; c < N; ++c) sw_flux_level(d, T, c, lev, d.anycld[c] != 0);
   for (int l = 0; l < L; ++l) for (int c = 0; c < N; ++c) sw_heat_layer(d, T, c, l);
+  if (cp) {
+    const SwCompOut o{cp->dirdflx, cp->difdflx, cp->dirdnuv, cp->difdnuv, cp->dirdnir, cp->difdnir, cp->dirdflxc, cp->difdflxc};
+    for (int lev = 0; lev <= L; ++lev) for (int c = 0; c < N; ++c) sw_components_level(d, T, partdir, o, c, lev, d.anycld[c] != 0);
+  }
+  if (bp) {   // as sw_bandflux_kernel maps its threads: every interface level, or the two boundary levels
+    const SwBandOut o{bp->up, bp->dn, bp->upc, bp->dnc, bp->dndir, bp->dndirc};
+    const int nrow = bp->levels ? 2 : L + 1;
+    for (int row = 0; row < nrow; ++row)
+      for (int c = 0; c < N; ++c) sw_band_level(d, T, partdir, o, c, bp->levels ? (row ? L : 0) : row, row, nrow, d.anycld[c] != 0);
+  }
   if (errflag) return fail(errflag, "device-side error flag " + std::to_string(errflag));
   return 0;
 }

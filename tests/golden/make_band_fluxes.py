@@ -1,5 +1,5 @@
 """Writes tests/golden/ref_bands_<case>.npz, the reference values of the fluxes by band (tests/band_cases.py), from the
-reference Fortran in oracle/_ref and our drivers of its procedures (tests/refshim/build_bands.sh).  Needs both built
+reference Fortran in oracle/_ref and our drivers of its procedures (tests/refshim/build.sh).  Needs both built
 (build()).  Before a fixture is written the shims check themselves: over the full band range they reproduce the binder's
 broadband outputs bit for bit, and the per-band rows sum to that broadband within the rounding bound.
 
@@ -31,7 +31,7 @@ def self_check(name):
 
 def main(names):
     if not B.shims_available():
-        sys.exit("oracle/_ref or tests/_refshim (build_bands.sh) is not built")
+        sys.exit("oracle/_ref or tests/_refshim (tests/refshim/build.sh) is not built")
     for name in names or list(B.CASES):
         self_check(name)
         path = os.path.join(HERE, "ref_bands_%s.npz" % name)

@@ -1,6 +1,6 @@
 """Writes tests/golden/ref_albedo_<case>.npz, the reference values of the shortwave with the surface albedo by band
 (tests/albedo_cases.py), from the reference Fortran in oracle/_ref and our driver of its procedures
-(tests/refshim/build_albedo.sh).  Needs both built (build()).  Before a fixture is written the driver checks itself: with
+(tests/refshim/build.sh).  Needs both built (build()).  Before a fixture is written the driver checks itself: with
 the per-band albedos filled by the reference driver's band rule it reproduces the binder's six outputs bit for bit.
 
     python tests/golden/make_spectral_albedo.py [case ...]
@@ -19,7 +19,7 @@ import albedo_cases as A  # noqa: E402
 
 def main(names):
     if not A.shim_available():
-        sys.exit("oracle/_ref or tests/_refshim/libsw_albedo_shim.so (build_albedo.sh) is not built")
+        sys.exit("oracle/_ref or tests/_refshim/libsw_shim.so (tests/refshim/build.sh) is not built")
     for name in names or list(A.CASES):
         arr = A.fixture_arrays(name)      # (asserts shim == binder under the band rule)
         albdir, albdif = arr["in/albdir"], arr["in/albdif"]

@@ -12,7 +12,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
-from climt_amd._lib import LwArgs, SwArgs, LW_OUT, SW_OUT, SW_DATA, LW_DATA, _LW_FIELDS, _LW_FLAGS, _SW_FIELDS, _SW_FLAGS  # noqa: E402
+from climt_amd._lib import (LwArgs, SwArgs, LW_OUT, SW_OUT, SW_DATA, LW_DATA, _LW_FIELDS, _LW_FLAGS, _SW_FIELDS, _SW_FLAGS,  # noqa: E402
+                            LwBandFluxes, SwBandFluxes, SwComponents, SwSurface)
 
 GOLDEN = os.path.join(ROOT, "tests", "golden")
 EMU_SO = os.path.join(ROOT, "tests", "_emu", "librrtmg_emu.so")
@@ -29,8 +30,7 @@ def emu_lib():
     """Host emulation of the device functions (tests/emu); built on demand with hipcc (no GPU needed)."""
     global _emu
     if _emu is None:
-        srcs = [os.path.join(ROOT, "tests", "emu", f) for f in ("emu_sw.hip", "emu_lw.hip")]
-        srcs += [os.path.join(ROOT, "climt_amd", "csrc", f) for f in os.listdir(os.path.join(ROOT, "climt_amd", "csrc"))]
+        srcs = [os.path.join(ROOT, d, f) for d in ("tests/emu", "climt_amd/csrc") for f in os.listdir(os.path.join(ROOT, d))]
         if not os.path.exists(EMU_SO) or os.path.getmtime(EMU_SO) < max(os.path.getmtime(s) for s in srcs):
             subprocess.check_call([os.path.join(ROOT, "tests", "emu", "build.sh")])
         _emu = C.CDLL(EMU_SO)
@@ -61,6 +61,80 @@ def _fill(a, inp, fields, flags, keep):
         setattr(a, f, arr.ctypes.data)
 
 
+def _ptr_struct(cls, arrays, **head):
+    """An optional struct of array pointers (SwSurface, SwComponents, SwBandFluxes, LwBandFluxes) over `arrays`; None for None."""
+    if arrays is None:
+        return None
+    s = cls()
+    s.struct_size = C.sizeof(cls)
+    for k, v in head.items():
+        setattr(s, k, v)
+    for k, v in arrays.items():
+        setattr(s, k, v.ctypes.data)
+    return s
+
+
+def _emu_call(fn, a, structs, blob):
+    eb = C.create_string_buffer(512)
+    rc = fn(C.byref(a), *[None if s is None else C.byref(s) for s in structs], blob.encode(), C.c_double(CPDAIR), _CONST_VEC.ctypes.data_as(C.c_void_p), eb, 512)
+    if rc:
+        from climt_amd._lib import RRTMGError
+        raise RRTMGError(rc, eb.value.decode())
+
+
+def _band_arrays(nband, nlay, ncol, levels, members):
+    return None if members is None else {m: np.zeros((nband, 2 if levels == "boundaries" else nlay + 1, ncol)) for m in members}
+
+
+def emu_sw(inp, mcica, surface=None, components=None, bands=None, levels="all", surface_struct_size=None, blob=SW_DATA, out=None):
+    """The shortwave device functions on the host, through the one entry of tests/emu/emu_sw.hip (the shape of
+    rrtmg_hip_sw_fluxes_surface).  surface: None, or {"albdir" / "albdif": [14][ncol] array | None} (surface_struct_size: a
+    struct_size other than the right one); components / bands: None, or the names of the members wanted; levels: "all" |
+    "boundaries", the rows of the band arrays -> (plain outputs, component arrays | None, band arrays | None).  A refusal
+    raises RRTMGError."""
+    nlay, ncol = inp["play"].shape
+    a, keep = SwArgs(), []
+    a.ncol, a.nlay, a.memspace, a.mcica = ncol, nlay, 0, int(bool(mcica))
+    a.icld, a.inflgsw, a.iceflgsw, a.liqflgsw, a.dyofyr = 1, 2, 1, 1, 1
+    a.adjes, a.scon, a.solcycfrac = float(inp.get("adjes", 1.0)), float(inp.get("scon", 1367.0)), float(inp.get("solcycfrac", 0.0))
+    _fill(a, inp, _SW_FIELDS, _SW_FLAGS, keep)
+    if out is None:
+        out = {k: np.zeros((nlay + lev, ncol)) for k, lev in SW_OUT}
+    for k, _ in SW_OUT:
+        setattr(a, k, out[k].ctypes.data)
+    sf = None
+    if surface is not None:
+        given = {k: np.ascontiguousarray(v, dtype=np.float64) for k, v in surface.items() if v is not None}
+        keep += given.values()
+        sf = _ptr_struct(SwSurface, given)
+        if surface_struct_size is not None:
+            sf.struct_size = surface_struct_size
+    comp = None if components is None else {k: np.zeros((nlay + 1, ncol)) for k in components}
+    band = _band_arrays(14, nlay, ncol, levels, bands)
+    _emu_call(emu_lib().emu_sw_fluxes, a, (sf, _ptr_struct(SwComponents, comp), _ptr_struct(SwBandFluxes, band, levels=int(levels == "boundaries"))), blob)
+    return out, comp, band
+
+
+def emu_lw(inp, mcica, bands=None, levels="all", blob=None, out=None):
+    """The longwave counterpart (tests/emu/emu_lw.hip, the shape of rrtmg_hip_lw_fluxes_bands) -> (plain outputs, band arrays | None)."""
+    nlay, ncol = inp["play"].shape
+    a, keep = LwArgs(), []
+    a.ncol, a.nlay, a.memspace, a.mcica = ncol, nlay, 0, int(bool(mcica))
+    a.icld, a.inflglw, a.iceflglw, a.liqflglw = 1, 2, 1, 1
+    _fill(a, inp, _LW_FIELDS, _LW_FLAGS, keep)
+    if out is None:
+        out = {k: np.zeros((nlay + lev, ncol)) for k, lev in LW_OUT}
+        if a.idrv:
+            out["duflx_dt"] = np.zeros((nlay + 1, ncol))
+            out["duflxc_dt"] = np.zeros((nlay + 1, ncol))
+    for k in out:
+        setattr(a, k, out[k].ctypes.data)
+    band = _band_arrays(16, nlay, ncol, levels, bands)
+    _emu_call(emu_lib().emu_lw_fluxes, a, (_ptr_struct(LwBandFluxes, band, levels=int(levels == "boundaries")),),
+              blob or os.environ.get("RRTMG_HIP_LW_DATA") or LW_DATA)      # as climt_amd._lib.Context.lw_init
+    return out, band
+
+
 class EmuContext:
     """Drop-in for climt_amd._lib.Context that runs the device functions on the host (tests only)."""
 
@@ -87,42 +161,10 @@ class EmuContext:
         pass
 
     def sw_fluxes(self, inp, mcica=False, out=None, memspace=0):
-        nlay, ncol = inp["play"].shape
-        a, keep = SwArgs(), []
-        a.ncol, a.nlay, a.memspace, a.mcica = ncol, nlay, 0, int(bool(mcica))
-        a.icld, a.inflgsw, a.iceflgsw, a.liqflgsw, a.dyofyr = 1, 2, 1, 1, 1
-        a.adjes, a.scon, a.solcycfrac = float(inp.get("adjes", 1.0)), float(inp.get("scon", 1367.0)), float(inp.get("solcycfrac", 0.0))
-        _fill(a, inp, _SW_FIELDS, _SW_FLAGS, keep)
-        if out is None:
-            out = {k: np.zeros((nlay + lev, ncol)) for k, lev in SW_OUT}
-        for k, _ in SW_OUT:
-            setattr(a, k, out[k].ctypes.data)
-        eb = C.create_string_buffer(512)
-        rc = self.lib.emu_sw_fluxes(C.byref(a), getattr(self, "sw_blob", SW_DATA).encode(), C.c_double(CPDAIR), _CONST_VEC.ctypes.data_as(C.c_void_p), eb, 512)
-        if rc:
-            from climt_amd._lib import RRTMGError
-            raise RRTMGError(rc, eb.value.decode())
-        return out
+        return emu_sw(inp, mcica, blob=getattr(self, "sw_blob", SW_DATA), out=out)[0]
 
     def lw_fluxes(self, inp, mcica=False, out=None, memspace=0):
-        nlay, ncol = inp["play"].shape
-        a, keep = LwArgs(), []
-        a.ncol, a.nlay, a.memspace, a.mcica = ncol, nlay, 0, int(bool(mcica))
-        a.icld, a.inflglw, a.iceflglw, a.liqflglw = 1, 2, 1, 1
-        _fill(a, inp, _LW_FIELDS, _LW_FLAGS, keep)
-        if out is None:
-            out = {k: np.zeros((nlay + lev, ncol)) for k, lev in LW_OUT}
-            if a.idrv:
-                out["duflx_dt"] = np.zeros((nlay + 1, ncol))
-                out["duflxc_dt"] = np.zeros((nlay + 1, ncol))
-        for k in out:
-            setattr(a, k, out[k].ctypes.data)
-        eb = C.create_string_buffer(512)
-        rc = self.lib.emu_lw_fluxes(C.byref(a), getattr(self, "lw_blob", LW_DATA).encode(), C.c_double(CPDAIR), _CONST_VEC.ctypes.data_as(C.c_void_p), eb, 512)
-        if rc:
-            from climt_amd._lib import RRTMGError
-            raise RRTMGError(rc, eb.value.decode())
-        return out
+        return emu_lw(inp, mcica, blob=getattr(self, "lw_blob", LW_DATA), out=out)[0]
 
     def mcica_mask(self, which, play, cldfrac, icld, permuteseed, irng):
         nlay, ncol = play.shape
@@ -290,6 +332,56 @@ def load_opt_case(name):
     spectrum = name.split("_")[0]
     exp = {k[3:]: z[k] for k in z.files if k.startswith(spectrum + "/")}
     return spectrum, mcica, c, exp
+
+
+# ---- our driver of the reference's shortwave procedures (tests/refshim/sw_shim.f90, built by tests/refshim/build.sh) ----------
+SW_SHIM = os.path.join(ROOT, "tests", "_refshim", "libsw_shim.so")
+VISIBLE = (9, 10, 11, 12)      # band index of the reference's bands 10-13: asdir / asdif under the driver's rule
+
+
+def sw_shim_available():
+    from oracle import ref_driver
+    return ref_driver.available("sw") and os.path.exists(SW_SHIM)
+
+
+def band_rule(c):
+    """The reference driver's rule: four broadband albedos [ncol] -> (albdir, albdif) [14][ncol]."""
+    vis = np.zeros(14, dtype=bool)
+    vis[list(VISIBLE)] = True
+    pick = lambda s, l: np.ascontiguousarray(np.where(vis[:, None], np.asarray(c[s])[None, :], np.asarray(c[l])[None, :]))
+    return pick("asdir", "aldir"), pick("asdif", "aldif")
+
+
+def sw_shim(c, mcica, albdir, albdif, subcol=None, band=0):
+    """Our driver of the reference's procedures on the inputs `c` with these per-band albedos ([14][ncol]; band_rule(c) for the
+    reference driver's own), over the full band range (band 0) or over band 1..14 alone -> (the 14 rows of the reference's
+    accumulators [14][nlay+1][ncol], in sw_shim.f90's order; swhr and swhrc [2][nlay][ncol]).  mcica: on `subcol`
+    (RefSW.subcol)."""
+    from oracle.ref_driver import _cd, _d, _rd, _ri
+    nlay, ncol = c["play"].shape
+    g = lambda k: _cd(c[k])
+    l2 = lambda k, v: _cd(c[k]) if k in c else np.full((nlay, ncol), v)
+    d3 = lambda k, v: _cd(c[k]) if k in c else np.full((nlay, ncol, 14), v)
+    aer = lambda k, v: _cd(c[k]) if k in c else np.full((14, nlay, ncol), v)
+    keep = [aer("tauaer", 0.0), aer("ssaaer", 1.0), aer("asmaer", 0.0), np.ones(16), np.ones(2), _cd(albdir), _cd(albdif)]
+    assert keep[5].shape == (14, ncol) and keep[6].shape == (14, ncol)
+    rows, hr = np.zeros((14, nlay + 1, ncol)), np.zeros((2, nlay, ncol))
+    head = [_ri(ncol), _ri(nlay), _ri(c["icld"]), _ri(c["iaer"]),
+            _d(g("play")), _d(g("plev")), _d(g("tlay")), _d(g("tlev")), _d(g("tsfc")),
+            _d(g("h2o")), _d(g("o3")), _d(g("co2")), _d(g("ch4")), _d(g("n2o")), _d(g("o2")),
+            _d(keep[5]), _d(keep[6]), _d(g("coszen")),
+            _rd(c["adjes"]), _ri(c["dyofyr"]), _rd(c["scon"]), _ri(c["isolvar"]), _ri(c["inflg"]), _ri(c["iceflg"]), _ri(c["liqflg"])]
+    tail = [_d(keep[0]), _d(keep[1]), _d(keep[2]), _d(keep[3]), _d(keep[4]), _rd(0.0), _ri(band), _d(rows), _d(hr)]
+    lib = C.CDLL(SW_SHIM, mode=C.RTLD_LOCAL)
+    if mcica:
+        s = {k: _cd(v) for k, v in subcol.items()}
+        lib.sw_shim_mcica(*(head + [_d(s["cldfmcl"]), _d(s["taucmcl"]), _d(s["ssacmcl"]), _d(s["asmcmcl"]), _d(s["fsfcmcl"]),
+                                    _d(s["ciwpmcl"]), _d(s["clwpmcl"]), _d(l2("reice", 20.0)), _d(l2("reliq", 10.0))] + tail))
+    else:
+        cld = [l2("cldfr", 0.0), d3("taucld", 0.0), d3("ssacld", 1.0), d3("asmcld", 0.0), d3("fsfcld", 0.0),
+               l2("cicewp", 0.0), l2("cliqwp", 0.0), l2("reice", 20.0), l2("reliq", 10.0)]
+        lib.sw_shim_nomcica(*(head + [_d(x) for x in cld] + tail))
+    return rows, hr
 
 
 # ---- the live oracle on many columns: reference library (oracle/_ref) if it travelled, else the C restatement ----------

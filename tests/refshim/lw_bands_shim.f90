@@ -4,7 +4,7 @@
 ! on McICA sub-columns) -> setcoef (istart = 1, as the driver) -> taumol -> the aerosol sum, as rrtmg_lw_rad.nomcica.f90:
 ! 458-541 and rrtmg_lw_rad.f90:472-548 do, and then the transfer routine once over the full range (iout = 0: slot 0, checked
 ! against the binder's outputs bit for bit) and once per band with istart = iend = iout = band (slots 1..16).  Compiled
-! against the reference's .mod files and linked against its shared library by tests/refshim/build_bands.sh, so that the
+! against the reference's .mod files and linked against its shared library by tests/refshim/build.sh, so that the
 ! module state set through the reference binder (rrtmg_set_constants, the k-tables, rrtmg_lw_ini_wrapper) is the state these
 ! procedures read.
 !

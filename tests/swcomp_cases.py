@@ -1,22 +1,20 @@
 """Cases of the shortwave flux components (rrtmg_hip_sw_fluxes_components) and their reference values.
 
-The expected values come from our driver of the reference's own shortwave procedures (tests/refshim/sw_components_shim.f90,
-built by tests/refshim/build.sh against oracle/_ref): the reference computes the direct / diffuse and UV-visible / near-IR
+The expected values come from our driver of the reference's own shortwave procedures (tests/refshim/sw_shim.f90, built by
+tests/refshim/build.sh against oracle/_ref; helpers.sw_shim): the reference computes the direct / diffuse and UV-visible / near-IR
 sums on every call, but its binder does not return them.  tests/golden/make_sw_components.py writes one fixture per case,
 tests/golden/ref_swcomp_<case>.npz: gen/ (climt_amd.synthetic.make_columns), flag/ (options), in/ (inputs given directly),
 pin (input hash) and sw/ (expected arrays).  The GPU tests read the fixtures only."""
-import ctypes as C
 import os
 
 import numpy as np
 
-from helpers import GOLDEN, input_hash
+from helpers import GOLDEN, band_rule, input_hash, sw_shim, sw_shim_available as shim_available  # noqa: F401
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SHIM = os.path.join(ROOT, "tests", "_refshim", "libsw_components_shim.so")
 COMPONENTS = ("dirdflx", "difdflx", "dirdnuv", "difdnuv", "dirdnir", "difdnir", "dirdflxc", "difdflxc")
 BROADBAND = ("swuflx", "swdflx", "swuflxc", "swdflxc")
-# rows of the shim's output comp[14][nlay+1][ncol]
+# rows of the shim's output [14][nlay+1][ncol]
 SHIM_ROWS = ("zbbfu", "zbbfd", "zbbcu", "zbbcd", "zbbfddir", "zbbcddir", "zuvfd", "zuvcd", "zuvfddir", "zuvcddir",
              "znifd", "znicd", "znifddir", "znicddir")
 _COMMON = dict(icld=1, iaer=0, adjes=1.0, dyofyr=1, scon=1367.0, isolvar=0, inflg=2, iceflg=1, liqflg=1, irng=0, permuteseed=1,
@@ -53,21 +51,10 @@ def case_inputs(name):
     return c, bool(flags["_mcica"]), flags
 
 
-def _shim():
-    lib = C.CDLL(SHIM, mode=C.RTLD_LOCAL)
-    return lib
-
-
-def shim_available():
-    from oracle import ref_driver
-    return ref_driver.available("sw") and os.path.exists(SHIM)
-
-
 def reference(name):
     """Run a case through the reference: the binder's broadband outputs and the shim's 14 sums (needs oracle/_ref and the shim).
     -> (inputs incl. the McICA sub-column mask, binder outputs, shim rows)"""
     from oracle import ref_driver
-    from oracle.ref_driver import _cd, _d, _rd, _ri
     c, mcica, flags = case_inputs(name)
     ref = ref_driver.RefSW()
     ref.init()
@@ -75,29 +62,8 @@ def reference(name):
     if mcica:
         c["cldfmcl"] = np.ascontiguousarray(subcol["cldfmcl"])
     binder = ref.fluxes(c, mcica=mcica, subcol=subcol)
-    nlay, ncol = c["play"].shape
-    g = lambda k: _cd(c[k])
-    l2 = lambda k, v: _cd(c[k]) if k in c else np.full((nlay, ncol), v)
-    d3 = lambda k, v: _cd(c[k]) if k in c else np.full((nlay, ncol, 14), v)
-    aer = lambda k, v: _cd(c[k]) if k in c else np.full((14, nlay, ncol), v)
-    keep = [aer("tauaer", 0.0), aer("ssaaer", 1.0), aer("asmaer", 0.0), np.ones(16), np.ones(2)]
-    out = np.zeros((len(SHIM_ROWS), nlay + 1, ncol))
-    head = [_ri(ncol), _ri(nlay), _ri(c["icld"]), _ri(c["iaer"]),
-            _d(g("play")), _d(g("plev")), _d(g("tlay")), _d(g("tlev")), _d(g("tsfc")),
-            _d(g("h2o")), _d(g("o3")), _d(g("co2")), _d(g("ch4")), _d(g("n2o")), _d(g("o2")),
-            _d(g("asdir")), _d(g("asdif")), _d(g("aldir")), _d(g("aldif")), _d(g("coszen")),
-            _rd(c["adjes"]), _ri(c["dyofyr"]), _rd(c["scon"]), _ri(c["isolvar"]), _ri(c["inflg"]), _ri(c["iceflg"]), _ri(c["liqflg"])]
-    tail = [_d(keep[0]), _d(keep[1]), _d(keep[2]), _d(keep[3]), _d(keep[4]), _rd(0.0), _d(out)]
-    lib = _shim()
-    if mcica:
-        s = {k: _cd(v) for k, v in subcol.items()}
-        lib.sw_components_mcica(*(head + [_d(s["cldfmcl"]), _d(s["taucmcl"]), _d(s["ssacmcl"]), _d(s["asmcmcl"]), _d(s["fsfcmcl"]),
-                                          _d(s["ciwpmcl"]), _d(s["clwpmcl"]), _d(l2("reice", 20.0)), _d(l2("reliq", 10.0))] + tail))
-    else:
-        cld = [l2("cldfr", 0.0), d3("taucld", 0.0), d3("ssacld", 1.0), d3("asmcld", 0.0), d3("fsfcld", 0.0),
-               l2("cicewp", 0.0), l2("cliqwp", 0.0), l2("reice", 20.0), l2("reliq", 10.0)]
-        lib.sw_components_nomcica(*(head + [_d(x) for x in cld] + tail))
-    return c, binder, dict(zip(SHIM_ROWS, out))
+    rows, _ = sw_shim(c, mcica, *band_rule(c), subcol=subcol)
+    return c, binder, dict(zip(SHIM_ROWS, rows))
 
 
 def expected_from_rows(z):

@@ -1,6 +1,6 @@
 """CPU tests of the fluxes by band (rrtmg_hip_sw_fluxes_bands, rrtmg_hip_lw_fluxes_bands, band_fluxes=True of the two
 components): the reference driver shims against the reference binder, the committed fixtures against a fresh run of the
-reference, the device functions of the band integration (host emulation, tests/emu_bands) against the fixtures, the struct
+reference, the device functions of the band integration (host emulation, tests/emu) against the fixtures, the struct
 mirrors and exports, the band limits, the components' properties, and the recorded comparison of the tuned kernels' device
 code with the parent commit's."""
 import ctypes as C
@@ -14,12 +14,11 @@ import numpy as np
 import pytest
 
 import band_cases as B
-from helpers import CPDAIR, GOLDEN, LW_DATA, SW_DATA, EmuContext, LwArgs, SwArgs, _CONST_VEC, _LW_FIELDS, _LW_FLAGS, _SW_FIELDS, _SW_FLAGS, _fill, maxdiff
-from climt_amd._lib import LW_OUT, SW_OUT, LwBandFluxes, SwBandFluxes
+from helpers import GOLDEN, EmuContext, emu_lw, emu_sw, maxdiff
+from climt_amd._lib import LwBandFluxes, SwBandFluxes
 
 ROOT = B.ROOT
 TIGHT = 1.0e-9       # as the emulation tests of the plain outputs (test_device_functions_emulated.py)
-EMU = os.path.join(ROOT, "tests", "_emu_bands", "librrtmg_emu_bands.so")
 FC = os.environ.get("FC", "/opt/rocm/lib/llvm/bin/flang")
 LARGEST_EXISTING_FIXTURE = 200729   # bytes: tests/golden/ref_swcomp_aer10_overcast.npz
 
@@ -34,7 +33,7 @@ needs_reference = pytest.mark.skipif(not _reference_present(), reason="oracle/_r
 
 @pytest.fixture(scope="module")
 def shims():
-    subprocess.check_call([os.path.join(ROOT, "tests", "refshim", "build_bands.sh")])
+    subprocess.check_call([os.path.join(ROOT, "tests", "refshim", "build.sh")])
     assert B.shims_available()
 
 
@@ -77,34 +76,10 @@ def test_fixtures_are_small_and_whole():
 
 def emu_bands(which, inp, mcica, levels="all", members=None):
     """The band path of the device functions, run on the host -> (plain outputs, requested band arrays)."""
-    if not os.path.exists(EMU) or os.path.getmtime(EMU) < max(os.path.getmtime(os.path.join(ROOT, "climt_amd", "csrc", f)) for f in os.listdir(os.path.join(ROOT, "climt_amd", "csrc"))):
-        subprocess.check_call([os.path.join(ROOT, "tests", "emu_bands", "build.sh")])
-    lib = C.CDLL(EMU)
-    nlay, ncol = inp["play"].shape
-    keep = []
-    if which == "sw":
-        a = SwArgs()
-        a.ncol, a.nlay, a.memspace, a.mcica = ncol, nlay, 0, int(bool(mcica))
-        a.icld, a.inflgsw, a.iceflgsw, a.liqflgsw, a.dyofyr = 1, 2, 1, 1, 1
-        a.adjes, a.scon, a.solcycfrac = float(inp.get("adjes", 1.0)), float(inp.get("scon", 1367.0)), float(inp.get("solcycfrac", 0.0))
-        _fill(a, inp, _SW_FIELDS, _SW_FLAGS, keep)
-        outs, b, fn, blob = SW_OUT, SwBandFluxes(), lib.emu_sw_bands, SW_DATA
-    else:
-        a = LwArgs()
-        a.ncol, a.nlay, a.memspace, a.mcica = ncol, nlay, 0, int(bool(mcica))
-        a.icld, a.inflglw, a.iceflglw, a.liqflglw = 1, 2, 1, 1
-        _fill(a, inp, _LW_FIELDS, _LW_FLAGS, keep)
-        outs, b, fn, blob = LW_OUT, LwBandFluxes(), lib.emu_lw_bands, os.environ.get("RRTMG_HIP_LW_DATA") or LW_DATA
-    out = {k: np.zeros((nlay + lev, ncol)) for k, lev in outs}
-    for k, _ in outs:
-        setattr(a, k, out[k].ctypes.data)
-    band = B.band_arrays(which, nlay, ncol, levels, members)
-    b.struct_size, b.levels = C.sizeof(b), 1 if levels == "boundaries" else 0
-    for k, v in band.items():
-        setattr(b, k, v.ctypes.data)
-    eb = C.create_string_buffer(512)
-    rc = fn(C.byref(a), C.byref(b), blob.encode(), C.c_double(CPDAIR), _CONST_VEC.ctypes.data_as(C.c_void_p), eb, 512)
-    assert rc == 0, eb.value.decode()
+    members = members or B.MEMBERS[which]
+    if which == "lw":
+        return emu_lw(inp, mcica, bands=members, levels=levels)
+    out, _, band = emu_sw(inp, mcica, bands=members, levels=levels)
     return out, band
 
 
@@ -127,6 +102,20 @@ def test_emulated_bands_match_reference(case):
     _, two = emu_bands(which, c, mcica, levels="boundaries")
     for m in B.MEMBERS[which]:
         assert np.array_equal(two[m][:, 0], band[m][:, 0]) and np.array_equal(two[m][:, 1], band[m][:, nlay]), (case, m)
+
+
+@pytest.mark.parametrize("case", ["sw_mcica_kiss_maxrand", "lw_mcica_kiss_random"])
+def test_emulated_bands_with_a_generated_mask(case):
+    """McICA with the sub-column mask generated inside the emulation (kissvec, no cldfmcl), which the band path could not do
+    while it had a driver of its own.  No fixture: the band sums close on the broadband outputs of the same run."""
+    which = case[:2]
+    c, mcica, _, _ = B.load_case(case)
+    assert mcica and c["irng"] == 0
+    c = {k: v for k, v in c.items() if k != "cldfmcl"}
+    out, band = emu_bands(which, c, mcica)
+    for m, k in B.BROADBAND[which].items():
+        assert out[k].max() > 1.0, (case, k)
+        assert np.all(np.abs(band[m].sum(axis=0) - out[k]) <= B.SUM_BOUND * np.abs(out[k])), (case, m)
 
 
 def test_emulated_bands_identities():

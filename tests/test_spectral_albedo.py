@@ -1,7 +1,7 @@
 """CPU tests of the shortwave surface albedo by band (rrtmg_hip_sw_fluxes_surface, Context.sw_fluxes(surface=...),
 RRTMGShortwave(spectral_surface_albedo=True), climt_amd.rrtmg.band_albedo): the reference driver shim against the reference
 binder, the committed fixtures against a fresh run of the reference, the device functions (host emulation,
-tests/emu_albedo) against the fixtures, the C entry point's struct rules, the helper's values, the instance properties and
+tests/emu) against the fixtures, the C entry point's struct rules, the helper's values, the instance properties and
 defaults, and the column slicing."""
 import ctypes as C
 import json
@@ -15,12 +15,11 @@ import pytest
 
 import albedo_cases as A
 import band_cases as B
-from helpers import CPDAIR, GOLDEN, SW_DATA, SwArgs, _CONST_VEC, _SW_FIELDS, _SW_FLAGS, _fill, maxdiff
-from climt_amd._lib import SW_OUT, SwBandFluxes, SwSurface
+from helpers import GOLDEN, SwArgs, emu_sw, maxdiff
+from climt_amd._lib import SW_COMPONENTS, RRTMGError, SwSurface
 
 ROOT = A.ROOT
 TIGHT = 5.0e-9       # the project's bound for committed fixtures, fluxes and heating rates alike (tests/test_gpu_parity.py:61)
-EMU = os.path.join(ROOT, "tests", "_emu_albedo", "librrtmg_emu_albedo.so")
 FC = os.environ.get("FC", "/opt/rocm/lib/llvm/bin/flang")
 RRTMG_ERR_ARG = 4
 
@@ -35,7 +34,7 @@ needs_reference = pytest.mark.skipif(not _reference_present(), reason="oracle/_r
 
 @pytest.fixture(scope="module")
 def shim():
-    subprocess.check_call([os.path.join(ROOT, "tests", "refshim", "build_albedo.sh")])
+    subprocess.check_call([os.path.join(ROOT, "tests", "refshim", "build.sh")])
     assert A.shim_available()
 
 
@@ -80,39 +79,11 @@ def test_fixtures_hold_what_the_cases_ask_for():
 def emu_surface(inp, mcica, surface, bands=False, struct_size=None):
     """The device functions with SwDev::albdir / albdif set from `surface` (None, or a dict of [14][ncol] arrays / None), run
     on the host -> (rc, message, plain outputs, band arrays or None)."""
-    csrc = os.path.join(ROOT, "climt_amd", "csrc")
-    if not os.path.exists(EMU) or os.path.getmtime(EMU) < max(os.path.getmtime(os.path.join(csrc, f)) for f in os.listdir(csrc)):
-        subprocess.check_call([os.path.join(ROOT, "tests", "emu_albedo", "build.sh")])
-    lib = C.CDLL(EMU)
-    nlay, ncol = inp["play"].shape
-    keep = []
-    a = SwArgs()
-    a.ncol, a.nlay, a.memspace, a.mcica = ncol, nlay, 0, int(bool(mcica))
-    a.icld, a.inflgsw, a.iceflgsw, a.liqflgsw, a.dyofyr = 1, 2, 1, 1, 1
-    a.adjes, a.scon, a.solcycfrac = float(inp.get("adjes", 1.0)), float(inp.get("scon", 1367.0)), float(inp.get("solcycfrac", 0.0))
-    _fill(a, inp, _SW_FIELDS, _SW_FLAGS, keep)
-    out = {k: np.zeros((nlay + lev, ncol)) for k, lev in SW_OUT}
-    for k, _ in SW_OUT:
-        setattr(a, k, out[k].ctypes.data)
-    sf = None
-    if surface is not None:
-        sf = SwSurface()
-        sf.struct_size = C.sizeof(SwSurface) if struct_size is None else struct_size
-        for k, v in surface.items():
-            if v is not None:
-                keep.append(np.ascontiguousarray(v, dtype=np.float64))
-                setattr(sf, k, keep[-1].ctypes.data)
-    band, b = None, None
-    if bands:
-        band = B.band_arrays("sw", nlay, ncol)
-        b = SwBandFluxes()
-        b.struct_size, b.levels = C.sizeof(b), 0
-        for k, v in band.items():
-            setattr(b, k, v.ctypes.data)
-    eb = C.create_string_buffer(512)
-    rc = lib.emu_sw_surface(C.byref(a), C.byref(sf) if sf is not None else None, C.byref(b) if b is not None else None, SW_DATA.encode(),
-                            C.c_double(CPDAIR), _CONST_VEC.ctypes.data_as(C.c_void_p), eb, 512)
-    return rc, eb.value.decode(), out, band
+    try:
+        out, _, band = emu_sw(inp, mcica, surface=surface, bands=B.MEMBERS["sw"] if bands else None, surface_struct_size=struct_size)
+    except RRTMGError as e:
+        return e.code, str(e), None, None
+    return 0, "", out, band
 
 
 @pytest.mark.parametrize("case", list(A.CASES))
@@ -159,6 +130,23 @@ def test_emulated_struct_rules(case):
     assert rc == RRTMG_ERR_ARG, (rc, msg)
     rc, msg, _, _ = emu_surface(plain, mcica, surface, struct_size=C.sizeof(SwSurface) - 8)
     assert rc == RRTMG_ERR_ARG and "struct_size" in msg
+
+
+@pytest.mark.parametrize("case", list(A.CASES))
+def test_emulated_requests_combine(case):
+    """Surface, components and bands in ONE call of the one emulation entry: each request gets the bits of the call that makes
+    it alone."""
+    c, mcica, _ = A.load_case(case)
+    plain, surface = A.split_surface(c)
+    out, comp, band = emu_sw(plain, mcica, surface=surface, components=SW_COMPONENTS, bands=B.MEMBERS["sw"])
+    alone = emu_sw(plain, mcica, surface=surface)[0], emu_sw(plain, mcica, surface=surface, components=SW_COMPONENTS)[1], \
+        emu_sw(plain, mcica, surface=surface, bands=B.MEMBERS["sw"])[2]
+    for got, want in zip((out, comp, band), alone):
+        assert set(got) == set(want)
+        for k in want:
+            assert np.array_equal(got[k], want[k]), (case, k)
+    # and the requests that do not take the surface struct are untouched by its presence in the signature
+    assert all(np.array_equal(emu_sw(plain, mcica, components=SW_COMPONENTS, bands=B.MEMBERS["sw"])[0][k], v) for k, v in emu_sw(plain, mcica)[0].items())
 
 
 def test_emulated_band_independence_and_surface_closure():

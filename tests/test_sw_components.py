@@ -11,12 +11,11 @@ import numpy as np
 import pytest
 
 import swcomp_cases as S
-from helpers import CPDAIR, GOLDEN, SW_DATA, SwArgs, _CONST_VEC, _SW_FIELDS, _SW_FLAGS, _fill, maxdiff
-from climt_amd._lib import SW_OUT, SwComponents
+from helpers import GOLDEN, emu_sw, maxdiff
+from climt_amd._lib import SwComponents
 
 ROOT = S.ROOT
 FLUX_TOL, TIGHT = 1.0e-2, 1.0e-9       # as the emulation tests of the plain outputs (test_device_functions_emulated.py)
-EMU = os.path.join(ROOT, "tests", "_emu_components", "librrtmg_emu_components.so")
 FC = os.environ.get("FC", "/opt/rocm/lib/llvm/bin/flang")
 
 
@@ -59,36 +58,11 @@ def test_fixtures_are_small():
         assert os.path.getsize(os.path.join(GOLDEN, "ref_swcomp_%s.npz" % case)) < 256 * 1024, case
 
 
-def emu_components(inp, mcica, want=S.COMPONENTS):
-    """The components path of the device functions, run on the host: -> (six plain outputs, requested components)."""
-    if not os.path.exists(EMU):
-        subprocess.check_call([os.path.join(ROOT, "tests", "emu_components", "build.sh")])
-    lib = C.CDLL(EMU)
-    nlay, ncol = inp["play"].shape
-    a, keep = SwArgs(), []
-    a.ncol, a.nlay, a.memspace, a.mcica = ncol, nlay, 0, int(bool(mcica))
-    a.icld, a.inflgsw, a.iceflgsw, a.liqflgsw, a.dyofyr = 1, 2, 1, 1, 1
-    a.adjes, a.scon, a.solcycfrac = float(inp.get("adjes", 1.0)), float(inp.get("scon", 1367.0)), float(inp.get("solcycfrac", 0.0))
-    _fill(a, inp, _SW_FIELDS, _SW_FLAGS, keep)
-    out = {k: np.zeros((nlay + lev, ncol)) for k, lev in SW_OUT}
-    for k, _ in SW_OUT:
-        setattr(a, k, out[k].ctypes.data)
-    comp = {k: np.zeros((nlay + 1, ncol)) for k in want}
-    c = SwComponents()
-    c.struct_size = C.sizeof(SwComponents)
-    for k, v in comp.items():
-        setattr(c, k, v.ctypes.data)
-    eb = C.create_string_buffer(512)
-    rc = lib.emu_sw_components(C.byref(a), C.byref(c), SW_DATA.encode(), C.c_double(CPDAIR), _CONST_VEC.ctypes.data_as(C.c_void_p), eb, 512)
-    assert rc == 0, eb.value.decode()
-    return out, comp
-
-
 @pytest.mark.parametrize("case", list(S.CASES))
 def test_emulated_components_match_reference(case):
     """Band split, cloudy / clear choice of the direct beam and the weights of the direct sums, without a GPU."""
     c, mcica, exp = S.load_case(case)
-    out, comp = emu_components(c, mcica)
+    out, comp, _ = emu_sw(c, mcica, components=S.COMPONENTS)
     for k in S.COMPONENTS:
         d = maxdiff(comp[k], exp[k])
         assert d <= FLUX_TOL and d <= TIGHT, (case, k, d)
@@ -100,14 +74,14 @@ def test_emulated_components_match_reference(case):
 
 def test_emulated_components_identities():
     c, mcica, _ = S.load_case("mcica_kiss_maxrand")
-    out, comp = emu_components(c, mcica)
+    out, comp, _ = emu_sw(c, mcica, components=S.COMPONENTS)
     nlay = c["play"].shape[0]
     assert np.all(comp["difdflx"][nlay] == 0.0) and np.all(comp["difdflxc"][nlay] == 0.0)
     for k in ("difdflx", "difdnuv", "difdnir", "difdflxc"):
         assert comp[k].min() >= -1e-9, k
     np.testing.assert_allclose(comp["dirdnuv"] + comp["dirdnir"], comp["dirdflx"], rtol=1e-10, atol=1e-12)
     np.testing.assert_allclose(comp["difdnuv"] + comp["difdnir"], comp["difdflx"], rtol=1e-10, atol=1e-10)
-    _, some = emu_components(c, mcica, want=("dirdnuv", "difdflxc"))
+    _, some, _ = emu_sw(c, mcica, components=("dirdnuv", "difdflxc"))
     assert np.array_equal(some["dirdnuv"], comp["dirdnuv"]) and np.array_equal(some["difdflxc"], comp["difdflxc"])
 
 

@@ -1,6 +1,7 @@
 #!/usr/bin/env bash
 # Development tool (CPU only): the host emulation of the device functions -- the same __host__ __device__ sources the kernels run
-# (climt_amd/csrc/rrtmg_{sw,lw}_device.h through tests/emu/) -- built with AddressSanitizer + UndefinedBehaviorSanitizer, and the CPU
+# (climt_amd/csrc/rrtmg_{sw,lw}_device.h through tests/emu/: the plain outputs, the flux components, the band fluxes and the surface
+# albedo by band all go through its two drivers) -- built with AddressSanitizer + UndefinedBehaviorSanitizer, and the CPU
 # suite run on it.  GPU sanitizers are not available on the pool; this is where an out-of-range table index or a signed overflow in
 # the physics shows up.  The sanitized library replaces tests/_emu/librrtmg_emu.so for the run and is rebuilt normally afterwards.
 #   tools/sanitize_emu.sh            (-O0 for the two emulation units: the optimiser needs > 10 min per unit with the sanitizers on)
