@@ -179,6 +179,9 @@ def load_library():
     lib.rrtmg_hip_kernel_ms.argtypes = [_vp, C.c_int, C.POINTER(C.c_double)]
     lib.rrtmg_hip_kernel_launches.argtypes = [_vp, C.c_int]
     lib.rrtmg_hip_set_column_sort.argtypes = [_vp, C.c_int]
+    if hasattr(lib, "rrtmg_hip_set_sw_night_skip"):      # (RRTMG_HIP_LIB may name a library that predates it, as for the entry above)
+        lib.rrtmg_hip_set_sw_night_skip.argtypes = [_vp, C.c_int]
+        lib.rrtmg_hip_sw_night_last.argtypes = [_vp, C.POINTER(C.c_int), C.POINTER(C.c_int)]
     lib.rrtmg_hip_copy_blocks.argtypes = [_vp, C.c_int, _vp, C.c_long, C.c_long, _vp, _vp, _vp]
     lib.rrtmg_hip_mcica_mask.argtypes = [_vp] + [C.c_int] * 6 + [_vp] * 3
     _lib = lib
@@ -328,8 +331,9 @@ class Context:
 
     @_locked
     def elementwise(self, op, n, a, out, b=None, alpha=1.0, beta=1.0):
-        """op: 'axpby' out = alpha*a (+ beta*b), 'cos' out = cos(a), 'muldiv' out = a*alpha/beta"""
-        self._ck(self.lib.rrtmg_hip_elementwise(self.h, {"axpby": 0, "cos": 1, "muldiv": 2}[op], int(n), a, b, float(alpha), float(beta), out))
+        """op: 'axpby' out = alpha*a (+ beta*b), 'cos' out = cos(a), 'muldiv' out = a*alpha/beta, 'cosday' out = 0 where
+        a >= pi/2, else cos(a)"""
+        self._ck(self.lib.rrtmg_hip_elementwise(self.h, {"axpby": 0, "cos": 1, "muldiv": 2, "cosday": 3}[op], int(n), a, b, float(alpha), float(beta), out))
 
     @_locked
     def ab_step(self, n, x, tendencies, weights, dt, out):
@@ -404,6 +408,20 @@ class Context:
     def set_column_sort(self, on=True):
         """Opt-in internal column order of device-resident calls with clouds: cloud-free columns first (rrtmg_hip_set_column_sort)."""
         self._ck(self.lib.rrtmg_hip_set_column_sort(self.h, 1 if on else 0))
+
+    @_locked
+    def set_sw_night_skip(self, on=True):
+        """Opt-in night-column skip of the shortwave (rrtmg_hip_set_sw_night_skip): columns with coszen <= 0 get exact zeros in
+        every output, and 64-column tiles whose columns are all night are not prepared or solved; day columns keep their bits."""
+        self._ck(self.lib.rrtmg_hip_set_sw_night_skip(self.h, 1 if on else 0))
+
+    @_locked
+    def sw_night_last(self):
+        """-> (night tiles, night columns) of the last completed shortwave call (in deferred mode: after synchronize());
+        (0, 0) when the skip was off (rrtmg_hip_sw_night_last)."""
+        t, c = C.c_int(0), C.c_int(0)
+        self._ck(self.lib.rrtmg_hip_sw_night_last(self.h, C.byref(t), C.byref(c)))
+        return t.value, c.value
 
     @_locked
     def get_table(self, name):

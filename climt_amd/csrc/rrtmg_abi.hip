@@ -52,10 +52,11 @@ int ctx_prepare_device(rrtmg_ctx *ctx) {
   if (!ctx->stream) RRTMG_HIP_CHECK(ctx, hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking));
   if (!ctx->stream_lw) RRTMG_HIP_CHECK(ctx, hipStreamCreateWithFlags(&ctx->stream_lw, hipStreamNonBlocking));
   if (!ctx->hint) {
-    RRTMG_HIP_CHECK(ctx, hipHostMalloc((void **)&ctx->hint, 2 * sizeof(rrtmg_ctx::CallHint), hipHostMallocDefault));
+    RRTMG_HIP_CHECK(ctx, hipHostMalloc((void **)&ctx->hint, 2 * sizeof(rrtmg_ctx::CallHint) + 2 * sizeof(int), hipHostMallocDefault));   // (+ rrtmg_ctx::night_host)
     for (int w = 0; w < 2; ++w) { ctx->hint[w].ntile = -1; ctx->hint[w].nlay = -1; ctx->hint[w].ncloudy = -1; }
-    RRTMG_HIP_CHECK(ctx, hipMalloc((void **)&ctx->ncloudy_dev, 2 * sizeof(int)));
-    RRTMG_HIP_CHECK(ctx, hipMemset(ctx->ncloudy_dev, 0, 2 * sizeof(int)));
+    ctx->night_host()[0] = 0; ctx->night_host()[1] = 0;
+    RRTMG_HIP_CHECK(ctx, hipMalloc((void **)&ctx->ncloudy_dev, 4 * sizeof(int)));
+    RRTMG_HIP_CHECK(ctx, hipMemset(ctx->ncloudy_dev, 0, 4 * sizeof(int)));
   }
   if (!ctx->err_dev) {
     RRTMG_HIP_CHECK(ctx, hipMalloc((void **)&ctx->err_dev, 64));
@@ -462,6 +463,19 @@ int rrtmg_hip_set_deferred(rrtmg_ctx *ctx, int on) {
 int rrtmg_hip_set_column_sort(rrtmg_ctx *ctx, int on) {
   if (!ctx) return RRTMG_ERR_ARG;
   ctx->sort_columns = on != 0;
+  return RRTMG_OK;
+}
+
+int rrtmg_hip_set_sw_night_skip(rrtmg_ctx *ctx, int on) {
+  if (!ctx) return RRTMG_ERR_ARG;
+  ctx->sw_night_skip = on != 0;
+  return RRTMG_OK;
+}
+int rrtmg_hip_sw_night_last(rrtmg_ctx *ctx, int *night_tiles, int *night_columns) {
+  if (!ctx || !night_tiles || !night_columns) return RRTMG_ERR_ARG;
+  const volatile int *n = ctx->sw_night_reported ? ctx->night_host() : nullptr;
+  *night_tiles = n ? n[0] : 0;
+  *night_columns = n ? n[1] : 0;
   return RRTMG_OK;
 }
 

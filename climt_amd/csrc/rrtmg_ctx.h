@@ -90,7 +90,12 @@ struct rrtmg_ctx {
   // taken the CUs) and the chunk depth of a cloudy grid with more than 80 layers.
   struct CallHint { int ntile, nlay, ncloudy; };
   volatile CallHint *hint = nullptr;   // [2], page-locked
-  int *ncloudy_dev = nullptr;          // [2]
+  int *ncloudy_dev = nullptr;          // [2], and behind them [2]: the night tiles and night columns a shortwave call with the skip on has counted so far
+  // rrtmg_hip_set_sw_night_skip: shortwave columns with coszen <= 0 get zeros, tiles of nothing else no work (rrtmg_sw.hip).
+  // The counts of the last such call are left in page-locked memory, behind the two hints, by the call's last kernel, as the
+  // hint is; sw_night_reported: the last enqueued shortwave call had the skip on (else rrtmg_hip_sw_night_last reports 0 / 0)
+  bool sw_night_skip = false, sw_night_reported = false;
+  volatile int *night_host() const { return hint ? (volatile int *)(hint + 2) : nullptr; }
   // KISS jump-ahead operators [sw|lw]: host copy, the key they were built for, the device buffer they were uploaded to
   std::vector<uint32_t> kiss_host[2][2];   // two staging copies per spectrum: a rebuild never waits for the previous upload
   hipEvent_t kiss_ev[2][2] = {{nullptr, nullptr}, {nullptr, nullptr}};   // recorded after the upload from kiss_host[w][k]

@@ -232,6 +232,16 @@ __global__ void __launch_bounds__(256) elementwise_kernel(int op, long n, const 
   else if (op == 1) out[i] = cos(a[i]);
   else out[i] = a[i] * alpha / beta;
 }
+// op 3 (a kernel of its own: elementwise_kernel stays the one of a library without this op): cos(zenith) for a shortwave call
+// with the night-column skip on -- 0.0 where the zenith angle is >= pi/2 (Instellation clamps it there, and the cosine of the
+// double nearest pi/2 is +6e-17: a night column the skip's `coszen <= 0` would not see), cos(a) as op 1 forms it elsewhere
+__global__ void __launch_bounds__(256) cos_day_kernel(long n, const double *a, double *out) {
+#pragma clang fp contract(off)
+  const long i = (long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  const double z = a[i];
+  out[i] = z >= 1.5707963267948966 ? 0.0 : cos(z);
+}
 // x_out = x + dt * (w0 f0 + w1 f1 + w2 f2 + w3 f3), the sum formed left to right as sympl's stepper does (0 + w0 f0 + ...)
 __global__ void __launch_bounds__(256) ab_step_kernel(long n, int order, const double *x, const double *f0, const double *f1, const double *f2,
                                                       const double *f3, double w0, double w1, double w2, double w3, double dt, double *out) {
@@ -291,10 +301,11 @@ extern "C" int rrtmg_hip_interface_values(rrtmg_ctx *ctx, int ncol, int nlay, co
 }
 extern "C" int rrtmg_hip_elementwise(rrtmg_ctx *ctx, int op, long n, const double *a, const double *b, double alpha, double beta, double *out) {
   if (!ctx) return RRTMG_ERR_ARG;
-  if (n <= 0 || op < 0 || op > 2 || !a || !out) return ctx->fail(RRTMG_ERR_ARG, "elementwise: bad argument");
+  if (n <= 0 || op < 0 || op > 3 || !a || !out) return ctx->fail(RRTMG_ERR_ARG, "elementwise: bad argument");
   int rc = ctx_prepare_device(ctx);
   if (rc) return rc;
-  hipLaunchKernelGGL(elementwise_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, op, n, a, b, alpha, beta, out);
+  if (op == 3) hipLaunchKernelGGL(cos_day_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, n, a, out);
+  else hipLaunchKernelGGL(elementwise_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, op, n, a, b, alpha, beta, out);
   RRTMG_HIP_CHECK(ctx, hipGetLastError());
   if (!ctx->deferred) RRTMG_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
   return RRTMG_OK;

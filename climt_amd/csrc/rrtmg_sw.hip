@@ -22,6 +22,9 @@
 //   boundary levels only) behind them, and the *_dir solve variants where a direct-beam member is set
 //   With the surface albedo by band (rrtmg_hip_sw_fluxes_surface): the same launches; the solve reads its two albedos from
 //   the caller's [band][column] rows (SwDev::albdir / albdif) instead of the four broadband arrays
+//   With the night-column skip on (rrtmg_hip_set_sw_night_skip): sw_kiss_mask_night_kernel, sw_prep_fused_night_kernel,
+//   sw_cloud_night_kernel, sw_tile_lists_night_kernel and sw_{fluxheat,components,bandflux}_night_kernel in the places of their
+//   namesakes; the solve kernels are the same and find a night tile in neither of their lists
 #include <future>
 
 #include "rrtmg_ctx.h"
@@ -288,6 +291,143 @@ __global__ void __launch_bounds__(64 * kBandLev) sw_bandflux_kernel(SwDev d, SwT
   sw_band_level(d, T, partdir, o, col, lev, row, levels ? 2 : d.nlay + 1, d.tile_cld[tile] != 0);
 }
 
+// ---- Night-column skip (rrtmg_hip_set_sw_night_skip; opt-in) -----------------------------------------------------------------
+// Kernels of their own, launched INSTEAD of their namesakes when the option is on: with it off the launch sequence and every
+// kernel in it are those of a library without the option (tools/isa_compare.py, profiles/isa_compare_night_skip.txt).
+// A night column has coszen <= 0 as the caller passed it (SwDev::coszen, before the clamp of sw_prep_column; NaN compares
+// false: day).  A night TILE -- every in-range column night -- gets SwDev::tile_cld = 2, a value that lands in neither list of
+// sw_tile_lists_night_kernel: no solve workgroup has work for it, and nothing else of the preparation runs, so its prep rows,
+// pdp, cloud optics, mask words and partial planes are never written NOR read.  The integration kernels decide per COLUMN from
+// coszen alone (in a night tile every column takes that path): zeros for a night column, the default kernels' arithmetic for a
+// day column.  Night columns of a mixed tile are prepared and solved in lockstep with their day neighbours, then zeroed.
+// night_cnt: [night tiles, night columns] of the call so far (device; the call's last integration launch publishes and clears it)
+constexpr int kTileNight = 2;
+__global__ void __launch_bounds__(64 * kPrepWaves) sw_prep_fused_night_kernel(SwDev d, SwTab T, int clouds, int tile0, int32_t *night_cnt) {
+  const int tile = tile0 + blockIdx.x, lane = threadIdx.x & 63, col = tile * 64 + lane;
+  const bool act = col < d.ncol, dark = act && d.coszen[col] <= 0.0;
+  // (each of the 16 wavefronts looks at the tile's 64 columns: the same two masks in all of them, the exit is workgroup-uniform)
+  const unsigned long long mday = __ballot(act && !dark), mdark = __ballot(dark);
+  if (threadIdx.x == 0 && mdark) atomicAdd(night_cnt + 1, __popcll(mdark));
+  if (mday == 0ull) {
+    if (threadIdx.x == 0) { d.tile_cld[tile] = kTileNight; atomicAdd(night_cnt, 1); }
+    return;
+  }
+  // From here sw_prep_fused_kernel's body, a copy: that kernel routed through a shared body came out with other instructions,
+  // and its ISA is to stay the one of a library without the option -- a change to it is made here too.
+  const int w = threadIdx.x >> 6;
+  __shared__ int sh_cld;
+  extern __shared__ int sh_idx[];
+  if (act)
+    for (int l = w; l < d.nlay; l += kPrepWaves) sh_idx[l * 64 + lane] = sw_prep_layer(d, T, col, l);
+  __syncthreads();
+  if (act)
+    for (int b = w; b < kSwNBand; b += kPrepWaves) sw_prep_column(d, T, col, b, b + 1, sh_idx + lane, 64);
+  if (w == 0) {
+    const unsigned long long any = __ballot(act && d.anycld[col] != 0);
+    if (lane == 0) { d.tile_cld[tile] = any != 0ull; sh_cld = any != 0ull; if (any) atomicAdd(d.ncloudy, 1); }
+  }
+  if (!clouds) return;
+  __syncthreads();
+  if (!sh_cld || !act) return;
+  for (int l = w; l < d.nlay; l += kPrepWaves) sw_cloud_layer(d, T, col, l);
+}
+__global__ void __launch_bounds__(64) sw_cloud_night_kernel(SwDev d, SwTab T, int tile0) {
+  const int tile = tile0 + blockIdx.x;
+  if (d.tile_cld[tile] != 1) return;   // cloud-free tile, or night tile
+  const int col = tile * 64 + threadIdx.x;
+  const int lay = blockIdx.y;
+  if (col < d.ncol) sw_cloud_layer(d, T, col, lay);
+}
+// tile_lists_kernel with a third flag value that lands in neither list (the longwave never produces it: its list kernel stays as it is)
+__global__ void __launch_bounds__(64) sw_tile_lists_night_kernel(const int32_t *tile_cld, int ntile, int32_t *list, int32_t *cnt, int cap) {
+  const int lane = threadIdx.x;
+  if (ntile > cap) ntile = cap;
+  int n0 = 0, n1 = 0;
+  for (int t0 = 0; t0 < ntile; t0 += 64) {
+    const int t = t0 + lane;
+    const int flag = t < ntile ? tile_cld[t] : kTileNight;
+    const unsigned long long m1 = __ballot(flag == 1), m0 = __ballot(flag == 0);
+    const unsigned long long lower = (1ull << lane) - 1ull;
+    if (flag == 1) list[cap + n1 + __popcll(m1 & lower)] = t;
+    else if (flag == 0) list[n0 + __popcll(m0 & lower)] = t;
+    n0 += __popcll(m0); n1 += __popcll(m1);
+  }
+  if (lane == 0) { cnt[0] = n0; cnt[1] = n1; }
+}
+// kiss_mask_kernel (a block = the 64 columns of a tile x one sub-column) that draws nothing for a night tile
+__global__ void __launch_bounds__(64) sw_kiss_mask_night_kernel(int ncol, int nlay, int icld, const double *play, const double *cldfr, uint64_t *mask,
+                                                                int nw, int *err, const uint32_t *jumps, const double *coszen) {
+  const int col = blockIdx.y * 64 + threadIdx.x;
+  const bool act = col < ncol;
+  if (__ballot(act && !(coszen[col] <= 0.0)) == 0ull) return;
+  if (act) kiss_mask_jump(ncol, nlay, icld, play, cldfr, mask, nw, err, jumps, col, blockIdx.x);
+}
+// sw_fluxheat_kernel: a day column's sums, differences and stores are those of that kernel; a night column stores +0.0 and
+// reads neither the partial planes nor pdp
+__global__ void __launch_bounds__(64 * (kFluxLev + 1)) sw_fluxheat_night_kernel(SwDev d, SwTab T, int tile0, int32_t *night_cnt, int32_t *night_out) {
+  if (blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) {
+    if (d.hint_out) { *d.hint_out = *d.ncloudy; *d.ncloudy = 0; }
+    // (night_out: page-locked, set in the call's last launch like hint_out -- every preparation kernel of the call has finished)
+    if (night_out) { night_out[0] = night_cnt[0]; night_out[1] = night_cnt[1]; night_cnt[0] = 0; night_cnt[1] = 0; }
+  }
+  const int tile = tile0 + blockIdx.x, lane = threadIdx.x & 63, j = threadIdx.x >> 6;
+  const int col = tile * 64 + lane, lev = blockIdx.y * kFluxLev + j;
+  __shared__ double net[kFluxLev + 1][64], netc[kFluxLev + 1][64];
+  const bool in = col < d.ncol && lev <= d.nlay;
+  const bool dark = col < d.ncol && d.coszen[col] <= 0.0;
+  if (in && !dark) {
+    double fu, fd, cu, cd;
+    sw_flux_sums(d, T, col, lev, d.tile_cld[tile] != 0, fu, fd, cu, cd);
+    if (j < kFluxLev || lev == d.nlay) {
+      const long o = (long)lev * d.ncol + col;
+      d.swuflx[o] = fu; d.swdflx[o] = fd; d.swuflxc[o] = cu; d.swdflxc[o] = cd;
+    }
+    net[j][lane] = fd - fu; netc[j][lane] = cd - cu;
+  } else if (in && (j < kFluxLev || lev == d.nlay)) {
+    const long o = (long)lev * d.ncol + col;
+    d.swuflx[o] = 0.0; d.swdflx[o] = 0.0; d.swuflxc[o] = 0.0; d.swdflxc[o] = 0.0;
+  }
+  __syncthreads();
+  if (col < d.ncol && j < kFluxLev && lev < d.nlay) {
+    const long o0 = (long)lev * d.ncol + col;
+    if (dark) {
+      d.swhrc[o0] = 0.0; d.swhr[o0] = 0.0;
+    } else {
+      const double zdpgcp = T.heatfac / d.pdp[o0];
+      d.swhrc[o0] = (netc[j + 1][lane] - netc[j][lane]) * zdpgcp;
+      d.swhr[o0] = (net[j + 1][lane] - net[j][lane]) * zdpgcp;
+    }
+  }
+}
+__global__ void __launch_bounds__(64 * kCompLev) sw_components_night_kernel(SwDev d, SwTab T, int tile0, const double *partdir, SwCompOut o) {
+  const int tile = tile0 + blockIdx.x, col = tile * 64 + (threadIdx.x & 63), lev = blockIdx.y * kCompLev + (threadIdx.x >> 6);
+  if (col >= d.ncol || lev > d.nlay) return;
+  if (d.coszen[col] <= 0.0) {
+    const long i = (long)lev * d.ncol + col;
+    double *const m[8] = {o.dirdflx, o.difdflx, o.dirdnuv, o.difdnuv, o.dirdnir, o.difdnir, o.dirdflxc, o.difdflxc};
+    for (int k = 0; k < 8; ++k)
+      if (m[k]) m[k][i] = 0.0;
+    return;
+  }
+  sw_components_level(d, T, partdir, o, col, lev, d.tile_cld[tile] != 0);
+}
+__global__ void __launch_bounds__(64 * kBandLev) sw_bandflux_night_kernel(SwDev d, SwTab T, int tile0, const double *partdir, SwBandOut o, int levels) {
+  const int tile = tile0 + blockIdx.x, col = tile * 64 + (threadIdx.x & 63), row = blockIdx.y * kBandLev + (threadIdx.x >> 6);
+  const int lev = levels ? (row ? d.nlay : 0) : row;
+  if (col >= d.ncol || row > (levels ? 1 : d.nlay)) return;
+  const int nrow = levels ? 2 : d.nlay + 1;
+  if (d.coszen[col] <= 0.0) {
+    double *const m[6] = {o.up, o.dn, o.upc, o.dnc, o.dndir, o.dndirc};
+    for (int band = 0; band < kSwNBand; ++band) {
+      const long i = ((long)band * nrow + row) * d.ncol + col;
+      for (int k = 0; k < 6; ++k)
+        if (m[k]) m[k][i] = 0.0;
+    }
+    return;
+  }
+  sw_band_level(d, T, partdir, o, col, lev, row, nrow, d.tile_cld[tile] != 0);
+}
+
 void free_sw_desc(rrtmg_ctx *ctx) {
   delete (SwTab *)ctx->sw_desc;
   ctx->sw_desc = nullptr;
@@ -394,9 +534,10 @@ static int sw_sorted_call(rrtmg_ctx *ctx, const rrtmg_sw_args *a) {
 // cp: the components requested (at least one member set), or nullptr; bp: the band fluxes requested (at least one member
 // set, levels 0 or 1), or nullptr; sp: the surface albedo by band (at least one member set), or nullptr; all nullptr: the
 // plain call.  A call with components or bands is never sorted: its outputs would need a scatter of their own; nor is one with
-// a surface struct: its rows would need a gather of their own.
+// a surface struct: its rows would need a gather of their own; nor is a call with the night-column skip on: the sort would move
+// night columns out of their tiles.
 int sw_fluxes_impl(rrtmg_ctx *ctx, const rrtmg_sw_args *a, const rrtmg_sw_surface *sp, const rrtmg_sw_components *cp, const rrtmg_sw_band_fluxes *bp) {
-  if (!cp && !bp && !sp && ctx->sw_ready && a && ctx->sort_columns && !ctx->sorting && a->memspace == 1 && a->icld != 0 && a->cldfr && a->ncol >= 128 && a->nlay > 0 && a->nlay <= 256 &&
+  if (!cp && !bp && !sp && !ctx->sw_night_skip && ctx->sw_ready && a && ctx->sort_columns && !ctx->sorting && a->memspace == 1 && a->icld != 0 && a->cldfr && a->ncol >= 128 && a->nlay > 0 && a->nlay <= 256 &&
       !(a->mcica && a->irng != 0))
     return sw_sorted_call(ctx, a);
   if (!ctx->sw_ready) return ctx->fail(RRTMG_ERR_NOT_INITIALISED, "rrtmg_hip_sw_init has not been called");
@@ -486,13 +627,22 @@ int sw_fluxes_impl(rrtmg_ctx *ctx, const rrtmg_sw_args *a, const rrtmg_sw_surfac
   const int ntile = (N + 63) / 64;
   // what the previous call found (rrtmg_ctx::CallHint): read without waiting, used for speed only
   const int hint_cloudy = (ctx->hint[0].ntile == ntile && ctx->hint[0].nlay == L) ? ctx->hint[0].ncloudy : -1;
+  const bool night = ctx->sw_night_skip;   // the *_night_kernel of every launch below that has one
+  // The count a call with the skip leaves is of the tiles that RAN cloudy: a night tile is of neither kind.  The chunk plan
+  // follows the cloudy share of the tiles that were not night in that call (its night count: a hint like the other), scaled to
+  // the grid: a grid keeps the plan it has without the skip, whichever way the previous call ran.
+  int plan_cloudy = hint_cloudy;
+  if (hint_cloudy >= 0 && ctx->sw_night_reported) {
+    const int nn = ctx->night_host()[0], run = ntile - nn;
+    if (nn > 0 && run > 0 && hint_cloudy <= run) plan_cloudy = (int)((long)hint_cloudy * ntile / run);
+  }
   int chunk_tiles = ctx->chunk_tiles;
-  if (ctx->chunk_auto && L > 80 && hint_cloudy >= 0 && 10 * hint_cloudy >= 9 * ntile) chunk_tiles = 64;   // deep cloudy grid: DESIGN.md 5
+  if (ctx->chunk_auto && L > 80 && plan_cloudy >= 0 && 10 * plan_cloudy >= 9 * ntile) chunk_tiles = 64;   // deep cloudy grid: DESIGN.md 5
   // (work space per tile of a mixed grid's chunk: the scratch slab, and with components the direct-beam partial planes -- half
   //  again the size of `part`, about 4 GB more on a 2048-tile chunk at 60 layers)
   const bool need_dir = cp || (bp && (bp->dndir || bp->dndirc));   // the *_dir solve variants and their partdir planes
   const size_t tile_bytes = ((size_t)kSwNGpt * F_NTOT * L + (need_dir ? (size_t)kSwNSlot * 2 * (L + 1) : 0)) * 64 * sizeof(double);
-  chunk_tiles = ctx->plan_chunks(0, chunk_tiles, ntile, L, (clouds && !ctx->sorting) ? hint_cloudy : -1,   /* (a sorted grid keeps the small chunks: its tiles are segregated by kind, every chunk but one is of one kind) */ tile_bytes, "sw.w.scratch");
+  chunk_tiles = ctx->plan_chunks(0, chunk_tiles, ntile, L, (clouds && !ctx->sorting) ? plan_cloudy : -1,   /* (a sorted grid keeps the small chunks: its tiles are segregated by kind, every chunk but one is of one kind) */ tile_bytes, "sw.w.scratch");
   const int ctile = ntile < chunk_tiles ? ntile : chunk_tiles;   // tiles per solve chunk
   int32_t *tlist = (int32_t *)ctx->buf("sw.w.tilelist", (size_t)(2 * ctile + 2) * 4);
   if (!tlist) ok = false;
@@ -546,6 +696,7 @@ int sw_fluxes_impl(rrtmg_ctx *ctx, const rrtmg_sw_args *a, const rrtmg_sw_surfac
 
   // ---- launches ---------------------------------------------------------------------------
   const dim3 gcl(ntile, L), blk(64);
+  int32_t *const night_cnt = ctx->ncloudy_dev + 2;
   if (d.iaer == 6) {
     double *ta = wd("aer.tau", nl * kSwNBand), *om = wd("aer.ssa", nl * kSwNBand), *as = wd("aer.asm", nl * kSwNBand);
     if (!ok) return ctx->status;
@@ -559,7 +710,8 @@ int sw_fluxes_impl(rrtmg_ctx *ctx, const rrtmg_sw_args *a, const rrtmg_sw_surfac
       } else if (a->irng == 0) {
         const uint32_t *jumps = kiss_jumps_device(ctx, 0, kSwNGpt, L, d.icld, a->permuteseed, s);
         if (!jumps) return ctx->status;
-        hipLaunchKernelGGL(kiss_mask_kernel, dim3(kSwNGpt, ntile), blk, 0, s, N, L, d.icld, d.play, d.cldfr, d.mask, d.nw, d.err, jumps);
+        if (night) hipLaunchKernelGGL(sw_kiss_mask_night_kernel, dim3(kSwNGpt, ntile), blk, 0, s, N, L, d.icld, d.play, d.cldfr, d.mask, d.nw, d.err, jumps, d.coszen);
+        else hipLaunchKernelGGL(kiss_mask_kernel, dim3(kSwNGpt, ntile), blk, 0, s, N, L, d.icld, d.play, d.cldfr, d.mask, d.nw, d.err, jumps);
       } else {
         rc = mt_mask_device(ctx, 0, N, L, kSwNGpt, d.icld, a->permuteseed, d.cldfr, d.mask, d.nw, a->shard_col0, a->shard_ncol, s);
         if (rc) return rc;
@@ -576,9 +728,15 @@ int sw_fluxes_impl(rrtmg_ctx *ctx, const rrtmg_sw_args *a, const rrtmg_sw_surfac
   for (int t0 = 0; t0 < ntile; t0 += ctile) {
     const int nt = ntile - t0 < ctile ? ntile - t0 : ctile;
     d.col0 = t0 * 64; d.pcols = ctile * 64;
-    hipLaunchKernelGGL(sw_prep_fused_kernel, dim3(nt), dim3(64 * kPrepWaves), (size_t)L * 64 * sizeof(int), s, d, T, clouds && !d.mcica ? 1 : 0, t0);
-    if (clouds && d.mcica) hipLaunchKernelGGL(sw_cloud_kernel, dim3(nt, L), blk, 0, s, d, T, t0);
-    hipLaunchKernelGGL(tile_lists_kernel, dim3(1), blk, 0, s, d.tile_cld + t0, nt, tlist, tlist + 2 * d.tcap, d.tcap);
+    if (night) {
+      hipLaunchKernelGGL(sw_prep_fused_night_kernel, dim3(nt), dim3(64 * kPrepWaves), (size_t)L * 64 * sizeof(int), s, d, T, clouds && !d.mcica ? 1 : 0, t0, night_cnt);
+      if (clouds && d.mcica) hipLaunchKernelGGL(sw_cloud_night_kernel, dim3(nt, L), blk, 0, s, d, T, t0);
+      hipLaunchKernelGGL(sw_tile_lists_night_kernel, dim3(1), blk, 0, s, d.tile_cld + t0, nt, tlist, tlist + 2 * d.tcap, d.tcap);
+    } else {
+      hipLaunchKernelGGL(sw_prep_fused_kernel, dim3(nt), dim3(64 * kPrepWaves), (size_t)L * 64 * sizeof(int), s, d, T, clouds && !d.mcica ? 1 : 0, t0);
+      if (clouds && d.mcica) hipLaunchKernelGGL(sw_cloud_kernel, dim3(nt, L), blk, 0, s, d, T, t0);
+      hipLaunchKernelGGL(tile_lists_kernel, dim3(1), blk, 0, s, d.tile_cld + t0, nt, tlist, tlist + 2 * d.tcap, d.tcap);
+    }
     const int ngrp = (nt + kSwWgWaves - 1) / kSwWgWaves;
     const dim3 wg(64 * kSwWgWaves);
     const int ci = t0 / ctile;
@@ -602,13 +760,24 @@ int sw_fluxes_impl(rrtmg_ctx *ctx, const rrtmg_sw_args *a, const rrtmg_sw_surfac
     if (expect_clear) { cloudy_variant(); clear_variant(); }
     else { clear_variant(); if (clouds) cloudy_variant(); }
     d.hint_out = t0 + ctile >= ntile ? (int32_t *)&ctx->hint[0].ncloudy : nullptr;
-    hipLaunchKernelGGL(sw_fluxheat_kernel, dim3(nt, (L + kFluxLev) / kFluxLev), dim3(64 * (kFluxLev + 1)), 0, s, d, T, t0);
-    if (cp) hipLaunchKernelGGL(sw_components_kernel, dim3(nt, (L + kCompLev) / kCompLev), dim3(64 * kCompLev), 0, s, d, T, t0, partdir, co);
+    const dim3 gfl(nt, (L + kFluxLev) / kFluxLev), bfl(64 * (kFluxLev + 1)), gco(nt, (L + kCompLev) / kCompLev), gba(nt, (L + kBandLev) / kBandLev);
+    if (night) {
+      hipLaunchKernelGGL(sw_fluxheat_night_kernel, gfl, bfl, 0, s, d, T, t0, night_cnt, d.hint_out ? (int32_t *)ctx->night_host() : nullptr);
+      if (cp) hipLaunchKernelGGL(sw_components_night_kernel, gco, dim3(64 * kCompLev), 0, s, d, T, t0, partdir, co);
+      if (bp) {
+        if (bp->levels) hipLaunchKernelGGL(sw_bandflux_night_kernel, dim3(nt, 1), dim3(64 * 2), 0, s, d, T, t0, partdir, bo, 1);
+        else hipLaunchKernelGGL(sw_bandflux_night_kernel, gba, dim3(64 * kBandLev), 0, s, d, T, t0, partdir, bo, 0);
+      }
+      continue;
+    }
+    hipLaunchKernelGGL(sw_fluxheat_kernel, gfl, bfl, 0, s, d, T, t0);
+    if (cp) hipLaunchKernelGGL(sw_components_kernel, gco, dim3(64 * kCompLev), 0, s, d, T, t0, partdir, co);
     if (bp) {
       if (bp->levels) hipLaunchKernelGGL(sw_bandflux_kernel, dim3(nt, 1), dim3(64 * 2), 0, s, d, T, t0, partdir, bo, 1);
-      else hipLaunchKernelGGL(sw_bandflux_kernel, dim3(nt, (L + kBandLev) / kBandLev), dim3(64 * kBandLev), 0, s, d, T, t0, partdir, bo, 0);
+      else hipLaunchKernelGGL(sw_bandflux_kernel, gba, dim3(64 * kBandLev), 0, s, d, T, t0, partdir, bo, 0);
     }
   }
+  ctx->sw_night_reported = night;   // (rrtmg_hip_sw_night_last: this call's counts, once it has completed)
   ctx->hint[0].ntile = ntile; ctx->hint[0].nlay = L;
   ctx->ev_chunks[0] = (ntile + ctile - 1) / ctile; ctx->ev_chunks[2] = clouds ? ctx->ev_chunks[0] : 0;
   RRTMG_HIP_CHECK(ctx, hipGetLastError());

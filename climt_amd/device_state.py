@@ -288,6 +288,11 @@ def shortwave_device_call(self, ds):
     if getattr(self, "_band_fluxes", False):
         from .rrtmg.shortwave import BAND_FLUX_DIAGNOSTICS
         bands = {b: w("band." + b, (14,) + il, ("num_shortwave_bands", "interface_levels", "*"), "W m^-2") for b in BAND_FLUX_DIAGNOSTICS.values()}
+    self._apply_night_skip(ds.ctx)
+    if getattr(self, "_skip_night", False):      # cos(zenith) with its night columns at 0.0 (RRTMGShortwave.night_coszen), same stream
+        cz = ds.work("d.coszen.night", (ncol,), ("*",), "dimensionless")
+        ds.ctx.elementwise("cosday", ncol, ds["zenith_angle"].ptr, cz.ptr)
+        inp["coszen"] = cz.ptr
     if comps or bands or surface:
         ds.ctx.sw_fluxes(inp, mcica=self._mcica, out=out, memspace=1, components={c: q.ptr for c, q in comps.items()} if comps else None,
                          bands={b: q.ptr for b, q in bands.items()} if bands else None, surface=surface)

@@ -183,14 +183,20 @@ class RRTMGShortwave(TendencyComponent):
                  solar_variability_method=0, use_solar_constant_from_fortran=False, ignore_day_of_year=False,
                  facular_sunspot_amplitude=None, solar_variability_by_band=None, aerosol_type="no_aerosol", mcica=False,
                  random_number_generator="mersenne_twister", device=0, flux_components=False, band_fluxes=False,
-                 spectral_surface_albedo=False, **kwargs):
+                 spectral_surface_albedo=False, skip_night_columns=False, **kwargs):
         """Same keyword arguments and defaults as climt.RRTMGShortwave (sw/component.py:179-194); the additions are `device`
         (GPU ordinal) and `flux_components`: True adds the downward flux split into direct and diffuse parts -- all bands,
         UV/visible bands, near-IR bands, and all bands clear sky (FLUX_COMPONENT_DIAGNOSTICS) -- to this instance's
         diagnostics; `band_fluxes`: True adds the up / down fluxes (all sky, clear sky) and the direct beam by spectral
         band (BAND_FLUX_DIAGNOSTICS); `spectral_surface_albedo`: True replaces, in this instance's inputs, the four broadband
         surface albedos by one direct and one diffuse albedo per band (SPECTRAL_ALBEDO_INPUTS; band_albedo() makes them from
-        a spectral curve); the class attributes are unchanged."""
+        a spectral curve); `skip_night_columns`: True gives every column whose zenith angle is >= pi/2 (a column at exactly pi/2, where
+        Instellation clamps the angle and the cosine in double precision is +6e-17, is night) exact zeros in every
+        output instead of the reference's fluxes of order 1e-7 W m^-2 (its driver clamps the cosine to 1e-10 and solves), and
+        does no work for 64-column tiles that are night throughout (rrtmg_hip_set_sw_night_skip; climt_amd.night.night_tiles
+        states which those are); the cosine it hands over is night_coszen(): 0 from a zenith angle of pi/2 on; day columns
+        keep their bits; the class attributes are unchanged."""
+        self._skip_night = bool(skip_night_columns)
         self._spectral_albedo = bool(spectral_surface_albedo)
         if self._spectral_albedo:
             self.input_properties = self.input_properties_for(True)
@@ -244,6 +250,23 @@ class RRTMGShortwave(TendencyComponent):
         self._ctx.sw_init(self._Cpd)
         super(RRTMGShortwave, self).__init__(**kwargs)
 
+    @staticmethod
+    def night_coszen(zenith_angle):
+        """cos(zenith) as an instance with skip_night_columns=True hands it to the library, whose night test is coszen <= 0:
+        0.0 where the zenith angle is >= pi/2, cos() elsewhere.  Instellation (like climt's) clamps the zenith angle to pi/2, and
+        the cosine of the double nearest pi/2 is +6e-17: without this the sun would never set."""
+        z = np.asarray(zenith_angle, dtype=np.float64)
+        return np.where(z >= 0.5 * np.pi, 0.0, np.cos(z))
+
+    def _apply_night_skip(self, ctx):
+        """This instance's `skip_night_columns` -> the context about to be called (contexts are shared between components, so
+        the switch is set before every call).  A context without the switch serves the default only."""
+        setter = getattr(ctx, "set_sw_night_skip", None)
+        if setter is not None:
+            setter(self._skip_night)
+        elif self._skip_night:
+            raise RuntimeError("skip_night_columns=True: this context has no set_sw_night_skip")
+
     def __call__(self, state, *args, **kwargs):
         """A host state goes through sympl's machinery to array_call; a climt_amd.DeviceState (state resident in HBM) takes
         the device path: same quantities, DeviceQuantity handles instead of arrays (climt_amd/device_state.py)."""
@@ -271,7 +294,7 @@ class RRTMGShortwave(TendencyComponent):
             tsfc=state["surface_temperature"], h2o=Q, o3=state["mole_fraction_of_ozone_in_air"],
             co2=state["mole_fraction_of_carbon_dioxide_in_air"], ch4=state["mole_fraction_of_methane_in_air"],
             n2o=state["mole_fraction_of_nitrous_oxide_in_air"], o2=state["mole_fraction_of_oxygen_in_air"],
-            coszen=np.cos(state["zenith_angle"]), cldfr=state["cloud_area_fraction_in_atmosphere_layer"],
+            coszen=self.night_coszen(state["zenith_angle"]) if self._skip_night else np.cos(state["zenith_angle"]), cldfr=state["cloud_area_fraction_in_atmosphere_layer"],
             taucld=state["shortwave_optical_thickness_due_to_cloud"], ssacld=state["single_scattering_albedo_due_to_cloud"],
             asmcld=state["cloud_asymmetry_parameter"], fsfcld=state["cloud_forward_scattering_fraction"],
             cicewp=unit["mass_content_of_cloud_ice_in_atmosphere_layer"],
@@ -303,6 +326,7 @@ class RRTMGShortwave(TendencyComponent):
             swdflxc=diagnostics["downwelling_shortwave_flux_in_air_assuming_clear_sky"],
             swhrc=diagnostics["air_temperature_tendency_from_shortwave_assuming_clear_sky"])
         self._input_staging.wait()
+        self._apply_night_skip(self._ctx)
         if self._flux_components or self._band_fluxes:
             comps = {c: diagnostics[k] for k, c in FLUX_COMPONENT_DIAGNOSTICS.items()} if self._flux_components else None
             bands = {b: diagnostics[k] for k, b in BAND_FLUX_DIAGNOSTICS.items()} if self._band_fluxes else None

@@ -121,6 +121,34 @@ int rrtmg_hip_set_deferred(rrtmg_ctx *ctx, int on);
  * function of its tile).  Calls with the Mersenne twister (one positional stream) and host-pointer calls are not sorted,
  * nor are calls that request flux components or band fluxes (rrtmg_hip_sw_fluxes_components, rrtmg_hip_*_fluxes_bands). */
 int rrtmg_hip_set_column_sort(rrtmg_ctx *ctx, int on);
+/* OPT-IN night-column skip of the shortwave (off by default; with it off nothing changes, and the reference-compatible symbols
+ * on the default context never have it).  The reference's driver does not skip night columns: it clamps coszen to 1e-10
+ * (rrtmg_sw_rad.nomcica.f90:641-642) and runs the whole solver for fluxes of at most 1e-10 * scon * adjes W m^-2.  With the skip on:
+ *  - a NIGHT COLUMN is one with coszen <= 0 as the caller passes it, before the clamp (0.0 and -0.0 are night, NaN is not);
+ *    every output of a night column -- the six arrays of rrtmg_sw_args, every requested member of rrtmg_sw_components and
+ *    every requested row of rrtmg_sw_band_fluxes -- is +0.0 at every level, layer and band;
+ *  - every output of a day column keeps the bits of the same call with the skip off (any mcica / irng / icld / iaer, per-band
+ *    albedo, host or device arrays, deferred mode, column chunks, shard_col0 / shard_ncol blocks);
+ *  - work is saved per TILE, the 64 consecutive columns 64 t .. 64 t + 63 of the call that the solve kernels work on (the last
+ *    tile may be shorter): a tile whose columns are all night is not prepared, its cloud optics and kissvec mask are not formed
+ *    and no solve workgroup runs for it.  A mixed tile -- night and day columns -- is solved whole, in the same kernel variant
+ *    and at the same place of the Mersenne twister's stream as without the skip, and its night columns are zeroed afterwards:
+ *    nothing is saved inside a mixed tile.  With longitude fastest a tile is 64 consecutive longitudes of one latitude row: a
+ *    grid with 128 longitudes has two tiles per row and few night tiles, one with 512 or more has close to half of them night.
+ *  - status codes: the inputs of a night tile other than coszen are not checked, so no status code can come from them (they
+ *    are not read either, but for two passes over the whole grid that raise no code and whose work is not saved: the ECMWF
+ *    aerosol mixing of iaer = 6 reads ecaer, the Mersenne twister's mask reads cldfr of every column); the night
+ *    columns of a mixed tile run in lockstep with their day neighbours and are checked as without the skip; a day column's bad
+ *    input raises the same code as without the skip, and the context stays usable.
+ * The host-side scalar set-up (the in-place rescale of indsolvar included) is unchanged.  A call with the skip on is never
+ * column-sorted (rrtmg_hip_set_column_sort).  The longwave is not touched.  The switch belongs to the context: a binder that
+ * shares one context between callers sets it before each shortwave call.  Probe for it by symbol; the argument structs and
+ * RRTMG_HIP_ABI_VERSION are unchanged. */
+int rrtmg_hip_set_sw_night_skip(rrtmg_ctx *ctx, int on);
+/* Night tiles and night columns (all of them: those of mixed tiles too) of the last completed shortwave call on this context:
+ * valid after the call has returned, in deferred mode after rrtmg_hip_synchronize.  0 / 0 if that call ran with the skip off.
+ * night_tiles * 64 columns of the call's (ncol + 63) / 64 * 64 cost no solve time. */
+int rrtmg_hip_sw_night_last(rrtmg_ctx *ctx, int *night_tiles, int *night_columns);
 /* Duration (ms, HIP events recorded on the stream the kernel is launched on) of a solve kernel in the last completed call:
  * which = 0 -> sw_solve_all_kernel<false> (clear-sky tiles), 1 -> lw_solve_all_kernel<false,..>, 2 -> sw_solve_cloudy_kernel,
  * 3 -> lw_solve_all_kernel<true,..>.  A call launches that kernel once per column chunk (RRTMG_HIP_CHUNK_TILES tiles of 64
@@ -182,7 +210,8 @@ int rrtmg_hip_slab_surface(rrtmg_ctx *ctx, int ncol, int memspace, const rrtmg_s
 int rrtmg_hip_interface_values(rrtmg_ctx *ctx, int ncol, int nlay, const double *mid, const double *surf, const double *pmid,
                                const double *pint, double *out);
 /* op 0: out = alpha*a (+ beta*b if b != NULL); op 1: out = cos(a) (sw/component.py:567); op 2: out = a*alpha/beta
- * (mass_to_volume_mixing_ratio, util.py:86, with its two roundings) */
+ * (mass_to_volume_mixing_ratio, util.py:86, with its two roundings); op 3: out = a >= pi/2 ? 0.0 : cos(a) -- cos(zenith) for a
+ * shortwave call with rrtmg_hip_set_sw_night_skip on: a zenith angle clamped to pi/2 (Instellation) has a cosine of +6e-17 */
 int rrtmg_hip_elementwise(rrtmg_ctx *ctx, int op, long n, const double *a, const double *b, double alpha, double beta, double *out);
 /* Adams-Bashforth update out = x + dt * sum_k w[k] f[k], k < order <= 4 (f, w: host arrays of device pointers / weights) */
 int rrtmg_hip_ab_step(rrtmg_ctx *ctx, long n, int order, const double *x, const double *const *f, const double *w, double dt, double *out);

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Compares the device code of named kernels between two builds of librrtmg_hip.so (development tool; no GPU needed).
 
-    python tools/isa_compare.py <parent librrtmg_hip.so> <this librrtmg_hip.so> [-o profiles/isa_compare_band_fluxes.txt]
+    python tools/isa_compare.py <parent librrtmg_hip.so> <this librrtmg_hip.so> [--all] [-o profiles/isa_compare_band_fluxes.txt]
 
 Every gfx950 code object is taken out of the `.hip_fatbin` section of each library (clang offload bundles, one per
 translation unit), disassembled with llvm-objdump -d, and cut into functions.  A kernel's instruction stream is its
@@ -9,7 +9,9 @@ disassembly with the addresses and encodings dropped, branch targets rewritten a
 pc-relative addresses (s_getpc_b64 + s_add_u32 literal) rewritten -- inside .text as an offset from the function's start,
 in a data section as the section's name and the 32 bytes found there -- so that code and constants that merely moved inside
 the object compare equal.  Prints one line per kernel of KERNELS (a prefix of the
-demangled name; all template instances are compared): "identical" or "DIFFERENT", with the instruction count."""
+demangled name; all template instances are compared): "identical" or "DIFFERENT", with the instruction count.  --all: one
+line per function of the PARENT's code objects instead (every kernel a default call can launch), and a list of the functions
+only this build has."""
 import argparse
 import os
 import re
@@ -100,9 +102,16 @@ def functions(lib):
     return funcs
 
 
-def compare(parent, this):
+def compare(parent, this, every=False):
     a, b = functions(parent), functions(this)
     lines, same = [], True
+    if every:
+        for n in sorted(a):
+            ok = n in b and a[n] == b[n]
+            same = same and ok
+            lines.append("%s  %s  (%d instructions)" % ("identical" if ok else "DIFFERENT" if n in b else "MISSING  ", n, len(a[n])))
+        lines += ["new        %s  (%d instructions)" % (n, len(b[n])) for n in sorted(set(b) - set(a))]
+        return lines, same
     for k in KERNELS:
         names = sorted(n for n in set(a) | set(b) if n.startswith(k) or n.startswith("void " + k))
         if not names:
@@ -120,8 +129,9 @@ def main():
     ap.add_argument("parent")
     ap.add_argument("this")
     ap.add_argument("-o", "--output")
+    ap.add_argument("--all", action="store_true", help="every function of the parent's code objects, not only KERNELS")
     args = ap.parse_args()
-    lines, same = compare(args.parent, args.this)
+    lines, same = compare(args.parent, args.this, args.all)
     text = "\n".join(["# tools/isa_compare.py: device code of the kernels below, parent commit's build vs this build (llvm-objdump -d of the",
                       "# gfx950 code objects, addresses normalised)"] + lines) + "\n"
     sys.stdout.write(text)
