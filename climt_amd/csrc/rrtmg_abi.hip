@@ -509,7 +509,7 @@ long rrtmg_hip_get_table(rrtmg_ctx *ctx, const char *name, double *out, long cap
 }
 
 int rrtmg_hip_sw_fluxes(rrtmg_ctx *ctx, const rrtmg_sw_args *a) { return sw_fluxes_checked(ctx, a, nullptr, nullptr, nullptr); }
-int rrtmg_hip_lw_fluxes(rrtmg_ctx *ctx, const rrtmg_lw_args *a) { return checked_call(ctx, a, "rrtmg_lw", lw_fluxes_impl); }
+int rrtmg_hip_lw_fluxes(rrtmg_ctx *ctx, const rrtmg_lw_args *a) { return checked_call(ctx, a, "rrtmg_lw", [](rrtmg_ctx *x, const rrtmg_lw_args *y) { return lw_fluxes_impl(x, y); }); }
 int rrtmg_hip_sw_fluxes_components(rrtmg_ctx *ctx, const rrtmg_sw_args *a, const rrtmg_sw_components *c) { return sw_fluxes_checked(ctx, a, nullptr, c, nullptr); }
 int rrtmg_hip_sw_fluxes_bands(rrtmg_ctx *ctx, const rrtmg_sw_args *a, const rrtmg_sw_components *c, const rrtmg_sw_band_fluxes *b) { return sw_fluxes_checked(ctx, a, nullptr, c, b); }
 int rrtmg_hip_sw_fluxes_surface(rrtmg_ctx *ctx, const rrtmg_sw_args *a, const rrtmg_sw_surface *sf, const rrtmg_sw_components *c, const rrtmg_sw_band_fluxes *b) { return sw_fluxes_checked(ctx, a, sf, c, b); }
@@ -517,7 +517,7 @@ int rrtmg_hip_lw_fluxes_bands(rrtmg_ctx *ctx, const rrtmg_lw_args *a, const rrtm
   if (!ctx) return RRTMG_ERR_ARG;
   if (int rc = check_band_struct(ctx, b, "rrtmg_lw_band_fluxes")) return rc;
   if (!b || !(b->up || b->dn || b->upc || b->dnc)) return rrtmg_hip_lw_fluxes(ctx, a);
-  return checked_call(ctx, a, "rrtmg_lw", [b](rrtmg_ctx *x, const rrtmg_lw_args *y) { return lw_fluxes_bands_impl(x, y, b); });
+  return checked_call(ctx, a, "rrtmg_lw", [b](rrtmg_ctx *x, const rrtmg_lw_args *y) { return lw_fluxes_impl(x, y, b); });
 }
 // band limits, cm^-1: shortwave bands 16..29 (wavenum1 / wavenum2 of rrtmg_sw_init.f90, band 29 last), longwave bands 1..16
 // (rrtmg_lw_init.f90:196-204; hi - lo == delwave)

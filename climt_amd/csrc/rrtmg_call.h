@@ -1,0 +1,179 @@
+// rrtmg_call.h -- the host steps that a shortwave and a longwave flux call have in common (private to rrtmg_sw.hip and
+// rrtmg_lw.hip; host code only: no kernel lives here, and the kernels launched here are those of rrtmg_mcica_kernels.h).
+// In the order of a call: the gate to the sorted call and that call's head and tail, the argument checks, the call's stream,
+// the optional output tables, the chunk plan, the error flag, the McICA mask, the chunk loop, the epilogue.  The drivers keep
+// what differs: their inputs, work buffers and the kernels of every launch stage with their geometry.
+// which: 0 shortwave, 1 longwave -- the index of rrtmg_ctx::hint, plans, pending, kiss_* and of the err_dev slot.
+#pragma once
+#include "rrtmg_ctx.h"
+#include "rrtmg_mcica_kernels.h"
+#include "rrtmg_sort.h"
+
+namespace rrtmg {
+
+struct CallSite { rrtmg_ctx *ctx; int which; hipStream_t s; };
+// ---- entry gate ---------------------------------------------------------------------------------------------------------------
+inline bool spectrum_ready(const rrtmg_ctx *ctx, int which) { return which == 0 ? ctx->sw_ready : ctx->lw_ready; }
+// The call runs as *_sorted_call (rrtmg_sort.h): opt-in, device pointers, clouds, at least two tiles, kissvec or no McICA, and not
+// the inner call itself.  excluded: what the spectrum never sorts (outputs that would need a scatter, inputs a gather, of their own)
+template <class Args>
+inline bool call_is_sorted(const rrtmg_ctx *ctx, int which, const Args *a, bool excluded) {
+  return !excluded && spectrum_ready(ctx, which) && a && ctx->sort_columns && !ctx->sorting && a->memspace == 1 && a->icld != 0 && a->cldfr && a->ncol >= 128 && a->nlay > 0 && a->nlay <= 256 && !(a->mcica && a->irng != 0);
+}
+// the four argument checks every call makes, then the device (hipSetDevice, and the streams and flags where they do not exist yet)
+template <class Args>
+inline int call_begin(rrtmg_ctx *ctx, int which, const Args *a) {
+  if (!spectrum_ready(ctx, which)) return ctx->fail(RRTMG_ERR_NOT_INITIALISED, "%s", which == 0 ? "rrtmg_hip_sw_init has not been called" : "rrtmg_hip_lw_init has not been called");
+  if (!a || a->ncol <= 0 || a->nlay <= 0) return ctx->fail(RRTMG_ERR_ARG, "ncol/nlay must be positive");
+  if (a->nlay > 256) return ctx->fail(RRTMG_ERR_ARG, "nlay > 256 not supported (cloud-mask words)");
+  if (a->shard_ncol != 0 && (a->shard_col0 < 0 || a->shard_col0 + a->ncol > a->shard_ncol)) return ctx->fail(RRTMG_ERR_ARG, "shard_col0/shard_ncol do not contain ncol columns");
+  return ctx_prepare_device(ctx);
+}
+// o: the six outputs every call has
+inline int check_outputs(rrtmg_ctx *ctx, double *const *o) {
+  for (int k = 0; k < 6; ++k)
+    if (!o[k]) return ctx->fail(RRTMG_ERR_ARG, "output array is NULL");
+  return RRTMG_OK;
+}
+// The stream rule: the shortwave is always on ctx->stream; the longwave moves to stream_lw when the call is deferred and
+// device-resident, so that the two spectra overlap on the GPU.  (After ctx_prepare_device: the streams are created there.)
+inline hipStream_t call_stream(const rrtmg_ctx *ctx, int which, int memspace) { return (which == 1 && ctx->deferred && memspace == 1) ? ctx->stream_lw : ctx->stream; }
+// ---- the sorted call: head and tail (the gather lists are the spectrum's own) ---------------------------------------------------
+// head: the device, the column map on the call's stream (a sorted call is device-resident), b = the call on the padded copy
+template <class Args>
+inline int sorted_head(rrtmg_ctx *ctx, int which, const Args *a, ColumnSort &cs, Args &b) {
+  if (int rc = ctx_prepare_device(ctx)) return rc;
+  cs.s = call_stream(ctx, which, 1);
+  if (!cs.prepare(a->cldfr)) return ctx->status;
+  b = *a; b.ncol = cs.Np; b.shard_col0 = 0; b.shard_ncol = 0;
+  return RRTMG_OK;
+}
+// tail: the inner call, the scatter of its nout outputs o -> the caller's u ([2] and [5], the heating rates, have nlay rows)
+template <class Inner>
+inline int sorted_tail(rrtmg_ctx *ctx, ColumnSort &cs, int nout, double *const *o, double *const *u, Inner inner) {
+  ctx->sorting = true;
+  const int rc = inner();
+  ctx->sorting = false;
+  if (rc) return rc;
+  const size_t l = (size_t)cs.L, l1 = l + 1;
+  for (int k = 0; k < nout; ++k) cs.scatter(o[k], u[k], (k == 2 || k == 5) ? l : l1);
+  RRTMG_HIP_CHECK(ctx, hipGetLastError());
+  if (!ctx->deferred) RRTMG_HIP_CHECK(ctx, hipStreamSynchronize(cs.s));
+  return RRTMG_OK;
+}
+// ---- optional output tables (shortwave components and bands, longwave bands) ---------------------------------------------------
+// One row per member: the work buffer's name, the caller's array (nullptr: not requested, the kernel skips it), the member of
+// the kernel's output struct.  The device array is the caller's pointer under memspace 1, else the named work buffer (wd: the
+// driver's allocator of doubles), which the epilogue downloads behind the same synchronise as the standard outputs.
+struct OptOut { const char *name; double *user; double **dev; };
+template <class Wd>
+inline void opt_out_bind(const OptOut *t, int n, int memspace, size_t count, Wd wd) {
+  for (int k = 0; k < n; ++k)
+    if (t[k].user) *t[k].dev = memspace == 1 ? t[k].user : wd(t[k].name, count);
+}
+inline int opt_out_append(const OptOut *t, int n, size_t count, OutCopy *oc, int nout) {
+  for (int k = 0; k < n; ++k)
+    if (t[k].user) oc[nout++] = {t[k].user, *t[k].dev, count};
+  return nout;
+}
+// ---- chunk plan -----------------------------------------------------------------------------------------------------------------
+// what the previous call found (rrtmg_ctx::CallHint): read without waiting, used for speed only; -1: another grid, or nothing yet
+inline int call_hint_cloudy(const rrtmg_ctx *ctx, int which, int ntile, int nlay) {
+  return (ctx->hint[which].ntile == ntile && ctx->hint[which].nlay == nlay) ? ctx->hint[which].ncloudy : -1;
+}
+// -> tiles per solve chunk; the chunk's tile lists in d.tcap, d.tlist, d.tcnt (d.tlist == nullptr: allocation failed).  plan_cloudy:
+// the cloudy tiles to plan for (the hint, or the shortwave's night-scaled share); tile_bytes: work space per tile of a mixed grid's chunk
+template <class Dev>
+inline int plan_call_chunks(rrtmg_ctx *ctx, int which, Dev &d, bool clouds, int plan_cloudy, size_t tile_bytes) {
+  const int ntile = (d.ncol + 63) / 64, L = d.nlay;
+  int chunk_tiles = ctx->chunk_tiles;
+  if (ctx->chunk_auto && L > 80 && plan_cloudy >= 0 && 10 * plan_cloudy >= 9 * ntile) chunk_tiles = 64;   // deep cloudy grid: DESIGN.md 5
+  // (a sorted grid keeps the small chunks: its tiles are segregated by kind, every chunk but one is of one kind)
+  chunk_tiles = ctx->plan_chunks(which, chunk_tiles, ntile, L, (clouds && !ctx->sorting) ? plan_cloudy : -1, tile_bytes, which == 0 ? "sw.w.scratch" : "lw.w.scratch");
+  const int ctile = ntile < chunk_tiles ? ntile : chunk_tiles;
+  int32_t *tlist = (int32_t *)ctx->buf(which == 0 ? "sw.w.tilelist" : "lw.w.tilelist", (size_t)(2 * ctile + 2) * 4);
+  d.tcap = ctile; d.tlist = tlist; d.tcnt = tlist ? tlist + 2 * d.tcap : nullptr;
+  return ctile;
+}
+// ---- error flag and deferred prologue ---------------------------------------------------------------------------------------------
+// d.err = the spectrum's slot of err_dev.  A synchronous call owns its flag: flags of calls still pending from deferred mode are
+// collected first, then the slot is cleared on the call's stream.  A deferred call (device-resident, in deferred mode) leaves
+// it: the flag accumulates (atomicMax) until rrtmg_hip_synchronize collects and clears it.
+template <class Dev>
+inline int call_own_flag(const CallSite &c, int memspace, Dev &d) {
+  rrtmg_ctx *ctx = c.ctx;
+  d.err = ctx->err_dev + c.which;
+  if (ctx->deferred && memspace == 1) return RRTMG_OK;
+  if (ctx->pending[0] || ctx->pending[1]) { const int prc = rrtmg_hip_synchronize(ctx); if (prc) return prc; }
+  RRTMG_HIP_CHECK(ctx, hipMemsetAsync(d.err, 0, sizeof(int), c.s));
+  return RRTMG_OK;
+}
+// ---- McICA sub-column mask (d.mask) -------------------------------------------------------------------------------------------
+// cldfmcl given: from the caller's sub-columns (cldfmcl_dev: their device copy); irng 0: kissvec, every thread jumping to its
+// sub-column's first draw; else the Mersenne twister.  ngpt: the spectrum's g-points = sub-columns.  night_kernel, coszen: the
+// shortwave's kissvec kernel that draws nothing for a night tile, with the night-column skip on.
+using KissNightKernel = void (*)(int, int, int, const double *, const double *, uint64_t *, int, int *, const uint32_t *, const double *);
+template <class Dev, class Args>
+inline int mcica_mask_launch(const CallSite &c, int ngpt, const Dev &d, const Args *a, const double *cldfmcl_dev, KissNightKernel night_kernel = nullptr, const double *coszen = nullptr) {
+  rrtmg_ctx *ctx = c.ctx;
+  const int N = d.ncol, L = d.nlay, ntile = (N + 63) / 64;
+  const dim3 blk(64);
+  if (a->cldfmcl) {
+    hipLaunchKernelGGL(mask_from_cldfmcl_kernel, dim3(ntile, ngpt), blk, 0, c.s, N, L, ngpt, cldfmcl_dev, d.mask, d.nw);
+  } else if (a->irng == 0) {
+    const uint32_t *jumps = kiss_jumps_device(ctx, c.which, ngpt, L, d.icld, a->permuteseed, c.s);
+    if (!jumps) return ctx->status;
+    if (night_kernel) hipLaunchKernelGGL(night_kernel, dim3(ngpt, ntile), blk, 0, c.s, N, L, d.icld, d.play, d.cldfr, d.mask, d.nw, d.err, jumps, coszen);
+    else hipLaunchKernelGGL(kiss_mask_kernel, dim3(ngpt, ntile), blk, 0, c.s, N, L, d.icld, d.play, d.cldfr, d.mask, d.nw, d.err, jumps);
+  } else {
+    return mt_mask_device(ctx, c.which, N, L, ngpt, d.icld, a->permuteseed, d.cldfr, d.mask, d.nw, a->shard_col0, a->shard_ncol, c.s);
+  }
+  return RRTMG_OK;
+}
+// ---- chunk loop -----------------------------------------------------------------------------------------------------------------
+// Preparation, solve and integration, one column chunk of d.tcap tiles at a time.  Per chunk (first tile t0, nt tiles) the driver
+// supplies its launches: before(t0, nt) -- preparation, McICA cloud optics, tile lists; clear(t0, nt) and cloudy(t0, nt) -- the two
+// solve variants, each bracketed here by the event pair chunk_event(which | which + 2, chunk, side) of rrtmg_hip_kernel_ms;
+// after(t0, nt) -- the integration launches, which find d.hint_out set in the call's last chunk.
+// The variant expected to find nothing goes first, and the cloudy one is launched only with clouds (order is speed only: each tile
+// belongs to exactly one of them).  A sorted grid -- rrtmg_sort.h -- has its cloud-free tiles first: the chunks in front of the
+// previous call's cloudy-tile count (hint_cloudy) are expected to hold no cloudy tile.
+template <class Dev, class Before, class Clear, class Cloudy, class After>
+inline void run_chunks(const CallSite &c, Dev &d, bool clouds, int hint_cloudy, Before before, Clear clear, Cloudy cloudy, After after) {
+  rrtmg_ctx *ctx = c.ctx;
+  const int w = c.which, ntile = (d.ncol + 63) / 64, ctile = d.tcap;
+  for (int t0 = 0; t0 < ntile; t0 += ctile) {
+    const int nt = ntile - t0 < ctile ? ntile - t0 : ctile, ci = t0 / ctile;
+    d.col0 = t0 * 64; d.pcols = ctile * 64;
+    before(t0, nt);
+    auto variant = [&](int k, auto &launch) { (void)hipEventRecord(ctx->chunk_event(k, ci, 0), c.s); launch(t0, nt); (void)hipEventRecord(ctx->chunk_event(k, ci, 1), c.s); };
+    const bool expect_clear = clouds && hint_cloudy >= 0 && (hint_cloudy == 0 || (ctx->sorting && t0 + nt <= ntile - hint_cloudy));
+    if (expect_clear) { variant(w + 2, cloudy); variant(w, clear); }
+    else { variant(w, clear); if (clouds) variant(w + 2, cloudy); }
+    d.hint_out = t0 + ctile >= ntile ? (int32_t *)&ctx->hint[w].ncloudy : nullptr;
+    after(t0, nt);
+  }
+  ctx->hint[w].ntile = ntile; ctx->hint[w].nlay = d.nlay;
+  ctx->ev_chunks[w] = (ntile + ctile - 1) / ctile; ctx->ev_chunks[w + 2] = clouds ? ctx->ev_chunks[w] : 0;
+}
+// ---- epilogue: status + outputs ---------------------------------------------------------------------------------------------------
+// oc[nout]: the standard outputs plus what opt_out_append added (read for a host-pointer call only).  A deferred call returns
+// once enqueued, its flag pending; a host-pointer call downloads outputs and flag behind one synchronise; a synchronous
+// device-resident call reads the flag.
+inline int call_finish(const CallSite &c, int memspace, const OutCopy *oc, int nout, int *err_dev) {
+  rrtmg_ctx *ctx = c.ctx;
+  RRTMG_HIP_CHECK(ctx, hipGetLastError());
+  if (ctx->deferred && memspace == 1) { ctx->pending[c.which] = true; ctx->status = 0; return RRTMG_OK; }
+  int herr = 0;
+  if (memspace == 0) {
+    if (const int rc = copy_out(ctx, c.s, oc, nout, err_dev, &herr)) return rc;
+  } else {
+    RRTMG_HIP_CHECK(ctx, hipMemcpyAsync(&herr, err_dev, sizeof(int), hipMemcpyDeviceToHost, c.s));
+    RRTMG_HIP_CHECK(ctx, hipStreamSynchronize(c.s));
+  }
+  if (herr) return c.which == 0 ? ctx->fail(herr, "shortwave: %s", status_message(herr)) : ctx->fail(herr, "longwave: %s", status_message(herr));
+  ctx->status = 0;
+  return RRTMG_OK;
+}
+
+}  // namespace rrtmg

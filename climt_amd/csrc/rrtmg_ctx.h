@@ -204,8 +204,7 @@ void free_lw_desc(rrtmg_ctx *ctx);
 // (sf, c, b: what rrtmg_hip_sw_fluxes_surface takes, each checked and with at least one member set, or nullptr)
 int sw_fluxes_impl(rrtmg_ctx *ctx, const rrtmg_sw_args *a, const rrtmg_sw_surface *sf = nullptr, const rrtmg_sw_components *c = nullptr,
                    const rrtmg_sw_band_fluxes *b = nullptr);
-int lw_fluxes_impl(rrtmg_ctx *ctx, const rrtmg_lw_args *a);
-int lw_fluxes_bands_impl(rrtmg_ctx *ctx, const rrtmg_lw_args *a, const rrtmg_lw_band_fluxes *b);
+int lw_fluxes_impl(rrtmg_ctx *ctx, const rrtmg_lw_args *a, const rrtmg_lw_band_fluxes *b = nullptr);   // (b: as for the shortwave)
 int sw_init_impl(rrtmg_ctx *ctx, double cpdair, const char *blob);
 int lw_init_impl(rrtmg_ctx *ctx, double cpdair, const char *blob);
 int mcica_mask_impl(rrtmg_ctx *ctx, int which, int ncol, int nlay, int icld, int permuteseed, int irng,

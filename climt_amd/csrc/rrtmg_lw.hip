@@ -11,13 +11,10 @@
 //     lw_solve_all_kernel  one launch per variant (cloud-free / cloudy tiles): wavefront = tile(64 columns) x work item (4|2
 //                          g-points of a band), workgroup = 4 tiles of one item sharing its k-distribution slice in LDS
 //     lw_fluxheat_kernel   <<<(tiles, levels/15), 16 waves>>>  band / g-point integration per interface + heating rates
-#include <future>
-
-#include "rrtmg_ctx.h"
+// The host steps this call shares with the shortwave's (gate, checks, chunk plan and loop, mask choice, epilogue): rrtmg_call.h
+#include "rrtmg_call.h"
 #include "rrtmg_lw_device.h"
 #include "rrtmg_lw_host.h"
-#include "rrtmg_mcica_kernels.h"
-#include "rrtmg_sort.h"
 
 namespace rrtmg {
 
@@ -200,18 +197,12 @@ int lw_init_impl(rrtmg_ctx *ctx, double cpdair, const char *blob_path) {
   return RRTMG_OK;
 }
 
-static int lw_fluxes_run(rrtmg_ctx *ctx, const rrtmg_lw_args *a, const rrtmg_lw_band_fluxes *bp);
 // the call on an internal copy of its inputs, cloud-free columns first (rrtmg_sort.h; see sw_sorted_call)
 static int lw_sorted_call(rrtmg_ctx *ctx, const rrtmg_lw_args *a) {
-  int rc = ctx_prepare_device(ctx);
-  if (rc) return rc;
-  hipStream_t s = ctx->deferred ? ctx->stream_lw : ctx->stream;
-  const int N = a->ncol, L = a->nlay;
-  ColumnSort cs(ctx, s, N, L, "lw.sort.");
-  if (!cs.prepare(a->cldfr)) return ctx->status;
-  rrtmg_lw_args b = *a;
-  b.ncol = cs.Np; b.shard_col0 = 0; b.shard_ncol = 0;
-  const size_t l = (size_t)L, l1 = l + 1;
+  ColumnSort cs(ctx, nullptr, a->ncol, a->nlay, "lw.sort.");
+  rrtmg_lw_args b;
+  if (int rc = sorted_head(ctx, 1, a, cs, b)) return rc;
+  const size_t l = (size_t)a->nlay, l1 = l + 1;
   b.play = cs.gather("play", a->play, l); b.plev = cs.gather("plev", a->plev, l1); b.tlay = cs.gather("tlay", a->tlay, l);
   b.tlev = cs.gather("tlev", a->tlev, l1); b.tsfc = cs.gather("tsfc", a->tsfc, 1);
   b.h2ovmr = cs.gather("h2o", a->h2ovmr, l); b.o3vmr = cs.gather("o3", a->o3vmr, l); b.co2vmr = cs.gather("co2", a->co2vmr, l);
@@ -228,33 +219,20 @@ static int lw_sorted_call(rrtmg_ctx *ctx, const rrtmg_lw_args *a) {
   double *o[8] = {cs.out("o0", l1), cs.out("o1", l1), cs.out("o2", l), cs.out("o3", l1), cs.out("o4", l1), cs.out("o5", l),
                   dr ? cs.out("o6", l1) : nullptr, dr ? cs.out("o7", l1) : nullptr};
   if (!cs.ok) return ctx->status;
-  if (!a->uflx || !a->dflx || !a->hr || !a->uflxc || !a->dflxc || !a->hrc) return ctx->fail(RRTMG_ERR_ARG, "output array is NULL");
+  double *u[8] = {a->uflx, a->dflx, a->hr, a->uflxc, a->dflxc, a->hrc, a->duflx_dt, a->duflxc_dt};
+  if (int rc = check_outputs(ctx, u)) return rc;
   if (dr && (!a->duflx_dt || !a->duflxc_dt)) return ctx->fail(RRTMG_ERR_ARG, "idrv=1 needs duflx_dt/duflxc_dt");
   b.uflx = o[0]; b.dflx = o[1]; b.hr = o[2]; b.uflxc = o[3]; b.dflxc = o[4]; b.hrc = o[5]; b.duflx_dt = o[6]; b.duflxc_dt = o[7];
-  ctx->sorting = true;
-  rc = lw_fluxes_run(ctx, &b, nullptr);
-  ctx->sorting = false;
-  if (rc) return rc;
-  double *u[8] = {a->uflx, a->dflx, a->hr, a->uflxc, a->dflxc, a->hrc, a->duflx_dt, a->duflxc_dt};
-  for (int k = 0; k < (dr ? 8 : 6); ++k) cs.scatter(o[k], u[k], (k == 2 || k == 5) ? l : l1);
-  RRTMG_HIP_CHECK(ctx, hipGetLastError());
-  if (!ctx->deferred) RRTMG_HIP_CHECK(ctx, hipStreamSynchronize(s));
-  return RRTMG_OK;
+  return sorted_tail(ctx, cs, dr ? 8 : 6, o, u, [&]() { return lw_fluxes_impl(ctx, &b); });
 }
 
 // bp: the band fluxes requested (at least one member set, levels 0 or 1), or nullptr for the plain call.  A call with bands
 // is never sorted: its outputs would need a scatter of their own.
-static int lw_fluxes_run(rrtmg_ctx *ctx, const rrtmg_lw_args *a, const rrtmg_lw_band_fluxes *bp) {
-  if (!bp && ctx->lw_ready && a && ctx->sort_columns && !ctx->sorting && a->memspace == 1 && a->icld != 0 && a->cldfr && a->ncol >= 128 && a->nlay > 0 && a->nlay <= 256 &&
-      !(a->mcica && a->irng != 0))
-    return lw_sorted_call(ctx, a);
-  if (!ctx->lw_ready) return ctx->fail(RRTMG_ERR_NOT_INITIALISED, "rrtmg_hip_lw_init has not been called");
-  if (!a || a->ncol <= 0 || a->nlay <= 0) return ctx->fail(RRTMG_ERR_ARG, "ncol/nlay must be positive");
-  if (a->nlay > 256) return ctx->fail(RRTMG_ERR_ARG, "nlay > 256 not supported (cloud-mask words)");
-  if (a->shard_ncol != 0 && (a->shard_col0 < 0 || a->shard_col0 + a->ncol > a->shard_ncol)) return ctx->fail(RRTMG_ERR_ARG, "shard_col0/shard_ncol do not contain ncol columns");
-  int rc = ctx_prepare_device(ctx);
+int lw_fluxes_impl(rrtmg_ctx *ctx, const rrtmg_lw_args *a, const rrtmg_lw_band_fluxes *bp) {
+  if (call_is_sorted(ctx, 1, a, bp != nullptr)) return lw_sorted_call(ctx, a);
+  int rc = call_begin(ctx, 1, a);
   if (rc) return rc;
-  hipStream_t s = (ctx->deferred && a->memspace == 1) ? ctx->stream_lw : ctx->stream;
+  const CallSite c{ctx, 1, call_stream(ctx, 1, a->memspace)}; hipStream_t s = c.s;
   const int N = a->ncol, L = a->nlay;
   const size_t nl = (size_t)N * L, nl1 = (size_t)N * (L + 1);
   const LwTab &T = *(LwTab *)ctx->lw_desc;
@@ -313,18 +291,13 @@ static int lw_fluxes_run(rrtmg_ctx *ctx, const rrtmg_lw_args *a, const rrtmg_lw_
   }
   const int ntile = (N + 63) / 64;
   const int nk = d.idrv ? 6 : 4;
-  // what the previous call found (rrtmg_ctx::CallHint): read without waiting, used for speed only
-  const int hint_cloudy = (ctx->hint[1].ntile == ntile && ctx->hint[1].nlay == L) ? ctx->hint[1].ncloudy : -1;
-  int chunk_tiles = ctx->chunk_tiles;
-  if (ctx->chunk_auto && L > 80 && hint_cloudy >= 0 && 10 * hint_cloudy >= 9 * ntile) chunk_tiles = 64;   // deep cloudy grid: DESIGN.md 5
-  chunk_tiles = ctx->plan_chunks(1, chunk_tiles, ntile, L, (clouds && !ctx->sorting) ? hint_cloudy : -1,   /* (a sorted grid keeps the small chunks: its tiles are segregated by kind, every chunk but one is of one kind) */ (size_t)kLwNGpt * LF_N * L * 64 * sizeof(double), "lw.w.scratch");
-  const int ctile = ntile < chunk_tiles ? ntile : chunk_tiles;   // tiles per solve chunk
-  int32_t *tlist = (int32_t *)ctx->buf("lw.w.tilelist", (size_t)(2 * ctile + 2) * 4);
-  if (!tlist) ok = false;
-  d.tcap = ctile; d.tlist = tlist; d.tcnt = tlist ? tlist + 2 * d.tcap : nullptr;
+  const int hint_cloudy = call_hint_cloudy(ctx, 1, ntile, L);
+  const int ctile = plan_call_chunks(ctx, 1, d, clouds, hint_cloudy, (size_t)kLwNGpt * LF_N * L * 64 * sizeof(double));   // tiles per solve chunk
+  if (!d.tlist) ok = false;
   d.scratch = wd("scratch", (size_t)ctile * kLwNGpt * LF_N * L * 64);
   d.part = wd("part", (size_t)T.nitem * nk * (L + 1) * ctile * 64);
-  if (!a->uflx || !a->dflx || !a->hr || !a->uflxc || !a->dflxc || !a->hrc) return ctx->fail(RRTMG_ERR_ARG, "output array is NULL");
+  double *const u[6] = {a->uflx, a->dflx, a->hr, a->uflxc, a->dflxc, a->hrc};
+  if ((rc = check_outputs(ctx, u))) return rc;
   if (d.idrv && (!a->duflx_dt || !a->duflxc_dt)) return ctx->fail(RRTMG_ERR_ARG, "idrv=1 needs duflx_dt/duflxc_dt");
   if (a->memspace == 1) {
     d.uflx = a->uflx; d.dflx = a->dflx; d.hr = a->hr; d.uflxc = a->uflxc; d.dflxc = a->dflxc; d.hrc = a->hrc;
@@ -335,30 +308,18 @@ static int lw_fluxes_run(rrtmg_ctx *ctx, const rrtmg_lw_args *a, const rrtmg_lw_
     if (d.idrv) { d.duflx_dt = wd("o.du", nl1); d.duflxc_dt = wd("o.duc", nl1); }
   }
   // band fluxes: [16][nrow][ncol] per requested member
+  static const rrtmg_lw_band_fluxes no_band{}; const rrtmg_lw_band_fluxes &br = bp ? *bp : no_band;   // (nothing requested: every member nullptr)
   LwBandOut bo{};
-  double *bpo[4] = {};   // the caller's arrays, in LwBandOut's order
-  double **boo[4] = {&bo.up, &bo.dn, &bo.upc, &bo.dnc};
-  const int brow = bp && bp->levels ? 2 : L + 1;
-  const size_t nband = (size_t)kLwNBand * brow * N;
-  if (bp) {
-    static const char *const names[4] = {"ob.up", "ob.dn", "ob.upc", "ob.dnc"};
-    double *const req[4] = {bp->up, bp->dn, bp->upc, bp->dnc};
-    for (int k = 0; k < 4; ++k)
-      if ((bpo[k] = req[k])) *boo[k] = a->memspace == 1 ? req[k] : wd(names[k], nband);
-  }
+  const OptOut bpt[4] = {{"ob.up", br.up, &bo.up}, {"ob.dn", br.dn, &bo.dn}, {"ob.upc", br.upc, &bo.upc}, {"ob.dnc", br.dnc, &bo.dnc}};
+  const size_t nband = (size_t)kLwNBand * (br.levels ? 2 : L + 1) * N;
+  opt_out_bind(bpt, 4, a->memspace, nband, wd);
   if (!ok) return ctx->status;
 #ifdef RRTMG_PROFILE
   d.phase = (unsigned long long *)ctx->buf("lw.w.phase", 16 * 8);
   if (!d.phase) return ctx->status;
   RRTMG_HIP_CHECK(ctx, hipMemsetAsync(d.phase, 0, 16 * 8, s));
 #endif
-  d.err = ctx->err_dev + 1;   // [0] shortwave, [1] longwave
-  const bool deferred_call = ctx->deferred && a->memspace == 1;
-  if (!deferred_call) {
-    // a synchronous call owns its flag; flags of calls still pending from deferred mode are collected first
-    if (ctx->pending[0] || ctx->pending[1]) { const int prc = rrtmg_hip_synchronize(ctx); if (prc) return prc; }
-    RRTMG_HIP_CHECK(ctx, hipMemsetAsync(d.err, 0, sizeof(int), s));
-  }   // deferred: the flag accumulates (atomicMax) until rrtmg_hip_synchronize collects and clears it
+  if ((rc = call_own_flag(c, a->memspace, d))) return rc;
 
   const dim3 gcol(ntile), blk(64);
   if (!d.tlev) {
@@ -372,59 +333,28 @@ static int lw_fluxes_run(rrtmg_ctx *ctx, const rrtmg_lw_args *a, const rrtmg_lw_
   // (more than 64 KB of dynamic LDS has to be allowed per kernel once; if the runtime refuses, the scan re-reads the slab)
   const bool big_lds = ctx->allow_dynamic_lds(0, (const void *)lw_prep_fused_kernel, kLwKeepLayers * 3 * 64 * (int)sizeof(double));
   const int keep_layers = (L <= kLwKeepLayers && (big_lds || (size_t)L * 3 * 64 * sizeof(double) <= 64 * 1024)) ? L : 0;
-  if (clouds) {
-    if (d.mcica) {
-      if (a->cldfmcl) {
-        hipLaunchKernelGGL(mask_from_cldfmcl_kernel, dim3(ntile, kLwNGpt), blk, 0, s, N, L, kLwNGpt, cldfmcl_dev, d.mask, d.nw);
-      } else if (a->irng == 0) {
-        const uint32_t *jumps = kiss_jumps_device(ctx, 1, kLwNGpt, L, d.icld, a->permuteseed, s);
-        if (!jumps) return ctx->status;
-        hipLaunchKernelGGL(kiss_mask_kernel, dim3(kLwNGpt, ntile), blk, 0, s, N, L, d.icld, d.play, d.cldfr, d.mask, d.nw, d.err, jumps);
-      } else {
-        rc = mt_mask_device(ctx, 1, N, L, kLwNGpt, d.icld, a->permuteseed, d.cldfr, d.mask, d.nw, a->shard_col0, a->shard_ncol, s);
-        if (rc) return rc;
-      }
-      hipLaunchKernelGGL(lw_anymask_kernel, gcol, blk, 0, s, d);
-    }
-  }
+  if (clouds && d.mcica && (rc = mcica_mask_launch(c, kLwNGpt, d, a, cldfmcl_dev))) return rc;
+  if (clouds && d.mcica) hipLaunchKernelGGL(lw_anymask_kernel, gcol, blk, 0, s, d);
   // preparation, solve and band integration, one column chunk at a time (see sw_fluxes_impl)
-  for (int t0 = 0; t0 < ntile; t0 += ctile) {
-    const int nt = ntile - t0 < ctile ? ntile - t0 : ctile;
-    d.col0 = t0 * 64; d.pcols = ctile * 64;
-    hipLaunchKernelGGL(lw_prep_fused_kernel, dim3(nt), dim3(64 * kPrepWaves), (size_t)keep_layers * 3 * 64 * sizeof(double), s, d, T,
-                       clouds && !d.mcica ? 1 : 0, maxrand ? 1 : 0, keep_layers, t0);
-    if (clouds && d.mcica) hipLaunchKernelGGL(lw_cloudmc_kernel, dim3(nt, L), blk, 0, s, d, T, t0);
-    hipLaunchKernelGGL(tile_lists_kernel, dim3(1), blk, 0, s, d.tile_cld + t0, nt, tlist, tlist + 2 * d.tcap, d.tcap);
-    const dim3 lwwg(64 * kLwWgWaves);
-    const int lwgrid = (nt + kLwTileGroup - 1) / kLwTileGroup * kLwGroupBlocks * T.nitem;
-    const int ci = t0 / ctile;
-    auto clear_variant = [&]() {
-      (void)hipEventRecord(ctx->chunk_event(1, ci, 0), s);
-      hipLaunchKernelGGL((lw_solve_all_kernel<false, false>), dim3(lwgrid), lwwg, 0, s, d, T, t0, nt);
-      (void)hipEventRecord(ctx->chunk_event(1, ci, 1), s);
-    };
-    auto cloudy_variant = [&]() {
-      (void)hipEventRecord(ctx->chunk_event(3, ci, 0), s);
-      if (maxrand) hipLaunchKernelGGL((lw_solve_all_kernel<true, true>), dim3(lwgrid), lwwg, 0, s, d, T, t0, nt);
-      else hipLaunchKernelGGL((lw_solve_all_kernel<true, false>), dim3(lwgrid), lwwg, 0, s, d, T, t0, nt);
-      (void)hipEventRecord(ctx->chunk_event(3, ci, 1), s);
-    };
-    // the variant expected to find nothing goes first (see sw_fluxes_impl)
-    // (a sorted grid -- rrtmg_sort.h -- has its cloud-free tiles first: the chunks in front of the previous call's cloudy-tile count
-    //  are expected to hold no cloudy tile)
-    const bool expect_clear = clouds && hint_cloudy >= 0 && (hint_cloudy == 0 || (ctx->sorting && t0 + nt <= ntile - hint_cloudy));
-    if (expect_clear) { cloudy_variant(); clear_variant(); }
-    else { clear_variant(); if (clouds) cloudy_variant(); }
-    d.hint_out = t0 + ctile >= ntile ? (int32_t *)&ctx->hint[1].ncloudy : nullptr;
-    hipLaunchKernelGGL(lw_fluxheat_kernel, dim3(nt, (L + kFluxLev) / kFluxLev), dim3(64 * (kFluxLev + 1)), 0, s, d, T, t0);
-    if (bp) {
-      if (bp->levels) hipLaunchKernelGGL(lw_bandflux_kernel, dim3(nt, 1), dim3(64 * 2), 0, s, d, T, t0, bo, 1);
-      else hipLaunchKernelGGL(lw_bandflux_kernel, dim3(nt, (L + kBandLev) / kBandLev), dim3(64 * kBandLev), 0, s, d, T, t0, bo, 0);
-    }
-  }
-  ctx->hint[1].ntile = ntile; ctx->hint[1].nlay = L;
-  ctx->ev_chunks[1] = (ntile + ctile - 1) / ctile; ctx->ev_chunks[3] = clouds ? ctx->ev_chunks[1] : 0;
-  RRTMG_HIP_CHECK(ctx, hipGetLastError());
+  const dim3 lwwg(64 * kLwWgWaves);
+  auto lwgrid = [&](int nt) { return dim3((nt + kLwTileGroup - 1) / kLwTileGroup * kLwGroupBlocks * T.nitem); };
+  run_chunks(c, d, clouds, hint_cloudy,
+    [&](int t0, int nt) {
+      hipLaunchKernelGGL(lw_prep_fused_kernel, dim3(nt), dim3(64 * kPrepWaves), (size_t)keep_layers * 3 * 64 * sizeof(double), s, d, T,
+                         clouds && !d.mcica ? 1 : 0, maxrand ? 1 : 0, keep_layers, t0);
+      if (clouds && d.mcica) hipLaunchKernelGGL(lw_cloudmc_kernel, dim3(nt, L), blk, 0, s, d, T, t0);
+      hipLaunchKernelGGL(tile_lists_kernel, dim3(1), blk, 0, s, d.tile_cld + t0, nt, (int32_t *)d.tlist, (int32_t *)d.tcnt, d.tcap);
+    },
+    [&](int t0, int nt) { hipLaunchKernelGGL((lw_solve_all_kernel<false, false>), lwgrid(nt), lwwg, 0, s, d, T, t0, nt); },
+    [&](int t0, int nt) {
+      if (maxrand) hipLaunchKernelGGL((lw_solve_all_kernel<true, true>), lwgrid(nt), lwwg, 0, s, d, T, t0, nt);
+      else hipLaunchKernelGGL((lw_solve_all_kernel<true, false>), lwgrid(nt), lwwg, 0, s, d, T, t0, nt);
+    },
+    [&](int t0, int nt) {
+      hipLaunchKernelGGL(lw_fluxheat_kernel, dim3(nt, (L + kFluxLev) / kFluxLev), dim3(64 * (kFluxLev + 1)), 0, s, d, T, t0);
+      if (bp && bp->levels) hipLaunchKernelGGL(lw_bandflux_kernel, dim3(nt, 1), dim3(64 * 2), 0, s, d, T, t0, bo, 1);
+      else if (bp) hipLaunchKernelGGL(lw_bandflux_kernel, dim3(nt, (L + kBandLev) / kBandLev), dim3(64 * kBandLev), 0, s, d, T, t0, bo, 0);
+    });
 #ifdef RRTMG_PROFILE
   {
     unsigned long long ph[16];
@@ -439,28 +369,9 @@ static int lw_fluxes_run(rrtmg_ctx *ctx, const rrtmg_lw_args *a, const rrtmg_lw_
     fprintf(stderr, "; up sweep per layer %.0f\n", ph[6] / w / L);
   }
 #endif
-
-  if (ctx->deferred && a->memspace == 1) { ctx->pending[1] = true; ctx->status = 0; return RRTMG_OK; }
-  int herr = 0;
-  if (a->memspace == 0) {
-    OutCopy oc[12] = {{a->uflx, d.uflx, nl1}, {a->dflx, d.dflx, nl1}, {a->uflxc, d.uflxc, nl1}, {a->dflxc, d.dflxc, nl1},
-                      {a->hr, d.hr, nl}, {a->hrc, d.hrc, nl}, {a->duflx_dt, d.duflx_dt, nl1}, {a->duflxc_dt, d.duflxc_dt, nl1}};
-    int nout = d.idrv ? 8 : 6;
-    if (bp)   // the requested band fluxes, behind the same synchronise
-      for (int k = 0; k < 4; ++k)
-        if (bpo[k]) oc[nout++] = {bpo[k], *boo[k], nband};
-    rc = copy_out(ctx, s, oc, nout, d.err, &herr);
-    if (rc) return rc;
-  } else {
-    RRTMG_HIP_CHECK(ctx, hipMemcpyAsync(&herr, d.err, sizeof(int), hipMemcpyDeviceToHost, s));
-    RRTMG_HIP_CHECK(ctx, hipStreamSynchronize(s));
-  }
-  if (herr) return ctx->fail(herr, "longwave: %s", status_message(herr));
-  ctx->status = 0;
-  return RRTMG_OK;
+  OutCopy oc[12] = {{a->uflx, d.uflx, nl1}, {a->dflx, d.dflx, nl1}, {a->uflxc, d.uflxc, nl1}, {a->dflxc, d.dflxc, nl1},
+                    {a->hr, d.hr, nl}, {a->hrc, d.hrc, nl}, {a->duflx_dt, d.duflx_dt, nl1}, {a->duflxc_dt, d.duflxc_dt, nl1}};
+  return call_finish(c, a->memspace, oc, opt_out_append(bpt, 4, nband, oc, d.idrv ? 8 : 6), d.err);   // the requested band fluxes behind the same synchronise
 }
-
-int lw_fluxes_impl(rrtmg_ctx *ctx, const rrtmg_lw_args *a) { return lw_fluxes_run(ctx, a, nullptr); }
-int lw_fluxes_bands_impl(rrtmg_ctx *ctx, const rrtmg_lw_args *a, const rrtmg_lw_band_fluxes *b) { return lw_fluxes_run(ctx, a, b); }
 
 }  // namespace rrtmg

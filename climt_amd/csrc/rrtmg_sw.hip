@@ -25,13 +25,10 @@
 //   With the night-column skip on (rrtmg_hip_set_sw_night_skip): sw_kiss_mask_night_kernel, sw_prep_fused_night_kernel,
 //   sw_cloud_night_kernel, sw_tile_lists_night_kernel and sw_{fluxheat,components,bandflux}_night_kernel in the places of their
 //   namesakes; the solve kernels are the same and find a night tile in neither of their lists
-#include <future>
-
-#include "rrtmg_ctx.h"
+// The host steps this call shares with the longwave's (gate, checks, chunk plan and loop, mask choice, epilogue): rrtmg_call.h
+#include "rrtmg_call.h"
 #include "rrtmg_sw_device.h"
 #include "rrtmg_sw_host.h"
-#include "rrtmg_mcica_kernels.h"
-#include "rrtmg_sort.h"
 
 namespace rrtmg {
 
@@ -494,14 +491,10 @@ int sw_init_impl(rrtmg_ctx *ctx, double cpdair, const char *blob_path) {
 
 // the call on an internal copy of its inputs, cloud-free columns first (rrtmg_sort.h; opt-in, device pointers, kissvec or no McICA)
 static int sw_sorted_call(rrtmg_ctx *ctx, const rrtmg_sw_args *a) {
-  int rc = ctx_prepare_device(ctx);
-  if (rc) return rc;
-  const int N = a->ncol, L = a->nlay;
-  ColumnSort cs(ctx, ctx->stream, N, L, "sw.sort.");
-  if (!cs.prepare(a->cldfr)) return ctx->status;
-  rrtmg_sw_args b = *a;
-  b.ncol = cs.Np; b.shard_col0 = 0; b.shard_ncol = 0;
-  const size_t l = (size_t)L, l1 = l + 1;
+  ColumnSort cs(ctx, nullptr, a->ncol, a->nlay, "sw.sort.");
+  rrtmg_sw_args b;
+  if (int rc = sorted_head(ctx, 0, a, cs, b)) return rc;
+  const size_t l = (size_t)a->nlay, l1 = l + 1;
   b.play = cs.gather("play", a->play, l); b.plev = cs.gather("plev", a->plev, l1); b.tlay = cs.gather("tlay", a->tlay, l);
   b.tlev = nullptr; b.tsfc = nullptr;   // (the shortwave reads neither)
   b.h2ovmr = cs.gather("h2o", a->h2ovmr, l); b.o3vmr = cs.gather("o3", a->o3vmr, l); b.co2vmr = cs.gather("co2", a->co2vmr, l);
@@ -518,17 +511,10 @@ static int sw_sorted_call(rrtmg_ctx *ctx, const rrtmg_sw_args *a) {
   b.cldfmcl = cs.gather("cldfmcl", a->cldfmcl, l, kSwNGpt);
   double *o[6] = {cs.out("o0", l1), cs.out("o1", l1), cs.out("o2", l), cs.out("o3", l1), cs.out("o4", l1), cs.out("o5", l)};
   if (!cs.ok) return ctx->status;
-  if (!a->swuflx || !a->swdflx || !a->swhr || !a->swuflxc || !a->swdflxc || !a->swhrc) return ctx->fail(RRTMG_ERR_ARG, "output array is NULL");
-  b.swuflx = o[0]; b.swdflx = o[1]; b.swhr = o[2]; b.swuflxc = o[3]; b.swdflxc = o[4]; b.swhrc = o[5];
-  ctx->sorting = true;
-  rc = sw_fluxes_impl(ctx, &b);
-  ctx->sorting = false;
-  if (rc) return rc;
   double *u[6] = {a->swuflx, a->swdflx, a->swhr, a->swuflxc, a->swdflxc, a->swhrc};
-  for (int k = 0; k < 6; ++k) cs.scatter(o[k], u[k], (k == 2 || k == 5) ? l : l1);
-  RRTMG_HIP_CHECK(ctx, hipGetLastError());
-  if (!ctx->deferred) RRTMG_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-  return RRTMG_OK;
+  if (int rc = check_outputs(ctx, u)) return rc;
+  b.swuflx = o[0]; b.swdflx = o[1]; b.swhr = o[2]; b.swuflxc = o[3]; b.swdflxc = o[4]; b.swhrc = o[5];
+  return sorted_tail(ctx, cs, 6, o, u, [&]() { return sw_fluxes_impl(ctx, &b); });
 }
 
 // cp: the components requested (at least one member set), or nullptr; bp: the band fluxes requested (at least one member
@@ -537,16 +523,10 @@ static int sw_sorted_call(rrtmg_ctx *ctx, const rrtmg_sw_args *a) {
 // a surface struct: its rows would need a gather of their own; nor is a call with the night-column skip on: the sort would move
 // night columns out of their tiles.
 int sw_fluxes_impl(rrtmg_ctx *ctx, const rrtmg_sw_args *a, const rrtmg_sw_surface *sp, const rrtmg_sw_components *cp, const rrtmg_sw_band_fluxes *bp) {
-  if (!cp && !bp && !sp && !ctx->sw_night_skip && ctx->sw_ready && a && ctx->sort_columns && !ctx->sorting && a->memspace == 1 && a->icld != 0 && a->cldfr && a->ncol >= 128 && a->nlay > 0 && a->nlay <= 256 &&
-      !(a->mcica && a->irng != 0))
-    return sw_sorted_call(ctx, a);
-  if (!ctx->sw_ready) return ctx->fail(RRTMG_ERR_NOT_INITIALISED, "rrtmg_hip_sw_init has not been called");
-  if (!a || a->ncol <= 0 || a->nlay <= 0) return ctx->fail(RRTMG_ERR_ARG, "ncol/nlay must be positive");
-  if (a->nlay > 256) return ctx->fail(RRTMG_ERR_ARG, "nlay > 256 not supported (cloud-mask words)");
-  if (a->shard_ncol != 0 && (a->shard_col0 < 0 || a->shard_col0 + a->ncol > a->shard_ncol)) return ctx->fail(RRTMG_ERR_ARG, "shard_col0/shard_ncol do not contain ncol columns");
-  int rc = ctx_prepare_device(ctx);
+  if (call_is_sorted(ctx, 0, a, cp || bp || sp || ctx->sw_night_skip)) return sw_sorted_call(ctx, a);
+  int rc = call_begin(ctx, 0, a);
   if (rc) return rc;
-  hipStream_t s = ctx->stream;
+  const CallSite c{ctx, 0, call_stream(ctx, 0, a->memspace)}; hipStream_t s = c.s;
   const int N = a->ncol, L = a->nlay;
   const size_t nl = (size_t)N * L, nl1 = (size_t)N * (L + 1);
   const SwTab &T = *(SwTab *)ctx->sw_desc;
@@ -625,8 +605,7 @@ int sw_fluxes_impl(rrtmg_ctx *ctx, const rrtmg_sw_args *a, const rrtmg_sw_surfac
   d.nw = (L + 63) / 64;
   if (clouds && d.mcica) { d.mask = (uint64_t *)ctx->buf("sw.w.mask", (size_t)kSwNGpt * d.nw * N * 8); if (!d.mask) ok = false; }
   const int ntile = (N + 63) / 64;
-  // what the previous call found (rrtmg_ctx::CallHint): read without waiting, used for speed only
-  const int hint_cloudy = (ctx->hint[0].ntile == ntile && ctx->hint[0].nlay == L) ? ctx->hint[0].ncloudy : -1;
+  const int hint_cloudy = call_hint_cloudy(ctx, 0, ntile, L);
   const bool night = ctx->sw_night_skip;   // the *_night_kernel of every launch below that has one
   // The count a call with the skip leaves is of the tiles that RAN cloudy: a night tile is of neither kind.  The chunk plan
   // follows the cloudy share of the tiles that were not night in that call (its night count: a hint like the other), scaled to
@@ -636,42 +615,29 @@ int sw_fluxes_impl(rrtmg_ctx *ctx, const rrtmg_sw_args *a, const rrtmg_sw_surfac
     const int nn = ctx->night_host()[0], run = ntile - nn;
     if (nn > 0 && run > 0 && hint_cloudy <= run) plan_cloudy = (int)((long)hint_cloudy * ntile / run);
   }
-  int chunk_tiles = ctx->chunk_tiles;
-  if (ctx->chunk_auto && L > 80 && plan_cloudy >= 0 && 10 * plan_cloudy >= 9 * ntile) chunk_tiles = 64;   // deep cloudy grid: DESIGN.md 5
   // (work space per tile of a mixed grid's chunk: the scratch slab, and with components the direct-beam partial planes -- half
   //  again the size of `part`, about 4 GB more on a 2048-tile chunk at 60 layers)
   const bool need_dir = cp || (bp && (bp->dndir || bp->dndirc));   // the *_dir solve variants and their partdir planes
   const size_t tile_bytes = ((size_t)kSwNGpt * F_NTOT * L + (need_dir ? (size_t)kSwNSlot * 2 * (L + 1) : 0)) * 64 * sizeof(double);
-  chunk_tiles = ctx->plan_chunks(0, chunk_tiles, ntile, L, (clouds && !ctx->sorting) ? plan_cloudy : -1,   /* (a sorted grid keeps the small chunks: its tiles are segregated by kind, every chunk but one is of one kind) */ tile_bytes, "sw.w.scratch");
-  const int ctile = ntile < chunk_tiles ? ntile : chunk_tiles;   // tiles per solve chunk
-  int32_t *tlist = (int32_t *)ctx->buf("sw.w.tilelist", (size_t)(2 * ctile + 2) * 4);
-  if (!tlist) ok = false;
-  d.tcap = ctile; d.tlist = tlist; d.tcnt = tlist ? tlist + 2 * d.tcap : nullptr;
+  const int ctile = plan_call_chunks(ctx, 0, d, clouds, plan_cloudy, tile_bytes);   // tiles per solve chunk
+  if (!d.tlist) ok = false;
   d.scratch = wd("scratch", (size_t)ctile * kSwNGpt * F_NTOT * L * 64);
   d.part = wd("part", (size_t)kSwNSlot * 4 * (L + 1) * ctile * 64);
   // components: the direct-beam partial planes [slot][2][nlay+1][pcols] (SwPartDirSink) and the outputs
   double *partdir = need_dir ? wd("partdir", (size_t)kSwNSlot * 2 * (L + 1) * ctile * 64) : nullptr;
+  static const rrtmg_sw_components no_comp{}; static const rrtmg_sw_band_fluxes no_band{};   // (nothing requested: every member nullptr)
+  const rrtmg_sw_components &cr = cp ? *cp : no_comp; const rrtmg_sw_band_fluxes &br = bp ? *bp : no_band;
   SwCompOut co{};
-  double *cpo[8] = {};   // the caller's arrays, in SwCompOut's order
-  double **coo[8] = {&co.dirdflx, &co.difdflx, &co.dirdnuv, &co.difdnuv, &co.dirdnir, &co.difdnir, &co.dirdflxc, &co.difdflxc};
-  if (cp) {
-    static const char *const names[8] = {"o.dirdflx", "o.difdflx", "o.dirdnuv", "o.difdnuv", "o.dirdnir", "o.difdnir", "o.dirdflxc", "o.difdflxc"};
-    double *const req[8] = {cp->dirdflx, cp->difdflx, cp->dirdnuv, cp->difdnuv, cp->dirdnir, cp->difdnir, cp->dirdflxc, cp->difdflxc};
-    for (int k = 0; k < 8; ++k)
-      if ((cpo[k] = req[k])) *coo[k] = a->memspace == 1 ? req[k] : wd(names[k], nl1);
-  }
+  const OptOut cpt[8] = {{"o.dirdflx", cr.dirdflx, &co.dirdflx}, {"o.difdflx", cr.difdflx, &co.difdflx}, {"o.dirdnuv", cr.dirdnuv, &co.dirdnuv},
+                         {"o.difdnuv", cr.difdnuv, &co.difdnuv}, {"o.dirdnir", cr.dirdnir, &co.dirdnir}, {"o.difdnir", cr.difdnir, &co.difdnir},
+                         {"o.dirdflxc", cr.dirdflxc, &co.dirdflxc}, {"o.difdflxc", cr.difdflxc, &co.difdflxc}};
+  opt_out_bind(cpt, 8, a->memspace, nl1, wd);
   // band fluxes: [14][nrow][ncol] per requested member
   SwBandOut bo{};
-  double *bpo[6] = {};   // the caller's arrays, in SwBandOut's order
-  double **boo[6] = {&bo.up, &bo.dn, &bo.upc, &bo.dnc, &bo.dndir, &bo.dndirc};
-  const int brow = bp && bp->levels ? 2 : L + 1;
-  const size_t nband = (size_t)kSwNBand * brow * N;
-  if (bp) {
-    static const char *const names[6] = {"ob.up", "ob.dn", "ob.upc", "ob.dnc", "ob.dndir", "ob.dndirc"};
-    double *const req[6] = {bp->up, bp->dn, bp->upc, bp->dnc, bp->dndir, bp->dndirc};
-    for (int k = 0; k < 6; ++k)
-      if ((bpo[k] = req[k])) *boo[k] = a->memspace == 1 ? req[k] : wd(names[k], nband);
-  }
+  const OptOut bpt[6] = {{"ob.up", br.up, &bo.up}, {"ob.dn", br.dn, &bo.dn}, {"ob.upc", br.upc, &bo.upc}, {"ob.dnc", br.dnc, &bo.dnc},
+                         {"ob.dndir", br.dndir, &bo.dndir}, {"ob.dndirc", br.dndirc, &bo.dndirc}};
+  const size_t nband = (size_t)kSwNBand * (br.levels ? 2 : L + 1) * N;
+  opt_out_bind(bpt, 6, a->memspace, nband, wd);
   if (!svar_col.empty()) {   // per-column solar-variability multipliers (rare: facular/sunspot amplitudes != 1)
     double *p = wd("svarcol", svar_col.size());
     if (!ok) return ctx->status;
@@ -685,14 +651,8 @@ int sw_fluxes_impl(rrtmg_ctx *ctx, const rrtmg_sw_args *a, const rrtmg_sw_surfac
     d.swuflx = wd("o.uflx", nl1); d.swdflx = wd("o.dflx", nl1); d.swhr = wd("o.hr", nl); d.swuflxc = wd("o.uflxc", nl1); d.swdflxc = wd("o.dflxc", nl1); d.swhrc = wd("o.hrc", nl);
   }
   if (!ok) return ctx->status;
-  if (!a->swuflx || !a->swdflx || !a->swhr || !a->swuflxc || !a->swdflxc || !a->swhrc) return ctx->fail(RRTMG_ERR_ARG, "output array is NULL");
-  d.err = ctx->err_dev;
-  const bool deferred_call = ctx->deferred && a->memspace == 1;
-  if (!deferred_call) {
-    // a synchronous call owns its flag; flags of calls still pending from deferred mode are collected first
-    if (ctx->pending[0] || ctx->pending[1]) { const int prc = rrtmg_hip_synchronize(ctx); if (prc) return prc; }
-    RRTMG_HIP_CHECK(ctx, hipMemsetAsync(d.err, 0, sizeof(int), s));
-  }   // deferred: the flag accumulates (atomicMax) until rrtmg_hip_synchronize collects and clears it
+  double *const u[6] = {a->swuflx, a->swdflx, a->swhr, a->swuflxc, a->swdflxc, a->swhrc};
+  if ((rc = check_outputs(ctx, u)) || (rc = call_own_flag(c, a->memspace, d))) return rc;
 
   // ---- launches ---------------------------------------------------------------------------
   const dim3 gcl(ntile, L), blk(64);
@@ -703,21 +663,7 @@ int sw_fluxes_impl(rrtmg_ctx *ctx, const rrtmg_sw_args *a, const rrtmg_sw_surfac
     hipLaunchKernelGGL(sw_aer_kernel, gcl, blk, 0, s, d, T, ecaer, ta, om, as);
     d.tauaer = ta; d.ssaaer = om; d.asmaer = as;
   }
-  if (clouds) {
-    if (d.mcica) {
-      if (a->cldfmcl) {
-        hipLaunchKernelGGL(mask_from_cldfmcl_kernel, dim3(ntile, kSwNGpt), blk, 0, s, N, L, kSwNGpt, cldfmcl_dev, d.mask, d.nw);
-      } else if (a->irng == 0) {
-        const uint32_t *jumps = kiss_jumps_device(ctx, 0, kSwNGpt, L, d.icld, a->permuteseed, s);
-        if (!jumps) return ctx->status;
-        if (night) hipLaunchKernelGGL(sw_kiss_mask_night_kernel, dim3(kSwNGpt, ntile), blk, 0, s, N, L, d.icld, d.play, d.cldfr, d.mask, d.nw, d.err, jumps, d.coszen);
-        else hipLaunchKernelGGL(kiss_mask_kernel, dim3(kSwNGpt, ntile), blk, 0, s, N, L, d.icld, d.play, d.cldfr, d.mask, d.nw, d.err, jumps);
-      } else {
-        rc = mt_mask_device(ctx, 0, N, L, kSwNGpt, d.icld, a->permuteseed, d.cldfr, d.mask, d.nw, a->shard_col0, a->shard_ncol, s);
-        if (rc) return rc;
-      }
-    }
-  }
+  if (clouds && d.mcica && (rc = mcica_mask_launch(c, kSwNGpt, d, a, cldfmcl_dev, night ? sw_kiss_mask_night_kernel : nullptr, d.coszen))) return rc;
   // preparation, solve and spectral integration, one column chunk at a time: the chunk's prep rows (58 MB at 8192 columns x
   // 60 layers) are read by its 32 work items while still in the L2s / the Infinity Cache, not streamed back from HBM after
   // the preparation of the whole grid (every solve launch of every chunk has its own event pair)
@@ -725,85 +671,46 @@ int sw_fluxes_impl(rrtmg_ctx *ctx, const rrtmg_sw_args *a, const rrtmg_sw_surfac
   // built and measured in round 6: 131 072 clear-sky columns 23.2 -> 24.1-24.5 ms, config-5 shard 72.9-73.7 -> 74.1-74.9,
   // config-4 shard 5.83-5.94 -> 5.79-5.89: the other spectrum's solve already runs over a chunk's preparation and
   // integration, and two solves of one spectrum sharing the CUs take 1.7 x as long each.  docs/EXPERIMENTS.md E.)
-  for (int t0 = 0; t0 < ntile; t0 += ctile) {
-    const int nt = ntile - t0 < ctile ? ntile - t0 : ctile;
-    d.col0 = t0 * 64; d.pcols = ctile * 64;
-    if (night) {
-      hipLaunchKernelGGL(sw_prep_fused_night_kernel, dim3(nt), dim3(64 * kPrepWaves), (size_t)L * 64 * sizeof(int), s, d, T, clouds && !d.mcica ? 1 : 0, t0, night_cnt);
-      if (clouds && d.mcica) hipLaunchKernelGGL(sw_cloud_night_kernel, dim3(nt, L), blk, 0, s, d, T, t0);
-      hipLaunchKernelGGL(sw_tile_lists_night_kernel, dim3(1), blk, 0, s, d.tile_cld + t0, nt, tlist, tlist + 2 * d.tcap, d.tcap);
-    } else {
-      hipLaunchKernelGGL(sw_prep_fused_kernel, dim3(nt), dim3(64 * kPrepWaves), (size_t)L * 64 * sizeof(int), s, d, T, clouds && !d.mcica ? 1 : 0, t0);
-      if (clouds && d.mcica) hipLaunchKernelGGL(sw_cloud_kernel, dim3(nt, L), blk, 0, s, d, T, t0);
-      hipLaunchKernelGGL(tile_lists_kernel, dim3(1), blk, 0, s, d.tile_cld + t0, nt, tlist, tlist + 2 * d.tcap, d.tcap);
-    }
-    const int ngrp = (nt + kSwWgWaves - 1) / kSwWgWaves;
-    const dim3 wg(64 * kSwWgWaves);
-    const int ci = t0 / ctile;
-    auto clear_variant = [&]() {
-      (void)hipEventRecord(ctx->chunk_event(0, ci, 0), s);
-      if (partdir) hipLaunchKernelGGL(sw_solve_all_dir_kernel<false>, dim3(ngrp * T.nitem), wg, 0, s, d, T, t0, nt, partdir);
-      else hipLaunchKernelGGL(sw_solve_all_kernel<false>, dim3(ngrp * T.nitem), wg, 0, s, d, T, t0, nt);
-      (void)hipEventRecord(ctx->chunk_event(0, ci, 1), s);
-    };
-    auto cloudy_variant = [&]() {
-      (void)hipEventRecord(ctx->chunk_event(2, ci, 0), s);
-      const dim3 gc((nt + kC4Waves - 1) / kC4Waves * T.nitem), bc(64 * kC4Waves);
+  // Each launch stage's geometry once; with the night-column skip on, the *_night_kernel of every stage that has one
+  const auto cloud_k = night ? sw_cloud_night_kernel : sw_cloud_kernel;
+  const auto lists_k = night ? sw_tile_lists_night_kernel : tile_lists_kernel;
+  const auto comp_k = night ? sw_components_night_kernel : sw_components_kernel;
+  const auto band_k = night ? sw_bandflux_night_kernel : sw_bandflux_kernel;
+  const dim3 bprep(64 * kPrepWaves), wg(64 * kSwWgWaves), bc(64 * kC4Waves), bfl(64 * (kFluxLev + 1));
+  const size_t lds_prep = (size_t)L * 64 * sizeof(int);
+  const int prep_clouds = clouds && !d.mcica ? 1 : 0;
+  run_chunks(c, d, clouds, hint_cloudy,
+    [&](int t0, int nt) {
+      if (night) hipLaunchKernelGGL(sw_prep_fused_night_kernel, dim3(nt), bprep, lds_prep, s, d, T, prep_clouds, t0, night_cnt);
+      else hipLaunchKernelGGL(sw_prep_fused_kernel, dim3(nt), bprep, lds_prep, s, d, T, prep_clouds, t0);
+      if (clouds && d.mcica) hipLaunchKernelGGL(cloud_k, dim3(nt, L), blk, 0, s, d, T, t0);
+      hipLaunchKernelGGL(lists_k, dim3(1), blk, 0, s, d.tile_cld + t0, nt, (int32_t *)d.tlist, (int32_t *)d.tcnt, d.tcap);
+    },
+    [&](int t0, int nt) {
+      const dim3 g((nt + kSwWgWaves - 1) / kSwWgWaves * T.nitem);
+      if (partdir) hipLaunchKernelGGL(sw_solve_all_dir_kernel<false>, g, wg, 0, s, d, T, t0, nt, partdir);
+      else hipLaunchKernelGGL(sw_solve_all_kernel<false>, g, wg, 0, s, d, T, t0, nt);
+    },
+    [&](int t0, int nt) {
+      const dim3 gc((nt + kC4Waves - 1) / kC4Waves * T.nitem);
       if (partdir) hipLaunchKernelGGL(sw_solve_cloudy_dir_kernel, gc, bc, 0, s, d, T, t0, nt, partdir);
       else hipLaunchKernelGGL(sw_solve_cloudy_kernel, gc, bc, 0, s, d, T, t0, nt);
-      (void)hipEventRecord(ctx->chunk_event(2, ci, 1), s);
-    };
-    // the variant expected to find nothing goes first (order is speed only: each tile belongs to exactly one of them)
-    // (a sorted grid -- rrtmg_sort.h -- has its cloud-free tiles first: the chunks in front of the previous call's cloudy-tile count
-    //  are expected to hold no cloudy tile)
-    const bool expect_clear = clouds && hint_cloudy >= 0 && (hint_cloudy == 0 || (ctx->sorting && t0 + nt <= ntile - hint_cloudy));
-    if (expect_clear) { cloudy_variant(); clear_variant(); }
-    else { clear_variant(); if (clouds) cloudy_variant(); }
-    d.hint_out = t0 + ctile >= ntile ? (int32_t *)&ctx->hint[0].ncloudy : nullptr;
-    const dim3 gfl(nt, (L + kFluxLev) / kFluxLev), bfl(64 * (kFluxLev + 1)), gco(nt, (L + kCompLev) / kCompLev), gba(nt, (L + kBandLev) / kBandLev);
-    if (night) {
-      hipLaunchKernelGGL(sw_fluxheat_night_kernel, gfl, bfl, 0, s, d, T, t0, night_cnt, d.hint_out ? (int32_t *)ctx->night_host() : nullptr);
-      if (cp) hipLaunchKernelGGL(sw_components_night_kernel, gco, dim3(64 * kCompLev), 0, s, d, T, t0, partdir, co);
-      if (bp) {
-        if (bp->levels) hipLaunchKernelGGL(sw_bandflux_night_kernel, dim3(nt, 1), dim3(64 * 2), 0, s, d, T, t0, partdir, bo, 1);
-        else hipLaunchKernelGGL(sw_bandflux_night_kernel, gba, dim3(64 * kBandLev), 0, s, d, T, t0, partdir, bo, 0);
-      }
-      continue;
-    }
-    hipLaunchKernelGGL(sw_fluxheat_kernel, gfl, bfl, 0, s, d, T, t0);
-    if (cp) hipLaunchKernelGGL(sw_components_kernel, gco, dim3(64 * kCompLev), 0, s, d, T, t0, partdir, co);
-    if (bp) {
-      if (bp->levels) hipLaunchKernelGGL(sw_bandflux_kernel, dim3(nt, 1), dim3(64 * 2), 0, s, d, T, t0, partdir, bo, 1);
-      else hipLaunchKernelGGL(sw_bandflux_kernel, gba, dim3(64 * kBandLev), 0, s, d, T, t0, partdir, bo, 0);
-    }
-  }
+    },
+    [&](int t0, int nt) {
+      const dim3 gfl(nt, (L + kFluxLev) / kFluxLev);
+      if (night) hipLaunchKernelGGL(sw_fluxheat_night_kernel, gfl, bfl, 0, s, d, T, t0, night_cnt, d.hint_out ? (int32_t *)ctx->night_host() : nullptr);
+      else hipLaunchKernelGGL(sw_fluxheat_kernel, gfl, bfl, 0, s, d, T, t0);
+      if (cp) hipLaunchKernelGGL(comp_k, dim3(nt, (L + kCompLev) / kCompLev), dim3(64 * kCompLev), 0, s, d, T, t0, partdir, co);
+      if (bp && bp->levels) hipLaunchKernelGGL(band_k, dim3(nt, 1), dim3(64 * 2), 0, s, d, T, t0, partdir, bo, 1);
+      else if (bp) hipLaunchKernelGGL(band_k, dim3(nt, (L + kBandLev) / kBandLev), dim3(64 * kBandLev), 0, s, d, T, t0, partdir, bo, 0);
+    });
   ctx->sw_night_reported = night;   // (rrtmg_hip_sw_night_last: this call's counts, once it has completed)
-  ctx->hint[0].ntile = ntile; ctx->hint[0].nlay = L;
-  ctx->ev_chunks[0] = (ntile + ctile - 1) / ctile; ctx->ev_chunks[2] = clouds ? ctx->ev_chunks[0] : 0;
-  RRTMG_HIP_CHECK(ctx, hipGetLastError());
 
   // ---- status + outputs -------------------------------------------------------------------
-  if (ctx->deferred && a->memspace == 1) { ctx->pending[0] = true; ctx->status = 0; return RRTMG_OK; }
-  int herr = 0;
-  if (a->memspace == 0) {
-    OutCopy oc[20] = {{a->swuflx, d.swuflx, nl1}, {a->swdflx, d.swdflx, nl1}, {a->swuflxc, d.swuflxc, nl1}, {a->swdflxc, d.swdflxc, nl1},
-                      {a->swhr, d.swhr, nl}, {a->swhrc, d.swhrc, nl}};
-    int nout = 6;
-    if (cp)   // the requested components, behind the same synchronise
-      for (int k = 0; k < 8; ++k)
-        if (cpo[k]) oc[nout++] = {cpo[k], *coo[k], nl1};
-    if (bp)
-      for (int k = 0; k < 6; ++k)
-        if (bpo[k]) oc[nout++] = {bpo[k], *boo[k], nband};
-    rc = copy_out(ctx, s, oc, nout, d.err, &herr);
-    if (rc) return rc;
-  } else {
-    RRTMG_HIP_CHECK(ctx, hipMemcpyAsync(&herr, d.err, sizeof(int), hipMemcpyDeviceToHost, s));
-    RRTMG_HIP_CHECK(ctx, hipStreamSynchronize(s));
-  }
-  if (herr) return ctx->fail(herr, "shortwave: %s", status_message(herr));
-  ctx->status = 0;
-  return RRTMG_OK;
+  OutCopy oc[20] = {{a->swuflx, d.swuflx, nl1}, {a->swdflx, d.swdflx, nl1}, {a->swuflxc, d.swuflxc, nl1}, {a->swdflxc, d.swdflxc, nl1},
+                    {a->swhr, d.swhr, nl}, {a->swhrc, d.swhrc, nl}};
+  const int nout = opt_out_append(bpt, 6, nband, oc, opt_out_append(cpt, 8, nl1, oc, 6));   // components, then bands: behind the same synchronise
+  return call_finish(c, a->memspace, oc, nout, d.err);
 }
 
 }  // namespace rrtmg

@@ -247,6 +247,19 @@ def test_recorded_isa_comparison_says_identical():
     assert not any(l.startswith(("DIFFERENT", "MISSING")) or "MISSING" in l for l in lines)
 
 
+def test_recorded_call_path_isa_comparison_says_identical():
+    """profiles/isa_compare_call_path.txt (tools/isa_compare.py --all, the parent commit's build against the build with the shared
+    host call path, csrc/rrtmg_call.h): every device function of the parent's code objects -- the kernels of both spectra, the
+    night kernels included -- disassembles to the same instruction stream, and this build has no function of its own."""
+    from tools.isa_compare import KERNELS
+    night = tuple("rrtmg::sw_%s_night_kernel(" % n for n in ("prep_fused", "cloud", "tile_lists", "kiss_mask", "fluxheat", "components", "bandflux"))
+    lines = [l for l in open(os.path.join(ROOT, "profiles", "isa_compare_call_path.txt")).read().splitlines() if l and not l.startswith("#")]
+    for k in KERNELS + night:
+        assert any(k in l for l in lines), k
+    for l in lines:
+        assert l.startswith("identical "), l
+
+
 def test_item_order_is_asserted_at_init():
     """The flush-on-change walk needs band-contiguous items: build_sw_tab / build_lw_tab check it and fail init otherwise."""
     for f in ("rrtmg_sw_host.h", "rrtmg_lw_host.h"):
