@@ -15,7 +15,8 @@ struct CallSite { rrtmg_ctx *ctx; int which; hipStream_t s; };
 // ---- entry gate ---------------------------------------------------------------------------------------------------------------
 inline bool spectrum_ready(const rrtmg_ctx *ctx, int which) { return which == 0 ? ctx->sw_ready : ctx->lw_ready; }
 // The call runs as *_sorted_call (rrtmg_sort.h): opt-in, device pointers, clouds, at least two tiles, kissvec or no McICA, and not
-// the inner call itself.  excluded: what the spectrum never sorts (outputs that would need a scatter, inputs a gather, of their own)
+// the inner call itself.  excluded: what the spectrum never sorts (outputs that would need a scatter, inputs a gather, of their own;
+// in the shortwave a second positional input besides the twister's stream: amplitudes indsolvar != 1, rescaled once per column)
 template <class Args>
 inline bool call_is_sorted(const rrtmg_ctx *ctx, int which, const Args *a, bool excluded) {
   return !excluded && spectrum_ready(ctx, which) && a && ctx->sort_columns && !ctx->sorting && a->memspace == 1 && a->icld != 0 && a->cldfr && a->ncol >= 128 && a->nlay > 0 && a->nlay <= 256 && !(a->mcica && a->irng != 0);

@@ -7,7 +7,9 @@
 // that no tile holds both kinds; the outputs are scattered back through the map.  Columns are independent in every routine
 // (rrtmg_sw_rad.f90:616, rrtmg_lw_rad.nomcica.f90:453); the kissvec sub-column generator seeds per column from the column's own
 // pressures, so the masks are the same wherever a column sits (the Mersenne twister's ONE stream is positional: such calls are
-// not sorted).  Why it is not the default: a cloud-free column then runs in the clear-sky variant, whose shortwave differs from
+// not sorted; nor are shortwave calls whose facular / sunspot amplitudes differ from 1: the host rescales them once per column in
+// the caller's order -- sw_scalar_setup -- so their multipliers are positional too, and the inner call on the padded copy must
+// never rescale the caller's IN/OUT array).  Why it is not the default: a cloud-free column then runs in the clear-sky variant, whose shortwave differs from
 // the cloudy variant's clear-sky stream by ~1e-12 W m^-2 (docs/EXPERIMENTS.md C) -- the default keeps a column's variant a function
 // of its tile, so that tile-aligned shards reproduce the whole grid bit for bit.
 //

@@ -521,9 +521,13 @@ static int sw_sorted_call(rrtmg_ctx *ctx, const rrtmg_sw_args *a) {
 // set, levels 0 or 1), or nullptr; sp: the surface albedo by band (at least one member set), or nullptr; all nullptr: the
 // plain call.  A call with components or bands is never sorted: its outputs would need a scatter of their own; nor is one with
 // a surface struct: its rows would need a gather of their own; nor is a call with the night-column skip on: the sort would move
-// night columns out of their tiles.
+// night columns out of their tiles; nor is a call whose facular/sunspot amplitudes `indsolvar` differ from 1: the host rescales
+// them once per column IN THE CALLER'S ORDER (sw_scalar_setup), so the multipliers are positional like the Mersenne twister's
+// stream, and the inner call on the padded copy would hand each column another column's multipliers and rescale the caller's
+// IN/OUT array once per padded slot.
+static bool sw_amplitudes_differ_from_one(const rrtmg_sw_args *a) { return a && a->indsolvar && (a->indsolvar[0] != 1.0 || a->indsolvar[1] != 1.0); }
 int sw_fluxes_impl(rrtmg_ctx *ctx, const rrtmg_sw_args *a, const rrtmg_sw_surface *sp, const rrtmg_sw_components *cp, const rrtmg_sw_band_fluxes *bp) {
-  if (call_is_sorted(ctx, 0, a, cp || bp || sp || ctx->sw_night_skip)) return sw_sorted_call(ctx, a);
+  if (call_is_sorted(ctx, 0, a, cp || bp || sp || ctx->sw_night_skip || sw_amplitudes_differ_from_one(a))) return sw_sorted_call(ctx, a);
   int rc = call_begin(ctx, 0, a);
   if (rc) return rc;
   const CallSite c{ctx, 0, call_stream(ctx, 0, a->memspace)}; hipStream_t s = c.s;
@@ -543,7 +547,8 @@ int sw_fluxes_impl(rrtmg_ctx *ctx, const rrtmg_sw_args *a, const rrtmg_sw_surfac
   {
     const long omg = ctx->sw_ts.off("sw/sol/mgavgcyc"), osb = ctx->sw_ts.off("sw/sol/sbavgcyc");
     rc = sw_scalar_setup(d, N, a->isolvar, a->adjes, a->dyofyr, a->scon, a->solcycfrac, a->bndsolvar, a->indsolvar,
-                         omg >= 0 ? ctx->sw_ts.flat.data() + omg : nullptr, osb >= 0 ? ctx->sw_ts.flat.data() + osb : nullptr, svar_col, err);
+                         omg >= 0 ? ctx->sw_ts.flat.data() + omg : nullptr, osb >= 0 ? ctx->sw_ts.flat.data() + osb : nullptr, svar_col, err,
+                         a->shard_col0, a->shard_ncol);
   }
   if (rc) return ctx->fail(rc, "%s", err.c_str());
   if (d.icld >= 1 && d.inflag == 1 && d.mcica) return ctx->fail(RRTMG_ERR_INFLAG1_MCICA, "shortwave: %s", status_message(RRTMG_ERR_INFLAG1_MCICA));   // rrtmg_sw_cldprmc.f90:166

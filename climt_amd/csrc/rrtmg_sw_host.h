@@ -126,10 +126,15 @@ inline double sw_earth_sun(int idn, double pi) {
 // towards the solar-cycle weight, and the caller's array comes back changed.  That is reproduced: `svar_col`
 // receives per-column (svar_f, svar_s, svar_i) -- [3][ncol] -- whenever the multipliers differ between columns
 // (it stays empty otherwise and the scalars in `d` apply), and `indsolvar` is updated as the reference leaves it.
+// The multipliers are therefore POSITIONAL, like the Mersenne twister's stream: shard_col0 / shard_ncol (rrtmg_sw_args; the default 0, 0 =
+// not sharded) place the call's columns in the grid.  A shard performs shard_col0 rescale steps before its first column, fills
+// the multipliers of its own columns from there, and goes on to shard_ncol steps in all: its columns get the whole grid's
+// multipliers, and every shard leaves `indsolvar` as the call on the whole grid does.  Scalar work, O(shard_ncol), and only
+// where the amplitudes differ from 1.
 // mgavgcyc / sbavgcyc: the 132-entry NRLSSI2 mean-cycle index tables (isolvar = 1).
 inline int sw_scalar_setup(SwDev &d, int ncol, int isolvar, double adjes, int dyofyr, double scon, double solcycfrac,
                            const double *bndsolvar, double *indsolvar, const double *mgavgcyc, const double *sbavgcyc,
-                           std::vector<double> &svar_col, std::string &err) {
+                           std::vector<double> &svar_col, std::string &err, int shard_col0 = 0, int shard_ncol = 0) {
   const double rrsw_scon = (double)1.36822e+03f;   // parrrsw.f90:115 -- a default-real (single precision) literal
   const double Iint = 1360.37, Fint = 0.996047, Sint = -0.511590;
   const double Foffset = 0.14959542, Soffset = 0.00066696, svar_f_avg = 0.1568113, svar_s_avg = 909.21910;
@@ -177,8 +182,8 @@ inline int sw_scalar_setup(SwDev &d, int ncol, int isolvar, double adjes, int dy
   const bool varies = (i1 != 1.0 || i2 != 1.0) && solcycfrac >= 0.0 && solcycfrac <= 1.0;
   const bool per_column = varies && (isolvar == 1 || (isolvar == 2 && scon == 0.0));
   if (per_column) svar_col.assign((size_t)3 * ncol, 1.0);
-  for (int k = 0; k < (varies ? ncol : 1); ++k) {
-    if (i1 != 1.0 || i2 != 1.0) {   // rrtmg_sw_rad.nomcica.f90:1199-1215, once per column
+  auto rescale = [&]() {   // rrtmg_sw_rad.nomcica.f90:1199-1215, once per column of the grid
+    if (i1 != 1.0 || i2 != 1.0) {
       if (solcycfrac >= 0.0 && solcycfrac < 0.0229) {
         const double wgt = (solcycfrac + 1.0 - 0.3817) / (1.0229 - 0.3817);
         i1 = i1 + wgt * (1.0 - i1); i2 = i2 + wgt * (1.0 - i2);
@@ -192,11 +197,18 @@ inline int sw_scalar_setup(SwDev &d, int ncol, int isolvar, double adjes, int dy
         i1 = i1 + wgt * (1.0 - i1); i2 = i2 + wgt * (1.0 - i2);
       }
     }
+  };
+  // the columns of the grid in front of this call's and behind them (a shard; none otherwise)
+  const int before = (varies && shard_ncol != 0) ? shard_col0 : 0, behind = (varies && shard_ncol != 0) ? shard_ncol - shard_col0 - ncol : 0;
+  for (int k = 0; k < before; ++k) rescale();
+  for (int k = 0; k < (varies ? ncol : 1); ++k) {
+    rescale();
     double f, s, i;
     multipliers(i1, i2, f, s, i);
     if (per_column) { svar_col[k] = f; svar_col[(size_t)ncol + k] = s; svar_col[(size_t)2 * ncol + k] = i; }
     if (k == 0) { d.svar_f = f; d.svar_s = s; d.svar_i = i; }
   }
+  for (int k = 0; k < behind; ++k) rescale();
   if (indsolvar) { indsolvar[0] = i1; indsolvar[1] = i2; }
 
   if (scon == 0.0) {

@@ -25,7 +25,12 @@ itself imports no torch.
 
 Sharded == unsharded, bit for bit, for ANY number of columns and ranks: kissvec sub-columns are seeded per column; for the
 Mersenne twister, whose reference stream is ONE sequence over (sub-column, column, layer), every rank passes its block's
-position (shard_col0, shard_ncol) and the generator starts at the rank's own draws (jump-ahead, csrc/rrtmg_mt_device.hip); and
+position (shard_col0, shard_ncol) and the generator starts at the rank's own draws (jump-ahead, csrc/rrtmg_mt_device.hip); the
+shortwave's facular / sunspot amplitudes `indsolvar`, which the reference rescales in place once per column of the call
+(rrtmg_sw_rad.nomcica.f90:1199-1215), are placed by the same two fields: a rank performs the rescale steps of the columns in
+front of its block before its first column, and those behind it afterwards, so that its columns get the whole grid's
+solar-variability multipliers and every rank's `indsolvar` comes back as the single-process call leaves it -- the next step
+starts equal on all ranks (a rank WITHOUT columns makes no call: its array is not advanced); and
 block boundaries are multiples of the 64-column tile (column_block(align=64)), so that every column runs in the same tile --
 and therefore in the same solve-kernel variant (clear-sky / cloudy tile) -- as in the unsharded call.  (A boundary inside a
 tile could move a column to the other variant, which changes the shortwave by round-off.)
@@ -407,9 +412,12 @@ class ShardedRadiation:
         local.pop("lat", None)
         local.update(shard_col0=self.lo, shard_ncol=self.ncol_total)
         if self.device:
-            self._keep = {k: self._hip.DeviceArray.from_host(v) for k, v in local.items() if isinstance(v, np.ndarray)}
+            # (bndsolvar / indsolvar -- no column axis -- are HOST arrays of the library under either memspace: the host-side scalar
+            #  set-up reads them, and rescales indsolvar in place, the caller's own array)
+            on_device = lambda k, v: isinstance(v, np.ndarray) and COLUMN_AXIS.get(k, 0) is not None
+            self._keep = {k: self._hip.DeviceArray.from_host(v) for k, v in local.items() if on_device(k, v)}
             self.inp = {k: v.ptr for k, v in self._keep.items()}
-            self.inp.update({k: v for k, v in local.items() if not isinstance(v, np.ndarray)})
+            self.inp.update({k: v for k, v in local.items() if not on_device(k, v)})
             self.inp.update(ncol=self.ncol, nlay=self.nlay)
         else:
             self.inp = local

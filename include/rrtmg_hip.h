@@ -119,7 +119,8 @@ int rrtmg_hip_set_deferred(rrtmg_ctx *ctx, int on);
  * tile now runs in the clear-sky variant, whose shortwave differs from the cloudy variant's clear-sky stream by ~1e-12 W m^-2 --
  * which is why this is not the default (tile-aligned shards == the whole grid bit for bit only when a column's variant is a
  * function of its tile).  Calls with the Mersenne twister (one positional stream) and host-pointer calls are not sorted,
- * nor are calls that request flux components or band fluxes (rrtmg_hip_sw_fluxes_components, rrtmg_hip_*_fluxes_bands). */
+ * nor are shortwave calls whose facular / sunspot amplitudes indsolvar differ from 1 (rescaled once per column in the caller's
+ * order: positional too; the caller's array comes back as without the sort), nor are calls that request flux components or band fluxes (rrtmg_hip_sw_fluxes_components, rrtmg_hip_*_fluxes_bands). */
 int rrtmg_hip_set_column_sort(rrtmg_ctx *ctx, int on);
 /* OPT-IN night-column skip of the shortwave (off by default; with it off nothing changes, and the reference-compatible symbols
  * on the default context never have it).  The reference's driver does not skip night columns: it clamps coszen to 1e-10
@@ -237,9 +238,10 @@ typedef struct rrtmg_sw_args {
   int32_t irng;         /* McICA RNG: 0 kissvec, 1 Mersenne twister */
   int32_t permuteseed;  /* McICA changeSeed */
   /* Column shard of a larger grid (multi-GPU): this call's columns are columns shard_col0 .. shard_col0+ncol-1 of a grid of
-   * shard_ncol columns; 0, 0 = not sharded.  Only the Mersenne twister needs it: the reference draws ONE stream in
-   * (sub-column, column, layer) order (mcica_subcol_gen_sw.f90:360-367), so a shard skips the other shards' draws and
-   * reproduces the unsharded masks bit for bit.  kissvec seeds are per column and ignore it. */
+   * shard_ncol columns; 0, 0 = not sharded.  Two inputs are positional and need it: the Mersenne twister -- the reference
+   * draws ONE stream in (sub-column, column, layer) order (mcica_subcol_gen_sw.f90:360-367), so a shard skips the other shards'
+   * draws and reproduces the unsharded masks bit for bit (kissvec seeds are per column and ignore it) -- and, in the shortwave,
+   * facular / sunspot amplitudes that differ from 1 (see indsolvar). */
   int32_t shard_col0, shard_ncol;
   /* sizeof(rrtmg_sw_args) of the header the CALLER was compiled against: REQUIRED.  Any value that is not the library's own
    * sizeof -- 0 included -- is refused with RRTMG_ERR_ARG: a caller built against another header never has fields dropped
@@ -248,8 +250,17 @@ typedef struct rrtmg_sw_args {
   int32_t struct_size;
   double adjes, scon, solcycfrac;
   const double *bndsolvar;   /* [14] (host) or NULL -> ones */
-  double *indsolvar;         /* [2]  (host) or NULL -> ones; IN/OUT: amplitudes != 1 are rescaled in place once per
-                              * column, as the reference does (rrtmg_sw_rad.nomcica.f90:1199-1215) */
+  double *indsolvar;         /* [2]  (host, under either memspace) or NULL -> ones; IN/OUT: amplitudes != 1 are rescaled in
+                              * place once per column, as the reference does (rrtmg_sw_rad.nomcica.f90:1199-1215: inatm_sw sits
+                              * inside its column loop).  Column k of the call sees amplitudes rescaled k + 1 times -- night
+                              * columns count, whether or not the night-column skip is on -- so with isolvar 1, or isolvar 2 and
+                              * scon 0, the solar-variability multipliers of a column depend on its POSITION in the call.  On return:
+                              *  - whole grid (shard_ncol 0): rescaled ncol times;
+                              *  - shard (shard_col0, shard_ncol): the call performs the shard_col0 steps of the columns in front
+                              *    of it first, so its columns get the multipliers they have in the whole grid, and the steps of
+                              *    the columns behind it afterwards: rescaled shard_ncol times, what the call on the whole grid
+                              *    leaves, on every shard (each shard starts from the amplitudes the whole grid would start from);
+                              *  - column sort enabled: as without it -- a call whose amplitudes differ from 1 is not sorted. */
   /* state */
   const double *play, *plev, *tlay, *tlev, *tsfc;
   const double *h2ovmr, *o3vmr, *co2vmr, *ch4vmr, *n2ovmr, *o2vmr;

@@ -106,7 +106,8 @@ class RefSW(_RefBase):
     def fluxes(self, inp, mcica=False, subcol=None):
         """inp: dict following the binder's argument names (see module docstring).
         mcica=True: runs mcica_subcol_sw_wrapper first (permuteseed, irng from inp) unless
-        `subcol` (dict of pre-generated sub-column arrays) is given.  Returns dict of outputs."""
+        `subcol` (dict of pre-generated sub-column arrays) is given.  Returns dict of outputs, and under "indsolvar" the
+        facular / sunspot amplitudes as the reference left them (it rescales them in place, once per column)."""
         if not self.inited:
             self.init()
         nlay, ncol = inp["play"].shape
@@ -149,6 +150,7 @@ class RefSW(_RefBase):
                 _d(s["cldfmcl"]), _d(s["taucmcl"]), _d(s["ssacmcl"]), _d(s["asmcmcl"]), _d(s["fsfcmcl"]),
                 _d(s["ciwpmcl"]), _d(s["clwpmcl"]), _d(reice), _d(reliq)] + tail))
             out["subcol"] = s
+        out["indsolvar"] = ind      # IN/OUT in the reference: the amplitudes as the call leaves them (the caller's array is not touched)
         return out
 
     def subcol(self, inp):

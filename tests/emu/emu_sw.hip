@@ -66,7 +66,8 @@ extern "C" int emu_sw_fluxes(const rrtmg_sw_args *a, const rrtmg_sw_surface *sf,
   std::vector<double> svar_col;
   const long omg = ts.off("sw/sol/mgavgcyc"), osb = ts.off("sw/sol/sbavgcyc");
   int rc = sw_scalar_setup(d, a->ncol, a->isolvar, a->adjes, a->dyofyr, a->scon, a->solcycfrac, a->bndsolvar, a->indsolvar,
-                           omg >= 0 ? ts.flat.data() + omg : nullptr, osb >= 0 ? ts.flat.data() + osb : nullptr, svar_col, err);
+                           omg >= 0 ? ts.flat.data() + omg : nullptr, osb >= 0 ? ts.flat.data() + osb : nullptr, svar_col, err,
+                           a->shard_col0, a->shard_ncol);
   if (!svar_col.empty()) d.svar_col = svar_col.data();
   if (rc) return fail(rc, err);
   d.play = a->play; d.plev = a->plev; d.tlay = a->tlay; d.h2o = a->h2ovmr; d.o3 = a->o3vmr; d.co2 = a->co2vmr;

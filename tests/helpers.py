@@ -356,14 +356,15 @@ def sw_shim(c, mcica, albdir, albdif, subcol=None, band=0):
     """Our driver of the reference's procedures on the inputs `c` with these per-band albedos ([14][ncol]; band_rule(c) for the
     reference driver's own), over the full band range (band 0) or over band 1..14 alone -> (the 14 rows of the reference's
     accumulators [14][nlay+1][ncol], in sw_shim.f90's order; swhr and swhrc [2][nlay][ncol]).  mcica: on `subcol`
-    (RefSW.subcol)."""
+    (RefSW.subcol).  The facular / sunspot amplitudes c["indsolvar"] (default: ones) are rescaled by the reference on a copy;
+    c["solcycfrac"] defaults to 0."""
     from oracle.ref_driver import _cd, _d, _rd, _ri
     nlay, ncol = c["play"].shape
     g = lambda k: _cd(c[k])
     l2 = lambda k, v: _cd(c[k]) if k in c else np.full((nlay, ncol), v)
     d3 = lambda k, v: _cd(c[k]) if k in c else np.full((nlay, ncol, 14), v)
     aer = lambda k, v: _cd(c[k]) if k in c else np.full((14, nlay, ncol), v)
-    keep = [aer("tauaer", 0.0), aer("ssaaer", 1.0), aer("asmaer", 0.0), np.ones(16), np.ones(2), _cd(albdir), _cd(albdif)]
+    keep = [aer("tauaer", 0.0), aer("ssaaer", 1.0), aer("asmaer", 0.0), np.ones(16), _cd(c.get("indsolvar", np.ones(2))).copy(), _cd(albdir), _cd(albdif)]
     assert keep[5].shape == (14, ncol) and keep[6].shape == (14, ncol)
     rows, hr = np.zeros((14, nlay + 1, ncol)), np.zeros((2, nlay, ncol))
     head = [_ri(ncol), _ri(nlay), _ri(c["icld"]), _ri(c["iaer"]),
@@ -371,7 +372,7 @@ def sw_shim(c, mcica, albdir, albdif, subcol=None, band=0):
             _d(g("h2o")), _d(g("o3")), _d(g("co2")), _d(g("ch4")), _d(g("n2o")), _d(g("o2")),
             _d(keep[5]), _d(keep[6]), _d(g("coszen")),
             _rd(c["adjes"]), _ri(c["dyofyr"]), _rd(c["scon"]), _ri(c["isolvar"]), _ri(c["inflg"]), _ri(c["iceflg"]), _ri(c["liqflg"])]
-    tail = [_d(keep[0]), _d(keep[1]), _d(keep[2]), _d(keep[3]), _d(keep[4]), _rd(0.0), _ri(band), _d(rows), _d(hr)]
+    tail = [_d(keep[0]), _d(keep[1]), _d(keep[2]), _d(keep[3]), _d(keep[4]), _rd(c.get("solcycfrac", 0.0)), _ri(band), _d(rows), _d(hr)]
     lib = C.CDLL(SW_SHIM, mode=C.RTLD_LOCAL)
     if mcica:
         s = {k: _cd(v) for k, v in subcol.items()}

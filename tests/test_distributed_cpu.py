@@ -167,6 +167,9 @@ def test_column_blocks_cover_and_balance():
     assert [column_block(100, 3, r) for r in range(3)] == [(0, 64), (64, 100), (100, 100)]      # fewer tiles than ranks
 
 
+SOLVAR_CASE = "mcica_i2_s0"
+
+
 def _worker3(rank, world, port, q):
     """1000 columns (not a multiple of anything) over three ranks, one of the blocks ragged; 100 columns: a rank with nothing."""
     sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
@@ -189,6 +192,15 @@ def _worker3(rank, world, port, q):
                 b = sr.step(mcica=True)
             sr.finish()
             res[(ncol, mode)] = (sr.gathered_host(b), (sr.lo, sr.hi), sr.gather_ingress_bytes())
+    # solar variability (tests/solvar_cases.py): the facular / sunspot amplitudes are rescaled once per column of the GRID, so the
+    # multipliers are positional like the twister's stream -- 136 columns, blocks of 64 / 64 / 8, every rank's array afterwards
+    import solvar_cases as S
+    c, mcica = S.case_inputs(SOLVAR_CASE)
+    sr = ShardedRadiation(ctx, TorchComm(dist, rank, world), S.NCOL, S.NLAY, gather="all", device=False, unpack=True)
+    sr.set_inputs(c)
+    b = sr.step(mcica=mcica)
+    sr.finish()
+    res["solvar"] = (sr.gathered_host(b), (sr.lo, sr.hi), c["indsolvar"].copy())
     # first-execution insurance of the 8-GPU run (bench.py: comm_selftest): every mode on a small pattern, checked on every
     # rank -- here over gloo with three ranks -- and a communicator that misroutes one block is NAMED, per mode
     from climt_amd.distributed import comm_selftest
@@ -241,6 +253,17 @@ def test_three_ranks_any_column_count_is_bit_identical():
                 assert all(np.array_equal(got[k], full[k]) for k in full), (ncol, rank, mode)
                 width = max(hi - lo for lo, hi in blocks)
                 assert ingress == 2 * 8 * sum((12 + lev) * width for lev in (1, 1, 0, 1, 1, 0) * 2)      # two peers' blocks
+    # solar variability: gathered outputs == the unsharded emulation bit for bit, and every rank ends with the amplitudes the
+    # single-process call leaves (the next model step starts equal on all ranks)
+    import solvar_cases as S
+    c, mcica = S.case_inputs(SOLVAR_CASE)
+    full = dict(e.sw_fluxes(c, mcica=mcica)); full.update(e.lw_fluxes(c, mcica=mcica))
+    assert not np.array_equal(c["indsolvar"], S.amplitudes(c["isolvar"]))
+    for rank in range(3):
+        got, block, ind = res[rank]["solvar"]
+        assert block == S.SHARDS[rank]
+        assert all(np.array_equal(got[k], full[k]) for k in full), (rank, [k for k in full if not np.array_equal(got[k], full[k])])
+        assert np.array_equal(ind, c["indsolvar"]), (rank, ind, c["indsolvar"])
 
 
 def test_tcp_rendezvous_hands_out_rank0s_bytes():
