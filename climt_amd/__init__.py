@@ -17,10 +17,10 @@ from .berger import BergerSolarInsolation  # noqa: F401,E402
 from .device_state import DeviceAdamsBashforth, DeviceQuantity, DeviceState  # noqa: F401,E402
 from .initialization import get_default_state, get_grid  # noqa: F401,E402
 from .instellation import Instellation  # noqa: F401,E402
-from .rrtmg import RRTMGLongwave, RRTMGShortwave  # noqa: F401,E402
+from .rrtmg import RRTMGLongwave, RRTMGShortwave, radiation_step  # noqa: F401,E402
 from .slab_surface import SlabSurface  # noqa: F401,E402
 from .timestepping import AdamsBashforth  # noqa: F401,E402
 from .wrappers import UpdateFrequencyWrapper  # noqa: F401,E402
 
 __all__ = ["RRTMGLongwave", "RRTMGShortwave", "Instellation", "BergerSolarInsolation", "SlabSurface", "get_grid", "get_default_state", "UpdateFrequencyWrapper", "AdamsBashforth",
-           "Context", "RRTMGError", "DeviceState", "DeviceQuantity", "DeviceAdamsBashforth"]
+           "Context", "RRTMGError", "DeviceState", "DeviceQuantity", "DeviceAdamsBashforth", "radiation_step"]

@@ -123,6 +123,13 @@ class LwArgs(C.Structure):
                 + [(n, _f64) for n in _SCALES])
 
 
+class RadiationCall(C.Structure):
+    """mirrors `rrtmg_radiation_call` (include/rrtmg_hip.h), field for field"""
+    _fields_ = [("struct_size", C.c_int), ("sw", C.POINTER(SwArgs)), ("sw_surface", C.POINTER(SwSurface)),
+                ("sw_components", C.POINTER(SwComponents)), ("sw_bands", C.POINTER(SwBandFluxes)),
+                ("lw", C.POINTER(LwArgs)), ("lw_bands", C.POINTER(LwBandFluxes))]
+
+
 SLAB_IN = ("sw_down lw_down sw_up lw_up lh sh up_heat_soil heat_flux_sea_ice sea_water_dens surf_dens heat_cap_soil surf_therm_cap "
            "ocean_mix_thick soil_layer_thick ocean_heat_transport").split()
 
@@ -182,6 +189,9 @@ def load_library():
     if hasattr(lib, "rrtmg_hip_set_sw_night_skip"):      # (RRTMG_HIP_LIB may name a library that predates it, as for the entry above)
         lib.rrtmg_hip_set_sw_night_skip.argtypes = [_vp, C.c_int]
         lib.rrtmg_hip_sw_night_last.argtypes = [_vp, C.POINTER(C.c_int), C.POINTER(C.c_int)]
+    if hasattr(lib, "rrtmg_hip_radiation_fluxes"):       # (likewise)
+        lib.rrtmg_hip_radiation_fluxes.argtypes = [_vp, C.POINTER(RadiationCall)]
+        lib.rrtmg_hip_radiation_last.argtypes = [_vp, C.POINTER(C.c_int), C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]
     lib.rrtmg_hip_copy_blocks.argtypes = [_vp, C.c_int, _vp, C.c_long, C.c_long, _vp, _vp, _vp]
     lib.rrtmg_hip_mcica_mask.argtypes = [_vp] + [C.c_int] * 6 + [_vp] * 3
     _lib = lib
@@ -461,10 +471,24 @@ class Context:
         pointer with memspace=1) that the call fills as well (rrtmg_hip_sw_fluxes_components); the names left out are not
         computed.  `bands`: None, or a dict SW_BAND_FLUXES name -> output [14][nrow][ncol] in the same way
         (rrtmg_hip_sw_fluxes_bands); `band_levels`: "all" (nrow = nlay+1) or "boundaries" (nrow = 2: surface, top)."""
+        keep = []
+        a, sf, c, b, out = self._sw_structs(inp, mcica, out, memspace, components, bands, band_levels, surface, keep)
+        if sf is None and c is None and b is None:
+            self._ck(self.lib.rrtmg_hip_sw_fluxes(self.h, C.byref(a)))
+        elif sf is not None:
+            self._ck(self.lib.rrtmg_hip_sw_fluxes_surface(self.h, C.byref(a), C.byref(sf), None if c is None else C.byref(c), None if b is None else C.byref(b)))
+        elif b is not None:
+            self._ck(self.lib.rrtmg_hip_sw_fluxes_bands(self.h, C.byref(a), None if c is None else C.byref(c), C.byref(b)))
+        else:
+            self._ck(self.lib.rrtmg_hip_sw_fluxes_components(self.h, C.byref(a), C.byref(c)))
+        return out
+
+    def _sw_structs(self, inp, mcica, out, memspace, components, bands, band_levels, surface, keep):
+        """-> (rrtmg_sw_args, surface struct | None, components struct | None, band struct | None, out) of a shortwave call;
+        the arrays the structs point into stay alive in `keep` (and in `out`, `components`, `bands`)."""
         nlay, ncol = (inp["nlay"], inp["ncol"]) if memspace else inp["play"].shape
         a = SwArgs()
         a.struct_size = C.sizeof(SwArgs)
-        keep = []
         a.ncol, a.nlay, a.memspace, a.mcica = int(ncol), int(nlay), int(memspace), int(bool(mcica))
         a.icld, a.inflgsw, a.iceflgsw, a.liqflgsw, a.dyofyr = 1, 2, 1, 1, 1
         a.adjes, a.scon, a.solcycfrac = float(inp.get("adjes", 1.0)), float(inp.get("scon", 1367.0)), float(inp.get("solcycfrac", 0.0))
@@ -476,26 +500,14 @@ class Context:
             setattr(a, k, int(v) if isinstance(v, (int, np.integer)) else v.ctypes.data)
         if surface is None and (inp.get("albdir") is not None or inp.get("albdif") is not None):
             surface = {k: inp.get(k) for k in SW_SURFACE}
-        if components is None and bands is None and surface is None:
-            self._ck(self.lib.rrtmg_hip_sw_fluxes(self.h, C.byref(a)))
-            return out
         b = None if bands is None else _band_struct(SwBandFluxes, SW_BAND_FLUXES, SW_NBAND, bands, band_levels, nlay, ncol)
+        sf = None
         if surface is not None:
             if not hasattr(self.lib, "rrtmg_hip_sw_fluxes_surface"):
                 raise RRTMGError(4, "this librrtmg_hip.so has no rrtmg_hip_sw_fluxes_surface (surface albedo by band)")
             sf = _surface_struct(surface, ncol, keep)
-            c = None if components is None else self._components_struct(components, nlay, ncol)
-            self._ck(self.lib.rrtmg_hip_sw_fluxes_surface(self.h, C.byref(a), C.byref(sf), None if c is None else C.byref(c), None if b is None else C.byref(b)))
-            return out
-        if components is None:
-            self._ck(self.lib.rrtmg_hip_sw_fluxes_bands(self.h, C.byref(a), None, C.byref(b)))
-            return out
-        c = self._components_struct(components, nlay, ncol)
-        if b is not None:
-            self._ck(self.lib.rrtmg_hip_sw_fluxes_bands(self.h, C.byref(a), C.byref(c), C.byref(b)))
-            return out
-        self._ck(self.lib.rrtmg_hip_sw_fluxes_components(self.h, C.byref(a), C.byref(c)))
-        return out
+        c = None if components is None else self._components_struct(components, nlay, ncol)
+        return a, sf, c, b, out
 
     @staticmethod
     def _components_struct(components, nlay, ncol):
@@ -517,10 +529,19 @@ class Context:
         """`bands`: None, or a dict LW_BAND_FLUXES name -> output (a C-contiguous float64 [16][nrow][ncol] array, or a device
         pointer with memspace=1) that the call fills as well (rrtmg_hip_lw_fluxes_bands); `band_levels`: "all" (nrow =
         nlay+1) or "boundaries" (nrow = 2: surface, top)."""
+        keep = []
+        a, b, out = self._lw_structs(inp, mcica, out, memspace, bands, band_levels, keep)
+        if b is None:
+            self._ck(self.lib.rrtmg_hip_lw_fluxes(self.h, C.byref(a)))
+        else:
+            self._ck(self.lib.rrtmg_hip_lw_fluxes_bands(self.h, C.byref(a), C.byref(b)))
+        return out
+
+    def _lw_structs(self, inp, mcica, out, memspace, bands, band_levels, keep):
+        """-> (rrtmg_lw_args, band struct | None, out) of a longwave call (see _sw_structs)."""
         nlay, ncol = (inp["nlay"], inp["ncol"]) if memspace else inp["play"].shape
         a = LwArgs()
         a.struct_size = C.sizeof(LwArgs)
-        keep = []
         a.ncol, a.nlay, a.memspace, a.mcica = int(ncol), int(nlay), int(memspace), int(bool(mcica))
         a.icld, a.inflglw, a.iceflglw, a.liqflglw = 1, 2, 1, 1
         self._fill(a, inp, _LW_FIELDS, _LW_FLAGS, keep)
@@ -532,12 +553,50 @@ class Context:
         for k in out:
             v = out[k]
             setattr(a, k, int(v) if isinstance(v, (int, np.integer)) else v.ctypes.data)
-        if bands is None:
-            self._ck(self.lib.rrtmg_hip_lw_fluxes(self.h, C.byref(a)))
-            return out
-        b = _band_struct(LwBandFluxes, LW_BAND_FLUXES, LW_NBAND, bands, band_levels, nlay, ncol)
-        self._ck(self.lib.rrtmg_hip_lw_fluxes_bands(self.h, C.byref(a), C.byref(b)))
-        return out
+        b = None if bands is None else _band_struct(LwBandFluxes, LW_BAND_FLUXES, LW_NBAND, bands, band_levels, nlay, ncol)
+        return a, b, out
+
+    @_locked
+    def radiation_fluxes(self, sw, lw):
+        """Both spectra of one host state in one library call (rrtmg_hip_radiation_fluxes): `sw` and `lw` are the keyword sets of
+        sw_fluxes and lw_fluxes as dicts -- `inp`, and optionally `mcica`, `out`, `bands`, `band_levels`, and for the shortwave
+        `components`, `surface`.  Host arrays only.  -> (sw out, lw out), bit for bit what sw_fluxes(**sw) followed by
+        lw_fluxes(**lw) give.  An input that both `inp` hold as the same array (with the same unit factors) is uploaded once,
+        and the two spectra overlap on the GPU; radiation_last() says what was shared."""
+        if not hasattr(self.lib, "rrtmg_hip_radiation_fluxes"):
+            raise RRTMGError(4, "this librrtmg_hip.so has no rrtmg_hip_radiation_fluxes (joint shortwave + longwave call)")
+        for name, kw, allowed in (("sw", sw, ("inp", "mcica", "out", "components", "bands", "band_levels", "surface")),
+                                  ("lw", lw, ("inp", "mcica", "out", "bands", "band_levels"))):
+            unknown = [k for k in kw if k not in allowed]
+            if unknown or "inp" not in kw:
+                raise TypeError("radiation_fluxes: %s takes 'inp' and optionally %s, not %s" % (name, ", ".join(allowed[1:]), ", ".join(map(repr, unknown)) or "nothing"))
+        keep = []   # (every array the structs point into, until the call has returned)
+        a, sf, c, b, sw_out = self._sw_structs(sw["inp"], sw.get("mcica", False), sw.get("out"), 0, sw.get("components"), sw.get("bands"),
+                                               sw.get("band_levels", "all"), sw.get("surface"), keep)
+        la, lb, lw_out = self._lw_structs(lw["inp"], lw.get("mcica", False), lw.get("out"), 0, lw.get("bands"), lw.get("band_levels", "all"), keep)
+        call = RadiationCall()
+        call.struct_size = C.sizeof(RadiationCall)
+        call.sw, call.lw = C.pointer(a), C.pointer(la)
+        if sf is not None:
+            call.sw_surface = C.pointer(sf)
+        if c is not None:
+            call.sw_components = C.pointer(c)
+        if b is not None:
+            call.sw_bands = C.pointer(b)
+        if lb is not None:
+            call.lw_bands = C.pointer(lb)
+        self._ck(self.lib.rrtmg_hip_radiation_fluxes(self.h, C.byref(call)))
+        del keep
+        return sw_out, lw_out
+
+    @_locked
+    def radiation_last(self):
+        """-> (arrays shared, bytes uploaded, bytes shared) of the last radiation_fluxes call on this context
+        (rrtmg_hip_radiation_last): inputs taken from what the call had already brought to the device, the host-to-device bytes it
+        copied, and the bytes it did not copy because of that."""
+        n, up, sh = C.c_int(0), C.c_longlong(0), C.c_longlong(0)
+        self._ck(self.lib.rrtmg_hip_radiation_last(self.h, C.byref(n), C.byref(up), C.byref(sh)))
+        return n.value, up.value, sh.value
 
     @_locked
     def mcica_mask(self, which, play, cldfrac, icld, permuteseed, irng):

@@ -58,6 +58,10 @@ int ctx_prepare_device(rrtmg_ctx *ctx) {
     RRTMG_HIP_CHECK(ctx, hipMalloc((void **)&ctx->ncloudy_dev, 4 * sizeof(int)));
     RRTMG_HIP_CHECK(ctx, hipMemset(ctx->ncloudy_dev, 0, 4 * sizeof(int)));
   }
+  if (!ctx->flag_host) {
+    RRTMG_HIP_CHECK(ctx, hipHostMalloc((void **)&ctx->flag_host, 2 * sizeof(int), hipHostMallocDefault));
+    ctx->flag_host[0] = ctx->flag_host[1] = 0;
+  }
   if (!ctx->err_dev) {
     RRTMG_HIP_CHECK(ctx, hipMalloc((void **)&ctx->err_dev, 64));
     RRTMG_HIP_CHECK(ctx, hipMemset(ctx->err_dev, 0, 64));
@@ -67,37 +71,49 @@ int ctx_prepare_device(rrtmg_ctx *ctx) {
       if (!ctx->kiss_ev[w][k]) RRTMG_HIP_CHECK(ctx, hipEventCreateWithFlags(&ctx->kiss_ev[w][k], hipEventDisableTiming));
   for (int w = 0; w < 2; ++w)
     if (!ctx->sync_ev[w]) RRTMG_HIP_CHECK(ctx, hipEventCreateWithFlags(&ctx->sync_ev[w], hipEventDisableTiming));
+  for (int w = 0; w < 2; ++w)
+    if (!ctx->share_ev[w]) RRTMG_HIP_CHECK(ctx, hipEventCreateWithFlags(&ctx->share_ev[w], hipEventDisableTiming));
   return RRTMG_OK;
 }
 
-int copy_out(rrtmg_ctx *ctx, hipStream_t s, const OutCopy *o, int count, int *herr_dev, int *herr_host) {
+int copy_out_enqueue(rrtmg_ctx *ctx, hipStream_t s, const OutCopy *o, int count, int *herr_dev, PendingOut &po, int slot) {
   // A destination that is page-locked memory the runtime knows (hipHostMalloc / hipHostRegister: the components' output pool
   // hands such arrays out) takes its copy directly; the others go through the staging buffer.
-  constexpr int kMaxOut = 24;   // shortwave: 6 outputs + 8 components + 6 band arrays
   if (count > kMaxOut) return ctx->fail(RRTMG_ERR_ARG, "copy_out: %d output arrays (at most %d)", count, kMaxOut);
-  bool direct[kMaxOut];
-  size_t total = 0;
+  po.count = count; po.total = 0; po.herr = 0; po.slot = slot; po.has_flag = herr_dev != nullptr; po.enqueued = false;
   for (int i = 0; i < count; ++i) {
     hipPointerAttribute_t at;
-    direct[i] = hipPointerGetAttributes(&at, o[i].host) == hipSuccess && at.type == hipMemoryTypeHost;
-    if (!direct[i]) total += o[i].n * sizeof(double);
+    po.oc[i] = o[i];
+    po.direct[i] = hipPointerGetAttributes(&at, o[i].host) == hipSuccess && at.type == hipMemoryTypeHost;
+    if (!po.direct[i]) po.total += o[i].n * sizeof(double);
   }
   (void)hipGetLastError();   // (an unknown pointer is an error code of the query, not of this call)
-  if (total > ctx->pinned_cap) {
-    if (ctx->pinned) (void)hipHostFree(ctx->pinned);
-    ctx->pinned = nullptr; ctx->pinned_cap = 0;
-    RRTMG_HIP_CHECK(ctx, hipHostMalloc(&ctx->pinned, total, hipHostMallocDefault));
-    ctx->pinned_cap = total;
+  if (po.total > ctx->pinned_cap[slot]) {
+    if (ctx->pinned[slot]) (void)hipHostFree(ctx->pinned[slot]);
+    ctx->pinned[slot] = nullptr; ctx->pinned_cap[slot] = 0;
+    RRTMG_HIP_CHECK(ctx, hipHostMalloc(&ctx->pinned[slot], po.total, hipHostMallocDefault));
+    ctx->pinned_cap[slot] = po.total;
   }
-  char *p = (char *)ctx->pinned;
-  if (herr_dev) RRTMG_HIP_CHECK(ctx, hipMemcpyAsync(herr_host, herr_dev, sizeof(int), hipMemcpyDeviceToHost, s));
+  char *p = (char *)ctx->pinned[slot];
+  if (herr_dev) RRTMG_HIP_CHECK(ctx, hipMemcpyAsync(&ctx->flag_host[slot], herr_dev, sizeof(int), hipMemcpyDeviceToHost, s));
   size_t off = 0;
   for (int i = 0; i < count; ++i) {
-    RRTMG_HIP_CHECK(ctx, hipMemcpyAsync(direct[i] ? (char *)o[i].host : p + off, o[i].dev, o[i].n * sizeof(double), hipMemcpyDeviceToHost, s));
-    if (!direct[i]) off += o[i].n * sizeof(double);
+    RRTMG_HIP_CHECK(ctx, hipMemcpyAsync(po.direct[i] ? (char *)o[i].host : p + off, o[i].dev, o[i].n * sizeof(double), hipMemcpyDeviceToHost, s));
+    if (!po.direct[i]) off += o[i].n * sizeof(double);
   }
-  RRTMG_HIP_CHECK(ctx, hipStreamSynchronize(s));
-  if (total == 0) return RRTMG_OK;
+  po.enqueued = true;
+  return RRTMG_OK;
+}
+
+void copy_out_complete(rrtmg_ctx *ctx, PendingOut &po) {
+  po.enqueued = false;
+  if (po.has_flag) po.herr = ctx->flag_host[po.slot];
+  const size_t total = po.total;
+  const int count = po.count;
+  const OutCopy *o = po.oc;
+  const bool *direct = po.direct;
+  const char *p = (const char *)ctx->pinned[po.slot];
+  if (total == 0) return;
   // pinned staging -> the caller's arrays, in slices on a few host threads (first touch of fresh pages dominates)
   unsigned nt = std::thread::hardware_concurrency();
   nt = nt == 0 ? 1 : (nt > 8 ? 8 : nt);
@@ -116,6 +132,14 @@ int copy_out(rrtmg_ctx *ctx, hipStream_t s, const OutCopy *o, int count, int *he
   for (unsigned t = 1; t < nt; ++t) th.emplace_back(work, t);
   work(0);
   for (auto &x : th) x.join();
+}
+
+int copy_out(rrtmg_ctx *ctx, hipStream_t s, const OutCopy *o, int count, int *herr_dev, int *herr_host) {
+  PendingOut po;
+  if (const int rc = copy_out_enqueue(ctx, s, o, count, herr_dev, po, 0)) return rc;
+  RRTMG_HIP_CHECK(ctx, hipStreamSynchronize(s));
+  copy_out_complete(ctx, po);
+  if (herr_dev) *herr_host = po.herr;
   return RRTMG_OK;
 }
 
@@ -243,6 +267,7 @@ bool HostInputs::upload(const Entry &e) {
   if (hipMemcpyAsync(dp, e.host, e.n * sizeof(double), hipMemcpyHostToDevice, s_) != hipSuccess) { ctx_->fail(RRTMG_ERR_HIP, "H2D copy of '%s' failed", e.name); return false; }
   if (e.mul != 0.0) launch_scale(s_, dp, e.n, e.mul, e.div);
   *e.slot = dp;
+  resolved(e, dp, e.n * sizeof(double));
   return true;
 }
 
@@ -260,15 +285,23 @@ bool HostInputs::fill(const Entry &e, double host_value) {
     b.uniform = true; b.uni_value = value; b.uni_n = e.n;
   }
   *e.slot = dp;
+  resolved(e, dp, 0);
   return true;
 }
 
 bool HostInputs::finish() {
   if (!ok_) return false;
+  // a joint call's table first: what it already holds, or what an earlier input of this batch is about to bring, is taken below
+  bool brought = false;
+  if (share_)
+    for (Entry &e : entries_) {
+      e.taken = share_->acquire(share_key(e.host, e.n, e.mul, e.div, (int)e.policy), owner_, &e.share) != ShareTable::Found::New;
+      if (!e.taken) brought = true;
+    }
   std::unique_ptr<ScanJob[]> jobs(new ScanJob[entries_.size() + 1]);
   int njobs = 0;
   for (Entry &e : entries_) {
-    if (e.n < kScanMin) continue;
+    if (e.taken || e.n < kScanMin) continue;
     const uint64_t *q = (const uint64_t *)e.host;
     const uint64_t w0 = q[0];
     uint64_t acc = 0;
@@ -282,17 +315,30 @@ bool HostInputs::finish() {
   HostPool::Batch batch;
   if (njobs) HostPool::get().start(jobs.get(), njobs, batch);
   for (const Entry &e : entries_)
-    if (e.job < 0 && !upload(e)) ok_ = false;
+    if (!e.taken && e.job < 0 && !upload(e)) ok_ = false;
   if (njobs) HostPool::get().wait(batch);
   for (const Entry &e : entries_) {
     if (e.job < 0) continue;
     const ScanJob &j = jobs[e.job];
     if (j.differs.load()) { if (!upload(e)) ok_ = false; continue; }
-    if (e.policy == InPolicy::ZeroAbsent && j.first == 0) { *e.slot = nullptr; continue; }   // all +0.0: the "array absent" path adds the same
+    if (e.policy == InPolicy::ZeroAbsent && j.first == 0) { *e.slot = nullptr; resolved(e, nullptr, 0); continue; }   // all +0.0: the "array absent" path adds the same
     double v;
     memcpy(&v, &j.first, sizeof v);
     if (!fill(e, v)) ok_ = false;
   }
+  if (!share_) return ok_;
+  // One event behind the last write of this batch into a buffer the table names; a batch that takes what the OTHER spectrum's
+  // stream wrote waits for that spectrum's event on its own stream (what its own stream wrote is ordered already).
+  if (brought && hipEventRecord(ctx_->share_ev[owner_], s_) != hipSuccess) { ctx_->fail(RRTMG_ERR_HIP, "hipEventRecord failed (shared inputs)"); ok_ = false; }
+  bool wait_other = false;
+  for (const Entry &e : entries_) {
+    if (!e.taken) continue;
+    if (!share_->resolved(e.share)) { ok_ = false; continue; }   // (its first upload failed: ctx says why)
+    *e.slot = share_->take(e.share);
+    if (share_->owner_of(e.share) != owner_) wait_other = true;
+  }
+  if (wait_other && hipStreamWaitEvent(s_, ctx_->share_ev[1 - owner_], 0) != hipSuccess) { ctx_->fail(RRTMG_ERR_HIP, "hipStreamWaitEvent failed (shared inputs)"); ok_ = false; }
+  share_->drop_unresolved();
   return ok_;
 }
 
@@ -344,15 +390,25 @@ static int check_band_struct(rrtmg_ctx *ctx, const S *b, const char *name) {
 }
 
 // Every shortwave flux entry point: sf, then b (size, then levels), then c; a struct without a member set is the call without it.
-static int sw_fluxes_checked(rrtmg_ctx *ctx, const rrtmg_sw_args *a, const rrtmg_sw_surface *sf, const rrtmg_sw_components *c, const rrtmg_sw_band_fluxes *b) {
-  if (!ctx) return RRTMG_ERR_ARG;
+static int sw_optional_checked(rrtmg_ctx *ctx, const rrtmg_sw_surface *&sf, const rrtmg_sw_components *&c, const rrtmg_sw_band_fluxes *&b) {
   if (int rc = check_struct(ctx, sf, "rrtmg_sw_surface")) return rc;
   if (sf && !(sf->albdir || sf->albdif)) sf = nullptr;
   if (int rc = check_band_struct(ctx, b, "rrtmg_sw_band_fluxes")) return rc;
   if (b && !(b->up || b->dn || b->upc || b->dnc || b->dndir || b->dndirc)) b = nullptr;
   if (int rc = check_struct(ctx, c, "rrtmg_sw_components")) return rc;
   if (c && !(c->dirdflx || c->difdflx || c->dirdnuv || c->difdnuv || c->dirdnir || c->difdnir || c->dirdflxc || c->difdflxc)) c = nullptr;
+  return 0;
+}
+static int sw_fluxes_checked(rrtmg_ctx *ctx, const rrtmg_sw_args *a, const rrtmg_sw_surface *sf, const rrtmg_sw_components *c, const rrtmg_sw_band_fluxes *b) {
+  if (!ctx) return RRTMG_ERR_ARG;
+  if (int rc = sw_optional_checked(ctx, sf, c, b)) return rc;
   return checked_call(ctx, a, "rrtmg_sw", [sf, c, b](rrtmg_ctx *x, const rrtmg_sw_args *y) { return sw_fluxes_impl(x, y, sf, c, b); });
+}
+// the longwave's band struct, likewise
+static int lw_optional_checked(rrtmg_ctx *ctx, const rrtmg_lw_band_fluxes *&b) {
+  if (int rc = check_band_struct(ctx, b, "rrtmg_lw_band_fluxes")) return rc;
+  if (b && !(b->up || b->dn || b->upc || b->dnc)) b = nullptr;
+  return 0;
 }
 
 extern "C" {
@@ -394,7 +450,9 @@ void rrtmg_hip_destroy(rrtmg_ctx *ctx) {
   if (ctx->err_dev) (void)hipFree(ctx->err_dev);
   if (ctx->ncloudy_dev) (void)hipFree(ctx->ncloudy_dev);
   if (ctx->hint) (void)hipHostFree((void *)ctx->hint);
-  if (ctx->pinned) (void)hipHostFree(ctx->pinned);
+  if (ctx->flag_host) (void)hipHostFree(ctx->flag_host);
+  for (int w = 0; w < 2; ++w)
+    if (ctx->pinned[w]) (void)hipHostFree(ctx->pinned[w]);
   for (int w = 0; w < 4; ++w)
     for (hipEvent_t e : ctx->ev[w])
       if (e) (void)hipEventDestroy(e);
@@ -403,6 +461,8 @@ void rrtmg_hip_destroy(rrtmg_ctx *ctx) {
       if (ctx->kiss_ev[w][k]) (void)hipEventDestroy(ctx->kiss_ev[w][k]);
   for (int w = 0; w < 2; ++w)
     if (ctx->sync_ev[w]) (void)hipEventDestroy(ctx->sync_ev[w]);
+  for (int w = 0; w < 2; ++w)
+    if (ctx->share_ev[w]) (void)hipEventDestroy(ctx->share_ev[w]);
   if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
   if (ctx->stream_lw) (void)hipStreamDestroy(ctx->stream_lw);
   rrtmg::free_sw_desc(ctx);
@@ -515,9 +575,36 @@ int rrtmg_hip_sw_fluxes_bands(rrtmg_ctx *ctx, const rrtmg_sw_args *a, const rrtm
 int rrtmg_hip_sw_fluxes_surface(rrtmg_ctx *ctx, const rrtmg_sw_args *a, const rrtmg_sw_surface *sf, const rrtmg_sw_components *c, const rrtmg_sw_band_fluxes *b) { return sw_fluxes_checked(ctx, a, sf, c, b); }
 int rrtmg_hip_lw_fluxes_bands(rrtmg_ctx *ctx, const rrtmg_lw_args *a, const rrtmg_lw_band_fluxes *b) {
   if (!ctx) return RRTMG_ERR_ARG;
-  if (int rc = check_band_struct(ctx, b, "rrtmg_lw_band_fluxes")) return rc;
-  if (!b || !(b->up || b->dn || b->upc || b->dnc)) return rrtmg_hip_lw_fluxes(ctx, a);
+  if (int rc = lw_optional_checked(ctx, b)) return rc;
+  if (!b) return rrtmg_hip_lw_fluxes(ctx, a);
   return checked_call(ctx, a, "rrtmg_lw", [b](rrtmg_ctx *x, const rrtmg_lw_args *y) { return lw_fluxes_impl(x, y, b); });
+}
+// Both spectra of one host state (radiation_fluxes_impl; rrtmg_call.h: joint_run).  Every check of the separate entry points, through the same helpers,
+// and the three of the joint call, before anything is enqueued.
+int rrtmg_hip_radiation_fluxes(rrtmg_ctx *ctx, const rrtmg_radiation_call *call) {
+  if (!ctx) return RRTMG_ERR_ARG;
+  if (!call) return ctx->fail(RRTMG_ERR_ARG, "rrtmg_radiation_call: NULL argument struct");
+  if (int rc = check_struct(ctx, call, "rrtmg_radiation_call")) return rc;
+  const rrtmg_sw_surface *sf = call->sw_surface; const rrtmg_sw_components *c = call->sw_components; const rrtmg_sw_band_fluxes *b = call->sw_bands;
+  const rrtmg_lw_band_fluxes *lb = call->lw_bands;
+  if (int rc = sw_optional_checked(ctx, sf, c, b)) return rc;
+  if (int rc = lw_optional_checked(ctx, lb)) return rc;
+  return checked_call(ctx, call->sw, "rrtmg_sw", [=](rrtmg_ctx *, const rrtmg_sw_args *sw) {
+    return checked_call(ctx, call->lw, "rrtmg_lw", [=](rrtmg_ctx *, const rrtmg_lw_args *lw) {
+      if (sw->memspace != 0 || lw->memspace != 0)
+        return ctx->fail(RRTMG_ERR_ARG, "rrtmg_hip_radiation_fluxes: host arrays only (memspace 0 in both structs); device-resident callers have deferred mode");
+      if (sw->ncol != lw->ncol || sw->nlay != lw->nlay)
+        return ctx->fail(RRTMG_ERR_ARG, "rrtmg_hip_radiation_fluxes: the shortwave has %d x %d columns x layers, the longwave %d x %d", (int)sw->ncol, (int)sw->nlay, (int)lw->ncol, (int)lw->nlay);
+      if (sw->shard_col0 != lw->shard_col0 || sw->shard_ncol != lw->shard_ncol)
+        return ctx->fail(RRTMG_ERR_ARG, "rrtmg_hip_radiation_fluxes: shard_col0 / shard_ncol differ between the two structs");
+      return radiation_fluxes_impl(ctx, sw, sf, c, b, lw, lb);
+    });
+  });
+}
+int rrtmg_hip_radiation_last(rrtmg_ctx *ctx, int *arrays_shared, long long *bytes_uploaded, long long *bytes_shared) {
+  if (!ctx || !arrays_shared || !bytes_uploaded || !bytes_shared || !ctx->joint_seen) return RRTMG_ERR_ARG;
+  *arrays_shared = ctx->joint_arrays_shared; *bytes_uploaded = ctx->joint_bytes_uploaded; *bytes_shared = ctx->joint_bytes_shared;
+  return RRTMG_OK;
 }
 // band limits, cm^-1: shortwave bands 16..29 (wavenum1 / wavenum2 of rrtmg_sw_init.f90, band 29 last), longwave bands 1..16
 // (rrtmg_lw_init.f90:196-204; hi - lo == delwave)

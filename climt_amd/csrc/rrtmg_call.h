@@ -37,8 +37,11 @@ inline int check_outputs(rrtmg_ctx *ctx, double *const *o) {
   return RRTMG_OK;
 }
 // The stream rule: the shortwave is always on ctx->stream; the longwave moves to stream_lw when the call is deferred and
-// device-resident, so that the two spectra overlap on the GPU.  (After ctx_prepare_device: the streams are created there.)
-inline hipStream_t call_stream(const rrtmg_ctx *ctx, int which, int memspace) { return (which == 1 && ctx->deferred && memspace == 1) ? ctx->stream_lw : ctx->stream; }
+// device-resident, or half of a joint call (rrtmg_hip_radiation_fluxes: host pointers), so that the two spectra overlap on the
+// GPU.  (After ctx_prepare_device: the streams are created there.)
+inline hipStream_t call_stream(const rrtmg_ctx *ctx, int which, int memspace) { return (which == 1 && (ctx->joint || (ctx->deferred && memspace == 1))) ? ctx->stream_lw : ctx->stream; }
+// the table of a joint call's inputs for HostInputs, or nullptr
+inline ShareTable *call_share(const rrtmg_ctx *ctx) { return ctx->joint ? &ctx->joint->table : nullptr; }
 // ---- the sorted call: head and tail (the gather lists are the spectrum's own) ---------------------------------------------------
 // head: the device, the column map on the call's stream (a sorted call is device-resident), b = the call on the padded copy
 template <class Args>
@@ -160,10 +163,15 @@ inline void run_chunks(const CallSite &c, Dev &d, bool clouds, int hint_cloudy, 
 // ---- epilogue: status + outputs ---------------------------------------------------------------------------------------------------
 // oc[nout]: the standard outputs plus what opt_out_append added (read for a host-pointer call only).  A deferred call returns
 // once enqueued, its flag pending; a host-pointer call downloads outputs and flag behind one synchronise; a synchronous
-// device-resident call reads the flag.
+// device-resident call reads the flag.  Half of a joint call: the copies of outputs and flag are enqueued behind the
+// spectrum's integration kernels and the call returns; joint_collect waits for both spectra and reads the flags.
+inline int spectrum_fail(rrtmg_ctx *ctx, int which, int herr) {
+  return which == 0 ? ctx->fail(herr, "shortwave: %s", status_message(herr)) : ctx->fail(herr, "longwave: %s", status_message(herr));
+}
 inline int call_finish(const CallSite &c, int memspace, const OutCopy *oc, int nout, int *err_dev) {
   rrtmg_ctx *ctx = c.ctx;
   RRTMG_HIP_CHECK(ctx, hipGetLastError());
+  if (ctx->joint) return copy_out_enqueue(ctx, c.s, oc, nout, err_dev, ctx->joint->out[c.which], c.which);
   if (ctx->deferred && memspace == 1) { ctx->pending[c.which] = true; ctx->status = 0; return RRTMG_OK; }
   int herr = 0;
   if (memspace == 0) {
@@ -172,7 +180,44 @@ inline int call_finish(const CallSite &c, int memspace, const OutCopy *oc, int n
     RRTMG_HIP_CHECK(ctx, hipMemcpyAsync(&herr, err_dev, sizeof(int), hipMemcpyDeviceToHost, c.s));
     RRTMG_HIP_CHECK(ctx, hipStreamSynchronize(c.s));
   }
-  if (herr) return c.which == 0 ? ctx->fail(herr, "shortwave: %s", status_message(herr)) : ctx->fail(herr, "longwave: %s", status_message(herr));
+  if (herr) return spectrum_fail(ctx, c.which, herr);
+  ctx->status = 0;
+  return RRTMG_OK;
+}
+// ---- the joint call: both spectra of one host state in one call -----------------------------------------------------------------
+// sw(), lw(): the two drivers on their checked arguments.  While ctx->joint is set they differ from separate calls in three
+// places, all above: call_stream (the longwave on stream_lw), call_share (inputs the shortwave has brought to the device are
+// taken, not uploaded again) and call_finish (output copies enqueued, not waited for).  So the shortwave's inputs, launches
+// and copies are enqueued first, then the longwave's; each spectrum's copies run under the other's solve.  Then one wait per
+// stream, the shortwave's first: its staged outputs reach the caller's arrays while the longwave still runs.  The flags are
+// read behind both.  Status: the shortwave's if it failed -- at a check or on the device -- else the longwave's; the spectrum
+// that did not fail has its outputs complete either way.  Work pending from deferred mode is collected first, as
+// call_own_flag does for a separate call.
+template <class Sw, class Lw>
+inline int joint_run(rrtmg_ctx *ctx, Sw sw, Lw lw) {
+  if (int rc = ctx_prepare_device(ctx)) return rc;
+  if (ctx->pending[0] || ctx->pending[1]) { if (const int prc = rrtmg_hip_synchronize(ctx)) return prc; }
+  JointCall j;
+  ctx->joint = &j;
+  int rc[2];
+  std::string msg[2];
+  rc[0] = sw(); msg[0] = ctx->err;
+  rc[1] = lw(); msg[1] = ctx->err;
+  ctx->joint = nullptr;
+  hipStream_t st[2] = {ctx->stream, ctx->stream_lw};
+  int hip_rc = RRTMG_OK;
+  for (int w = 0; w < 2; ++w) {
+    const hipError_t e = hipStreamSynchronize(st[w]);   // (also where a spectrum failed half-way: nothing of it stays in flight)
+    if (e != hipSuccess && !hip_rc) hip_rc = ctx->fail(RRTMG_ERR_HIP, "hipStreamSynchronize failed: %s", hipGetErrorString(e));
+    if (e == hipSuccess && !rc[w] && j.out[w].enqueued) copy_out_complete(ctx, j.out[w]);
+  }
+  ctx->joint_seen = true;
+  ctx->joint_arrays_shared = j.table.arrays_shared(); ctx->joint_bytes_uploaded = j.table.bytes_uploaded(); ctx->joint_bytes_shared = j.table.bytes_shared();
+  if (hip_rc) return hip_rc;
+  for (int w = 0; w < 2; ++w) {
+    if (rc[w]) { ctx->err = msg[w]; ctx->status = rc[w]; return rc[w]; }
+    if (j.out[w].herr) return spectrum_fail(ctx, w, j.out[w].herr);
+  }
   ctx->status = 0;
   return RRTMG_OK;
 }

@@ -27,6 +27,8 @@ struct DevBuf {
   size_t uni_n = 0;
 };
 
+struct JointCall;   // rrtmg_hip_radiation_fluxes in progress (below)
+
 }  // namespace rrtmg
 
 struct rrtmg_ctx {
@@ -129,8 +131,18 @@ struct rrtmg_ctx {
   // grow-only device work buffers, by name
   std::map<std::string, rrtmg::DevBuf> bufs;
   // grow-only PINNED host staging for the outputs of host-pointer calls (see copy_out)
-  void *pinned = nullptr;
-  size_t pinned_cap = 0;
+  // ([1]: the longwave's of a joint call, whose copies are in flight while the shortwave's are)
+  void *pinned[2] = {nullptr, nullptr};
+  size_t pinned_cap[2] = {0, 0};
+  // rrtmg_hip_radiation_fluxes: the call in progress (else nullptr: every call path is the one of a library without it);
+  // share_ev[w]: recorded on the stream of spectrum w behind the last input it brought to the device for the table; the
+  // three numbers of the last joint call (rrtmg_hip_radiation_last)
+  rrtmg::JointCall *joint = nullptr;
+  int *flag_host = nullptr;   // [2], page-locked: where copy_out_enqueue has the error flag of staging slot [0|1] copied to
+  hipEvent_t share_ev[2] = {nullptr, nullptr};
+  bool joint_seen = false;
+  int joint_arrays_shared = 0;
+  long long joint_bytes_uploaded = 0, joint_bytes_shared = 0;
   int *err_dev = nullptr;
   // HIP events around the solve launches of EVERY column chunk of the last call: [0] sw clear-sky kernel, [1] lw clear-sky
   // variant, [2] sw cloudy kernel, [3] lw cloudy variant; per chunk a (start, stop) pair, created on demand.
@@ -186,6 +198,17 @@ namespace rrtmg {
 void launch_interface_values(hipStream_t s, int ncol, int nlay, const double *mid, const double *surf, const double *pmid, const double *pint, double *out);
 struct OutCopy { double *host; const double *dev; size_t n; };
 int copy_out(rrtmg_ctx *ctx, hipStream_t s, const OutCopy *o, int count, int *herr_dev, int *herr_host);
+// The same in two steps, "enqueue now, wait later": copy_out_enqueue puts the flag's and the outputs' copies on s (staging
+// buffer `slot` of the context) and returns; once the caller has waited for s, copy_out_complete moves what was staged into
+// the caller's arrays.  po.herr then holds the flag.  Every copy lands in page-locked memory (the flag in ctx->flag_host), so
+// that enqueueing never waits for the stream: a device-to-host copy into pageable memory would.  copy_out is the two around hipStreamSynchronize(s).
+constexpr int kMaxOut = 24;   // shortwave: 6 outputs + 8 components + 6 band arrays
+struct PendingOut { OutCopy oc[kMaxOut]; bool direct[kMaxOut]; int count = 0; size_t total = 0; int herr = 0; int slot = 0; bool has_flag = false, enqueued = false; };
+int copy_out_enqueue(rrtmg_ctx *ctx, hipStream_t s, const OutCopy *o, int count, int *herr_dev, PendingOut &po, int slot);
+void copy_out_complete(rrtmg_ctx *ctx, PendingOut &po);
+// One rrtmg_hip_radiation_fluxes call: the inputs it has brought to the device, and per spectrum [sw|lw] the output copies
+// that are enqueued behind its integration kernels and not yet waited for.
+struct JointCall { ShareTable table; PendingOut out[2]; };
 }  // namespace rrtmg
 
 #define RRTMG_HIP_CHECK(ctx, call)                                                                     \
@@ -205,6 +228,9 @@ void free_lw_desc(rrtmg_ctx *ctx);
 int sw_fluxes_impl(rrtmg_ctx *ctx, const rrtmg_sw_args *a, const rrtmg_sw_surface *sf = nullptr, const rrtmg_sw_components *c = nullptr,
                    const rrtmg_sw_band_fluxes *b = nullptr);
 int lw_fluxes_impl(rrtmg_ctx *ctx, const rrtmg_lw_args *a, const rrtmg_lw_band_fluxes *b = nullptr);   // (b: as for the shortwave)
+// rrtmg_hip_radiation_fluxes on checked structs: call_begin of both spectra, then the two drivers above under joint_run (rrtmg_call.h)
+int radiation_fluxes_impl(rrtmg_ctx *ctx, const rrtmg_sw_args *sw, const rrtmg_sw_surface *sf, const rrtmg_sw_components *c, const rrtmg_sw_band_fluxes *b,
+                          const rrtmg_lw_args *lw, const rrtmg_lw_band_fluxes *lb);
 int sw_init_impl(rrtmg_ctx *ctx, double cpdair, const char *blob);
 int lw_init_impl(rrtmg_ctx *ctx, double cpdair, const char *blob);
 int mcica_mask_impl(rrtmg_ctx *ctx, int which, int ncol, int nlay, int icld, int permuteseed, int irng,

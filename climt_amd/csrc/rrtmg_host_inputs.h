@@ -14,11 +14,16 @@
 //     volume mixing ratio -- are applied on the device after the upload (rrtmg_{sw,lw}_args::*_scale), with the operations
 //     numpy would have used (one rounding per product, contraction off): same bits, no host pass over the array.
 // Device-pointer calls (memspace = 1) pass through untouched.
+// Inside a joint shortwave + longwave call (rrtmg_hip_radiation_fluxes) a ShareTable (rrtmg_share.h) is passed: an input whose
+// (host pointer, count, mul, div, policy) the call has brought to the device already takes that device pointer -- the filled
+// and the absent result included -- and is not scanned, copied or scaled again.  Without a table nothing changes.
 #pragma once
 #include <cstddef>
 #include <vector>
 
 #include <hip/hip_runtime.h>
+
+#include "rrtmg_share.h"
 
 struct rrtmg_ctx;
 
@@ -33,7 +38,9 @@ enum class InPolicy {
 
 class HostInputs {
  public:
-  HostInputs(rrtmg_ctx *ctx, hipStream_t s, const char *prefix, int memspace) : ctx_(ctx), s_(s), prefix_(prefix), memspace_(memspace) {}
+  // share, owner: the joint call's table and the spectrum that asks (0 shortwave, 1 longwave), or nullptr
+  HostInputs(rrtmg_ctx *ctx, hipStream_t s, const char *prefix, int memspace, ShareTable *share = nullptr, int owner = 0)
+      : ctx_(ctx), s_(s), prefix_(prefix), memspace_(memspace), share_(share), owner_(owner) {}
   // registers one input; *slot receives the device pointer in finish() (at once for memspace 1 and NULL arrays).
   // value on the device = host value * mul (/ div when div != 0); mul == 0: as given.
   void add(const double **slot, const double *host, size_t n, const char *name, bool required, InPolicy policy = InPolicy::Plain,
@@ -45,10 +52,14 @@ class HostInputs {
   struct Entry {
     const double **slot; const double *host; size_t n; const char *name; InPolicy policy; double mul, div;
     int job = -1;   // index into the scan jobs, or -1: upload without asking
+    int share = -1;        // the entry of the joint call's table
+    bool taken = false;    // ... which another input has brought, or is bringing, to the device: nothing to do but take it
   };
+  void resolved(const Entry &e, const double *dev, size_t copied_bytes) { if (share_) share_->resolve(e.share, dev, copied_bytes); }
   bool upload(const Entry &e);
   bool fill(const Entry &e, double host_value);
   rrtmg_ctx *ctx_; hipStream_t s_; const char *prefix_; int memspace_;
+  ShareTable *share_; int owner_;
   std::vector<Entry> entries_;
   bool ok_ = true;
 };

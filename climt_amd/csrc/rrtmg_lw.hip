@@ -251,7 +251,7 @@ int lw_fluxes_impl(rrtmg_ctx *ctx, const rrtmg_lw_args *a, const rrtmg_lw_band_f
   // ---- inputs (rrtmg_host_inputs.h: uniform arrays are filled on the device, all-zero band arrays are absent) ----------------
   bool ok = true;
   const double ps = a->pressure_scale, ws = a->water_path_scale;
-  HostInputs hi(ctx, s, "lw.in.", a->memspace);
+  HostInputs hi(ctx, s, "lw.in.", a->memspace, call_share(ctx), 1);
   hi.add(&d.play, a->play, nl, "play", true, InPolicy::Plain, ps); hi.add(&d.plev, a->plev, nl1, "plev", true, InPolicy::Plain, ps);
   hi.add(&d.tlay, a->tlay, nl, "tlay", true); hi.add(&d.tlev, a->tlev, nl1, "tlev", false); hi.add(&d.tsfc, a->tsfc, N, "tsfc", true);
   hi.add(&d.h2o, a->h2ovmr, nl, "h2o", true, InPolicy::Plain, a->h2o_mul, a->h2o_div); hi.add(&d.o3, a->o3vmr, nl, "o3", true);
@@ -372,6 +372,15 @@ int lw_fluxes_impl(rrtmg_ctx *ctx, const rrtmg_lw_args *a, const rrtmg_lw_band_f
   OutCopy oc[12] = {{a->uflx, d.uflx, nl1}, {a->dflx, d.dflx, nl1}, {a->uflxc, d.uflxc, nl1}, {a->dflxc, d.dflxc, nl1},
                     {a->hr, d.hr, nl}, {a->hrc, d.hrc, nl}, {a->duflx_dt, d.duflx_dt, nl1}, {a->duflxc_dt, d.duflxc_dt, nl1}};
   return call_finish(c, a->memspace, oc, opt_out_append(bpt, 4, nband, oc, d.idrv ? 8 : 6), d.err);   // the requested band fluxes behind the same synchronise
+}
+
+// Both spectra of one host state (rrtmg_hip_radiation_fluxes): the argument checks of both before anything is enqueued, then
+// the two drivers, each with its one body, under joint_run (rrtmg_call.h).
+int radiation_fluxes_impl(rrtmg_ctx *ctx, const rrtmg_sw_args *sw, const rrtmg_sw_surface *sf, const rrtmg_sw_components *c, const rrtmg_sw_band_fluxes *b,
+                          const rrtmg_lw_args *lw, const rrtmg_lw_band_fluxes *lb) {
+  if (int rc = call_begin(ctx, 0, sw)) return rc;
+  if (int rc = call_begin(ctx, 1, lw)) return rc;
+  return joint_run(ctx, [=]() { return sw_fluxes_impl(ctx, sw, sf, c, b); }, [=]() { return lw_fluxes_impl(ctx, lw, lb); });
 }
 
 }  // namespace rrtmg

@@ -557,7 +557,7 @@ int sw_fluxes_impl(rrtmg_ctx *ctx, const rrtmg_sw_args *a, const rrtmg_sw_surfac
   // ---- inputs (rrtmg_host_inputs.h: uniform arrays are filled on the device, all-zero band arrays are absent) ----------------
   bool ok = true;
   const double ps = a->pressure_scale, ws = a->water_path_scale;
-  HostInputs hi(ctx, s, "sw.in.", a->memspace);
+  HostInputs hi(ctx, s, "sw.in.", a->memspace, call_share(ctx), 0);
   hi.add(&d.play, a->play, nl, "play", true, InPolicy::Plain, ps); hi.add(&d.plev, a->plev, nl1, "plev", true, InPolicy::Plain, ps);
   hi.add(&d.tlay, a->tlay, nl, "tlay", true);
   hi.add(&d.h2o, a->h2ovmr, nl, "h2o", true, InPolicy::Plain, a->h2o_mul, a->h2o_div); hi.add(&d.o3, a->o3vmr, nl, "o3", true);

@@ -154,6 +154,13 @@ class RRTMGLongwave(TendencyComponent):
     @ensure_contiguous_state
     def array_call(self, state):
         """Longwave heating tendency and up/down fluxes (all-sky and clear-sky)."""
+        call = self._prepare_call(state)
+        self._ctx.lw_fluxes(**call["library"])
+        return self._finish_call(call)
+
+    def _prepare_call(self, state):
+        """array_call, part 1 of 3: the raw state -> {"library": the keyword arguments of Context.lw_fluxes, "tendencies",
+        "diagnostics"}.  Part 2 is the library call, part 3 _finish_call (see RRTMGShortwave._prepare_call)."""
         # mass_to_volume_mixing_ratio(q, 18.02) = q * 28.964 / 18.02 and the unit factors of the pressures and cloud water paths
         # are applied by the library on the device, after the upload (common.library_scales): no host pass over those arrays
         scales, unit = library_scales(state)
@@ -199,11 +206,14 @@ class RRTMGLongwave(TendencyComponent):
             for key in ("duflx_dt", "duflxc_dt"):
                 out[key] = self._pool.zeros_like_fresh(key, (n_layers + 1, n_columns))
         self._input_staging.wait()
+        library = dict(inp=inp, mcica=self._mcica, out=out)
         if self._band_fluxes:
-            bands = {b: diagnostics[k] for k, b in BAND_FLUX_DIAGNOSTICS.items()}
-            self._ctx.lw_fluxes(inp, mcica=self._mcica, out=out, bands=bands)
-        else:
-            self._ctx.lw_fluxes(inp, mcica=self._mcica, out=out)
+            library.update(bands={b: diagnostics[k] for k, b in BAND_FLUX_DIAGNOSTICS.items()})
+        return dict(library=library, tendencies=tendencies, diagnostics=diagnostics)
+
+    def _finish_call(self, call):
+        """array_call, part 3 of 3: what follows the library call."""
+        tendencies, diagnostics, out = call["tendencies"], call["diagnostics"], call["library"]["out"]
         if self._calc_dflxdt:
             self.change_in_upward_flux_with_surface_temperature = out["duflx_dt"]
             self.change_in_clear_sky_upward_flux_with_surface_temperature = out["duflxc_dt"]

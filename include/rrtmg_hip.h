@@ -399,6 +399,39 @@ typedef struct rrtmg_lw_band_fluxes {
 /* rrtmg_hip_lw_fluxes plus the requested band fluxes: the rules of rrtmg_hip_sw_fluxes_bands. */
 int rrtmg_hip_lw_fluxes_bands(rrtmg_ctx *ctx, const rrtmg_lw_args *a, const rrtmg_lw_band_fluxes *b);
 
+/* ---- shortwave and longwave of one host state in one call ------------------------------- */
+/* A host caller (memspace 0) that computes both spectra of the same state says so with this call instead of two separate
+ * ones.  The outputs are bit for bit those of rrtmg_hip_sw_fluxes*(sw ...) followed by rrtmg_hip_lw_fluxes*(lw ...) on the
+ * same arguments, every optional output included; what differs is the schedule:
+ *  - an input that both structs give as the SAME host pointer, with the same element count and the same unit factors (play,
+ *    plev, tlay, the gases, the cloud arrays of a model state), crosses to the device once.  Inside one call the caller's
+ *    arrays cannot change, so an identical pointer is identical content; nothing is shared across calls, and anything that
+ *    differs in pointer, count or factor is uploaded on its own, as by the separate calls;
+ *  - the shortwave runs on the context's stream, the longwave on its second stream: the two solves overlap on the GPU, and
+ *    each spectrum's outputs come down while the other still computes.  The call returns when both are complete.
+ * Every check of the separate entry points is made, for both spectra, before anything is enqueued; on top, with
+ * RRTMG_ERR_ARG: both memspace must be 0 (device-resident callers have deferred mode, rrtmg_hip_set_deferred), ncol and nlay
+ * must agree, and so must shard_col0 / shard_ncol.  The column sort never applies (it is for device pointers).  Work pending
+ * from deferred mode is collected first: its error, if any, is what the call returns, and nothing of the call has run then.
+ * Status: the shortwave's if the shortwave fails, else the longwave's; when one spectrum fails the other's outputs are still
+ * complete and correct, the context stays usable, and rrtmg_hip_last_error names the spectrum.
+ * sw and lw are required; the optional members are those of rrtmg_hip_sw_fluxes_surface and rrtmg_hip_lw_fluxes_bands (NULL, or
+ * a struct without a member set: not requested).  RRTMG_HIP_ABI_VERSION is unchanged: probe for the symbol. */
+typedef struct rrtmg_radiation_call {
+  int struct_size;                       /* sizeof(rrtmg_radiation_call) */
+  const rrtmg_sw_args *sw;               /* required */
+  const rrtmg_sw_surface *sw_surface;    /* optional, as in rrtmg_hip_sw_fluxes_surface */
+  const rrtmg_sw_components *sw_components;
+  const rrtmg_sw_band_fluxes *sw_bands;
+  const rrtmg_lw_args *lw;               /* required */
+  const rrtmg_lw_band_fluxes *lw_bands;
+} rrtmg_radiation_call;
+int rrtmg_hip_radiation_fluxes(rrtmg_ctx *ctx, const rrtmg_radiation_call *call);
+/* The last rrtmg_hip_radiation_fluxes call of the context: arrays_shared = inputs taken from what the call had already
+ * brought to the device; bytes_uploaded = host-to-device bytes the call copied; bytes_shared = bytes it did not copy because
+ * of that (an array that was filled on the device, or absent, counts 0 in both).  RRTMG_ERR_ARG before any such call. */
+int rrtmg_hip_radiation_last(rrtmg_ctx *ctx, int *arrays_shared, long long *bytes_uploaded, long long *bytes_shared);
+
 /* sub-column generators on their own (mcica_subcol_gen_{sw,lw}.f90); host pointers.
  * which: 0 = SW (112 sub-columns), 1 = LW (140).  cldfmcl out: [nlay][ncol][ngpt] of 0/1. */
 int rrtmg_hip_mcica_mask(rrtmg_ctx *ctx, int which, int ncol, int nlay, int icld, int permuteseed,
