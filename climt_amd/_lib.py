@@ -189,6 +189,8 @@ def load_library():
     if hasattr(lib, "rrtmg_hip_set_sw_night_skip"):      # (RRTMG_HIP_LIB may name a library that predates it, as for the entry above)
         lib.rrtmg_hip_set_sw_night_skip.argtypes = [_vp, C.c_int]
         lib.rrtmg_hip_sw_night_last.argtypes = [_vp, C.POINTER(C.c_int), C.POINTER(C.c_int)]
+    if hasattr(lib, "rrtmg_hip_set_sw_night_pack"):      # (likewise)
+        lib.rrtmg_hip_set_sw_night_pack.argtypes = [_vp, C.c_int]
     if hasattr(lib, "rrtmg_hip_radiation_fluxes"):       # (likewise)
         lib.rrtmg_hip_radiation_fluxes.argtypes = [_vp, C.POINTER(RadiationCall)]
         lib.rrtmg_hip_radiation_last.argtypes = [_vp, C.POINTER(C.c_int), C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]
@@ -425,10 +427,21 @@ class Context:
         every output, and 64-column tiles whose columns are all night are not prepared or solved; day columns keep their bits."""
         self._ck(self.lib.rrtmg_hip_set_sw_night_skip(self.h, 1 if on else 0))
 
+    @property
+    def has_sw_night_pack(self):
+        return hasattr(self.lib, "rrtmg_hip_set_sw_night_pack")
+
+    @_locked
+    def set_sw_night_pack(self, on=True):
+        """Opt-in day-column pack of the shortwave (rrtmg_hip_set_sw_night_pack): an eligible device-resident call runs on an
+        internal copy with the day columns packed into dense tiles, so that every night column's solve is saved; any other call
+        runs as with set_sw_night_skip(True).  Night columns get exact zeros either way."""
+        self._ck(self.lib.rrtmg_hip_set_sw_night_pack(self.h, 1 if on else 0))
+
     @_locked
     def sw_night_last(self):
         """-> (night tiles, night columns) of the last completed shortwave call (in deferred mode: after synchronize());
-        (0, 0) when the skip was off (rrtmg_hip_sw_night_last)."""
+        (0, 0) when the skip was off (rrtmg_hip_sw_night_last); after a packed call: night.packed_counts."""
         t, c = C.c_int(0), C.c_int(0)
         self._ck(self.lib.rrtmg_hip_sw_night_last(self.h, C.byref(t), C.byref(c)))
         return t.value, c.value

@@ -98,6 +98,11 @@ struct rrtmg_ctx {
   // hint is; sw_night_reported: the last enqueued shortwave call had the skip on (else rrtmg_hip_sw_night_last reports 0 / 0)
   bool sw_night_skip = false, sw_night_reported = false;
   volatile int *night_host() const { return hint ? (volatile int *)(hint + 2) : nullptr; }
+  // rrtmg_hip_set_sw_night_pack (rrtmg_pack.h): an eligible device-resident shortwave call runs on an internal copy with the day
+  // columns packed into dense tiles, any other call as with the skip on.  sw_packing: this is the inner call of a packed one (it
+  // does not enter the gate again, runs the night kernels and leaves the epilogue to the packed call); sw_pack_reported: the
+  // last enqueued shortwave call was packed (its night count is that of the caller's grid, one tile less than the copy's)
+  bool sw_night_pack = false, sw_packing = false, sw_pack_reported = false;
   // KISS jump-ahead operators [sw|lw]: host copy, the key they were built for, the device buffer they were uploaded to
   std::vector<uint32_t> kiss_host[2][2];   // two staging copies per spectrum: a rebuild never waits for the previous upload
   hipEvent_t kiss_ev[2][2] = {{nullptr, nullptr}, {nullptr, nullptr}};   // recorded after the upload from kiss_host[w][k]

@@ -25,8 +25,12 @@
 //   With the night-column skip on (rrtmg_hip_set_sw_night_skip): sw_kiss_mask_night_kernel, sw_prep_fused_night_kernel,
 //   sw_cloud_night_kernel, sw_tile_lists_night_kernel and sw_{fluxheat,components,bandflux}_night_kernel in the places of their
 //   namesakes; the solve kernels are the same and find a night tile in neither of their lists
+//   With the day-column pack on (rrtmg_hip_set_sw_night_pack; rrtmg_pack.h), around the sequence above with the night kernels on
+//   an internal copy: pack_count_kernel, pack_scan_kernel, pack_map_kernel, pack_gather_kernel (+ pack_gather_elem_kernel for
+//   band-fastest cloud arrays) in front, pack_scatter_kernel behind
 // The host steps this call shares with the longwave's (gate, checks, chunk plan and loop, mask choice, epilogue): rrtmg_call.h
 #include "rrtmg_call.h"
+#include "rrtmg_pack.h"
 #include "rrtmg_sw_device.h"
 #include "rrtmg_sw_host.h"
 
@@ -526,8 +530,86 @@ static int sw_sorted_call(rrtmg_ctx *ctx, const rrtmg_sw_args *a) {
 // stream, and the inner call on the padded copy would hand each column another column's multipliers and rescale the caller's
 // IN/OUT array once per padded slot.
 static bool sw_amplitudes_differ_from_one(const rrtmg_sw_args *a) { return a && a->indsolvar && (a->indsolvar[0] != 1.0 || a->indsolvar[1] != 1.0); }
+// The call runs packed (rrtmg_pack.h): opt-in, device pointers, at least two tiles, kissvec or no McICA, amplitudes indsolvar
+// equal to 1 (the twister's stream and the rescaled amplitudes are positional), not half of a joint call and not the inner
+// call itself.  Any other call with the option on runs as with the night-column skip on.
+static bool sw_call_is_packed(const rrtmg_ctx *ctx, const rrtmg_sw_args *a) {
+  return ctx->sw_night_pack && !ctx->sw_packing && !ctx->sorting && !ctx->joint && ctx->sw_ready && a && a->memspace == 1 && a->coszen && a->ncol > 64 &&
+         a->nlay > 0 && a->nlay <= 256 && !(a->mcica && a->irng != 0) && !sw_amplitudes_differ_from_one(a);
+}
+// The packed call: the column map from coszen, ONE gather launch for the [rows][N] inputs (one more for the band-fastest cloud
+// arrays where they are given), the ordinary driver with the night kernels on the copy of Np slots, ONE scatter launch for
+// every requested output, which also leaves the counts of rrtmg_hip_sw_night_last, then the epilogue the inner call skipped.
+// Components, bands and the surface struct ride along: their rows are entries of the same two tables.
+static int sw_packed_call(rrtmg_ctx *ctx, const rrtmg_sw_args *a, const rrtmg_sw_surface *sp, const rrtmg_sw_components *cp, const rrtmg_sw_band_fluxes *bp) {
+  if (int rc = call_begin(ctx, 0, a)) return rc;
+  const CallSite c{ctx, 0, call_stream(ctx, 0, 1)};
+  DayPack pk(ctx, c.s, a->ncol, a->nlay);
+  double *const u[6] = {a->swuflx, a->swdflx, a->swhr, a->swuflxc, a->swdflxc, a->swhrc};
+  if (int rc = check_outputs(ctx, u)) return rc;
+  if (!pk.prepare(a->coszen)) return ctx->status;
+  rrtmg_sw_args b = *a;
+  b.ncol = pk.Np; b.shard_col0 = 0; b.shard_ncol = 0;
+  const size_t l = (size_t)a->nlay, l1 = l + 1;
+  // (what the driver reads under the call's icld / iaer, normalised as it normalises them; the rest stays nullptr)
+  const int icld = (a->icld < 0 || a->icld > 3) ? 2 : a->icld;
+  b.play = pk.gather("play", a->play, l); b.plev = pk.gather("plev", a->plev, l1); b.tlay = pk.gather("tlay", a->tlay, l);
+  b.tlev = nullptr; b.tsfc = nullptr;   // (the shortwave reads neither)
+  b.h2ovmr = pk.gather("h2o", a->h2ovmr, l); b.o3vmr = pk.gather("o3", a->o3vmr, l); b.co2vmr = pk.gather("co2", a->co2vmr, l);
+  b.ch4vmr = pk.gather("ch4", a->ch4vmr, l); b.n2ovmr = pk.gather("n2o", a->n2ovmr, l); b.o2vmr = pk.gather("o2", a->o2vmr, l);
+  b.asdir = pk.gather("asdir", a->asdir, 1); b.asdif = pk.gather("asdif", a->asdif, 1); b.aldir = pk.gather("aldir", a->aldir, 1);
+  b.aldif = pk.gather("aldif", a->aldif, 1);
+  b.coszen = pk.gather("coszen", a->coszen, 1, true);   // every slot: the night kernels decide from it
+  rrtmg_sw_surface sb{};
+  if (sp) { sb = *sp; sb.albdir = pk.gather("albdir", sp->albdir, kSwNBand); sb.albdif = pk.gather("albdif", sp->albdif, kSwNBand); }
+  b.cldfr = nullptr; b.taucld = b.ssacld = b.asmcld = b.fsfcld = nullptr; b.cicewp = b.cliqwp = b.reice = b.reliq = nullptr; b.cldfmcl = nullptr;
+  if (icld >= 1) {
+    b.cldfr = pk.gather("cldfr", a->cldfr, l);
+    b.cicewp = pk.gather("cicewp", a->cicewp, l); b.cliqwp = pk.gather("cliqwp", a->cliqwp, l);
+    b.reice = pk.gather("reice", a->reice, l); b.reliq = pk.gather("reliq", a->reliq, l);
+    b.taucld = pk.gather_elem("taucld", a->taucld, kSwNBand); b.ssacld = pk.gather_elem("ssacld", a->ssacld, kSwNBand);
+    b.asmcld = pk.gather_elem("asmcld", a->asmcld, kSwNBand); b.fsfcld = pk.gather_elem("fsfcld", a->fsfcld, kSwNBand);
+    if (a->mcica) b.cldfmcl = pk.gather_elem("cldfmcl", a->cldfmcl, kSwNGpt);
+  }
+  b.tauaer = b.ssaaer = b.asmaer = nullptr; b.ecaer = nullptr;
+  if (a->iaer == 10) {
+    b.tauaer = pk.gather("tauaer", a->tauaer, l * kSwNBand); b.ssaaer = pk.gather("ssaaer", a->ssaaer, l * kSwNBand);
+    b.asmaer = pk.gather("asmaer", a->asmaer, l * kSwNBand);
+  } else if (a->iaer == 6) {
+    b.ecaer = pk.gather("ecaer", a->ecaer, l * 6, true);   // sw_aer_kernel runs over the whole grid
+  }
+  if (!pk.ok) return ctx->status;
+  pk.flush_gather();
+  // the inner call's outputs, registered for the scatter in the order plain, components, bands
+  b.swuflx = pk.out("o0", u[0], l1); b.swdflx = pk.out("o1", u[1], l1); b.swhr = pk.out("o2", u[2], l);
+  b.swuflxc = pk.out("o3", u[3], l1); b.swdflxc = pk.out("o4", u[4], l1); b.swhrc = pk.out("o5", u[5], l);
+  rrtmg_sw_components cb{};
+  if (cp) {
+    cb = *cp;
+    cb.dirdflx = pk.out("c0", cp->dirdflx, l1); cb.difdflx = pk.out("c1", cp->difdflx, l1); cb.dirdnuv = pk.out("c2", cp->dirdnuv, l1);
+    cb.difdnuv = pk.out("c3", cp->difdnuv, l1); cb.dirdnir = pk.out("c4", cp->dirdnir, l1); cb.difdnir = pk.out("c5", cp->difdnir, l1);
+    cb.dirdflxc = pk.out("c6", cp->dirdflxc, l1); cb.difdflxc = pk.out("c7", cp->difdflxc, l1);
+  }
+  rrtmg_sw_band_fluxes bb{};
+  if (bp) {
+    const size_t rows = (size_t)kSwNBand * (bp->levels ? 2 : l1);
+    bb = *bp;
+    bb.up = pk.out("b0", bp->up, rows); bb.dn = pk.out("b1", bp->dn, rows); bb.upc = pk.out("b2", bp->upc, rows);
+    bb.dnc = pk.out("b3", bp->dnc, rows); bb.dndir = pk.out("b4", bp->dndir, rows); bb.dndirc = pk.out("b5", bp->dndirc, rows);
+  }
+  if (!pk.ok) return ctx->status;
+  ctx->sw_packing = true;
+  const int rc = sw_fluxes_impl(ctx, &b, sp ? &sb : nullptr, cp ? &cb : nullptr, bp ? &bb : nullptr);
+  ctx->sw_packing = false;
+  if (rc) return rc;
+  ctx->sw_pack_reported = true;
+  pk.flush_scatter((int32_t *)ctx->night_host());
+  return call_finish(c, 1, nullptr, 0, ctx->err_dev + 0);
+}
+
 int sw_fluxes_impl(rrtmg_ctx *ctx, const rrtmg_sw_args *a, const rrtmg_sw_surface *sp, const rrtmg_sw_components *cp, const rrtmg_sw_band_fluxes *bp) {
-  if (call_is_sorted(ctx, 0, a, cp || bp || sp || ctx->sw_night_skip || sw_amplitudes_differ_from_one(a))) return sw_sorted_call(ctx, a);
+  if (sw_call_is_packed(ctx, a)) return sw_packed_call(ctx, a, sp, cp, bp);
+  if (call_is_sorted(ctx, 0, a, cp || bp || sp || ctx->sw_night_skip || ctx->sw_night_pack || sw_amplitudes_differ_from_one(a))) return sw_sorted_call(ctx, a);
   int rc = call_begin(ctx, 0, a);
   if (rc) return rc;
   const CallSite c{ctx, 0, call_stream(ctx, 0, a->memspace)}; hipStream_t s = c.s;
@@ -611,13 +693,14 @@ int sw_fluxes_impl(rrtmg_ctx *ctx, const rrtmg_sw_args *a, const rrtmg_sw_surfac
   if (clouds && d.mcica) { d.mask = (uint64_t *)ctx->buf("sw.w.mask", (size_t)kSwNGpt * d.nw * N * 8); if (!d.mask) ok = false; }
   const int ntile = (N + 63) / 64;
   const int hint_cloudy = call_hint_cloudy(ctx, 0, ntile, L);
-  const bool night = ctx->sw_night_skip;   // the *_night_kernel of every launch below that has one
+  const bool night = ctx->sw_night_skip || ctx->sw_night_pack;   // the *_night_kernel of every launch below that has one (the pack: on the packed copy, and as the skip where a call is not packed)
   // The count a call with the skip leaves is of the tiles that RAN cloudy: a night tile is of neither kind.  The chunk plan
   // follows the cloudy share of the tiles that were not night in that call (its night count: a hint like the other), scaled to
   // the grid: a grid keeps the plan it has without the skip, whichever way the previous call ran.
   int plan_cloudy = hint_cloudy;
   if (hint_cloudy >= 0 && ctx->sw_night_reported) {
-    const int nn = ctx->night_host()[0], run = ntile - nn;
+    // (a packed call reports the night tiles of the caller's grid: its copy, this call's grid, has one more)
+    const int nn = ctx->night_host()[0] + (ctx->sw_packing && ctx->sw_pack_reported ? 1 : 0), run = ntile - nn;
     if (nn > 0 && run > 0 && hint_cloudy <= run) plan_cloudy = (int)((long)hint_cloudy * ntile / run);
   }
   // (work space per tile of a mixed grid's chunk: the scratch slab, and with components the direct-beam partial planes -- half
@@ -710,6 +793,9 @@ int sw_fluxes_impl(rrtmg_ctx *ctx, const rrtmg_sw_args *a, const rrtmg_sw_surfac
       else if (bp) hipLaunchKernelGGL(band_k, dim3(nt, (L + kBandLev) / kBandLev), dim3(64 * kBandLev), 0, s, d, T, t0, partdir, bo, 0);
     });
   ctx->sw_night_reported = night;   // (rrtmg_hip_sw_night_last: this call's counts, once it has completed)
+  ctx->sw_pack_reported = false;    // (sw_packed_call sets it behind its inner call)
+  // the inner call of a packed one stops here, enqueued: sw_packed_call scatters behind it and runs the epilogue
+  if (ctx->sw_packing) { RRTMG_HIP_CHECK(ctx, hipGetLastError()); return RRTMG_OK; }
 
   // ---- status + outputs -------------------------------------------------------------------
   OutCopy oc[20] = {{a->swuflx, d.swuflx, nl1}, {a->swdflx, d.swdflx, nl1}, {a->swuflxc, d.swuflxc, nl1}, {a->swdflxc, d.swdflxc, nl1},

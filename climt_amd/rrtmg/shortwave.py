@@ -183,7 +183,7 @@ class RRTMGShortwave(TendencyComponent):
                  solar_variability_method=0, use_solar_constant_from_fortran=False, ignore_day_of_year=False,
                  facular_sunspot_amplitude=None, solar_variability_by_band=None, aerosol_type="no_aerosol", mcica=False,
                  random_number_generator="mersenne_twister", device=0, flux_components=False, band_fluxes=False,
-                 spectral_surface_albedo=False, skip_night_columns=False, **kwargs):
+                 spectral_surface_albedo=False, skip_night_columns=False, pack_day_columns=False, **kwargs):
         """Same keyword arguments and defaults as climt.RRTMGShortwave (sw/component.py:179-194); the additions are `device`
         (GPU ordinal) and `flux_components`: True adds the downward flux split into direct and diffuse parts -- all bands,
         UV/visible bands, near-IR bands, and all bands clear sky (FLUX_COMPONENT_DIAGNOSTICS) -- to this instance's
@@ -195,8 +195,18 @@ class RRTMGShortwave(TendencyComponent):
         output instead of the reference's fluxes of order 1e-7 W m^-2 (its driver clamps the cosine to 1e-10 and solves), and
         does no work for 64-column tiles that are night throughout (rrtmg_hip_set_sw_night_skip; climt_amd.night.night_tiles
         states which those are); the cosine it hands over is night_coszen(): 0 from a zenith angle of pi/2 on; day columns
-        keep their bits; the class attributes are unchanged."""
+        keep their bits; `pack_day_columns`: True (requires skip_night_columns=True, else ValueError) also packs the day
+        columns into dense tiles inside the library, so that EVERY night column's solve is saved on any grid, 128 longitudes
+        included, where the skip alone finds no night tile (rrtmg_hip_set_sw_night_pack; climt_amd.night.packed_order and
+        packed_counts state the layout and what sw_night_last() reports).  Only the device-resident path packs -- a
+        climt_amd.DeviceState with kissvec or no McICA and facular_sunspot_amplitude of 1; a host state, radiation_step's
+        joint call and every other call run as with skip_night_columns alone.  The night columns' zeros are the same; a day
+        column's bits are those of a call on the day columns alone (see the header for when they differ from the whole
+        grid's, by at most 1e-10); the class attributes are unchanged."""
+        if pack_day_columns and not skip_night_columns:
+            raise ValueError("pack_day_columns=True requires skip_night_columns=True")
         self._skip_night = bool(skip_night_columns)
+        self._pack_day = bool(pack_day_columns)
         self._spectral_albedo = bool(spectral_surface_albedo)
         if self._spectral_albedo:
             self.input_properties = self.input_properties_for(True)
@@ -266,6 +276,11 @@ class RRTMGShortwave(TendencyComponent):
             setter(self._skip_night)
         elif self._skip_night:
             raise RuntimeError("skip_night_columns=True: this context has no set_sw_night_skip")
+        pack, setter = getattr(self, "_pack_day", False), getattr(ctx, "set_sw_night_pack", None)
+        if setter is not None and (pack or getattr(ctx, "has_sw_night_pack", True)):
+            setter(pack)
+        elif pack:
+            raise RuntimeError("pack_day_columns=True: this context has no set_sw_night_pack")
 
     def __call__(self, state, *args, **kwargs):
         """A host state goes through sympl's machinery to array_call; a climt_amd.DeviceState (state resident in HBM) takes

@@ -146,8 +146,38 @@ int rrtmg_hip_set_column_sort(rrtmg_ctx *ctx, int on);
  * shares one context between callers sets it before each shortwave call.  Probe for it by symbol; the argument structs and
  * RRTMG_HIP_ABI_VERSION are unchanged. */
 int rrtmg_hip_set_sw_night_skip(rrtmg_ctx *ctx, int on);
+/* OPT-IN day-column pack of the shortwave (off by default; with it off nothing changes, and the reference-compatible symbols
+ * on the default context never have it): the night-column skip for grids whose tiles are all mixed.  An ELIGIBLE call runs on
+ * an internal copy of its inputs in which the day columns come first, in the caller's order, padded to a 64-column tile
+ * boundary with replicas of the last of them, and the night columns follow: no tile holds both kinds, and every tile behind
+ * the day block costs no preparation and no solve time, on any grid and in any column order.  The outputs are scattered back
+ * to the caller's columns on the device.  The output contract is the skip's: a night column (coszen <= 0 as passed; NaN is
+ * day) gets +0.0 in every output -- the six arrays, every requested component, every requested band row -- whether or not
+ * rrtmg_hip_set_sw_night_skip is also on.
+ *  - Eligible: device pointers (memspace 1), more than 64 columns (at least two tiles), kissvec or no McICA, amplitudes
+ *    indsolvar equal to 1 (or NULL).  The Mersenne twister's one stream and rescaled amplitudes are positional, so such calls
+ *    are not packed.  HOST-POINTER CALLS (memspace 0, rrtmg_hip_radiation_fluxes included) ARE NOT PACKED in this version.  A
+ *    call that is not eligible runs exactly as with rrtmg_hip_set_sw_night_skip(ctx, 1): the tile skip's bits, its counts in
+ *    rrtmg_hip_sw_night_last, indsolvar rescaled as always.  Components, band fluxes and the surface struct all run packed.
+ *    With the option on no call is column-sorted (rrtmg_hip_set_column_sort).
+ *  - Bits: a day column's outputs are, bit for bit, those of a call with the skip off on the day columns alone, in the same
+ *    order (ncol = number of day columns).  Against the call with the skip off on the WHOLE grid this means: where every tile
+ *    runs one solve variant (icld = 0, or a cloud in every column) day columns keep their bits; in a grid with cloudy and
+ *    cloud-free columns a cloudy day column keeps its bits, and a cloud-free day column may change solve variant, because its
+ *    tile has other members: it stays within 1e-10 W m^-2 (K d^-1) of the unpacked result (the variants differ by ~1e-12, the
+ *    column sort's caveat).  The same caveat applies to shard == whole grid: a shard packs its own day columns.
+ *  - Status codes: a night column's inputs other than coszen are never read or checked (but ecaer under iaer = 6, whose
+ *    whole-grid pass raises no code); a day column's bad input raises the code it raises with the skip off, and the context
+ *    stays usable.
+ *  - rrtmg_hip_sw_night_last after a packed call: night_columns = ncol - day columns; night_tiles = ceil(ncol / 64) -
+ *    ceil(day columns / 64), the tiles' worth of solve work not done.
+ *  - Cost: three small launches for the column map, one gather launch for all inputs (one more for band-fastest cloud arrays),
+ *    one scatter launch for all outputs, and an internal copy of inputs and outputs of 64 x (ceil(ncol / 64) + 1) columns.
+ * Probe for it by symbol; the argument structs and RRTMG_HIP_ABI_VERSION are unchanged. */
+int rrtmg_hip_set_sw_night_pack(rrtmg_ctx *ctx, int on);
 /* Night tiles and night columns (all of them: those of mixed tiles too) of the last completed shortwave call on this context:
- * valid after the call has returned, in deferred mode after rrtmg_hip_synchronize.  0 / 0 if that call ran with the skip off.
+ * valid after the call has returned, in deferred mode after rrtmg_hip_synchronize.  0 / 0 if that call ran with the skip off
+ * (and the pack off); after a packed call (rrtmg_hip_set_sw_night_pack) the counts stated there.
  * night_tiles * 64 columns of the call's (ncol + 63) / 64 * 64 cost no solve time. */
 int rrtmg_hip_sw_night_last(rrtmg_ctx *ctx, int *night_tiles, int *night_columns);
 /* Duration (ms, HIP events recorded on the stream the kernel is launched on) of a solve kernel in the last completed call:
