@@ -1,25 +1,25 @@
 // rrtmg_call.h -- the host steps that a shortwave and a longwave flux call have in common (private to rrtmg_sw.hip and
 // rrtmg_lw.hip; host code only: no kernel lives here, and the kernels launched here are those of rrtmg_mcica_kernels.h).
-// In the order of a call: the gate to the sorted call and that call's head and tail, the argument checks, the call's stream,
-// the optional output tables, the chunk plan, the error flag, the McICA mask, the chunk loop, the epilogue.  The drivers keep
+// In the order of a call: the gate to the sorted call, the argument checks, the call's stream, the optional output tables, the
+// chunk plan, the error flag, the McICA mask, the chunk loop, the epilogue, the tail of a permuted call.  The drivers keep
 // what differs: their inputs, work buffers and the kernels of every launch stage with their geometry.
 // which: 0 shortwave, 1 longwave -- the index of rrtmg_ctx::hint, plans, pending, kiss_* and of the err_dev slot.
 #pragma once
 #include "rrtmg_ctx.h"
 #include "rrtmg_mcica_kernels.h"
-#include "rrtmg_sort.h"
+#include "rrtmg_permute.h"
 
 namespace rrtmg {
 
 struct CallSite { rrtmg_ctx *ctx; int which; hipStream_t s; };
 // ---- entry gate ---------------------------------------------------------------------------------------------------------------
 inline bool spectrum_ready(const rrtmg_ctx *ctx, int which) { return which == 0 ? ctx->sw_ready : ctx->lw_ready; }
-// The call runs as *_sorted_call (rrtmg_sort.h): opt-in, device pointers, clouds, at least two tiles, kissvec or no McICA, and not
+// The call runs sorted (rrtmg_permute.h): opt-in, device pointers, clouds, at least two tiles, kissvec or no McICA, and not
 // the inner call itself.  excluded: what the spectrum never sorts (outputs that would need a scatter, inputs a gather, of their own;
 // in the shortwave a second positional input besides the twister's stream: amplitudes indsolvar != 1, rescaled once per column)
 template <class Args>
 inline bool call_is_sorted(const rrtmg_ctx *ctx, int which, const Args *a, bool excluded) {
-  return !excluded && spectrum_ready(ctx, which) && a && ctx->sort_columns && !ctx->sorting && a->memspace == 1 && a->icld != 0 && a->cldfr && a->ncol >= 128 && a->nlay > 0 && a->nlay <= 256 && !(a->mcica && a->irng != 0);
+  return !excluded && spectrum_ready(ctx, which) && a && ctx->sort_columns && ctx->inner == kInnerNone && a->memspace == 1 && a->icld != 0 && a->cldfr && a->ncol >= 128 && a->nlay > 0 && a->nlay <= 256 && !(a->mcica && a->irng != 0);
 }
 // the four argument checks every call makes, then the device (hipSetDevice, and the streams and flags where they do not exist yet)
 template <class Args>
@@ -42,29 +42,6 @@ inline int check_outputs(rrtmg_ctx *ctx, double *const *o) {
 inline hipStream_t call_stream(const rrtmg_ctx *ctx, int which, int memspace) { return (which == 1 && (ctx->joint || (ctx->deferred && memspace == 1))) ? ctx->stream_lw : ctx->stream; }
 // the table of a joint call's inputs for HostInputs, or nullptr
 inline ShareTable *call_share(const rrtmg_ctx *ctx) { return ctx->joint ? &ctx->joint->table : nullptr; }
-// ---- the sorted call: head and tail (the gather lists are the spectrum's own) ---------------------------------------------------
-// head: the device, the column map on the call's stream (a sorted call is device-resident), b = the call on the padded copy
-template <class Args>
-inline int sorted_head(rrtmg_ctx *ctx, int which, const Args *a, ColumnSort &cs, Args &b) {
-  if (int rc = ctx_prepare_device(ctx)) return rc;
-  cs.s = call_stream(ctx, which, 1);
-  if (!cs.prepare(a->cldfr)) return ctx->status;
-  b = *a; b.ncol = cs.Np; b.shard_col0 = 0; b.shard_ncol = 0;
-  return RRTMG_OK;
-}
-// tail: the inner call, the scatter of its nout outputs o -> the caller's u ([2] and [5], the heating rates, have nlay rows)
-template <class Inner>
-inline int sorted_tail(rrtmg_ctx *ctx, ColumnSort &cs, int nout, double *const *o, double *const *u, Inner inner) {
-  ctx->sorting = true;
-  const int rc = inner();
-  ctx->sorting = false;
-  if (rc) return rc;
-  const size_t l = (size_t)cs.L, l1 = l + 1;
-  for (int k = 0; k < nout; ++k) cs.scatter(o[k], u[k], (k == 2 || k == 5) ? l : l1);
-  RRTMG_HIP_CHECK(ctx, hipGetLastError());
-  if (!ctx->deferred) RRTMG_HIP_CHECK(ctx, hipStreamSynchronize(cs.s));
-  return RRTMG_OK;
-}
 // ---- optional output tables (shortwave components and bands, longwave bands) ---------------------------------------------------
 // One row per member: the work buffer's name, the caller's array (nullptr: not requested, the kernel skips it), the member of
 // the kernel's output struct.  The device array is the caller's pointer under memspace 1, else the named work buffer (wd: the
@@ -93,7 +70,7 @@ inline int plan_call_chunks(rrtmg_ctx *ctx, int which, Dev &d, bool clouds, int 
   int chunk_tiles = ctx->chunk_tiles;
   if (ctx->chunk_auto && L > 80 && plan_cloudy >= 0 && 10 * plan_cloudy >= 9 * ntile) chunk_tiles = 64;   // deep cloudy grid: DESIGN.md 5
   // (a sorted grid keeps the small chunks: its tiles are segregated by kind, every chunk but one is of one kind)
-  chunk_tiles = ctx->plan_chunks(which, chunk_tiles, ntile, L, (clouds && !ctx->sorting) ? plan_cloudy : -1, tile_bytes, which == 0 ? "sw.w.scratch" : "lw.w.scratch");
+  chunk_tiles = ctx->plan_chunks(which, chunk_tiles, ntile, L, (clouds && ctx->inner != kInnerSorted) ? plan_cloudy : -1, tile_bytes, which == 0 ? "sw.w.scratch" : "lw.w.scratch");
   const int ctile = ntile < chunk_tiles ? ntile : chunk_tiles;
   int32_t *tlist = (int32_t *)ctx->buf(which == 0 ? "sw.w.tilelist" : "lw.w.tilelist", (size_t)(2 * ctile + 2) * 4);
   d.tcap = ctile; d.tlist = tlist; d.tcnt = tlist ? tlist + 2 * d.tcap : nullptr;
@@ -140,7 +117,7 @@ inline int mcica_mask_launch(const CallSite &c, int ngpt, const Dev &d, const Ar
 // solve variants, each bracketed here by the event pair chunk_event(which | which + 2, chunk, side) of rrtmg_hip_kernel_ms;
 // after(t0, nt) -- the integration launches, which find d.hint_out set in the call's last chunk.
 // The variant expected to find nothing goes first, and the cloudy one is launched only with clouds (order is speed only: each tile
-// belongs to exactly one of them).  A sorted grid -- rrtmg_sort.h -- has its cloud-free tiles first: the chunks in front of the
+// belongs to exactly one of them).  A sorted grid -- rrtmg_permute.h -- has its cloud-free tiles first: the chunks in front of the
 // previous call's cloudy-tile count (hint_cloudy) are expected to hold no cloudy tile.
 template <class Dev, class Before, class Clear, class Cloudy, class After>
 inline void run_chunks(const CallSite &c, Dev &d, bool clouds, int hint_cloudy, Before before, Clear clear, Cloudy cloudy, After after) {
@@ -151,7 +128,7 @@ inline void run_chunks(const CallSite &c, Dev &d, bool clouds, int hint_cloudy, 
     d.col0 = t0 * 64; d.pcols = ctile * 64;
     before(t0, nt);
     auto variant = [&](int k, auto &launch) { (void)hipEventRecord(ctx->chunk_event(k, ci, 0), c.s); launch(t0, nt); (void)hipEventRecord(ctx->chunk_event(k, ci, 1), c.s); };
-    const bool expect_clear = clouds && hint_cloudy >= 0 && (hint_cloudy == 0 || (ctx->sorting && t0 + nt <= ntile - hint_cloudy));
+    const bool expect_clear = clouds && hint_cloudy >= 0 && (hint_cloudy == 0 || (ctx->inner == kInnerSorted && t0 + nt <= ntile - hint_cloudy));
     if (expect_clear) { variant(w + 2, cloudy); variant(w, clear); }
     else { variant(w, clear); if (clouds) variant(w + 2, cloudy); }
     d.hint_out = t0 + ctile >= ntile ? (int32_t *)&ctx->hint[w].ncloudy : nullptr;
@@ -183,6 +160,20 @@ inline int call_finish(const CallSite &c, int memspace, const OutCopy *oc, int n
   if (herr) return spectrum_fail(ctx, c.which, herr);
   ctx->status = 0;
   return RRTMG_OK;
+}
+// ---- the permuted call (rrtmg_permute.h: sorted or packed; the gather and output lists are the spectrum's own) -------------------
+// inner(): the spectrum's driver on the copy, which returns once it is enqueued (it finds ctx->inner set).  Behind it ONE
+// scatter launch for every output registered with pm -- which also leaves the counts of rrtmg_hip_sw_night_last where
+// night_out is given -- and the one epilogue: a permuted call is device-resident, so only the flag is read.
+template <class Inner>
+inline int permuted_tail(const CallSite &c, ColumnPermute &pm, Inner inner, int32_t *night_out = nullptr) {
+  rrtmg_ctx *ctx = c.ctx;
+  ctx->inner = pm.kind;
+  const int rc = inner();
+  ctx->inner = kInnerNone;
+  if (rc) return rc;
+  pm.flush_scatter(night_out);
+  return call_finish(c, 1, nullptr, 0, ctx->err_dev + c.which);
 }
 // ---- the joint call: both spectra of one host state in one call -----------------------------------------------------------------
 // sw(), lw(): the two drivers on their checked arguments.  While ctx->joint is set they differ from separate calls in three

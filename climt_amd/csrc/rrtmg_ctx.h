@@ -29,6 +29,11 @@ struct DevBuf {
 
 struct JointCall;   // rrtmg_hip_radiation_fluxes in progress (below)
 
+// What a call is to the permuted call around it (rrtmg_permute.h): not inside one, or the inner call -- the ordinary driver on
+// the internal copy -- of a sorted or of a packed call.  An inner call does not enter the gates again and stops once it is
+// enqueued: the permuted call scatters behind it and runs the one epilogue.
+enum InnerCall { kInnerNone, kInnerSorted, kInnerPacked };
+
 }  // namespace rrtmg
 
 struct rrtmg_ctx {
@@ -98,11 +103,10 @@ struct rrtmg_ctx {
   // hint is; sw_night_reported: the last enqueued shortwave call had the skip on (else rrtmg_hip_sw_night_last reports 0 / 0)
   bool sw_night_skip = false, sw_night_reported = false;
   volatile int *night_host() const { return hint ? (volatile int *)(hint + 2) : nullptr; }
-  // rrtmg_hip_set_sw_night_pack (rrtmg_pack.h): an eligible device-resident shortwave call runs on an internal copy with the day
-  // columns packed into dense tiles, any other call as with the skip on.  sw_packing: this is the inner call of a packed one (it
-  // does not enter the gate again, runs the night kernels and leaves the epilogue to the packed call); sw_pack_reported: the
-  // last enqueued shortwave call was packed (its night count is that of the caller's grid, one tile less than the copy's)
-  bool sw_night_pack = false, sw_packing = false, sw_pack_reported = false;
+  // rrtmg_hip_set_sw_night_pack (rrtmg_permute.h): an eligible device-resident shortwave call runs on an internal copy with the
+  // day columns packed into dense tiles, any other call as with the skip on.  sw_pack_reported: the last enqueued shortwave call
+  // was packed (its night count is that of the caller's grid, one tile less than the copy's)
+  bool sw_night_pack = false, sw_pack_reported = false;
   // KISS jump-ahead operators [sw|lw]: host copy, the key they were built for, the device buffer they were uploaded to
   std::vector<uint32_t> kiss_host[2][2];   // two staging copies per spectrum: a rebuild never waits for the previous upload
   hipEvent_t kiss_ev[2][2] = {{nullptr, nullptr}, {nullptr, nullptr}};   // recorded after the upload from kiss_host[w][k]
@@ -121,9 +125,10 @@ struct rrtmg_ctx {
     if (big_lds[slot] < 0) big_lds[slot] = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes) == hipSuccess ? 1 : 0;
     return big_lds[slot] > 0;
   }
-  // rrtmg_hip_set_column_sort (rrtmg_sort.h): device-resident calls with clouds run on an internal copy of their inputs, cloud-free
-  // columns first; `sorting` = this is the inner call
-  bool sort_columns = false, sorting = false;
+  // rrtmg_hip_set_column_sort (rrtmg_permute.h): device-resident calls with clouds run on an internal copy of their inputs,
+  // cloud-free columns first
+  bool sort_columns = false;
+  rrtmg::InnerCall inner = rrtmg::kInnerNone;   // the call being enqueued is the inner call of a sorted / packed one
   std::string err;
   int status = 0;
   rrtmg::Constants k{};

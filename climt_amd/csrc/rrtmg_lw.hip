@@ -197,33 +197,39 @@ int lw_init_impl(rrtmg_ctx *ctx, double cpdair, const char *blob_path) {
   return RRTMG_OK;
 }
 
-// the call on an internal copy of its inputs, cloud-free columns first (rrtmg_sort.h; see sw_sorted_call)
+// the call on an internal copy of its inputs, cloud-free columns first (rrtmg_permute.h; see sw_permuted_call): what the driver
+// reads with clouds (the gate has icld != 0), the optional arrays where they are given
 static int lw_sorted_call(rrtmg_ctx *ctx, const rrtmg_lw_args *a) {
-  ColumnSort cs(ctx, nullptr, a->ncol, a->nlay, "lw.sort.");
-  rrtmg_lw_args b;
-  if (int rc = sorted_head(ctx, 1, a, cs, b)) return rc;
-  const size_t l = (size_t)a->nlay, l1 = l + 1;
-  b.play = cs.gather("play", a->play, l); b.plev = cs.gather("plev", a->plev, l1); b.tlay = cs.gather("tlay", a->tlay, l);
-  b.tlev = cs.gather("tlev", a->tlev, l1); b.tsfc = cs.gather("tsfc", a->tsfc, 1);
-  b.h2ovmr = cs.gather("h2o", a->h2ovmr, l); b.o3vmr = cs.gather("o3", a->o3vmr, l); b.co2vmr = cs.gather("co2", a->co2vmr, l);
-  b.ch4vmr = cs.gather("ch4", a->ch4vmr, l); b.n2ovmr = cs.gather("n2o", a->n2ovmr, l); b.o2vmr = cs.gather("o2", a->o2vmr, l);
-  b.cfc11vmr = cs.gather("cfc11", a->cfc11vmr, l); b.cfc12vmr = cs.gather("cfc12", a->cfc12vmr, l);
-  b.cfc22vmr = cs.gather("cfc22", a->cfc22vmr, l); b.ccl4vmr = cs.gather("ccl4", a->ccl4vmr, l);
-  b.emis = cs.gather("emis", a->emis, 16);
-  b.cldfr = cs.gather("cldfr", a->cldfr, l); b.taucld = cs.gather("taucld", a->taucld, l, 16);
-  b.cicewp = cs.gather("cicewp", a->cicewp, l); b.cliqwp = cs.gather("cliqwp", a->cliqwp, l);
-  b.reice = cs.gather("reice", a->reice, l); b.reliq = cs.gather("reliq", a->reliq, l);
-  b.tauaer = cs.gather("tauaer", a->tauaer, l * 16);
-  b.cldfmcl = cs.gather("cldfmcl", a->cldfmcl, l, kLwNGpt);
+  if (int rc = ctx_prepare_device(ctx)) return rc;
+  const CallSite c{ctx, 1, call_stream(ctx, 1, 1)};
   const bool dr = a->idrv != 0;
-  double *o[8] = {cs.out("o0", l1), cs.out("o1", l1), cs.out("o2", l), cs.out("o3", l1), cs.out("o4", l1), cs.out("o5", l),
-                  dr ? cs.out("o6", l1) : nullptr, dr ? cs.out("o7", l1) : nullptr};
-  if (!cs.ok) return ctx->status;
-  double *u[8] = {a->uflx, a->dflx, a->hr, a->uflxc, a->dflxc, a->hrc, a->duflx_dt, a->duflxc_dt};
+  double *const u[6] = {a->uflx, a->dflx, a->hr, a->uflxc, a->dflxc, a->hrc};
   if (int rc = check_outputs(ctx, u)) return rc;
   if (dr && (!a->duflx_dt || !a->duflxc_dt)) return ctx->fail(RRTMG_ERR_ARG, "idrv=1 needs duflx_dt/duflxc_dt");
-  b.uflx = o[0]; b.dflx = o[1]; b.hr = o[2]; b.uflxc = o[3]; b.dflxc = o[4]; b.hrc = o[5]; b.duflx_dt = o[6]; b.duflxc_dt = o[7];
-  return sorted_tail(ctx, cs, dr ? 8 : 6, o, u, [&]() { return lw_fluxes_impl(ctx, &b); });
+  ColumnPermute pm(ctx, c.s, kInnerSorted, a->ncol, a->nlay, "lw.sort.");
+  if (!pm.prepare(a->cldfr)) return ctx->status;
+  rrtmg_lw_args b = *a;
+  b.ncol = pm.Np; b.shard_col0 = 0; b.shard_ncol = 0;
+  const size_t l = (size_t)a->nlay, l1 = l + 1;
+  b.play = pm.gather("play", a->play, l); b.plev = pm.gather("plev", a->plev, l1); b.tlay = pm.gather("tlay", a->tlay, l);
+  b.tlev = pm.gather("tlev", a->tlev, l1); b.tsfc = pm.gather("tsfc", a->tsfc, 1);
+  b.h2ovmr = pm.gather("h2o", a->h2ovmr, l); b.o3vmr = pm.gather("o3", a->o3vmr, l); b.co2vmr = pm.gather("co2", a->co2vmr, l);
+  b.ch4vmr = pm.gather("ch4", a->ch4vmr, l); b.n2ovmr = pm.gather("n2o", a->n2ovmr, l); b.o2vmr = pm.gather("o2", a->o2vmr, l);
+  b.cfc11vmr = pm.gather("cfc11", a->cfc11vmr, l); b.cfc12vmr = pm.gather("cfc12", a->cfc12vmr, l);
+  b.cfc22vmr = pm.gather("cfc22", a->cfc22vmr, l); b.ccl4vmr = pm.gather("ccl4", a->ccl4vmr, l);
+  b.emis = pm.gather("emis", a->emis, 16);
+  b.cldfr = pm.gather("cldfr", a->cldfr, l); b.taucld = pm.gather_elem("taucld", a->taucld, 16);
+  b.cicewp = pm.gather("cicewp", a->cicewp, l); b.cliqwp = pm.gather("cliqwp", a->cliqwp, l);
+  b.reice = pm.gather("reice", a->reice, l); b.reliq = pm.gather("reliq", a->reliq, l);
+  b.tauaer = pm.gather("tauaer", a->tauaer, l * 16);
+  b.cldfmcl = a->mcica ? pm.gather_elem("cldfmcl", a->cldfmcl, kLwNGpt) : nullptr;
+  if (!pm.ok) return ctx->status;
+  pm.flush_gather();
+  b.uflx = pm.out("o0", u[0], l1); b.dflx = pm.out("o1", u[1], l1); b.hr = pm.out("o2", u[2], l);
+  b.uflxc = pm.out("o3", u[3], l1); b.dflxc = pm.out("o4", u[4], l1); b.hrc = pm.out("o5", u[5], l);
+  b.duflx_dt = dr ? pm.out("o6", a->duflx_dt, l1) : nullptr; b.duflxc_dt = dr ? pm.out("o7", a->duflxc_dt, l1) : nullptr;
+  if (!pm.ok) return ctx->status;
+  return permuted_tail(c, pm, [&]() { return lw_fluxes_impl(ctx, &b); });
 }
 
 // bp: the band fluxes requested (at least one member set, levels 0 or 1), or nullptr for the plain call.  A call with bands
@@ -369,6 +375,8 @@ int lw_fluxes_impl(rrtmg_ctx *ctx, const rrtmg_lw_args *a, const rrtmg_lw_band_f
     fprintf(stderr, "; up sweep per layer %.0f\n", ph[6] / w / L);
   }
 #endif
+  // the inner call of a sorted one stops here, enqueued: permuted_tail scatters behind it and runs the epilogue
+  if (ctx->inner != kInnerNone) { RRTMG_HIP_CHECK(ctx, hipGetLastError()); return RRTMG_OK; }
   OutCopy oc[12] = {{a->uflx, d.uflx, nl1}, {a->dflx, d.dflx, nl1}, {a->uflxc, d.uflxc, nl1}, {a->dflxc, d.dflxc, nl1},
                     {a->hr, d.hr, nl}, {a->hrc, d.hrc, nl}, {a->duflx_dt, d.duflx_dt, nl1}, {a->duflxc_dt, d.duflxc_dt, nl1}};
   return call_finish(c, a->memspace, oc, opt_out_append(bpt, 4, nband, oc, d.idrv ? 8 : 6), d.err);   // the requested band fluxes behind the same synchronise

@@ -25,12 +25,12 @@
 //   With the night-column skip on (rrtmg_hip_set_sw_night_skip): sw_kiss_mask_night_kernel, sw_prep_fused_night_kernel,
 //   sw_cloud_night_kernel, sw_tile_lists_night_kernel and sw_{fluxheat,components,bandflux}_night_kernel in the places of their
 //   namesakes; the solve kernels are the same and find a night tile in neither of their lists
-//   With the day-column pack on (rrtmg_hip_set_sw_night_pack; rrtmg_pack.h), around the sequence above with the night kernels on
-//   an internal copy: pack_count_kernel, pack_scan_kernel, pack_map_kernel, pack_gather_kernel (+ pack_gather_elem_kernel for
-//   band-fastest cloud arrays) in front, pack_scatter_kernel behind
+//   A permuted call (rrtmg_permute.h) -- with the column sort on (rrtmg_hip_set_column_sort), or with the day-column pack on
+//   (rrtmg_hip_set_sw_night_pack): then with the night kernels -- runs the sequence above on an internal copy, around it:
+//   permute_class_kernel, permute_scan_kernel, permute_map_kernel, permute_gather_kernel (+ permute_gather_elem_kernel for
+//   band-fastest cloud arrays) in front, permute_scatter_kernel behind
 // The host steps this call shares with the longwave's (gate, checks, chunk plan and loop, mask choice, epilogue): rrtmg_call.h
 #include "rrtmg_call.h"
-#include "rrtmg_pack.h"
 #include "rrtmg_sw_device.h"
 #include "rrtmg_sw_host.h"
 
@@ -493,34 +493,6 @@ int sw_init_impl(rrtmg_ctx *ctx, double cpdair, const char *blob_path) {
   return RRTMG_OK;
 }
 
-// the call on an internal copy of its inputs, cloud-free columns first (rrtmg_sort.h; opt-in, device pointers, kissvec or no McICA)
-static int sw_sorted_call(rrtmg_ctx *ctx, const rrtmg_sw_args *a) {
-  ColumnSort cs(ctx, nullptr, a->ncol, a->nlay, "sw.sort.");
-  rrtmg_sw_args b;
-  if (int rc = sorted_head(ctx, 0, a, cs, b)) return rc;
-  const size_t l = (size_t)a->nlay, l1 = l + 1;
-  b.play = cs.gather("play", a->play, l); b.plev = cs.gather("plev", a->plev, l1); b.tlay = cs.gather("tlay", a->tlay, l);
-  b.tlev = nullptr; b.tsfc = nullptr;   // (the shortwave reads neither)
-  b.h2ovmr = cs.gather("h2o", a->h2ovmr, l); b.o3vmr = cs.gather("o3", a->o3vmr, l); b.co2vmr = cs.gather("co2", a->co2vmr, l);
-  b.ch4vmr = cs.gather("ch4", a->ch4vmr, l); b.n2ovmr = cs.gather("n2o", a->n2ovmr, l); b.o2vmr = cs.gather("o2", a->o2vmr, l);
-  b.asdir = cs.gather("asdir", a->asdir, 1); b.asdif = cs.gather("asdif", a->asdif, 1); b.aldir = cs.gather("aldir", a->aldir, 1);
-  b.aldif = cs.gather("aldif", a->aldif, 1); b.coszen = cs.gather("coszen", a->coszen, 1);
-  b.cldfr = cs.gather("cldfr", a->cldfr, l);
-  b.taucld = cs.gather("taucld", a->taucld, l, kSwNBand); b.ssacld = cs.gather("ssacld", a->ssacld, l, kSwNBand);
-  b.asmcld = cs.gather("asmcld", a->asmcld, l, kSwNBand); b.fsfcld = cs.gather("fsfcld", a->fsfcld, l, kSwNBand);
-  b.cicewp = cs.gather("cicewp", a->cicewp, l); b.cliqwp = cs.gather("cliqwp", a->cliqwp, l);
-  b.reice = cs.gather("reice", a->reice, l); b.reliq = cs.gather("reliq", a->reliq, l);
-  b.tauaer = cs.gather("tauaer", a->tauaer, l * kSwNBand); b.ssaaer = cs.gather("ssaaer", a->ssaaer, l * kSwNBand);
-  b.asmaer = cs.gather("asmaer", a->asmaer, l * kSwNBand); b.ecaer = cs.gather("ecaer", a->ecaer, l * 6);
-  b.cldfmcl = cs.gather("cldfmcl", a->cldfmcl, l, kSwNGpt);
-  double *o[6] = {cs.out("o0", l1), cs.out("o1", l1), cs.out("o2", l), cs.out("o3", l1), cs.out("o4", l1), cs.out("o5", l)};
-  if (!cs.ok) return ctx->status;
-  double *u[6] = {a->swuflx, a->swdflx, a->swhr, a->swuflxc, a->swdflxc, a->swhrc};
-  if (int rc = check_outputs(ctx, u)) return rc;
-  b.swuflx = o[0]; b.swdflx = o[1]; b.swhr = o[2]; b.swuflxc = o[3]; b.swdflxc = o[4]; b.swhrc = o[5];
-  return sorted_tail(ctx, cs, 6, o, u, [&]() { return sw_fluxes_impl(ctx, &b); });
-}
-
 // cp: the components requested (at least one member set), or nullptr; bp: the band fluxes requested (at least one member
 // set, levels 0 or 1), or nullptr; sp: the surface albedo by band (at least one member set), or nullptr; all nullptr: the
 // plain call.  A call with components or bands is never sorted: its outputs would need a scatter of their own; nor is one with
@@ -530,86 +502,87 @@ static int sw_sorted_call(rrtmg_ctx *ctx, const rrtmg_sw_args *a) {
 // stream, and the inner call on the padded copy would hand each column another column's multipliers and rescale the caller's
 // IN/OUT array once per padded slot.
 static bool sw_amplitudes_differ_from_one(const rrtmg_sw_args *a) { return a && a->indsolvar && (a->indsolvar[0] != 1.0 || a->indsolvar[1] != 1.0); }
-// The call runs packed (rrtmg_pack.h): opt-in, device pointers, at least two tiles, kissvec or no McICA, amplitudes indsolvar
-// equal to 1 (the twister's stream and the rescaled amplitudes are positional), not half of a joint call and not the inner
+// The call runs packed (rrtmg_permute.h): opt-in, device pointers, at least two tiles, kissvec or no McICA, amplitudes indsolvar
+// equal to 1 (the twister's stream and the rescaled amplitudes are positional), not half of a joint call and not an inner
 // call itself.  Any other call with the option on runs as with the night-column skip on.
 static bool sw_call_is_packed(const rrtmg_ctx *ctx, const rrtmg_sw_args *a) {
-  return ctx->sw_night_pack && !ctx->sw_packing && !ctx->sorting && !ctx->joint && ctx->sw_ready && a && a->memspace == 1 && a->coszen && a->ncol > 64 &&
+  return ctx->sw_night_pack && ctx->inner == kInnerNone && !ctx->joint && ctx->sw_ready && a && a->memspace == 1 && a->coszen && a->ncol > 64 &&
          a->nlay > 0 && a->nlay <= 256 && !(a->mcica && a->irng != 0) && !sw_amplitudes_differ_from_one(a);
 }
-// The packed call: the column map from coszen, ONE gather launch for the [rows][N] inputs (one more for the band-fastest cloud
-// arrays where they are given), the ordinary driver with the night kernels on the copy of Np slots, ONE scatter launch for
-// every requested output, which also leaves the counts of rrtmg_hip_sw_night_last, then the epilogue the inner call skipped.
-// Components, bands and the surface struct ride along: their rows are entries of the same two tables.
-static int sw_packed_call(rrtmg_ctx *ctx, const rrtmg_sw_args *a, const rrtmg_sw_surface *sp, const rrtmg_sw_components *cp, const rrtmg_sw_band_fluxes *bp) {
-  if (int rc = call_begin(ctx, 0, a)) return rc;
+// The permuted call, kind = sorted | packed: the column map from cldfr | coszen, ONE gather launch for the [rows][N] inputs (one
+// more for the band-fastest cloud arrays where they are given), the ordinary driver on the copy of Np slots (packed: with the
+// night kernels), ONE scatter launch for every requested output (packed: it also leaves the counts of
+// rrtmg_hip_sw_night_last), then the epilogue the inner call left out.  Components, bands and the surface struct ride along
+// where the gate lets them through (the sort's never does): their rows are entries of the same two tables.
+static int sw_permuted_call(rrtmg_ctx *ctx, InnerCall kind, const rrtmg_sw_args *a, const rrtmg_sw_surface *sp, const rrtmg_sw_components *cp, const rrtmg_sw_band_fluxes *bp) {
+  const bool packed = kind == kInnerPacked;
+  // (the sorted call has never checked the shard arguments: its inner call, kissvec or no McICA, does not read them)
+  if (int rc = packed ? call_begin(ctx, 0, a) : ctx_prepare_device(ctx)) return rc;
   const CallSite c{ctx, 0, call_stream(ctx, 0, 1)};
-  DayPack pk(ctx, c.s, a->ncol, a->nlay);
   double *const u[6] = {a->swuflx, a->swdflx, a->swhr, a->swuflxc, a->swdflxc, a->swhrc};
   if (int rc = check_outputs(ctx, u)) return rc;
-  if (!pk.prepare(a->coszen)) return ctx->status;
+  ColumnPermute pm(ctx, c.s, kind, a->ncol, a->nlay, packed ? "sw.pack." : "sw.sort.");
+  if (!pm.prepare(packed ? a->coszen : a->cldfr)) return ctx->status;
   rrtmg_sw_args b = *a;
-  b.ncol = pk.Np; b.shard_col0 = 0; b.shard_ncol = 0;
+  b.ncol = pm.Np; b.shard_col0 = 0; b.shard_ncol = 0;
   const size_t l = (size_t)a->nlay, l1 = l + 1;
   // (what the driver reads under the call's icld / iaer, normalised as it normalises them; the rest stays nullptr)
   const int icld = (a->icld < 0 || a->icld > 3) ? 2 : a->icld;
-  b.play = pk.gather("play", a->play, l); b.plev = pk.gather("plev", a->plev, l1); b.tlay = pk.gather("tlay", a->tlay, l);
+  b.play = pm.gather("play", a->play, l); b.plev = pm.gather("plev", a->plev, l1); b.tlay = pm.gather("tlay", a->tlay, l);
   b.tlev = nullptr; b.tsfc = nullptr;   // (the shortwave reads neither)
-  b.h2ovmr = pk.gather("h2o", a->h2ovmr, l); b.o3vmr = pk.gather("o3", a->o3vmr, l); b.co2vmr = pk.gather("co2", a->co2vmr, l);
-  b.ch4vmr = pk.gather("ch4", a->ch4vmr, l); b.n2ovmr = pk.gather("n2o", a->n2ovmr, l); b.o2vmr = pk.gather("o2", a->o2vmr, l);
-  b.asdir = pk.gather("asdir", a->asdir, 1); b.asdif = pk.gather("asdif", a->asdif, 1); b.aldir = pk.gather("aldir", a->aldir, 1);
-  b.aldif = pk.gather("aldif", a->aldif, 1);
-  b.coszen = pk.gather("coszen", a->coszen, 1, true);   // every slot: the night kernels decide from it
+  b.h2ovmr = pm.gather("h2o", a->h2ovmr, l); b.o3vmr = pm.gather("o3", a->o3vmr, l); b.co2vmr = pm.gather("co2", a->co2vmr, l);
+  b.ch4vmr = pm.gather("ch4", a->ch4vmr, l); b.n2ovmr = pm.gather("n2o", a->n2ovmr, l); b.o2vmr = pm.gather("o2", a->o2vmr, l);
+  b.asdir = pm.gather("asdir", a->asdir, 1); b.asdif = pm.gather("asdif", a->asdif, 1); b.aldir = pm.gather("aldir", a->aldir, 1);
+  b.aldif = pm.gather("aldif", a->aldif, 1);
+  b.coszen = pm.gather("coszen", a->coszen, 1, true);   // every slot: the night kernels decide from it
   rrtmg_sw_surface sb{};
-  if (sp) { sb = *sp; sb.albdir = pk.gather("albdir", sp->albdir, kSwNBand); sb.albdif = pk.gather("albdif", sp->albdif, kSwNBand); }
+  if (sp) { sb = *sp; sb.albdir = pm.gather("albdir", sp->albdir, kSwNBand); sb.albdif = pm.gather("albdif", sp->albdif, kSwNBand); }
   b.cldfr = nullptr; b.taucld = b.ssacld = b.asmcld = b.fsfcld = nullptr; b.cicewp = b.cliqwp = b.reice = b.reliq = nullptr; b.cldfmcl = nullptr;
   if (icld >= 1) {
-    b.cldfr = pk.gather("cldfr", a->cldfr, l);
-    b.cicewp = pk.gather("cicewp", a->cicewp, l); b.cliqwp = pk.gather("cliqwp", a->cliqwp, l);
-    b.reice = pk.gather("reice", a->reice, l); b.reliq = pk.gather("reliq", a->reliq, l);
-    b.taucld = pk.gather_elem("taucld", a->taucld, kSwNBand); b.ssacld = pk.gather_elem("ssacld", a->ssacld, kSwNBand);
-    b.asmcld = pk.gather_elem("asmcld", a->asmcld, kSwNBand); b.fsfcld = pk.gather_elem("fsfcld", a->fsfcld, kSwNBand);
-    if (a->mcica) b.cldfmcl = pk.gather_elem("cldfmcl", a->cldfmcl, kSwNGpt);
+    b.cldfr = pm.gather("cldfr", a->cldfr, l);
+    b.cicewp = pm.gather("cicewp", a->cicewp, l); b.cliqwp = pm.gather("cliqwp", a->cliqwp, l);
+    b.reice = pm.gather("reice", a->reice, l); b.reliq = pm.gather("reliq", a->reliq, l);
+    b.taucld = pm.gather_elem("taucld", a->taucld, kSwNBand); b.ssacld = pm.gather_elem("ssacld", a->ssacld, kSwNBand);
+    b.asmcld = pm.gather_elem("asmcld", a->asmcld, kSwNBand); b.fsfcld = pm.gather_elem("fsfcld", a->fsfcld, kSwNBand);
+    if (a->mcica) b.cldfmcl = pm.gather_elem("cldfmcl", a->cldfmcl, kSwNGpt);
   }
   b.tauaer = b.ssaaer = b.asmaer = nullptr; b.ecaer = nullptr;
   if (a->iaer == 10) {
-    b.tauaer = pk.gather("tauaer", a->tauaer, l * kSwNBand); b.ssaaer = pk.gather("ssaaer", a->ssaaer, l * kSwNBand);
-    b.asmaer = pk.gather("asmaer", a->asmaer, l * kSwNBand);
+    b.tauaer = pm.gather("tauaer", a->tauaer, l * kSwNBand); b.ssaaer = pm.gather("ssaaer", a->ssaaer, l * kSwNBand);
+    b.asmaer = pm.gather("asmaer", a->asmaer, l * kSwNBand);
   } else if (a->iaer == 6) {
-    b.ecaer = pk.gather("ecaer", a->ecaer, l * 6, true);   // sw_aer_kernel runs over the whole grid
+    b.ecaer = pm.gather("ecaer", a->ecaer, l * 6, true);   // sw_aer_kernel runs over the whole grid
   }
-  if (!pk.ok) return ctx->status;
-  pk.flush_gather();
+  if (!pm.ok) return ctx->status;
+  pm.flush_gather();
   // the inner call's outputs, registered for the scatter in the order plain, components, bands
-  b.swuflx = pk.out("o0", u[0], l1); b.swdflx = pk.out("o1", u[1], l1); b.swhr = pk.out("o2", u[2], l);
-  b.swuflxc = pk.out("o3", u[3], l1); b.swdflxc = pk.out("o4", u[4], l1); b.swhrc = pk.out("o5", u[5], l);
+  b.swuflx = pm.out("o0", u[0], l1); b.swdflx = pm.out("o1", u[1], l1); b.swhr = pm.out("o2", u[2], l);
+  b.swuflxc = pm.out("o3", u[3], l1); b.swdflxc = pm.out("o4", u[4], l1); b.swhrc = pm.out("o5", u[5], l);
   rrtmg_sw_components cb{};
   if (cp) {
     cb = *cp;
-    cb.dirdflx = pk.out("c0", cp->dirdflx, l1); cb.difdflx = pk.out("c1", cp->difdflx, l1); cb.dirdnuv = pk.out("c2", cp->dirdnuv, l1);
-    cb.difdnuv = pk.out("c3", cp->difdnuv, l1); cb.dirdnir = pk.out("c4", cp->dirdnir, l1); cb.difdnir = pk.out("c5", cp->difdnir, l1);
-    cb.dirdflxc = pk.out("c6", cp->dirdflxc, l1); cb.difdflxc = pk.out("c7", cp->difdflxc, l1);
+    cb.dirdflx = pm.out("c0", cp->dirdflx, l1); cb.difdflx = pm.out("c1", cp->difdflx, l1); cb.dirdnuv = pm.out("c2", cp->dirdnuv, l1);
+    cb.difdnuv = pm.out("c3", cp->difdnuv, l1); cb.dirdnir = pm.out("c4", cp->dirdnir, l1); cb.difdnir = pm.out("c5", cp->difdnir, l1);
+    cb.dirdflxc = pm.out("c6", cp->dirdflxc, l1); cb.difdflxc = pm.out("c7", cp->difdflxc, l1);
   }
   rrtmg_sw_band_fluxes bb{};
   if (bp) {
     const size_t rows = (size_t)kSwNBand * (bp->levels ? 2 : l1);
     bb = *bp;
-    bb.up = pk.out("b0", bp->up, rows); bb.dn = pk.out("b1", bp->dn, rows); bb.upc = pk.out("b2", bp->upc, rows);
-    bb.dnc = pk.out("b3", bp->dnc, rows); bb.dndir = pk.out("b4", bp->dndir, rows); bb.dndirc = pk.out("b5", bp->dndirc, rows);
+    bb.up = pm.out("b0", bp->up, rows); bb.dn = pm.out("b1", bp->dn, rows); bb.upc = pm.out("b2", bp->upc, rows);
+    bb.dnc = pm.out("b3", bp->dnc, rows); bb.dndir = pm.out("b4", bp->dndir, rows); bb.dndirc = pm.out("b5", bp->dndirc, rows);
   }
-  if (!pk.ok) return ctx->status;
-  ctx->sw_packing = true;
-  const int rc = sw_fluxes_impl(ctx, &b, sp ? &sb : nullptr, cp ? &cb : nullptr, bp ? &bb : nullptr);
-  ctx->sw_packing = false;
-  if (rc) return rc;
-  ctx->sw_pack_reported = true;
-  pk.flush_scatter((int32_t *)ctx->night_host());
-  return call_finish(c, 1, nullptr, 0, ctx->err_dev + 0);
+  if (!pm.ok) return ctx->status;
+  return permuted_tail(c, pm, [&]() {
+    const int rc = sw_fluxes_impl(ctx, &b, sp ? &sb : nullptr, cp ? &cb : nullptr, bp ? &bb : nullptr);
+    if (!rc && packed) ctx->sw_pack_reported = true;
+    return rc;
+  }, packed ? (int32_t *)ctx->night_host() : nullptr);
 }
 
 int sw_fluxes_impl(rrtmg_ctx *ctx, const rrtmg_sw_args *a, const rrtmg_sw_surface *sp, const rrtmg_sw_components *cp, const rrtmg_sw_band_fluxes *bp) {
-  if (sw_call_is_packed(ctx, a)) return sw_packed_call(ctx, a, sp, cp, bp);
-  if (call_is_sorted(ctx, 0, a, cp || bp || sp || ctx->sw_night_skip || ctx->sw_night_pack || sw_amplitudes_differ_from_one(a))) return sw_sorted_call(ctx, a);
+  if (sw_call_is_packed(ctx, a)) return sw_permuted_call(ctx, kInnerPacked, a, sp, cp, bp);
+  if (call_is_sorted(ctx, 0, a, cp || bp || sp || ctx->sw_night_skip || ctx->sw_night_pack || sw_amplitudes_differ_from_one(a))) return sw_permuted_call(ctx, kInnerSorted, a, nullptr, nullptr, nullptr);
   int rc = call_begin(ctx, 0, a);
   if (rc) return rc;
   const CallSite c{ctx, 0, call_stream(ctx, 0, a->memspace)}; hipStream_t s = c.s;
@@ -700,7 +673,7 @@ int sw_fluxes_impl(rrtmg_ctx *ctx, const rrtmg_sw_args *a, const rrtmg_sw_surfac
   int plan_cloudy = hint_cloudy;
   if (hint_cloudy >= 0 && ctx->sw_night_reported) {
     // (a packed call reports the night tiles of the caller's grid: its copy, this call's grid, has one more)
-    const int nn = ctx->night_host()[0] + (ctx->sw_packing && ctx->sw_pack_reported ? 1 : 0), run = ntile - nn;
+    const int nn = ctx->night_host()[0] + (ctx->inner == kInnerPacked && ctx->sw_pack_reported ? 1 : 0), run = ntile - nn;
     if (nn > 0 && run > 0 && hint_cloudy <= run) plan_cloudy = (int)((long)hint_cloudy * ntile / run);
   }
   // (work space per tile of a mixed grid's chunk: the scratch slab, and with components the direct-beam partial planes -- half
@@ -793,9 +766,9 @@ int sw_fluxes_impl(rrtmg_ctx *ctx, const rrtmg_sw_args *a, const rrtmg_sw_surfac
       else if (bp) hipLaunchKernelGGL(band_k, dim3(nt, (L + kBandLev) / kBandLev), dim3(64 * kBandLev), 0, s, d, T, t0, partdir, bo, 0);
     });
   ctx->sw_night_reported = night;   // (rrtmg_hip_sw_night_last: this call's counts, once it has completed)
-  ctx->sw_pack_reported = false;    // (sw_packed_call sets it behind its inner call)
-  // the inner call of a packed one stops here, enqueued: sw_packed_call scatters behind it and runs the epilogue
-  if (ctx->sw_packing) { RRTMG_HIP_CHECK(ctx, hipGetLastError()); return RRTMG_OK; }
+  ctx->sw_pack_reported = false;    // (sw_permuted_call sets it behind the inner call of a packed one)
+  // the inner call of a permuted one stops here, enqueued: permuted_tail scatters behind it and runs the epilogue
+  if (ctx->inner != kInnerNone) { RRTMG_HIP_CHECK(ctx, hipGetLastError()); return RRTMG_OK; }
 
   // ---- status + outputs -------------------------------------------------------------------
   OutCopy oc[20] = {{a->swuflx, d.swuflx, nl1}, {a->swdflx, d.swdflx, nl1}, {a->swuflxc, d.swuflxc, nl1}, {a->swdflxc, d.swdflxc, nl1},

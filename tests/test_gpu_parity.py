@@ -1373,7 +1373,7 @@ def test_copy_blocks_kernel_unpacks_a_three_rank_gather(gpu_ctx):
 
 @pytest.mark.parametrize("mcica", [True, False])
 def test_opt_in_column_sort_keeps_cloudy_columns_bits_and_moves_cloud_free_ones_to_the_clear_sky_variant(gpu_ctx, mcica):
-    """rrtmg_hip_set_column_sort (csrc/rrtmg_sort.h): a device-resident call runs on an internal copy of its inputs,
+    """rrtmg_hip_set_column_sort (csrc/rrtmg_permute.h): a device-resident call runs on an internal copy of its inputs,
     cloud-free columns first.  Columns are independent and kissvec seeds per column: (i) a cloudy column gets the same BITS as
     without the sort; (ii) a cloud-free column now runs in the clear-sky variant -- the same bits as in a call that holds
     cloud-free columns only, and within 1e-10 W m^-2 of the unsorted call (the variants' clear-sky streams differ by ~1e-12 in

@@ -1,6 +1,10 @@
 """CPU tests of the numpy statements of the shortwave's day-column pack (climt_amd.night.packed_order / packed_counts:
 rrtmg_hip_set_sw_night_pack, RRTMGShortwave(pack_day_columns=True)), checked by hand on tiny fields, and of the component's
-constructor check.  The kernels are tested against these statements in tests/test_night_pack_gpu.py."""
+constructor check.  The kernels are tested against these statements in tests/test_night_pack_gpu.py; the slot rule they use
+(csrc/rrtmg_permute.h) is checked against the same hand-written fields by tools/permute_check.cpp, built and run here."""
+import os
+import subprocess
+
 import numpy as np
 import pytest
 
@@ -98,3 +102,11 @@ def test_component_requires_the_skip():
         RRTMGShortwave(pack_day_columns=True)
     with pytest.raises(ValueError, match="skip_night_columns"):
         RRTMGShortwave(pack_day_columns=True, skip_night_columns=False)
+
+
+def test_permute_check_program(tmp_path):
+    """tools/permute_check.cpp -- the library's own slot rule, head and table builder on the CPU -- compiles and reports ok."""
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    exe = str(tmp_path / "permute_check")
+    subprocess.check_call(["c++", "-std=c++17", "-O1", os.path.join(root, "tools", "permute_check.cpp"), "-o", exe])
+    assert subprocess.run([exe], capture_output=True, text=True, check=True).stdout.strip() == "ok"
