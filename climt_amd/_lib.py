@@ -191,6 +191,8 @@ def load_library():
         lib.rrtmg_hip_sw_night_last.argtypes = [_vp, C.POINTER(C.c_int), C.POINTER(C.c_int)]
     if hasattr(lib, "rrtmg_hip_set_sw_night_pack"):      # (likewise)
         lib.rrtmg_hip_set_sw_night_pack.argtypes = [_vp, C.c_int]
+    if hasattr(lib, "rrtmg_hip_set_sw_clear_sky"):       # (likewise)
+        lib.rrtmg_hip_set_sw_clear_sky.argtypes = [_vp, C.c_int]
     if hasattr(lib, "rrtmg_hip_radiation_fluxes"):       # (likewise)
         lib.rrtmg_hip_radiation_fluxes.argtypes = [_vp, C.POINTER(RadiationCall)]
         lib.rrtmg_hip_radiation_last.argtypes = [_vp, C.POINTER(C.c_int), C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]
@@ -218,6 +220,7 @@ _SW_FLAGS = dict(icld="icld", iaer="iaer", inflg="inflgsw", iceflg="iceflgsw", l
 _LW_FLAGS = dict(icld="icld", idrv="idrv", inflg="inflglw", iceflg="iceflglw", liqflg="liqflglw", irng="irng",
                  permuteseed="permuteseed", shard_col0="shard_col0", shard_ncol="shard_ncol")
 SW_OUT = (("swuflx", 1), ("swdflx", 1), ("swhr", 0), ("swuflxc", 1), ("swdflxc", 1), ("swhrc", 0))
+SW_OUT_ALLSKY = ("swuflx", "swdflx", "swhr")      # what a call fills after Context.set_sw_clear_sky(False)
 LW_OUT = (("uflx", 1), ("dflx", 1), ("hr", 0), ("uflxc", 1), ("dflxc", 1), ("hrc", 0))
 
 
@@ -438,6 +441,21 @@ class Context:
         runs as with set_sw_night_skip(True).  Night columns get exact zeros either way."""
         self._ck(self.lib.rrtmg_hip_set_sw_night_pack(self.h, 1 if on else 0))
 
+    @property
+    def has_sw_clear_sky(self):
+        return hasattr(self.lib, "rrtmg_hip_set_sw_clear_sky")
+
+    @_locked
+    def set_sw_clear_sky(self, on=True):
+        """Clear-sky outputs of the shortwave (rrtmg_hip_set_sw_clear_sky; on by default).  Off: a shortwave call forms no
+        clear-sky stream -- tiles with cloud run a one-stream solve -- and swuflxc, swdflxc and swhrc are neither computed nor
+        copied: `out` may leave them out (or hold None), and what it holds for them is not touched.  Calls with components or
+        bands are refused while it is off."""
+        if not self.has_sw_clear_sky:
+            raise RRTMGError(4, "this librrtmg_hip.so has no rrtmg_hip_set_sw_clear_sky (shortwave call without the clear-sky outputs)")
+        self._ck(self.lib.rrtmg_hip_set_sw_clear_sky(self.h, 1 if on else 0))
+        self.sw_clear_sky = bool(on)
+
     @_locked
     def sw_night_last(self):
         """-> (night tiles, night columns) of the last completed shortwave call (in deferred mode: after synchronize());
@@ -506,11 +524,13 @@ class Context:
         a.icld, a.inflgsw, a.iceflgsw, a.liqflgsw, a.dyofyr = 1, 2, 1, 1, 1
         a.adjes, a.scon, a.solcycfrac = float(inp.get("adjes", 1.0)), float(inp.get("scon", 1367.0)), float(inp.get("solcycfrac", 0.0))
         self._fill(a, inp, _SW_FIELDS, _SW_FLAGS, keep)
+        clear = getattr(self, "sw_clear_sky", True)      # (set_sw_clear_sky(False): the three clear-sky outputs may be absent -> NULL)
         if out is None:
-            out = {k: np.zeros((nlay + lev, ncol)) for k, lev in SW_OUT}
+            out = {k: np.zeros((nlay + lev, ncol)) for k, lev in SW_OUT if clear or k in SW_OUT_ALLSKY}
         for k, _ in SW_OUT:
-            v = out[k]
-            setattr(a, k, int(v) if isinstance(v, (int, np.integer)) else v.ctypes.data)
+            v = out[k] if clear or k in SW_OUT_ALLSKY else out.get(k)
+            if v is not None:
+                setattr(a, k, int(v) if isinstance(v, (int, np.integer)) else v.ctypes.data)
         if surface is None and (inp.get("albdir") is not None or inp.get("albdif") is not None):
             surface = {k: inp.get(k) for k in SW_SURFACE}
         b = None if bands is None else _band_struct(SwBandFluxes, SW_BAND_FLUXES, SW_NBAND, bands, band_levels, nlay, ncol)

@@ -30,9 +30,9 @@ inline int call_begin(rrtmg_ctx *ctx, int which, const Args *a) {
   if (a->shard_ncol != 0 && (a->shard_col0 < 0 || a->shard_col0 + a->ncol > a->shard_ncol)) return ctx->fail(RRTMG_ERR_ARG, "shard_col0/shard_ncol do not contain ncol columns");
   return ctx_prepare_device(ctx);
 }
-// o: the six outputs every call has
-inline int check_outputs(rrtmg_ctx *ctx, double *const *o) {
-  for (int k = 0; k < 6; ++k)
+// o: the six outputs every call has (n = 3: a shortwave call without its clear-sky outputs looks at the first three)
+inline int check_outputs(rrtmg_ctx *ctx, double *const *o, int n = 6) {
+  for (int k = 0; k < n; ++k)
     if (!o[k]) return ctx->fail(RRTMG_ERR_ARG, "output array is NULL");
   return RRTMG_OK;
 }

@@ -107,6 +107,9 @@ struct rrtmg_ctx {
   // day columns packed into dense tiles, any other call as with the skip on.  sw_pack_reported: the last enqueued shortwave call
   // was packed (its night count is that of the caller's grid, one tile less than the copy's)
   bool sw_night_pack = false, sw_pack_reported = false;
+  // rrtmg_hip_set_sw_clear_sky: false = a shortwave call forms no clear-sky stream and writes, reads and copies none of swuflxc,
+  // swdflxc, swhrc (rrtmg_sw.hip: sw_solve_cloudy_allsky_kernel, sw_fluxheat_allsky_kernel)
+  bool sw_clear_sky = true;
   // KISS jump-ahead operators [sw|lw]: host copy, the key they were built for, the device buffer they were uploaded to
   std::vector<uint32_t> kiss_host[2][2];   // two staging copies per spectrum: a rebuild never waits for the previous upload
   hipEvent_t kiss_ev[2][2] = {{nullptr, nullptr}, {nullptr, nullptr}};   // recorded after the upload from kiss_host[w][k]

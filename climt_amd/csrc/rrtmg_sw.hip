@@ -29,6 +29,9 @@
 //   (rrtmg_hip_set_sw_night_pack): then with the night kernels -- runs the sequence above on an internal copy, around it:
 //   permute_class_kernel, permute_scan_kernel, permute_map_kernel, permute_gather_kernel (+ permute_gather_elem_kernel for
 //   band-fastest cloud arrays) in front, permute_scatter_kernel behind
+//   With the clear-sky outputs off (rrtmg_hip_set_sw_clear_sky(0)): sw_solve_cloudy_allsky_kernel in the place of
+//   sw_solve_cloudy_kernel and sw_fluxheat_allsky_kernel<night> in the place of sw_fluxheat[_night]_kernel; swuflxc, swdflxc and
+//   swhrc are neither formed nor copied
 // The host steps this call shares with the longwave's (gate, checks, chunk plan and loop, mask choice, epilogue): rrtmg_call.h
 #include "rrtmg_call.h"
 #include "rrtmg_sw_device.h"
@@ -429,6 +432,76 @@ __global__ void __launch_bounds__(64 * kBandLev) sw_bandflux_night_kernel(SwDev 
   sw_band_level(d, T, partdir, o, col, lev, row, nrow, d.tile_cld[tile] != 0);
 }
 
+// ---- No clear-sky outputs (rrtmg_hip_set_sw_clear_sky(0); opt-in) ----------------------------------------------------------------
+// Kernels of their own, launched INSTEAD of sw_solve_cloudy_kernel and sw_fluxheat[_night]_kernel when the clear-sky outputs are
+// off: with them on the launch sequence and every kernel in it are those of a library without the option (tools/isa_compare.py,
+// profiles/isa_compare_allsky_only.txt).  The cloudy tiles run sw_solve_thread's ONE mode: the total-sky stream alone, two partial
+// planes per slot like a cloud-free tile, the F_RUP / F_RUPD rows of the scratch slab.  Cloud-free tiles run sw_solve_all_kernel<false>
+// as ever.  Tile list, launch order and LDS staging: sw_solve_cloudy_kernel's.  Workgroup shape: kAsWaves wavefronts at kAsWaves / 4 per
+// SIMD (RRTMG_ALLSKY_WAVES, 8, 12 or 16: DESIGN.md 5 has them measured).
+#ifndef RRTMG_ALLSKY_WAVES
+#define RRTMG_ALLSKY_WAVES 8
+#endif
+constexpr int kAsWaves = RRTMG_ALLSKY_WAVES;
+constexpr int kAsGroupsPerBlock = (128 + kAsWaves - 1) / kAsWaves;   // 128 tiles per block of the launch order (12 waves: 132)
+static_assert(kAsWaves == 8 || kAsWaves == 12 || kAsWaves == 16, "RRTMG_ALLSKY_WAVES: 8 (2 waves per SIMD), 12 (3) or 16 (4)");
+__global__ void __launch_bounds__(64 * kAsWaves) __attribute__((amdgpu_waves_per_eu(kAsWaves / 4, kAsWaves / 4))) sw_solve_cloudy_allsky_kernel(SwDev d, SwTab T, int tile0, int ntile) {
+  const int nmine = d.tcnt[1];   // the cloudy tiles, compacted (SwDev::tlist); the workgroups with work first and dense: see sw_solve_all_kernel
+  const int ngrp = (nmine + kAsWaves - 1) / kAsWaves;
+  const int q = blockIdx.x, per = kAsGroupsPerBlock * T.nitem, nfull = ngrp / kAsGroupsPerBlock;      // blocks of 128 tiles
+  if (q >= ngrp * T.nitem) return;
+  const int gpb = q < nfull * per ? kAsGroupsPerBlock : ngrp - nfull * kAsGroupsPerBlock, r = q < nfull * per ? q % per : q - nfull * per;
+  const int grp = (q < nfull * per ? q / per : nfull) * kAsGroupsPerBlock + r % gpb, first = grp * kAsWaves, k = r / gpb;
+  RRTMG_PROFILE_ONLY_ITEM(d, k)
+  const int id = T.sched[k], item = T.item[id], slot = id;      // one slot per chunk
+  __shared__ __attribute__((aligned(16))) double sh_k[kSwSlabMaxRows * 4];
+  sw_stage_slice(T, item, sh_k, 64 * kAsWaves);
+  __shared__ double sh_exp[kExpTblN];
+  for (int i = threadIdx.x; i < kExpTblN; i += 64 * kAsWaves) sh_exp[i] = T.t[T.exp_tbl + i];
+  __syncthreads();
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  if (first + wave >= nmine) return;
+  const int ctile = d.tlist[d.tcap + first + wave], tile = tile0 + ctile;
+  const int lane = threadIdx.x & 63;
+  const int col = tile * 64 + lane;
+  if (col >= d.ncol) return;
+  double *scr = d.scratch + ((long)ctile * kSwNGpt + item_iw0(item)) * (long)F_NTOT * d.nlay * 64 + lane * 2;
+  SwPartSink sink = sw_part_sink(d, slot, col);
+  sw_solve_item<true, true, true>(d, T, sh_exp, item, col, scr, 64, sink, sh_k);
+}
+// sw_fluxheat_kernel without the clear-sky half: two planes per slot in EVERY tile (sw_flux_sums with cld = false), the sums,
+// differences and stores of swuflx, swdflx and swhr as there.  NIGHT: sw_fluxheat_night_kernel's column rule and counts.
+template <bool NIGHT>
+__global__ void __launch_bounds__(64 * (kFluxLev + 1)) sw_fluxheat_allsky_kernel(SwDev d, SwTab T, int tile0, int32_t *night_cnt, int32_t *night_out) {
+  if (blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) {
+    if (d.hint_out) { *d.hint_out = *d.ncloudy; *d.ncloudy = 0; }
+    if (NIGHT && night_out) { night_out[0] = night_cnt[0]; night_out[1] = night_cnt[1]; night_cnt[0] = 0; night_cnt[1] = 0; }
+  }
+  const int tile = tile0 + blockIdx.x, lane = threadIdx.x & 63, j = threadIdx.x >> 6;
+  const int col = tile * 64 + lane, lev = blockIdx.y * kFluxLev + j;
+  __shared__ double net[kFluxLev + 1][64];
+  const bool in = col < d.ncol && lev <= d.nlay;
+  const bool dark = NIGHT && col < d.ncol && d.coszen[col] <= 0.0;
+  if (in && !dark) {
+    double fu, fd, cu, cd;
+    sw_flux_sums(d, T, col, lev, false, fu, fd, cu, cd);
+    if (j < kFluxLev || lev == d.nlay) {
+      const long o = (long)lev * d.ncol + col;
+      d.swuflx[o] = fu; d.swdflx[o] = fd;
+    }
+    net[j][lane] = fd - fu;
+  } else if (in && (j < kFluxLev || lev == d.nlay)) {
+    const long o = (long)lev * d.ncol + col;
+    d.swuflx[o] = 0.0; d.swdflx[o] = 0.0;
+  }
+  __syncthreads();
+  if (col < d.ncol && j < kFluxLev && lev < d.nlay) {
+    const long o0 = (long)lev * d.ncol + col;
+    if (dark) d.swhr[o0] = 0.0;
+    else d.swhr[o0] = (net[j + 1][lane] - net[j][lane]) * (T.heatfac / d.pdp[o0]);
+  }
+}
+
 void free_sw_desc(rrtmg_ctx *ctx) {
   delete (SwTab *)ctx->sw_desc;
   ctx->sw_desc = nullptr;
@@ -519,8 +592,10 @@ static int sw_permuted_call(rrtmg_ctx *ctx, InnerCall kind, const rrtmg_sw_args 
   // (the sorted call has never checked the shard arguments: its inner call, kissvec or no McICA, does not read them)
   if (int rc = packed ? call_begin(ctx, 0, a) : ctx_prepare_device(ctx)) return rc;
   const CallSite c{ctx, 0, call_stream(ctx, 0, 1)};
-  double *const u[6] = {a->swuflx, a->swdflx, a->swhr, a->swuflxc, a->swdflxc, a->swhrc};
-  if (int rc = check_outputs(ctx, u)) return rc;
+  // (clear-sky outputs off: the three are absent from the scatter table, and from the inner call)
+  const bool clr = ctx->sw_clear_sky;
+  double *const u[6] = {a->swuflx, a->swdflx, a->swhr, clr ? a->swuflxc : nullptr, clr ? a->swdflxc : nullptr, clr ? a->swhrc : nullptr};
+  if (int rc = check_outputs(ctx, u, clr ? 6 : 3)) return rc;
   ColumnPermute pm(ctx, c.s, kind, a->ncol, a->nlay, packed ? "sw.pack." : "sw.sort.");
   if (!pm.prepare(packed ? a->coszen : a->cldfr)) return ctx->status;
   rrtmg_sw_args b = *a;
@@ -581,6 +656,8 @@ static int sw_permuted_call(rrtmg_ctx *ctx, InnerCall kind, const rrtmg_sw_args 
 }
 
 int sw_fluxes_impl(rrtmg_ctx *ctx, const rrtmg_sw_args *a, const rrtmg_sw_surface *sp, const rrtmg_sw_components *cp, const rrtmg_sw_band_fluxes *bp) {
+  const bool clr = ctx->sw_clear_sky;   // rrtmg_hip_set_sw_clear_sky: false = swuflxc, swdflxc and swhrc are neither formed nor read from `a`
+  if (!clr && (cp || bp)) return ctx->fail(RRTMG_ERR_ARG, "shortwave flux components and band fluxes need the clear-sky stream: rrtmg_hip_set_sw_clear_sky(ctx, 0) is in force (set it to 1 for this call)");
   if (sw_call_is_packed(ctx, a)) return sw_permuted_call(ctx, kInnerPacked, a, sp, cp, bp);
   if (call_is_sorted(ctx, 0, a, cp || bp || sp || ctx->sw_night_skip || ctx->sw_night_pack || sw_amplitudes_differ_from_one(a))) return sw_permuted_call(ctx, kInnerSorted, a, nullptr, nullptr, nullptr);
   int rc = call_begin(ctx, 0, a);
@@ -706,14 +783,17 @@ int sw_fluxes_impl(rrtmg_ctx *ctx, const rrtmg_sw_args *a, const rrtmg_sw_surfac
     RRTMG_HIP_CHECK(ctx, hipStreamSynchronize(s));   // svar_col is a local
     d.svar_col = p;
   }
+  // (clear-sky outputs off: d.swuflxc, d.swdflxc and d.swhrc stay nullptr -- no kernel of that path dereferences them)
   if (a->memspace == 1) {
-    d.swuflx = a->swuflx; d.swdflx = a->swdflx; d.swhr = a->swhr; d.swuflxc = a->swuflxc; d.swdflxc = a->swdflxc; d.swhrc = a->swhrc;
+    d.swuflx = a->swuflx; d.swdflx = a->swdflx; d.swhr = a->swhr;
+    if (clr) { d.swuflxc = a->swuflxc; d.swdflxc = a->swdflxc; d.swhrc = a->swhrc; }
   } else {
-    d.swuflx = wd("o.uflx", nl1); d.swdflx = wd("o.dflx", nl1); d.swhr = wd("o.hr", nl); d.swuflxc = wd("o.uflxc", nl1); d.swdflxc = wd("o.dflxc", nl1); d.swhrc = wd("o.hrc", nl);
+    d.swuflx = wd("o.uflx", nl1); d.swdflx = wd("o.dflx", nl1); d.swhr = wd("o.hr", nl);
+    if (clr) { d.swuflxc = wd("o.uflxc", nl1); d.swdflxc = wd("o.dflxc", nl1); d.swhrc = wd("o.hrc", nl); }
   }
   if (!ok) return ctx->status;
   double *const u[6] = {a->swuflx, a->swdflx, a->swhr, a->swuflxc, a->swdflxc, a->swhrc};
-  if ((rc = check_outputs(ctx, u)) || (rc = call_own_flag(c, a->memspace, d))) return rc;
+  if ((rc = check_outputs(ctx, u, clr ? 6 : 3)) || (rc = call_own_flag(c, a->memspace, d))) return rc;
 
   // ---- launches ---------------------------------------------------------------------------
   const dim3 gcl(ntile, L), blk(64);
@@ -737,7 +817,7 @@ int sw_fluxes_impl(rrtmg_ctx *ctx, const rrtmg_sw_args *a, const rrtmg_sw_surfac
   const auto lists_k = night ? sw_tile_lists_night_kernel : tile_lists_kernel;
   const auto comp_k = night ? sw_components_night_kernel : sw_components_kernel;
   const auto band_k = night ? sw_bandflux_night_kernel : sw_bandflux_kernel;
-  const dim3 bprep(64 * kPrepWaves), wg(64 * kSwWgWaves), bc(64 * kC4Waves), bfl(64 * (kFluxLev + 1));
+  const dim3 bprep(64 * kPrepWaves), wg(64 * kSwWgWaves), bc(64 * kC4Waves), bas(64 * kAsWaves), bfl(64 * (kFluxLev + 1));
   const size_t lds_prep = (size_t)L * 64 * sizeof(int);
   const int prep_clouds = clouds && !d.mcica ? 1 : 0;
   run_chunks(c, d, clouds, hint_cloudy,
@@ -754,12 +834,15 @@ int sw_fluxes_impl(rrtmg_ctx *ctx, const rrtmg_sw_args *a, const rrtmg_sw_surfac
     },
     [&](int t0, int nt) {
       const dim3 gc((nt + kC4Waves - 1) / kC4Waves * T.nitem);
-      if (partdir) hipLaunchKernelGGL(sw_solve_cloudy_dir_kernel, gc, bc, 0, s, d, T, t0, nt, partdir);
+      if (!clr) hipLaunchKernelGGL(sw_solve_cloudy_allsky_kernel, dim3((nt + kAsWaves - 1) / kAsWaves * T.nitem), bas, 0, s, d, T, t0, nt);
+      else if (partdir) hipLaunchKernelGGL(sw_solve_cloudy_dir_kernel, gc, bc, 0, s, d, T, t0, nt, partdir);
       else hipLaunchKernelGGL(sw_solve_cloudy_kernel, gc, bc, 0, s, d, T, t0, nt);
     },
     [&](int t0, int nt) {
       const dim3 gfl(nt, (L + kFluxLev) / kFluxLev);
-      if (night) hipLaunchKernelGGL(sw_fluxheat_night_kernel, gfl, bfl, 0, s, d, T, t0, night_cnt, d.hint_out ? (int32_t *)ctx->night_host() : nullptr);
+      if (!clr && night) hipLaunchKernelGGL(sw_fluxheat_allsky_kernel<true>, gfl, bfl, 0, s, d, T, t0, night_cnt, d.hint_out ? (int32_t *)ctx->night_host() : nullptr);
+      else if (!clr) hipLaunchKernelGGL(sw_fluxheat_allsky_kernel<false>, gfl, bfl, 0, s, d, T, t0, (int32_t *)nullptr, (int32_t *)nullptr);
+      else if (night) hipLaunchKernelGGL(sw_fluxheat_night_kernel, gfl, bfl, 0, s, d, T, t0, night_cnt, d.hint_out ? (int32_t *)ctx->night_host() : nullptr);
       else hipLaunchKernelGGL(sw_fluxheat_kernel, gfl, bfl, 0, s, d, T, t0);
       if (cp) hipLaunchKernelGGL(comp_k, dim3(nt, (L + kCompLev) / kCompLev), dim3(64 * kCompLev), 0, s, d, T, t0, partdir, co);
       if (bp && bp->levels) hipLaunchKernelGGL(band_k, dim3(nt, 1), dim3(64 * 2), 0, s, d, T, t0, partdir, bo, 1);
@@ -773,6 +856,10 @@ int sw_fluxes_impl(rrtmg_ctx *ctx, const rrtmg_sw_args *a, const rrtmg_sw_surfac
   // ---- status + outputs -------------------------------------------------------------------
   OutCopy oc[20] = {{a->swuflx, d.swuflx, nl1}, {a->swdflx, d.swdflx, nl1}, {a->swuflxc, d.swuflxc, nl1}, {a->swdflxc, d.swdflxc, nl1},
                     {a->swhr, d.swhr, nl}, {a->swhrc, d.swhrc, nl}};
+  if (!clr) {   // three downloads, not six (neither components nor bands: refused above)
+    const OutCopy oa[3] = {{a->swuflx, d.swuflx, nl1}, {a->swdflx, d.swdflx, nl1}, {a->swhr, d.swhr, nl}};
+    return call_finish(c, a->memspace, oa, 3, d.err);
+  }
   const int nout = opt_out_append(bpt, 6, nband, oc, opt_out_append(cpt, 8, nl1, oc, 6));   // components, then bands: behind the same synchronise
   return call_finish(c, a->memspace, oc, nout, d.err);
 }

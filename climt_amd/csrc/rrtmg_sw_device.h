@@ -940,7 +940,11 @@ template <int G> struct SwThreadCtx {
 // five more level arrays per g-point through HBM (profiles/r01_pmc_*.txt).
 // consume(g, clear, total) is called for each g-point right after its optics are ready, so that only ONE g-point's
 // ten layer operators are live at a time (register pressure).
-template <int BAND, int G, bool CLD, bool LDSK, class Consume>
+// ONE (rrtmg_hip_set_sw_clear_sky(0): no clear-sky outputs; CLD = true only): consume(g, op, op) receives ONE operator per
+// g-point, the total-sky one -- the clear-sky operator in a (sub-)column without cloud, as the CLD code passes it for both.  Where
+// McICA's mask bit is set the cloud operators REPLACE the clear ones, so the clear-sky sw_reftra is not evaluated there (its
+// inputs ztauc / zomcc / zgcc still are: the cloud mix starts from them); a fractional cloud (mcica = 0) mixes the two, both stay.
+template <int BAND, int G, bool CLD, bool LDSK, bool ONE = false, class Consume>
 RRTMG_HD void sw_layer_optics(const SwDev &d, const SwTab &T, SwThreadCtx<G> &c, int col, int l, Consume &&consume) {
   const int L = d.nlay, N = d.ncol;
   const double *exp_tbl = c.exp_tbl;
@@ -969,6 +973,61 @@ RRTMG_HD void sw_layer_optics(const SwDev &d, const SwTab &T, SwThreadCtx<G> &c,
 #pragma unroll
   for (int g = 0; g < G; ++g) {
     SwLayerOpt oc, ot;
+    if constexpr (ONE) {
+      // the branches below, in their order, with the clear-sky sw_reftra left out where nothing reads its results
+      bool lcld = false;
+      double zc = 0.0;
+      if (c.cloudy[g]) {
+        if (d.mcica) { lcld = (c.mw[g] >> (l & 63)) & 1ull; zc = lcld ? 1.0 : 0.0; }
+        else { zc = zcloud; lcld = lcld_band; }
+      }
+      const bool replaced = d.mcica && lcld;
+      double ztauc, zomcc, zgcc;
+      if (d.tauaer) {
+        ztauc = taur[g] + taug[g] + taua;
+        zomcc = taur[g] * 1.0 + taua * omga;
+        zgcc = qdiv(asya * omga * taua, zomcc);
+        zomcc = qdiv(zomcc, ztauc);
+        const double zf = zgcc * zgcc, zwf = zomcc * zf;
+        ztauc = (1.0 - zwf) * ztauc;
+        zomcc = qdiv(zomcc - zwf, 1.0 - zwf);
+        zgcc = qdiv(zgcc - zf, 1.0 - zf);
+        if (!replaced) sw_reftra<false>(exp_tbl, zgcc, prmu0, rmu0, ztauc, zomcc, oc.ref, oc.refd, oc.tra, oc.trad, oc.dbt);
+      } else {
+        ztauc = taur[g] + taug[g];
+        zomcc = qdiv(taur[g], ztauc);
+        zgcc = 0.0;
+        if (!replaced) sw_reftra<true>(exp_tbl, 0.0, prmu0, rmu0, ztauc, zomcc, oc.ref, oc.refd, oc.tra, oc.trad, oc.dbt);
+      }
+      if (!c.cloudy[g]) { consume(g, oc, oc); continue; }
+      const double ptc = (lcld || !d.mcica) ? ptauc : 0.0;
+      if (lcld) {
+        const double ztauo = ztauc + ptc;
+        double zomco = ztauc * zomcc + ptc * pomgc;
+        const double zgco = qdiv(ptc * pomgc * pasyc + ztauc * zomcc * zgcc, zomco);
+        zomco = qdiv(zomco, ztauo);
+        double refo, refdo, trao, trado, dbto;
+        sw_reftra<false>(exp_tbl, zgco, prmu0, rmu0, ztauo, zomco, refo, refdo, trao, trado, dbto);
+        if (d.mcica) {
+          ot.ref = refo; ot.refd = refdo; ot.tra = trao; ot.trad = trado; ot.dbt = dbto;
+        } else {
+          const double zclear = 1.0 - zc;
+          ot.ref = zclear * oc.ref + zc * refo; ot.refd = zclear * oc.refd + zc * refdo;
+          ot.tra = zclear * oc.tra + zc * trao; ot.trad = zclear * oc.trad + zc * trado;
+          ot.dbt = zclear * oc.dbt + zc * dbto;
+        }
+      } else if (!d.mcica && zc != 0.0) {
+        const double zclear = 1.0 - zc;
+        const double dbto = sw_dbt(exp_tbl, ztauc + ptc, rmu0);
+        ot.ref = zclear * oc.ref; ot.refd = zclear * oc.refd; ot.tra = zclear * oc.tra + zc;
+        ot.trad = zclear * oc.trad + zc;
+        ot.dbt = zclear * oc.dbt + zc * dbto;
+      } else {
+        ot = oc;
+      }
+      consume(g, ot, ot);
+      continue;
+    }
     // clear-sky optical properties and delta scaling (rrtmg_sw_spcvrt.f90:447-498)
     double ztauc, zomcc, zgcc;
     if (d.tauaer) {
@@ -1029,7 +1088,10 @@ RRTMG_HD void sw_layer_optics(const SwDev &d, const SwTab &T, SwThreadCtx<G> &c,
 // (sub-)columns -- the total sky.  The weighted fluxes of the G g-points are added in g-point order before they
 // leave through `sink`.
 // CLD = false: the caller guarantees a cloud-free column (the cloud code is compiled out: fewer registers).
-template <int BAND, int G, bool CLD, bool LDSK, class Sink>
+// ONE (see sw_layer_optics; CLD = true): the total-sky stream alone -- one recurrence per sweep, the F_RUP / F_RUPD rows of the
+// slab alone, and the sums leave through emit_clear, so a cloudy tile fills the two planes a cloud-free tile fills.  Its
+// arithmetic is, operation for operation, that of the total-sky stream below.
+template <int BAND, int G, bool CLD, bool LDSK, bool ONE = false, class Sink>
 RRTMG_HD void sw_solve_thread(const SwDev &d, const SwTab &T, const double *exp_tbl, int col, int ig0, double *scr, long stride, Sink &sink, const double *kb) {
   const int L = d.nlay, N = d.ncol;
   SwThreadCtx<G> c;
@@ -1066,6 +1128,72 @@ RRTMG_HD void sw_solve_thread(const SwDev &d, const SwTab &T, const double *exp_
   // scratch slab of this (tile, item): [layer][field][lane][G] -- the G values of a lane are one 16-byte access;
   // scr points at this lane's first element, stride = lanes per row (64 on the device, 1 in the host emulation)
   auto SP = [&](int f, int l) -> double * { return scr + ((long)l * F_NTOT + f) * stride * G; };
+  if constexpr (ONE) {
+    static_assert(CLD, "the all-sky-only mode is a mode of the cloudy variant");
+    // sweep 1 (a g-point without cloud in its (sub-)column receives its clear-sky operator: the CLD code's fu = cu there)
+    double rup[G], rupd[G];
+#pragma unroll
+    for (int g = 0; g < G; ++g) { rup[g] = albp; rupd[g] = albd; }
+    for (int l = 0; l < L; ++l) {
+      sw_layer_optics<BAND, G, CLD, LDSK, true>(d, T, c, col, l, [&](int g, const SwLayerOpt &, const SwLayerOpt &ot) {
+        const double zr = qrcp(1.0 - rupd[g] * ot.refd);
+        const double nrup = ot.ref + (ot.trad * ((ot.tra - ot.dbt) * rupd[g] + ot.dbt * rup[g])) * zr;
+        const double nrupd = ot.refd + ot.trad * ot.trad * rupd[g] * zr;
+        rup[g] = nrup; rupd[g] = nrupd;
+      });
+      V<G> v0, v1;
+#pragma unroll
+      for (int g = 0; g < G; ++g) { v0[g] = rup[g]; v1[g] = rupd[g]; }
+      scr_store<G>(SP(F_RUP, l), stride, v0); scr_store<G>(SP(F_RUPD, l), stride, v1);
+    }
+    // sweep 2
+    double tdn[G], rdnd[G], tdbt[G];
+#pragma unroll
+    for (int g = 0; g < G; ++g) {
+#if defined(__HIP_DEVICE_COMPILE__)
+      const double zinc = sw_incflux<BAND>(d, T, col, ig0 + g, c.prmu0);   // (the fluxes leave weighted: see below)
+#else
+      const double zinc = 1.0;
+#endif
+      tdn[g] = zinc; rdnd[g] = 0.0; tdbt[g] = zinc;
+    }
+#if !defined(__HIP_DEVICE_COMPILE__)
+    double zinc[G];
+    for (int g = 0; g < G; ++g) zinc[g] = sw_incflux<BAND>(d, T, col, ig0 + g, c.prmu0);
+#endif
+    for (int lev = L; lev >= 0; --lev) {
+      double sfu[G / 2], sfd[G / 2];
+#pragma unroll
+      for (int h = 0; h < G / 2; ++h) { sfu[h] = 0.0; sfd[h] = 0.0; }
+      V<G> c_r, c_rd;
+      if (lev > 0) { c_r = scr_load<G>(SP(F_RUP, lev - 1), stride); c_rd = scr_load<G>(SP(F_RUPD, lev - 1), stride); }
+#pragma unroll
+      for (int g = 0; g < G; ++g) {
+        const double r = (lev > 0) ? c_r[g] : albp;
+        const double rd = (lev > 0) ? c_rd[g] : albd;
+        const double zr = qrcp(1.0 - rdnd[g] * rd);
+        const double fu = (tdbt[g] * r + (tdn[g] - tdbt[g]) * rd) * zr;
+        const double fd = tdbt[g] + (tdn[g] - tdbt[g] + tdbt[g] * r * rdnd[g]) * zr;
+        const int h = g >> 1;
+#if defined(__HIP_DEVICE_COMPILE__)
+        sfu[h] = sfu[h] + fu; sfd[h] = sfd[h] + fd;
+#else
+        sfu[h] = sfu[h] + zinc[g] * fu; sfd[h] = sfd[h] + zinc[g] * fd;
+#endif
+      }
+      if constexpr (G == 4) sink.emit_clear(lev, sfu[0] + sfu[1], sfd[0] + sfd[1]);   // one slot per chunk, pair0 + pair1
+      else sink.emit_clear(lev, sfu[0], sfd[0]);
+      if (lev > 0) {
+        sw_layer_optics<BAND, G, CLD, LDSK, true>(d, T, c, col, lev - 1, [&](int g, const SwLayerOpt &, const SwLayerOpt &ot) {
+          const double zr = qrcp(1.0 - ot.refd * rdnd[g]);
+          const double ntdn = tdbt[g] * ot.tra + (ot.trad * ((tdn[g] - tdbt[g]) + tdbt[g] * ot.ref * rdnd[g])) * zr;
+          const double nrdnd = ot.refd + ot.trad * ot.trad * rdnd[g] * zr;
+          tdn[g] = ntdn; rdnd[g] = nrdnd; tdbt[g] = ot.dbt * tdbt[g];
+        });
+      }
+    }
+    return;
+  }
 
   // ---- sweep 1: bottom -> top, upward adding recurrence (rrtmg_sw_vrtqdr.f90:114-140) ---------------
   double rupc[G], rupdc[G], rup[G], rupd[G];
@@ -1203,33 +1331,33 @@ RRTMG_HD void sw_solve_thread(const SwDev &d, const SwTab &T, const double *exp_
 }
 
 // Dispatch of one work item (packed, see SwTab) for one column: band switch + G in {4, 2}.
-template <int BAND, bool CLD, bool LDSK, class Sink>
+template <int BAND, bool CLD, bool LDSK, bool ONE = false, class Sink>
 RRTMG_HD void sw_solve_band(const SwDev &d, const SwTab &T, const double *exp_tbl, int g, int col, int ig0, double *scr, long stride, Sink &sink, const double *kb) {
   constexpr int ng = SwBandCfg<BAND>::ng;
   if constexpr (ng >= 4) {
-    if (g == 4) { sw_solve_thread<BAND, 4, CLD, LDSK>(d, T, exp_tbl, col, ig0, scr, stride, sink, kb); return; }
+    if (g == 4) { sw_solve_thread<BAND, 4, CLD, LDSK, ONE>(d, T, exp_tbl, col, ig0, scr, stride, sink, kb); return; }
   }
-  if constexpr (ng % 4 != 0) sw_solve_thread<BAND, 2, CLD, LDSK>(d, T, exp_tbl, col, ig0, scr, stride, sink, kb);
+  if constexpr (ng % 4 != 0) sw_solve_thread<BAND, 2, CLD, LDSK, ONE>(d, T, exp_tbl, col, ig0, scr, stride, sink, kb);
 }
 // LDSK / kb: see sw_taug (kb = the workgroup's LDS slice of the item's band slab, or nullptr with LDSK = false)
-template <bool CLD, bool LDSK = false, class Sink>
+template <bool CLD, bool LDSK = false, bool ONE = false, class Sink>
 RRTMG_HD void sw_solve_item(const SwDev &d, const SwTab &T, const double *exp_tbl, int item, int col, double *scr, long stride, Sink &sink, const double *kb = nullptr) {
   const int g = item_g(item), ig0 = item_ig0(item);
   switch (item_band(item) + 16) {
-    case 16: sw_solve_band<16, CLD, LDSK>(d, T, exp_tbl, g, col, ig0, scr, stride, sink, kb); break;
-    case 17: sw_solve_band<17, CLD, LDSK>(d, T, exp_tbl, g, col, ig0, scr, stride, sink, kb); break;
-    case 18: sw_solve_band<18, CLD, LDSK>(d, T, exp_tbl, g, col, ig0, scr, stride, sink, kb); break;
-    case 19: sw_solve_band<19, CLD, LDSK>(d, T, exp_tbl, g, col, ig0, scr, stride, sink, kb); break;
-    case 20: sw_solve_band<20, CLD, LDSK>(d, T, exp_tbl, g, col, ig0, scr, stride, sink, kb); break;
-    case 21: sw_solve_band<21, CLD, LDSK>(d, T, exp_tbl, g, col, ig0, scr, stride, sink, kb); break;
-    case 22: sw_solve_band<22, CLD, LDSK>(d, T, exp_tbl, g, col, ig0, scr, stride, sink, kb); break;
-    case 23: sw_solve_band<23, CLD, LDSK>(d, T, exp_tbl, g, col, ig0, scr, stride, sink, kb); break;
-    case 24: sw_solve_band<24, CLD, LDSK>(d, T, exp_tbl, g, col, ig0, scr, stride, sink, kb); break;
-    case 25: sw_solve_band<25, CLD, LDSK>(d, T, exp_tbl, g, col, ig0, scr, stride, sink, kb); break;
-    case 26: sw_solve_band<26, CLD, LDSK>(d, T, exp_tbl, g, col, ig0, scr, stride, sink, kb); break;
-    case 27: sw_solve_band<27, CLD, LDSK>(d, T, exp_tbl, g, col, ig0, scr, stride, sink, kb); break;
-    case 28: sw_solve_band<28, CLD, LDSK>(d, T, exp_tbl, g, col, ig0, scr, stride, sink, kb); break;
-    default: sw_solve_band<29, CLD, LDSK>(d, T, exp_tbl, g, col, ig0, scr, stride, sink, kb); break;
+    case 16: sw_solve_band<16, CLD, LDSK, ONE>(d, T, exp_tbl, g, col, ig0, scr, stride, sink, kb); break;
+    case 17: sw_solve_band<17, CLD, LDSK, ONE>(d, T, exp_tbl, g, col, ig0, scr, stride, sink, kb); break;
+    case 18: sw_solve_band<18, CLD, LDSK, ONE>(d, T, exp_tbl, g, col, ig0, scr, stride, sink, kb); break;
+    case 19: sw_solve_band<19, CLD, LDSK, ONE>(d, T, exp_tbl, g, col, ig0, scr, stride, sink, kb); break;
+    case 20: sw_solve_band<20, CLD, LDSK, ONE>(d, T, exp_tbl, g, col, ig0, scr, stride, sink, kb); break;
+    case 21: sw_solve_band<21, CLD, LDSK, ONE>(d, T, exp_tbl, g, col, ig0, scr, stride, sink, kb); break;
+    case 22: sw_solve_band<22, CLD, LDSK, ONE>(d, T, exp_tbl, g, col, ig0, scr, stride, sink, kb); break;
+    case 23: sw_solve_band<23, CLD, LDSK, ONE>(d, T, exp_tbl, g, col, ig0, scr, stride, sink, kb); break;
+    case 24: sw_solve_band<24, CLD, LDSK, ONE>(d, T, exp_tbl, g, col, ig0, scr, stride, sink, kb); break;
+    case 25: sw_solve_band<25, CLD, LDSK, ONE>(d, T, exp_tbl, g, col, ig0, scr, stride, sink, kb); break;
+    case 26: sw_solve_band<26, CLD, LDSK, ONE>(d, T, exp_tbl, g, col, ig0, scr, stride, sink, kb); break;
+    case 27: sw_solve_band<27, CLD, LDSK, ONE>(d, T, exp_tbl, g, col, ig0, scr, stride, sink, kb); break;
+    case 28: sw_solve_band<28, CLD, LDSK, ONE>(d, T, exp_tbl, g, col, ig0, scr, stride, sink, kb); break;
+    default: sw_solve_band<29, CLD, LDSK, ONE>(d, T, exp_tbl, g, col, ig0, scr, stride, sink, kb); break;
   }
 }
 
@@ -1327,6 +1455,21 @@ RRTMG_HD void sw_heat_layer(const SwDev &d, const SwTab &T, int col, int lay) {
   const double netc0 = d.swdflxc[o0] - d.swuflxc[o0], netc1 = d.swdflxc[o1] - d.swuflxc[o1];
   const double zdpgcp = T.heatfac / d.pdp[o0];
   d.swhrc[o0] = (netc1 - netc0) * zdpgcp;
+  d.swhr[o0] = (net1 - net0) * zdpgcp;
+}
+// The two above without the clear-sky outputs (rrtmg_hip_set_sw_clear_sky(0)): every tile's slots hold two planes
+// (sw_solve_thread's ONE mode leaves through emit_clear), swuflxc / swdflxc / swhrc are not dereferenced.
+RRTMG_HD void sw_flux_level_allsky(const SwDev &d, const SwTab &T, int col, int lev) {
+  double fu, fd, cu, cd;
+  sw_flux_sums(d, T, col, lev, false, fu, fd, cu, cd);
+  const long o = (long)lev * d.ncol + col;
+  d.swuflx[o] = fu; d.swdflx[o] = fd;
+}
+RRTMG_HD void sw_heat_layer_allsky(const SwDev &d, const SwTab &T, int col, int lay) {
+  const int N = d.ncol;
+  const long o0 = (long)lay * N + col, o1 = o0 + N;
+  const double net0 = d.swdflx[o0] - d.swuflx[o0], net1 = d.swdflx[o1] - d.swuflx[o1];
+  const double zdpgcp = T.heatfac / d.pdp[o0];
   d.swhr[o0] = (net1 - net0) * zdpgcp;
 }
 

@@ -276,10 +276,14 @@ def shortwave_device_call(self, ds):
     il, ml = (nlay + 1, ncol), (nlay, ncol)
     self._device_calls = getattr(self, "_device_calls", 0) + 1          # outputs alternate between two buffer sets: the
     w = lambda key, shape, dims, units: ds.work(("sw", id(self), key, self._device_calls & 1), shape, dims, units)   # state may still hold the last ones
-    fl = {k: w(k, il, ("interface_levels", "*"), "W m^-2") for k in ("swuflx", "swdflx", "swuflxc", "swdflxc")}
-    hr, hrc = w("swhr", ml, ("mid_levels", "*"), "degK day^-1"), w("swhrc", ml, ("mid_levels", "*"), "degK day^-1")
+    clear = getattr(self, "_clear_sky", True)      # False: no buffers for the three clear-sky outputs, which the library then leaves out
+    fl = {k: w(k, il, ("interface_levels", "*"), "W m^-2") for k in (("swuflx", "swdflx", "swuflxc", "swdflxc") if clear else ("swuflx", "swdflx"))}
+    hr = w("swhr", ml, ("mid_levels", "*"), "degK day^-1")
     out = {k: v.ptr for k, v in fl.items()}
-    out.update(swhr=hr.ptr, swhrc=hrc.ptr)
+    out.update(swhr=hr.ptr)
+    if clear:
+        hrc = w("swhrc", ml, ("mid_levels", "*"), "degK day^-1")
+        out.update(swhrc=hrc.ptr)
     comps = None
     if getattr(self, "_flux_components", False):
         from .rrtmg.shortwave import FLUX_COMPONENT_DIAGNOSTICS
@@ -298,10 +302,11 @@ def shortwave_device_call(self, ds):
                          bands={b: q.ptr for b, q in bands.items()} if bands else None, surface=surface)
     else:
         ds.ctx.sw_fluxes(inp, mcica=self._mcica, out=out, memspace=1)
-    diagnostics = {
-        "upwelling_shortwave_flux_in_air": fl["swuflx"], "downwelling_shortwave_flux_in_air": fl["swdflx"],
-        "upwelling_shortwave_flux_in_air_assuming_clear_sky": fl["swuflxc"], "downwelling_shortwave_flux_in_air_assuming_clear_sky": fl["swdflxc"],
-        "air_temperature_tendency_from_shortwave_assuming_clear_sky": hrc, "air_temperature_tendency_from_shortwave": hr}
+    diagnostics = {"upwelling_shortwave_flux_in_air": fl["swuflx"], "downwelling_shortwave_flux_in_air": fl["swdflx"],
+                   "air_temperature_tendency_from_shortwave": hr}
+    if clear:
+        diagnostics.update({"upwelling_shortwave_flux_in_air_assuming_clear_sky": fl["swuflxc"], "downwelling_shortwave_flux_in_air_assuming_clear_sky": fl["swdflxc"],
+                            "air_temperature_tendency_from_shortwave_assuming_clear_sky": hrc})
     if comps:
         diagnostics.update({k: comps[c] for k, c in FLUX_COMPONENT_DIAGNOSTICS.items()})
     if bands:

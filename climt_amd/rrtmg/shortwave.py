@@ -101,6 +101,14 @@ def band_albedo(wavenumber_cm1, albedo):
     return out[:, 0] if a.ndim == 1 else out
 
 
+# the diagnostics an instance made with clear_sky_diagnostics=False does not have -> the library's output behind each
+CLEAR_SKY_DIAGNOSTICS = {
+    "upwelling_shortwave_flux_in_air_assuming_clear_sky": "swuflxc",
+    "downwelling_shortwave_flux_in_air_assuming_clear_sky": "swdflxc",
+    "air_temperature_tendency_from_shortwave_assuming_clear_sky": "swhrc",
+}
+
+
 class RRTMGShortwave(TendencyComponent):
     """The Rapid Radiative Transfer Model (RRTMG), shortwave, on AMD MI355X."""
 
@@ -156,12 +164,13 @@ class RRTMGShortwave(TendencyComponent):
     }
 
     @classmethod
-    def diagnostic_properties_for(cls, flux_components=False, band_fluxes=False):
+    def diagnostic_properties_for(cls, flux_components=False, band_fluxes=False, clear_sky_diagnostics=True):
         """The diagnostic_properties of an instance made with these options: the class dict itself, or a new dict of it plus
-        the eight flux components (interface levels, W m^-2) and / or the six band fluxes (bands x interface levels)."""
-        if not flux_components and not band_fluxes:
+        the eight flux components (interface levels, W m^-2) and / or the six band fluxes (bands x interface levels), or
+        without the three CLEAR_SKY_DIAGNOSTICS."""
+        if not flux_components and not band_fluxes and clear_sky_diagnostics:
             return cls.diagnostic_properties
-        props = dict(cls.diagnostic_properties)
+        props = {k: v for k, v in cls.diagnostic_properties.items() if clear_sky_diagnostics or k not in CLEAR_SKY_DIAGNOSTICS}
         if flux_components:
             props.update({k: _prop(_IL, "W m^-2") for k in FLUX_COMPONENT_DIAGNOSTICS})
         if band_fluxes:
@@ -183,7 +192,8 @@ class RRTMGShortwave(TendencyComponent):
                  solar_variability_method=0, use_solar_constant_from_fortran=False, ignore_day_of_year=False,
                  facular_sunspot_amplitude=None, solar_variability_by_band=None, aerosol_type="no_aerosol", mcica=False,
                  random_number_generator="mersenne_twister", device=0, flux_components=False, band_fluxes=False,
-                 spectral_surface_albedo=False, skip_night_columns=False, pack_day_columns=False, **kwargs):
+                 spectral_surface_albedo=False, skip_night_columns=False, pack_day_columns=False, clear_sky_diagnostics=True,
+                 **kwargs):
         """Same keyword arguments and defaults as climt.RRTMGShortwave (sw/component.py:179-194); the additions are `device`
         (GPU ordinal) and `flux_components`: True adds the downward flux split into direct and diffuse parts -- all bands,
         UV/visible bands, near-IR bands, and all bands clear sky (FLUX_COMPONENT_DIAGNOSTICS) -- to this instance's
@@ -202,9 +212,19 @@ class RRTMGShortwave(TendencyComponent):
         climt_amd.DeviceState with kissvec or no McICA and facular_sunspot_amplitude of 1; a host state, radiation_step's
         joint call and every other call run as with skip_night_columns alone.  The night columns' zeros are the same; a day
         column's bits are those of a call on the day columns alone (see the header for when they differ from the whole
-        grid's, by at most 1e-10); the class attributes are unchanged."""
+        grid's, by at most 1e-10); the class attributes are unchanged; `clear_sky_diagnostics`: False takes the three
+        `*_assuming_clear_sky` quantities (CLEAR_SKY_DIAGNOSTICS) out of this instance's diagnostics and has the library form no
+        clear-sky stream (rrtmg_hip_set_sw_clear_sky): columns with cloud are solved once, not twice, and three of the six
+        outputs are not copied; the other diagnostics and the tendency agree with the default instance's to rounding (<= 5e-8
+        W m^-2).  Not together with flux_components or band_fluxes (ValueError): their clear-sky and direct-beam members
+        read the stream that is not formed."""
         if pack_day_columns and not skip_night_columns:
             raise ValueError("pack_day_columns=True requires skip_night_columns=True")
+        if not clear_sky_diagnostics and (flux_components or band_fluxes):
+            raise ValueError("clear_sky_diagnostics=False cannot be combined with %s=True" % ("flux_components" if flux_components else "band_fluxes"))
+        self._clear_sky = bool(clear_sky_diagnostics)
+        if not self._clear_sky:
+            self.diagnostic_properties = self.diagnostic_properties_for(clear_sky_diagnostics=False)
         self._skip_night = bool(skip_night_columns)
         self._pack_day = bool(pack_day_columns)
         self._spectral_albedo = bool(spectral_surface_albedo)
@@ -281,6 +301,12 @@ class RRTMGShortwave(TendencyComponent):
             setter(pack)
         elif pack:
             raise RuntimeError("pack_day_columns=True: this context has no set_sw_night_pack")
+        # `clear_sky_diagnostics`, likewise
+        clear, setter = getattr(self, "_clear_sky", True), getattr(ctx, "set_sw_clear_sky", None)
+        if setter is not None and (not clear or getattr(ctx, "has_sw_clear_sky", True)):
+            setter(clear)
+        elif not clear:
+            raise RuntimeError("clear_sky_diagnostics=False: this context has no set_sw_clear_sky")
 
     def __call__(self, state, *args, **kwargs):
         """A host state goes through sympl's machinery to array_call; a climt_amd.DeviceState (state resident in HBM) takes
@@ -346,9 +372,9 @@ class RRTMGShortwave(TendencyComponent):
             inp.update(irng=self._random_number_generator, permuteseed=self._permute_seed)
         out = dict(
             swuflx=diagnostics["upwelling_shortwave_flux_in_air"], swdflx=diagnostics["downwelling_shortwave_flux_in_air"],
-            swhr=tendencies["air_temperature"], swuflxc=diagnostics["upwelling_shortwave_flux_in_air_assuming_clear_sky"],
-            swdflxc=diagnostics["downwelling_shortwave_flux_in_air_assuming_clear_sky"],
-            swhrc=diagnostics["air_temperature_tendency_from_shortwave_assuming_clear_sky"])
+            swhr=tendencies["air_temperature"])
+        if getattr(self, "_clear_sky", True):
+            out.update({m: diagnostics[k] for k, m in CLEAR_SKY_DIAGNOSTICS.items()})
         self._input_staging.wait()
         library = dict(inp=inp, mcica=self._mcica, out=out)
         if self._flux_components or self._band_fluxes:

@@ -175,6 +175,23 @@ int rrtmg_hip_set_sw_night_skip(rrtmg_ctx *ctx, int on);
  *    one scatter launch for all outputs, and an internal copy of inputs and outputs of 64 x (ceil(ncol / 64) + 1) columns.
  * Probe for it by symbol; the argument structs and RRTMG_HIP_ABI_VERSION are unchanged. */
 int rrtmg_hip_set_sw_night_pack(rrtmg_ctx *ctx, int on);
+/* OPT-IN shortwave call without the clear-sky outputs (on = 1 by default: nothing changes; the reference-compatible symbols on
+ * the default context always have 1).  With on = 0 a shortwave call forms no clear-sky stream: tiles with cloud run a one-stream
+ * solve (under McICA one layer operator and one adding recurrence per g-point and layer instead of two), and swuflxc, swdflxc
+ * and swhrc are neither computed nor copied.
+ *  - The three members may be NULL.  Whatever they point to is ignored: on a device-pointer call (memspace 1) not one element
+ *    is written; on a host-pointer call the arrays are neither downloaded nor touched.
+ *  - swuflx, swdflx and swhr: a column of a cloud-free tile (64 columns) keeps its bits; a column of a tile with cloud agrees with
+ *    the default call to rounding (the same operations on the total-sky stream, compiled in another kernel: <= 5e-8 W m-2).
+ *  - Covers rrtmg_hip_sw_fluxes, rrtmg_hip_sw_fluxes_surface with the albedo by band, and the shortwave half of
+ *    rrtmg_hip_radiation_fluxes; chunks, shards, deferred mode, rrtmg_hip_set_column_sort, rrtmg_hip_set_sw_night_skip and
+ *    rrtmg_hip_set_sw_night_pack work as with on = 1 (a night column gets +0.0 in the three outputs).
+ *  - rrtmg_hip_sw_fluxes_components, rrtmg_hip_sw_fluxes_bands and a call of rrtmg_hip_sw_fluxes_surface or
+ *    rrtmg_hip_radiation_fluxes that requests a component or a band member return RRTMG_ERR_ARG while on = 0 (their clear-sky and
+ *    direct-beam members read the stream that is not formed); the context stays usable.
+ * The longwave is not touched.  The switch belongs to the context: a binder that shares one context between callers sets it
+ * before each shortwave call.  Probe for it by symbol; the argument structs and RRTMG_HIP_ABI_VERSION are unchanged. */
+int rrtmg_hip_set_sw_clear_sky(rrtmg_ctx *ctx, int on);
 /* Night tiles and night columns (all of them: those of mixed tiles too) of the last completed shortwave call on this context:
  * valid after the call has returned, in deferred mode after rrtmg_hip_synchronize.  0 / 0 if that call ran with the skip off
  * (and the pack off); after a packed call (rrtmg_hip_set_sw_night_pack) the counts stated there.
