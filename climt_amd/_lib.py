@@ -193,6 +193,8 @@ def load_library():
         lib.rrtmg_hip_set_sw_night_pack.argtypes = [_vp, C.c_int]
     if hasattr(lib, "rrtmg_hip_set_sw_clear_sky"):       # (likewise)
         lib.rrtmg_hip_set_sw_clear_sky.argtypes = [_vp, C.c_int]
+    if hasattr(lib, "rrtmg_hip_set_lw_clear_sky"):       # (likewise)
+        lib.rrtmg_hip_set_lw_clear_sky.argtypes = [_vp, C.c_int]
     if hasattr(lib, "rrtmg_hip_radiation_fluxes"):       # (likewise)
         lib.rrtmg_hip_radiation_fluxes.argtypes = [_vp, C.POINTER(RadiationCall)]
         lib.rrtmg_hip_radiation_last.argtypes = [_vp, C.POINTER(C.c_int), C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]
@@ -222,6 +224,7 @@ _LW_FLAGS = dict(icld="icld", idrv="idrv", inflg="inflglw", iceflg="iceflglw", l
 SW_OUT = (("swuflx", 1), ("swdflx", 1), ("swhr", 0), ("swuflxc", 1), ("swdflxc", 1), ("swhrc", 0))
 SW_OUT_ALLSKY = ("swuflx", "swdflx", "swhr")      # what a call fills after Context.set_sw_clear_sky(False)
 LW_OUT = (("uflx", 1), ("dflx", 1), ("hr", 0), ("uflxc", 1), ("dflxc", 1), ("hrc", 0))
+LW_OUT_CLEAR = ("uflxc", "dflxc", "hrc", "duflxc_dt")      # what a call leaves out after Context.set_lw_clear_sky(False)
 
 
 def source_hash():
@@ -456,6 +459,21 @@ class Context:
         self._ck(self.lib.rrtmg_hip_set_sw_clear_sky(self.h, 1 if on else 0))
         self.sw_clear_sky = bool(on)
 
+    @property
+    def has_lw_clear_sky(self):
+        return hasattr(self.lib, "rrtmg_hip_set_lw_clear_sky")
+
+    @_locked
+    def set_lw_clear_sky(self, on=True):
+        """Clear-sky outputs of the longwave (rrtmg_hip_set_lw_clear_sky; on by default).  Off: a longwave call forms no
+        clear-sky stream -- tiles with cloud run a one-stream solve -- and uflxc, dflxc, hrc (and duflxc_dt with idrv) are neither
+        computed nor copied: `out` may leave them out (or hold None); an array it does hold for one of them is handed to the
+        library, which neither writes nor reads it.  Band calls that request upc or dnc are refused while it is off; up and dn are served."""
+        if not self.has_lw_clear_sky:
+            raise RRTMGError(4, "this librrtmg_hip.so has no rrtmg_hip_set_lw_clear_sky (longwave call without the clear-sky outputs)")
+        self._ck(self.lib.rrtmg_hip_set_lw_clear_sky(self.h, 1 if on else 0))
+        self.lw_clear_sky = bool(on)
+
     @_locked
     def sw_night_last(self):
         """-> (night tiles, night columns) of the last completed shortwave call (in deferred mode: after synchronize());
@@ -578,14 +596,18 @@ class Context:
         a.ncol, a.nlay, a.memspace, a.mcica = int(ncol), int(nlay), int(memspace), int(bool(mcica))
         a.icld, a.inflglw, a.iceflglw, a.liqflglw = 1, 2, 1, 1
         self._fill(a, inp, _LW_FIELDS, _LW_FLAGS, keep)
+        clear = getattr(self, "lw_clear_sky", True)      # (set_lw_clear_sky(False): the clear-sky outputs may be absent or None -> NULL;
+        #                                                    one that `out` does hold is handed over, and the library ignores it)
         if out is None:
-            out = {k: np.zeros((nlay + lev, ncol)) for k, lev in LW_OUT}
+            out = {k: np.zeros((nlay + lev, ncol)) for k, lev in LW_OUT if clear or k not in LW_OUT_CLEAR}
             if a.idrv:
                 out["duflx_dt"] = np.zeros((nlay + 1, ncol))
-                out["duflxc_dt"] = np.zeros((nlay + 1, ncol))
+                if clear:
+                    out["duflxc_dt"] = np.zeros((nlay + 1, ncol))
         for k in out:
             v = out[k]
-            setattr(a, k, int(v) if isinstance(v, (int, np.integer)) else v.ctypes.data)
+            if v is not None:
+                setattr(a, k, int(v) if isinstance(v, (int, np.integer)) else v.ctypes.data)
         b = None if bands is None else _band_struct(LwBandFluxes, LW_BAND_FLUXES, LW_NBAND, bands, band_levels, nlay, ncol)
         return a, b, out
 

@@ -541,6 +541,11 @@ int rrtmg_hip_set_sw_clear_sky(rrtmg_ctx *ctx, int on) {
   ctx->sw_clear_sky = on != 0;
   return RRTMG_OK;
 }
+int rrtmg_hip_set_lw_clear_sky(rrtmg_ctx *ctx, int on) {
+  if (!ctx) return RRTMG_ERR_ARG;
+  ctx->lw_clear_sky = on != 0;
+  return RRTMG_OK;
+}
 int rrtmg_hip_sw_night_last(rrtmg_ctx *ctx, int *night_tiles, int *night_columns) {
   if (!ctx || !night_tiles || !night_columns) return RRTMG_ERR_ARG;
   const volatile int *n = ctx->sw_night_reported ? ctx->night_host() : nullptr;

@@ -110,6 +110,9 @@ struct rrtmg_ctx {
   // rrtmg_hip_set_sw_clear_sky: false = a shortwave call forms no clear-sky stream and writes, reads and copies none of swuflxc,
   // swdflxc, swhrc (rrtmg_sw.hip: sw_solve_cloudy_allsky_kernel, sw_fluxheat_allsky_kernel)
   bool sw_clear_sky = true;
+  // rrtmg_hip_set_lw_clear_sky: false = a longwave call forms no clear-sky stream and writes, reads and copies none of uflxc,
+  // dflxc, hrc, duflxc_dt (rrtmg_lw.hip: lw_solve_all_allsky_kernel, lw_fluxheat_allsky_kernel)
+  bool lw_clear_sky = true;
   // KISS jump-ahead operators [sw|lw]: host copy, the key they were built for, the device buffer they were uploaded to
   std::vector<uint32_t> kiss_host[2][2];   // two staging copies per spectrum: a rebuild never waits for the previous upload
   hipEvent_t kiss_ev[2][2] = {{nullptr, nullptr}, {nullptr, nullptr}};   // recorded after the upload from kiss_host[w][k]

@@ -11,6 +11,9 @@
 //     lw_solve_all_kernel  one launch per variant (cloud-free / cloudy tiles): wavefront = tile(64 columns) x work item (4|2
 //                          g-points of a band), workgroup = 4 tiles of one item sharing its k-distribution slice in LDS
 //     lw_fluxheat_kernel   <<<(tiles, levels/15), 16 waves>>>  band / g-point integration per interface + heating rates
+// With the clear-sky outputs off (rrtmg_hip_set_lw_clear_sky(0)): lw_solve_all_allsky_kernel in the place of lw_solve_all_kernel,
+// lw_fluxheat_allsky_kernel in the place of lw_fluxheat_kernel, lw_bandflux_allsky_kernel in the place of lw_bandflux_kernel;
+// uflxc, dflxc, hrc and duflxc_dt are neither formed nor copied, and the partial planes are half as many
 // The host steps this call shares with the shortwave's (gate, checks, chunk plan and loop, mask choice, epilogue): rrtmg_call.h
 #include "rrtmg_call.h"
 #include "rrtmg_lw_device.h"
@@ -170,6 +173,79 @@ __global__ void __launch_bounds__(64 * kBandLev) lw_bandflux_kernel(LwDev d, LwT
   lw_band_level(d, T, o, col, lev, row, levels ? 2 : d.nlay + 1, d.tile_cld[tile] != 0);
 }
 
+// ---- No clear-sky outputs (rrtmg_hip_set_lw_clear_sky(0); opt-in) ----------------------------------------------------------------
+// Kernels of their own, launched INSTEAD of lw_solve_all_kernel, lw_fluxheat_kernel and lw_bandflux_kernel when the clear-sky
+// outputs are off: with them on the launch sequence and every kernel in it are those of a library without the option
+// (tools/isa_compare.py, profiles/isa_compare_lw_allsky_only.txt).  The partial planes are LwPartSinkAllsky's: up and down (and
+// d(up)/dTs with idrv) per item, in every tile.  CLD = true: lw_solve_thread's ONE mode, the total-sky stream alone.  CLD = false:
+// the cloud-free tiles run the device functions they always ran -- lw_solve_thread<.., CLD = false> has no second stream -- and
+// differ from lw_solve_all_kernel<false, false> in where the sink stores.  Tile lists, launch order, LDS staging and
+// amdgpu_waves_per_eu: lw_solve_all_kernel's.
+template <bool CLD, bool MR>
+__global__ void __launch_bounds__(64 * kLwWgWaves) __attribute__((amdgpu_waves_per_eu(2))) lw_solve_all_allsky_kernel(LwDev d, LwTab T, int tile0, int ntile) {
+  const int nmine = d.tcnt[CLD ? 1 : 0];
+  const int nblk = (nmine + kLwWgWaves - 1) / kLwWgWaves;
+  const int q = blockIdx.x;
+  if (q >= nblk * T.nitem) return;   // workgroup-uniform exit before the slice is staged
+  const int per = kLwGroupBlocks * T.nitem, nfull = nblk / kLwGroupBlocks;
+  const int bpg = q < nfull * per ? kLwGroupBlocks : nblk - nfull * kLwGroupBlocks, r = q < nfull * per ? q % per : q - nfull * per;
+  const int grp = q < nfull * per ? q / per : nfull;
+  const int k = r / bpg;
+  const int first = grp * kLwTileGroup + (r % bpg) * kLwWgWaves;
+  RRTMG_PROFILE_ONLY_ITEM(d, k)
+  const int slot = T.sched[k], item = T.item[slot];
+  const int g = (item >> 16) & 0xf, ig0 = (item >> 8) & 0xff;
+  __shared__ __attribute__((aligned(16))) double sh_k[kLwSlabMaxRows * 4];   // rows are read 16 bytes at a time
+  {
+    const LwBandTab &B = T.b[item & 0xff];
+    const double *src = T.t + B.slab + ig0;
+    const int ng = B.ng, sh = g == 4 ? 2 : 1, n = B.nrows << sh;
+    for (int i = threadIdx.x; i < n; i += 64 * kLwWgWaves) sh_k[i] = src[(long)(i >> sh) * ng + (i & (g - 1))];
+  }
+  __syncthreads();
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  if (first + wave >= nmine) return;
+  const int ctile = d.tlist[(CLD ? d.tcap : 0) + first + wave], tile = tile0 + ctile;
+  const int lane = threadIdx.x & 63;
+  const int col = tile * 64 + lane;
+  if (col >= d.ncol) return;
+  double *scr = d.scratch + ((long)ctile * kLwNGpt + ((item >> 20) & 0xff)) * (long)LF_N * d.nlay * 64 + lane * 2;
+  LwPartSinkAllsky sink = lw_part_sink_allsky(d, slot, col);
+  lw_solve_item<CLD, MR, true, CLD>(d, T, item, col, scr, 64, sink, sh_k);
+}
+// lw_fluxheat_kernel without the clear-sky half: LwPartSinkAllsky's planes in EVERY tile, the sums, differences and stores of
+// uflx, dflx, hr (and duflx_dt) as there
+__global__ void __launch_bounds__(64 * (kFluxLev + 1)) lw_fluxheat_allsky_kernel(LwDev d, LwTab T, int tile0) {
+  if (d.hint_out && blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) { *d.hint_out = *d.ncloudy; *d.ncloudy = 0; }
+  const int tile = tile0 + blockIdx.x, lane = threadIdx.x & 63, j = threadIdx.x >> 6;
+  const int col = tile * 64 + lane, lev = blockIdx.y * kFluxLev + j;
+  __shared__ double net[kFluxLev + 1][64];
+  const bool act = col < d.ncol && lev <= d.nlay;
+  if (act) {
+    double f[3];
+    lw_flux_sums_allsky(d, col, lev, T.nitem, f);
+    if (j < kFluxLev || lev == d.nlay) {
+      const long o = (long)lev * d.ncol + col;
+      d.uflx[o] = f[0]; d.dflx[o] = f[1];
+      if (d.idrv) d.duflx_dt[o] = f[2];
+    }
+    net[j][lane] = f[0] - f[1];
+  }
+  __syncthreads();
+  if (col < d.ncol && j < kFluxLev && lev < d.nlay) {
+    const long o0 = (long)lev * d.ncol + col;
+    const double dp = d.plev[o0] - d.plev[o0 + d.ncol];
+    d.hr[o0] = T.heatfac * (net[j][lane] - net[j + 1][lane]) / dp;
+  }
+}
+// lw_bandflux_kernel on LwPartSinkAllsky's planes: the members up and dn (upc, dnc: refused by the driver)
+__global__ void __launch_bounds__(64 * kBandLev) lw_bandflux_allsky_kernel(LwDev d, LwTab T, int tile0, LwBandOut o, int levels) {
+  const int tile = tile0 + blockIdx.x, col = tile * 64 + (threadIdx.x & 63), row = blockIdx.y * kBandLev + (threadIdx.x >> 6);
+  const int lev = levels ? (row ? d.nlay : 0) : row;
+  if (col >= d.ncol || row > (levels ? 1 : d.nlay)) return;
+  lw_band_level_allsky(d, T, o, col, lev, row, levels ? 2 : d.nlay + 1);
+}
+
 void free_lw_desc(rrtmg_ctx *ctx) {
   delete (LwTab *)ctx->lw_desc;
   ctx->lw_desc = nullptr;
@@ -203,9 +279,11 @@ static int lw_sorted_call(rrtmg_ctx *ctx, const rrtmg_lw_args *a) {
   if (int rc = ctx_prepare_device(ctx)) return rc;
   const CallSite c{ctx, 1, call_stream(ctx, 1, 1)};
   const bool dr = a->idrv != 0;
-  double *const u[6] = {a->uflx, a->dflx, a->hr, a->uflxc, a->dflxc, a->hrc};
-  if (int rc = check_outputs(ctx, u)) return rc;
-  if (dr && (!a->duflx_dt || !a->duflxc_dt)) return ctx->fail(RRTMG_ERR_ARG, "idrv=1 needs duflx_dt/duflxc_dt");
+  // (clear-sky outputs off: the four are absent from the scatter table, and from the inner call)
+  const bool clr = ctx->lw_clear_sky;
+  double *const u[6] = {a->uflx, a->dflx, a->hr, clr ? a->uflxc : nullptr, clr ? a->dflxc : nullptr, clr ? a->hrc : nullptr};
+  if (int rc = check_outputs(ctx, u, clr ? 6 : 3)) return rc;
+  if (dr && (!a->duflx_dt || (clr && !a->duflxc_dt))) return ctx->fail(RRTMG_ERR_ARG, clr ? "idrv=1 needs duflx_dt/duflxc_dt" : "idrv=1 needs duflx_dt");
   ColumnPermute pm(ctx, c.s, kInnerSorted, a->ncol, a->nlay, "lw.sort.");
   if (!pm.prepare(a->cldfr)) return ctx->status;
   rrtmg_lw_args b = *a;
@@ -226,18 +304,26 @@ static int lw_sorted_call(rrtmg_ctx *ctx, const rrtmg_lw_args *a) {
   if (!pm.ok) return ctx->status;
   pm.flush_gather();
   b.uflx = pm.out("o0", u[0], l1); b.dflx = pm.out("o1", u[1], l1); b.hr = pm.out("o2", u[2], l);
-  b.uflxc = pm.out("o3", u[3], l1); b.dflxc = pm.out("o4", u[4], l1); b.hrc = pm.out("o5", u[5], l);
-  b.duflx_dt = dr ? pm.out("o6", a->duflx_dt, l1) : nullptr; b.duflxc_dt = dr ? pm.out("o7", a->duflxc_dt, l1) : nullptr;
+  b.uflxc = clr ? pm.out("o3", u[3], l1) : nullptr; b.dflxc = clr ? pm.out("o4", u[4], l1) : nullptr; b.hrc = clr ? pm.out("o5", u[5], l) : nullptr;
+  b.duflx_dt = dr ? pm.out("o6", a->duflx_dt, l1) : nullptr; b.duflxc_dt = dr && clr ? pm.out("o7", a->duflxc_dt, l1) : nullptr;
   if (!pm.ok) return ctx->status;
   return permuted_tail(c, pm, [&]() { return lw_fluxes_impl(ctx, &b); });
 }
 
 // bp: the band fluxes requested (at least one member set, levels 0 or 1), or nullptr for the plain call.  A call with bands
 // is never sorted: its outputs would need a scatter of their own.
+// the clear-sky band members of a call without the clear-sky stream: refused before anything is enqueued
+static int lw_refuse_clear_bands(rrtmg_ctx *ctx, const rrtmg_lw_band_fluxes *bp) {
+  if (ctx->lw_clear_sky || !bp || (!bp->upc && !bp->dnc)) return RRTMG_OK;
+  return ctx->fail(RRTMG_ERR_ARG, "longwave band fluxes upc / dnc need the clear-sky stream: rrtmg_hip_set_lw_clear_sky(ctx, 0) is in force (set it to 1 for this call, or request up / dn only)");
+}
+
 int lw_fluxes_impl(rrtmg_ctx *ctx, const rrtmg_lw_args *a, const rrtmg_lw_band_fluxes *bp) {
+  const bool clr = ctx->lw_clear_sky;   // rrtmg_hip_set_lw_clear_sky: false = uflxc, dflxc, hrc and duflxc_dt are neither formed nor read from `a`
   if (call_is_sorted(ctx, 1, a, bp != nullptr)) return lw_sorted_call(ctx, a);
   int rc = call_begin(ctx, 1, a);
   if (rc) return rc;
+  if ((rc = lw_refuse_clear_bands(ctx, bp))) return rc;   // (a call with bands is never sorted; nothing is enqueued yet)
   const CallSite c{ctx, 1, call_stream(ctx, 1, a->memspace)}; hipStream_t s = c.s;
   const int N = a->ncol, L = a->nlay;
   const size_t nl = (size_t)N * L, nl1 = (size_t)N * (L + 1);
@@ -296,22 +382,23 @@ int lw_fluxes_impl(rrtmg_ctx *ctx, const rrtmg_lw_args *a, const rrtmg_lw_band_f
     if (!d.mask || !d.anymask) ok = false;
   }
   const int ntile = (N + 63) / 64;
-  const int nk = d.idrv ? 6 : 4;
+  const int nk = clr ? (d.idrv ? 6 : 4) : lw_allsky_planes(d);   // partial planes per item (LwPartSink | LwPartSinkAllsky)
   const int hint_cloudy = call_hint_cloudy(ctx, 1, ntile, L);
   const int ctile = plan_call_chunks(ctx, 1, d, clouds, hint_cloudy, (size_t)kLwNGpt * LF_N * L * 64 * sizeof(double));   // tiles per solve chunk
   if (!d.tlist) ok = false;
   d.scratch = wd("scratch", (size_t)ctile * kLwNGpt * LF_N * L * 64);
   d.part = wd("part", (size_t)T.nitem * nk * (L + 1) * ctile * 64);
   double *const u[6] = {a->uflx, a->dflx, a->hr, a->uflxc, a->dflxc, a->hrc};
-  if ((rc = check_outputs(ctx, u))) return rc;
-  if (d.idrv && (!a->duflx_dt || !a->duflxc_dt)) return ctx->fail(RRTMG_ERR_ARG, "idrv=1 needs duflx_dt/duflxc_dt");
+  if ((rc = check_outputs(ctx, u, clr ? 6 : 3))) return rc;
+  if (d.idrv && (!a->duflx_dt || (clr && !a->duflxc_dt))) return ctx->fail(RRTMG_ERR_ARG, clr ? "idrv=1 needs duflx_dt/duflxc_dt" : "idrv=1 needs duflx_dt");
+  // (clear-sky outputs off: d.uflxc, d.dflxc, d.hrc and d.duflxc_dt stay nullptr -- no kernel of that path dereferences them)
   if (a->memspace == 1) {
-    d.uflx = a->uflx; d.dflx = a->dflx; d.hr = a->hr; d.uflxc = a->uflxc; d.dflxc = a->dflxc; d.hrc = a->hrc;
-    d.duflx_dt = a->duflx_dt; d.duflxc_dt = a->duflxc_dt;
+    d.uflx = a->uflx; d.dflx = a->dflx; d.hr = a->hr; d.duflx_dt = a->duflx_dt;
+    if (clr) { d.uflxc = a->uflxc; d.dflxc = a->dflxc; d.hrc = a->hrc; d.duflxc_dt = a->duflxc_dt; }
   } else {
-    d.uflx = wd("o.uflx", nl1); d.dflx = wd("o.dflx", nl1); d.hr = wd("o.hr", nl); d.uflxc = wd("o.uflxc", nl1);
-    d.dflxc = wd("o.dflxc", nl1); d.hrc = wd("o.hrc", nl);
-    if (d.idrv) { d.duflx_dt = wd("o.du", nl1); d.duflxc_dt = wd("o.duc", nl1); }
+    d.uflx = wd("o.uflx", nl1); d.dflx = wd("o.dflx", nl1); d.hr = wd("o.hr", nl);
+    if (clr) { d.uflxc = wd("o.uflxc", nl1); d.dflxc = wd("o.dflxc", nl1); d.hrc = wd("o.hrc", nl); }
+    if (d.idrv) { d.duflx_dt = wd("o.du", nl1); if (clr) d.duflxc_dt = wd("o.duc", nl1); }
   }
   // band fluxes: [16][nrow][ncol] per requested member
   static const rrtmg_lw_band_fluxes no_band{}; const rrtmg_lw_band_fluxes &br = bp ? *bp : no_band;   // (nothing requested: every member nullptr)
@@ -351,15 +438,22 @@ int lw_fluxes_impl(rrtmg_ctx *ctx, const rrtmg_lw_args *a, const rrtmg_lw_band_f
       if (clouds && d.mcica) hipLaunchKernelGGL(lw_cloudmc_kernel, dim3(nt, L), blk, 0, s, d, T, t0);
       hipLaunchKernelGGL(tile_lists_kernel, dim3(1), blk, 0, s, d.tile_cld + t0, nt, (int32_t *)d.tlist, (int32_t *)d.tcnt, d.tcap);
     },
-    [&](int t0, int nt) { hipLaunchKernelGGL((lw_solve_all_kernel<false, false>), lwgrid(nt), lwwg, 0, s, d, T, t0, nt); },
     [&](int t0, int nt) {
-      if (maxrand) hipLaunchKernelGGL((lw_solve_all_kernel<true, true>), lwgrid(nt), lwwg, 0, s, d, T, t0, nt);
+      if (!clr) hipLaunchKernelGGL((lw_solve_all_allsky_kernel<false, false>), lwgrid(nt), lwwg, 0, s, d, T, t0, nt);
+      else hipLaunchKernelGGL((lw_solve_all_kernel<false, false>), lwgrid(nt), lwwg, 0, s, d, T, t0, nt);
+    },
+    [&](int t0, int nt) {
+      if (!clr && maxrand) hipLaunchKernelGGL((lw_solve_all_allsky_kernel<true, true>), lwgrid(nt), lwwg, 0, s, d, T, t0, nt);
+      else if (!clr) hipLaunchKernelGGL((lw_solve_all_allsky_kernel<true, false>), lwgrid(nt), lwwg, 0, s, d, T, t0, nt);
+      else if (maxrand) hipLaunchKernelGGL((lw_solve_all_kernel<true, true>), lwgrid(nt), lwwg, 0, s, d, T, t0, nt);
       else hipLaunchKernelGGL((lw_solve_all_kernel<true, false>), lwgrid(nt), lwwg, 0, s, d, T, t0, nt);
     },
     [&](int t0, int nt) {
-      hipLaunchKernelGGL(lw_fluxheat_kernel, dim3(nt, (L + kFluxLev) / kFluxLev), dim3(64 * (kFluxLev + 1)), 0, s, d, T, t0);
-      if (bp && bp->levels) hipLaunchKernelGGL(lw_bandflux_kernel, dim3(nt, 1), dim3(64 * 2), 0, s, d, T, t0, bo, 1);
-      else if (bp) hipLaunchKernelGGL(lw_bandflux_kernel, dim3(nt, (L + kBandLev) / kBandLev), dim3(64 * kBandLev), 0, s, d, T, t0, bo, 0);
+      const auto flux_k = clr ? lw_fluxheat_kernel : lw_fluxheat_allsky_kernel;
+      const auto band_k = clr ? lw_bandflux_kernel : lw_bandflux_allsky_kernel;
+      hipLaunchKernelGGL(flux_k, dim3(nt, (L + kFluxLev) / kFluxLev), dim3(64 * (kFluxLev + 1)), 0, s, d, T, t0);
+      if (bp && bp->levels) hipLaunchKernelGGL(band_k, dim3(nt, 1), dim3(64 * 2), 0, s, d, T, t0, bo, 1);
+      else if (bp) hipLaunchKernelGGL(band_k, dim3(nt, (L + kBandLev) / kBandLev), dim3(64 * kBandLev), 0, s, d, T, t0, bo, 0);
     });
 #ifdef RRTMG_PROFILE
   {
@@ -377,6 +471,10 @@ int lw_fluxes_impl(rrtmg_ctx *ctx, const rrtmg_lw_args *a, const rrtmg_lw_band_f
 #endif
   // the inner call of a sorted one stops here, enqueued: permuted_tail scatters behind it and runs the epilogue
   if (ctx->inner != kInnerNone) { RRTMG_HIP_CHECK(ctx, hipGetLastError()); return RRTMG_OK; }
+  if (!clr) {   // three downloads (four with idrv), not six (eight), and the band members up / dn behind them
+    OutCopy oa[8] = {{a->uflx, d.uflx, nl1}, {a->dflx, d.dflx, nl1}, {a->hr, d.hr, nl}, {a->duflx_dt, d.duflx_dt, nl1}};
+    return call_finish(c, a->memspace, oa, opt_out_append(bpt, 4, nband, oa, d.idrv ? 4 : 3), d.err);
+  }
   OutCopy oc[12] = {{a->uflx, d.uflx, nl1}, {a->dflx, d.dflx, nl1}, {a->uflxc, d.uflxc, nl1}, {a->dflxc, d.dflxc, nl1},
                     {a->hr, d.hr, nl}, {a->hrc, d.hrc, nl}, {a->duflx_dt, d.duflx_dt, nl1}, {a->duflxc_dt, d.duflxc_dt, nl1}};
   return call_finish(c, a->memspace, oc, opt_out_append(bpt, 4, nband, oc, d.idrv ? 8 : 6), d.err);   // the requested band fluxes behind the same synchronise
@@ -388,6 +486,7 @@ int radiation_fluxes_impl(rrtmg_ctx *ctx, const rrtmg_sw_args *sw, const rrtmg_s
                           const rrtmg_lw_args *lw, const rrtmg_lw_band_fluxes *lb) {
   if (int rc = call_begin(ctx, 0, sw)) return rc;
   if (int rc = call_begin(ctx, 1, lw)) return rc;
+  if (int rc = lw_refuse_clear_bands(ctx, lb)) return rc;
   return joint_run(ctx, [=]() { return sw_fluxes_impl(ctx, sw, sf, c, b); }, [=]() { return lw_fluxes_impl(ctx, lw, lb); });
 }
 

@@ -960,6 +960,29 @@ RRTMG_HD LwPartSink lw_part_sink(const LwDev &d, int slot, int col) {
   return s;
 }
 
+// The sink of a call without the clear-sky outputs (rrtmg_hip_set_lw_clear_sky(0)): part[item][k][level][column] holds the total
+// planes only, k = 0 up, 1 down (2 = d/dTs of 0 with idrv) -- half the planes of LwPartSink, in every tile.  dn / up: the
+// one-stream mode of lw_solve_thread (ONE); dn_clear / up_clear: its cloud-free variant, which never had a second stream.
+struct LwPartSinkAllsky {
+  double *p;       // part + (slot*nk*(L+1))*N + col
+  long N, st;      // st = (L+1)*N
+  bool idrv;
+  RRTMG_HD void dn(int lev, double rd) { part_store(p + st + (long)lev * N, rd); }
+  RRTMG_HD void up(int lev, double ru, double du) {
+    part_store(p + (long)lev * N, ru);
+    if (idrv) part_store(p + 2 * st + (long)lev * N, du);
+  }
+  RRTMG_HD void dn_clear(int lev, double rd) { dn(lev, rd); }
+  RRTMG_HD void up_clear(int lev, double ru, double du) { up(lev, ru, du); }
+};
+RRTMG_HD int lw_allsky_planes(const LwDev &d) { return d.idrv ? 3 : 2; }
+RRTMG_HD LwPartSinkAllsky lw_part_sink_allsky(const LwDev &d, int slot, int col) {
+  LwPartSinkAllsky s;
+  s.N = d.pcols; s.st = (long)(d.nlay + 1) * d.pcols; s.idrv = d.idrv != 0;
+  s.p = d.part + ((long)slot * lw_allsky_planes(d) * (d.nlay + 1)) * d.pcols + (col - d.col0);
+  return s;
+}
+
 // quotient of the Pade table index x/(bpade + x): the IEEE division (the index decides which table entry is read)
 #define LW_TDIV(a, b) ((a) / (b))
 // (clamped to the table, 0 .. ntbl: these are per-lane GLOBAL gathers, and an optical depth that is negative or not a number
@@ -1039,7 +1062,11 @@ RRTMG_HD void lw_cells(const LwLut &lut, bool icldlyr, const double *odepth_in, 
 // CLD = false: the caller guarantees a cloud-free column (the cloud code is compiled out).
 // MR = true (non-McICA icld >= 2): rtrnmr, maximum/random overlap of the cloudy layers (rrtmg_lw_rtrnmr.f90:454-700)
 // with the column's overlap factors from lw_mr_column; MR = false: rtrn / rtrnmc.
-template <int BAND, int G, bool CLD, bool MR, bool LDSK, class Sink>
+// ONE (rrtmg_hip_set_lw_clear_sky(0): no clear-sky outputs; CLD = true only): the total-sky stream alone, every operation on it
+// as written for the two-stream mode -- the clear-sky recurrences (radclrd, radclru, iclddn, d_radclru_dt) and their sums are not
+// formed, and the sink (LwPartSinkAllsky) takes the total planes only.  The four scratch rows of a cloudy layer remain: the
+// cfrac / efclfrac blend and rtrnmr read atrans and the gas source going up.
+template <int BAND, int G, bool CLD, bool MR, bool LDSK, bool ONE, class Sink>
 RRTMG_HD void lw_solve_thread(const LwDev &d, const LwTab &T, int col, int ig0, double *scr, long stride, Sink &sink, const double *kb) {
   const int L = d.nlay, N = d.ncol;
   const int ib = BAND - 1;
@@ -1086,8 +1113,11 @@ RRTMG_HD void lw_solve_thread(const LwDev &d, const LwTab &T, int col, int ig0, 
   double cldrad[G], clrrad[G], radmr[G];   // rtrnmr: cloudy / clear parts of the radiance and the overlap carry `rad`
   int iclddn[G];
 #pragma unroll
-  for (int g = 0; g < G; ++g) { radld[g] = 0.0; radclrd[g] = 0.0; plfrac_bot[g] = 0.0; iclddn[g] = 0; cldrad[g] = 0.0; clrrad[g] = 0.0; radmr[g] = 0.0; }
-  if constexpr (CLD) sink.dn(L, 0.0, 0.0); else sink.dn_clear(L, 0.0);
+  for (int g = 0; g < G; ++g) {
+    radld[g] = 0.0; plfrac_bot[g] = 0.0; cldrad[g] = 0.0; clrrad[g] = 0.0; radmr[g] = 0.0;
+    if constexpr (!ONE) { radclrd[g] = 0.0; iclddn[g] = 0; }
+  }
+  if constexpr (ONE) sink.dn(L, 0.0); else if constexpr (CLD) sink.dn(L, 0.0, 0.0); else sink.dn_clear(L, 0.0);
   double plev_up = lw_planck_finish(lw_planck_fetch(T, ib, d.tlev[(long)L * N + col]));   // Planck function at the interface above the layer
   RRTMG_PH_DECL
   RRTMG_PH_MARK(0, plev_up)      // 0: setup before the sweep
@@ -1165,7 +1195,7 @@ RRTMG_HD void lw_solve_thread(const LwDev &d, const LwTab &T, int col, int ig0, 
       const LwCell &c = cells[g];
       const double atrans = c.atrans, bbd = c.bbd, bbugas = c.bbugas;
       if (icldlyr) {
-        iclddn[g] = 1;
+        if constexpr (!ONE) iclddn[g] = 1;
         const double gassrc = c.gassrc, atot = c.atot, bbdtot = c.bbdtot, bbutot = c.bbutot;
         if constexpr (MR) {
           if (mr_start == 1.0) { cldrad[g] = cfrac * radld[g]; clrrad[g] = radld[g] - cldrad[g]; radmr[g] = 0.0; }
@@ -1189,12 +1219,15 @@ RRTMG_HD void lw_solve_thread(const LwDev &d, const LwTab &T, int col, int ig0, 
       }
       v_atrans[g] = atrans;
       v_bbugas[g] = bbugas;
-      if (iclddn[g] == 1) {
-        radclrd[g] = radclrd[g] + (bbd - radclrd[g]) * atrans;
-      } else {
-        radclrd[g] = radld[g];
+      if constexpr (!ONE) {
+        if (iclddn[g] == 1) {
+          radclrd[g] = radclrd[g] + (bbd - radclrd[g]) * atrans;
+        } else {
+          radclrd[g] = radld[g];
+        }
       }
-      srd = srd + W(radld[g]); srcd = srcd + W(radclrd[g]);
+      srd = srd + W(radld[g]);
+      if constexpr (!ONE) srcd = srcd + W(radclrd[g]);
       plfrac_bot[g] = plf;
     }
     RRTMG_PH_MARK(4, radld[0] + radld[G - 1] + srd)      // 4: table index, exp/tfn lookups, recurrence of the G g-points
@@ -1202,7 +1235,7 @@ RRTMG_HD void lw_solve_thread(const LwDev &d, const LwTab &T, int col, int ig0, 
     scr_store<G>(SP(LF_BBUGAS, l), stride, v_bbugas);
     if (icldlyr) { scr_store<G>(SP(LF_ATOT, l), stride, v_atot); scr_store<G>(SP(LF_BBUTOT, l), stride, v_bbutot); }
     (void)v_od;
-    if constexpr (CLD) sink.dn(lev - 1, srd, srcd); else sink.dn_clear(lev - 1, srd);
+    if constexpr (ONE) sink.dn(lev - 1, srd); else if constexpr (CLD) sink.dn(lev - 1, srd, srcd); else sink.dn_clear(lev - 1, srd);
     RRTMG_PH_MARK(5, srd)      // 5: scratch rows and partial sums stored
   }
 
@@ -1218,15 +1251,18 @@ RRTMG_HD void lw_solve_thread(const LwDev &d, const LwTab &T, int col, int ig0, 
     for (int g = 0; g < G; ++g) {
       const double rad0 = plfrac_bot[g] * plankbnd;
       radlu[g] = rad0 + reflect * radld[g];
-      radclru[g] = rad0 + reflect * radclrd[g];
-      d_radlu_dt[g] = 0.0; d_radclru_dt[g] = 0.0;
+      if constexpr (!ONE) radclru[g] = rad0 + reflect * radclrd[g];
+      d_radlu_dt[g] = 0.0;
+      if constexpr (!ONE) d_radclru_dt[g] = 0.0;
       if (d.idrv) {
         const double d_rad0_dt = plfrac_bot[g] * (semiss * lw_planck_deriv(T, ib, tbound));
-        d_radlu_dt[g] = d_rad0_dt; d_radclru_dt[g] = d_rad0_dt;
+        d_radlu_dt[g] = d_rad0_dt;
+        if constexpr (!ONE) d_radclru_dt[g] = d_rad0_dt;
       }
-      s0 = s0 + W(radlu[g]); s1 = s1 + W(radclru[g]); s2 = s2 + W(d_radlu_dt[g]); s3 = s3 + W(d_radclru_dt[g]);
+      s0 = s0 + W(radlu[g]); s2 = s2 + W(d_radlu_dt[g]);
+      if constexpr (!ONE) { s1 = s1 + W(radclru[g]); s3 = s3 + W(d_radclru_dt[g]); }
     }
-    if constexpr (CLD) sink.up(0, s0, s1, s2, s3); else sink.up_clear(0, s0, s2);
+    if constexpr (ONE) sink.up(0, s0, s2); else if constexpr (CLD) sink.up(0, s0, s1, s2, s3); else sink.up_clear(0, s0, s2);
   }
 
   // ---- upward sweep: kU layers at a time, their scratch rows are loaded before the first is used ----------
@@ -1309,52 +1345,58 @@ RRTMG_HD void lw_solve_thread(const LwDev &d, const LwTab &T, int col, int ig0, 
           radlu[g] = radlu[g] + (bbugas - radlu[g]) * atrans;
           if (d.idrv) d_radlu_dt[g] = d_radlu_dt[g] * (1.0 - atrans);
         }
-        if (iclddn[g] == 1) {
-          radclru[g] = radclru[g] + (bbugas - radclru[g]) * atrans;
-          if (d.idrv) d_radclru_dt[g] = d_radclru_dt[g] * (1.0 - atrans);
-        } else {
-          radclru[g] = radlu[g];
-          if (d.idrv) d_radclru_dt[g] = d_radlu_dt[g];
+        if constexpr (!ONE) {
+          if (iclddn[g] == 1) {
+            radclru[g] = radclru[g] + (bbugas - radclru[g]) * atrans;
+            if (d.idrv) d_radclru_dt[g] = d_radclru_dt[g] * (1.0 - atrans);
+          } else {
+            radclru[g] = radlu[g];
+            if (d.idrv) d_radclru_dt[g] = d_radlu_dt[g];
+          }
         }
-        s0 = s0 + W(radlu[g]); s1 = s1 + W(radclru[g]); s2 = s2 + W(d_radlu_dt[g]); s3 = s3 + W(d_radclru_dt[g]);
+        s0 = s0 + W(radlu[g]); s2 = s2 + W(d_radlu_dt[g]);
+        if constexpr (!ONE) { s1 = s1 + W(radclru[g]); s3 = s3 + W(d_radclru_dt[g]); }
       }
-      if constexpr (CLD) sink.up(lev, s0, s1, s2, s3); else sink.up_clear(lev, s0, s2);
+      if constexpr (ONE) sink.up(lev, s0, s2); else if constexpr (CLD) sink.up(lev, s0, s1, s2, s3); else sink.up_clear(lev, s0, s2);
     }
   }
+  (void)radclrd; (void)radclru; (void)iclddn; (void)d_radclru_dt;
   RRTMG_PH_MARK(6, radlu[0])      // 6: surface + the whole upward sweep
   RRTMG_PH_FLUSH(d)
 }
 
 // Dispatch of one work item (packed, see LwTab) for one column: band switch + G in {4, 2}.
-template <int BAND, bool CLD, bool MR, bool LDSK, class Sink>
+template <int BAND, bool CLD, bool MR, bool LDSK, bool ONE, class Sink>
 RRTMG_HD void lw_solve_band(const LwDev &d, const LwTab &T, int g, int col, int ig0, double *scr, long stride, Sink &sink, const double *kb) {
   constexpr int ng = kLwNg[BAND - 1];
   if constexpr (ng >= 4) {
-    if (g == 4) { lw_solve_thread<BAND, 4, CLD, MR, LDSK>(d, T, col, ig0, scr, stride, sink, kb); return; }
+    if (g == 4) { lw_solve_thread<BAND, 4, CLD, MR, LDSK, ONE>(d, T, col, ig0, scr, stride, sink, kb); return; }
   }
-  if constexpr (ng % 4 != 0) lw_solve_thread<BAND, 2, CLD, MR, LDSK>(d, T, col, ig0, scr, stride, sink, kb);
+  if constexpr (ng % 4 != 0) lw_solve_thread<BAND, 2, CLD, MR, LDSK, ONE>(d, T, col, ig0, scr, stride, sink, kb);
 }
 // LDSK / kb: see lw_taug (kb = the workgroup's LDS slice of the item's band slab, or nullptr with LDSK = false)
-template <bool CLD, bool MR, bool LDSK = false, class Sink>
+// ONE: see lw_solve_thread (with CLD = true and an LwPartSinkAllsky only)
+template <bool CLD, bool MR, bool LDSK = false, bool ONE = false, class Sink>
 RRTMG_HD void lw_solve_item(const LwDev &d, const LwTab &T, int item, int col, double *scr, long stride, Sink &sink, const double *kb = nullptr) {
+  static_assert(!ONE || CLD, "the one-stream mode is a mode of the cloudy variant: a cloud-free column has no second stream to drop");
   const int g = (item >> 16) & 0xf, ig0 = (item >> 8) & 0xff;
   switch ((item & 0xff) + 1) {
-    case 1: lw_solve_band<1, CLD, MR, LDSK>(d, T, g, col, ig0, scr, stride, sink, kb); break;
-    case 2: lw_solve_band<2, CLD, MR, LDSK>(d, T, g, col, ig0, scr, stride, sink, kb); break;
-    case 3: lw_solve_band<3, CLD, MR, LDSK>(d, T, g, col, ig0, scr, stride, sink, kb); break;
-    case 4: lw_solve_band<4, CLD, MR, LDSK>(d, T, g, col, ig0, scr, stride, sink, kb); break;
-    case 5: lw_solve_band<5, CLD, MR, LDSK>(d, T, g, col, ig0, scr, stride, sink, kb); break;
-    case 6: lw_solve_band<6, CLD, MR, LDSK>(d, T, g, col, ig0, scr, stride, sink, kb); break;
-    case 7: lw_solve_band<7, CLD, MR, LDSK>(d, T, g, col, ig0, scr, stride, sink, kb); break;
-    case 8: lw_solve_band<8, CLD, MR, LDSK>(d, T, g, col, ig0, scr, stride, sink, kb); break;
-    case 9: lw_solve_band<9, CLD, MR, LDSK>(d, T, g, col, ig0, scr, stride, sink, kb); break;
-    case 10: lw_solve_band<10, CLD, MR, LDSK>(d, T, g, col, ig0, scr, stride, sink, kb); break;
-    case 11: lw_solve_band<11, CLD, MR, LDSK>(d, T, g, col, ig0, scr, stride, sink, kb); break;
-    case 12: lw_solve_band<12, CLD, MR, LDSK>(d, T, g, col, ig0, scr, stride, sink, kb); break;
-    case 13: lw_solve_band<13, CLD, MR, LDSK>(d, T, g, col, ig0, scr, stride, sink, kb); break;
-    case 14: lw_solve_band<14, CLD, MR, LDSK>(d, T, g, col, ig0, scr, stride, sink, kb); break;
-    case 15: lw_solve_band<15, CLD, MR, LDSK>(d, T, g, col, ig0, scr, stride, sink, kb); break;
-    default: lw_solve_band<16, CLD, MR, LDSK>(d, T, g, col, ig0, scr, stride, sink, kb); break;
+    case 1: lw_solve_band<1, CLD, MR, LDSK, ONE>(d, T, g, col, ig0, scr, stride, sink, kb); break;
+    case 2: lw_solve_band<2, CLD, MR, LDSK, ONE>(d, T, g, col, ig0, scr, stride, sink, kb); break;
+    case 3: lw_solve_band<3, CLD, MR, LDSK, ONE>(d, T, g, col, ig0, scr, stride, sink, kb); break;
+    case 4: lw_solve_band<4, CLD, MR, LDSK, ONE>(d, T, g, col, ig0, scr, stride, sink, kb); break;
+    case 5: lw_solve_band<5, CLD, MR, LDSK, ONE>(d, T, g, col, ig0, scr, stride, sink, kb); break;
+    case 6: lw_solve_band<6, CLD, MR, LDSK, ONE>(d, T, g, col, ig0, scr, stride, sink, kb); break;
+    case 7: lw_solve_band<7, CLD, MR, LDSK, ONE>(d, T, g, col, ig0, scr, stride, sink, kb); break;
+    case 8: lw_solve_band<8, CLD, MR, LDSK, ONE>(d, T, g, col, ig0, scr, stride, sink, kb); break;
+    case 9: lw_solve_band<9, CLD, MR, LDSK, ONE>(d, T, g, col, ig0, scr, stride, sink, kb); break;
+    case 10: lw_solve_band<10, CLD, MR, LDSK, ONE>(d, T, g, col, ig0, scr, stride, sink, kb); break;
+    case 11: lw_solve_band<11, CLD, MR, LDSK, ONE>(d, T, g, col, ig0, scr, stride, sink, kb); break;
+    case 12: lw_solve_band<12, CLD, MR, LDSK, ONE>(d, T, g, col, ig0, scr, stride, sink, kb); break;
+    case 13: lw_solve_band<13, CLD, MR, LDSK, ONE>(d, T, g, col, ig0, scr, stride, sink, kb); break;
+    case 14: lw_solve_band<14, CLD, MR, LDSK, ONE>(d, T, g, col, ig0, scr, stride, sink, kb); break;
+    case 15: lw_solve_band<15, CLD, MR, LDSK, ONE>(d, T, g, col, ig0, scr, stride, sink, kb); break;
+    default: lw_solve_band<16, CLD, MR, LDSK, ONE>(d, T, g, col, ig0, scr, stride, sink, kb); break;
   }
 }
 
@@ -1380,6 +1422,20 @@ RRTMG_HD void lw_flux_sums(const LwDev &d, int col, int lev, int nparts, bool cl
   if (!cld) { t2 = t0; t3 = t1; t5 = t4; }   // the clear-sky variant wrote the total planes only (LwPartSink::dn_clear)
   out[0] = t0 * d.fluxfac; out[1] = t1 * d.fluxfac; out[2] = t2 * d.fluxfac; out[3] = t3 * d.fluxfac;
   out[4] = t4 * d.fluxfac; out[5] = t5 * d.fluxfac;
+}
+// The same for a call without the clear-sky outputs: LwPartSinkAllsky's planes, in every tile; the sums in the order of t0, t1,
+// t4 above.  out[0..2] = uflx, dflx, duflx_dt
+RRTMG_HD void lw_flux_sums_allsky(const LwDev &d, int col, int lev, int nparts, double *out) {
+  const int L = d.nlay;
+  const int nk = lw_allsky_planes(d);
+  const long st = (long)(L + 1) * d.pcols;
+  double t0 = 0.0, t1 = 0.0, t4 = 0.0;
+  for (int iw = 0; iw < nparts; ++iw) {
+    const double *p = d.part + ((long)iw * nk * (L + 1) + lev) * d.pcols + (col - d.col0);
+    t0 = t0 + part_load(p); t1 = t1 + part_load(p + st);
+    if (d.idrv) t4 = t4 + part_load(p + 2 * st);
+  }
+  out[0] = t0 * d.fluxfac; out[1] = t1 * d.fluxfac; out[2] = t4 * d.fluxfac;
 }
 // Outputs of rrtmg_hip_lw_fluxes_bands, [16][nrow][ncol] (nrow = nlay+1, or 2: surface and top); a NULL member is not
 // written and its planes are not read.
@@ -1410,6 +1466,25 @@ RRTMG_HD void lw_band_level(const LwDev &d, const LwTab &T, const LwBandOut &o, 
     t0 = 0.0; t1 = 0.0; t2 = 0.0; t3 = 0.0;
   }
 }
+// lw_band_level of a call without the clear-sky outputs: o.up and o.dn from LwPartSinkAllsky's planes (o.upc, o.dnc: refused by
+// the driver, not looked at here)
+RRTMG_HD void lw_band_level_allsky(const LwDev &d, const LwTab &T, const LwBandOut &o, int col, int lev, int row, int nrow) {
+  const int L = d.nlay;
+  const int nk = lw_allsky_planes(d);
+  const long st = (long)(L + 1) * d.pcols;
+  double t0 = 0.0, t1 = 0.0;
+  for (int iw = 0; iw < T.nitem; ++iw) {
+    const double *p = d.part + ((long)iw * nk * (L + 1) + lev) * d.pcols + (col - d.col0);
+    if (o.up) t0 = t0 + part_load(p);
+    if (o.dn) t1 = t1 + part_load(p + st);
+    const int band = T.item[iw] & 0xff;
+    if (iw + 1 < T.nitem && (T.item[iw + 1] & 0xff) == band) continue;
+    const long i = ((long)band * nrow + row) * d.ncol + col;
+    if (o.up) o.up[i] = t0 * d.fluxfac;
+    if (o.dn) o.dn[i] = t1 * d.fluxfac;
+    t0 = 0.0; t1 = 0.0;
+  }
+}
 RRTMG_HD void lw_flux_level(const LwDev &d, const LwTab &T, int col, int lev, int nparts, bool cld) {
   (void)T;
   double f[6];
@@ -1427,6 +1502,24 @@ RRTMG_HD void lw_heat_layer(const LwDev &d, const LwTab &T, int col, int lay) {
   const double dp = d.plev[o0] - d.plev[o1];
   d.hr[o0] = T.heatfac * (fnet0 - fnet1) / dp;
   d.hrc[o0] = T.heatfac * (fnetc0 - fnetc1) / dp;
+}
+
+// The two above without the clear-sky outputs: uflx, dflx, hr (and duflx_dt) only; d.uflxc, d.dflxc, d.hrc and d.duflxc_dt are
+// not dereferenced (the arithmetic of lw_fluxheat_allsky_kernel, for the host emulation)
+RRTMG_HD void lw_flux_level_allsky(const LwDev &d, const LwTab &T, int col, int lev, int nparts) {
+  (void)T;
+  double f[3];
+  lw_flux_sums_allsky(d, col, lev, nparts, f);
+  const long o = (long)lev * d.ncol + col;
+  d.uflx[o] = f[0]; d.dflx[o] = f[1];
+  if (d.idrv) d.duflx_dt[o] = f[2];
+}
+RRTMG_HD void lw_heat_layer_allsky(const LwDev &d, const LwTab &T, int col, int lay) {
+  const int N = d.ncol;
+  const long o0 = (long)lay * N + col, o1 = o0 + N;
+  const double fnet0 = d.uflx[o0] - d.dflx[o0], fnet1 = d.uflx[o1] - d.dflx[o1];
+  const double dp = d.plev[o0] - d.plev[o1];
+  d.hr[o0] = T.heatfac * (fnet0 - fnet1) / dp;
 }
 
 }  // namespace rrtmg

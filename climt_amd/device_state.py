@@ -341,29 +341,39 @@ def longwave_device_call(self, ds):
     il, ml = (nlay + 1, ncol), (nlay, ncol)
     self._device_calls = getattr(self, "_device_calls", 0) + 1
     w = lambda key, shape, dims, units: ds.work(("lw", id(self), key, self._device_calls & 1), shape, dims, units)
-    fl = {k: w(k, il, ("interface_levels", "*"), "W m^-2") for k in ("uflx", "dflx", "uflxc", "dflxc")}
-    hr, hrc = w("hr", ml, ("mid_levels", "*"), "degK day^-1"), w("hrc", ml, ("mid_levels", "*"), "degK day^-1")
+    clear = getattr(self, "_clear_sky", True)      # False: no buffers for the clear-sky outputs, which the library then leaves out
+    fl = {k: w(k, il, ("interface_levels", "*"), "W m^-2") for k in (("uflx", "dflx", "uflxc", "dflxc") if clear else ("uflx", "dflx"))}
+    hr = w("hr", ml, ("mid_levels", "*"), "degK day^-1")
     out = {k: v.ptr for k, v in fl.items()}
-    out.update(hr=hr.ptr, hrc=hrc.ptr)
+    out.update(hr=hr.ptr)
+    if clear:
+        hrc = w("hrc", ml, ("mid_levels", "*"), "degK day^-1")
+        out.update(hrc=hrc.ptr)
     if self._calc_dflxdt:
-        du, duc = w("duflx_dt", il, ("interface_levels", "*"), "W m^-2 K^-1"), w("duflxc_dt", il, ("interface_levels", "*"), "W m^-2 K^-1")
-        out.update(duflx_dt=du.ptr, duflxc_dt=duc.ptr)
+        du = w("duflx_dt", il, ("interface_levels", "*"), "W m^-2 K^-1")
+        duc = w("duflxc_dt", il, ("interface_levels", "*"), "W m^-2 K^-1") if clear else None
+        out.update(duflx_dt=du.ptr)
+        if clear:
+            out.update(duflxc_dt=duc.ptr)
         self.change_in_upward_flux_with_surface_temperature, self.change_in_clear_sky_upward_flux_with_surface_temperature = du, duc
     bands = None
     if getattr(self, "_band_fluxes", False):
         from .rrtmg.longwave import BAND_FLUX_DIAGNOSTICS
-        bands = {b: w("band." + b, (16,) + il, ("num_longwave_bands", "interface_levels", "*"), "W m^-2") for b in BAND_FLUX_DIAGNOSTICS.values()}
+        names = getattr(self, "_band_names", tuple(BAND_FLUX_DIAGNOSTICS))
+        bands = {BAND_FLUX_DIAGNOSTICS[k]: w("band." + BAND_FLUX_DIAGNOSTICS[k], (16,) + il, ("num_longwave_bands", "interface_levels", "*"), "W m^-2") for k in names}
+    self._apply_clear_sky(ds.ctx)
     if bands:
         ds.ctx.lw_fluxes(inp, mcica=self._mcica, out=out, memspace=1, bands={b: q.ptr for b, q in bands.items()})
     else:
         ds.ctx.lw_fluxes(inp, mcica=self._mcica, out=out, memspace=1)
     ds._lw_inflight = True      # consumers on the main stream (tendency sum, slab, the next derived fields) join first: join_streams()
-    diagnostics = {
-        "upwelling_longwave_flux_in_air": fl["uflx"], "downwelling_longwave_flux_in_air": fl["dflx"],
-        "upwelling_longwave_flux_in_air_assuming_clear_sky": fl["uflxc"], "downwelling_longwave_flux_in_air_assuming_clear_sky": fl["dflxc"],
-        "air_temperature_tendency_from_longwave_assuming_clear_sky": hrc, "air_temperature_tendency_from_longwave": hr}
+    diagnostics = {"upwelling_longwave_flux_in_air": fl["uflx"], "downwelling_longwave_flux_in_air": fl["dflx"],
+                   "air_temperature_tendency_from_longwave": hr}
+    if clear:
+        diagnostics.update({"upwelling_longwave_flux_in_air_assuming_clear_sky": fl["uflxc"], "downwelling_longwave_flux_in_air_assuming_clear_sky": fl["dflxc"],
+                            "air_temperature_tendency_from_longwave_assuming_clear_sky": hrc})
     if bands:
-        diagnostics.update({k: bands[b] for k, b in BAND_FLUX_DIAGNOSTICS.items()})
+        diagnostics.update({k: bands[b] for k, b in BAND_FLUX_DIAGNOSTICS.items() if b in bands})
     return {"air_temperature": hr}, diagnostics
 
 

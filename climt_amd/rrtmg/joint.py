@@ -111,6 +111,7 @@ def radiation_step(shortwave, longwave, state):
     sw_call = shortwave._prepare_call(_raw_view(raw, shortwave))
     lw_call = longwave._prepare_call(_raw_view(raw, longwave))
     shortwave._apply_night_skip(ctx)
+    longwave._apply_clear_sky(ctx)
     ctx.radiation_fluxes(sw=sw_call["library"], lw=lw_call["library"])
     sw_t, sw_d = shortwave._finish_call(sw_call)
     lw_t, lw_d = longwave._finish_call(lw_call)

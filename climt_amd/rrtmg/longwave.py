@@ -26,7 +26,8 @@ def _prop(dims, units):
 _ML, _IL = ["mid_levels", "*"], ["interface_levels", "*"]
 
 
-# the diagnostics of RRTMGLongwave(band_fluxes=True) -> member of rrtmg_lw_band_fluxes: the broadband names with _by_band
+# the diagnostics of RRTMGLongwave(band_fluxes=True) (band_fluxes=[names]: those of them that are listed) -> member of
+# rrtmg_lw_band_fluxes: the broadband names with _by_band
 # appended; dims [num_longwave_bands, interface_levels, *], bands 1..16
 BAND_FLUX_DIAGNOSTICS = {
     "upwelling_longwave_flux_in_air_by_band": "up",
@@ -36,9 +37,19 @@ BAND_FLUX_DIAGNOSTICS = {
 }
 _BIL = ["num_longwave_bands", "interface_levels", "*"]
 
+# the diagnostics an instance made with clear_sky_diagnostics=False does not have -> the library's output behind each
+CLEAR_SKY_DIAGNOSTICS = {
+    "upwelling_longwave_flux_in_air_assuming_clear_sky": "uflxc",
+    "downwelling_longwave_flux_in_air_assuming_clear_sky": "dflxc",
+    "air_temperature_tendency_from_longwave_assuming_clear_sky": "hrc",
+}
+# the band diagnostics that read the clear-sky stream
+CLEAR_SKY_BAND_DIAGNOSTICS = tuple(k for k, b in BAND_FLUX_DIAGNOSTICS.items() if b in ("upc", "dnc"))
+
 
 class RRTMGLongwave(TendencyComponent):
-    """The Rapid Radiative Transfer Model (RRTMG), longwave, on AMD MI355X."""
+    """The Rapid Radiative Transfer Model (RRTMG), longwave, on AMD MI355X.  Additions to the reference's keyword arguments
+    (see __init__): `band_fluxes` (True, or a list of BAND_FLUX_DIAGNOSTICS names) and `clear_sky_diagnostics`."""
 
     num_longwave_bands = 16
     num_reduced_g_intervals = 140
@@ -82,24 +93,45 @@ class RRTMGLongwave(TendencyComponent):
     }
 
     @classmethod
-    def diagnostic_properties_for(cls, band_fluxes=False):
-        """The diagnostic_properties of an instance made with that `band_fluxes`: the class dict itself, or a new dict of it
-        plus the four band fluxes (bands x interface levels, W m^-2)."""
-        if not band_fluxes:
+    def diagnostic_properties_for(cls, band_fluxes=False, clear_sky_diagnostics=True):
+        """The diagnostic_properties of an instance made with these options: the class dict itself, or a new dict of it
+        plus the band fluxes (bands x interface levels, W m^-2) -- the four of BAND_FLUX_DIAGNOSTICS for True, or the names
+        given -- or without the three CLEAR_SKY_DIAGNOSTICS."""
+        if not band_fluxes and clear_sky_diagnostics:
             return cls.diagnostic_properties
-        return dict(cls.diagnostic_properties, **{k: _prop(_BIL, "W m^-2") for k in BAND_FLUX_DIAGNOSTICS})
+        props = {k: v for k, v in cls.diagnostic_properties.items() if clear_sky_diagnostics or k not in CLEAR_SKY_DIAGNOSTICS}
+        if band_fluxes:
+            props.update({k: _prop(_BIL, "W m^-2") for k in (BAND_FLUX_DIAGNOSTICS if band_fluxes is True else band_fluxes)})
+        return props
 
     def __init__(self, calculate_change_up_flux=False, cloud_overlap_method=None, cloud_optical_properties="liquid_and_ice_clouds",
                  cloud_ice_properties="ebert_curry_two", cloud_liquid_water_properties="radius_dependent_absorption",
                  calculate_interface_temperature=True, mcica=False, random_number_generator="mersenne_twister", device=0,
-                 allow_synthetic_tables=False, band_fluxes=False, **kwargs):
+                 allow_synthetic_tables=False, band_fluxes=False, clear_sky_diagnostics=True, **kwargs):
         """Same keyword arguments and defaults as climt.RRTMGLongwave (lw/component.py:167-178); additions: `device`
         (GPU ordinal), `allow_synthetic_tables` (see the module docstring) and `band_fluxes`: True adds the up / down fluxes
-        (all sky, clear sky) by spectral band (BAND_FLUX_DIAGNOSTICS) to this instance's diagnostics; the class attributes are
-        unchanged."""
-        self._band_fluxes = bool(band_fluxes)
-        if self._band_fluxes:
-            self.diagnostic_properties = self.diagnostic_properties_for(True)
+        (all sky, clear sky) by spectral band (BAND_FLUX_DIAGNOSTICS) to this instance's diagnostics -- or, given as a list
+        of those names, the ones listed; the class attributes are unchanged; `clear_sky_diagnostics`: False takes the three
+        `*_assuming_clear_sky` quantities (CLEAR_SKY_DIAGNOSTICS) out of this instance's diagnostics and has the library form no
+        clear-sky stream (rrtmg_hip_set_lw_clear_sky): columns with cloud carry one recurrence per sweep, not two, and the
+        clear-sky outputs are not copied; the other diagnostics and the tendency are those of the default instance;
+        change_in_clear_sky_upward_flux_with_surface_temperature stays None.  Not together with clear-sky band diagnostics
+        (band_fluxes=True, or a list naming one of CLEAR_SKY_BAND_DIAGNOSTICS: ValueError); all-sky band diagnostics (a list of
+        the other two names) stay allowed."""
+        if isinstance(band_fluxes, (list, tuple, set, frozenset)):
+            unknown = [k for k in band_fluxes if k not in BAND_FLUX_DIAGNOSTICS]
+            if unknown:
+                raise ValueError("band_fluxes: unknown band diagnostic %r (one of %s)" % (unknown[0], ", ".join(BAND_FLUX_DIAGNOSTICS)))
+            self._band_names = tuple(k for k in BAND_FLUX_DIAGNOSTICS if k in band_fluxes)
+        else:
+            self._band_names = tuple(BAND_FLUX_DIAGNOSTICS) if band_fluxes else ()
+        self._band_fluxes = bool(self._band_names)
+        self._clear_sky = bool(clear_sky_diagnostics)
+        if not self._clear_sky and any(k in CLEAR_SKY_BAND_DIAGNOSTICS for k in self._band_names):
+            raise ValueError("clear_sky_diagnostics=False cannot be combined with the clear-sky band_fluxes (%s): ask for %s"
+                             % (", ".join(CLEAR_SKY_BAND_DIAGNOSTICS), ", ".join(k for k in BAND_FLUX_DIAGNOSTICS if k not in CLEAR_SKY_BAND_DIAGNOSTICS)))
+        if self._band_fluxes or not self._clear_sky:
+            self.diagnostic_properties = self.diagnostic_properties_for(self._band_names if self._band_fluxes else False, self._clear_sky)
         self.input_properties = RRTMGLongwave.input_properties.copy()
         self._calc_dflxdt = 1 if calculate_change_up_flux else 0
         self._mcica = mcica
@@ -151,10 +183,20 @@ class RRTMGLongwave(TendencyComponent):
             return longwave_device_call(self, state)
         return super(RRTMGLongwave, self).__call__(state, *args, **kwargs)
 
+    def _apply_clear_sky(self, ctx):
+        """Hands `clear_sky_diagnostics` to the context before a call: the context is shared between components, so each says
+        what it wants every time.  A context without the setting serves the default only."""
+        clear, setter = getattr(self, "_clear_sky", True), getattr(ctx, "set_lw_clear_sky", None)
+        if setter is not None and (not clear or getattr(ctx, "has_lw_clear_sky", True)):
+            setter(clear)
+        elif not clear:
+            raise RuntimeError("clear_sky_diagnostics=False: this context has no set_lw_clear_sky")
+
     @ensure_contiguous_state
     def array_call(self, state):
         """Longwave heating tendency and up/down fluxes (all-sky and clear-sky)."""
         call = self._prepare_call(state)
+        self._apply_clear_sky(self._ctx)
         self._ctx.lw_fluxes(**call["library"])
         return self._finish_call(call)
 
@@ -197,18 +239,19 @@ class RRTMGLongwave(TendencyComponent):
             inp.update(irng=self._random_number_generator, permuteseed=self._permute_seed)
         out = dict(
             uflx=diagnostics["upwelling_longwave_flux_in_air"], dflx=diagnostics["downwelling_longwave_flux_in_air"],
-            hr=tendencies["air_temperature"], uflxc=diagnostics["upwelling_longwave_flux_in_air_assuming_clear_sky"],
-            dflxc=diagnostics["downwelling_longwave_flux_in_air_assuming_clear_sky"],
-            hrc=diagnostics["air_temperature_tendency_from_longwave_assuming_clear_sky"])
+            hr=tendencies["air_temperature"])
+        clear = getattr(self, "_clear_sky", True)
+        if clear:
+            out.update({m: diagnostics[k] for k, m in CLEAR_SKY_DIAGNOSTICS.items()})
         if self._calc_dflxdt:
             # (computed, not returned -- as in the reference, lw/component.py:386-399.  From the liveness-tracked output pool,
             #  like every other result: an array the caller still holds from an earlier call is never written again)
-            for key in ("duflx_dt", "duflxc_dt"):
+            for key in (("duflx_dt", "duflxc_dt") if clear else ("duflx_dt",)):
                 out[key] = self._pool.zeros_like_fresh(key, (n_layers + 1, n_columns))
         self._input_staging.wait()
         library = dict(inp=inp, mcica=self._mcica, out=out)
         if self._band_fluxes:
-            library.update(bands={b: diagnostics[k] for k, b in BAND_FLUX_DIAGNOSTICS.items()})
+            library.update(bands={BAND_FLUX_DIAGNOSTICS[k]: diagnostics[k] for k in self._band_names})
         return dict(library=library, tendencies=tendencies, diagnostics=diagnostics)
 
     def _finish_call(self, call):
@@ -216,7 +259,7 @@ class RRTMGLongwave(TendencyComponent):
         tendencies, diagnostics, out = call["tendencies"], call["diagnostics"], call["library"]["out"]
         if self._calc_dflxdt:
             self.change_in_upward_flux_with_surface_temperature = out["duflx_dt"]
-            self.change_in_clear_sky_upward_flux_with_surface_temperature = out["duflxc_dt"]
+            self.change_in_clear_sky_upward_flux_with_surface_temperature = out.get("duflxc_dt")      # (None without the clear-sky stream)
         # the reference aliases (not copies) the tendency here (lw/component.py:518-520)
         diagnostics["air_temperature_tendency_from_longwave"] = tendencies["air_temperature"]
         return tendencies, diagnostics

@@ -192,6 +192,28 @@ int rrtmg_hip_set_sw_night_pack(rrtmg_ctx *ctx, int on);
  * The longwave is not touched.  The switch belongs to the context: a binder that shares one context between callers sets it
  * before each shortwave call.  Probe for it by symbol; the argument structs and RRTMG_HIP_ABI_VERSION are unchanged. */
 int rrtmg_hip_set_sw_clear_sky(rrtmg_ctx *ctx, int on);
+/* OPT-IN longwave call without the clear-sky outputs (on = 1 by default: nothing changes; the reference-compatible symbols on
+ * the default context always run with 1).  With on = 0 a longwave call forms no clear-sky stream: tiles with cloud run a one-stream
+ * solve (no clear-sky recurrence in either sweep, half the partial flux planes), and uflxc, dflxc, hrc and duflxc_dt are neither
+ * computed nor copied.  A NULL context returns RRTMG_ERR_ARG.
+ *  - Clear-sky outputs: uflxc, dflxc and hrc may be NULL; with idrv = 1 so may duflxc_dt (duflx_dt is still required).  Whatever
+ *    these pointers hold is ignored: on a device-pointer call (memspace 1) not one element is written; on a host-pointer call
+ *    the arrays are neither downloaded nor touched.
+ *  - All-sky outputs (uflx, dflx, hr, duflx_dt): a column of a cloud-free tile (64 columns) keeps its bits -- it runs the device
+ *    functions it always ran, which write the total planes only.  A column of a tile with cloud runs the same operations on the
+ *    total-sky stream in another instantiation: same bits as the default call (measured: the largest difference over the GPU
+ *    tests of tests/test_lw_allsky_only_gpu.py is 0, and they assert equality).
+ *  - Covers rrtmg_hip_lw_fluxes and the longwave half of rrtmg_hip_radiation_fluxes; mcica 0 and 1, icld 0 to 3, both random
+ *    number generators, an external cldfmcl, idrv 0 and 1; rtrn, rtrnmc and rtrnmr; column chunks, shard_col0 / shard_ncol and
+ *    deferred mode work as with on = 1.  Under rrtmg_hip_set_column_sort the permuted call's output table carries no entry for the
+ *    absent arrays.
+ *  - Band fluxes: rrtmg_hip_lw_fluxes_bands with upc or dnc requested returns RRTMG_ERR_ARG before anything is enqueued, and the
+ *    context stays usable; a band call that requests only up and / or dn is served (those members read the total planes only).
+ *    The same rule applies to lw_bands inside rrtmg_hip_radiation_fluxes.
+ * The shortwave is not touched: rrtmg_hip_set_sw_clear_sky and this switch are independent of each other.  The switch belongs
+ * to the context: a binder that shares one context between callers sets it before each longwave call.  Probe for it by symbol;
+ * the argument structs and RRTMG_HIP_ABI_VERSION are unchanged. */
+int rrtmg_hip_set_lw_clear_sky(rrtmg_ctx *ctx, int on);
 /* Night tiles and night columns (all of them: those of mixed tiles too) of the last completed shortwave call on this context:
  * valid after the call has returned, in deferred mode after rrtmg_hip_synchronize.  0 / 0 if that call ran with the skip off
  * (and the pack off); after a packed call (rrtmg_hip_set_sw_night_pack) the counts stated there.

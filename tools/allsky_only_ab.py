@@ -44,7 +44,7 @@ def main():
     print("# shortwave clear-sky outputs, setting 1 against 0, %d alternations after 2 warm-up rounds, medians (ms); sw: HIP events around one"
           " device-resident call (host row: host clock around the host-pointer call); solve: the shortwave solve kernels' event brackets of"
           " that call, summed; step: SW + LW deferred on two streams, host clock to the end of synchronize(); library %s src:%s"
-          % (os.path.basename(LIB_PATH), source_hash()))
+          % (args.alternations, os.path.basename(LIB_PATH), source_hash()))
     print("# %-28s %9s %9s %7s %9s %9s %7s %9s %9s %7s" % ("row", "sw 1", "sw 0", "0/1", "solve 1", "solve 0", "0/1", "step 1", "step 0", "0/1"))
     for name in args.rows.split(","):
         n, nlay, mcica, mixed, shard_of, host = ROWS[name]
