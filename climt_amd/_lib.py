@@ -70,7 +70,29 @@ class SwSurface(C.Structure):
     _fields_ = [("struct_size", _i32), ("reserved", _i32)] + [(n, _vp) for n in SW_SURFACE]
 
 
-def _surface_struct(surface, ncol, keep):
+PRECISIONS = {"float64": np.dtype(np.float64), "float32": np.dtype(np.float32)}   # the `precision` of a flux call -> element type of its grid arrays
+
+
+def _precision(precision):
+    if precision not in PRECISIONS:
+        raise ValueError("precision %r: one of %s" % (precision, ", ".join(repr(k) for k in PRECISIONS)))
+    return PRECISIONS[precision]
+
+
+def _device_pointer(v, dtype, what):
+    """`v` as the integer a struct member takes: a raw device pointer, or a climt_amd._hip.DeviceArray, whose dtype must be the call's."""
+    if hasattr(v, "ptr") and hasattr(v, "dtype"):
+        if np.dtype(v.dtype) != dtype:
+            raise ValueError("%s: a DeviceArray of dtype %s in a %s call" % (what, np.dtype(v.dtype).name, dtype.name))
+        return int(v.ptr)
+    return int(v)
+
+
+def _is_pointer(v):
+    return isinstance(v, (int, np.integer)) or (hasattr(v, "ptr") and hasattr(v, "dtype") and not isinstance(v, np.ndarray))
+
+
+def _surface_struct(surface, ncol, keep, dtype=PRECISIONS["float64"]):
     """The filled struct of a `surface=` input (Context.sw_fluxes): arrays [14][ncol] (kept alive in `keep`) or device pointers."""
     s = SwSurface()
     s.struct_size = C.sizeof(SwSurface)
@@ -79,10 +101,10 @@ def _surface_struct(surface, ncol, keep):
             raise KeyError("unknown surface input %r (one of %s)" % (k, ", ".join(SW_SURFACE)))
         if v is None:
             continue
-        if isinstance(v, (int, np.integer)):
-            setattr(s, k, int(v))
+        if _is_pointer(v):
+            setattr(s, k, _device_pointer(v, dtype, "surface input %r" % k))
             continue
-        arr = np.ascontiguousarray(v, dtype=np.float64)
+        arr = np.ascontiguousarray(v, dtype=dtype)
         if arr.shape != (SW_NBAND, ncol):
             raise ValueError("surface input %r: an array of %d x %d (band, column), not %r" % (k, SW_NBAND, ncol, arr.shape))
         keep.append(arr)
@@ -95,7 +117,7 @@ class LwBandFluxes(C.Structure):
     _fields_ = [("struct_size", _i32), ("levels", _i32)] + [(n, _vp) for n in LW_BAND_FLUXES]
 
 
-def _band_struct(cls, names, nband, bands, band_levels, nlay, ncol):
+def _band_struct(cls, names, nband, bands, band_levels, nlay, ncol, dtype=PRECISIONS["float64"]):
     """The filled struct of a `bands=` request (Context.sw_fluxes / lw_fluxes)."""
     if band_levels not in BAND_LEVELS:
         raise ValueError("band_levels %r: one of %s" % (band_levels, ", ".join(repr(k) for k in BAND_LEVELS)))
@@ -105,11 +127,11 @@ def _band_struct(cls, names, nband, bands, band_levels, nlay, ncol):
     for k, v in bands.items():
         if k not in names:
             raise KeyError("unknown band flux %r (one of %s)" % (k, ", ".join(names)))
-        if isinstance(v, (int, np.integer)):
-            setattr(b, k, int(v))
+        if _is_pointer(v):
+            setattr(b, k, _device_pointer(v, dtype, "band flux %r" % k))
             continue
-        if not (isinstance(v, np.ndarray) and v.dtype == np.float64 and v.flags.c_contiguous and v.size == nband * nrow * ncol):
-            raise ValueError("band flux %r: the library writes it in place: a C-contiguous float64 array of %d x %d x %d" % (k, nband, nrow, ncol))
+        if not (isinstance(v, np.ndarray) and v.dtype == dtype and v.flags.c_contiguous and v.size == nband * nrow * ncol):
+            raise ValueError("band flux %r: the library writes it in place: a C-contiguous %s array of %d x %d x %d" % (k, dtype.name, nband, nrow, ncol))
         setattr(b, k, v.ctypes.data)
     return b
 
@@ -198,6 +220,10 @@ def load_library():
     if hasattr(lib, "rrtmg_hip_radiation_fluxes"):       # (likewise)
         lib.rrtmg_hip_radiation_fluxes.argtypes = [_vp, C.POINTER(RadiationCall)]
         lib.rrtmg_hip_radiation_last.argtypes = [_vp, C.POINTER(C.c_int), C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]
+    if hasattr(lib, "rrtmg_hip_sw_fluxes_f32"):          # (likewise: the float32 boundary)
+        lib.rrtmg_hip_sw_fluxes_f32.argtypes = [_vp, C.POINTER(SwArgs), C.POINTER(SwSurface), C.POINTER(SwComponents), C.POINTER(SwBandFluxes)]
+        lib.rrtmg_hip_lw_fluxes_f32.argtypes = [_vp, C.POINTER(LwArgs), C.POINTER(LwBandFluxes)]
+        lib.rrtmg_hip_radiation_fluxes_f32.argtypes = [_vp, C.POINTER(RadiationCall)]
     lib.rrtmg_hip_copy_blocks.argtypes = [_vp, C.c_int, _vp, C.c_long, C.c_long, _vp, _vp, _vp]
     lib.rrtmg_hip_mcica_mask.argtypes = [_vp] + [C.c_int] * 6 + [_vp] * 3
     _lib = lib
@@ -492,7 +518,26 @@ class Context:
         return out
 
     # -- host-pointer calls: `inp` maps boundary names to numpy arrays (see _SW_FIELDS) -------
-    def _fill(self, a, inp, fields, flags, keep):
+    @property
+    def has_f32_boundary(self):
+        """Whether the library exports the float32 boundary (rrtmg_hip_{sw,lw,radiation}_fluxes_f32; probed by the symbols)."""
+        return all(hasattr(self.lib, n) for n in ("rrtmg_hip_sw_fluxes_f32", "rrtmg_hip_lw_fluxes_f32", "rrtmg_hip_radiation_fluxes_f32"))
+
+    def _f32_entry(self, name):
+        if not self.has_f32_boundary:
+            raise RRTMGError(4, "this librrtmg_hip.so has no %s (float32 boundary)" % name)
+        return getattr(self.lib, name)
+
+    @staticmethod
+    def _out_pointer(k, v, shape_size, dtype):
+        """An output of a call as the integer its struct member takes.  precision="float32" checks what the library will write into."""
+        if _is_pointer(v):
+            return _device_pointer(v, dtype, "output %r" % k)
+        if dtype != PRECISIONS["float64"] and not (isinstance(v, np.ndarray) and v.dtype == dtype and v.flags.c_contiguous and v.size == shape_size):
+            raise ValueError("output %r: the library writes it in place: a C-contiguous %s array of %d elements" % (k, dtype.name, shape_size))
+        return v.ctypes.data
+
+    def _fill(self, a, inp, fields, flags, keep, dtype=PRECISIONS["float64"]):
         for k, f in flags.items():
             if k in inp:
                 setattr(a, f, int(inp[k]))
@@ -503,15 +548,16 @@ class Context:
             v = inp.get(k)
             if v is None:
                 continue
-            if isinstance(v, (int, np.integer)):      # raw device pointer
-                setattr(a, f, int(v))
+            host64 = k in ("bndsolvar", "indsolvar")      # host arrays of a few doubles, whatever the precision of the grid arrays
+            if _is_pointer(v):      # raw device pointer (or a DeviceArray)
+                setattr(a, f, _device_pointer(v, PRECISIONS["float64"] if host64 else dtype, "input %r" % k))
             else:
-                arr = np.ascontiguousarray(v, dtype=np.float64)
+                arr = np.ascontiguousarray(v, dtype=np.float64 if host64 else dtype)
                 keep.append(arr)
                 setattr(a, f, arr.ctypes.data)
 
     @_locked
-    def sw_fluxes(self, inp, mcica=False, out=None, memspace=0, components=None, bands=None, band_levels="all", surface=None):
+    def sw_fluxes(self, inp, mcica=False, out=None, memspace=0, components=None, bands=None, band_levels="all", surface=None, precision="float64"):
         """`surface`: None, or a dict with "albdir" and / or "albdif": the surface albedo by band for the direct beam / for
         diffuse radiation, [14][ncol] arrays (device pointers with memspace=1), bands in the order of band_limits("sw")
         (rrtmg_hip_sw_fluxes_surface); the one left out follows from asdir / aldir (asdif / aldif) by the reference driver's band
@@ -519,10 +565,18 @@ class Context:
         `components`: None, or a dict SW_COMPONENTS name -> output (a C-contiguous float64 [nlay+1][ncol] array, or a device
         pointer with memspace=1) that the call fills as well (rrtmg_hip_sw_fluxes_components); the names left out are not
         computed.  `bands`: None, or a dict SW_BAND_FLUXES name -> output [14][nrow][ncol] in the same way
-        (rrtmg_hip_sw_fluxes_bands); `band_levels`: "all" (nrow = nlay+1) or "boundaries" (nrow = 2: surface, top)."""
+        (rrtmg_hip_sw_fluxes_bands); `band_levels`: "all" (nrow = nlay+1) or "boundaries" (nrow = 2: surface, top).
+        `precision`: "float64" (the default: exactly the call without the keyword) or "float32" -- the float32 boundary
+        (rrtmg_hip_sw_fluxes_f32): inputs are handed over as C-contiguous float32 (no copy of an array that already is one),
+        outputs, components and band arrays must be C-contiguous float32 arrays (device arrays: dtype float32), and the
+        results are those of the float64 call on the widened inputs, rounded once."""
         keep = []
-        a, sf, c, b, out = self._sw_structs(inp, mcica, out, memspace, components, bands, band_levels, surface, keep)
-        if sf is None and c is None and b is None:
+        dtype = _precision(precision)
+        a, sf, c, b, out = self._sw_structs(inp, mcica, out, memspace, components, bands, band_levels, surface, keep, dtype)
+        if dtype == PRECISIONS["float32"]:
+            self._ck(self._f32_entry("rrtmg_hip_sw_fluxes_f32")(self.h, C.byref(a), None if sf is None else C.byref(sf), None if c is None else C.byref(c),
+                                                               None if b is None else C.byref(b)))
+        elif sf is None and c is None and b is None:
             self._ck(self.lib.rrtmg_hip_sw_fluxes(self.h, C.byref(a)))
         elif sf is not None:
             self._ck(self.lib.rrtmg_hip_sw_fluxes_surface(self.h, C.byref(a), C.byref(sf), None if c is None else C.byref(c), None if b is None else C.byref(b)))
@@ -532,7 +586,7 @@ class Context:
             self._ck(self.lib.rrtmg_hip_sw_fluxes_components(self.h, C.byref(a), C.byref(c)))
         return out
 
-    def _sw_structs(self, inp, mcica, out, memspace, components, bands, band_levels, surface, keep):
+    def _sw_structs(self, inp, mcica, out, memspace, components, bands, band_levels, surface, keep, dtype=PRECISIONS["float64"]):
         """-> (rrtmg_sw_args, surface struct | None, components struct | None, band struct | None, out) of a shortwave call;
         the arrays the structs point into stay alive in `keep` (and in `out`, `components`, `bands`)."""
         nlay, ncol = (inp["nlay"], inp["ncol"]) if memspace else inp["play"].shape
@@ -541,83 +595,88 @@ class Context:
         a.ncol, a.nlay, a.memspace, a.mcica = int(ncol), int(nlay), int(memspace), int(bool(mcica))
         a.icld, a.inflgsw, a.iceflgsw, a.liqflgsw, a.dyofyr = 1, 2, 1, 1, 1
         a.adjes, a.scon, a.solcycfrac = float(inp.get("adjes", 1.0)), float(inp.get("scon", 1367.0)), float(inp.get("solcycfrac", 0.0))
-        self._fill(a, inp, _SW_FIELDS, _SW_FLAGS, keep)
+        self._fill(a, inp, _SW_FIELDS, _SW_FLAGS, keep, dtype)
         clear = getattr(self, "sw_clear_sky", True)      # (set_sw_clear_sky(False): the three clear-sky outputs may be absent -> NULL)
         if out is None:
-            out = {k: np.zeros((nlay + lev, ncol)) for k, lev in SW_OUT if clear or k in SW_OUT_ALLSKY}
-        for k, _ in SW_OUT:
+            out = {k: np.zeros((nlay + lev, ncol), dtype=dtype) for k, lev in SW_OUT if clear or k in SW_OUT_ALLSKY}
+        for k, lev in SW_OUT:
             v = out[k] if clear or k in SW_OUT_ALLSKY else out.get(k)
             if v is not None:
-                setattr(a, k, int(v) if isinstance(v, (int, np.integer)) else v.ctypes.data)
+                setattr(a, k, self._out_pointer(k, v, (nlay + lev) * ncol, dtype))
         if surface is None and (inp.get("albdir") is not None or inp.get("albdif") is not None):
             surface = {k: inp.get(k) for k in SW_SURFACE}
-        b = None if bands is None else _band_struct(SwBandFluxes, SW_BAND_FLUXES, SW_NBAND, bands, band_levels, nlay, ncol)
+        b = None if bands is None else _band_struct(SwBandFluxes, SW_BAND_FLUXES, SW_NBAND, bands, band_levels, nlay, ncol, dtype)
         sf = None
         if surface is not None:
             if not hasattr(self.lib, "rrtmg_hip_sw_fluxes_surface"):
                 raise RRTMGError(4, "this librrtmg_hip.so has no rrtmg_hip_sw_fluxes_surface (surface albedo by band)")
-            sf = _surface_struct(surface, ncol, keep)
-        c = None if components is None else self._components_struct(components, nlay, ncol)
+            sf = _surface_struct(surface, ncol, keep, dtype)
+        c = None if components is None else self._components_struct(components, nlay, ncol, dtype)
         return a, sf, c, b, out
 
     @staticmethod
-    def _components_struct(components, nlay, ncol):
+    def _components_struct(components, nlay, ncol, dtype=PRECISIONS["float64"]):
         c = SwComponents()
         c.struct_size = C.sizeof(SwComponents)
         for k, v in components.items():
             if k not in SW_COMPONENTS:
                 raise KeyError("unknown shortwave flux component %r (one of %s)" % (k, ", ".join(SW_COMPONENTS)))
-            if isinstance(v, (int, np.integer)):
-                setattr(c, k, int(v))
+            if _is_pointer(v):
+                setattr(c, k, _device_pointer(v, dtype, "component %r" % k))
                 continue
-            if not (isinstance(v, np.ndarray) and v.dtype == np.float64 and v.flags.c_contiguous and v.size == (nlay + 1) * ncol):
-                raise ValueError("component %r: the library writes it in place: a C-contiguous float64 array of %d x %d" % (k, nlay + 1, ncol))
+            if not (isinstance(v, np.ndarray) and v.dtype == dtype and v.flags.c_contiguous and v.size == (nlay + 1) * ncol):
+                raise ValueError("component %r: the library writes it in place: a C-contiguous %s array of %d x %d" % (k, dtype.name, nlay + 1, ncol))
             setattr(c, k, v.ctypes.data)
         return c
 
     @_locked
-    def lw_fluxes(self, inp, mcica=False, out=None, memspace=0, bands=None, band_levels="all"):
+    def lw_fluxes(self, inp, mcica=False, out=None, memspace=0, bands=None, band_levels="all", precision="float64"):
         """`bands`: None, or a dict LW_BAND_FLUXES name -> output (a C-contiguous float64 [16][nrow][ncol] array, or a device
         pointer with memspace=1) that the call fills as well (rrtmg_hip_lw_fluxes_bands); `band_levels`: "all" (nrow =
-        nlay+1) or "boundaries" (nrow = 2: surface, top)."""
+        nlay+1) or "boundaries" (nrow = 2: surface, top).  `precision`: as in sw_fluxes (rrtmg_hip_lw_fluxes_f32)."""
         keep = []
-        a, b, out = self._lw_structs(inp, mcica, out, memspace, bands, band_levels, keep)
-        if b is None:
+        dtype = _precision(precision)
+        a, b, out = self._lw_structs(inp, mcica, out, memspace, bands, band_levels, keep, dtype)
+        if dtype == PRECISIONS["float32"]:
+            self._ck(self._f32_entry("rrtmg_hip_lw_fluxes_f32")(self.h, C.byref(a), None if b is None else C.byref(b)))
+        elif b is None:
             self._ck(self.lib.rrtmg_hip_lw_fluxes(self.h, C.byref(a)))
         else:
             self._ck(self.lib.rrtmg_hip_lw_fluxes_bands(self.h, C.byref(a), C.byref(b)))
         return out
 
-    def _lw_structs(self, inp, mcica, out, memspace, bands, band_levels, keep):
+    def _lw_structs(self, inp, mcica, out, memspace, bands, band_levels, keep, dtype=PRECISIONS["float64"]):
         """-> (rrtmg_lw_args, band struct | None, out) of a longwave call (see _sw_structs)."""
         nlay, ncol = (inp["nlay"], inp["ncol"]) if memspace else inp["play"].shape
         a = LwArgs()
         a.struct_size = C.sizeof(LwArgs)
         a.ncol, a.nlay, a.memspace, a.mcica = int(ncol), int(nlay), int(memspace), int(bool(mcica))
         a.icld, a.inflglw, a.iceflglw, a.liqflglw = 1, 2, 1, 1
-        self._fill(a, inp, _LW_FIELDS, _LW_FLAGS, keep)
+        self._fill(a, inp, _LW_FIELDS, _LW_FLAGS, keep, dtype)
         clear = getattr(self, "lw_clear_sky", True)      # (set_lw_clear_sky(False): the clear-sky outputs may be absent or None -> NULL;
         #                                                    one that `out` does hold is handed over, and the library ignores it)
         if out is None:
-            out = {k: np.zeros((nlay + lev, ncol)) for k, lev in LW_OUT if clear or k not in LW_OUT_CLEAR}
+            out = {k: np.zeros((nlay + lev, ncol), dtype=dtype) for k, lev in LW_OUT if clear or k not in LW_OUT_CLEAR}
             if a.idrv:
-                out["duflx_dt"] = np.zeros((nlay + 1, ncol))
+                out["duflx_dt"] = np.zeros((nlay + 1, ncol), dtype=dtype)
                 if clear:
-                    out["duflxc_dt"] = np.zeros((nlay + 1, ncol))
+                    out["duflxc_dt"] = np.zeros((nlay + 1, ncol), dtype=dtype)
         for k in out:
             v = out[k]
             if v is not None:
-                setattr(a, k, int(v) if isinstance(v, (int, np.integer)) else v.ctypes.data)
-        b = None if bands is None else _band_struct(LwBandFluxes, LW_BAND_FLUXES, LW_NBAND, bands, band_levels, nlay, ncol)
+                setattr(a, k, self._out_pointer(k, v, (nlay + (0 if k in ("hr", "hrc") else 1)) * ncol, dtype))
+        b = None if bands is None else _band_struct(LwBandFluxes, LW_BAND_FLUXES, LW_NBAND, bands, band_levels, nlay, ncol, dtype)
         return a, b, out
 
     @_locked
-    def radiation_fluxes(self, sw, lw):
+    def radiation_fluxes(self, sw, lw, precision="float64"):
         """Both spectra of one host state in one library call (rrtmg_hip_radiation_fluxes): `sw` and `lw` are the keyword sets of
         sw_fluxes and lw_fluxes as dicts -- `inp`, and optionally `mcica`, `out`, `bands`, `band_levels`, and for the shortwave
         `components`, `surface`.  Host arrays only.  -> (sw out, lw out), bit for bit what sw_fluxes(**sw) followed by
         lw_fluxes(**lw) give.  An input that both `inp` hold as the same array (with the same unit factors) is uploaded once,
-        and the two spectra overlap on the GPU; radiation_last() says what was shared."""
+        and the two spectra overlap on the GPU; radiation_last() says what was shared.  `precision`: as in sw_fluxes, for both
+        spectra (rrtmg_hip_radiation_fluxes_f32)."""
+        dtype = _precision(precision)
         if not hasattr(self.lib, "rrtmg_hip_radiation_fluxes"):
             raise RRTMGError(4, "this librrtmg_hip.so has no rrtmg_hip_radiation_fluxes (joint shortwave + longwave call)")
         for name, kw, allowed in (("sw", sw, ("inp", "mcica", "out", "components", "bands", "band_levels", "surface")),
@@ -627,8 +686,8 @@ class Context:
                 raise TypeError("radiation_fluxes: %s takes 'inp' and optionally %s, not %s" % (name, ", ".join(allowed[1:]), ", ".join(map(repr, unknown)) or "nothing"))
         keep = []   # (every array the structs point into, until the call has returned)
         a, sf, c, b, sw_out = self._sw_structs(sw["inp"], sw.get("mcica", False), sw.get("out"), 0, sw.get("components"), sw.get("bands"),
-                                               sw.get("band_levels", "all"), sw.get("surface"), keep)
-        la, lb, lw_out = self._lw_structs(lw["inp"], lw.get("mcica", False), lw.get("out"), 0, lw.get("bands"), lw.get("band_levels", "all"), keep)
+                                               sw.get("band_levels", "all"), sw.get("surface"), keep, dtype)
+        la, lb, lw_out = self._lw_structs(lw["inp"], lw.get("mcica", False), lw.get("out"), 0, lw.get("bands"), lw.get("band_levels", "all"), keep, dtype)
         call = RadiationCall()
         call.struct_size = C.sizeof(RadiationCall)
         call.sw, call.lw = C.pointer(a), C.pointer(la)
@@ -640,7 +699,8 @@ class Context:
             call.sw_bands = C.pointer(b)
         if lb is not None:
             call.lw_bands = C.pointer(lb)
-        self._ck(self.lib.rrtmg_hip_radiation_fluxes(self.h, C.byref(call)))
+        entry = self._f32_entry("rrtmg_hip_radiation_fluxes_f32") if dtype == PRECISIONS["float32"] else self.lib.rrtmg_hip_radiation_fluxes
+        self._ck(entry(self.h, C.byref(call)))
         del keep
         return sw_out, lw_out
 

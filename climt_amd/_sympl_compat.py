@@ -188,7 +188,9 @@ except ImportError:
                 values = np.asarray(state[name].values)
                 key = name
                 if numeric:
-                    values = values.astype(np.float64, copy=False)
+                    # (a component with a float32 boundary takes 4-byte reals as they are: no widening copy on the host)
+                    if values.dtype != getattr(self, "_boundary_dtype", np.float64):
+                        values = values.astype(np.float64, copy=False)
                     if factor is not None and name in on_device and values.ndim >= 2:
                         unit_factors[name] = factor
                         key = name + "@raw"

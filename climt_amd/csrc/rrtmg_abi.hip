@@ -80,12 +80,17 @@ int copy_out_enqueue(rrtmg_ctx *ctx, hipStream_t s, const OutCopy *o, int count,
   // A destination that is page-locked memory the runtime knows (hipHostMalloc / hipHostRegister: the components' output pool
   // hands such arrays out) takes its copy directly; the others go through the staging buffer.
   if (count > kMaxOut) return ctx->fail(RRTMG_ERR_ARG, "copy_out: %d output arrays (at most %d)", count, kMaxOut);
-  po.count = count; po.total = 0; po.herr = 0; po.slot = slot; po.has_flag = herr_dev != nullptr; po.enqueued = false;
+  // A float32-boundary call (ctx->f32): ONE narrow launch on s for all the outputs, into a float staging buffer of the device;
+  // what comes down, and what the caller's arrays hold, are 4 n bytes each.
+  const size_t elem = ctx->f32 ? sizeof(float) : sizeof(double);
+  po.count = count; po.total = 0; po.herr = 0; po.slot = slot; po.has_flag = herr_dev != nullptr; po.enqueued = false; po.elem = elem;
+  size_t all = 0;
   for (int i = 0; i < count; ++i) {
     hipPointerAttribute_t at;
     po.oc[i] = o[i];
     po.direct[i] = hipPointerGetAttributes(&at, o[i].host) == hipSuccess && at.type == hipMemoryTypeHost;
-    if (!po.direct[i]) po.total += o[i].n * sizeof(double);
+    if (!po.direct[i]) po.total += o[i].n * elem;
+    all += (o[i].n + 3) / 4 * 4;   // (every output starts 16-byte aligned in the float staging buffer)
   }
   (void)hipGetLastError();   // (an unknown pointer is an error code of the query, not of this call)
   if (po.total > ctx->pinned_cap[slot]) {
@@ -96,10 +101,22 @@ int copy_out_enqueue(rrtmg_ctx *ctx, hipStream_t s, const OutCopy *o, int count,
   }
   char *p = (char *)ctx->pinned[slot];
   if (herr_dev) RRTMG_HIP_CHECK(ctx, hipMemcpyAsync(&ctx->flag_host[slot], herr_dev, sizeof(int), hipMemcpyDeviceToHost, s));
-  size_t off = 0;
+  const float *narrow = nullptr;
+  if (ctx->f32 && all) {
+    float *q = (float *)ctx->buf(slot == 0 ? "out.f32.0" : "out.f32.1", all * sizeof(float));
+    if (!q) return ctx->status;
+    PrecisionBatch nb(s, false);
+    size_t at = 0;
+    for (int i = 0; i < count; ++i) { nb.add(o[i].dev, q + at, o[i].n); at += (o[i].n + 3) / 4 * 4; }
+    nb.flush();
+    narrow = q;
+  }
+  size_t off = 0, at = 0;
   for (int i = 0; i < count; ++i) {
-    RRTMG_HIP_CHECK(ctx, hipMemcpyAsync(po.direct[i] ? (char *)o[i].host : p + off, o[i].dev, o[i].n * sizeof(double), hipMemcpyDeviceToHost, s));
-    if (!po.direct[i]) off += o[i].n * sizeof(double);
+    const void *dev = narrow ? (const void *)(narrow + at) : (const void *)o[i].dev;
+    RRTMG_HIP_CHECK(ctx, hipMemcpyAsync(po.direct[i] ? (char *)o[i].host : p + off, dev, o[i].n * elem, hipMemcpyDeviceToHost, s));
+    if (!po.direct[i]) off += o[i].n * elem;
+    at += (o[i].n + 3) / 4 * 4;
   }
   po.enqueued = true;
   return RRTMG_OK;
@@ -123,7 +140,7 @@ void copy_out_complete(rrtmg_ctx *ctx, PendingOut &po) {
     size_t off2 = 0;
     for (int i = 0; i < count; ++i) {
       if (direct[i]) continue;
-      const size_t bytes = o[i].n * sizeof(double), per = (bytes / nt + 4095) & ~(size_t)4095;
+      const size_t bytes = o[i].n * po.elem, per = (bytes / nt + 4095) & ~(size_t)4095;
       const size_t lo = (size_t)t * per, hi = lo + per < bytes ? lo + per : bytes;
       if (lo < bytes) memcpy((char *)o[i].host + lo, p + off2 + lo, hi - lo);
       off2 += bytes;
@@ -256,6 +273,7 @@ void HostInputs::add(const double **slot, const double *host, size_t n, const ch
   }
   if (memspace_ == 1) { *slot = host; return; }   // device pointers are used as they are
   Entry e{slot, host, n, name, policy, mul, div};
+  e.f32 = f32_;
   entries_.push_back(e);
 }
 
@@ -264,6 +282,15 @@ bool HostInputs::upload(const Entry &e) {
   double *dp = (double *)ctx_->buf(key, e.n * sizeof(double));
   if (!dp) return false;
   ctx_->bufs[key].uniform = false;
+  if (e.f32) {   // 4 n bytes up into the staging buffer; widened, with the unit factor, by the batch's one launch (finish)
+    float *st = (float *)ctx_->buf(key + ".f32", e.n * sizeof(float));
+    if (!st) return false;
+    if (hipMemcpyAsync(st, e.host, e.n * sizeof(float), hipMemcpyHostToDevice, s_) != hipSuccess) { ctx_->fail(RRTMG_ERR_HIP, "H2D copy of '%s' failed", e.name); return false; }
+    widen_.add(st, dp, e.n, e.mul, e.div);
+    *e.slot = dp;
+    resolved(e, dp, e.n * sizeof(float));
+    return true;
+  }
   if (hipMemcpyAsync(dp, e.host, e.n * sizeof(double), hipMemcpyHostToDevice, s_) != hipSuccess) { ctx_->fail(RRTMG_ERR_HIP, "H2D copy of '%s' failed", e.name); return false; }
   if (e.mul != 0.0) launch_scale(s_, dp, e.n, e.mul, e.div);
   *e.slot = dp;
@@ -295,7 +322,7 @@ bool HostInputs::finish() {
   bool brought = false;
   if (share_)
     for (Entry &e : entries_) {
-      e.taken = share_->acquire(share_key(e.host, e.n, e.mul, e.div, (int)e.policy), owner_, &e.share) != ShareTable::Found::New;
+      e.taken = share_->acquire(share_key(e.host, e.n, e.mul, e.div, (int)e.policy, e.f32 ? 4 : 8), owner_, &e.share) != ShareTable::Found::New;
       if (!e.taken) brought = true;
     }
   std::unique_ptr<ScanJob[]> jobs(new ScanJob[entries_.size() + 1]);
@@ -303,13 +330,25 @@ bool HostInputs::finish() {
   for (Entry &e : entries_) {
     if (e.taken || e.n < kScanMin) continue;
     const uint64_t *q = (const uint64_t *)e.host;
-    const uint64_t w0 = q[0];
+    size_t nq = e.n;
+    uint64_t w0;
     uint64_t acc = 0;
-    for (size_t i = 1; i < 2048; ++i) acc |= q[i] ^ w0;                       // the head ...
-    for (size_t k = 1; k <= 16; ++k) acc |= q[(e.n - 1) / 16 * k] ^ w0;        // ... and sixteen places further on
+    if (e.f32) {
+      // 4-byte patterns, compared two at a time: the words from the first 8-byte aligned element on, against the first
+      // element's pattern twice; the odd element behind them on its own
+      const uint32_t *f = (const uint32_t *)e.host;
+      const size_t skip = ((uintptr_t)f & 7) ? 1 : 0;
+      q = (const uint64_t *)(f + skip); nq = (e.n - skip) / 2;
+      w0 = (uint64_t)f[0] | (uint64_t)f[0] << 32;
+      if ((e.n - skip) & 1) acc |= f[e.n - 1] ^ f[0];
+    } else {
+      w0 = q[0];
+    }
+    for (size_t i = 0; i < 2048; ++i) acc |= q[i] ^ w0;                       // the head ...
+    for (size_t k = 1; k <= 16; ++k) acc |= q[(nq - 1) / 16 * k] ^ w0;         // ... and sixteen places further on
     if (acc) continue;                                                         // certainly not uniform: goes up at once
     e.job = njobs;
-    jobs[njobs].q = q; jobs[njobs].n = e.n; jobs[njobs].first = w0;
+    jobs[njobs].q = q; jobs[njobs].n = nq; jobs[njobs].first = w0;
     ++njobs;
   }
   HostPool::Batch batch;
@@ -321,11 +360,13 @@ bool HostInputs::finish() {
     if (e.job < 0) continue;
     const ScanJob &j = jobs[e.job];
     if (j.differs.load()) { if (!upload(e)) ok_ = false; continue; }
-    if (e.policy == InPolicy::ZeroAbsent && j.first == 0) { *e.slot = nullptr; resolved(e, nullptr, 0); continue; }   // all +0.0: the "array absent" path adds the same
+    if (e.policy == InPolicy::ZeroAbsent && j.first == 0) { *e.slot = nullptr; resolved(e, nullptr, 0); continue; }   // all +0.0 (+0.0f): the "array absent" path adds the same
     double v;
-    memcpy(&v, &j.first, sizeof v);
+    if (e.f32) { float f; memcpy(&f, &j.first, sizeof f); v = (double)f; }   // (exact: fill() applies the factors to it as to a double)
+    else memcpy(&v, &j.first, sizeof v);
     if (!fill(e, v)) ok_ = false;
   }
+  widen_.flush();   // behind every upload of the batch, in front of what the call enqueues next and of the table's event
   if (!share_) return ok_;
   // One event behind the last write of this batch into a buffer the table names; a batch that takes what the OTHER spectrum's
   // stream wrote waits for that spectrum's event on its own stream (what its own stream wrote is ordered already).
@@ -399,10 +440,11 @@ static int sw_optional_checked(rrtmg_ctx *ctx, const rrtmg_sw_surface *&sf, cons
   if (c && !(c->dirdflx || c->difdflx || c->dirdnuv || c->difdnuv || c->dirdnir || c->difdnir || c->dirdflxc || c->difdflxc)) c = nullptr;
   return 0;
 }
-static int sw_fluxes_checked(rrtmg_ctx *ctx, const rrtmg_sw_args *a, const rrtmg_sw_surface *sf, const rrtmg_sw_components *c, const rrtmg_sw_band_fluxes *b) {
+// (f32: the float32 boundary, rrtmg_precision.h -- the same checks in the same order, then the driver behind the boundary)
+static int sw_fluxes_checked(rrtmg_ctx *ctx, const rrtmg_sw_args *a, const rrtmg_sw_surface *sf, const rrtmg_sw_components *c, const rrtmg_sw_band_fluxes *b, bool f32 = false) {
   if (!ctx) return RRTMG_ERR_ARG;
   if (int rc = sw_optional_checked(ctx, sf, c, b)) return rc;
-  return checked_call(ctx, a, "rrtmg_sw", [sf, c, b](rrtmg_ctx *x, const rrtmg_sw_args *y) { return sw_fluxes_impl(x, y, sf, c, b); });
+  return checked_call(ctx, a, "rrtmg_sw", [sf, c, b, f32](rrtmg_ctx *x, const rrtmg_sw_args *y) { return f32 ? sw_fluxes_f32_impl(x, y, sf, c, b) : sw_fluxes_impl(x, y, sf, c, b); });
 }
 // the longwave's band struct, likewise
 static int lw_optional_checked(rrtmg_ctx *ctx, const rrtmg_lw_band_fluxes *&b) {
@@ -596,7 +638,7 @@ int rrtmg_hip_lw_fluxes_bands(rrtmg_ctx *ctx, const rrtmg_lw_args *a, const rrtm
 }
 // Both spectra of one host state (radiation_fluxes_impl; rrtmg_call.h: joint_run).  Every check of the separate entry points, through the same helpers,
 // and the three of the joint call, before anything is enqueued.
-int rrtmg_hip_radiation_fluxes(rrtmg_ctx *ctx, const rrtmg_radiation_call *call) {
+static int radiation_fluxes_checked(rrtmg_ctx *ctx, const rrtmg_radiation_call *call, bool f32) {
   if (!ctx) return RRTMG_ERR_ARG;
   if (!call) return ctx->fail(RRTMG_ERR_ARG, "rrtmg_radiation_call: NULL argument struct");
   if (int rc = check_struct(ctx, call, "rrtmg_radiation_call")) return rc;
@@ -612,10 +654,24 @@ int rrtmg_hip_radiation_fluxes(rrtmg_ctx *ctx, const rrtmg_radiation_call *call)
         return ctx->fail(RRTMG_ERR_ARG, "rrtmg_hip_radiation_fluxes: the shortwave has %d x %d columns x layers, the longwave %d x %d", (int)sw->ncol, (int)sw->nlay, (int)lw->ncol, (int)lw->nlay);
       if (sw->shard_col0 != lw->shard_col0 || sw->shard_ncol != lw->shard_ncol)
         return ctx->fail(RRTMG_ERR_ARG, "rrtmg_hip_radiation_fluxes: shard_col0 / shard_ncol differ between the two structs");
-      return radiation_fluxes_impl(ctx, sw, sf, c, b, lw, lb);
+      ctx->f32 = f32;   // (host pointers: both drivers upload and download 4-byte reals for the duration of the call)
+      const int rc = radiation_fluxes_impl(ctx, sw, sf, c, b, lw, lb);
+      ctx->f32 = false;
+      return rc;
     });
   });
 }
+int rrtmg_hip_radiation_fluxes(rrtmg_ctx *ctx, const rrtmg_radiation_call *call) { return radiation_fluxes_checked(ctx, call, false); }
+// The float32 boundary (rrtmg_precision.h): the entry point chooses the precision of ITS call
+int rrtmg_hip_sw_fluxes_f32(rrtmg_ctx *ctx, const rrtmg_sw_args *a, const rrtmg_sw_surface *surface, const rrtmg_sw_components *c, const rrtmg_sw_band_fluxes *b) {
+  return sw_fluxes_checked(ctx, a, surface, c, b, true);
+}
+int rrtmg_hip_lw_fluxes_f32(rrtmg_ctx *ctx, const rrtmg_lw_args *a, const rrtmg_lw_band_fluxes *b) {
+  if (!ctx) return RRTMG_ERR_ARG;
+  if (int rc = lw_optional_checked(ctx, b)) return rc;
+  return checked_call(ctx, a, "rrtmg_lw", [b](rrtmg_ctx *x, const rrtmg_lw_args *y) { return lw_fluxes_f32_impl(x, y, b); });
+}
+int rrtmg_hip_radiation_fluxes_f32(rrtmg_ctx *ctx, const rrtmg_radiation_call *call) { return radiation_fluxes_checked(ctx, call, true); }
 int rrtmg_hip_radiation_last(rrtmg_ctx *ctx, int *arrays_shared, long long *bytes_uploaded, long long *bytes_shared) {
   if (!ctx || !arrays_shared || !bytes_uploaded || !bytes_shared || !ctx->joint_seen) return RRTMG_ERR_ARG;
   *arrays_shared = ctx->joint_arrays_shared; *bytes_uploaded = ctx->joint_bytes_uploaded; *bytes_shared = ctx->joint_bytes_shared;

@@ -175,6 +175,48 @@ inline int permuted_tail(const CallSite &c, ColumnPermute &pm, Inner inner, int3
   pm.flush_scatter(night_out);
   return call_finish(c, 1, nullptr, 0, ctx->err_dev + c.which);
 }
+// ---- the float32 boundary of a device-resident call (rrtmg_precision.h; the input and output lists are the spectrum's own) -------
+// The caller's device arrays hold float.  in(): the internal fp64 copy of an input (nullptr stays nullptr), registered for the
+// ONE widen launch; out(): the inner call's fp64 array for the caller's `user`, registered for the ONE narrow launch.  The
+// copies live in named grow-only work buffers ("sw.f32.", "lw.f32.").  The inner call is the ordinary device-resident driver:
+// the sort, the pack, deferred mode and every other option run inside it unchanged.
+struct BoundaryF32 {
+  rrtmg_ctx *ctx;
+  std::string prefix;
+  PrecisionBatch widen, narrow;
+  bool ok = true;
+  BoundaryF32(rrtmg_ctx *c, hipStream_t s, const char *pre) : ctx(c), prefix(pre), widen(s, true), narrow(s, false) {}
+  double *buf(const char *name, size_t n) {
+    double *p = (double *)ctx->buf(prefix + name, n * sizeof(double));
+    if (!p) ok = false;
+    return p;
+  }
+  const double *in(const char *name, const double *user, size_t n) {
+    if (!user) return nullptr;
+    double *p = buf(name, n);
+    if (p) widen.add(user, p, n);
+    return p;
+  }
+  double *out(const char *name, double *user, size_t n) {
+    if (!user) return nullptr;
+    double *p = buf(name, n);
+    if (p) narrow.add(p, user, n);
+    return p;
+  }
+};
+// inner(): the fp64 driver on the copies.  It returns with its own epilogue done -- enqueued in deferred mode, else complete
+// and its flag read -- and the narrow launch goes behind its last kernel (or its scatter) on the same stream; a synchronous
+// call then waits for it.  A call that fails returns the inner call's status, and the caller's outputs are not written.
+template <class Inner>
+inline int boundary_f32_tail(const CallSite &c, BoundaryF32 &bf, Inner inner) {
+  rrtmg_ctx *ctx = c.ctx;
+  bf.widen.flush();
+  if (const int rc = inner()) return rc;
+  bf.narrow.flush();
+  RRTMG_HIP_CHECK(ctx, hipGetLastError());
+  if (!ctx->deferred) RRTMG_HIP_CHECK(ctx, hipStreamSynchronize(c.s));
+  return RRTMG_OK;
+}
 // ---- the joint call: both spectra of one host state in one call -----------------------------------------------------------------
 // sw(), lw(): the two drivers on their checked arguments.  While ctx->joint is set they differ from separate calls in three
 // places, all above: call_stream (the longwave on stream_lw), call_share (inputs the shortwave has brought to the device are

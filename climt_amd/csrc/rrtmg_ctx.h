@@ -135,6 +135,10 @@ struct rrtmg_ctx {
   // cloud-free columns first
   bool sort_columns = false;
   rrtmg::InnerCall inner = rrtmg::kInnerNone;   // the call being enqueued is the inner call of a sorted / packed one
+  // rrtmg_hip_*_fluxes_f32 with host pointers in progress (rrtmg_precision.h): the grid arrays of the structs point to float --
+  // HostInputs uploads 4 n bytes and widens on the device, copy_out narrows on the device and downloads 4 n bytes.  Set by the
+  // entry point for the duration of the call, never by the caller: precision is chosen per call
+  bool f32 = false;
   std::string err;
   int status = 0;
   rrtmg::Constants k{};
@@ -219,7 +223,8 @@ int copy_out(rrtmg_ctx *ctx, hipStream_t s, const OutCopy *o, int count, int *he
 // the caller's arrays.  po.herr then holds the flag.  Every copy lands in page-locked memory (the flag in ctx->flag_host), so
 // that enqueueing never waits for the stream: a device-to-host copy into pageable memory would.  copy_out is the two around hipStreamSynchronize(s).
 constexpr int kMaxOut = 24;   // shortwave: 6 outputs + 8 components + 6 band arrays
-struct PendingOut { OutCopy oc[kMaxOut]; bool direct[kMaxOut]; int count = 0; size_t total = 0; int herr = 0; int slot = 0; bool has_flag = false, enqueued = false; };
+// elem: bytes per element on the host side -- 8, or 4 in a float32-boundary call (OutCopy::host then points to float)
+struct PendingOut { OutCopy oc[kMaxOut]; bool direct[kMaxOut]; int count = 0; size_t total = 0; int herr = 0; int slot = 0; bool has_flag = false, enqueued = false; size_t elem = sizeof(double); };
 int copy_out_enqueue(rrtmg_ctx *ctx, hipStream_t s, const OutCopy *o, int count, int *herr_dev, PendingOut &po, int slot);
 void copy_out_complete(rrtmg_ctx *ctx, PendingOut &po);
 // One rrtmg_hip_radiation_fluxes call: the inputs it has brought to the device, and per spectrum [sw|lw] the output copies
@@ -244,6 +249,9 @@ void free_lw_desc(rrtmg_ctx *ctx);
 int sw_fluxes_impl(rrtmg_ctx *ctx, const rrtmg_sw_args *a, const rrtmg_sw_surface *sf = nullptr, const rrtmg_sw_components *c = nullptr,
                    const rrtmg_sw_band_fluxes *b = nullptr);
 int lw_fluxes_impl(rrtmg_ctx *ctx, const rrtmg_lw_args *a, const rrtmg_lw_band_fluxes *b = nullptr);   // (b: as for the shortwave)
+// rrtmg_hip_{sw,lw}_fluxes_f32 on checked structs (rrtmg_precision.hip): the grid arrays of the structs point to float
+int sw_fluxes_f32_impl(rrtmg_ctx *ctx, const rrtmg_sw_args *a, const rrtmg_sw_surface *sf, const rrtmg_sw_components *c, const rrtmg_sw_band_fluxes *b);
+int lw_fluxes_f32_impl(rrtmg_ctx *ctx, const rrtmg_lw_args *a, const rrtmg_lw_band_fluxes *b);
 // rrtmg_hip_radiation_fluxes on checked structs: call_begin of both spectra, then the two drivers above under joint_run (rrtmg_call.h)
 int radiation_fluxes_impl(rrtmg_ctx *ctx, const rrtmg_sw_args *sw, const rrtmg_sw_surface *sf, const rrtmg_sw_components *c, const rrtmg_sw_band_fluxes *b,
                           const rrtmg_lw_args *lw, const rrtmg_lw_band_fluxes *lb);

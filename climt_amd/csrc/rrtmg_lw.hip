@@ -343,7 +343,7 @@ int lw_fluxes_impl(rrtmg_ctx *ctx, const rrtmg_lw_args *a, const rrtmg_lw_band_f
   // ---- inputs (rrtmg_host_inputs.h: uniform arrays are filled on the device, all-zero band arrays are absent) ----------------
   bool ok = true;
   const double ps = a->pressure_scale, ws = a->water_path_scale;
-  HostInputs hi(ctx, s, "lw.in.", a->memspace, call_share(ctx), 1);
+  HostInputs hi(ctx, s, "lw.in.", a->memspace, call_share(ctx), 1, ctx->f32);
   hi.add(&d.play, a->play, nl, "play", true, InPolicy::Plain, ps); hi.add(&d.plev, a->plev, nl1, "plev", true, InPolicy::Plain, ps);
   hi.add(&d.tlay, a->tlay, nl, "tlay", true); hi.add(&d.tlev, a->tlev, nl1, "tlev", false); hi.add(&d.tsfc, a->tsfc, N, "tsfc", true);
   hi.add(&d.h2o, a->h2ovmr, nl, "h2o", true, InPolicy::Plain, a->h2o_mul, a->h2o_div); hi.add(&d.o3, a->o3vmr, nl, "o3", true);
@@ -488,6 +488,53 @@ int radiation_fluxes_impl(rrtmg_ctx *ctx, const rrtmg_sw_args *sw, const rrtmg_s
   if (int rc = call_begin(ctx, 1, lw)) return rc;
   if (int rc = lw_refuse_clear_bands(ctx, lb)) return rc;
   return joint_run(ctx, [=]() { return sw_fluxes_impl(ctx, sw, sf, c, b); }, [=]() { return lw_fluxes_impl(ctx, lw, lb); });
+}
+
+// rrtmg_hip_lw_fluxes_f32 (rrtmg_precision.h; see sw_fluxes_f32_impl): host pointers run the ordinary driver with ctx->f32 set;
+// device pointers get ONE widen launch for what the driver reads, the ordinary call on the fp64 copies, ONE narrow launch.
+int lw_fluxes_f32_impl(rrtmg_ctx *ctx, const rrtmg_lw_args *a, const rrtmg_lw_band_fluxes *bp) {
+  if (a->memspace != 1) {
+    ctx->f32 = true;
+    const int rc = lw_fluxes_impl(ctx, a, bp);
+    ctx->f32 = false;
+    return rc;
+  }
+  // (the sorted call has never checked the shard arguments: lw_sorted_call)
+  if (int rc = call_is_sorted(ctx, 1, a, bp != nullptr) ? ctx_prepare_device(ctx) : call_begin(ctx, 1, a)) return rc;
+  if (int rc = lw_refuse_clear_bands(ctx, bp)) return rc;
+  const CallSite c{ctx, 1, call_stream(ctx, 1, 1)};
+  const bool clr = ctx->lw_clear_sky, dr = a->idrv != 0;
+  BoundaryF32 bf(ctx, c.s, "lw.f32.");
+  rrtmg_lw_args b = *a;
+  const size_t N = (size_t)a->ncol, nl = N * a->nlay, nl1 = N * (a->nlay + 1);
+  const int icld = (a->icld < 0 || a->icld > 3) ? 2 : a->icld;
+  b.play = bf.in("play", a->play, nl); b.plev = bf.in("plev", a->plev, nl1); b.tlay = bf.in("tlay", a->tlay, nl);
+  b.tlev = bf.in("tlev", a->tlev, nl1); b.tsfc = bf.in("tsfc", a->tsfc, N);
+  b.h2ovmr = bf.in("h2o", a->h2ovmr, nl); b.o3vmr = bf.in("o3", a->o3vmr, nl); b.co2vmr = bf.in("co2", a->co2vmr, nl);
+  b.ch4vmr = bf.in("ch4", a->ch4vmr, nl); b.n2ovmr = bf.in("n2o", a->n2ovmr, nl); b.o2vmr = bf.in("o2", a->o2vmr, nl);
+  b.cfc11vmr = bf.in("cfc11", a->cfc11vmr, nl); b.cfc12vmr = bf.in("cfc12", a->cfc12vmr, nl);
+  b.cfc22vmr = bf.in("cfc22", a->cfc22vmr, nl); b.ccl4vmr = bf.in("ccl4", a->ccl4vmr, nl);
+  b.emis = bf.in("emis", a->emis, N * 16);
+  b.cldfr = nullptr; b.taucld = nullptr; b.cicewp = b.cliqwp = b.reice = b.reliq = nullptr; b.cldfmcl = nullptr;
+  if (icld >= 1) {
+    b.cldfr = bf.in("cldfr", a->cldfr, nl); b.taucld = bf.in("taucld", a->taucld, nl * 16);
+    b.cicewp = bf.in("cicewp", a->cicewp, nl); b.cliqwp = bf.in("cliqwp", a->cliqwp, nl);
+    b.reice = bf.in("reice", a->reice, nl); b.reliq = bf.in("reliq", a->reliq, nl);
+    if (a->mcica) b.cldfmcl = bf.in("cldfmcl", a->cldfmcl, nl * kLwNGpt);
+  }
+  b.tauaer = bf.in("tauaer", a->tauaer, nl * 16);
+  // (clear-sky outputs off: whatever the four point to is ignored -- absent from the narrow table, and from the inner call)
+  b.uflx = bf.out("o0", a->uflx, nl1); b.dflx = bf.out("o1", a->dflx, nl1); b.hr = bf.out("o2", a->hr, nl);
+  b.uflxc = clr ? bf.out("o3", a->uflxc, nl1) : nullptr; b.dflxc = clr ? bf.out("o4", a->dflxc, nl1) : nullptr; b.hrc = clr ? bf.out("o5", a->hrc, nl) : nullptr;
+  b.duflx_dt = dr ? bf.out("o6", a->duflx_dt, nl1) : nullptr; b.duflxc_dt = dr && clr ? bf.out("o7", a->duflxc_dt, nl1) : nullptr;
+  rrtmg_lw_band_fluxes bb{};
+  if (bp) {
+    const size_t nband = (size_t)kLwNBand * (bp->levels ? 2 : a->nlay + 1) * N;
+    bb = *bp;
+    bb.up = bf.out("b0", bp->up, nband); bb.dn = bf.out("b1", bp->dn, nband); bb.upc = bf.out("b2", bp->upc, nband); bb.dnc = bf.out("b3", bp->dnc, nband);
+  }
+  if (!bf.ok) return ctx->status;
+  return boundary_f32_tail(c, bf, [&]() { return lw_fluxes_impl(ctx, &b, bp ? &bb : nullptr); });
 }
 
 }  // namespace rrtmg

@@ -4,8 +4,8 @@
 //
 // Inside ONE call the caller's arrays cannot change, so an identical host pointer means identical content; what the device
 // holds for it depends, besides, on how many elements were taken, on the unit factors applied after the upload and on the
-// policy that may replace an all-zero array by "absent".  The key is those five; anything that differs in one of them is
-// uploaded on its own.  The table lives for one call: nothing is shared across calls.
+// policy that may replace an all-zero array by "absent", and on the element type on the host (8-byte reals, or 4-byte ones in a
+// float32-boundary call).  The key is those six; anything that differs in one of them is uploaded on its own.  The table lives for one call: nothing is shared across calls.
 #pragma once
 #include <cstddef>
 #include <cstdint>
@@ -16,10 +16,11 @@ namespace rrtmg {
 
 struct ShareKey {
   const void *host; size_t n; uint64_t mul, div; int policy;   // (mul, div: the factors' bit patterns -- 0.0 and -0.0 differ, a NaN equals itself)
-  bool operator==(const ShareKey &o) const { return host == o.host && n == o.n && mul == o.mul && div == o.div && policy == o.policy; }
+  int elem;                                                    // bytes per element on the host: 8, or 4
+  bool operator==(const ShareKey &o) const { return host == o.host && n == o.n && mul == o.mul && div == o.div && policy == o.policy && elem == o.elem; }
 };
-inline ShareKey share_key(const void *host, size_t n, double mul, double div, int policy) {
-  ShareKey k{host, n, 0, 0, policy};
+inline ShareKey share_key(const void *host, size_t n, double mul, double div, int policy, int elem = 8) {
+  ShareKey k{host, n, 0, 0, policy, elem};
   memcpy(&k.mul, &mul, sizeof mul); memcpy(&k.div, &div, sizeof div);
   return k;
 }

@@ -689,7 +689,7 @@ int sw_fluxes_impl(rrtmg_ctx *ctx, const rrtmg_sw_args *a, const rrtmg_sw_surfac
   // ---- inputs (rrtmg_host_inputs.h: uniform arrays are filled on the device, all-zero band arrays are absent) ----------------
   bool ok = true;
   const double ps = a->pressure_scale, ws = a->water_path_scale;
-  HostInputs hi(ctx, s, "sw.in.", a->memspace, call_share(ctx), 0);
+  HostInputs hi(ctx, s, "sw.in.", a->memspace, call_share(ctx), 0, ctx->f32);
   hi.add(&d.play, a->play, nl, "play", true, InPolicy::Plain, ps); hi.add(&d.plev, a->plev, nl1, "plev", true, InPolicy::Plain, ps);
   hi.add(&d.tlay, a->tlay, nl, "tlay", true);
   hi.add(&d.h2o, a->h2ovmr, nl, "h2o", true, InPolicy::Plain, a->h2o_mul, a->h2o_div); hi.add(&d.o3, a->o3vmr, nl, "o3", true);
@@ -862,6 +862,77 @@ int sw_fluxes_impl(rrtmg_ctx *ctx, const rrtmg_sw_args *a, const rrtmg_sw_surfac
   }
   const int nout = opt_out_append(bpt, 6, nband, oc, opt_out_append(cpt, 8, nl1, oc, 6));   // components, then bands: behind the same synchronise
   return call_finish(c, a->memspace, oc, nout, d.err);
+}
+
+// rrtmg_hip_sw_fluxes_f32 (rrtmg_precision.h): every grid array of the structs points to float.  Host pointers: the ordinary
+// driver with ctx->f32 set -- HostInputs widens behind the upload, copy_out narrows in front of the download.  Device pointers:
+// ONE widen launch for what the driver reads under the call's icld / iaer (the list of sw_permuted_call), the ordinary
+// device-resident call on the fp64 copies, ONE narrow launch for every requested output.  The checks in front are the driver's
+// own, in its order, so that nothing is sized from arguments it would refuse.
+int sw_fluxes_f32_impl(rrtmg_ctx *ctx, const rrtmg_sw_args *a, const rrtmg_sw_surface *sp, const rrtmg_sw_components *cp, const rrtmg_sw_band_fluxes *bp) {
+  if (a->memspace != 1) {
+    ctx->f32 = true;
+    const int rc = sw_fluxes_impl(ctx, a, sp, cp, bp);
+    ctx->f32 = false;
+    return rc;
+  }
+  const bool clr = ctx->sw_clear_sky;
+  if (!clr && (cp || bp)) return sw_fluxes_impl(ctx, a, sp, cp, bp);   // (refused there, before anything is read)
+  // (the sorted call has never checked the shard arguments: sw_permuted_call)
+  const bool sorted = !sw_call_is_packed(ctx, a) && call_is_sorted(ctx, 0, a, cp || bp || sp || ctx->sw_night_skip || ctx->sw_night_pack || sw_amplitudes_differ_from_one(a));
+  if (int rc = sorted ? ctx_prepare_device(ctx) : call_begin(ctx, 0, a)) return rc;
+  const CallSite c{ctx, 0, call_stream(ctx, 0, 1)};
+  BoundaryF32 bf(ctx, c.s, "sw.f32.");
+  rrtmg_sw_args b = *a;
+  const size_t N = (size_t)a->ncol, nl = N * a->nlay, nl1 = N * (a->nlay + 1);
+  const int icld = (a->icld < 0 || a->icld > 3) ? 2 : a->icld;
+  b.play = bf.in("play", a->play, nl); b.plev = bf.in("plev", a->plev, nl1); b.tlay = bf.in("tlay", a->tlay, nl);
+  b.tlev = nullptr; b.tsfc = nullptr;   // (the shortwave reads neither)
+  b.h2ovmr = bf.in("h2o", a->h2ovmr, nl); b.o3vmr = bf.in("o3", a->o3vmr, nl); b.co2vmr = bf.in("co2", a->co2vmr, nl);
+  b.ch4vmr = bf.in("ch4", a->ch4vmr, nl); b.n2ovmr = bf.in("n2o", a->n2ovmr, nl); b.o2vmr = bf.in("o2", a->o2vmr, nl);
+  // (a broadband pair is read only where its per-band array is not given)
+  const bool bdir = sp && sp->albdir, bdif = sp && sp->albdif;
+  b.asdir = bdir ? nullptr : bf.in("asdir", a->asdir, N); b.aldir = bdir ? nullptr : bf.in("aldir", a->aldir, N);
+  b.asdif = bdif ? nullptr : bf.in("asdif", a->asdif, N); b.aldif = bdif ? nullptr : bf.in("aldif", a->aldif, N);
+  b.coszen = bf.in("coszen", a->coszen, N);
+  rrtmg_sw_surface sb{};
+  if (sp) { sb = *sp; sb.albdir = bf.in("albdir", sp->albdir, (size_t)kSwNBand * N); sb.albdif = bf.in("albdif", sp->albdif, (size_t)kSwNBand * N); }
+  b.cldfr = nullptr; b.taucld = b.ssacld = b.asmcld = b.fsfcld = nullptr; b.cicewp = b.cliqwp = b.reice = b.reliq = nullptr; b.cldfmcl = nullptr;
+  if (icld >= 1) {
+    b.cldfr = bf.in("cldfr", a->cldfr, nl);
+    b.cicewp = bf.in("cicewp", a->cicewp, nl); b.cliqwp = bf.in("cliqwp", a->cliqwp, nl);
+    b.reice = bf.in("reice", a->reice, nl); b.reliq = bf.in("reliq", a->reliq, nl);
+    b.taucld = bf.in("taucld", a->taucld, nl * kSwNBand); b.ssacld = bf.in("ssacld", a->ssacld, nl * kSwNBand);
+    b.asmcld = bf.in("asmcld", a->asmcld, nl * kSwNBand); b.fsfcld = bf.in("fsfcld", a->fsfcld, nl * kSwNBand);
+    if (a->mcica) b.cldfmcl = bf.in("cldfmcl", a->cldfmcl, nl * kSwNGpt);
+  }
+  b.tauaer = b.ssaaer = b.asmaer = nullptr; b.ecaer = nullptr;
+  if (a->iaer == 10) {
+    b.tauaer = bf.in("tauaer", a->tauaer, nl * kSwNBand); b.ssaaer = bf.in("ssaaer", a->ssaaer, nl * kSwNBand);
+    b.asmaer = bf.in("asmaer", a->asmaer, nl * kSwNBand);
+  } else if (a->iaer == 6) {
+    b.ecaer = bf.in("ecaer", a->ecaer, nl * 6);
+  }
+  // (clear-sky outputs off: whatever the three point to is ignored -- absent from the narrow table, and from the inner call)
+  b.swuflx = bf.out("o0", a->swuflx, nl1); b.swdflx = bf.out("o1", a->swdflx, nl1); b.swhr = bf.out("o2", a->swhr, nl);
+  b.swuflxc = clr ? bf.out("o3", a->swuflxc, nl1) : nullptr; b.swdflxc = clr ? bf.out("o4", a->swdflxc, nl1) : nullptr;
+  b.swhrc = clr ? bf.out("o5", a->swhrc, nl) : nullptr;
+  rrtmg_sw_components cb{};
+  if (cp) {
+    cb = *cp;
+    cb.dirdflx = bf.out("c0", cp->dirdflx, nl1); cb.difdflx = bf.out("c1", cp->difdflx, nl1); cb.dirdnuv = bf.out("c2", cp->dirdnuv, nl1);
+    cb.difdnuv = bf.out("c3", cp->difdnuv, nl1); cb.dirdnir = bf.out("c4", cp->dirdnir, nl1); cb.difdnir = bf.out("c5", cp->difdnir, nl1);
+    cb.dirdflxc = bf.out("c6", cp->dirdflxc, nl1); cb.difdflxc = bf.out("c7", cp->difdflxc, nl1);
+  }
+  rrtmg_sw_band_fluxes bb{};
+  if (bp) {
+    const size_t nband = (size_t)kSwNBand * (bp->levels ? 2 : a->nlay + 1) * N;
+    bb = *bp;
+    bb.up = bf.out("b0", bp->up, nband); bb.dn = bf.out("b1", bp->dn, nband); bb.upc = bf.out("b2", bp->upc, nband);
+    bb.dnc = bf.out("b3", bp->dnc, nband); bb.dndir = bf.out("b4", bp->dndir, nband); bb.dndirc = bf.out("b5", bp->dndirc, nband);
+  }
+  if (!bf.ok) return ctx->status;
+  return boundary_f32_tail(c, bf, [&]() { return sw_fluxes_impl(ctx, &b, sp ? &sb : nullptr, cp ? &cb : nullptr, bp ? &bb : nullptr); });
 }
 
 }  // namespace rrtmg

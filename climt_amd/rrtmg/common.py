@@ -64,8 +64,10 @@ class OutputPool:
     the bytearray to the free list when the last such view has died; an interpreter that collects later only delays the
     re-use."""
 
-    def __init__(self, keep=4):
+    def __init__(self, keep=4, dtype=np.float64):
+        """`dtype`: the element type of every array handed out (float32 for a component with a float32 boundary)."""
         self._free, self._keep, self._out = {}, keep, 0
+        self._dtype = np.dtype(dtype)
 
     def _release(self, key, backing):
         self._out -= 1
@@ -86,13 +88,13 @@ class OutputPool:
                 # that keeps every result gets pageable arrays beyond the first few: page-locked memory is not for archives.)
                 try:
                     from .._hip import pinned_buffer
-                    backing = pinned_buffer(8 * int(np.prod(shape)))
-                    np.frombuffer(backing, dtype=np.float64)[:] = 0.0
+                    backing = pinned_buffer(self._dtype.itemsize * int(np.prod(shape)))
+                    np.frombuffer(backing, dtype=self._dtype)[:] = 0.0
                 except Exception:
                     backing = None
             if backing is None:
-                backing = bytearray(8 * int(np.prod(shape)))      # zero-filled, pages touched
-        root = np.frombuffer(backing, dtype=np.float64)
+                backing = bytearray(self._dtype.itemsize * int(np.prod(shape)))      # zero-filled, pages touched
+        root = np.frombuffer(backing, dtype=self._dtype)
         weakref.finalize(root, self._release, key, backing)
         self._out += 1
         return root.reshape(shape)
@@ -179,6 +181,31 @@ def library_scales(state):
                     state[n] = r * fac      # (a new array in the unit input_properties declares; the caller's is untouched)
                 arrays[n] = state[n]
     return scales, arrays
+
+
+BOUNDARY_DTYPES = ("float64", "float32")
+# inputs of a library call that stay float64 whatever the boundary (include/rrtmg_hip.h: host arrays of a few numbers)
+_ALWAYS_FLOAT64 = ("bndsolvar", "indsolvar")
+
+
+def boundary_dtype(value):
+    """The `boundary_dtype` option of the radiation components -> numpy dtype; ValueError for anything but the two."""
+    try:
+        dt = np.dtype(value)
+    except TypeError:
+        dt = None
+    if dt is None or dt.name not in BOUNDARY_DTYPES:
+        raise ValueError("boundary_dtype %r: one of %s" % (value, ", ".join(BOUNDARY_DTYPES)))
+    return dt
+
+
+def cast_inputs(inp, dtype):
+    """The arrays of a library call's `inp` (or `surface`) as C-contiguous `dtype`, in place in the dict: an array that
+    already is one is handed over as it is -- the same buffer, no copy."""
+    for k, v in inp.items():
+        if isinstance(v, np.ndarray) and k not in _ALWAYS_FLOAT64:
+            inp[k] = np.ascontiguousarray(v, dtype=dtype)
+    return inp
 
 
 def output_arrays(pool, output_properties, raw_input_state, input_properties):

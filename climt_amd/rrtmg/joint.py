@@ -64,6 +64,7 @@ class _JointExtraction(object if _sc.HAVE_SYMPL else _sc.TendencyComponent):
         self.input_properties = _union_properties(shortwave, longwave)
         self._unit_factor_on_device = tuple(n for n in shortwave._unit_factor_on_device if n in longwave._unit_factor_on_device)
         self._input_staging = shortwave._input_staging
+        self._boundary_dtype = shortwave._boundary_dtype      # (radiation_step has checked that the longwave's is the same)
         super(_JointExtraction, self).__init__()
 
     def extract(self, state):
@@ -89,7 +90,8 @@ def radiation_step(shortwave, longwave, state):
     `longwave(state)` return, in that order -- same keys, types, units, aliasing and values, bit for bit -- from one
     Context.radiation_fluxes call: shared inputs uploaded once, the two spectra overlapped on the GPU
     (Context.radiation_last() reports what was shared).  McICA seeds are drawn shortwave first, then longwave, as the two
-    separate calls draw them.  Host states only: a DeviceState has its own overlapped path."""
+    separate calls draw them.  Host states only: a DeviceState has its own overlapped path.  Both components must have the same
+    `boundary_dtype` (ValueError otherwise); with "float32" the one call is rrtmg_hip_radiation_fluxes_f32."""
     from ..device_state import DeviceState
     if not isinstance(shortwave, RRTMGShortwave) or not isinstance(longwave, RRTMGLongwave):
         raise ValueError("radiation_step(shortwave, longwave, state): an RRTMGShortwave and an RRTMGLongwave, in that order")
@@ -99,6 +101,9 @@ def radiation_step(shortwave, longwave, state):
     if longwave._ctx is not ctx:
         raise ValueError("radiation_step: the two components are on different contexts or devices (%r, %r): one library call serves one context"
                          % (getattr(ctx, "device", None), getattr(longwave._ctx, "device", None)))
+    if shortwave._boundary_dtype != longwave._boundary_dtype:
+        raise ValueError("radiation_step: the shortwave has boundary_dtype %s, the longwave %s: one library call has one element type"
+                         % (shortwave._boundary_dtype.name, longwave._boundary_dtype.name))
     if _sc.HAVE_SYMPL and (getattr(shortwave, "tendencies_in_diagnostics", False) or getattr(longwave, "tendencies_in_diagnostics", False)):   # pragma: no cover
         raise ValueError("radiation_step: tendencies_in_diagnostics is not supported; call the components separately")
     # (the extraction plan is worked out once per pair of components and state structure, as each component keeps its own)
@@ -112,7 +117,10 @@ def radiation_step(shortwave, longwave, state):
     lw_call = longwave._prepare_call(_raw_view(raw, longwave))
     shortwave._apply_night_skip(ctx)
     longwave._apply_clear_sky(ctx)
-    ctx.radiation_fluxes(sw=sw_call["library"], lw=lw_call["library"])
+    sw_kw, lw_kw = dict(sw_call["library"]), dict(lw_call["library"])
+    precision = {"precision": sw_kw.pop("precision")} if "precision" in sw_kw else {}      # (float32 boundary: said once, for both)
+    lw_kw.pop("precision", None)
+    ctx.radiation_fluxes(sw=sw_kw, lw=lw_kw, **precision)
     sw_t, sw_d = shortwave._finish_call(sw_call)
     lw_t, lw_d = longwave._finish_call(lw_call)
     return joint.wrap(shortwave, state, sw_t, sw_d), joint.wrap(longwave, state, lw_t, lw_d)

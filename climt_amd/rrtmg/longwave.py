@@ -15,6 +15,7 @@ import numpy as np
 
 from .._sympl_compat import TendencyComponent, get_constant
 from .._util import ensure_contiguous_state
+from .common import boundary_dtype as _boundary_dtype, cast_inputs
 from .common import (UNIT_FACTOR_ON_DEVICE, InputStaging, library_scales, OutputPool, make_context, output_arrays, rrtmg_cloud_ice_props_dict, rrtmg_cloud_liquid_props_dict, rrtmg_cloud_overlap_method_dict,
                      rrtmg_cloud_props_dict, rrtmg_random_number_dict)
 
@@ -107,7 +108,7 @@ class RRTMGLongwave(TendencyComponent):
     def __init__(self, calculate_change_up_flux=False, cloud_overlap_method=None, cloud_optical_properties="liquid_and_ice_clouds",
                  cloud_ice_properties="ebert_curry_two", cloud_liquid_water_properties="radius_dependent_absorption",
                  calculate_interface_temperature=True, mcica=False, random_number_generator="mersenne_twister", device=0,
-                 allow_synthetic_tables=False, band_fluxes=False, clear_sky_diagnostics=True, **kwargs):
+                 allow_synthetic_tables=False, band_fluxes=False, clear_sky_diagnostics=True, boundary_dtype="float64", **kwargs):
         """Same keyword arguments and defaults as climt.RRTMGLongwave (lw/component.py:167-178); additions: `device`
         (GPU ordinal), `allow_synthetic_tables` (see the module docstring) and `band_fluxes`: True adds the up / down fluxes
         (all sky, clear sky) by spectral band (BAND_FLUX_DIAGNOSTICS) to this instance's diagnostics -- or, given as a list
@@ -117,7 +118,9 @@ class RRTMGLongwave(TendencyComponent):
         clear-sky outputs are not copied; the other diagnostics and the tendency are those of the default instance;
         change_in_clear_sky_upward_flux_with_surface_temperature stays None.  Not together with clear-sky band diagnostics
         (band_fluxes=True, or a list naming one of CLEAR_SKY_BAND_DIAGNOSTICS: ValueError); all-sky band diagnostics (a list of
-        the other two names) stay allowed."""
+        the other two names) stay allowed; `boundary_dtype`: "float32" hands the state arrays to the library as 4-byte reals
+        (rrtmg_hip_lw_fluxes_f32; see RRTMGShortwave) and returns float32 diagnostics and tendencies."""
+        self._boundary_dtype = _boundary_dtype(boundary_dtype)
         if isinstance(band_fluxes, (list, tuple, set, frozenset)):
             unknown = [k for k in band_fluxes if k not in BAND_FLUX_DIAGNOSTICS]
             if unknown:
@@ -159,7 +162,7 @@ class RRTMGLongwave(TendencyComponent):
         if not self._calc_Tint:
             self.input_properties["air_temperature_on_interface_levels"] = _prop(_IL, "degK")
         self._ctx = make_context(device)
-        self._pool = OutputPool()
+        self._pool = OutputPool(dtype=self._boundary_dtype)
         self._input_staging = InputStaging()
         self._ctx.lw_init(self._Cpd)
         if self._ctx.lw_tables_synthetic():
@@ -250,6 +253,9 @@ class RRTMGLongwave(TendencyComponent):
                 out[key] = self._pool.zeros_like_fresh(key, (n_layers + 1, n_columns))
         self._input_staging.wait()
         library = dict(inp=inp, mcica=self._mcica, out=out)
+        if getattr(self, "_boundary_dtype", np.float64) == np.float32:      # (the default passes no keyword: any context serves it)
+            cast_inputs(inp, np.float32)
+            library.update(precision="float32")
         if self._band_fluxes:
             library.update(bands={BAND_FLUX_DIAGNOSTICS[k]: diagnostics[k] for k in self._band_names})
         return dict(library=library, tendencies=tendencies, diagnostics=diagnostics)

@@ -8,6 +8,7 @@ import numpy as np
 
 from .._sympl_compat import TendencyComponent, get_constant
 from .._util import ensure_contiguous_state
+from .common import boundary_dtype as _boundary_dtype, cast_inputs
 from .common import (UNIT_FACTOR_ON_DEVICE, InputStaging, library_scales, OutputPool, make_context, output_arrays, rrtmg_aerosol_input_dict, rrtmg_cloud_ice_props_dict, rrtmg_cloud_liquid_props_dict,
                      rrtmg_cloud_overlap_method_dict, rrtmg_cloud_props_dict, rrtmg_random_number_dict)
 
@@ -193,7 +194,7 @@ class RRTMGShortwave(TendencyComponent):
                  facular_sunspot_amplitude=None, solar_variability_by_band=None, aerosol_type="no_aerosol", mcica=False,
                  random_number_generator="mersenne_twister", device=0, flux_components=False, band_fluxes=False,
                  spectral_surface_albedo=False, skip_night_columns=False, pack_day_columns=False, clear_sky_diagnostics=True,
-                 **kwargs):
+                 boundary_dtype="float64", **kwargs):
         """Same keyword arguments and defaults as climt.RRTMGShortwave (sw/component.py:179-194); the additions are `device`
         (GPU ordinal) and `flux_components`: True adds the downward flux split into direct and diffuse parts -- all bands,
         UV/visible bands, near-IR bands, and all bands clear sky (FLUX_COMPONENT_DIAGNOSTICS) -- to this instance's
@@ -217,7 +218,11 @@ class RRTMGShortwave(TendencyComponent):
         clear-sky stream (rrtmg_hip_set_sw_clear_sky): columns with cloud are solved once, not twice, and three of the six
         outputs are not copied; the other diagnostics and the tendency agree with the default instance's to rounding (<= 5e-8
         W m^-2).  Not together with flux_components or band_fluxes (ValueError): their clear-sky and direct-beam members
-        read the stream that is not formed."""
+        read the stream that is not formed; `boundary_dtype`: "float32" hands the state arrays to the library as 4-byte reals
+        (rrtmg_hip_sw_fluxes_f32: an array that already is float32 goes over as it is, the quantities formed here -- the cosine
+        of the zenith angle -- are computed as always and then cast) and returns float32 diagnostics and tendencies: the
+        fp64 results of those inputs, rounded once.  Half the bytes cross PCIe.  Host states only: a DeviceState stays float64."""
+        self._boundary_dtype = _boundary_dtype(boundary_dtype)
         if pack_day_columns and not skip_night_columns:
             raise ValueError("pack_day_columns=True requires skip_night_columns=True")
         if not clear_sky_diagnostics and (flux_components or band_fluxes):
@@ -273,7 +278,7 @@ class RRTMGShortwave(TendencyComponent):
         self._solar_const = 0 if use_solar_constant_from_fortran else get_constant("stellar_irradiance", "W/m^2")
         self._Cpd = get_constant("heat_capacity_of_dry_air_at_constant_pressure", "J/kg/K")
         self._ctx = make_context(device)
-        self._pool = OutputPool()
+        self._pool = OutputPool(dtype=self._boundary_dtype)
         self._input_staging = InputStaging()
         # the reference re-runs rrtmg_sw_ini on every McICA call (sw/component.py:547-560); the tables do
         # not depend on the call, so they are built once here
@@ -377,6 +382,11 @@ class RRTMGShortwave(TendencyComponent):
             out.update({m: diagnostics[k] for k, m in CLEAR_SKY_DIAGNOSTICS.items()})
         self._input_staging.wait()
         library = dict(inp=inp, mcica=self._mcica, out=out)
+        if getattr(self, "_boundary_dtype", np.float64) == np.float32:      # (the default passes no keyword: any context serves it)
+            cast_inputs(inp, np.float32)
+            if surface is not None:
+                cast_inputs(surface, np.float32)
+            library.update(precision="float32")
         if self._flux_components or self._band_fluxes:
             comps = {c: diagnostics[k] for k, c in FLUX_COMPONENT_DIAGNOSTICS.items()} if self._flux_components else None
             bands = {b: diagnostics[k] for k, b in BAND_FLUX_DIAGNOSTICS.items()} if self._band_fluxes else None

@@ -501,6 +501,39 @@ int rrtmg_hip_radiation_fluxes(rrtmg_ctx *ctx, const rrtmg_radiation_call *call)
  * of that (an array that was filled on the device, or absent, counts 0 in both).  RRTMG_ERR_ARG before any such call. */
 int rrtmg_hip_radiation_last(rrtmg_ctx *ctx, int *arrays_shared, long long *bytes_uploaded, long long *bytes_shared);
 
+/* ---- float32 boundary: the flux calls on single-precision arrays ------------------------------- */
+/* The three calls above for a caller that keeps its state in 4-byte reals.  They take the SAME structs; what changes is what the
+ * pointers point to.  RRTMG_HIP_ABI_VERSION is unchanged: probe for the symbols (dlsym), as for rrtmg_hip_sw_fluxes_components.
+ *  - In an _f32 call every pointer member that holds a grid array points to float: all state, cloud, aerosol, albedo, coszen, emis,
+ *    tsfc and cldfmcl inputs, albdir / albdif of rrtmg_sw_surface, and every output of the argument, components and band structs.
+ *    Element counts and layouts are unchanged; the arrays need only 4-byte alignment, under either memspace.
+ *  - bndsolvar, indsolvar and the by-value doubles (adjes, scon, solcycfrac, the unit factors) stay double.
+ *  - Precision is chosen per call, by the entry point; there is no switch on the context that a later call could forget (an fp64
+ *    kernel would read twice past a float buffer).  fp64 and _f32 calls may alternate freely on one context.
+ *  - Result: the same bits as the fp64 entry point called on the inputs converted float -> double (exact), with each output
+ *    rounded once to float, to nearest-even (what numpy.astype(float32) does), results in the subnormal range included.  The
+ *    arithmetic is fp64: no kernel that does physics is another one.
+ *  - Unit factors (host arrays only, as in the fp64 calls) are applied in fp64 after the widening: double(x) * mul, then / div,
+ *    one rounding per operation.
+ *  - The caller's input arrays are never modified, and nothing is written outside the n * 4 bytes of an output.
+ *  - Everything that modifies a call composes with unchanged meaning: deferred mode, rrtmg_hip_set_sw_night_skip / _night_pack,
+ *    rrtmg_hip_set_column_sort, rrtmg_hip_set_sw_clear_sky / _lw_clear_sky (NULL clear-sky outputs included), shard_col0 /
+ *    shard_ncol, both McICA generators and an external cldfmcl, idrv, levels 0 / 1.
+ *  - The argument checks, their order and their status codes are those of the fp64 entry points (rrtmg_hip_sw_fluxes_surface,
+ *    rrtmg_hip_lw_fluxes_bands, rrtmg_hip_radiation_fluxes); surface, c and b may be NULL.
+ *  - Cost.  Device pointers (memspace 1): one widen launch for all inputs in front of the call and one narrow launch for all
+ *    requested outputs behind it, on the call's stream, and an internal fp64 copy of inputs and outputs (grow-only work buffers of
+ *    the context).  Host pointers: an input crosses as 4 n bytes and is widened on the device, an output is narrowed on the device
+ *    and comes down as 4 n bytes -- half the PCIe traffic of the fp64 call.  A uniform array is detected by its 4-byte pattern and
+ *    filled on the device; "all zero" means every element is +0.0f (a -0.0f makes the array present, as -0.0 does).
+ *  - The joint call shares an input under the same key as rrtmg_hip_radiation_fluxes plus the element type, and
+ *    rrtmg_hip_radiation_last reports the bytes actually copied (4 per element).
+ * Not covered (fp64 only): the reference-compatible symbols, rrtmg_hip_mcica_mask, the zenith-angle, slab-surface and glue calls. */
+int rrtmg_hip_sw_fluxes_f32(rrtmg_ctx *ctx, const rrtmg_sw_args *a, const rrtmg_sw_surface *surface, const rrtmg_sw_components *c,
+                            const rrtmg_sw_band_fluxes *b);
+int rrtmg_hip_lw_fluxes_f32(rrtmg_ctx *ctx, const rrtmg_lw_args *a, const rrtmg_lw_band_fluxes *b);
+int rrtmg_hip_radiation_fluxes_f32(rrtmg_ctx *ctx, const rrtmg_radiation_call *call);
+
 /* sub-column generators on their own (mcica_subcol_gen_{sw,lw}.f90); host pointers.
  * which: 0 = SW (112 sub-columns), 1 = LW (140).  cldfmcl out: [nlay][ncol][ngpt] of 0/1. */
 int rrtmg_hip_mcica_mask(rrtmg_ctx *ctx, int which, int ncol, int nlay, int icld, int permuteseed,

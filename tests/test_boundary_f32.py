@@ -1,0 +1,211 @@
+"""The float32 boundary without a GPU: the exported symbols and the header's contract, the stand-alone check program of the
+element functions and the head / body / tail split (tools/precision_check.cpp on csrc/rrtmg_precision.h), and the Python layer
+-- what a component with boundary_dtype="float32" hands to its context, on the host emulation of the device functions."""
+import ctypes as C
+import os
+import re
+import subprocess
+
+import numpy as np
+import pytest
+
+import climt_amd
+from climt_amd import _lib
+from climt_amd.rrtmg import longwave, shortwave
+from helpers import ROOT, EmuContext
+
+F32_SYMBOLS = ("rrtmg_hip_sw_fluxes_f32", "rrtmg_hip_lw_fluxes_f32", "rrtmg_hip_radiation_fluxes_f32")
+
+
+def test_symbols_header_and_abi_version():
+    syms = subprocess.check_output(["nm", "-D", "--defined-only", _lib.LIB_PATH]).decode()
+    for s in F32_SYMBOLS:
+        assert re.search(r" T %s\b" % s, syms), s
+    hdr = open(os.path.join(ROOT, "include", "rrtmg_hip.h")).read()
+    flat = " ".join(hdr.split())
+    assert ("int rrtmg_hip_sw_fluxes_f32(rrtmg_ctx *ctx, const rrtmg_sw_args *a, const rrtmg_sw_surface *surface, const rrtmg_sw_components *c, "
+            "const rrtmg_sw_band_fluxes *b);") in flat
+    assert "int rrtmg_hip_lw_fluxes_f32(rrtmg_ctx *ctx, const rrtmg_lw_args *a, const rrtmg_lw_band_fluxes *b);" in flat
+    assert "int rrtmg_hip_radiation_fluxes_f32(rrtmg_ctx *ctx, const rrtmg_radiation_call *call);" in flat
+    for phrase in ("points to float", "rounded once", "never modified", "4-byte"):
+        assert phrase in flat, phrase
+    assert "#define RRTMG_HIP_ABI_VERSION 5" in hdr
+    lib = _lib.load_library()
+    assert lib.rrtmg_hip_abi_version() == 5
+    assert all(hasattr(lib, s) for s in F32_SYMBOLS)
+
+
+def test_null_context_is_an_argument_error():
+    lib = _lib.load_library()
+    a, la, call = _lib.SwArgs(), _lib.LwArgs(), _lib.RadiationCall()
+    assert lib.rrtmg_hip_sw_fluxes_f32(None, C.byref(a), None, None, None) == 4
+    assert lib.rrtmg_hip_lw_fluxes_f32(None, C.byref(la), None) == 4
+    assert lib.rrtmg_hip_radiation_fluxes_f32(None, C.byref(call)) == 4
+
+
+def test_precision_check_program(tmp_path):
+    """tools/precision_check.cpp -- the library's own element functions, split and per-entry loop on the CPU: every offset of
+    0-3 elements, the counts 0, 1, 3, 4, 5, 63, 64, 65, 1027, +-0, subnormals, FLT_MIN and rounding ties against the C cast,
+    guards intact -- compiles with the host compiler and reports ok."""
+    exe = str(tmp_path / "precision_check")
+    subprocess.check_call(["c++", "-std=c++17", "-O1", os.path.join(ROOT, "tools", "precision_check.cpp"), "-o", exe])
+    out = subprocess.check_output([exe]).decode()
+    assert out.startswith("ok"), out
+
+
+# ---- the Python layer -------------------------------------------------------------------------------------------------------
+class F32EmuContext(EmuContext):
+    """The host emulation behind Context's keyword: records what it is handed, computes in float64 on the widened inputs and
+    rounds once into the outputs (what the library's float32 boundary does on the device)."""
+
+    def __init__(self, device=0):
+        super().__init__(device)
+        self.calls = []
+
+    def _run(self, which, inp, mcica, out, precision):
+        self.calls.append((which, inp, out, precision))
+        if precision == "float32":
+            for k, v in out.items():
+                if not (isinstance(v, np.ndarray) and v.dtype == np.float32 and v.flags.c_contiguous):
+                    raise ValueError("output %r: the library writes it in place: a C-contiguous float32 array" % k)
+        wide = {k: (v.astype(np.float64) if isinstance(v, np.ndarray) else v) for k, v in inp.items()}
+        res = (EmuContext.sw_fluxes if which == "sw" else EmuContext.lw_fluxes)(self, wide, mcica=mcica)
+        for k, v in out.items():
+            v[...] = res[k]
+        return out
+
+    def sw_fluxes(self, inp, mcica=False, out=None, memspace=0, precision="float64"):
+        return self._run("sw", inp, mcica, out, precision)
+
+    def lw_fluxes(self, inp, mcica=False, out=None, memspace=0, precision="float64"):
+        return self._run("lw", inp, mcica, out, precision)
+
+    def radiation_fluxes(self, sw, lw, precision="float64"):
+        return self._run("sw", sw["inp"], sw.get("mcica", False), sw["out"], precision), self._run("lw", lw["inp"], lw.get("mcica", False), lw["out"], precision)
+
+
+@pytest.fixture
+def emu(monkeypatch):
+    ctx = F32EmuContext()
+    monkeypatch.setattr(shortwave, "make_context", lambda device: ctx)
+    monkeypatch.setattr(longwave, "make_context", lambda device: ctx)
+    return ctx
+
+
+def _state(sw, lw, dtype=None):
+    state = climt_amd.get_default_state([sw, lw], grid_state=climt_amd.get_grid(nx=4, ny=3, nz=10))
+    if dtype is not None:
+        for k, v in state.items():
+            if hasattr(v, "values") and np.asarray(v.values).dtype == np.float64:
+                v.values = np.asarray(v.values).astype(dtype)
+    return state
+
+
+def _arrays(d):
+    return {k: v for k, v in d.items() if isinstance(v, np.ndarray) and k not in ("bndsolvar", "indsolvar")}
+
+
+def test_float32_components_hand_over_float32_and_return_float32(emu):
+    sw, lw = climt_amd.RRTMGShortwave(boundary_dtype="float32"), climt_amd.RRTMGLongwave(boundary_dtype="float32", allow_synthetic_tables=True)
+    state = _state(sw, lw)      # a float64 state: cast on the way in
+    (sw_t, sw_d), (lw_t, lw_d) = sw(state), lw(state)
+    assert [c[0] for c in emu.calls] == ["sw", "lw"] and all(c[3] == "float32" for c in emu.calls)
+    for which, inp, out, _ in emu.calls:
+        arrays = _arrays(inp)
+        assert len(arrays) >= 15
+        for k, v in arrays.items():
+            assert v.dtype == np.float32 and v.flags.c_contiguous, (which, k, v.dtype)
+        for k, v in out.items():
+            assert v.dtype == np.float32 and v.flags.c_contiguous, (which, k)
+    sw_inp = emu.calls[0][1]
+    assert sw_inp["bndsolvar"].dtype == np.float64 and sw_inp["indsolvar"].dtype == np.float64      # the header: these stay double
+    # derived on the host as always, then cast: the cosine of the zenith angle
+    assert np.array_equal(sw_inp["coszen"], np.cos(np.asarray(state["zenith_angle"].values, dtype=np.float64)).reshape(-1).astype(np.float32))
+    for group in (sw_t, sw_d, lw_t, lw_d):
+        for k, v in group.items():
+            assert np.asarray(v.values).dtype == np.float32, k
+    # ... and the numbers are the float64 component's on the same (widened float32) inputs, rounded once
+    assert float(np.abs(sw_d["downwelling_shortwave_flux_in_air"].values).max()) > 100.0
+    assert float(np.abs(lw_d["upwelling_longwave_flux_in_air"].values).max()) > 100.0
+    # property dictionaries and class attributes unchanged
+    assert sw.input_properties is climt_amd.RRTMGShortwave.input_properties and sw.diagnostic_properties is climt_amd.RRTMGShortwave.diagnostic_properties
+    assert lw.diagnostic_properties is climt_amd.RRTMGLongwave.diagnostic_properties
+
+
+def test_float32_state_arrives_as_the_same_buffer(emu):
+    sw, lw = climt_amd.RRTMGShortwave(boundary_dtype="float32"), climt_amd.RRTMGLongwave(boundary_dtype="float32", allow_synthetic_tables=True)
+    state = _state(sw, lw, np.float32)
+    sw(state); lw(state)
+    for (which, inp, _, _), name in zip(emu.calls, ("air_temperature", "air_temperature")):
+        held = np.asarray(state[name].values)
+        assert held.dtype == np.float32
+        assert inp["tlay"].dtype == np.float32 and np.shares_memory(inp["tlay"], held), which
+    held = np.asarray(state["mole_fraction_of_ozone_in_air"].values)
+    assert np.shares_memory(emu.calls[1][1]["o3"], held)
+
+
+def test_default_instance_still_hands_over_float64(emu):
+    sw, lw = climt_amd.RRTMGShortwave(), climt_amd.RRTMGLongwave(allow_synthetic_tables=True)
+    state = _state(sw, lw)
+    (sw_t, sw_d), (lw_t, lw_d) = sw(state), lw(state)
+    for which, inp, out, precision in emu.calls:
+        assert precision == "float64"
+        assert all(v.dtype == np.float64 for v in _arrays(inp).values()) and all(v.dtype == np.float64 for v in out.values())
+    assert np.asarray(sw_d["downwelling_shortwave_flux_in_air"].values).dtype == np.float64
+    assert np.asarray(lw_t["air_temperature"].values).dtype == np.float64
+
+
+def test_float32_results_are_the_rounded_float64_results_on_the_same_inputs(emu):
+    sw32, lw32 = climt_amd.RRTMGShortwave(boundary_dtype="float32"), climt_amd.RRTMGLongwave(boundary_dtype="float32", allow_synthetic_tables=True)
+    sw64, lw64 = climt_amd.RRTMGShortwave(), climt_amd.RRTMGLongwave(allow_synthetic_tables=True)
+    s32 = _state(sw32, lw32, np.float32)
+    s64 = _state(sw64, lw64, np.float32)
+    for k, v in s64.items():      # the same values, widened
+        if hasattr(v, "values") and np.asarray(v.values).dtype == np.float32:
+            v.values = np.asarray(v.values).astype(np.float64)
+    (_, d32), (_, d64) = sw32(s32), sw64(s64)
+    # (the cosine is formed in float64 from the zenith angle and then cast, so compare a quantity that does not depend on it)
+    (t32, l32), (t64, l64) = lw32(s32), lw64(s64)
+    for k in l64:
+        assert np.array_equal(np.asarray(l32[k].values), np.asarray(l64[k].values).astype(np.float32)), k
+    assert np.array_equal(np.asarray(t32["air_temperature"].values), np.asarray(t64["air_temperature"].values).astype(np.float32))
+    assert set(d32) == set(d64)
+
+
+def test_radiation_step_needs_one_dtype(emu):
+    sw, lw = climt_amd.RRTMGShortwave(boundary_dtype="float32"), climt_amd.RRTMGLongwave(allow_synthetic_tables=True)
+    with pytest.raises(ValueError, match="boundary_dtype"):
+        climt_amd.radiation_step(sw, lw, _state(sw, lw))
+    lw32 = climt_amd.RRTMGLongwave(boundary_dtype="float32", allow_synthetic_tables=True)
+    (sw_t, sw_d), (lw_t, lw_d) = climt_amd.radiation_step(sw, lw32, _state(sw, lw32))
+    assert [c[3] for c in emu.calls] == ["float32", "float32"]
+    assert np.asarray(lw_d["upwelling_longwave_flux_in_air"].values).dtype == np.float32
+    with pytest.raises(ValueError, match="boundary_dtype"):
+        climt_amd.RRTMGShortwave(boundary_dtype="float16")
+
+
+def test_context_refuses_a_float64_output_in_a_float32_call():
+    """Context's own argument handling (no GPU: the check is made before the library is entered)."""
+    ctx = _lib.Context.__new__(_lib.Context)
+    ctx.lib = _lib.load_library()
+    assert ctx.has_f32_boundary is True
+    nlay, ncol = 3, 5
+    inp = dict(play=np.ones((nlay, ncol), np.float32))
+    out = {k: np.zeros((nlay + lev, ncol), np.float32) for k, lev in _lib.SW_OUT}
+    out["swhr"] = np.zeros((nlay, ncol))      # float64
+    with pytest.raises(ValueError, match="float32"):
+        ctx._sw_structs(inp, False, out, 0, None, None, "all", None, [], _lib.PRECISIONS["float32"])
+    lout = {k: np.zeros((nlay + lev, ncol), np.float32) for k, lev in _lib.LW_OUT}
+    lout["uflx"] = np.zeros((nlay + 1, ncol))
+    with pytest.raises(ValueError, match="float32"):
+        ctx._lw_structs(inp, False, lout, 0, None, "all", [], _lib.PRECISIONS["float32"])
+    with pytest.raises(ValueError, match="float32"):
+        ctx._sw_structs(inp, False, None, 0, {"dirdflx": np.zeros((nlay + 1, ncol))}, None, "all", None, [], _lib.PRECISIONS["float32"])
+    with pytest.raises(ValueError, match="float32"):
+        ctx._sw_structs(inp, False, None, 0, None, {"up": np.zeros((14, nlay + 1, ncol))}, "all", None, [], _lib.PRECISIONS["float32"])
+    with pytest.raises(ValueError, match="precision"):
+        _lib._precision("float16")
+    # the arrays it would hand over: float32, and an array that already is float32 is not copied
+    keep = []
+    a, _, _, _, made = ctx._sw_structs(inp, False, None, 0, None, None, "all", None, keep, _lib.PRECISIONS["float32"])
+    assert a.play == inp["play"].ctypes.data and all(v.dtype == np.float32 for v in made.values())
