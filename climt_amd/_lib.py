@@ -224,6 +224,9 @@ def load_library():
         lib.rrtmg_hip_sw_fluxes_f32.argtypes = [_vp, C.POINTER(SwArgs), C.POINTER(SwSurface), C.POINTER(SwComponents), C.POINTER(SwBandFluxes)]
         lib.rrtmg_hip_lw_fluxes_f32.argtypes = [_vp, C.POINTER(LwArgs), C.POINTER(LwBandFluxes)]
         lib.rrtmg_hip_radiation_fluxes_f32.argtypes = [_vp, C.POINTER(RadiationCall)]
+    if hasattr(lib, "rrtmg_hip_set_mcica_overlap_alpha"):   # (likewise: exponential / exponential-random McICA overlap)
+        lib.rrtmg_hip_set_mcica_overlap_alpha.argtypes = [_vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp]
+        lib.rrtmg_hip_overlap_alpha.argtypes = [_vp, C.c_int, C.c_int, C.c_int, _vp, _vp, _f64, _f64, _vp]
     lib.rrtmg_hip_copy_blocks.argtypes = [_vp, C.c_int, _vp, C.c_long, C.c_long, _vp, _vp, _vp]
     lib.rrtmg_hip_mcica_mask.argtypes = [_vp] + [C.c_int] * 6 + [_vp] * 3
     _lib = lib
@@ -500,6 +503,51 @@ class Context:
         self._ck(self.lib.rrtmg_hip_set_lw_clear_sky(self.h, 1 if on else 0))
         self.lw_clear_sky = bool(on)
 
+    @property
+    def has_mcica_overlap_alpha(self):
+        """Whether the library exports exponential McICA overlap (rrtmg_hip_set_mcica_overlap_alpha, rrtmg_hip_overlap_alpha)."""
+        return hasattr(self.lib, "rrtmg_hip_set_mcica_overlap_alpha") and hasattr(self.lib, "rrtmg_hip_overlap_alpha")
+
+    def _overlap_entry(self, name):
+        if not self.has_mcica_overlap_alpha:
+            raise RRTMGError(4, "this librrtmg_hip.so has no %s (exponential McICA overlap)" % name)
+        return getattr(self.lib, name)
+
+    @_locked
+    def set_mcica_overlap_alpha(self, which, alpha, memspace=0, ncol=None, nlay=None):
+        """Rank correlations of adjacent layers for exponential (icld 4) and exponential-random (icld 5) McICA overlap
+        (rrtmg_hip_set_mcica_overlap_alpha).  which: "sw", "lw" or "both" (0, 1, 2).  alpha: [nlay][ncol] host array, or a device
+        pointer with memspace=1 (then `ncol`, `nlay`); None clears the setting.  The library copies the array: it may be reused
+        at once and is set again when the state changes."""
+        w = {"sw": 0, "lw": 1, "both": 2}.get(which, which)
+        entry = self._overlap_entry("rrtmg_hip_set_mcica_overlap_alpha")
+        if alpha is None:
+            self._ck(entry(self.h, int(w), 0, 0, 0, None))
+        elif memspace:
+            self._ck(entry(self.h, int(w), int(ncol), int(nlay), 1, int(alpha)))
+        else:
+            a = np.ascontiguousarray(alpha, dtype=np.float64)
+            if a.ndim != 2:
+                raise ValueError("alpha must be [nlay][ncol], got shape %r" % (a.shape,))
+            self._ck(entry(self.h, int(w), a.shape[1], a.shape[0], 0, a.ctypes.data))
+
+    @_locked
+    def overlap_alpha(self, play, tlay, decorrelation_length, rd_over_g=287.05 / 9.80665, out=None, memspace=0, ncol=None, nlay=None):
+        """alpha [nlay][ncol] = exp(-dz / decorrelation_length) from mid-layer pressure and temperature, row 0 = 1
+        (rrtmg_hip_overlap_alpha): dz = rd_over_g * mean temperature of the two layers * ln(p[l-1] / p[l]), metres.  Host arrays
+        [nlay][ncol], or device pointers with memspace=1 (then `out`, `ncol`, `nlay`)."""
+        entry = self._overlap_entry("rrtmg_hip_overlap_alpha")
+        if memspace:
+            self._ck(entry(self.h, int(ncol), int(nlay), 1, int(play), int(tlay), float(rd_over_g), float(decorrelation_length), int(out)))
+            return out
+        p = np.ascontiguousarray(play, dtype=np.float64)
+        t = np.ascontiguousarray(tlay, dtype=np.float64)
+        if p.ndim != 2 or p.shape != t.shape:
+            raise ValueError("play and tlay must be [nlay][ncol] arrays of one shape")
+        a = np.empty(p.shape) if out is None else out
+        self._ck(entry(self.h, p.shape[1], p.shape[0], 0, p.ctypes.data, t.ctypes.data, float(rd_over_g), float(decorrelation_length), a.ctypes.data))
+        return a
+
     @_locked
     def sw_night_last(self):
         """-> (night tiles, night columns) of the last completed shortwave call (in deferred mode: after synchronize());
@@ -715,6 +763,8 @@ class Context:
 
     @_locked
     def mcica_mask(self, which, play, cldfrac, icld, permuteseed, irng):
+        """Sub-column cloud mask [nlay][ncol][112 | 140] of 0 / 1 (rrtmg_hip_mcica_mask): icld 1, 2, 3, and -- while
+        set_mcica_overlap_alpha holds an array of this shape for the spectrum -- 4 (exponential) and 5 (exponential-random)."""
         nlay, ncol = play.shape
         nsub = 112 if which == "sw" else 140
         out = np.zeros((nlay, ncol, nsub))

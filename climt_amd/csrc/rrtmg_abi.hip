@@ -73,6 +73,8 @@ int ctx_prepare_device(rrtmg_ctx *ctx) {
     if (!ctx->sync_ev[w]) RRTMG_HIP_CHECK(ctx, hipEventCreateWithFlags(&ctx->sync_ev[w], hipEventDisableTiming));
   for (int w = 0; w < 2; ++w)
     if (!ctx->share_ev[w]) RRTMG_HIP_CHECK(ctx, hipEventCreateWithFlags(&ctx->share_ev[w], hipEventDisableTiming));
+  for (int w = 0; w < 2; ++w)
+    if (!ctx->alpha_ev[w]) RRTMG_HIP_CHECK(ctx, hipEventCreateWithFlags(&ctx->alpha_ev[w], hipEventDisableTiming));
   return RRTMG_OK;
 }
 
@@ -505,6 +507,8 @@ void rrtmg_hip_destroy(rrtmg_ctx *ctx) {
     if (ctx->sync_ev[w]) (void)hipEventDestroy(ctx->sync_ev[w]);
   for (int w = 0; w < 2; ++w)
     if (ctx->share_ev[w]) (void)hipEventDestroy(ctx->share_ev[w]);
+  for (int w = 0; w < 2; ++w)
+    if (ctx->alpha_ev[w]) (void)hipEventDestroy(ctx->alpha_ev[w]);
   if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
   if (ctx->stream_lw) (void)hipStreamDestroy(ctx->stream_lw);
   rrtmg::free_sw_desc(ctx);
@@ -586,6 +590,44 @@ int rrtmg_hip_set_sw_clear_sky(rrtmg_ctx *ctx, int on) {
 int rrtmg_hip_set_lw_clear_sky(rrtmg_ctx *ctx, int on) {
   if (!ctx) return RRTMG_ERR_ARG;
   ctx->lw_clear_sky = on != 0;
+  return RRTMG_OK;
+}
+// The rank correlations of exponential overlap, copied into the context (rrtmg_ctx::alpha).  Host memory: the copy is complete
+// on return.  Every mask step that reads the buffer first has its stream wait for alpha_ev (mcica_mask_launch, mcica_mask_impl).  Device memory: the copy goes on the stream the spectrum's device-resident calls run on -- the longwave's own
+// stream first waits for what the main stream holds, where rrtmg_hip_overlap_alpha runs -- in front of every later call.
+int rrtmg_hip_set_mcica_overlap_alpha(rrtmg_ctx *ctx, int which, int ncol, int nlay, int memspace, const double *alpha) {
+  if (!ctx) return RRTMG_ERR_ARG;
+  if (which < 0 || which > 2) return ctx->fail(RRTMG_ERR_ARG, "set_mcica_overlap_alpha: which must be 0 (shortwave), 1 (longwave) or 2 (both)");
+  if (!alpha) {
+    for (int w = 0; w < 2; ++w)
+      if (which == 2 || which == w) ctx->alpha[w] = rrtmg_ctx::OverlapAlpha();
+    return RRTMG_OK;
+  }
+  if (ncol <= 0 || nlay <= 0 || nlay > 256 || (memspace != 0 && memspace != 1)) return ctx->fail(RRTMG_ERR_ARG, "set_mcica_overlap_alpha: bad argument");
+  if (int rc = ctx_prepare_device(ctx)) return rc;
+  const size_t bytes = (size_t)ncol * nlay * sizeof(double);
+  for (int w = 0; w < 2; ++w) {
+    if (which != 2 && which != w) continue;
+    ctx->alpha[w] = rrtmg_ctx::OverlapAlpha();
+    double *dev = (double *)ctx->buf(w == 0 ? "sw.alpha" : "lw.alpha", bytes);
+    if (!dev) return ctx->status;
+    if (memspace == 0) {
+      // (calls still in flight from deferred mode may read the buffer: they are waited for, as a synchronous call does)
+      if (ctx->pending[0] || ctx->pending[1]) { if (const int prc = rrtmg_hip_synchronize(ctx)) return prc; }
+      RRTMG_HIP_CHECK(ctx, hipEventSynchronize(ctx->alpha_ev[w]));   // (an earlier copy from device memory into the same buffer may still be in flight)
+      RRTMG_HIP_CHECK(ctx, hipMemcpy(dev, alpha, bytes, hipMemcpyHostToDevice));
+    } else {
+      hipStream_t s = (w == 1 && ctx->deferred) ? ctx->stream_lw : ctx->stream;
+      if (s != ctx->stream) {
+        RRTMG_HIP_CHECK(ctx, hipEventRecord(ctx->alpha_ev[w], ctx->stream));
+        RRTMG_HIP_CHECK(ctx, hipStreamWaitEvent(s, ctx->alpha_ev[w], 0));
+      }
+      RRTMG_HIP_CHECK(ctx, hipMemcpyAsync(dev, alpha, bytes, hipMemcpyDeviceToDevice, s));
+      RRTMG_HIP_CHECK(ctx, hipEventRecord(ctx->alpha_ev[w], s));
+      if (!ctx->deferred) RRTMG_HIP_CHECK(ctx, hipStreamSynchronize(s));
+    }
+    ctx->alpha[w].dev = dev; ctx->alpha[w].ncol = ncol; ctx->alpha[w].nlay = nlay;
+  }
   return RRTMG_OK;
 }
 int rrtmg_hip_sw_night_last(rrtmg_ctx *ctx, int *night_tiles, int *night_columns) {

@@ -94,22 +94,55 @@ inline int call_own_flag(const CallSite &c, int memspace, Dev &d) {
 // sub-column's first draw; else the Mersenne twister.  ngpt: the spectrum's g-points = sub-columns.  night_kernel, coszen: the
 // shortwave's kissvec kernel that draws nothing for a night tile, with the night-column skip on.
 using KissNightKernel = void (*)(int, int, int, const double *, const double *, uint64_t *, int, int *, const uint32_t *, const double *);
+// Exponential and exponential-random overlap (icld 4, 5; rrtmg_hip_set_mcica_overlap_alpha): the siblings kiss_mask_exp_kernel,
+// the shortwave's exp_night_kernel and mt_mask_exp_kernel, with alpha -- call_overlap's answer -- as one more input.
+using KissExpNightKernel = void (*)(int, int, int, const double *, const double *, const double *, uint64_t *, int, int *, const uint32_t *, const double *);
 template <class Dev, class Args>
-inline int mcica_mask_launch(const CallSite &c, int ngpt, const Dev &d, const Args *a, const double *cldfmcl_dev, KissNightKernel night_kernel = nullptr, const double *coszen = nullptr) {
+inline int mcica_mask_launch(const CallSite &c, int ngpt, const Dev &d, const Args *a, const double *cldfmcl_dev, KissNightKernel night_kernel = nullptr, const double *coszen = nullptr,
+                             const double *alpha = nullptr, KissExpNightKernel exp_night_kernel = nullptr) {
   rrtmg_ctx *ctx = c.ctx;
   const int N = d.ncol, L = d.nlay, ntile = (N + 63) / 64;
   const dim3 blk(64);
+  const bool expo = d.icld >= 4;
   if (a->cldfmcl) {
     hipLaunchKernelGGL(mask_from_cldfmcl_kernel, dim3(ntile, ngpt), blk, 0, c.s, N, L, ngpt, cldfmcl_dev, d.mask, d.nw);
+  } else if (expo && !alpha) {
+    return ctx->fail(RRTMG_ERR_ARG, "icld %d: no rank correlations for this call", d.icld);
+  } else if (expo && hipStreamWaitEvent(c.s, ctx->alpha_ev[c.which], 0) != hipSuccess) {
+    // (a copy from device memory may have gone on the spectrum's other stream -- the longwave's own in deferred mode, while a
+    //  host-pointer call runs on the main one: the mask step waits for it on the device, the host does not block)
+    return ctx->fail(RRTMG_ERR_HIP, "hipStreamWaitEvent on the rank correlations' copy failed");
   } else if (a->irng == 0) {
     const uint32_t *jumps = kiss_jumps_device(ctx, c.which, ngpt, L, d.icld, a->permuteseed, c.s);
     if (!jumps) return ctx->status;
-    if (night_kernel) hipLaunchKernelGGL(night_kernel, dim3(ngpt, ntile), blk, 0, c.s, N, L, d.icld, d.play, d.cldfr, d.mask, d.nw, d.err, jumps, coszen);
+    if (expo && night_kernel) hipLaunchKernelGGL(exp_night_kernel, dim3(ngpt, ntile), blk, 0, c.s, N, L, d.icld, d.play, d.cldfr, alpha, d.mask, d.nw, d.err, jumps, coszen);
+    else if (expo) hipLaunchKernelGGL(kiss_mask_exp_kernel, dim3(ngpt, ntile), blk, 0, c.s, N, L, d.icld, d.play, d.cldfr, alpha, d.mask, d.nw, d.err, jumps);
+    else if (night_kernel) hipLaunchKernelGGL(night_kernel, dim3(ngpt, ntile), blk, 0, c.s, N, L, d.icld, d.play, d.cldfr, d.mask, d.nw, d.err, jumps, coszen);
     else hipLaunchKernelGGL(kiss_mask_kernel, dim3(ngpt, ntile), blk, 0, c.s, N, L, d.icld, d.play, d.cldfr, d.mask, d.nw, d.err, jumps);
   } else {
-    return mt_mask_device(ctx, c.which, N, L, ngpt, d.icld, a->permuteseed, d.cldfr, d.mask, d.nw, a->shard_col0, a->shard_ncol, c.s);
+    return mt_mask_device(ctx, c.which, N, L, ngpt, d.icld, a->permuteseed, d.cldfr, d.mask, d.nw, a->shard_col0, a->shard_ncol, c.s, alpha);
   }
   return RRTMG_OK;
+}
+// The overlap rule a call runs under.  icld 4 and 5 exist only while the spectrum has rank correlations set
+// (rrtmg_hip_set_mcica_overlap_alpha), and only for McICA; otherwise any icld outside 0..3 is 2, as in the reference.
+template <class Args>
+inline bool call_overlap_exp(const rrtmg_ctx *ctx, int which, const Args *a) { return a && (a->icld == 4 || a->icld == 5) && ctx->alpha[which].dev != nullptr; }
+// the checks of such a call, in front of the gates to the permuted calls: nothing is enqueued for a call that is refused
+template <class Args>
+inline int call_overlap_check(rrtmg_ctx *ctx, int which, const Args *a) {
+  if (ctx->inner != kInnerNone || !call_overlap_exp(ctx, which, a)) return RRTMG_OK;
+  if (!a->mcica) return ctx->fail(RRTMG_ERR_ARG, "icld %d (exponential overlap) needs mcica = 1: there is no non-McICA exponential overlap", (int)a->icld);
+  const rrtmg_ctx::OverlapAlpha &o = ctx->alpha[which];
+  if (o.ncol != a->ncol || o.nlay != a->nlay) return ctx->fail(RRTMG_ERR_ARG, "icld %d: the rank correlations were set for %d x %d columns x layers, the call has %d x %d", (int)a->icld, o.ncol, o.nlay, (int)a->ncol, (int)a->nlay);
+  return RRTMG_OK;
+}
+// -> the driver's icld; alpha: what the mask step reads under icld 4 and 5 (the inner call of a permuted one: the gathered copy)
+template <class Args>
+inline int call_overlap(const rrtmg_ctx *ctx, int which, const Args *a, const double *&alpha) {
+  alpha = nullptr;
+  if (call_overlap_exp(ctx, which, a)) { alpha = ctx->inner != kInnerNone ? ctx->alpha_inner[which] : ctx->alpha[which].dev; return a->icld; }
+  return (a->icld < 0 || a->icld > 3) ? 2 : a->icld;
 }
 // ---- chunk loop -----------------------------------------------------------------------------------------------------------------
 // Preparation, solve and integration, one column chunk of d.tcap tiles at a time.  Per chunk (first tile t0, nt tiles) the driver
@@ -171,6 +204,7 @@ inline int permuted_tail(const CallSite &c, ColumnPermute &pm, Inner inner, int3
   ctx->inner = pm.kind;
   const int rc = inner();
   ctx->inner = kInnerNone;
+  ctx->alpha_inner[c.which] = nullptr;
   if (rc) return rc;
   pm.flush_scatter(night_out);
   return call_finish(c, 1, nullptr, 0, ctx->err_dev + c.which);

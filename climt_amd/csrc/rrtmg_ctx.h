@@ -125,12 +125,22 @@ struct rrtmg_ctx {
   const void *mt_dev[2] = {nullptr, nullptr};
   // hipFuncSetAttribute(MaxDynamicSharedMemorySize) holds per DEVICE (a kernel's code object is loaded once per device): a
   // context belongs to one device, so every context asks once -- after ctx_prepare_device has made its device current --
-  // and keeps the answer.  [0] lw_prep_fused_kernel, [1] mt_jump_kernel, [2] mt_mask_kernel; -1 = not asked yet
-  int big_lds[3] = {-1, -1, -1};
+  // and keeps the answer.  [0] lw_prep_fused_kernel, [1] mt_jump_kernel, [2] mt_mask_kernel, [3] mt_mask_exp_kernel;
+  // -1 = not asked yet
+  int big_lds[4] = {-1, -1, -1, -1};
   bool allow_dynamic_lds(int slot, const void *kernel, int bytes) {
     if (big_lds[slot] < 0) big_lds[slot] = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes) == hipSuccess ? 1 : 0;
     return big_lds[slot] > 0;
   }
+  // rrtmg_hip_set_mcica_overlap_alpha [sw|lw]: the context's own copy of the caller's rank correlations alpha [nlay][ncol] (work
+  // buffers "sw.alpha" / "lw.alpha") and the shape it was given with.  While one is set, a McICA call of that spectrum with icld
+  // 4 or 5 generates its mask by exponential / exponential-random overlap; not set (the default): every call is the one of a
+  // library without the option.  alpha_inner: the gathered copy for the inner call of a permuted one (rrtmg_permute.h), set
+  // around that call only.  alpha_ev[w]: recorded behind the last copy from device memory.
+  struct OverlapAlpha { const double *dev = nullptr; int ncol = 0, nlay = 0; };
+  OverlapAlpha alpha[2];
+  const double *alpha_inner[2] = {nullptr, nullptr};
+  hipEvent_t alpha_ev[2] = {nullptr, nullptr};
   // rrtmg_hip_set_column_sort (rrtmg_permute.h): device-resident calls with clouds run on an internal copy of their inputs,
   // cloud-free columns first
   bool sort_columns = false;
@@ -260,6 +270,7 @@ int lw_init_impl(rrtmg_ctx *ctx, double cpdair, const char *blob);
 int mcica_mask_impl(rrtmg_ctx *ctx, int which, int ncol, int nlay, int icld, int permuteseed, int irng,
                     const double *play, const double *cldfrac, double *cldfmcl);
 // Mersenne-twister sub-column masks on the device (rrtmg_mt_device.hip): cldfr, mask device pointers, everything on stream s
+// (alpha: the rank correlations [nlay][ncol] of icld 4 and 5, device pointer; not read under icld 0 to 3)
 int mt_mask_device(rrtmg_ctx *ctx, int which, int ncol, int nlay, int nsub, int icld, int seed, const double *cldfr, uint64_t *mask, int nw,
-                   int col0, int ncol_total, hipStream_t s);
+                   int col0, int ncol_total, hipStream_t s, const double *alpha = nullptr);
 }  // namespace rrtmg

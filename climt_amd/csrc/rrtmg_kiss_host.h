@@ -51,7 +51,7 @@ inline KissOp kiss_power(uint32_t n) {
 // that 140 independent exponentiations took -- the host side of a device-resident McICA step was bound by it).
 inline void kiss_build_jumps(int nsub, int nlay, int icld, int changeSeed, std::vector<uint32_t> &out) {
   out.assign((size_t)nsub * kKissJumpWords, 0u);
-  const uint32_t per = (icld == 3) ? 1u : (uint32_t)nlay;
+  const uint32_t per = (icld == 3) ? 1u : (icld == 4 || icld == 5) ? 2u * (uint32_t)nlay : (uint32_t)nlay;   // (exponential overlap: x and y per layer)
   const uint32_t n0 = (uint32_t)(changeSeed < 0 ? 0 : changeSeed);
   KissOp cur = kiss_power(n0);
   const KissOp step = kiss_power(per);

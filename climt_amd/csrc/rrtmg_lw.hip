@@ -301,12 +301,14 @@ static int lw_sorted_call(rrtmg_ctx *ctx, const rrtmg_lw_args *a) {
   b.reice = pm.gather("reice", a->reice, l); b.reliq = pm.gather("reliq", a->reliq, l);
   b.tauaer = pm.gather("tauaer", a->tauaer, l * 16);
   b.cldfmcl = a->mcica ? pm.gather_elem("cldfmcl", a->cldfmcl, kLwNGpt) : nullptr;
-  if (!pm.ok) return ctx->status;
+  // exponential overlap: the rank correlations are one more [nlay][N] input of the mask step
+  if (call_overlap_exp(ctx, 1, a) && !a->cldfmcl) ctx->alpha_inner[1] = pm.gather("alpha", ctx->alpha[1].dev, l);
+  if (!pm.ok) { ctx->alpha_inner[1] = nullptr; return ctx->status; }
   pm.flush_gather();
   b.uflx = pm.out("o0", u[0], l1); b.dflx = pm.out("o1", u[1], l1); b.hr = pm.out("o2", u[2], l);
   b.uflxc = clr ? pm.out("o3", u[3], l1) : nullptr; b.dflxc = clr ? pm.out("o4", u[4], l1) : nullptr; b.hrc = clr ? pm.out("o5", u[5], l) : nullptr;
   b.duflx_dt = dr ? pm.out("o6", a->duflx_dt, l1) : nullptr; b.duflxc_dt = dr && clr ? pm.out("o7", a->duflxc_dt, l1) : nullptr;
-  if (!pm.ok) return ctx->status;
+  if (!pm.ok) { ctx->alpha_inner[1] = nullptr; return ctx->status; }
   return permuted_tail(c, pm, [&]() { return lw_fluxes_impl(ctx, &b); });
 }
 
@@ -320,6 +322,7 @@ static int lw_refuse_clear_bands(rrtmg_ctx *ctx, const rrtmg_lw_band_fluxes *bp)
 
 int lw_fluxes_impl(rrtmg_ctx *ctx, const rrtmg_lw_args *a, const rrtmg_lw_band_fluxes *bp) {
   const bool clr = ctx->lw_clear_sky;   // rrtmg_hip_set_lw_clear_sky: false = uflxc, dflxc, hrc and duflxc_dt are neither formed nor read from `a`
+  if (int orc = call_overlap_check(ctx, 1, a)) return orc;
   if (call_is_sorted(ctx, 1, a, bp != nullptr)) return lw_sorted_call(ctx, a);
   int rc = call_begin(ctx, 1, a);
   if (rc) return rc;
@@ -330,8 +333,8 @@ int lw_fluxes_impl(rrtmg_ctx *ctx, const rrtmg_lw_args *a, const rrtmg_lw_band_f
   const LwTab &T = *(LwTab *)ctx->lw_desc;
   LwDev d{};
   d.ncol = N; d.nlay = L;
-  d.icld = a->icld;
-  if (d.icld < 0 || d.icld > 3) d.icld = 2;   // rrtmg_lw_rad.nomcica.f90:436
+  const double *alpha = nullptr;
+  d.icld = call_overlap(ctx, 1, a, alpha);    // (outside 0..3: 2, rrtmg_lw_rad.nomcica.f90:436; 4, 5 with rank correlations set)
   d.idrv = a->idrv ? 1 : 0;
   d.inflag = a->inflglw; d.iceflag = a->iceflglw; d.liqflag = a->liqflglw; d.mcica = a->mcica ? 1 : 0;
   d.k = ctx->k;
@@ -426,7 +429,7 @@ int lw_fluxes_impl(rrtmg_ctx *ctx, const rrtmg_lw_args *a, const rrtmg_lw_band_f
   // (more than 64 KB of dynamic LDS has to be allowed per kernel once; if the runtime refuses, the scan re-reads the slab)
   const bool big_lds = ctx->allow_dynamic_lds(0, (const void *)lw_prep_fused_kernel, kLwKeepLayers * 3 * 64 * (int)sizeof(double));
   const int keep_layers = (L <= kLwKeepLayers && (big_lds || (size_t)L * 3 * 64 * sizeof(double) <= 64 * 1024)) ? L : 0;
-  if (clouds && d.mcica && (rc = mcica_mask_launch(c, kLwNGpt, d, a, cldfmcl_dev))) return rc;
+  if (clouds && d.mcica && (rc = mcica_mask_launch(c, kLwNGpt, d, a, cldfmcl_dev, nullptr, nullptr, alpha))) return rc;
   if (clouds && d.mcica) hipLaunchKernelGGL(lw_anymask_kernel, gcol, blk, 0, s, d);
   // preparation, solve and band integration, one column chunk at a time (see sw_fluxes_impl)
   const dim3 lwwg(64 * kLwWgWaves);

@@ -44,6 +44,14 @@ static __global__ void __launch_bounds__(64) kiss_mask_kernel(int ncol, int nlay
   if (col < ncol) kiss_mask_jump(ncol, nlay, icld, play, cldfr, mask, nw, err, jumps, col, blockIdx.x);
 }
 
+// kiss_mask_kernel's sibling for exponential (icld 4) and exponential-random (icld 5) overlap (kiss_mask_jump_exp): same grid,
+// alpha [nlay][ncol] is the context's copy (rrtmg_hip_set_mcica_overlap_alpha) or, in a permuted call, its gathered copy
+static __global__ void __launch_bounds__(64) kiss_mask_exp_kernel(int ncol, int nlay, int icld, const double *play, const double *cldfr, const double *alpha,
+                                                                  uint64_t *mask, int nw, int *err, const uint32_t *jumps) {
+  const int col = blockIdx.y * 64 + threadIdx.x;
+  if (col < ncol) kiss_mask_jump_exp(ncol, nlay, icld, play, cldfr, alpha, mask, nw, err, jumps, col, blockIdx.x);
+}
+
 // Jump operators of (nsub, nlay, icld, seed) on the device; rebuilt and uploaded only when the key changes.
 // which: 0 shortwave, 1 longwave (separate buffers: the two may be in flight on different streams).
 static const uint32_t *kiss_jumps_device(rrtmg_ctx *ctx, int which, int nsub, int nlay, int icld, int seed, hipStream_t s) {

@@ -178,14 +178,49 @@ __global__ void __launch_bounds__(64) mt_mask_kernel(int ncol, int nlay, int icl
   }
 }
 
+// mt_mask_kernel's sibling for exponential (icld 4) and exponential-random (icld 5) overlap (include/rrtmg_hip.h,
+// rrtmg_hip_set_mcica_overlap_alpha): a column takes 2 * nlay draws per sub-column, x_0 y_0 x_1 y_1 ..., the stream stays ordered
+// (sub-column, column, layer, {x, y}).  The tile's 64 x 2 nlay draws are staged as there, row stride (2 nlay) | 1: 131 328 bytes
+// of LDS at 256 layers, of 160 KB.  The rule is kiss_mask_subcolumn_exp's (rrtmg_sw_device.h).
+__global__ void __launch_bounds__(64) mt_mask_exp_kernel(int ncol, int nlay, int icld, const double *cldfr, const double *alpha, const uint32_t *draws, uint64_t *mask, int nw, int g0) {
+  extern __shared__ uint32_t sh[];
+  const int lane = threadIdx.x, col0 = blockIdx.y * 64, col = col0 + lane, g = g0 + blockIdx.x;
+  const int per_col = 2 * nlay, ld = per_col | 1;
+  const int ncols_here = ncol - col0 < 64 ? ncol - col0 : 64;
+  const uint32_t *src = draws + ((long)blockIdx.x * ncol + col0) * per_col;
+  for (int i = lane; i < ncols_here * per_col; i += 64) sh[(i / per_col) * ld + i % per_col] = src[i];
+  __syncthreads();
+  if (col >= ncol) return;
+  const double cldmin = 1.0e-20;
+  const uint32_t *r = sh + lane * ld;
+  double rank = 0.0, cfm = 0.0;
+  uint64_t bits = 0;
+  for (int l = 0; l < nlay; ++l) {
+    double cf = cldfr[(long)l * ncol + col];
+    if (cf < cldmin) cf = 0.0;
+    const double x = mt_real(r[2 * l]), y = mt_real(r[2 * l + 1]);
+    if (l == 0) {
+      rank = x;
+    } else {
+      const double a = (icld == 5 && cfm == 0.0) ? 0.0 : alpha[(long)l * ncol + col];
+      if (!(y < a)) rank = x;
+    }
+    cfm = cf;
+    if (rank >= 1.0 - cf) bits |= 1ull << (l & 63);
+    if ((l & 63) == 63 || l == nlay - 1) { mask[((long)g * nw + (l >> 6)) * ncol + col] = bits; bits = 0; }
+  }
+}
+
 // The sub-column masks of columns col0 .. col0 + ncol - 1 of a grid of ncol_total columns (ncol_total <= 0: not sharded), all on
 // stream s; cldfr and mask are device pointers.  which: 0 shortwave, 1 longwave (work buffers and polynomial caches apart: the two
 // may be in flight on different streams).
 int mt_mask_device(rrtmg_ctx *ctx, int which, int ncol, int nlay, int nsub, int icld, int seed, const double *cldfr, uint64_t *mask, int nw,
-                   int col0, int ncol_total, hipStream_t s) {
+                   int col0, int ncol_total, hipStream_t s, const double *alpha) {
   const size_t mask_bytes = (size_t)nsub * nw * ncol * sizeof(uint64_t);
   if (icld == 0) { RRTMG_HIP_CHECK(ctx, hipMemsetAsync(mask, 0, mask_bytes, s)); return RRTMG_OK; }
-  const uint64_t per_col = icld == 3 ? 1 : (uint64_t)nlay;
+  const bool expo = icld == 4 || icld == 5;   // exponential overlap: x and y per layer
+  if (expo && !alpha) return ctx->fail(RRTMG_ERR_ARG, "mt_mask_device: icld %d without rank correlations", icld);
+  const uint64_t per_col = icld == 3 ? 1 : expo ? 2 * (uint64_t)nlay : (uint64_t)nlay;
   const uint64_t ncolT = ncol_total > 0 ? (uint64_t)ncol_total : (uint64_t)ncol;
   const uint64_t first = (ncol_total > 0 ? (uint64_t)col0 : 0) * per_col, stride = ncolT * per_col;
   const long count = (long)ncol * (long)per_col;
@@ -223,15 +258,16 @@ int mt_mask_device(rrtmg_ctx *ctx, int which, int ncol, int nlay, int nsub, int 
   }
   const bool big_lds = ctx->allow_dynamic_lds(1, (const void *)mt_jump_kernel, kMtJumpLds);
   if (!big_lds) return ctx->fail(RRTMG_ERR_HIP, "mt_jump_kernel: %d bytes of dynamic LDS refused", kMtJumpLds);
-  const size_t mask_lds = (size_t)64 * ((icld == 3 ? 1 : nlay) | 1) * 4;   // (256 layers: 64.25 KB, just over what a kernel may have unasked)
-  const bool mask_lds_ok = ctx->allow_dynamic_lds(2, (const void *)mt_mask_kernel, 64 * 257 * 4);
+  const size_t mask_lds = (size_t)64 * ((size_t)per_col | 1) * 4;   // (256 layers: 64.25 KB, just over what a kernel may have unasked; icld 4, 5: 128.25 KB)
+  const bool mask_lds_ok = expo ? ctx->allow_dynamic_lds(3, (const void *)mt_mask_exp_kernel, 64 * 513 * 4) : ctx->allow_dynamic_lds(2, (const void *)mt_mask_kernel, 64 * 257 * 4);
   if (mask_lds > 64 * 1024 && !mask_lds_ok) return ctx->fail(RRTMG_ERR_HIP, "mt_mask_kernel: %zu bytes of dynamic LDS refused", mask_lds);
   hipLaunchKernelGGL(mt_seed_kernel, dim3(1), dim3(kMtGenThreads), 0, s, (uint32_t)seed, x);
   hipLaunchKernelGGL(mt_jump_kernel, dim3(nseg), dim3(kMtJumpThreads), (size_t)kMtJumpLds, s, x, lists, counts, win);
   for (int g0 = 0; g0 < nsub; g0 += gsub) {
     const int ng = nsub - g0 < gsub ? nsub - g0 : gsub;
     hipLaunchKernelGGL(mt_stream_kernel, dim3(ng * npiece), dim3(kMtGenThreads), 0, s, win, count, piece, npiece, g0 * npiece, draws);
-    hipLaunchKernelGGL(mt_mask_kernel, dim3(ng, (ncol + 63) / 64), dim3(64), mask_lds, s, ncol, nlay, icld, cldfr, draws, mask, nw, g0);
+    if (expo) hipLaunchKernelGGL(mt_mask_exp_kernel, dim3(ng, (ncol + 63) / 64), dim3(64), mask_lds, s, ncol, nlay, icld, cldfr, alpha, draws, mask, nw, g0);
+    else hipLaunchKernelGGL(mt_mask_kernel, dim3(ng, (ncol + 63) / 64), dim3(64), mask_lds, s, ncol, nlay, icld, cldfr, draws, mask, nw, g0);
   }
   RRTMG_HIP_CHECK(ctx, hipGetLastError());
   return RRTMG_OK;

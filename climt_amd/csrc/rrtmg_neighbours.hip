@@ -277,6 +277,19 @@ __global__ void __launch_bounds__(256) scale_kernel(double *p, size_t n, double 
   if (div != 0.0) x = x / div;
   p[i] = x;
 }
+// rank correlations of adjacent layers for exponential cloud overlap (rrtmg_hip_overlap_alpha): one thread per (column, layer),
+// row 0 = 1; layer l >= 1: exp(-dz / decorrelation), dz = rd_over_g * mean temperature of the two layers * ln(p[l-1] / p[l]),
+// the hypsometric distance between the two mid-layer pressures.  Every operation rounded on its own, as the numpy
+// statement of the same line is.
+__global__ void __launch_bounds__(256) overlap_alpha_kernel(int ncol, int nlay, const double *play, const double *tlay, double rd_over_g, double decorrelation_m, double *alpha) {
+#pragma clang fp contract(off)
+  const int col = blockIdx.x * 256 + threadIdx.x, l = blockIdx.y;
+  if (col >= ncol || l >= nlay) return;
+  const long o = (long)l * ncol + col;
+  if (l == 0) { alpha[o] = 1.0; return; }
+  const double dz = rd_over_g * (0.5 * (tlay[o] + tlay[o - ncol])) * log(play[o - ncol] / play[o]);
+  alpha[o] = exp(-dz / decorrelation_m);
+}
 void launch_fill(hipStream_t s, double *p, size_t n, double value) {
   hipLaunchKernelGGL(fill_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, p, n, value);
 }
@@ -321,6 +334,32 @@ extern "C" int rrtmg_hip_ab_step(rrtmg_ctx *ctx, long n, int order, const double
                      order > 2 ? f[2] : nullptr, order > 3 ? f[3] : nullptr, w[0], order > 1 ? w[1] : 0.0, order > 2 ? w[2] : 0.0, order > 3 ? w[3] : 0.0, dt, out);
   RRTMG_HIP_CHECK(ctx, hipGetLastError());
   if (!ctx->deferred) RRTMG_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+  return RRTMG_OK;
+}
+extern "C" int rrtmg_hip_overlap_alpha(rrtmg_ctx *ctx, int ncol, int nlay, int memspace, const double *play, const double *tlay,
+                                       double rd_over_g, double decorrelation_m, double *alpha) {
+  if (!ctx) return RRTMG_ERR_ARG;
+  if (ncol <= 0 || nlay <= 0 || nlay > 65535 || !play || !tlay || !alpha || (memspace != 0 && memspace != 1) || !(decorrelation_m > 0.0))
+    return ctx->fail(RRTMG_ERR_ARG, "overlap_alpha: bad argument");
+  int rc = ctx_prepare_device(ctx);
+  if (rc) return rc;
+  hipStream_t s = ctx->stream;
+  const size_t bytes = (size_t)ncol * nlay * sizeof(double);
+  const double *dp = play, *dt = tlay;
+  double *da = alpha;
+  if (memspace == 0) {
+    double *a = (double *)ctx->buf("oa.play", bytes), *b = (double *)ctx->buf("oa.tlay", bytes);
+    da = (double *)ctx->buf("oa.out", bytes);
+    if (!a || !b || !da) return ctx->status;
+    RRTMG_HIP_CHECK(ctx, hipMemcpyAsync(a, play, bytes, hipMemcpyHostToDevice, s));
+    RRTMG_HIP_CHECK(ctx, hipMemcpyAsync(b, tlay, bytes, hipMemcpyHostToDevice, s));
+    dp = a; dt = b;
+  }
+  hipLaunchKernelGGL(overlap_alpha_kernel, dim3((ncol + 255) / 256, nlay), dim3(256), 0, s, ncol, nlay, dp, dt, rd_over_g, decorrelation_m, da);
+  RRTMG_HIP_CHECK(ctx, hipGetLastError());
+  if (memspace == 0) RRTMG_HIP_CHECK(ctx, hipMemcpyAsync(alpha, da, bytes, hipMemcpyDeviceToHost, s));
+  if (ctx->deferred && memspace == 1) return RRTMG_OK;   // ordered before a later rrtmg_hip_set_mcica_overlap_alpha
+  RRTMG_HIP_CHECK(ctx, hipStreamSynchronize(s));
   return RRTMG_OK;
 }
 // direction 0: the longwave stream waits for everything enqueued so far on the main stream (inputs prepared there);

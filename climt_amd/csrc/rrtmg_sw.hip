@@ -366,6 +366,14 @@ __global__ void __launch_bounds__(64) sw_kiss_mask_night_kernel(int ncol, int nl
   if (__ballot(act && !(coszen[col] <= 0.0)) == 0ull) return;
   if (act) kiss_mask_jump(ncol, nlay, icld, play, cldfr, mask, nw, err, jumps, col, blockIdx.x);
 }
+// ... and kiss_mask_exp_kernel's (exponential overlap, icld 4 and 5)
+__global__ void __launch_bounds__(64) sw_kiss_mask_exp_night_kernel(int ncol, int nlay, int icld, const double *play, const double *cldfr, const double *alpha,
+                                                                    uint64_t *mask, int nw, int *err, const uint32_t *jumps, const double *coszen) {
+  const int col = blockIdx.y * 64 + threadIdx.x;
+  const bool act = col < ncol;
+  if (__ballot(act && !(coszen[col] <= 0.0)) == 0ull) return;
+  if (act) kiss_mask_jump_exp(ncol, nlay, icld, play, cldfr, alpha, mask, nw, err, jumps, col, blockIdx.x);
+}
 // sw_fluxheat_kernel: a day column's sums, differences and stores are those of that kernel; a night column stores +0.0 and
 // reads neither the partial planes nor pdp
 __global__ void __launch_bounds__(64 * (kFluxLev + 1)) sw_fluxheat_night_kernel(SwDev d, SwTab T, int tile0, int32_t *night_cnt, int32_t *night_out) {
@@ -511,7 +519,12 @@ void free_sw_desc(rrtmg_ctx *ctx) {
 int mcica_mask_impl(rrtmg_ctx *ctx, int which, int ncol, int nlay, int icld, int permuteseed, int irng,
                     const double *play, const double *cldfrac, double *cldfmcl) {
   if (ncol <= 0 || nlay <= 0 || !play || !cldfrac || !cldfmcl) return ctx->fail(RRTMG_ERR_ARG, "mcica_mask: bad argument");
-  if (icld < 0 || icld > 3) return ctx->fail(RRTMG_ERR_ICLD, "%s", status_message(RRTMG_ERR_ICLD));
+  // (icld 4 and 5 -- exponential overlap -- exist while rank correlations are set for the spectrum: rrtmg_hip_set_mcica_overlap_alpha)
+  const int w = which == 0 ? 0 : 1;
+  const bool expo = (icld == 4 || icld == 5) && ctx->alpha[w].dev;
+  if ((icld < 0 || icld > 3) && !expo) return ctx->fail(RRTMG_ERR_ICLD, "%s", status_message(RRTMG_ERR_ICLD));
+  if (expo && (ctx->alpha[w].ncol != ncol || ctx->alpha[w].nlay != nlay))
+    return ctx->fail(RRTMG_ERR_ARG, "mcica_mask: the rank correlations were set for %d x %d columns x layers, the call has %d x %d", ctx->alpha[w].ncol, ctx->alpha[w].nlay, ncol, nlay);
   const int nsub = which == 0 ? kSwNGpt : 140;
   const int nw = (nlay + 63) / 64;
   const size_t nl = (size_t)ncol * nlay;
@@ -527,13 +540,16 @@ int mcica_mask_impl(rrtmg_ctx *ctx, int which, int ncol, int nlay, int icld, int
   RRTMG_HIP_CHECK(ctx, hipMemcpyAsync(dc, cldfrac, nl * 8, hipMemcpyHostToDevice, s));
   RRTMG_HIP_CHECK(ctx, hipMemsetAsync(ctx->err_dev, 0, sizeof(int), s));
   const int ntile = (ncol + 63) / 64;
+  const double *alpha = expo ? ctx->alpha[w].dev : nullptr;
+  if (expo) RRTMG_HIP_CHECK(ctx, hipStreamWaitEvent(s, ctx->alpha_ev[w], 0));   // (a copy from device memory may be on the longwave's stream)
   if (irng != 0) {
-    rc = mt_mask_device(ctx, which == 0 ? 0 : 1, ncol, nlay, nsub, icld, permuteseed, dc, mk, nw, 0, 0, s);
+    rc = mt_mask_device(ctx, w, ncol, nlay, nsub, icld, permuteseed, dc, mk, nw, 0, 0, s, alpha);
     if (rc) return rc;
   } else {
-    const uint32_t *jumps = kiss_jumps_device(ctx, which == 0 ? 0 : 1, nsub, nlay, icld, permuteseed, s);
+    const uint32_t *jumps = kiss_jumps_device(ctx, w, nsub, nlay, icld, permuteseed, s);
     if (!jumps) return ctx->status;
-    hipLaunchKernelGGL(kiss_mask_kernel, dim3(nsub, ntile), dim3(64), 0, s, ncol, nlay, icld, dp, dc, mk, nw, ctx->err_dev, jumps);
+    if (expo) hipLaunchKernelGGL(kiss_mask_exp_kernel, dim3(nsub, ntile), dim3(64), 0, s, ncol, nlay, icld, dp, dc, alpha, mk, nw, ctx->err_dev, jumps);
+    else hipLaunchKernelGGL(kiss_mask_kernel, dim3(nsub, ntile), dim3(64), 0, s, ncol, nlay, icld, dp, dc, mk, nw, ctx->err_dev, jumps);
   }
   hipLaunchKernelGGL(cldfmcl_from_mask_kernel, dim3(ntile, nsub), dim3(64), 0, s, ncol, nlay, nsub, mk, nw, dm);
   int herr = 0;
@@ -620,6 +636,8 @@ static int sw_permuted_call(rrtmg_ctx *ctx, InnerCall kind, const rrtmg_sw_args 
     b.taucld = pm.gather_elem("taucld", a->taucld, kSwNBand); b.ssacld = pm.gather_elem("ssacld", a->ssacld, kSwNBand);
     b.asmcld = pm.gather_elem("asmcld", a->asmcld, kSwNBand); b.fsfcld = pm.gather_elem("fsfcld", a->fsfcld, kSwNBand);
     if (a->mcica) b.cldfmcl = pm.gather_elem("cldfmcl", a->cldfmcl, kSwNGpt);
+    // exponential overlap: the rank correlations are one more [nlay][N] input of the mask step
+    if (call_overlap_exp(ctx, 0, a) && !a->cldfmcl) ctx->alpha_inner[0] = pm.gather("alpha", ctx->alpha[0].dev, l);
   }
   b.tauaer = b.ssaaer = b.asmaer = nullptr; b.ecaer = nullptr;
   if (a->iaer == 10) {
@@ -628,7 +646,7 @@ static int sw_permuted_call(rrtmg_ctx *ctx, InnerCall kind, const rrtmg_sw_args 
   } else if (a->iaer == 6) {
     b.ecaer = pm.gather("ecaer", a->ecaer, l * 6, true);   // sw_aer_kernel runs over the whole grid
   }
-  if (!pm.ok) return ctx->status;
+  if (!pm.ok) { ctx->alpha_inner[0] = nullptr; return ctx->status; }
   pm.flush_gather();
   // the inner call's outputs, registered for the scatter in the order plain, components, bands
   b.swuflx = pm.out("o0", u[0], l1); b.swdflx = pm.out("o1", u[1], l1); b.swhr = pm.out("o2", u[2], l);
@@ -647,7 +665,7 @@ static int sw_permuted_call(rrtmg_ctx *ctx, InnerCall kind, const rrtmg_sw_args 
     bb.up = pm.out("b0", bp->up, rows); bb.dn = pm.out("b1", bp->dn, rows); bb.upc = pm.out("b2", bp->upc, rows);
     bb.dnc = pm.out("b3", bp->dnc, rows); bb.dndir = pm.out("b4", bp->dndir, rows); bb.dndirc = pm.out("b5", bp->dndirc, rows);
   }
-  if (!pm.ok) return ctx->status;
+  if (!pm.ok) { ctx->alpha_inner[0] = nullptr; return ctx->status; }
   return permuted_tail(c, pm, [&]() {
     const int rc = sw_fluxes_impl(ctx, &b, sp ? &sb : nullptr, cp ? &cb : nullptr, bp ? &bb : nullptr);
     if (!rc && packed) ctx->sw_pack_reported = true;
@@ -658,6 +676,7 @@ static int sw_permuted_call(rrtmg_ctx *ctx, InnerCall kind, const rrtmg_sw_args 
 int sw_fluxes_impl(rrtmg_ctx *ctx, const rrtmg_sw_args *a, const rrtmg_sw_surface *sp, const rrtmg_sw_components *cp, const rrtmg_sw_band_fluxes *bp) {
   const bool clr = ctx->sw_clear_sky;   // rrtmg_hip_set_sw_clear_sky: false = swuflxc, swdflxc and swhrc are neither formed nor read from `a`
   if (!clr && (cp || bp)) return ctx->fail(RRTMG_ERR_ARG, "shortwave flux components and band fluxes need the clear-sky stream: rrtmg_hip_set_sw_clear_sky(ctx, 0) is in force (set it to 1 for this call)");
+  if (int orc = call_overlap_check(ctx, 0, a)) return orc;
   if (sw_call_is_packed(ctx, a)) return sw_permuted_call(ctx, kInnerPacked, a, sp, cp, bp);
   if (call_is_sorted(ctx, 0, a, cp || bp || sp || ctx->sw_night_skip || ctx->sw_night_pack || sw_amplitudes_differ_from_one(a))) return sw_permuted_call(ctx, kInnerSorted, a, nullptr, nullptr, nullptr);
   int rc = call_begin(ctx, 0, a);
@@ -668,8 +687,9 @@ int sw_fluxes_impl(rrtmg_ctx *ctx, const rrtmg_sw_args *a, const rrtmg_sw_surfac
   const SwTab &T = *(SwTab *)ctx->sw_desc;
   SwDev d{};
   d.ncol = N; d.nlay = L;
-  d.icld = a->icld; d.iaer = a->iaer;
-  if (d.icld < 0 || d.icld > 3) d.icld = 2;                 // rrtmg_sw_rad.nomcica.f90:563
+  d.iaer = a->iaer;
+  const double *alpha = nullptr;
+  d.icld = call_overlap(ctx, 0, a, alpha);                  // (outside 0..3: 2, rrtmg_sw_rad.nomcica.f90:563; 4, 5 with rank correlations set)
   if (d.iaer != 0 && d.iaer != 6 && d.iaer != 10) d.iaer = 0;
   d.inflag = a->inflgsw; d.iceflag = a->iceflgsw; d.liqflag = a->liqflgsw; d.mcica = a->mcica ? 1 : 0;
   d.k = ctx->k;
@@ -804,7 +824,7 @@ int sw_fluxes_impl(rrtmg_ctx *ctx, const rrtmg_sw_args *a, const rrtmg_sw_surfac
     hipLaunchKernelGGL(sw_aer_kernel, gcl, blk, 0, s, d, T, ecaer, ta, om, as);
     d.tauaer = ta; d.ssaaer = om; d.asmaer = as;
   }
-  if (clouds && d.mcica && (rc = mcica_mask_launch(c, kSwNGpt, d, a, cldfmcl_dev, night ? sw_kiss_mask_night_kernel : nullptr, d.coszen))) return rc;
+  if (clouds && d.mcica && (rc = mcica_mask_launch(c, kSwNGpt, d, a, cldfmcl_dev, night ? sw_kiss_mask_night_kernel : nullptr, d.coszen, alpha, sw_kiss_mask_exp_night_kernel))) return rc;
   // preparation, solve and spectral integration, one column chunk at a time: the chunk's prep rows (58 MB at 8192 columns x
   // 60 layers) are read by its 32 work items while still in the L2s / the Infinity Cache, not streamed back from HBM after
   // the preparation of the whole grid (every solve launch of every chunk has its own event pair)

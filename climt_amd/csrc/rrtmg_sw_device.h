@@ -517,6 +517,53 @@ RRTMG_HD void kiss_mask_jump(int ncol, int nlay, int icld, const double *play, c
   kiss_mask_subcolumn(ncol, nlay, icld, cldfr, mask, nw, col, g, k);
 }
 
+// ---- exponential (icld 4) and exponential-random (icld 5) overlap: opt-in, not in the reference (the definition is in
+// include/rrtmg_hip.h, rrtmg_hip_set_mcica_overlap_alpha).  A sub-column takes 2 * nlay draws, x_0 y_0 x_1 y_1 ...: the rank of
+// layer l is that of layer l - 1 where y_l < a_l, else the fresh draw x_l; a_l = alpha[l][col], and 0 under icld 5 above a layer
+// without cloud.  y_0 is drawn and not used.  The bit is the existing comparison, rank >= 1 - cf.
+// Siblings of kiss_mask_subcolumn, kiss_mask_column and kiss_mask_jump, whose code stays as it is.
+RRTMG_HD void kiss_mask_subcolumn_exp(int ncol, int nlay, int icld, const double *cldfr, const double *alpha, uint64_t *mask, int nw, int col, int g, Kiss &k) {
+  const int N = ncol, L = nlay;
+  const double cldmin = 1.0e-20;
+  double rank = 0.0, cfm = 0.0;
+  uint64_t word = 0;
+  for (int l = 0; l < L; ++l) {
+    double cf = cldfr[(long)l * N + col];
+    if (cf < cldmin) cf = 0.0;
+    const double x = kiss_next(k), y = kiss_next(k);
+    if (l == 0) {
+      rank = x;
+    } else {
+      const double a = (icld == 5 && cfm == 0.0) ? 0.0 : alpha[(long)l * N + col];
+      if (!(y < a)) rank = x;
+    }
+    cfm = cf;
+    if (rank >= 1.0 - cf) word |= (1ull << (l & 63));
+    if ((l & 63) == 63 || l == L - 1) { mask[((long)g * nw + (l >> 6)) * N + col] = word; word = 0; }
+  }
+}
+// one stream per column, the sub-columns one after the other: the definition the jump-ahead form is tested against
+RRTMG_HD void kiss_mask_column_exp(int ncol, int nlay, int nsub, int icld, int changeSeed, const double *play, const double *cldfr,
+                                   const double *alpha, uint64_t *mask, int nw, int *err, int col) {
+  for (int g = 0; g < nsub; ++g)
+    for (int w = 0; w < nw; ++w) mask[((long)g * nw + w) * ncol + col] = 0ull;
+  if (nlay < 4) { report_error(err, RRTMG_ERR_ARG); return; }
+  Kiss k;
+  if (!kiss_seed_column(ncol, play, err, col, k)) return;
+  for (int i = 0; i < changeSeed; ++i) (void)kiss_next(k);
+  for (int g = 0; g < nsub; ++g) kiss_mask_subcolumn_exp(ncol, nlay, icld, cldfr, alpha, mask, nw, col, g, k);
+}
+// one thread per (column, sub-column); jumps: kiss_build_jumps with icld 4 or 5 (2 * nlay draws per sub-column)
+RRTMG_HD void kiss_mask_jump_exp(int ncol, int nlay, int icld, const double *play, const double *cldfr, const double *alpha, uint64_t *mask, int nw,
+                                 int *err, const uint32_t *jumps, int col, int g) {
+  for (int w = 0; w < nw; ++w) mask[((long)g * nw + w) * ncol + col] = 0ull;
+  if (nlay < 4) { report_error(err, RRTMG_ERR_ARG); return; }
+  Kiss k;
+  if (!kiss_seed_column(ncol, play, err, col, k)) return;
+  kiss_jump(k, jumps + (long)g * kKissJumpWords);
+  kiss_mask_subcolumn_exp(ncol, nlay, icld, cldfr, alpha, mask, nw, col, g, k);
+}
+
 // ------------------------------------------------------------------------------------------
 // transmittance table / two-stream layer operators
 // ------------------------------------------------------------------------------------------

@@ -237,6 +237,19 @@ def _derived(ds, comp_inputs):
     return out
 
 
+def _device_overlap(self, ds, which, inp):
+    """cloud_overlap_method "exponential" / "exponential_random" on a DeviceState: the rank correlations from the resident
+    pressure and temperature (rrtmg_hip_overlap_alpha with device pointers, on the main stream), copied into the context for
+    this spectrum in stream order (rrtmg_hip_set_mcica_overlap_alpha) -- nothing leaves HBM."""
+    if not getattr(self, "_exp_overlap", None):
+        return
+    from .rrtmg.common import rd_over_g
+    nlay, ncol = inp["nlay"], inp["ncol"]
+    alpha = ds.work(("d.overlap_alpha", which), (nlay, ncol), ("mid_levels", "*"), "dimensionless")
+    ds.ctx.overlap_alpha(inp["play"], inp["tlay"], self._exp_overlap[1], rd_over_g(), out=alpha.ptr, memspace=1, ncol=ncol, nlay=nlay)
+    ds.ctx.set_mcica_overlap_alpha(which, alpha.ptr, memspace=1, ncol=ncol, nlay=nlay)
+
+
 def shortwave_device_call(self, ds):
     """RRTMGShortwave on a DeviceState: the body of array_call (sw/component.py:472-668) with device pointers."""
     ds.init_tables("sw", self._Cpd)
@@ -297,6 +310,7 @@ def shortwave_device_call(self, ds):
         cz = ds.work("d.coszen.night", (ncol,), ("*",), "dimensionless")
         ds.ctx.elementwise("cosday", ncol, ds["zenith_angle"].ptr, cz.ptr)
         inp["coszen"] = cz.ptr
+    _device_overlap(self, ds, "sw", inp)
     if comps or bands or surface:
         ds.ctx.sw_fluxes(inp, mcica=self._mcica, out=out, memspace=1, components={c: q.ptr for c, q in comps.items()} if comps else None,
                          bands={b: q.ptr for b, q in bands.items()} if bands else None, surface=surface)
@@ -362,6 +376,7 @@ def longwave_device_call(self, ds):
         names = getattr(self, "_band_names", tuple(BAND_FLUX_DIAGNOSTICS))
         bands = {BAND_FLUX_DIAGNOSTICS[k]: w("band." + BAND_FLUX_DIAGNOSTICS[k], (16,) + il, ("num_longwave_bands", "interface_levels", "*"), "W m^-2") for k in names}
     self._apply_clear_sky(ds.ctx)
+    _device_overlap(self, ds, "lw", inp)
     if bands:
         ds.ctx.lw_fluxes(inp, mcica=self._mcica, out=out, memspace=1, bands={b: q.ptr for b, q in bands.items()})
     else:

@@ -439,7 +439,9 @@ class ShardedRadiation:
         waits for the kernels before it starts the gather.
         sync=False: do not wait for this step's kernels (a time loop that needs nothing on the host: the streams order
         step i+1 behind step i, the status flags are sticky and are collected by the next synchronizing step or finish();
-        the host still waits for the gather that last read the buffer this step writes, nbuf steps back)."""
+        the host still waits for the gather that last read the buffer this step writes, nbuf steps back).
+        Exponential McICA overlap (icld 4, 5 in `inp`): no argument here -- the owner of the block sets its block's columns of
+        the rank correlations on its context, ctx.set_mcica_overlap_alpha("both", alpha[:, lo:hi]), before the step."""
         b = self.i % self.nbuf
         self.i += 1
         if self.inflight[b]:                      # the gather that read this buffer (nbuf steps ago) must be done

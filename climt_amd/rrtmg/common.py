@@ -8,6 +8,10 @@ from .._lib import CONSTANT_NAMES, Context
 from .._sympl_compat import get_constant
 
 rrtmg_cloud_overlap_method_dict = {"clear_only": 0, "random": 1, "maximum_random": 2, "maximum": 3}
+# Exponential and exponential-random McICA overlap (icld 4, 5): not in the reference, so not in the dict above (whose keys and
+# values are the reference's).  The components look here first; the library generates such masks while rank correlations are
+# set on the context (Context.set_mcica_overlap_alpha).
+rrtmg_exponential_overlap_dict = {"exponential": 4, "exponential_random": 5}
 rrtmg_cloud_props_dict = {"direct_input": 0, "single_cloud_type": 1, "liquid_and_ice_clouds": 2}
 rrtmg_cloud_ice_props_dict = {"ebert_curry_one": 0, "ebert_curry_two": 1, "key_streamer_manual": 2, "fu": 3}
 rrtmg_cloud_liquid_props_dict = {"radius_independent_absorption": 0, "radius_dependent_absorption": 1}
@@ -225,3 +229,47 @@ def output_arrays(pool, output_properties, raw_input_state, input_properties):
             dims = input_properties[name]["dims"]
         out[name] = pool.zeros_like_fresh(name, [lengths[d] for d in dims])
     return out
+
+
+def exponential_overlap_option(cloud_overlap_method, mcica, decorrelation_length):
+    """-> (icld, decorrelation length in metres) for cloud_overlap_method "exponential" / "exponential_random", or None for
+    any other method (which then goes through rrtmg_cloud_overlap_method_dict as ever).  These methods exist for McICA only."""
+    if type(cloud_overlap_method) is not str or cloud_overlap_method.lower() not in rrtmg_exponential_overlap_dict:
+        return None
+    if not mcica:
+        raise ValueError("cloud_overlap_method=%r needs mcica=True: there is no non-McICA exponential overlap" % cloud_overlap_method)
+    length = float(decorrelation_length)
+    if not length > 0.0:
+        raise ValueError("cloud_overlap_decorrelation_length must be positive (metres), got %r" % (decorrelation_length,))
+    return rrtmg_exponential_overlap_dict[cloud_overlap_method.lower()], length
+
+
+def rd_over_g():
+    """Gas constant of dry air over gravity (m K^-1): the factor of the hypsometric layer distance in Context.overlap_alpha."""
+    return get_constant("gas_constant_of_dry_air", "J kg^-1 K^-1") / get_constant("gravitational_acceleration", "m/s^2")
+
+
+def set_overlap_alpha(ctx, which, length, play, tlay):
+    """Rank correlations alpha = exp(-dz / length) from the state's mid-layer pressure (any unit: only ratios enter) and
+    temperature, [nlay][ncol] host arrays, computed by the library and set on `ctx` for `which` ("sw", "lw", "both").  The
+    context is shared between components, so each sets its own before every call.
+    On a library context alpha never comes back to the host: pressure and temperature go up into scratch buffers kept with the
+    context, rrtmg_hip_overlap_alpha writes a device buffer and rrtmg_hip_set_mcica_overlap_alpha copies it on the device --
+    two uploads per call instead of two uploads, a download and a third upload.  Any other context (the host emulation of the
+    tests) gets the host-array calls."""
+    play, tlay = np.ascontiguousarray(play, dtype=np.float64), np.ascontiguousarray(tlay, dtype=np.float64)
+    if not isinstance(ctx, Context):
+        ctx.set_mcica_overlap_alpha(which, ctx.overlap_alpha(play, tlay, length, rd_over_g()))
+        return
+    from .. import _hip
+    nlay, ncol = play.shape
+    scratch = ctx.__dict__.setdefault("_overlap_scratch", {})
+    if scratch.get("shape") != (nlay, ncol):
+        scratch.clear()
+        scratch.update(shape=(nlay, ncol), play=_hip.DeviceArray((nlay, ncol)), tlay=_hip.DeviceArray((nlay, ncol)), alpha=_hip.DeviceArray((nlay, ncol)))
+    # (work enqueued by a device-resident caller in deferred mode may still read the buffers: a host-state call waits, as the
+    #  library's host-pointer calls do)
+    ctx.synchronize()
+    scratch["play"].upload(play); scratch["tlay"].upload(tlay)
+    ctx.overlap_alpha(scratch["play"].ptr, scratch["tlay"].ptr, length, rd_over_g(), out=scratch["alpha"].ptr, memspace=1, ncol=ncol, nlay=nlay)
+    ctx.set_mcica_overlap_alpha(which, scratch["alpha"].ptr, memspace=1, ncol=ncol, nlay=nlay)

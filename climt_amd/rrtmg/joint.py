@@ -117,6 +117,13 @@ def radiation_step(shortwave, longwave, state):
     lw_call = longwave._prepare_call(_raw_view(raw, longwave))
     shortwave._apply_night_skip(ctx)
     longwave._apply_clear_sky(ctx)
+    # exponential overlap: the rank correlations of the one state, set for both spectra at once where both ask for the same length
+    se, le = getattr(shortwave, "_exp_overlap", None), getattr(longwave, "_exp_overlap", None)
+    if se and le and se[1] == le[1]:
+        shortwave._apply_overlap(ctx, sw_call, which="both")
+    else:
+        shortwave._apply_overlap(ctx, sw_call)
+        longwave._apply_overlap(ctx, lw_call)
     sw_kw, lw_kw = dict(sw_call["library"]), dict(lw_call["library"])
     precision = {"precision": sw_kw.pop("precision")} if "precision" in sw_kw else {}      # (float32 boundary: said once, for both)
     lw_kw.pop("precision", None)

@@ -16,7 +16,7 @@ import numpy as np
 from .._sympl_compat import TendencyComponent, get_constant
 from .._util import ensure_contiguous_state
 from .common import boundary_dtype as _boundary_dtype, cast_inputs
-from .common import (UNIT_FACTOR_ON_DEVICE, InputStaging, library_scales, OutputPool, make_context, output_arrays, rrtmg_cloud_ice_props_dict, rrtmg_cloud_liquid_props_dict, rrtmg_cloud_overlap_method_dict,
+from .common import (UNIT_FACTOR_ON_DEVICE, InputStaging, library_scales, OutputPool, make_context, output_arrays, rrtmg_cloud_ice_props_dict, rrtmg_cloud_liquid_props_dict, rrtmg_cloud_overlap_method_dict, exponential_overlap_option, set_overlap_alpha,
                      rrtmg_cloud_props_dict, rrtmg_random_number_dict)
 
 
@@ -108,7 +108,8 @@ class RRTMGLongwave(TendencyComponent):
     def __init__(self, calculate_change_up_flux=False, cloud_overlap_method=None, cloud_optical_properties="liquid_and_ice_clouds",
                  cloud_ice_properties="ebert_curry_two", cloud_liquid_water_properties="radius_dependent_absorption",
                  calculate_interface_temperature=True, mcica=False, random_number_generator="mersenne_twister", device=0,
-                 allow_synthetic_tables=False, band_fluxes=False, clear_sky_diagnostics=True, boundary_dtype="float64", **kwargs):
+                 allow_synthetic_tables=False, band_fluxes=False, clear_sky_diagnostics=True, boundary_dtype="float64",
+                 cloud_overlap_decorrelation_length=2000.0, **kwargs):
         """Same keyword arguments and defaults as climt.RRTMGLongwave (lw/component.py:167-178); additions: `device`
         (GPU ordinal), `allow_synthetic_tables` (see the module docstring) and `band_fluxes`: True adds the up / down fluxes
         (all sky, clear sky) by spectral band (BAND_FLUX_DIAGNOSTICS) to this instance's diagnostics -- or, given as a list
@@ -119,7 +120,9 @@ class RRTMGLongwave(TendencyComponent):
         change_in_clear_sky_upward_flux_with_surface_temperature stays None.  Not together with clear-sky band diagnostics
         (band_fluxes=True, or a list naming one of CLEAR_SKY_BAND_DIAGNOSTICS: ValueError); all-sky band diagnostics (a list of
         the other two names) stay allowed; `boundary_dtype`: "float32" hands the state arrays to the library as 4-byte reals
-        (rrtmg_hip_lw_fluxes_f32; see RRTMGShortwave) and returns float32 diagnostics and tendencies."""
+        (rrtmg_hip_lw_fluxes_f32; see RRTMGShortwave) and returns float32 diagnostics and tendencies;
+        `cloud_overlap_method` also takes "exponential" and "exponential_random" with `cloud_overlap_decorrelation_length`
+        (metres), as RRTMGShortwave does: McICA only (ValueError without mcica=True)."""
         self._boundary_dtype = _boundary_dtype(boundary_dtype)
         if isinstance(band_fluxes, (list, tuple, set, frozenset)):
             unknown = [k for k in band_fluxes if k not in BAND_FLUX_DIAGNOSTICS]
@@ -153,7 +156,9 @@ class RRTMGLongwave(TendencyComponent):
                                 "clouds using McICA.")
         if cloud_overlap_method is None:
             cloud_overlap_method = "random"
-        self._cloud_overlap = rrtmg_cloud_overlap_method_dict[cloud_overlap_method.lower()]
+        # "exponential" / "exponential_random" (McICA only; not in the reference's dict): icld 4 / 5 and the decorrelation length
+        self._exp_overlap = exponential_overlap_option(cloud_overlap_method, mcica, cloud_overlap_decorrelation_length)
+        self._cloud_overlap = self._exp_overlap[0] if self._exp_overlap else rrtmg_cloud_overlap_method_dict[cloud_overlap_method.lower()]
         self._cloud_optics = rrtmg_cloud_props_dict[cloud_optical_properties.lower()]
         self._ice_props = rrtmg_cloud_ice_props_dict[cloud_ice_properties.lower()]
         self._liq_props = rrtmg_cloud_liquid_props_dict[cloud_liquid_water_properties.lower()]
@@ -195,11 +200,19 @@ class RRTMGLongwave(TendencyComponent):
         elif not clear:
             raise RuntimeError("clear_sky_diagnostics=False: this context has no set_lw_clear_sky")
 
+    def _apply_overlap(self, ctx, call):
+        """cloud_overlap_method "exponential" / "exponential_random": the rank correlations of this state, set on the context for
+        the longwave before the call (see RRTMGShortwave._apply_overlap).  Any other method: nothing."""
+        if getattr(self, "_exp_overlap", None):
+            play, tlay = call["overlap_state"]
+            set_overlap_alpha(ctx, "lw", self._exp_overlap[1], play, tlay)
+
     @ensure_contiguous_state
     def array_call(self, state):
         """Longwave heating tendency and up/down fluxes (all-sky and clear-sky)."""
         call = self._prepare_call(state)
         self._apply_clear_sky(self._ctx)
+        self._apply_overlap(self._ctx, call)
         self._ctx.lw_fluxes(**call["library"])
         return self._finish_call(call)
 
@@ -253,12 +266,13 @@ class RRTMGLongwave(TendencyComponent):
                 out[key] = self._pool.zeros_like_fresh(key, (n_layers + 1, n_columns))
         self._input_staging.wait()
         library = dict(inp=inp, mcica=self._mcica, out=out)
+        overlap_state = (inp["play"], inp["tlay"])      # (what _apply_overlap reads: the float64 arrays, before any cast)
         if getattr(self, "_boundary_dtype", np.float64) == np.float32:      # (the default passes no keyword: any context serves it)
             cast_inputs(inp, np.float32)
             library.update(precision="float32")
         if self._band_fluxes:
             library.update(bands={BAND_FLUX_DIAGNOSTICS[k]: diagnostics[k] for k in self._band_names})
-        return dict(library=library, tendencies=tendencies, diagnostics=diagnostics)
+        return dict(library=library, tendencies=tendencies, diagnostics=diagnostics, overlap_state=overlap_state)
 
     def _finish_call(self, call):
         """array_call, part 3 of 3: what follows the library call."""

@@ -10,7 +10,7 @@ from .._sympl_compat import TendencyComponent, get_constant
 from .._util import ensure_contiguous_state
 from .common import boundary_dtype as _boundary_dtype, cast_inputs
 from .common import (UNIT_FACTOR_ON_DEVICE, InputStaging, library_scales, OutputPool, make_context, output_arrays, rrtmg_aerosol_input_dict, rrtmg_cloud_ice_props_dict, rrtmg_cloud_liquid_props_dict,
-                     rrtmg_cloud_overlap_method_dict, rrtmg_cloud_props_dict, rrtmg_random_number_dict)
+                     rrtmg_cloud_overlap_method_dict, rrtmg_cloud_props_dict, rrtmg_random_number_dict, exponential_overlap_option, set_overlap_alpha)
 
 
 def _prop(dims, units):
@@ -194,7 +194,7 @@ class RRTMGShortwave(TendencyComponent):
                  facular_sunspot_amplitude=None, solar_variability_by_band=None, aerosol_type="no_aerosol", mcica=False,
                  random_number_generator="mersenne_twister", device=0, flux_components=False, band_fluxes=False,
                  spectral_surface_albedo=False, skip_night_columns=False, pack_day_columns=False, clear_sky_diagnostics=True,
-                 boundary_dtype="float64", **kwargs):
+                 boundary_dtype="float64", cloud_overlap_decorrelation_length=2000.0, **kwargs):
         """Same keyword arguments and defaults as climt.RRTMGShortwave (sw/component.py:179-194); the additions are `device`
         (GPU ordinal) and `flux_components`: True adds the downward flux split into direct and diffuse parts -- all bands,
         UV/visible bands, near-IR bands, and all bands clear sky (FLUX_COMPONENT_DIAGNOSTICS) -- to this instance's
@@ -266,7 +266,9 @@ class RRTMGShortwave(TendencyComponent):
                                     "the shortwave.")
         if cloud_overlap_method is None:
             cloud_overlap_method = "random"
-        self._cloud_overlap = rrtmg_cloud_overlap_method_dict[cloud_overlap_method.lower()]
+        # "exponential" / "exponential_random" (McICA only; not in the reference's dict): icld 4 / 5 and the decorrelation length
+        self._exp_overlap = exponential_overlap_option(cloud_overlap_method, mcica, cloud_overlap_decorrelation_length)
+        self._cloud_overlap = self._exp_overlap[0] if self._exp_overlap else rrtmg_cloud_overlap_method_dict[cloud_overlap_method.lower()]
         self._cloud_optics = rrtmg_cloud_props_dict[cloud_optical_properties.lower()]
         self._ice_props = rrtmg_cloud_ice_props_dict[cloud_ice_properties.lower()]
         self._liq_props = rrtmg_cloud_liquid_props_dict[cloud_liquid_water_properties.lower()]
@@ -313,6 +315,14 @@ class RRTMGShortwave(TendencyComponent):
         elif not clear:
             raise RuntimeError("clear_sky_diagnostics=False: this context has no set_sw_clear_sky")
 
+    def _apply_overlap(self, ctx, call, which="sw"):
+        """cloud_overlap_method "exponential" / "exponential_random": the rank correlations of this state, computed by the library
+        from the call's mid-layer pressure and temperature and set on the context for this spectrum (which="both": for the
+        longwave of a joint call too).  Any other method: nothing."""
+        if getattr(self, "_exp_overlap", None):
+            play, tlay = call["overlap_state"]
+            set_overlap_alpha(ctx, which, self._exp_overlap[1], play, tlay)
+
     def __call__(self, state, *args, **kwargs):
         """A host state goes through sympl's machinery to array_call; a climt_amd.DeviceState (state resident in HBM) takes
         the device path: same quantities, DeviceQuantity handles instead of arrays (climt_amd/device_state.py)."""
@@ -326,6 +336,7 @@ class RRTMGShortwave(TendencyComponent):
         """Shortwave heating tendency and up/down fluxes (all-sky and clear-sky)."""
         call = self._prepare_call(state)
         self._apply_night_skip(self._ctx)
+        self._apply_overlap(self._ctx, call)
         self._ctx.sw_fluxes(**call["library"])
         return self._finish_call(call)
 
@@ -382,6 +393,7 @@ class RRTMGShortwave(TendencyComponent):
             out.update({m: diagnostics[k] for k, m in CLEAR_SKY_DIAGNOSTICS.items()})
         self._input_staging.wait()
         library = dict(inp=inp, mcica=self._mcica, out=out)
+        overlap_state = (inp["play"], inp["tlay"])      # (what _apply_overlap reads: the float64 arrays, before any cast)
         if getattr(self, "_boundary_dtype", np.float64) == np.float32:      # (the default passes no keyword: any context serves it)
             cast_inputs(inp, np.float32)
             if surface is not None:
@@ -393,7 +405,7 @@ class RRTMGShortwave(TendencyComponent):
             library.update(components=comps, bands=bands, surface=surface)
         elif surface is not None:
             library.update(surface=surface)
-        return dict(library=library, tendencies=tendencies, diagnostics=diagnostics)
+        return dict(library=library, tendencies=tendencies, diagnostics=diagnostics, overlap_state=overlap_state)
 
     @staticmethod
     def _finish_call(call):

@@ -539,6 +539,49 @@ int rrtmg_hip_radiation_fluxes_f32(rrtmg_ctx *ctx, const rrtmg_radiation_call *c
 int rrtmg_hip_mcica_mask(rrtmg_ctx *ctx, int which, int ncol, int nlay, int icld, int permuteseed,
                          int irng, const double *play, const double *cldfrac, double *cldfmcl);
 
+/* ---- McICA: exponential and exponential-random cloud overlap (opt-in; not in the reference) ------------------------------
+ * icld 1, 2, 3 are the reference's random, maximum-random and maximum overlap.  Maximum-random overlap treats a contiguous cloud
+ * deck as perfectly correlated however deep it is and so underestimates total cloud cover.  Exponential overlap lets the rank
+ * correlation of adjacent layers decay, alpha = exp(-dz / L) for a decorrelation length L; its exponential-random variant makes
+ * cloud blocks separated by clear air independent.  While rank correlations are set for a spectrum, a McICA call of that
+ * spectrum with icld = 4 (exponential) or 5 (exponential-random) and cldfmcl == NULL generates its sub-column mask on the
+ * device as follows, with either irng.  Only the mask changes: the solves consume mask bits as ever.
+ *
+ * Definition, for one column and one sub-column g, layers l = 0 .. L-1 from the surface up:
+ *  - cf_l = cldfr[l], set to 0 where < 1e-20 (the generators' cldmin rule).
+ *  - The sub-column consumes 2 L draws, in the order x_0, y_0, x_1, y_1, ..., x_{L-1}, y_{L-1}; y_0 is drawn and unused.  A draw
+ *    becomes a real number as in the generator's other modes (kissvec: kiss * 2.328306e-10 + 0.5; Mersenne twister: getRandomReal).
+ *  - alpha_l = alpha[l][col] of the array set below; row 0 is ignored; values are used as given, with no clamp.
+ *      icld = 4: a_l = alpha_l;      icld = 5: a_l = 0 if cf_{l-1} == 0, else alpha_l.
+ *  - Ranks: c_0 = x_0; for l >= 1, c_l = c_{l-1} if y_l < a_l (strictly), otherwise c_l = x_l.
+ *  - Bit l of the mask is set iff c_l >= 1 - cf_l (the comparison of the other modes).
+ * Stream positions: kissvec -- sub-column g of a column starts changeSeed + g * 2 L draws into that column's stream; Mersenne
+ * twister -- the one stream is ordered (sub-column, column, layer, {x, y}), and a shard (shard_col0 / shard_ncol) skips
+ * shard_col0 * 2 L draws per sub-column, so that shards reproduce the whole grid bit for bit.
+ *
+ * rrtmg_hip_set_mcica_overlap_alpha: which = 0 shortwave, 1 longwave, 2 both; alpha [nlay][ncol] under memspace 0 (host) or 1
+ * (device); alpha = NULL clears the setting (ncol, nlay, memspace are then ignored).  The array is COPIED into a buffer of the
+ * context: host memory before the call returns, device memory in order on the stream the spectrum's calls run on -- the caller
+ * may reuse its array at once, and sets it again when the state changes.  A sharded caller sets its block's columns: the shape
+ * is that of the flux call.
+ *  - While set: a flux call of that spectrum with icld 4 or 5 and mcica = 0 returns RRTMG_ERR_ARG (there is no non-McICA
+ *    exponential overlap), and so does one whose ncol, nlay differ from the stored shape; nothing is enqueued and the context
+ *    stays usable.  icld 0..3 behaves as without the setting.  rrtmg_hip_mcica_mask with icld 4 or 5 returns the exponential
+ *    mask (shape mismatch: RRTMG_ERR_ARG).  With an external cldfmcl the rank correlations are not read.
+ *  - While not set (the default): nothing changes -- a flux call resets icld > 3 to 2 as the reference does, and
+ *    rrtmg_hip_mcica_mask answers RRTMG_ERR_ICLD.  The reference-compatible symbols below never see the setting: it belongs to
+ *    a context, and they reset icld > 3 before the call.
+ *  - The column sort and the day-column pack gather the rank correlations with the call's other inputs; deferred mode, the
+ *    night-column skip, the joint call and the float32 boundary (alpha itself stays double) compose unchanged.
+ * rrtmg_hip_overlap_alpha: alpha [nlay][ncol] from mid-layer pressure and temperature, one streaming kernel: row 0 is 1; for
+ * l >= 1, alpha_l = exp(-dz_l / decorrelation_m) with dz_l = rd_over_g * 0.5 * (T_l + T_{l-1}) * ln(p_{l-1} / p_l) -- the
+ * hypsometric distance of the two mid-layer pressures, rd_over_g = gas constant of dry air / gravity (m K^-1).  memspace as in
+ * the flux calls; with device pointers the kernel is enqueued on the main stream (deferred mode: the call returns at once).
+ * Probe for both by symbol; the argument structs and RRTMG_HIP_ABI_VERSION are unchanged. */
+int rrtmg_hip_set_mcica_overlap_alpha(rrtmg_ctx *ctx, int which, int ncol, int nlay, int memspace, const double *alpha);
+int rrtmg_hip_overlap_alpha(rrtmg_ctx *ctx, int ncol, int nlay, int memspace, const double *play, const double *tlay,
+                            double rd_over_g, double decorrelation_m, double *alpha);
+
 /* ---- reference-compatible entry points (host pointers, default context) ---------------- */
 int rrtmg_hip_default_status(void);
 const char *rrtmg_hip_default_error(void);
