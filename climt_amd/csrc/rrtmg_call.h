@@ -1,10 +1,12 @@
 // rrtmg_call.h -- the host steps that a shortwave and a longwave flux call have in common (private to rrtmg_sw.hip and
 // rrtmg_lw.hip; host code only: no kernel lives here, and the kernels launched here are those of rrtmg_mcica_kernels.h).
-// In the order of a call: the gate to the sorted call, the argument checks, the call's stream, the optional output tables, the
-// chunk plan, the error flag, the McICA mask, the chunk loop, the epilogue, the tail of a permuted call.  The drivers keep
-// what differs: their inputs, work buffers and the kernels of every launch stage with their geometry.
+// In the order of a call: the gate to the sorted call, the argument checks, the call's stream, the walks of the array tables, the
+// chunk plan, the error flag, the McICA mask, the chunk loop, the epilogue, the tail of a permuted call -- and every walk of the
+// call's array tables (rrtmg_call_arrays.h): input registration, output binding, gathers and scatter, widen and narrow.  The
+// drivers keep what differs: the rules of their inputs, work buffers and the kernels of every launch stage with their geometry.
 // which: 0 shortwave, 1 longwave -- the index of rrtmg_ctx::hint, plans, pending, kiss_* and of the err_dev slot.
 #pragma once
+#include "rrtmg_call_arrays.h"
 #include "rrtmg_ctx.h"
 #include "rrtmg_mcica_kernels.h"
 #include "rrtmg_permute.h"
@@ -30,10 +32,11 @@ inline int call_begin(rrtmg_ctx *ctx, int which, const Args *a) {
   if (a->shard_ncol != 0 && (a->shard_col0 < 0 || a->shard_col0 + a->ncol > a->shard_ncol)) return ctx->fail(RRTMG_ERR_ARG, "shard_col0/shard_ncol do not contain ncol columns");
   return ctx_prepare_device(ctx);
 }
-// o: the six outputs every call has (n = 3: a shortwave call without its clear-sky outputs looks at the first three)
-inline int check_outputs(rrtmg_ctx *ctx, double *const *o, int n = 6) {
-  for (int k = 0; k < n; ++k)
-    if (!o[k]) return ctx->fail(RRTMG_ERR_ARG, "output array is NULL");
+// the outputs the call must be given (rrtmg_call_arrays.h: `required`, group on) are there
+template <class Out, size_t n, class All>
+inline int check_outputs(rrtmg_ctx *ctx, const Out (&t)[n], unsigned on, const All &x) {
+  for (const Out &e : t)
+    if (e.required && array_is_read(e.need, on) && !(x.*(e.m))) return ctx->fail(RRTMG_ERR_ARG, "output array is NULL");
   return RRTMG_OK;
 }
 // The stream rule: the shortwave is always on ctx->stream; the longwave moves to stream_lw when the call is deferred and
@@ -42,19 +45,34 @@ inline int check_outputs(rrtmg_ctx *ctx, double *const *o, int n = 6) {
 inline hipStream_t call_stream(const rrtmg_ctx *ctx, int which, int memspace) { return (which == 1 && (ctx->joint || (ctx->deferred && memspace == 1))) ? ctx->stream_lw : ctx->stream; }
 // the table of a joint call's inputs for HostInputs, or nullptr
 inline ShareTable *call_share(const rrtmg_ctx *ctx) { return ctx->joint ? &ctx->joint->table : nullptr; }
-// ---- optional output tables (shortwave components and bands, longwave bands) ---------------------------------------------------
-// One row per member: the work buffer's name, the caller's array (nullptr: not requested, the kernel skips it), the member of
-// the kernel's output struct.  The device array is the caller's pointer under memspace 1, else the named work buffer (wd: the
-// driver's allocator of doubles), which the epilogue downloads behind the same synchronise as the standard outputs.
-struct OptOut { const char *name; double *user; double **dev; };
-template <class Wd>
-inline void opt_out_bind(const OptOut *t, int n, int memspace, size_t count, Wd wd) {
-  for (int k = 0; k < n; ++k)
-    if (t[k].user) *t[k].dev = memspace == 1 ? t[k].user : wd(t[k].name, count);
+// ---- the driver's walks of the array tables (rrtmg_call_arrays.h) ----------------------------------------------------------------
+// Inputs -> HostInputs, in table order.  What is the driver's own comes as `rules`, keyed by the bound member, for the inputs
+// that differ from the default: required, InPolicy::Plain, no unit factor, registered wherever the group is on.
+struct InRule { bool required = true; InPolicy policy = InPolicy::Plain; double mul = 0.0, div = 0.0; bool skip = false; };
+template <class Bound> struct InRuleFor { const double *Bound::*dev; InRule rule; };
+template <class In, size_t n, class All, class Bound, size_t nr>
+inline void register_inputs(HostInputs &hi, const In (&t)[n], unsigned on, const All &x, Bound &d, const GridShape &g, const InRuleFor<Bound> (&rules)[nr]) {
+  for (const In &e : t) {
+    if (!array_is_read(e.need, on)) continue;
+    InRule r;
+    for (const InRuleFor<Bound> &o : rules)
+      if (o.dev == e.dev) r = o.rule;
+    if (!r.skip) hi.add(&(d.*(e.dev)), x.*(e.m), ext_count(e.ext, e.k, g), e.name, r.required, r.policy, r.mul, r.div);
+  }
 }
-inline int opt_out_append(const OptOut *t, int n, size_t count, OutCopy *oc, int nout) {
-  for (int k = 0; k < n; ++k)
-    if (t[k].user) oc[nout++] = {t[k].user, *t[k].dev, count};
+// Outputs.  The device array of one that is read (its group on, the caller's pointer set; nullptr: the kernel skips it) is the
+// caller's pointer under memspace 1, else the named work buffer (wd: the driver's allocator of doubles), which the epilogue
+// downloads behind one synchronise: oc[] in table order -> the number of copies.
+template <class Out, size_t n, class All, class Bound, class Wd>
+inline int bind_outputs(const Out (&t)[n], unsigned on, const All &x, Bound &d, const GridShape &g, int memspace, Wd wd, OutCopy *oc) {
+  int nout = 0;
+  for (const Out &e : t) {
+    double *const user = x.*(e.m);
+    if (!user || !array_is_read(e.need, on)) continue;
+    const size_t count = ext_count(e.ext, e.k, g);
+    d.*(e.dev) = memspace == 1 ? user : wd(e.wname, count);
+    oc[nout++] = {user, d.*(e.dev), count};
+  }
   return nout;
 }
 // ---- chunk plan -----------------------------------------------------------------------------------------------------------------
@@ -194,7 +212,25 @@ inline int call_finish(const CallSite &c, int memspace, const OutCopy *oc, int n
   ctx->status = 0;
   return RRTMG_OK;
 }
-// ---- the permuted call (rrtmg_permute.h: sorted or packed; the gather and output lists are the spectrum's own) -------------------
+// ---- the permuted call (rrtmg_permute.h: sorted or packed; what is gathered and scattered: rrtmg_call_arrays.h) -----------------
+// x: the copy of the caller's structs.  Every input the call reads becomes its gathered copy (nullptr stays nullptr: an absent
+// optional array), every other one nullptr; likewise the outputs, registered for the scatter.
+template <class In, size_t n, class All>
+inline void permute_inputs(ColumnPermute &pm, const In (&t)[n], unsigned on, All &x, const GridShape &g) {
+  for (const In &e : t)
+    x.*(e.m) = !array_is_read(e.need, on) ? nullptr : e.ext == Ext::LayColK ? pm.gather_elem(e.name, x.*(e.m), e.k) : pm.gather(e.name, x.*(e.m), ext_rows(e.ext, e.k, g), e.whole);
+}
+template <class Out, size_t n, class All>
+inline void permute_outputs(ColumnPermute &pm, const Out (&t)[n], unsigned on, All &x, const GridShape &g) {
+  for (const Out &e : t) x.*(e.m) = array_is_read(e.need, on) ? pm.out(e.name, x.*(e.m), ext_rows(e.ext, e.k, g)) : nullptr;
+}
+// The scatter cannot run before the inner call: its table must hold a call's whole output list (a band member: k entries)
+template <class Out, size_t n> constexpr int scatter_entries(const Out (&t)[n]) {
+  int s = 0;
+  for (const Out &e : t) s += e.ext == Ext::KBandLev ? e.k : 1;
+  return s;
+}
+static_assert(scatter_entries(kSwOut) <= kPermuteMaxEntries && scatter_entries(kLwOut) <= kPermuteMaxEntries, "kPermuteMaxEntries: one scatter table for every output");
 // inner(): the spectrum's driver on the copy, which returns once it is enqueued (it finds ctx->inner set).  Behind it ONE
 // scatter launch for every output registered with pm -- which also leaves the counts of rrtmg_hip_sw_night_last where
 // night_out is given -- and the one epilogue: a permuted call is device-resident, so only the flag is read.
@@ -209,7 +245,7 @@ inline int permuted_tail(const CallSite &c, ColumnPermute &pm, Inner inner, int3
   pm.flush_scatter(night_out);
   return call_finish(c, 1, nullptr, 0, ctx->err_dev + c.which);
 }
-// ---- the float32 boundary of a device-resident call (rrtmg_precision.h; the input and output lists are the spectrum's own) -------
+// ---- the float32 boundary of a device-resident call (rrtmg_precision.h; what is widened and narrowed: rrtmg_call_arrays.h) -------
 // The caller's device arrays hold float.  in(): the internal fp64 copy of an input (nullptr stays nullptr), registered for the
 // ONE widen launch; out(): the inner call's fp64 array for the caller's `user`, registered for the ONE narrow launch.  The
 // copies live in named grow-only work buffers ("sw.f32.", "lw.f32.").  The inner call is the ordinary device-resident driver:
@@ -238,6 +274,17 @@ struct BoundaryF32 {
     return p;
   }
 };
+// x: the copy of the caller's structs -- what the call reads becomes its fp64 copy, the rest nullptr (see permute_inputs)
+template <class In, size_t n, class All>
+inline void boundary_inputs(BoundaryF32 &bf, const In (&t)[n], unsigned on, All &x, const GridShape &g) {
+  for (const In &e : t) x.*(e.m) = array_is_read(e.need, on) ? bf.in(e.name, x.*(e.m), ext_count(e.ext, e.k, g)) : nullptr;
+}
+template <class Out, size_t n, class All>
+inline void boundary_outputs(BoundaryF32 &bf, const Out (&t)[n], unsigned on, All &x, const GridShape &g) {
+  for (const Out &e : t) x.*(e.m) = array_is_read(e.need, on) ? bf.out(e.name, x.*(e.m), ext_count(e.ext, e.k, g)) : nullptr;
+}
+// ONE widen and ONE narrow launch: each table holds a whole list
+static_assert(table_size(kSwIn) <= kPrecisionMaxEntries && table_size(kSwOut) <= kPrecisionMaxEntries && table_size(kLwIn) <= kPrecisionMaxEntries && table_size(kLwOut) <= kPrecisionMaxEntries, "kPrecisionMaxEntries");
 // inner(): the fp64 driver on the copies.  It returns with its own epilogue done -- enqueued in deferred mode, else complete
 // and its flag read -- and the narrow launch goes behind its last kernel (or its scatter) on the same stream; a synchronous
 // call then waits for it.  A call that fails returns the inner call's status, and the caller's outputs are not written.

@@ -14,7 +14,9 @@
 // With the clear-sky outputs off (rrtmg_hip_set_lw_clear_sky(0)): lw_solve_all_allsky_kernel in the place of lw_solve_all_kernel,
 // lw_fluxheat_allsky_kernel in the place of lw_fluxheat_kernel, lw_bandflux_allsky_kernel in the place of lw_bandflux_kernel;
 // uflxc, dflxc, hrc and duflxc_dt are neither formed nor copied, and the partial planes are half as many
-// The host steps this call shares with the shortwave's (gate, checks, chunk plan and loop, mask choice, epilogue): rrtmg_call.h
+// The host steps this call shares with the shortwave's (gate, checks, chunk plan and loop, mask choice, epilogue): rrtmg_call.h;
+// the call's grid arrays -- what the driver, the sorted call and the float32 boundary register, gather and copy: the tables
+// kLwIn / kLwOut of rrtmg_call_arrays.h
 #include "rrtmg_call.h"
 #include "rrtmg_lw_device.h"
 #include "rrtmg_lw_host.h"
@@ -273,41 +275,32 @@ int lw_init_impl(rrtmg_ctx *ctx, double cpdair, const char *blob_path) {
   return RRTMG_OK;
 }
 
+// the outputs a call must be given: the standard ones, and with idrv the derivative(s)
+static int lw_check_outputs(rrtmg_ctx *ctx, unsigned on, const LwStructs &x) {
+  if (int rc = check_outputs(ctx, kLwOut, on, x)) return rc;
+  const bool clr = on & kClear;
+  if ((on & kDrv) && (!x.duflx_dt || (clr && !x.duflxc_dt))) return ctx->fail(RRTMG_ERR_ARG, clr ? "idrv=1 needs duflx_dt/duflxc_dt" : "idrv=1 needs duflx_dt");
+  return RRTMG_OK;
+}
 // the call on an internal copy of its inputs, cloud-free columns first (rrtmg_permute.h; see sw_permuted_call): what the driver
-// reads with clouds (the gate has icld != 0), the optional arrays where they are given
+// reads (kLwIn under lw_call_reads; the gate has icld != 0), the optional arrays where they are given
 static int lw_sorted_call(rrtmg_ctx *ctx, const rrtmg_lw_args *a) {
   if (int rc = ctx_prepare_device(ctx)) return rc;
   const CallSite c{ctx, 1, call_stream(ctx, 1, 1)};
-  const bool dr = a->idrv != 0;
   // (clear-sky outputs off: the four are absent from the scatter table, and from the inner call)
-  const bool clr = ctx->lw_clear_sky;
-  double *const u[6] = {a->uflx, a->dflx, a->hr, clr ? a->uflxc : nullptr, clr ? a->dflxc : nullptr, clr ? a->hrc : nullptr};
-  if (int rc = check_outputs(ctx, u, clr ? 6 : 3)) return rc;
-  if (dr && (!a->duflx_dt || (clr && !a->duflxc_dt))) return ctx->fail(RRTMG_ERR_ARG, clr ? "idrv=1 needs duflx_dt/duflxc_dt" : "idrv=1 needs duflx_dt");
+  LwStructs b(a, nullptr);
+  const unsigned on = lw_call_reads(a, nullptr, ctx->lw_clear_sky);
+  if (int rc = lw_check_outputs(ctx, on, b)) return rc;
   ColumnPermute pm(ctx, c.s, kInnerSorted, a->ncol, a->nlay, "lw.sort.");
   if (!pm.prepare(a->cldfr)) return ctx->status;
-  rrtmg_lw_args b = *a;
   b.ncol = pm.Np; b.shard_col0 = 0; b.shard_ncol = 0;
-  const size_t l = (size_t)a->nlay, l1 = l + 1;
-  b.play = pm.gather("play", a->play, l); b.plev = pm.gather("plev", a->plev, l1); b.tlay = pm.gather("tlay", a->tlay, l);
-  b.tlev = pm.gather("tlev", a->tlev, l1); b.tsfc = pm.gather("tsfc", a->tsfc, 1);
-  b.h2ovmr = pm.gather("h2o", a->h2ovmr, l); b.o3vmr = pm.gather("o3", a->o3vmr, l); b.co2vmr = pm.gather("co2", a->co2vmr, l);
-  b.ch4vmr = pm.gather("ch4", a->ch4vmr, l); b.n2ovmr = pm.gather("n2o", a->n2ovmr, l); b.o2vmr = pm.gather("o2", a->o2vmr, l);
-  b.cfc11vmr = pm.gather("cfc11", a->cfc11vmr, l); b.cfc12vmr = pm.gather("cfc12", a->cfc12vmr, l);
-  b.cfc22vmr = pm.gather("cfc22", a->cfc22vmr, l); b.ccl4vmr = pm.gather("ccl4", a->ccl4vmr, l);
-  b.emis = pm.gather("emis", a->emis, 16);
-  b.cldfr = pm.gather("cldfr", a->cldfr, l); b.taucld = pm.gather_elem("taucld", a->taucld, 16);
-  b.cicewp = pm.gather("cicewp", a->cicewp, l); b.cliqwp = pm.gather("cliqwp", a->cliqwp, l);
-  b.reice = pm.gather("reice", a->reice, l); b.reliq = pm.gather("reliq", a->reliq, l);
-  b.tauaer = pm.gather("tauaer", a->tauaer, l * 16);
-  b.cldfmcl = a->mcica ? pm.gather_elem("cldfmcl", a->cldfmcl, kLwNGpt) : nullptr;
+  const GridShape g = grid_shape(a->ncol, a->nlay, 0);
+  permute_inputs(pm, kLwIn, on, b, g);
   // exponential overlap: the rank correlations are one more [nlay][N] input of the mask step
-  if (call_overlap_exp(ctx, 1, a) && !a->cldfmcl) ctx->alpha_inner[1] = pm.gather("alpha", ctx->alpha[1].dev, l);
+  if (call_overlap_exp(ctx, 1, a) && !a->cldfmcl) ctx->alpha_inner[1] = pm.gather("alpha", ctx->alpha[1].dev, g.L);
   if (!pm.ok) { ctx->alpha_inner[1] = nullptr; return ctx->status; }
   pm.flush_gather();
-  b.uflx = pm.out("o0", u[0], l1); b.dflx = pm.out("o1", u[1], l1); b.hr = pm.out("o2", u[2], l);
-  b.uflxc = clr ? pm.out("o3", u[3], l1) : nullptr; b.dflxc = clr ? pm.out("o4", u[4], l1) : nullptr; b.hrc = clr ? pm.out("o5", u[5], l) : nullptr;
-  b.duflx_dt = dr ? pm.out("o6", a->duflx_dt, l1) : nullptr; b.duflxc_dt = dr && clr ? pm.out("o7", a->duflxc_dt, l1) : nullptr;
+  permute_outputs(pm, kLwOut, on, b, g);
   if (!pm.ok) { ctx->alpha_inner[1] = nullptr; return ctx->status; }
   return permuted_tail(c, pm, [&]() { return lw_fluxes_impl(ctx, &b); });
 }
@@ -331,7 +324,8 @@ int lw_fluxes_impl(rrtmg_ctx *ctx, const rrtmg_lw_args *a, const rrtmg_lw_band_f
   const int N = a->ncol, L = a->nlay;
   const size_t nl = (size_t)N * L, nl1 = (size_t)N * (L + 1);
   const LwTab &T = *(LwTab *)ctx->lw_desc;
-  LwDev d{};
+  LwBound bound{};   // the kernels' struct and what else the array tables bind (rrtmg_call_arrays.h)
+  LwDev &d = bound;
   d.ncol = N; d.nlay = L;
   const double *alpha = nullptr;
   d.icld = call_overlap(ctx, 1, a, alpha);    // (outside 0..3: 2, rrtmg_lw_rad.nomcica.f90:436; 4, 5 with rank correlations set)
@@ -347,25 +341,19 @@ int lw_fluxes_impl(rrtmg_ctx *ctx, const rrtmg_lw_args *a, const rrtmg_lw_band_f
   bool ok = true;
   const double ps = a->pressure_scale, ws = a->water_path_scale;
   HostInputs hi(ctx, s, "lw.in.", a->memspace, call_share(ctx), 1, ctx->f32);
-  hi.add(&d.play, a->play, nl, "play", true, InPolicy::Plain, ps); hi.add(&d.plev, a->plev, nl1, "plev", true, InPolicy::Plain, ps);
-  hi.add(&d.tlay, a->tlay, nl, "tlay", true); hi.add(&d.tlev, a->tlev, nl1, "tlev", false); hi.add(&d.tsfc, a->tsfc, N, "tsfc", true);
-  hi.add(&d.h2o, a->h2ovmr, nl, "h2o", true, InPolicy::Plain, a->h2o_mul, a->h2o_div); hi.add(&d.o3, a->o3vmr, nl, "o3", true);
-  hi.add(&d.co2, a->co2vmr, nl, "co2", true); hi.add(&d.ch4, a->ch4vmr, nl, "ch4", true); hi.add(&d.n2o, a->n2ovmr, nl, "n2o", true);
-  hi.add(&d.o2, a->o2vmr, nl, "o2", true);
-  hi.add(&d.cfc11, a->cfc11vmr, nl, "cfc11", false); hi.add(&d.cfc12, a->cfc12vmr, nl, "cfc12", false);
-  hi.add(&d.cfc22, a->cfc22vmr, nl, "cfc22", false); hi.add(&d.ccl4, a->ccl4vmr, nl, "ccl4", false);
-  hi.add(&d.emis, a->emis, (size_t)N * 16, "emis", true);
-  const bool clouds = d.icld >= 1;
-  if (clouds) {
-    hi.add(&d.cldfr, a->cldfr, nl, "cldfr", true);
-    // (given directly -- inflag 0 -- the cloud optical depth is used as it is; otherwise zeros mean there is none to add)
-    hi.add(&d.taucld, a->taucld, nl * 16, "taucld", d.inflag == 0, d.inflag == 0 ? InPolicy::Plain : InPolicy::ZeroAbsent);
-    hi.add(&d.cicewp, a->cicewp, nl, "cicewp", d.inflag >= 1, InPolicy::Plain, ws); hi.add(&d.cliqwp, a->cliqwp, nl, "cliqwp", d.inflag >= 1, InPolicy::Plain, ws);
-    hi.add(&d.reice, a->reice, nl, "reice", d.inflag == 2); hi.add(&d.reliq, a->reliq, nl, "reliq", d.inflag == 2);
-  }
-  hi.add(&d.tauaer, a->tauaer, nl * 16, "tauaer", false, InPolicy::ZeroAbsent);
-  const double *cldfmcl_dev = nullptr;
-  if (clouds && d.mcica && a->cldfmcl) hi.add(&cldfmcl_dev, a->cldfmcl, nl * kLwNGpt, "cldfmcl", true);
+  const LwStructs x(a, bp);
+  const unsigned on = lw_call_reads(a, bp, clr);
+  const GridShape g = grid_shape(N, L, bp ? bp->levels : 0);
+  const bool clouds = on & kClouds;
+  // (taucld given directly -- inflag 0 -- is used as it is; otherwise zeros mean there is none to add, as for tauaer)
+  const InRule optional{false};
+  const InRuleFor<LwBound> rules[] = {
+      {&LwDev::play, {true, InPolicy::Plain, ps}}, {&LwDev::plev, {true, InPolicy::Plain, ps}}, {&LwDev::h2o, {true, InPolicy::Plain, a->h2o_mul, a->h2o_div}},
+      {&LwDev::tlev, optional}, {&LwDev::cfc11, optional}, {&LwDev::cfc12, optional}, {&LwDev::cfc22, optional}, {&LwDev::ccl4, optional},
+      {&LwDev::taucld, {d.inflag == 0, d.inflag == 0 ? InPolicy::Plain : InPolicy::ZeroAbsent}},
+      {&LwDev::cicewp, {d.inflag >= 1, InPolicy::Plain, ws}}, {&LwDev::cliqwp, {d.inflag >= 1, InPolicy::Plain, ws}}, {&LwDev::reice, {d.inflag == 2}}, {&LwDev::reliq, {d.inflag == 2}},
+      {&LwDev::tauaer, {false, InPolicy::ZeroAbsent}}, {&CallLocals::cldfmcl, optional}};   // (the sub-columns: where given)
+  register_inputs(hi, kLwIn, on, x, bound, g, rules);
   if (!hi.finish()) return ctx->status;
 
   auto wd = [&](const char *name, size_t n) -> double * { double *p = (double *)ctx->buf(std::string("lw.w.") + name, n * sizeof(double)); if (!p) ok = false; return p; };
@@ -391,24 +379,12 @@ int lw_fluxes_impl(rrtmg_ctx *ctx, const rrtmg_lw_args *a, const rrtmg_lw_band_f
   if (!d.tlist) ok = false;
   d.scratch = wd("scratch", (size_t)ctile * kLwNGpt * LF_N * L * 64);
   d.part = wd("part", (size_t)T.nitem * nk * (L + 1) * ctile * 64);
-  double *const u[6] = {a->uflx, a->dflx, a->hr, a->uflxc, a->dflxc, a->hrc};
-  if ((rc = check_outputs(ctx, u, clr ? 6 : 3))) return rc;
-  if (d.idrv && (!a->duflx_dt || (clr && !a->duflxc_dt))) return ctx->fail(RRTMG_ERR_ARG, clr ? "idrv=1 needs duflx_dt/duflxc_dt" : "idrv=1 needs duflx_dt");
+  if ((rc = lw_check_outputs(ctx, on, x))) return rc;
+  // the outputs: the standard ones (with idrv: the derivatives), the band fluxes [16][nrow][ncol] where requested
   // (clear-sky outputs off: d.uflxc, d.dflxc, d.hrc and d.duflxc_dt stay nullptr -- no kernel of that path dereferences them)
-  if (a->memspace == 1) {
-    d.uflx = a->uflx; d.dflx = a->dflx; d.hr = a->hr; d.duflx_dt = a->duflx_dt;
-    if (clr) { d.uflxc = a->uflxc; d.dflxc = a->dflxc; d.hrc = a->hrc; d.duflxc_dt = a->duflxc_dt; }
-  } else {
-    d.uflx = wd("o.uflx", nl1); d.dflx = wd("o.dflx", nl1); d.hr = wd("o.hr", nl);
-    if (clr) { d.uflxc = wd("o.uflxc", nl1); d.dflxc = wd("o.dflxc", nl1); d.hrc = wd("o.hrc", nl); }
-    if (d.idrv) { d.duflx_dt = wd("o.du", nl1); if (clr) d.duflxc_dt = wd("o.duc", nl1); }
-  }
-  // band fluxes: [16][nrow][ncol] per requested member
-  static const rrtmg_lw_band_fluxes no_band{}; const rrtmg_lw_band_fluxes &br = bp ? *bp : no_band;   // (nothing requested: every member nullptr)
-  LwBandOut bo{};
-  const OptOut bpt[4] = {{"ob.up", br.up, &bo.up}, {"ob.dn", br.dn, &bo.dn}, {"ob.upc", br.upc, &bo.upc}, {"ob.dnc", br.dnc, &bo.dnc}};
-  const size_t nband = (size_t)kLwNBand * (br.levels ? 2 : L + 1) * N;
-  opt_out_bind(bpt, 4, a->memspace, nband, wd);
+  OutCopy oc[table_size(kLwOut)];
+  const int nout = bind_outputs(kLwOut, on, x, bound, g, a->memspace, wd, oc);
+  const LwBandOut &bo = bound;
   if (!ok) return ctx->status;
 #ifdef RRTMG_PROFILE
   d.phase = (unsigned long long *)ctx->buf("lw.w.phase", 16 * 8);
@@ -429,7 +405,7 @@ int lw_fluxes_impl(rrtmg_ctx *ctx, const rrtmg_lw_args *a, const rrtmg_lw_band_f
   // (more than 64 KB of dynamic LDS has to be allowed per kernel once; if the runtime refuses, the scan re-reads the slab)
   const bool big_lds = ctx->allow_dynamic_lds(0, (const void *)lw_prep_fused_kernel, kLwKeepLayers * 3 * 64 * (int)sizeof(double));
   const int keep_layers = (L <= kLwKeepLayers && (big_lds || (size_t)L * 3 * 64 * sizeof(double) <= 64 * 1024)) ? L : 0;
-  if (clouds && d.mcica && (rc = mcica_mask_launch(c, kLwNGpt, d, a, cldfmcl_dev, nullptr, nullptr, alpha))) return rc;
+  if (clouds && d.mcica && (rc = mcica_mask_launch(c, kLwNGpt, d, a, bound.cldfmcl, nullptr, nullptr, alpha))) return rc;
   if (clouds && d.mcica) hipLaunchKernelGGL(lw_anymask_kernel, gcol, blk, 0, s, d);
   // preparation, solve and band integration, one column chunk at a time (see sw_fluxes_impl)
   const dim3 lwwg(64 * kLwWgWaves);
@@ -474,13 +450,7 @@ int lw_fluxes_impl(rrtmg_ctx *ctx, const rrtmg_lw_args *a, const rrtmg_lw_band_f
 #endif
   // the inner call of a sorted one stops here, enqueued: permuted_tail scatters behind it and runs the epilogue
   if (ctx->inner != kInnerNone) { RRTMG_HIP_CHECK(ctx, hipGetLastError()); return RRTMG_OK; }
-  if (!clr) {   // three downloads (four with idrv), not six (eight), and the band members up / dn behind them
-    OutCopy oa[8] = {{a->uflx, d.uflx, nl1}, {a->dflx, d.dflx, nl1}, {a->hr, d.hr, nl}, {a->duflx_dt, d.duflx_dt, nl1}};
-    return call_finish(c, a->memspace, oa, opt_out_append(bpt, 4, nband, oa, d.idrv ? 4 : 3), d.err);
-  }
-  OutCopy oc[12] = {{a->uflx, d.uflx, nl1}, {a->dflx, d.dflx, nl1}, {a->uflxc, d.uflxc, nl1}, {a->dflxc, d.dflxc, nl1},
-                    {a->hr, d.hr, nl}, {a->hrc, d.hrc, nl}, {a->duflx_dt, d.duflx_dt, nl1}, {a->duflxc_dt, d.duflxc_dt, nl1}};
-  return call_finish(c, a->memspace, oc, opt_out_append(bpt, 4, nband, oc, d.idrv ? 8 : 6), d.err);   // the requested band fluxes behind the same synchronise
+  return call_finish(c, a->memspace, oc, nout, d.err);   // the requested band fluxes behind the same synchronise
 }
 
 // Both spectra of one host state (rrtmg_hip_radiation_fluxes): the argument checks of both before anything is enqueued, then
@@ -506,38 +476,15 @@ int lw_fluxes_f32_impl(rrtmg_ctx *ctx, const rrtmg_lw_args *a, const rrtmg_lw_ba
   if (int rc = call_is_sorted(ctx, 1, a, bp != nullptr) ? ctx_prepare_device(ctx) : call_begin(ctx, 1, a)) return rc;
   if (int rc = lw_refuse_clear_bands(ctx, bp)) return rc;
   const CallSite c{ctx, 1, call_stream(ctx, 1, 1)};
-  const bool clr = ctx->lw_clear_sky, dr = a->idrv != 0;
   BoundaryF32 bf(ctx, c.s, "lw.f32.");
-  rrtmg_lw_args b = *a;
-  const size_t N = (size_t)a->ncol, nl = N * a->nlay, nl1 = N * (a->nlay + 1);
-  const int icld = (a->icld < 0 || a->icld > 3) ? 2 : a->icld;
-  b.play = bf.in("play", a->play, nl); b.plev = bf.in("plev", a->plev, nl1); b.tlay = bf.in("tlay", a->tlay, nl);
-  b.tlev = bf.in("tlev", a->tlev, nl1); b.tsfc = bf.in("tsfc", a->tsfc, N);
-  b.h2ovmr = bf.in("h2o", a->h2ovmr, nl); b.o3vmr = bf.in("o3", a->o3vmr, nl); b.co2vmr = bf.in("co2", a->co2vmr, nl);
-  b.ch4vmr = bf.in("ch4", a->ch4vmr, nl); b.n2ovmr = bf.in("n2o", a->n2ovmr, nl); b.o2vmr = bf.in("o2", a->o2vmr, nl);
-  b.cfc11vmr = bf.in("cfc11", a->cfc11vmr, nl); b.cfc12vmr = bf.in("cfc12", a->cfc12vmr, nl);
-  b.cfc22vmr = bf.in("cfc22", a->cfc22vmr, nl); b.ccl4vmr = bf.in("ccl4", a->ccl4vmr, nl);
-  b.emis = bf.in("emis", a->emis, N * 16);
-  b.cldfr = nullptr; b.taucld = nullptr; b.cicewp = b.cliqwp = b.reice = b.reliq = nullptr; b.cldfmcl = nullptr;
-  if (icld >= 1) {
-    b.cldfr = bf.in("cldfr", a->cldfr, nl); b.taucld = bf.in("taucld", a->taucld, nl * 16);
-    b.cicewp = bf.in("cicewp", a->cicewp, nl); b.cliqwp = bf.in("cliqwp", a->cliqwp, nl);
-    b.reice = bf.in("reice", a->reice, nl); b.reliq = bf.in("reliq", a->reliq, nl);
-    if (a->mcica) b.cldfmcl = bf.in("cldfmcl", a->cldfmcl, nl * kLwNGpt);
-  }
-  b.tauaer = bf.in("tauaer", a->tauaer, nl * 16);
+  LwStructs b(a, bp);
+  const unsigned on = lw_call_reads(a, bp, ctx->lw_clear_sky);
+  const GridShape g = grid_shape(a->ncol, a->nlay, bp ? bp->levels : 0);
+  boundary_inputs(bf, kLwIn, on, b, g);
   // (clear-sky outputs off: whatever the four point to is ignored -- absent from the narrow table, and from the inner call)
-  b.uflx = bf.out("o0", a->uflx, nl1); b.dflx = bf.out("o1", a->dflx, nl1); b.hr = bf.out("o2", a->hr, nl);
-  b.uflxc = clr ? bf.out("o3", a->uflxc, nl1) : nullptr; b.dflxc = clr ? bf.out("o4", a->dflxc, nl1) : nullptr; b.hrc = clr ? bf.out("o5", a->hrc, nl) : nullptr;
-  b.duflx_dt = dr ? bf.out("o6", a->duflx_dt, nl1) : nullptr; b.duflxc_dt = dr && clr ? bf.out("o7", a->duflxc_dt, nl1) : nullptr;
-  rrtmg_lw_band_fluxes bb{};
-  if (bp) {
-    const size_t nband = (size_t)kLwNBand * (bp->levels ? 2 : a->nlay + 1) * N;
-    bb = *bp;
-    bb.up = bf.out("b0", bp->up, nband); bb.dn = bf.out("b1", bp->dn, nband); bb.upc = bf.out("b2", bp->upc, nband); bb.dnc = bf.out("b3", bp->dnc, nband);
-  }
+  boundary_outputs(bf, kLwOut, on, b, g);
   if (!bf.ok) return ctx->status;
-  return boundary_f32_tail(c, bf, [&]() { return lw_fluxes_impl(ctx, &b, bp ? &bb : nullptr); });
+  return boundary_f32_tail(c, bf, [&]() { return lw_fluxes_impl(ctx, &b, bp ? &b : nullptr); });
 }
 
 }  // namespace rrtmg

@@ -70,12 +70,13 @@ RRTMG_PERMUTE_HD int permute_replica(int slot, const PermuteHead &h, int ncol, b
 // aux: gather of [rows][N] arrays -- 1 = `whole`: every slot is filled, 0 = the live slots only;
 //      gather of band-fastest arrays -- the elements per (row, column); scatter: unused
 struct PermuteEntry { const double *in; double *out; int32_t rows, aux; };
-// The scatter's table must hold a call's outputs at once (it cannot run before the inner call): the shortwave's 6 outputs + 8
-// components + 6 band members of 14 entries each = 98 (the longwave's sorted call: 8).  The gathers flush a full table and go
-// on.  104 entries are 2496 bytes; with the launch's other arguments 2536 bytes of kernel arguments, of 4096 at the most.
+// The scatter's table must hold a call's whole output list (it cannot run before the inner call): rrtmg_call.h asserts that
+// the lists of rrtmg_call_arrays.h fit, a band member counting as one entry per band.  The gathers may flush a full table and
+// go on (an input list never fills one at nlay + 1 >= 14).  104 entries are 2496 bytes; with the launch's other arguments 2536
+// bytes of kernel arguments, of 4096 at the most.
 constexpr int kPermuteMaxEntries = 104;
 struct PermuteTable { PermuteEntry e[kPermuteMaxEntries]; };
-constexpr int kPermuteMaxElemEntries = 5;   // shortwave: taucld, ssacld, asmcld, fsfcld, cldfmcl (14, 14, 14, 14, 112 elements); longwave: taucld, cldfmcl (16, 140)
+constexpr int kPermuteMaxElemEntries = 5;   // the band-fastest inputs of a spectrum (a full table is flushed: gather_elem)
 struct PermuteElemTable { PermuteEntry e[kPermuteMaxElemEntries]; };
 static_assert(sizeof(PermuteTable) + 40 <= 4096 && sizeof(PermuteElemTable) + 40 <= 4096, "kernel arguments: 4 KB at the most");
 constexpr int permute_entries(size_t rows, int depth) { return (int)((rows + depth - 1) / depth); }

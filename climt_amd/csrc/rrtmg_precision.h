@@ -47,7 +47,8 @@ RRTMG_PRECISION_HD PrecisionSplit precision_split(uintptr_t addr, size_t n) {
 
 // One table entry: widen src = const float *, dst = double *; narrow src = const double *, dst = float *
 struct PrecisionEntry { const void *src; void *dst; size_t n; double mul, div; };
-// shortwave: 29 inputs at the most, 6 outputs + 8 components + 6 band members
+// one widen table for a call's inputs, one narrow table for its outputs: rrtmg_call.h asserts that the lists of
+// rrtmg_call_arrays.h fit (HostInputs' batch of a host-pointer call may flush a full table and go on)
 constexpr int kPrecisionMaxEntries = 32;
 struct PrecisionTable { PrecisionEntry e[kPrecisionMaxEntries]; };
 static_assert(sizeof(PrecisionTable) + 40 <= 4096, "kernel arguments: 4 KB at the most");

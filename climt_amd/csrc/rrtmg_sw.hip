@@ -32,7 +32,9 @@
 //   With the clear-sky outputs off (rrtmg_hip_set_sw_clear_sky(0)): sw_solve_cloudy_allsky_kernel in the place of
 //   sw_solve_cloudy_kernel and sw_fluxheat_allsky_kernel<night> in the place of sw_fluxheat[_night]_kernel; swuflxc, swdflxc and
 //   swhrc are neither formed nor copied
-// The host steps this call shares with the longwave's (gate, checks, chunk plan and loop, mask choice, epilogue): rrtmg_call.h
+// The host steps this call shares with the longwave's (gate, checks, chunk plan and loop, mask choice, epilogue): rrtmg_call.h;
+// the call's grid arrays -- what the driver, the permuted call and the float32 boundary register, gather and copy: the tables
+// kSwIn / kSwOut of rrtmg_call_arrays.h
 #include "rrtmg_call.h"
 #include "rrtmg_sw_device.h"
 #include "rrtmg_sw_host.h"
@@ -609,65 +611,22 @@ static int sw_permuted_call(rrtmg_ctx *ctx, InnerCall kind, const rrtmg_sw_args 
   if (int rc = packed ? call_begin(ctx, 0, a) : ctx_prepare_device(ctx)) return rc;
   const CallSite c{ctx, 0, call_stream(ctx, 0, 1)};
   // (clear-sky outputs off: the three are absent from the scatter table, and from the inner call)
-  const bool clr = ctx->sw_clear_sky;
-  double *const u[6] = {a->swuflx, a->swdflx, a->swhr, clr ? a->swuflxc : nullptr, clr ? a->swdflxc : nullptr, clr ? a->swhrc : nullptr};
-  if (int rc = check_outputs(ctx, u, clr ? 6 : 3)) return rc;
+  SwStructs b(a, sp, cp, bp);
+  const unsigned on = sw_call_reads(a, sp, cp, bp, ctx->sw_clear_sky);
+  if (int rc = check_outputs(ctx, kSwOut, on, b)) return rc;
   ColumnPermute pm(ctx, c.s, kind, a->ncol, a->nlay, packed ? "sw.pack." : "sw.sort.");
   if (!pm.prepare(packed ? a->coszen : a->cldfr)) return ctx->status;
-  rrtmg_sw_args b = *a;
   b.ncol = pm.Np; b.shard_col0 = 0; b.shard_ncol = 0;
-  const size_t l = (size_t)a->nlay, l1 = l + 1;
-  // (what the driver reads under the call's icld / iaer, normalised as it normalises them; the rest stays nullptr)
-  const int icld = (a->icld < 0 || a->icld > 3) ? 2 : a->icld;
-  b.play = pm.gather("play", a->play, l); b.plev = pm.gather("plev", a->plev, l1); b.tlay = pm.gather("tlay", a->tlay, l);
-  b.tlev = nullptr; b.tsfc = nullptr;   // (the shortwave reads neither)
-  b.h2ovmr = pm.gather("h2o", a->h2ovmr, l); b.o3vmr = pm.gather("o3", a->o3vmr, l); b.co2vmr = pm.gather("co2", a->co2vmr, l);
-  b.ch4vmr = pm.gather("ch4", a->ch4vmr, l); b.n2ovmr = pm.gather("n2o", a->n2ovmr, l); b.o2vmr = pm.gather("o2", a->o2vmr, l);
-  b.asdir = pm.gather("asdir", a->asdir, 1); b.asdif = pm.gather("asdif", a->asdif, 1); b.aldir = pm.gather("aldir", a->aldir, 1);
-  b.aldif = pm.gather("aldif", a->aldif, 1);
-  b.coszen = pm.gather("coszen", a->coszen, 1, true);   // every slot: the night kernels decide from it
-  rrtmg_sw_surface sb{};
-  if (sp) { sb = *sp; sb.albdir = pm.gather("albdir", sp->albdir, kSwNBand); sb.albdif = pm.gather("albdif", sp->albdif, kSwNBand); }
-  b.cldfr = nullptr; b.taucld = b.ssacld = b.asmcld = b.fsfcld = nullptr; b.cicewp = b.cliqwp = b.reice = b.reliq = nullptr; b.cldfmcl = nullptr;
-  if (icld >= 1) {
-    b.cldfr = pm.gather("cldfr", a->cldfr, l);
-    b.cicewp = pm.gather("cicewp", a->cicewp, l); b.cliqwp = pm.gather("cliqwp", a->cliqwp, l);
-    b.reice = pm.gather("reice", a->reice, l); b.reliq = pm.gather("reliq", a->reliq, l);
-    b.taucld = pm.gather_elem("taucld", a->taucld, kSwNBand); b.ssacld = pm.gather_elem("ssacld", a->ssacld, kSwNBand);
-    b.asmcld = pm.gather_elem("asmcld", a->asmcld, kSwNBand); b.fsfcld = pm.gather_elem("fsfcld", a->fsfcld, kSwNBand);
-    if (a->mcica) b.cldfmcl = pm.gather_elem("cldfmcl", a->cldfmcl, kSwNGpt);
-    // exponential overlap: the rank correlations are one more [nlay][N] input of the mask step
-    if (call_overlap_exp(ctx, 0, a) && !a->cldfmcl) ctx->alpha_inner[0] = pm.gather("alpha", ctx->alpha[0].dev, l);
-  }
-  b.tauaer = b.ssaaer = b.asmaer = nullptr; b.ecaer = nullptr;
-  if (a->iaer == 10) {
-    b.tauaer = pm.gather("tauaer", a->tauaer, l * kSwNBand); b.ssaaer = pm.gather("ssaaer", a->ssaaer, l * kSwNBand);
-    b.asmaer = pm.gather("asmaer", a->asmaer, l * kSwNBand);
-  } else if (a->iaer == 6) {
-    b.ecaer = pm.gather("ecaer", a->ecaer, l * 6, true);   // sw_aer_kernel runs over the whole grid
-  }
+  const GridShape g = grid_shape(a->ncol, a->nlay, bp ? bp->levels : 0);
+  permute_inputs(pm, kSwIn, on, b, g);
+  // exponential overlap: the rank correlations are one more [nlay][N] input of the mask step
+  if (call_overlap_exp(ctx, 0, a) && !a->cldfmcl) ctx->alpha_inner[0] = pm.gather("alpha", ctx->alpha[0].dev, g.L);
   if (!pm.ok) { ctx->alpha_inner[0] = nullptr; return ctx->status; }
   pm.flush_gather();
-  // the inner call's outputs, registered for the scatter in the order plain, components, bands
-  b.swuflx = pm.out("o0", u[0], l1); b.swdflx = pm.out("o1", u[1], l1); b.swhr = pm.out("o2", u[2], l);
-  b.swuflxc = pm.out("o3", u[3], l1); b.swdflxc = pm.out("o4", u[4], l1); b.swhrc = pm.out("o5", u[5], l);
-  rrtmg_sw_components cb{};
-  if (cp) {
-    cb = *cp;
-    cb.dirdflx = pm.out("c0", cp->dirdflx, l1); cb.difdflx = pm.out("c1", cp->difdflx, l1); cb.dirdnuv = pm.out("c2", cp->dirdnuv, l1);
-    cb.difdnuv = pm.out("c3", cp->difdnuv, l1); cb.dirdnir = pm.out("c4", cp->dirdnir, l1); cb.difdnir = pm.out("c5", cp->difdnir, l1);
-    cb.dirdflxc = pm.out("c6", cp->dirdflxc, l1); cb.difdflxc = pm.out("c7", cp->difdflxc, l1);
-  }
-  rrtmg_sw_band_fluxes bb{};
-  if (bp) {
-    const size_t rows = (size_t)kSwNBand * (bp->levels ? 2 : l1);
-    bb = *bp;
-    bb.up = pm.out("b0", bp->up, rows); bb.dn = pm.out("b1", bp->dn, rows); bb.upc = pm.out("b2", bp->upc, rows);
-    bb.dnc = pm.out("b3", bp->dnc, rows); bb.dndir = pm.out("b4", bp->dndir, rows); bb.dndirc = pm.out("b5", bp->dndirc, rows);
-  }
+  permute_outputs(pm, kSwOut, on, b, g);   // registered for the scatter in the order plain, components, bands
   if (!pm.ok) { ctx->alpha_inner[0] = nullptr; return ctx->status; }
   return permuted_tail(c, pm, [&]() {
-    const int rc = sw_fluxes_impl(ctx, &b, sp ? &sb : nullptr, cp ? &cb : nullptr, bp ? &bb : nullptr);
+    const int rc = sw_fluxes_impl(ctx, &b, sp ? &b : nullptr, cp ? &b : nullptr, bp ? &b : nullptr);
     if (!rc && packed) ctx->sw_pack_reported = true;
     return rc;
   }, packed ? (int32_t *)ctx->night_host() : nullptr);
@@ -683,9 +642,10 @@ int sw_fluxes_impl(rrtmg_ctx *ctx, const rrtmg_sw_args *a, const rrtmg_sw_surfac
   if (rc) return rc;
   const CallSite c{ctx, 0, call_stream(ctx, 0, a->memspace)}; hipStream_t s = c.s;
   const int N = a->ncol, L = a->nlay;
-  const size_t nl = (size_t)N * L, nl1 = (size_t)N * (L + 1);
+  const size_t nl = (size_t)N * L;
   const SwTab &T = *(SwTab *)ctx->sw_desc;
-  SwDev d{};
+  SwBound bound{};   // the kernels' struct and what else the array tables bind (rrtmg_call_arrays.h)
+  SwDev &d = bound;
   d.ncol = N; d.nlay = L;
   d.iaer = a->iaer;
   const double *alpha = nullptr;
@@ -710,43 +670,20 @@ int sw_fluxes_impl(rrtmg_ctx *ctx, const rrtmg_sw_args *a, const rrtmg_sw_surfac
   bool ok = true;
   const double ps = a->pressure_scale, ws = a->water_path_scale;
   HostInputs hi(ctx, s, "sw.in.", a->memspace, call_share(ctx), 0, ctx->f32);
-  hi.add(&d.play, a->play, nl, "play", true, InPolicy::Plain, ps); hi.add(&d.plev, a->plev, nl1, "plev", true, InPolicy::Plain, ps);
-  hi.add(&d.tlay, a->tlay, nl, "tlay", true);
-  hi.add(&d.h2o, a->h2ovmr, nl, "h2o", true, InPolicy::Plain, a->h2o_mul, a->h2o_div); hi.add(&d.o3, a->o3vmr, nl, "o3", true);
-  hi.add(&d.co2, a->co2vmr, nl, "co2", true); hi.add(&d.ch4, a->ch4vmr, nl, "ch4", true); hi.add(&d.n2o, a->n2ovmr, nl, "n2o", true);
-  hi.add(&d.o2, a->o2vmr, nl, "o2", true);
-  // (a broadband pair is read only where its per-band array is not given)
-  const bool bdir = sp && sp->albdir, bdif = sp && sp->albdif;
-  if (!bdir) { hi.add(&d.asdir, a->asdir, N, "asdir", true); hi.add(&d.aldir, a->aldir, N, "aldir", true); }
-  if (!bdif) { hi.add(&d.asdif, a->asdif, N, "asdif", true); hi.add(&d.aldif, a->aldif, N, "aldif", true); }
-  if (bdir) hi.add(&d.albdir, sp->albdir, (size_t)kSwNBand * N, "albdir", true);
-  if (bdif) hi.add(&d.albdif, sp->albdif, (size_t)kSwNBand * N, "albdif", true);
-  hi.add(&d.coszen, a->coszen, N, "coszen", true);
-  const bool clouds = d.icld >= 1;
-  if (clouds) {
-    hi.add(&d.cldfr, a->cldfr, nl, "cldfr", true);
-    const bool optics = (d.inflag == 0);
-    // single-scattering albedo / asymmetry / forward fraction are read only where the optics are given directly -- under
-    // inflag 2 they would multiply an optical depth below cldmin = 1e-20 at most -- so host copies are not uploaded then
-    const bool up = optics || a->memspace == 1;
-    if (up) {
-      hi.add(&d.ssacld, a->ssacld, nl * kSwNBand, "ssacld", optics); hi.add(&d.asmcld, a->asmcld, nl * kSwNBand, "asmcld", optics);
-      hi.add(&d.fsfcld, a->fsfcld, nl * kSwNBand, "fsfcld", optics);
-    }
-    hi.add(&d.cicewp, a->cicewp, nl, "cicewp", d.inflag == 2, InPolicy::Plain, ws); hi.add(&d.cliqwp, a->cliqwp, nl, "cliqwp", d.inflag == 2, InPolicy::Plain, ws);
-    hi.add(&d.reice, a->reice, nl, "reice", d.inflag == 2); hi.add(&d.reliq, a->reliq, nl, "reliq", d.inflag == 2);
-    // (stays live under inflag 2: the tauctot gate of cldprop_sw; given directly -- inflag 0 -- it is used as it is)
-    hi.add(&d.taucld, a->taucld, nl * kSwNBand, "taucld", optics, optics ? InPolicy::Plain : InPolicy::ZeroAbsent);
-  }
-  const double *ecaer = nullptr;
-  if (d.iaer == 10) {
-    hi.add(&d.tauaer, a->tauaer, nl * kSwNBand, "tauaer", true); hi.add(&d.ssaaer, a->ssaaer, nl * kSwNBand, "ssaaer", true);
-    hi.add(&d.asmaer, a->asmaer, nl * kSwNBand, "asmaer", true);
-  } else if (d.iaer == 6) {
-    hi.add(&ecaer, a->ecaer, nl * 6, "ecaer", true);
-  }
-  const double *cldfmcl_dev = nullptr;
-  if (clouds && d.mcica && a->cldfmcl) hi.add(&cldfmcl_dev, a->cldfmcl, nl * kSwNGpt, "cldfmcl", true);
+  const SwStructs x(a, sp, cp, bp);
+  const unsigned on = sw_call_reads(a, sp, cp, bp, clr);
+  const GridShape g = grid_shape(N, L, bp ? bp->levels : 0);
+  const bool clouds = on & kClouds, optics = d.inflag == 0, given = d.inflag == 2;
+  // single-scattering albedo / asymmetry / forward fraction are read only where the optics are given directly -- under
+  // inflag 2 they would multiply an optical depth below cldmin = 1e-20 at most -- so host copies are not uploaded then.
+  // taucld stays live under inflag 2 (the tauctot gate of cldprop_sw); given directly -- inflag 0 -- it is used as it is.
+  const InRule direct{optics, InPolicy::Plain, 0.0, 0.0, !(optics || a->memspace == 1)};
+  const InRuleFor<SwBound> rules[] = {
+      {&SwDev::play, {true, InPolicy::Plain, ps}}, {&SwDev::plev, {true, InPolicy::Plain, ps}}, {&SwDev::h2o, {true, InPolicy::Plain, a->h2o_mul, a->h2o_div}},
+      {&SwDev::ssacld, direct}, {&SwDev::asmcld, direct}, {&SwDev::fsfcld, direct},
+      {&SwDev::cicewp, {given, InPolicy::Plain, ws}}, {&SwDev::cliqwp, {given, InPolicy::Plain, ws}}, {&SwDev::reice, {given}}, {&SwDev::reliq, {given}},
+      {&SwDev::taucld, {optics, optics ? InPolicy::Plain : InPolicy::ZeroAbsent}}, {&CallLocals::cldfmcl, {false}}};   // (the sub-columns: where given)
+  register_inputs(hi, kSwIn, on, x, bound, g, rules);
   if (!hi.finish()) return ctx->status;
 
   // ---- work buffers -------------------------------------------------------------------------
@@ -783,19 +720,6 @@ int sw_fluxes_impl(rrtmg_ctx *ctx, const rrtmg_sw_args *a, const rrtmg_sw_surfac
   d.part = wd("part", (size_t)kSwNSlot * 4 * (L + 1) * ctile * 64);
   // components: the direct-beam partial planes [slot][2][nlay+1][pcols] (SwPartDirSink) and the outputs
   double *partdir = need_dir ? wd("partdir", (size_t)kSwNSlot * 2 * (L + 1) * ctile * 64) : nullptr;
-  static const rrtmg_sw_components no_comp{}; static const rrtmg_sw_band_fluxes no_band{};   // (nothing requested: every member nullptr)
-  const rrtmg_sw_components &cr = cp ? *cp : no_comp; const rrtmg_sw_band_fluxes &br = bp ? *bp : no_band;
-  SwCompOut co{};
-  const OptOut cpt[8] = {{"o.dirdflx", cr.dirdflx, &co.dirdflx}, {"o.difdflx", cr.difdflx, &co.difdflx}, {"o.dirdnuv", cr.dirdnuv, &co.dirdnuv},
-                         {"o.difdnuv", cr.difdnuv, &co.difdnuv}, {"o.dirdnir", cr.dirdnir, &co.dirdnir}, {"o.difdnir", cr.difdnir, &co.difdnir},
-                         {"o.dirdflxc", cr.dirdflxc, &co.dirdflxc}, {"o.difdflxc", cr.difdflxc, &co.difdflxc}};
-  opt_out_bind(cpt, 8, a->memspace, nl1, wd);
-  // band fluxes: [14][nrow][ncol] per requested member
-  SwBandOut bo{};
-  const OptOut bpt[6] = {{"ob.up", br.up, &bo.up}, {"ob.dn", br.dn, &bo.dn}, {"ob.upc", br.upc, &bo.upc}, {"ob.dnc", br.dnc, &bo.dnc},
-                         {"ob.dndir", br.dndir, &bo.dndir}, {"ob.dndirc", br.dndirc, &bo.dndirc}};
-  const size_t nband = (size_t)kSwNBand * (br.levels ? 2 : L + 1) * N;
-  opt_out_bind(bpt, 6, a->memspace, nband, wd);
   if (!svar_col.empty()) {   // per-column solar-variability multipliers (rare: facular/sunspot amplitudes != 1)
     double *p = wd("svarcol", svar_col.size());
     if (!ok) return ctx->status;
@@ -803,17 +727,13 @@ int sw_fluxes_impl(rrtmg_ctx *ctx, const rrtmg_sw_args *a, const rrtmg_sw_surfac
     RRTMG_HIP_CHECK(ctx, hipStreamSynchronize(s));   // svar_col is a local
     d.svar_col = p;
   }
+  // the outputs: the standard ones, the components [nlay+1][ncol], the band fluxes [14][nrow][ncol], each where requested
   // (clear-sky outputs off: d.swuflxc, d.swdflxc and d.swhrc stay nullptr -- no kernel of that path dereferences them)
-  if (a->memspace == 1) {
-    d.swuflx = a->swuflx; d.swdflx = a->swdflx; d.swhr = a->swhr;
-    if (clr) { d.swuflxc = a->swuflxc; d.swdflxc = a->swdflxc; d.swhrc = a->swhrc; }
-  } else {
-    d.swuflx = wd("o.uflx", nl1); d.swdflx = wd("o.dflx", nl1); d.swhr = wd("o.hr", nl);
-    if (clr) { d.swuflxc = wd("o.uflxc", nl1); d.swdflxc = wd("o.dflxc", nl1); d.swhrc = wd("o.hrc", nl); }
-  }
+  OutCopy oc[table_size(kSwOut)];
+  const int nout = bind_outputs(kSwOut, on, x, bound, g, a->memspace, wd, oc);
+  const SwCompOut &co = bound; const SwBandOut &bo = bound;
   if (!ok) return ctx->status;
-  double *const u[6] = {a->swuflx, a->swdflx, a->swhr, a->swuflxc, a->swdflxc, a->swhrc};
-  if ((rc = check_outputs(ctx, u, clr ? 6 : 3)) || (rc = call_own_flag(c, a->memspace, d))) return rc;
+  if ((rc = check_outputs(ctx, kSwOut, on, x)) || (rc = call_own_flag(c, a->memspace, d))) return rc;
 
   // ---- launches ---------------------------------------------------------------------------
   const dim3 gcl(ntile, L), blk(64);
@@ -821,10 +741,10 @@ int sw_fluxes_impl(rrtmg_ctx *ctx, const rrtmg_sw_args *a, const rrtmg_sw_surfac
   if (d.iaer == 6) {
     double *ta = wd("aer.tau", nl * kSwNBand), *om = wd("aer.ssa", nl * kSwNBand), *as = wd("aer.asm", nl * kSwNBand);
     if (!ok) return ctx->status;
-    hipLaunchKernelGGL(sw_aer_kernel, gcl, blk, 0, s, d, T, ecaer, ta, om, as);
+    hipLaunchKernelGGL(sw_aer_kernel, gcl, blk, 0, s, d, T, bound.ecaer, ta, om, as);
     d.tauaer = ta; d.ssaaer = om; d.asmaer = as;
   }
-  if (clouds && d.mcica && (rc = mcica_mask_launch(c, kSwNGpt, d, a, cldfmcl_dev, night ? sw_kiss_mask_night_kernel : nullptr, d.coszen, alpha, sw_kiss_mask_exp_night_kernel))) return rc;
+  if (clouds && d.mcica && (rc = mcica_mask_launch(c, kSwNGpt, d, a, bound.cldfmcl, night ? sw_kiss_mask_night_kernel : nullptr, d.coszen, alpha, sw_kiss_mask_exp_night_kernel))) return rc;
   // preparation, solve and spectral integration, one column chunk at a time: the chunk's prep rows (58 MB at 8192 columns x
   // 60 layers) are read by its 32 work items while still in the L2s / the Infinity Cache, not streamed back from HBM after
   // the preparation of the whole grid (every solve launch of every chunk has its own event pair)
@@ -874,19 +794,12 @@ int sw_fluxes_impl(rrtmg_ctx *ctx, const rrtmg_sw_args *a, const rrtmg_sw_surfac
   if (ctx->inner != kInnerNone) { RRTMG_HIP_CHECK(ctx, hipGetLastError()); return RRTMG_OK; }
 
   // ---- status + outputs -------------------------------------------------------------------
-  OutCopy oc[20] = {{a->swuflx, d.swuflx, nl1}, {a->swdflx, d.swdflx, nl1}, {a->swuflxc, d.swuflxc, nl1}, {a->swdflxc, d.swdflxc, nl1},
-                    {a->swhr, d.swhr, nl}, {a->swhrc, d.swhrc, nl}};
-  if (!clr) {   // three downloads, not six (neither components nor bands: refused above)
-    const OutCopy oa[3] = {{a->swuflx, d.swuflx, nl1}, {a->swdflx, d.swdflx, nl1}, {a->swhr, d.swhr, nl}};
-    return call_finish(c, a->memspace, oa, 3, d.err);
-  }
-  const int nout = opt_out_append(bpt, 6, nband, oc, opt_out_append(cpt, 8, nl1, oc, 6));   // components, then bands: behind the same synchronise
   return call_finish(c, a->memspace, oc, nout, d.err);
 }
 
 // rrtmg_hip_sw_fluxes_f32 (rrtmg_precision.h): every grid array of the structs points to float.  Host pointers: the ordinary
 // driver with ctx->f32 set -- HostInputs widens behind the upload, copy_out narrows in front of the download.  Device pointers:
-// ONE widen launch for what the driver reads under the call's icld / iaer (the list of sw_permuted_call), the ordinary
+// ONE widen launch for what the driver reads under the call's icld / iaer (kSwIn under sw_call_reads), the ordinary
 // device-resident call on the fp64 copies, ONE narrow launch for every requested output.  The checks in front are the driver's
 // own, in its order, so that nothing is sized from arguments it would refuse.
 int sw_fluxes_f32_impl(rrtmg_ctx *ctx, const rrtmg_sw_args *a, const rrtmg_sw_surface *sp, const rrtmg_sw_components *cp, const rrtmg_sw_band_fluxes *bp) {
@@ -903,56 +816,14 @@ int sw_fluxes_f32_impl(rrtmg_ctx *ctx, const rrtmg_sw_args *a, const rrtmg_sw_su
   if (int rc = sorted ? ctx_prepare_device(ctx) : call_begin(ctx, 0, a)) return rc;
   const CallSite c{ctx, 0, call_stream(ctx, 0, 1)};
   BoundaryF32 bf(ctx, c.s, "sw.f32.");
-  rrtmg_sw_args b = *a;
-  const size_t N = (size_t)a->ncol, nl = N * a->nlay, nl1 = N * (a->nlay + 1);
-  const int icld = (a->icld < 0 || a->icld > 3) ? 2 : a->icld;
-  b.play = bf.in("play", a->play, nl); b.plev = bf.in("plev", a->plev, nl1); b.tlay = bf.in("tlay", a->tlay, nl);
-  b.tlev = nullptr; b.tsfc = nullptr;   // (the shortwave reads neither)
-  b.h2ovmr = bf.in("h2o", a->h2ovmr, nl); b.o3vmr = bf.in("o3", a->o3vmr, nl); b.co2vmr = bf.in("co2", a->co2vmr, nl);
-  b.ch4vmr = bf.in("ch4", a->ch4vmr, nl); b.n2ovmr = bf.in("n2o", a->n2ovmr, nl); b.o2vmr = bf.in("o2", a->o2vmr, nl);
-  // (a broadband pair is read only where its per-band array is not given)
-  const bool bdir = sp && sp->albdir, bdif = sp && sp->albdif;
-  b.asdir = bdir ? nullptr : bf.in("asdir", a->asdir, N); b.aldir = bdir ? nullptr : bf.in("aldir", a->aldir, N);
-  b.asdif = bdif ? nullptr : bf.in("asdif", a->asdif, N); b.aldif = bdif ? nullptr : bf.in("aldif", a->aldif, N);
-  b.coszen = bf.in("coszen", a->coszen, N);
-  rrtmg_sw_surface sb{};
-  if (sp) { sb = *sp; sb.albdir = bf.in("albdir", sp->albdir, (size_t)kSwNBand * N); sb.albdif = bf.in("albdif", sp->albdif, (size_t)kSwNBand * N); }
-  b.cldfr = nullptr; b.taucld = b.ssacld = b.asmcld = b.fsfcld = nullptr; b.cicewp = b.cliqwp = b.reice = b.reliq = nullptr; b.cldfmcl = nullptr;
-  if (icld >= 1) {
-    b.cldfr = bf.in("cldfr", a->cldfr, nl);
-    b.cicewp = bf.in("cicewp", a->cicewp, nl); b.cliqwp = bf.in("cliqwp", a->cliqwp, nl);
-    b.reice = bf.in("reice", a->reice, nl); b.reliq = bf.in("reliq", a->reliq, nl);
-    b.taucld = bf.in("taucld", a->taucld, nl * kSwNBand); b.ssacld = bf.in("ssacld", a->ssacld, nl * kSwNBand);
-    b.asmcld = bf.in("asmcld", a->asmcld, nl * kSwNBand); b.fsfcld = bf.in("fsfcld", a->fsfcld, nl * kSwNBand);
-    if (a->mcica) b.cldfmcl = bf.in("cldfmcl", a->cldfmcl, nl * kSwNGpt);
-  }
-  b.tauaer = b.ssaaer = b.asmaer = nullptr; b.ecaer = nullptr;
-  if (a->iaer == 10) {
-    b.tauaer = bf.in("tauaer", a->tauaer, nl * kSwNBand); b.ssaaer = bf.in("ssaaer", a->ssaaer, nl * kSwNBand);
-    b.asmaer = bf.in("asmaer", a->asmaer, nl * kSwNBand);
-  } else if (a->iaer == 6) {
-    b.ecaer = bf.in("ecaer", a->ecaer, nl * 6);
-  }
+  SwStructs b(a, sp, cp, bp);
+  const unsigned on = sw_call_reads(a, sp, cp, bp, clr);
+  const GridShape g = grid_shape(a->ncol, a->nlay, bp ? bp->levels : 0);
+  boundary_inputs(bf, kSwIn, on, b, g);
   // (clear-sky outputs off: whatever the three point to is ignored -- absent from the narrow table, and from the inner call)
-  b.swuflx = bf.out("o0", a->swuflx, nl1); b.swdflx = bf.out("o1", a->swdflx, nl1); b.swhr = bf.out("o2", a->swhr, nl);
-  b.swuflxc = clr ? bf.out("o3", a->swuflxc, nl1) : nullptr; b.swdflxc = clr ? bf.out("o4", a->swdflxc, nl1) : nullptr;
-  b.swhrc = clr ? bf.out("o5", a->swhrc, nl) : nullptr;
-  rrtmg_sw_components cb{};
-  if (cp) {
-    cb = *cp;
-    cb.dirdflx = bf.out("c0", cp->dirdflx, nl1); cb.difdflx = bf.out("c1", cp->difdflx, nl1); cb.dirdnuv = bf.out("c2", cp->dirdnuv, nl1);
-    cb.difdnuv = bf.out("c3", cp->difdnuv, nl1); cb.dirdnir = bf.out("c4", cp->dirdnir, nl1); cb.difdnir = bf.out("c5", cp->difdnir, nl1);
-    cb.dirdflxc = bf.out("c6", cp->dirdflxc, nl1); cb.difdflxc = bf.out("c7", cp->difdflxc, nl1);
-  }
-  rrtmg_sw_band_fluxes bb{};
-  if (bp) {
-    const size_t nband = (size_t)kSwNBand * (bp->levels ? 2 : a->nlay + 1) * N;
-    bb = *bp;
-    bb.up = bf.out("b0", bp->up, nband); bb.dn = bf.out("b1", bp->dn, nband); bb.upc = bf.out("b2", bp->upc, nband);
-    bb.dnc = bf.out("b3", bp->dnc, nband); bb.dndir = bf.out("b4", bp->dndir, nband); bb.dndirc = bf.out("b5", bp->dndirc, nband);
-  }
+  boundary_outputs(bf, kSwOut, on, b, g);
   if (!bf.ok) return ctx->status;
-  return boundary_f32_tail(c, bf, [&]() { return sw_fluxes_impl(ctx, &b, sp ? &sb : nullptr, cp ? &cb : nullptr, bp ? &bb : nullptr); });
+  return boundary_f32_tail(c, bf, [&]() { return sw_fluxes_impl(ctx, &b, sp ? &b : nullptr, cp ? &b : nullptr, bp ? &b : nullptr); });
 }
 
 }  // namespace rrtmg
