@@ -162,6 +162,14 @@ class SlabArgs(C.Structure):
                                    "heat_cap_soil surf_therm_cap ocean_mix_thick soil_layer_thick ocean_heat_transport tend_ts depth").split()]
 
 
+class ScaleEntry(C.Structure):
+    """mirrors `rrtmg_scale_entry` (include/rrtmg_hip.h), field for field"""
+    _fields_ = [("src", _vp), ("dst", _vp), ("rows", _i32), ("reserved", _i32)]
+
+
+SCALE_MAX_ENTRIES = 16      # RRTMG_SCALE_MAX_ENTRIES: the arrays of one rrtmg_hip_scale_columns call
+
+
 _lib = None
 
 
@@ -227,6 +235,10 @@ def load_library():
     if hasattr(lib, "rrtmg_hip_set_mcica_overlap_alpha"):   # (likewise: exponential / exponential-random McICA overlap)
         lib.rrtmg_hip_set_mcica_overlap_alpha.argtypes = [_vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp]
         lib.rrtmg_hip_overlap_alpha.argtypes = [_vp, C.c_int, C.c_int, C.c_int, _vp, _vp, _f64, _f64, _vp]
+    if hasattr(lib, "rrtmg_hip_mean_coszen"):               # (likewise: the shortwave between radiation calls)
+        lib.rrtmg_hip_mean_coszen.argtypes = [_vp, C.c_int, C.c_int, _vp, _vp, _f64, _f64, _vp, _vp, _vp, _vp]
+        lib.rrtmg_hip_mean_coszen_sun.argtypes = [_vp, C.c_int, C.c_int, _vp, _vp, _f64, _f64, _f64, _f64, _vp, _vp, _vp, _vp]
+        lib.rrtmg_hip_scale_columns.argtypes = [_vp, C.c_int, _vp, _vp, C.c_int, C.POINTER(ScaleEntry)]
     lib.rrtmg_hip_copy_blocks.argtypes = [_vp, C.c_int, _vp, C.c_long, C.c_long, _vp, _vp, _vp]
     lib.rrtmg_hip_mcica_mask.argtypes = [_vp] + [C.c_int] * 6 + [_vp] * 3
     _lib = lib
@@ -413,6 +425,68 @@ class Context:
         z = np.empty(lat.shape) if out is None else out
         self._ck(self.lib.rrtmg_hip_zenith_angle(self.h, lat.size, 0, lat.ctypes.data, lon.ctypes.data, float(julian_centuries), z.ctypes.data))
         return z
+
+    @property
+    def has_intermittent(self):
+        """Whether the library exports the shortwave between radiation calls (rrtmg_hip_mean_coszen, rrtmg_hip_mean_coszen_sun,
+        rrtmg_hip_scale_columns; probed by the symbols)."""
+        return all(hasattr(self.lib, n) for n in ("rrtmg_hip_mean_coszen", "rrtmg_hip_mean_coszen_sun", "rrtmg_hip_scale_columns"))
+
+    def _intermittent_entry(self, name):
+        if not self.has_intermittent:
+            raise RRTMGError(4, "this librrtmg_hip.so has no %s (shortwave between radiation calls)" % name)
+        return getattr(self.lib, name)
+
+    @_locked
+    def mean_coszen(self, lat_deg, lon_deg, t0_centuries, t1_centuries, out_mean=None, out_fraction=None, memspace=0, ncol=None,
+                    out_zenith=None, out_insolation=None, sun=None):
+        """Cosine of the zenith angle averaged over the sunlit part of [t0, t1] (Julian centuries, 12 hours at the most) and
+        the sunlit fraction of the interval, of every column (rrtmg_hip_mean_coszen) -> (mean, fraction).  Host arrays, or
+        device pointers with memspace=1 (then `out_mean`, `out_fraction`, `ncol`).  `out_zenith`, `out_insolation`: filled as
+        well where given -- acos(mean), pi/2 where the mean is 0, and mean * fraction.  `sun`: (sin_dec, cos_dec, hour angle of
+        Greenwich at t0, its advance in (0, 2 pi)) in place of the two times (rrtmg_hip_mean_coszen_sun)."""
+        if sun is None:
+            entry, head = self._intermittent_entry("rrtmg_hip_mean_coszen"), (float(t0_centuries), float(t1_centuries))
+        else:
+            entry, head = self._intermittent_entry("rrtmg_hip_mean_coszen_sun"), tuple(float(v) for v in sun)
+            if len(head) != 4:
+                raise ValueError("sun: (sin_dec, cos_dec, hour_angle0, hour_angle_advance)")
+        if memspace:
+            opt = [None if p is None else int(p) for p in (out_zenith, out_insolation)]
+            self._ck(entry(self.h, int(ncol), 1, int(lat_deg), int(lon_deg), *head, int(out_mean), int(out_fraction), *opt))
+            return out_mean, out_fraction
+        lat = np.ascontiguousarray(lat_deg, dtype=np.float64)
+        lon = np.ascontiguousarray(lon_deg, dtype=np.float64)
+        if lat.shape != lon.shape:
+            raise ValueError("latitude and longitude must have one shape")
+        mean = np.empty(lat.shape) if out_mean is None else out_mean
+        frac = np.empty(lat.shape) if out_fraction is None else out_fraction
+        for o in (mean, frac, out_zenith, out_insolation):
+            if o is not None and not (isinstance(o, np.ndarray) and o.dtype == np.float64 and o.flags.c_contiguous and o.size == lat.size):
+                raise ValueError("mean_coszen: an output is written in place: a C-contiguous float64 array of %d elements" % lat.size)
+        opt = [None if o is None else o.ctypes.data for o in (out_zenith, out_insolation)]
+        self._ck(entry(self.h, lat.size, 0, lat.ctypes.data, lon.ctypes.data, *head, mean.ctypes.data, frac.ctypes.data, *opt))
+        return mean, frac
+
+    @_locked
+    def scale_columns(self, num, den, entries, ncol=None):
+        """dst[r][c] = src[r][c] * s[c], s[c] = den[c] > 0 ? num[c] / den[c] : +0.0, for every (src, dst, rows) of `entries` --
+        [rows][ncol] arrays, dst may be src -- in one launch per 16 entries (rrtmg_hip_scale_columns).  Device pointers (or
+        DeviceArrays) throughout, on the context's main stream; `ncol` is needed where num is a raw pointer."""
+        entry = self._intermittent_entry("rrtmg_hip_scale_columns")
+        f64 = PRECISIONS["float64"]
+        if ncol is None:
+            ncol = int(np.prod(num.shape))
+        entries = list(entries)
+        if not entries:
+            raise ValueError("scale_columns: no entries")
+        n, d = _device_pointer(num, f64, "num"), _device_pointer(den, f64, "den")
+        for i in range(0, len(entries), SCALE_MAX_ENTRIES):
+            part = entries[i:i + SCALE_MAX_ENTRIES]
+            table = (ScaleEntry * len(part))()
+            for e, (src, dst, rows) in zip(table, part):
+                e.src, e.dst, e.rows = _device_pointer(src, f64, "src"), _device_pointer(dst, f64, "dst"), int(rows)
+            self._ck(entry(self.h, int(ncol), n, d, len(part), table))
 
     @_locked
     def solar_insolation(self, lat, lon, sin_delta, cos_delta, fractional_day, irradiance):

@@ -12,35 +12,9 @@
 #include <cmath>
 
 #include "rrtmg_ctx.h"
+#include "rrtmg_intermittent.h"   // SunPos, sun_position: shared with the interval mean (rrtmg_hip_mean_coszen)
 
 namespace rrtmg {
-
-struct SunPos { double sin_dec, cos_dec, ra, gmst; };
-
-static double deg2rad(double x) { return x * (M_PI / 180.0); }
-
-static SunPos sun_position(double t) {
-  const double eps = deg2rad(23.0 + 26.0 / 60 + 21.406 / 3600.0 -
-                             (46.836769 * t - 0.0001831 * (t * t) + 0.00200340 * (t * t * t) - 0.576e-6 * (t * t * t * t) -
-                              4.34e-8 * (t * t * t * t * t)) / 3600.0);
-  const double mean_anomaly = deg2rad(357.52910 + 35999.05030 * t - 0.0001559 * t * t - 0.00000048 * t * t * t);
-  const double mean_longitude = deg2rad(280.46645 + 36000.76983 * t + 0.0003032 * (t * t));
-  const double d_l = deg2rad((1.914600 - 0.004817 * t - 0.000014 * (t * t)) * sin(mean_anomaly) +
-                             (0.019993 - 0.000101 * t) * sin(2 * mean_anomaly) + 0.000290 * sin(3 * mean_anomaly));
-  const double eclon = mean_longitude + d_l;
-  const double x = cos(eclon), y = cos(eps) * sin(eclon), z = sin(eps) * sin(eclon);
-  const double r = sqrt(1.0 - z * z);
-  const double declination = atan2(z, r);
-  SunPos s;
-  s.sin_dec = sin(declination); s.cos_dec = cos(declination);
-  s.ra = 2.0 * atan2(y, (x + r));
-  // "6.2 * 10e-6" is the reference's literal (component.py:186)
-  const double theta = 67310.54841 + t * (876600.0 * 3600 + 8640184.812866 + t * (0.093104 - t * 6.2 * 10e-6));
-  double g = fmod(deg2rad(theta / 240.0), 2.0 * M_PI);
-  if (g < 0) g += 2.0 * M_PI;   // numpy's % is non-negative for a positive modulus
-  s.gmst = g;
-  return s;
-}
 
 __global__ void __launch_bounds__(256) zenith_kernel(int n, const double *lat_deg, const double *lon_deg, SunPos s, double *zenith) {
   const int i = blockIdx.x * 256 + threadIdx.x;

@@ -250,8 +250,10 @@ def _device_overlap(self, ds, which, inp):
     ds.ctx.set_mcica_overlap_alpha(which, alpha.ptr, memspace=1, ncol=ncol, nlay=nlay)
 
 
-def shortwave_device_call(self, ds):
-    """RRTMGShortwave on a DeviceState: the body of array_call (sw/component.py:472-668) with device pointers."""
+def shortwave_device_call(self, ds, output_work=None):
+    """RRTMGShortwave on a DeviceState: the body of array_call (sw/component.py:472-668) with device pointers.
+    `output_work(key, shape, dims, units)`: the caller's own buffers for the outputs (climt_amd.IntermittentShortwave keeps a
+    call's results across model steps); default: two alternating sets of the state's."""
     ds.init_tables("sw", self._Cpd)
     P = self.input_properties
     g = lambda n: ds.need(n, P[n]).ptr
@@ -288,7 +290,7 @@ def shortwave_device_call(self, ds):
         inp.update(irng=self._random_number_generator, permuteseed=self._permute_seed)
     il, ml = (nlay + 1, ncol), (nlay, ncol)
     self._device_calls = getattr(self, "_device_calls", 0) + 1          # outputs alternate between two buffer sets: the
-    w = lambda key, shape, dims, units: ds.work(("sw", id(self), key, self._device_calls & 1), shape, dims, units)   # state may still hold the last ones
+    w = output_work or (lambda key, shape, dims, units: ds.work(("sw", id(self), key, self._device_calls & 1), shape, dims, units))   # state may still hold the last ones
     clear = getattr(self, "_clear_sky", True)      # False: no buffers for the three clear-sky outputs, which the library then leaves out
     fl = {k: w(k, il, ("interface_levels", "*"), "W m^-2") for k in (("swuflx", "swdflx", "swuflxc", "swdflxc") if clear else ("swuflx", "swdflx"))}
     hr = w("swhr", ml, ("mid_levels", "*"), "degK day^-1")
@@ -400,6 +402,23 @@ def instellation_device_call(self, ds):
     zen = ds.work(("sun", id(self), self._device_calls & 1), (ds.ncol,), ("*",), "radians")
     ds.ctx.zenith_angle(lat.ptr, lon.ptr, days_from_2000(ds["time"]) / 36525.0, out=zen.ptr, memspace=1, ncol=ds.ncol)
     return {"zenith_angle": zen}
+
+
+def instellation_interval_device_call(self, ds, timedelta, work=None):
+    """Instellation.interval_mean on a DeviceState (rrtmg_hip_mean_coszen with device pointers, on the main stream) ->
+    zenith_angle, sunlit_fraction and, for climt_amd.IntermittentShortwave, coszen_mean and insolation (mean * fraction).
+    `work(key, shape, dims, units)`: where the four outputs live; default: two alternating sets of the state's own."""
+    from .instellation import interval_centuries
+    lat, lon = ds.need("latitude", self.input_properties["latitude"]), ds.need("longitude", self.input_properties["longitude"])
+    if work is None:
+        self._interval_calls = getattr(self, "_interval_calls", 0) + 1
+        work = lambda key, shape, dims, units: ds.work(("sun.interval", id(self), key, self._interval_calls & 1), shape, dims, units)
+    out = {k: work(k, (ds.ncol,), ("*",), u) for k, u in (("zenith_angle", "radians"), ("sunlit_fraction", "dimensionless"),
+                                                         ("coszen_mean", "dimensionless"), ("insolation", "dimensionless"))}
+    ds.ctx.mean_coszen(lat.ptr, lon.ptr, *interval_centuries(ds["time"], timedelta), out_mean=out["coszen_mean"].ptr,
+                       out_fraction=out["sunlit_fraction"].ptr, memspace=1, ncol=ds.ncol, out_zenith=out["zenith_angle"].ptr,
+                       out_insolation=out["insolation"].ptr)
+    return out
 
 
 def slab_device_call(self, ds):

@@ -328,7 +328,7 @@ class RRTMGShortwave(TendencyComponent):
         the device path: same quantities, DeviceQuantity handles instead of arrays (climt_amd/device_state.py)."""
         from ..device_state import DeviceState, shortwave_device_call
         if isinstance(state, DeviceState):
-            return shortwave_device_call(self, state)
+            return shortwave_device_call(self, state, **kwargs)      # (output_work: the caller's own output buffers)
         return super(RRTMGShortwave, self).__call__(state, *args, **kwargs)
 
     @ensure_contiguous_state

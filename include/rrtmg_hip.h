@@ -582,6 +582,48 @@ int rrtmg_hip_set_mcica_overlap_alpha(rrtmg_ctx *ctx, int which, int ncol, int n
 int rrtmg_hip_overlap_alpha(rrtmg_ctx *ctx, int ncol, int nlay, int memspace, const double *play, const double *tlay,
                             double rd_over_g, double decorrelation_m, double *alpha);
 
+/* ---- shortwave between radiation calls: interval-mean zenith, flux rescale (OPT-IN) ------------- */
+/* A model that calls the radiation every few steps (Hogan & Hirahara 2016; Manners et al. 2009) hands the call the cosine of
+ * the zenith angle averaged over the SUNLIT part of the interval the call stands for, and rescales the call's fluxes and heating
+ * rates at every step by that step's own insolation: dst = src * (mean * fraction of the step) / (mean of the call).
+ *
+ * rrtmg_hip_mean_coszen: sibling of rrtmg_hip_zenith_angle (memspace, deferred mode and status codes as there) for the interval
+ * t0 < t1 in Julian centuries, 12 hours at the most -- anything else, t1 <= t0 included, returns RRTMG_ERR_ARG.  The sun's
+ * position (as rrtmg_hip_zenith_angle forms it) is evaluated on the host at t0, t1 and the midpoint: sin_dec, cos_dec of the
+ * midpoint; g0 = gmst(t0) - ra(t0), the hour angle of Greenwich at t0; D = ((gmst(t1) - ra(t1)) - g0) mod 2 pi in (0, 2 pi), its
+ * advance.  One thread per column: A = sin(lat) sin_dec, B = cos(lat) cos_dec (cos(lat) = 0 at latitude +-90 degrees exactly);
+ * h0 = g0 + lon reduced to [-pi, pi), h1 = h0 + D; H = acos(clamp(-A / B, -1, 1)), the sunset hour angle (pi or 0 by the sign
+ * of A where B = 0).  The sunlit set is [h0, h1] n U_k [-H + 2 pi k, H + 2 pi k], k = -1, 0, 1: up to TWO pieces (an interval
+ * that spans a short polar-summer night).  S = the pieces' total length, I = sum over the pieces [a, b] of
+ * A (b - a) + B (sin b - sin a), every operation rounded on its own.
+ *   sunlit_fraction[i] = S / D
+ *   coszen_mean[i]     = S > 0 ? I / S : 0, clamped to [0, 1]
+ *   zenith_mean[i]     = acos(coszen_mean[i]), and pi/2 (1.5707963267948966, what the night-column skip tests against) where
+ *                        coszen_mean is 0: the zenith angle to hand the shortwave call of the interval       (may be NULL)
+ *   insolation[i]      = coszen_mean[i] * sunlit_fraction[i], the interval-mean insolation factor I / D      (may be NULL)
+ * rrtmg_hip_mean_coszen_sun is the same kernel for a caller with a sun of its own (another orbit, a fixed declination): the four
+ * host-side numbers are arguments; hour_angle_advance outside (0, 2 pi) returns RRTMG_ERR_ARG.
+ *
+ * rrtmg_hip_scale_columns: dst[r][c] = src[r][c] * s[c], s[c] = den[c] > 0 ? num[c] / den[c] : +0.0, for up to 16 arrays
+ * [rows][ncol] in ONE launch -- everything a shortwave call returned.  A column with s = 0 is written as +0.0 whatever src
+ * holds (never -0.0, never NaN * 0).  dst == src scales in place; else the two must not overlap.  DEVICE pointers only (num,
+ * den and every src / dst; `entries` itself is a host array, copied before the call returns), on the context's main stream; in
+ * deferred mode the call returns once enqueued.  nentries outside 1..16, a NULL array or rows <= 0 return RRTMG_ERR_ARG.
+ * Probe for the three by symbol; the argument structs and RRTMG_HIP_ABI_VERSION are unchanged. */
+int rrtmg_hip_mean_coszen(rrtmg_ctx *ctx, int ncol, int memspace, const double *lat_deg, const double *lon_deg, double t0_centuries,
+                          double t1_centuries, double *coszen_mean, double *sunlit_fraction, double *zenith_mean, double *insolation);
+int rrtmg_hip_mean_coszen_sun(rrtmg_ctx *ctx, int ncol, int memspace, const double *lat_deg, const double *lon_deg, double sin_dec,
+                              double cos_dec, double hour_angle0, double hour_angle_advance, double *coszen_mean, double *sunlit_fraction,
+                              double *zenith_mean, double *insolation);
+typedef struct rrtmg_scale_entry {
+  const double *src;   /* [rows][ncol] */
+  double *dst;         /* [rows][ncol]; == src: in place */
+  int32_t rows;
+  int32_t reserved;    /* 0 */
+} rrtmg_scale_entry;
+#define RRTMG_SCALE_MAX_ENTRIES 16
+int rrtmg_hip_scale_columns(rrtmg_ctx *ctx, int ncol, const double *num, const double *den, int nentries, const rrtmg_scale_entry *entries);
+
 /* ---- reference-compatible entry points (host pointers, default context) ---------------- */
 int rrtmg_hip_default_status(void);
 const char *rrtmg_hip_default_error(void);
