@@ -9,6 +9,8 @@
 2. ref_sw_*.npz / ref_lw_*.npz -- outputs of the reference Fortran (oracle/_ref) on seeded synthetic
    columns (climt_amd.synthetic) for the boundary-level parity tests that must run where the
    reference library is not available.  LW fixtures are on the SYNTHETIC k-tables of the LW blob.
+3. ref_state_*.npz -- the same on atmospheric states that do NOT come from climt_amd.synthetic (state_cases): hot and wet, cold
+   and dry, deep columns, a ragged tropopause, a grazing sun.  `make_golden.py states [substring ...]` regenerates them alone.
 """
 import os
 import sys
@@ -347,6 +349,240 @@ def reference_option_cases(only=None):
         print("option case", name, {k: float(np.abs(r[k]).max()) for k in keys[:2]})
 
 
+# ---- atmospheric states off the synthetic profile: index clamps and branch edges of setcoef / taumol / the solvers ---------
+STATE_NCOL, STATE_NLAY = 24, 40
+
+
+def state_columns(ps, ptop, dt, rh, stretch, nlay=STATE_NLAY, seed=0, dt_weight=None, cloudy=False, dp_top=None, cloud_free_columns=True):
+    """Boundary-level inputs of columns that do NOT come from climt_amd.synthetic.make_columns.  Per column: surface pressure
+    `ps` and top pressure `ptop` [hPa], temperature offset `dt` [K] from the k-distribution's own reference profile (tref on
+    preflog, read from the shipped shortwave blob), humidity as the factor `rh` of saturation, and the grid stretch: interface
+    k of n lies at ps * (ptop / ps) ** ((k / n) ** stretch), so 1 is even in log-pressure, > 1 is fine near the surface and
+    coarse aloft, < 1 the other way round.  dt_weight(play / ps) -> the share of `dt` a layer gets (default: all of it).
+    dp_top [hPa], where > 0: the top layer is that thick and the rule above spaces the n - 1 layers below it (a heating rate is
+    a flux difference times 8.4 K day-1 / dp[hPa]: under a top at 0.002 hPa the rule alone leaves layers of 1e-3 hPa, in
+    which the last place of a 1000 W m-2 flux is worth 1e-9 K day-1).  cloudy: broken decks between 0.3 and 0.85 of the surface
+    pressure, fractions 0 / 0.3 / 0.6 / 1 by pairs of columns; cloud_free_columns=False: 0.45 in place of 0 and at least one
+    cloudy layer in every column (a cloud-free column ALONE makes a cloud-free tile, which the library hands to its clear-sky
+    solve variant, whose last bits differ by design: a case whose columns are compared with one-column calls has none)."""
+    from climt_amd import synthetic
+    from climt_amd.synthetic import _ozone_profile, _qsat
+    from tools.pack_tables import read_blob
+    blob = read_blob(os.path.join(ROOT, "climt_amd", "data", "rrtmg_sw_data.bin"))
+    preflog, tref = np.asarray(blob["sw/ref/preflog"], dtype=np.float64), np.asarray(blob["sw/ref/tref"], dtype=np.float64)
+    ps, ptop, dt, rh, stretch = (np.asarray(a, dtype=np.float64) for a in (ps, ptop, dt, rh, stretch))
+    ncol = ps.size
+    rng = np.random.default_rng(7100 + seed)
+    x = (np.arange(nlay + 1) / nlay)[:, None] ** stretch[None, :]
+    plev = ps[None, :] * (ptop / ps)[None, :] ** x
+    if dp_top is not None:
+        dp_top = np.asarray(dp_top, dtype=np.float64)
+        x = (np.arange(nlay) / (nlay - 1))[:, None] ** stretch[None, :]
+        thick = np.concatenate([ps[None, :] * ((ptop + dp_top) / ps)[None, :] ** x, ptop[None, :]])
+        plev = np.where(dp_top[None, :] > 0, thick, plev)
+    play = 0.5 * (plev[:-1] + plev[1:])
+    tstd = np.interp(np.log(play), preflog[::-1], tref[::-1])                 # (held at the table's ends outside it)
+    w = 1.0 if dt_weight is None else dt_weight(play / ps[None, :])
+    tlay = tstd + w * dt[None, :] + 0.3 * rng.standard_normal(play.shape)
+    tsfc = tlay[0] + rng.uniform(0.2, 2.0, ncol)
+    lp = np.log(play)
+    tlev = np.zeros((nlay + 1, ncol))
+    wi = (np.log(plev[1:-1]) - lp[1:]) / (lp[:-1] - lp[1:])
+    tlev[1:-1] = tlay[1:] - wi * (tlay[1:] - tlay[:-1])
+    tlev[0] = tsfc
+    tlev[-1] = tlay[-1]
+    q = np.where(play > 100.0, np.maximum(rh[None, :] * _qsat(tlay, play), 3.0e-6), 3.0e-6)
+    _ozone_profile(np.array([1.0e4]))                                          # (loads the table)
+    ptab = synthetic._OZONE[0]
+    o3 = np.maximum(_ozone_profile(np.clip(100.0 * play, ptab.min(), ptab.max())), 1.0e-9)   # the spline inside its table only
+    full = lambda v: np.full((nlay, ncol), v)
+    u1, u2 = rng.uniform(-1, 1, ncol), rng.uniform(-1, 1, ncol)
+    c = dict(play=play, plev=plev, tlay=tlay, tlev=tlev, tsfc=tsfc, h2o=q * 28.964 / 18.02, o3=o3,
+             co2=full(330e-6), ch4=full(1.7e-6), n2o=full(0.3e-6), o2=full(0.21),
+             cfc11=full(0.25e-9), cfc12=full(0.5e-9), cfc22=full(0.1e-9), ccl4=full(0.1e-9),
+             emis=rng.uniform(0.92, 1.0, (16, ncol)),
+             asdir=0.06 + 0.2 * u1 ** 2, asdif=0.06 + 0.2 * u2 ** 2, aldir=0.08 + 0.3 * u1 ** 2, aldif=0.08 + 0.3 * u2 ** 2,
+             coszen=rng.uniform(0.15, 1.0, ncol))
+    cld, clwp, ciwp = np.zeros((nlay, ncol)), np.zeros((nlay, ncol)), np.zeros((nlay, ncol))
+    if cloudy:
+        frac = np.array([0.0 if cloud_free_columns else 0.45, 0.3, 0.6, 1.0])[(np.arange(ncol) // 2) % 4]   # neighbours share a fraction, not a profile
+        deck = ((np.arange(nlay)[:, None] + np.arange(ncol)[None, :]) % 5) < 3
+        sigma = play / ps[None, :]
+        inband = (sigma > 0.3) & (sigma < 0.85)
+        if not cloud_free_columns:      # (a column whose decks all miss the band: its lowest layer inside it)
+            deck = deck | ((np.cumsum(inband, axis=0) == 1) & inband & ~(inband & deck).any(0)[None, :])
+        cld = np.where(inband & deck, frac[None, :], 0.0)
+        clwp = np.where((cld > 0) & (tlay > 253.0), rng.uniform(20.0, 80.0, cld.shape), 0.0)
+        ciwp = np.where((cld > 0) & (tlay < 263.0), rng.uniform(5.0, 30.0, cld.shape), 0.0)
+        cld = np.where((clwp + ciwp) > 0, cld, 0.0)
+    c.update(cldfr=cld, cliqwp=clwp, cicewp=ciwp, reliq=full(10.0), reice=full(30.0))
+    return {k: np.ascontiguousarray(v, dtype=np.float64) for k, v in c.items()}
+
+
+def _alternate(ordinary, edge, ncol=STATE_NCOL):
+    """Even columns from `ordinary`, odd ones from `edge` (arrays of ncol / 2 each, or scalars): the lanes of one wavefront
+    disagree about every index the regime is about."""
+    out = np.empty(ncol)
+    out[0::2], out[1::2] = ordinary, edge
+    return out
+
+
+def _state_regime(regime, seed, cloudy, spectrum="lw"):
+    """The five regimes (see state_cases); ordinary mid-latitude columns (even) alternate with edge columns (odd)."""
+    h = STATE_NCOL // 2
+    r = np.random.default_rng(7000 + seed)
+    low = lambda s: np.clip((s - 0.25) / 0.35, 0.0, 1.0)      # all of dt below 0.6 ps, none of it above 0.25 ps
+    ps_ord = 1013.2 * (1.0 + 0.02 * r.uniform(-1, 1, h))
+    # MOVED INWARD: the humidity of the hot columns in the SHORTWAVE fixtures, 0.1 of saturation instead of 0.97.  Above 330 K and
+    # near saturation (h2o 0.2 ... 0.5 by volume) the reference extrapolates its self-continuum and k tables to negative optical
+    # depths and returns finite nonsense -- upward fluxes of 2.3e6 W m-2, downward ones of -4e4 W m-2 in 6 of the 12 hot columns --
+    # on which no absolute bound means anything.  At 0.1 (h2o <= 0.06) every flux lies between 0 and the incoming one.  No
+    # shortwave edge depends on the humidity; the longwave ones that do (the diffusivity angles) keep 0.97.
+    rh_hot = 0.97 if spectrum == "lw" else 0.1
+    if regime == "hot_wet":
+        # edge columns 35 ... 60 K above tref in the lower troposphere, humidity 0.97 of saturation; the ordinary ones are
+        # cool and dry enough (precipitable water < 1 cm) for band 6's diffusivity angle to sit on its upper limit
+        c = state_columns(_alternate(ps_ord, 1013.2 * (1.0 + 0.02 * r.uniform(-1, 1, h))), np.full(STATE_NCOL, 0.2),
+                          _alternate(r.uniform(-14.0, -6.0, h), np.linspace(35.0, 60.0, h)), _alternate(r.uniform(0.1, 0.25, h), rh_hot),
+                          _alternate(1.0, r.uniform(1.0, 1.4, h)), seed=seed, dt_weight=low, cloudy=cloudy)
+    elif regime == "cold_dry":
+        c = state_columns(_alternate(ps_ord, 1013.2 * (1.0 + 0.02 * r.uniform(-1, 1, h))), np.full(STATE_NCOL, 0.2),
+                          _alternate(r.uniform(-5.0, 5.0, h), -np.linspace(35.0, 75.0, h)), _alternate(0.7, 0.0),
+                          _alternate(1.0, r.uniform(0.9, 1.3, h)), seed=seed, cloudy=cloudy)
+        c["h2o"][:, 1::2] = 1.0e-9
+        # gases exactly zero in a few layers of some edge columns: the `== 0 -> 1e-32 * coldry` substitutions
+        for k, (col, lays) in dict(co2=(1, (0, 7, 30)), ch4=(5, (2, 3, 25)), o2=(9, (0, 1, 39)), o3=(13, (5, 20, 38)), n2o=(17, (4, 12, 33))).items():
+            c[k][list(lays), col] = 0.0
+        c["co2"][10, 21] = c["ch4"][10, 21] = c["o2"][10, 21] = c["o3"][10, 21] = c["n2o"][10, 21] = 0.0
+    elif regime == "deep_column":
+        c = state_columns(_alternate(ps_ord, np.linspace(1060.0, 1085.0, h)), _alternate(0.2, np.geomspace(0.002, 0.006, h)),
+                          _alternate(r.uniform(-5.0, 5.0, h), r.uniform(-8.0, 8.0, h)), np.full(STATE_NCOL, 0.7),
+                          _alternate(1.0, r.uniform(2.0, 2.6, h)), seed=seed, cloudy=cloudy, dp_top=_alternate(0.0, r.uniform(0.009, 0.0115, h)),
+                          cloud_free_columns=False)
+        # (a low sun over the thin layers aloft: the last place of the flux there, which is what a heating rate in a layer of
+        # 0.01 hPa magnifies 800 times, is that of 200 W m-2 and not of 1400)
+        c["coszen"][1::2] = r.uniform(0.1, 0.3, h)
+    elif regime == "ragged_tropopause":
+        # edge columns: mountains and low tops.  Column 1 keeps exactly one layer above 95.6 hPa (laytrop = nlay - 1), column 3
+        # exactly one below it (laytrop = 1); the tops at 90 ... 3 hPa end below the reference layer (jp 18, 30, 32, 49, 58) of
+        # some or all of bands 16, 17, 27, 29, 28, so those bands take their default solar-source layer there and not next door
+        ps_e = np.array([1000.0, 520.0, 1050.0, 700.0, 600.0, 950.0, 520.0, 820.0, 1040.0, 560.0, 900.0, 650.0])
+        pt_e = np.array([90.0, 0.5, 40.0, 10.0, 1.0, 0.1, 60.0, 3.0, 0.02, 25.0, 0.5, 5.0])
+        st_e = np.array([1.0, 0.3, 1.2, 0.8, 1.5, 1.8, 0.6, 1.3, 0.9, 0.7, 1.4, 1.0])
+        c = state_columns(_alternate(ps_ord, ps_e), _alternate(0.2, pt_e), _alternate(r.uniform(-5.0, 5.0, h), r.uniform(-10.0, 10.0, h)),
+                          np.full(STATE_NCOL, 0.7), _alternate(1.0, st_e), seed=seed, cloudy=cloudy, dp_top=_alternate(0.0, np.where(pt_e == 0.02, 0.02, 0.0)),
+                          cloud_free_columns=False)
+    elif regime == "grazing_sun":
+        # deep_column's edge profile on the even columns, hot_wet's on the odd ones; each pair shares one zenith cosine
+        c = state_columns(_alternate(np.linspace(1060.0, 1085.0, h), 1013.2 * (1.0 + 0.02 * r.uniform(-1, 1, h))),
+                          _alternate(np.geomspace(0.002, 0.006, h), 0.2), _alternate(r.uniform(-8.0, 8.0, h), np.linspace(35.0, 60.0, h)),
+                          _alternate(0.7, rh_hot), _alternate(r.uniform(2.6, 3.2, h), r.uniform(1.0, 1.4, h)), seed=seed,
+                          dt_weight=lambda s: np.where((np.arange(STATE_NCOL) % 2 == 1)[None, :], low(s), 1.0), cloudy=cloudy,
+                          dp_top=_alternate(r.uniform(0.03, 0.04, h), 0.0))      # (thicker than deep_column's: the sun is high here)
+        c["coszen"] = np.repeat([1.0e-12, 1.0e-10, 1.0e-6, 1.0e-3, 0.01, 0.03, 0.1, 0.2, 0.4, 0.6, 0.8, 1.0], 2)
+    else:
+        raise KeyError(regime)
+    return c
+
+
+STATE_REGIMES = ("hot_wet", "cold_dry", "deep_column", "ragged_tropopause", "grazing_sun")
+
+
+def state_cases():
+    """name -> (spectrum, mcica, inputs): 24 columns x 40 layers, ordinary mid-latitude columns alternating with edge columns.
+
+    hot_wet             lower troposphere 35-60 K above tref, near saturation: jt / jt1 clamp at 4, indself at 9, indfor at 1 with
+                        a negative factor, Planck index at 180 (surface, interfaces, layers), diffusivity angles on 1.50 / 1.80
+    cold_dry            35-75 K below tref, h2o 1e-9, gases exactly zero in a few layers: jt / jt1 clamp at 1, indself at 1, indfor
+                        at 2, indminor at 1, Planck index at 1 (layers, interfaces), the 1e-32 * coldry substitutions
+    deep_column         surface up to 1085 hPa (jp clamps at 1, fp < 0), top down to 0.002 hPa (jp clamps at 58, fp > 1), spacing
+                        uneven and different by column
+    ragged_tropopause   surfaces 520 ... 1050 hPa, tops 90 ... 0.02 hPa: many values of laytrop in one wavefront, laytrop = nlay - 1
+                        and laytrop = 1, tops below the reference layer of bands 16, 17, 27, 28, 29 (default solar-source layer)
+    grazing_sun (SW)    cos(zenith) 1e-12 ... 1 on the deep_column and hot_wet edge profiles: the 1e-10 floor, tau / mu0 > 500
+
+    Shortwave: clear sky and McICA (icld 2, kissvec); longwave: clear sky, random overlap without McICA, McICA (icld 2, idrv 1).
+    No column has laytrop = 0 or laytrop = nlay: the reference's shortwave then reads solar-source entries no taumol routine has
+    set (rrtmg_sw_spcvrt.f90:272), so there is nothing to compare with.
+
+    The reference is finite on every column.  MOVED INWARD, one thing: the humidity of the hot columns in the shortwave fixtures
+    (hot_wet, grazing_sun), 0.1 of saturation instead of 0.97 -- see _state_regime; no edge was given up for it.  Shaped for
+    conditioning, with every edge kept: the thin layers under the 0.002 hPa tops (state_columns: dp_top; a low sun over
+    deep_column's edge columns), and a cloud in every column of the cloudy deep_column / ragged_tropopause cases.
+    Measured when the fixtures were made (the reference Fortran twice: on the inputs, and on tlay / play / h2o moved by one unit
+    in the last place, McICA on the same sub-columns; stored under cond/): no output moves by more than 1.3e-10 (heating rates;
+    fluxes <= 6.3e-12 W m-2), so every case is held to the plain bounds of the option fixtures and no test reads cond/."""
+    cases = {}
+    base = dict(iaer=0, adjes=1.0, dyofyr=1, scon=1367.0, isolvar=0, inflg=2, iceflg=1, liqflg=1, irng=0)
+    for i, regime in enumerate(STATE_REGIMES):
+        kinds = [("sw", "clear", False, dict(icld=0)), ("sw", "mcica", True, dict(icld=2))]
+        if regime != "grazing_sun":
+            kinds += [("lw", "clear", False, dict(icld=0)), ("lw", "random", False, dict(icld=1)), ("lw", "mcica", True, dict(icld=2, idrv=1))]
+        for j, (spectrum, kind, mcica, flags) in enumerate(kinds):
+            c = _state_regime(regime, 10 * i + j, cloudy=kind != "clear", spectrum=spectrum)
+            c.update(base); c.update(flags); c["permuteseed"] = 101 + 10 * i + j
+            cases["%s_%s_%s" % (spectrum, regime, kind)] = (spectrum, mcica, c)
+    return cases
+
+
+def state_edges(c, preflog, tref, grav=9.80665):
+    """The indices of rrtmg_{sw,lw}_setcoef.f90 BEFORE their clamps, restated in numpy on boundary-level inputs -> dict.
+    (What the generator prints; tests/test_device_functions_emulated.py has its own copy and asserts on it.)"""
+    play, tlay = c["play"], c["tlay"]
+    plog = np.log(play)
+    jp_raw = np.trunc(36.0 - 5.0 * (plog + 0.04)).astype(int)
+    jp = np.clip(jp_raw, 1, 58)
+    lower = plog > 4.56
+    return dict(jp_raw=jp_raw, jp=jp, fp=5.0 * (preflog[jp - 1] - plog), laytrop=lower.sum(0),
+                jt_raw=np.trunc(3.0 + (tlay - tref[jp - 1]) / 15.0).astype(int), jt1_raw=np.trunc(3.0 + (tlay - tref[jp]) / 15.0).astype(int),
+                lower=lower, forfactor=(332.0 - tlay) / 36.0, indself_raw=np.trunc((tlay - 188.0) / 7.2).astype(int) - 7,
+                indminor_raw=np.trunc((tlay - 180.8) / 7.2).astype(int))
+
+
+def reference_state_cases(only=None, cond=True):
+    """ref_state_<name>.npz, laid out as ref_opt_*: inputs under in/ and flag/, outputs of the reference Fortran under sw/ or lw/
+    (longwave on the tables of the shipped blob), and under cond/ how far each output moves when tlay, play and h2o move by one
+    unit in the last place -- the conditioning of the reference itself on these states."""
+    from oracle.ref_driver import RefLW, RefSW
+    from tools.pack_tables import read_blob
+    from tools.synth_lw_tables import fill_reference_from_blob
+    sw = RefSW()
+    blob = read_blob(os.path.join(ROOT, "climt_amd", "data", "rrtmg_lw_data.bin"))
+    swblob = read_blob(os.path.join(ROOT, "climt_amd", "data", "rrtmg_sw_data.bin"))
+    preflog, tref = np.asarray(swblob["sw/ref/preflog"]), np.asarray(swblob["sw/ref/tref"])
+    lw = RefLW()
+    lw.init(fill_tables=lambda r: fill_reference_from_blob(r, blob))
+    for name, (spectrum, mcica, c) in state_cases().items():
+        if only and not any(o in name for o in only):
+            continue
+        save = {"in/" + k: v for k, v in c.items() if isinstance(v, np.ndarray)}
+        save.update({"flag/" + k: np.array(v) for k, v in c.items() if not isinstance(v, np.ndarray)})
+        save["flag/_mcica"] = np.array(int(mcica))
+        ref = sw if spectrum == "sw" else lw
+        r = ref.fluxes(dict(c), mcica=mcica)
+        keys = ("swuflx", "swdflx", "swhr", "swuflxc", "swdflxc", "swhrc") if spectrum == "sw" else \
+               ("uflx", "dflx", "hr", "uflxc", "dflxc", "hrc") + (("duflx_dt", "duflxc_dt") if c.get("idrv") else ())
+        for k in keys:
+            save["%s/%s" % (spectrum, k)] = r[k]
+        assert all(np.all(np.isfinite(r[k])) for k in keys), name
+        worst = {}
+        if cond:
+            up = dict(c)
+            for k in ("tlay", "play", "h2o"):
+                up[k] = np.nextafter(c[k], np.inf)
+            # (on the first run's sub-columns: kissvec seeds from the digits of the pressures, and a last-place move of `play`
+            # can draw another cloud mask altogether, which is no rounding effect)
+            r2 = ref.fluxes(up, mcica=mcica, subcol=r["subcol"]) if mcica else ref.fluxes(up, mcica=False)
+            for k in keys:
+                worst[k] = float(np.abs(r2[k] - r[k]).max())
+                save["cond/" + k] = np.array(worst[k])
+        np.savez_compressed(os.path.join(OUT, "ref_state_%s.npz" % name), **save)
+        e = state_edges(c, preflog, tref)
+        print("state case", name, "jp_raw %d..%d jt_raw %d..%d laytrop %s T %.1f..%.1f tsfc max %.1f cond %.1e" % (
+            e["jp_raw"].min(), e["jp_raw"].max(), min(e["jt_raw"].min(), e["jt1_raw"].min()), max(e["jt_raw"].max(), e["jt1_raw"].max()),
+            sorted(set(e["laytrop"].tolist())), c["tlay"].min(), c["tlay"].max(), c["tsfc"].max(), max(worst.values()) if worst else -1.0))
+
+
 def cache_outputs_only(cls, desc):
     """climt_cacheout_<Class>-<desc>.npz: the expected outputs of a reference cache whose input state is a missing blob
     (`*_stepping-1.cache` absent: .MISSING_LARGE_BLOBS) but is the plain default state of the reference's test
@@ -587,6 +823,9 @@ if __name__ == "__main__":
     if sys.argv[1:2] == ["options"]:      # options <substring> ...: only those option fixtures
         reference_option_cases(only=sys.argv[2:])
         sys.exit(0)
+    if sys.argv[1:2] == ["states"]:       # states <substring> ...: only those state fixtures
+        reference_state_cases(only=sys.argv[2:])
+        sys.exit(0)
     n = 0
     for cls in ("TestRRTMGLongwave", "TestRRTMGLongwaveMCICA", "TestRRTMGLongwaveWithClouds",
                 "TestRRTMGLongwaveWithExternalInterfaceTemperature", "TestRRTMGShortwave", "TestRRTMGShortwaveMCICA"):
@@ -600,6 +839,7 @@ if __name__ == "__main__":
     berger_cases()
     slab_surface_cases()
     reference_option_cases()
+    reference_state_cases()
     for cls in ("TestRRTMGShortwave", "TestRRTMGLongwave"):
         cache_outputs_only(cls, "3d")
     reference_lw_class_cases()

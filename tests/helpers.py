@@ -322,9 +322,9 @@ def load_lwmr_case(name):
 OPT_CASES = tuple(sorted(f[len("ref_opt_"):-len(".npz")] for f in os.listdir(GOLDEN) if f.startswith("ref_opt_") and f.endswith(".npz")))
 
 
-def load_opt_case(name):
+def load_opt_case(name, prefix="ref_opt_"):
     """-> (spectrum 'sw' | 'lw', mcica flag, inputs at the C-ABI boundary, expected outputs of the reference Fortran)."""
-    z = np.load(os.path.join(GOLDEN, "ref_opt_%s.npz" % name))
+    z = np.load(os.path.join(GOLDEN, "%s%s.npz" % (prefix, name)))
     c = {k[3:]: np.ascontiguousarray(z[k]) for k in z.files if k.startswith("in/")}
     flags = {k[5:]: z[k].item() for k in z.files if k.startswith("flag/")}
     mcica = bool(flags.pop("_mcica"))
@@ -332,6 +332,16 @@ def load_opt_case(name):
     spectrum = name.split("_")[0]
     exp = {k[3:]: z[k] for k in z.files if k.startswith(spectrum + "/")}
     return spectrum, mcica, c, exp
+
+
+# ---- atmospheric states off the synthetic profile (self-contained as the option fixtures; make_golden.py states) ----------------
+STATE_CASES = tuple(sorted(f[len("ref_state_"):-len(".npz")] for f in os.listdir(GOLDEN) if f.startswith("ref_state_") and f.endswith(".npz")))
+
+
+def load_state_case(name):
+    """As load_opt_case.  (The files also hold, under cond/, how far each output of the reference moved when tlay, play and h2o
+    moved by one unit in the last place: every case meets the plain bounds, so no test reads it.)"""
+    return load_opt_case(name, prefix="ref_state_")
 
 
 # ---- our driver of the reference's shortwave procedures (tests/refshim/sw_shim.f90, built by tests/refshim/build.sh) ----------
