@@ -21,7 +21,7 @@ from .rrtmg import RRTMGLongwave, RRTMGShortwave, radiation_step  # noqa: F401,E
 from .slab_surface import SlabSurface  # noqa: F401,E402
 from .timestepping import AdamsBashforth  # noqa: F401,E402
 from .wrappers import UpdateFrequencyWrapper  # noqa: F401,E402
-from .intermittent import IntermittentShortwave  # noqa: F401,E402
+from .intermittent import IntermittentLongwave, IntermittentShortwave  # noqa: F401,E402
 
-__all__ = ["RRTMGLongwave", "RRTMGShortwave", "Instellation", "BergerSolarInsolation", "SlabSurface", "get_grid", "get_default_state", "UpdateFrequencyWrapper", "IntermittentShortwave", "AdamsBashforth",
+__all__ = ["RRTMGLongwave", "RRTMGShortwave", "Instellation", "BergerSolarInsolation", "SlabSurface", "get_grid", "get_default_state", "UpdateFrequencyWrapper", "IntermittentShortwave", "IntermittentLongwave", "AdamsBashforth",
            "Context", "RRTMGError", "DeviceState", "DeviceQuantity", "DeviceAdamsBashforth", "radiation_step"]

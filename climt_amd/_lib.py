@@ -170,6 +170,13 @@ class ScaleEntry(C.Structure):
 SCALE_MAX_ENTRIES = 16      # RRTMG_SCALE_MAX_ENTRIES: the arrays of one rrtmg_hip_scale_columns call
 
 
+class LwAdjust(C.Structure):
+    """mirrors `rrtmg_lw_adjust` (include/rrtmg_hip.h), field for field"""
+    _fields_ = ([("struct_size", C.c_uint32), ("ncol", _i32), ("nlay", _i32)]
+                + [(n, _vp) for n in ("tsfc_call", "tsfc_now", "plev")] + [("pressure_scale", _f64)]
+                + [(n, _vp) for n in "uflx dflx duflx_dt uflxc dflxc duflxc_dt uflx_out hr_out uflxc_out hrc_out".split()])
+
+
 _lib = None
 
 
@@ -239,7 +246,9 @@ def load_library():
         lib.rrtmg_hip_mean_coszen.argtypes = [_vp, C.c_int, C.c_int, _vp, _vp, _f64, _f64, _vp, _vp, _vp, _vp]
         lib.rrtmg_hip_mean_coszen_sun.argtypes = [_vp, C.c_int, C.c_int, _vp, _vp, _f64, _f64, _f64, _f64, _vp, _vp, _vp, _vp]
         lib.rrtmg_hip_scale_columns.argtypes = [_vp, C.c_int, _vp, _vp, C.c_int, C.POINTER(ScaleEntry)]
-    lib.rrtmg_hip_copy_blocks.argtypes = [_vp, C.c_int, _vp, C.c_long, C.c_long, _vp, _vp, _vp]
+    if hasattr(lib, "rrtmg_hip_lw_adjust_surface"):         # (likewise: the longwave between radiation calls)
+        lib.rrtmg_hip_lw_adjust_surface.argtypes = [_vp, C.POINTER(LwAdjust)]
+    lib.rrtmg_hip_copy_blocks.argtypes =[_vp, C.c_int, _vp, C.c_long, C.c_long, _vp, _vp, _vp]
     lib.rrtmg_hip_mcica_mask.argtypes = [_vp] + [C.c_int] * 6 + [_vp] * 3
     _lib = lib
     return lib
@@ -487,6 +496,33 @@ class Context:
             for e, (src, dst, rows) in zip(table, part):
                 e.src, e.dst, e.rows = _device_pointer(src, f64, "src"), _device_pointer(dst, f64, "dst"), int(rows)
             self._ck(entry(self.h, int(ncol), n, d, len(part), table))
+
+    @property
+    def has_lw_adjust(self):
+        """Whether the library exports the longwave between radiation calls (rrtmg_hip_lw_adjust_surface; probed by the symbol)."""
+        return hasattr(self.lib, "rrtmg_hip_lw_adjust_surface")
+
+    @_locked
+    def lw_adjust_surface(self, ncol, nlay, tsfc_call, tsfc_now, plev, all_sky, clear_sky=None, pressure_scale=0.0):
+        """uflx' = uflx + duflx_dt * (tsfc_now - tsfc_call) by column and level, and the heating rates of the corrected net
+        fluxes (rrtmg_hip_lw_adjust_surface): one launch on the longwave's stream.  `all_sky`, `clear_sky` (None: no clear-sky
+        stream): (uflx, dflx, duflx_dt, uflx_out, hr_out), uflx_out may be uflx.  Device pointers (or DeviceArrays) throughout;
+        `pressure_scale` as in a flux call (0: plev is in mbar)."""
+        if not self.has_lw_adjust:
+            raise RRTMGError(4, "this librrtmg_hip.so has no rrtmg_hip_lw_adjust_surface (longwave between radiation calls)")
+        f64 = PRECISIONS["float64"]
+        a = LwAdjust()
+        a.struct_size, a.ncol, a.nlay, a.pressure_scale = C.sizeof(LwAdjust), int(ncol), int(nlay), float(pressure_scale)
+        for name, v in (("tsfc_call", tsfc_call), ("tsfc_now", tsfc_now), ("plev", plev)):
+            setattr(a, name, _device_pointer(v, f64, name))
+        for stream, names in ((all_sky, ("uflx", "dflx", "duflx_dt", "uflx_out", "hr_out")), (clear_sky, ("uflxc", "dflxc", "duflxc_dt", "uflxc_out", "hrc_out"))):
+            if stream is None:
+                continue
+            if len(stream) != 5:
+                raise ValueError("lw_adjust_surface: a stream is (uflx, dflx, duflx_dt, uflx_out, hr_out)")
+            for name, v in zip(names, stream):
+                setattr(a, name, None if v is None else _device_pointer(v, f64, name))
+        self._ck(self.lib.rrtmg_hip_lw_adjust_surface(self.h, C.byref(a)))
 
     @_locked
     def solar_insolation(self, lat, lon, sin_delta, cos_delta, fractional_day, irradiance):

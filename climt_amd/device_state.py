@@ -330,8 +330,10 @@ def shortwave_device_call(self, ds, output_work=None):
     return {"air_temperature": hr}, diagnostics
 
 
-def longwave_device_call(self, ds):
-    """RRTMGLongwave on a DeviceState: the body of array_call (lw/component.py:373-522) with device pointers."""
+def longwave_device_call(self, ds, output_work=None):
+    """RRTMGLongwave on a DeviceState: the body of array_call (lw/component.py:373-522) with device pointers.
+    `output_work(key, shape, dims, units)`: the caller's own buffers for the outputs, the derivatives of idrv = 1 included
+    (climt_amd.IntermittentLongwave keeps a call's results across model steps); default: two alternating sets of the state's."""
     ds.init_tables("lw", self._Cpd)
     P = self.input_properties
     g = lambda n: ds.need(n, P[n]).ptr
@@ -356,7 +358,7 @@ def longwave_device_call(self, ds):
         inp.update(irng=self._random_number_generator, permuteseed=self._permute_seed)
     il, ml = (nlay + 1, ncol), (nlay, ncol)
     self._device_calls = getattr(self, "_device_calls", 0) + 1
-    w = lambda key, shape, dims, units: ds.work(("lw", id(self), key, self._device_calls & 1), shape, dims, units)
+    w = output_work or (lambda key, shape, dims, units: ds.work(("lw", id(self), key, self._device_calls & 1), shape, dims, units))
     clear = getattr(self, "_clear_sky", True)      # False: no buffers for the clear-sky outputs, which the library then leaves out
     fl = {k: w(k, il, ("interface_levels", "*"), "W m^-2") for k in (("uflx", "dflx", "uflxc", "dflxc") if clear else ("uflx", "dflx"))}
     hr = w("hr", ml, ("mid_levels", "*"), "degK day^-1")

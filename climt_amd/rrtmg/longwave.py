@@ -188,7 +188,7 @@ class RRTMGLongwave(TendencyComponent):
         the device path: same quantities, DeviceQuantity handles instead of arrays (climt_amd/device_state.py)."""
         from ..device_state import DeviceState, longwave_device_call
         if isinstance(state, DeviceState):
-            return longwave_device_call(self, state)
+            return longwave_device_call(self, state, **kwargs)      # (output_work: the caller's own output buffers)
         return super(RRTMGLongwave, self).__call__(state, *args, **kwargs)
 
     def _apply_clear_sky(self, ctx):
@@ -280,6 +280,10 @@ class RRTMGLongwave(TendencyComponent):
         if self._calc_dflxdt:
             self.change_in_upward_flux_with_surface_temperature = out["duflx_dt"]
             self.change_in_clear_sky_upward_flux_with_surface_temperature = out.get("duflxc_dt")      # (None without the clear-sky stream)
+            # what the heating rates of this call were formed over, for whoever forms them again (climt_amd.IntermittentLongwave):
+            # the interface pressures as handed to the library and the factor it applied to them (0: none)
+            inp = call["library"]["inp"]
+            self._interface_pressure_of_call = (inp["plev"], float(inp.get("pressure_scale") or 0.0))
         # the reference aliases (not copies) the tendency here (lw/component.py:518-520)
         diagnostics["air_temperature_tendency_from_longwave"] = tendencies["air_temperature"]
         return tendencies, diagnostics

@@ -624,6 +624,34 @@ typedef struct rrtmg_scale_entry {
 #define RRTMG_SCALE_MAX_ENTRIES 16
 int rrtmg_hip_scale_columns(rrtmg_ctx *ctx, int ncol, const double *num, const double *den, int nentries, const rrtmg_scale_entry *entries);
 
+/* ---- longwave between radiation calls: surface-temperature flux adjustment (OPT-IN) ------------- */
+/* The consumer of idrv = 1: a model that calls the longwave every few steps corrects the kept upward fluxes at every step for
+ * the surface temperature of that step (the comment on idrv in rrtmg_lw_rad; Hogan & Bozzo 2015), and forms the heating rates
+ * again.  By column, dT = tsfc_now - tsfc_call:
+ *   uflx_out[l] = uflx[l] + duflx_dt[l] * dT                          l = 0..nlay; the product rounded, then the sum
+ *   hr_out[k]   = heatfac * ((uflx_out[k] - dflx[k]) - (uflx_out[k+1] - dflx[k+1])) / (plev[k] - plev[k+1])      k = 0..nlay-1
+ * -- the expression and the order of the flux call's own heating rate, heatfac that of rrtmg_hip_lw_init (before it:
+ * RRTMG_ERR_NOT_INITIALISED); pressure_scale as in rrtmg_lw_args (0: plev is in mbar; else every plev is multiplied by it first,
+ * then the difference taken, as the flux call does) -- here with device pointers too.  dT = 0 returns the bits of uflx and of the
+ * hr the flux call wrote.  The same for the clear-sky stream where uflxc, dflxc, duflxc_dt, uflxc_out and hrc_out are given (all
+ * five, or none: the call of rrtmg_hip_set_lw_clear_sky(ctx, 0) has none).  dflx and dflxc are only read.  FIRST ORDER in dT, and
+ * not clamped: the neglected term is about 0.5 % of the correction per kelvin in the window bands.
+ * DEVICE pointers only.  uflx_out may be uflx, uflxc_out may be uflxc (in place: the launch then gives each column to one
+ * thread); any other overlap of an output with an input or another output returns RRTMG_ERR_ARG, as do a struct_size other than
+ * sizeof(rrtmg_lw_adjust), ncol or nlay <= 0, a NULL array of the all-sky stream and a clear-sky stream given in part.  One
+ * launch on the stream of the longwave flux call (deferred mode: the longwave's own stream, and the call returns once enqueued;
+ * consumers on the main stream order themselves behind it with rrtmg_hip_order_streams(ctx, 1)); otherwise the call waits.
+ * Probe for it by symbol; the argument structs of the flux calls and RRTMG_HIP_ABI_VERSION are unchanged. */
+typedef struct {
+  uint32_t struct_size; int32_t ncol, nlay;
+  const double *tsfc_call, *tsfc_now;                 /* [ncol] */
+  const double *plev; double pressure_scale;          /* [nlay+1][ncol] */
+  const double *uflx, *dflx, *duflx_dt;               /* [nlay+1][ncol] */
+  const double *uflxc, *dflxc, *duflxc_dt;            /* all three NULL: no clear-sky stream */
+  double *uflx_out, *hr_out, *uflxc_out, *hrc_out;    /* uflx_out may be uflx (in place); hr [nlay][ncol] */
+} rrtmg_lw_adjust;
+int rrtmg_hip_lw_adjust_surface(rrtmg_ctx *ctx, const rrtmg_lw_adjust *a);
+
 /* ---- reference-compatible entry points (host pointers, default context) ---------------- */
 int rrtmg_hip_default_status(void);
 const char *rrtmg_hip_default_error(void);
