@@ -1,7 +1,7 @@
 """climt_amd -- MI355X-native RRTMG longwave + shortwave radiation, drop-in for
 climt.RRTMGLongwave / climt.RRTMGShortwave (climt/_components/rrtmg/__init__.py:1-4), plus the zenith-angle producer
 upstream of the shortwave, climt.Instellation and climt.BergerSolarInsolation, and the consumer of the surface
-fluxes downstream, climt.SlabSurface; and what a model script needs to set the path up: get_grid / get_default_state
+fluxes downstream, climt.SlabSurface, and climt.DryConvectiveAdjustment behind them; and what a model script needs to set the path up: get_grid / get_default_state
 (climt/_core/initialization.py), UpdateFrequencyWrapper and the AdamsBashforth tendency stepper."""
 import os as _os
 
@@ -15,6 +15,7 @@ _os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
 from ._lib import Context, RRTMGError  # noqa: F401,E402
 from .berger import BergerSolarInsolation  # noqa: F401,E402
 from .device_state import DeviceAdamsBashforth, DeviceQuantity, DeviceState  # noqa: F401,E402
+from .dry_convection import DryConvectiveAdjustment  # noqa: F401,E402
 from .initialization import get_default_state, get_grid  # noqa: F401,E402
 from .instellation import Instellation  # noqa: F401,E402
 from .rrtmg import RRTMGLongwave, RRTMGShortwave, radiation_step  # noqa: F401,E402
@@ -23,5 +24,5 @@ from .timestepping import AdamsBashforth  # noqa: F401,E402
 from .wrappers import UpdateFrequencyWrapper  # noqa: F401,E402
 from .intermittent import IntermittentLongwave, IntermittentShortwave  # noqa: F401,E402
 
-__all__ = ["RRTMGLongwave", "RRTMGShortwave", "Instellation", "BergerSolarInsolation", "SlabSurface", "get_grid", "get_default_state", "UpdateFrequencyWrapper", "IntermittentShortwave", "IntermittentLongwave", "AdamsBashforth",
+__all__ = ["RRTMGLongwave", "RRTMGShortwave", "Instellation", "BergerSolarInsolation", "SlabSurface", "DryConvectiveAdjustment", "get_grid", "get_default_state", "UpdateFrequencyWrapper", "IntermittentShortwave", "IntermittentLongwave", "AdamsBashforth",
            "Context", "RRTMGError", "DeviceState", "DeviceQuantity", "DeviceAdamsBashforth", "radiation_step"]

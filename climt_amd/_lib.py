@@ -177,6 +177,16 @@ class LwAdjust(C.Structure):
                 + [(n, _vp) for n in "uflx dflx duflx_dt uflxc dflxc duflxc_dt uflx_out hr_out uflxc_out hrc_out".split()])
 
 
+DRY_ADJUST_CONSTANTS = ("cpd", "cvap", "rd", "rv", "pref")
+
+
+class DryAdjust(C.Structure):
+    """mirrors `rrtmg_dry_adjust` (include/rrtmg_hip.h), field for field"""
+    _fields_ = ([("struct_size", C.c_uint32), ("ncol", _i32), ("nlay", _i32), ("memspace", _i32)]
+                + [(n, _vp) for n in ("t", "q", "pmid", "pint")] + [(n, _f64) for n in DRY_ADJUST_CONSTANTS]
+                + [(n, _vp) for n in ("t_out", "q_out", "mixed_top")])
+
+
 _lib = None
 
 
@@ -248,6 +258,8 @@ def load_library():
         lib.rrtmg_hip_scale_columns.argtypes = [_vp, C.c_int, _vp, _vp, C.c_int, C.POINTER(ScaleEntry)]
     if hasattr(lib, "rrtmg_hip_lw_adjust_surface"):         # (likewise: the longwave between radiation calls)
         lib.rrtmg_hip_lw_adjust_surface.argtypes = [_vp, C.POINTER(LwAdjust)]
+    if hasattr(lib, "rrtmg_hip_dry_adjustment"):            # (likewise: the dry convective adjustment)
+        lib.rrtmg_hip_dry_adjustment.argtypes = [_vp, C.POINTER(DryAdjust)]
     lib.rrtmg_hip_copy_blocks.argtypes =[_vp, C.c_int, _vp, C.c_long, C.c_long, _vp, _vp, _vp]
     lib.rrtmg_hip_mcica_mask.argtypes = [_vp] + [C.c_int] * 6 + [_vp] * 3
     _lib = lib
@@ -523,6 +535,50 @@ class Context:
             for name, v in zip(names, stream):
                 setattr(a, name, None if v is None else _device_pointer(v, f64, name))
         self._ck(self.lib.rrtmg_hip_lw_adjust_surface(self.h, C.byref(a)))
+
+    @property
+    def has_dry_adjustment(self):
+        """Whether the library exports the dry convective adjustment (rrtmg_hip_dry_adjustment; probed by the symbol)."""
+        return hasattr(self.lib, "rrtmg_hip_dry_adjustment")
+
+    @_locked
+    def dry_adjustment(self, t, q, pmid, pint, constants, t_out=None, q_out=None, mixed_top=None, memspace=0, ncol=None, nlay=None):
+        """climt's DryConvectiveAdjustment by column (rrtmg_hip_dry_adjustment) -> (t_out, q_out, mixed_top).  `constants`: cpd,
+        cvap, rd, rv and pref, pref in the units of the pressures.  Host arrays t, q, pmid [nlay][ncol] and pint [nlay+1][ncol]
+        (outputs are allocated unless given; t_out may be t, q_out may be q), or device pointers (or DeviceArrays) with
+        memspace=1 -- then `t_out`, `q_out`, `ncol` and `nlay`, one launch on the main stream; `mixed_top` (int32 [ncol]) is
+        written where given, and with host arrays always."""
+        if not self.has_dry_adjustment:
+            raise RRTMGError(4, "this librrtmg_hip.so has no rrtmg_hip_dry_adjustment (dry convective adjustment)")
+        a = DryAdjust()
+        a.struct_size, a.memspace = C.sizeof(DryAdjust), 1 if memspace else 0
+        for n in DRY_ADJUST_CONSTANTS:
+            setattr(a, n, float(constants[n]))
+        if memspace:
+            f64 = PRECISIONS["float64"]
+            if t_out is None or q_out is None or ncol is None or nlay is None:
+                raise ValueError("dry_adjustment: device pointers need t_out, q_out, ncol and nlay")
+            a.ncol, a.nlay = int(ncol), int(nlay)
+            for name, v in (("t", t), ("q", q), ("pmid", pmid), ("pint", pint), ("t_out", t_out), ("q_out", q_out)):
+                setattr(a, name, _device_pointer(v, f64, name))
+            if mixed_top is not None:
+                a.mixed_top = _device_pointer(mixed_top, np.dtype(np.int32), "mixed_top")
+            self._ck(self.lib.rrtmg_hip_dry_adjustment(self.h, C.byref(a)))
+            return t_out, q_out, mixed_top
+        t, q, pmid, pint = (np.ascontiguousarray(v, dtype=np.float64) for v in (t, q, pmid, pint))
+        if t.ndim != 2 or q.shape != t.shape or pmid.shape != t.shape or pint.shape != (t.shape[0] + 1, t.shape[1]):
+            raise ValueError("dry_adjustment: t, q, pmid must be [nlay][ncol] arrays of one shape and pint [nlay+1][ncol]")
+        t_out = np.empty(t.shape) if t_out is None else t_out
+        q_out = np.empty(t.shape) if q_out is None else q_out
+        mixed_top = np.empty(t.shape[1], dtype=np.int32) if mixed_top is None else mixed_top
+        for name, v, dtype in (("t_out", t_out, np.float64), ("q_out", q_out, np.float64), ("mixed_top", mixed_top, np.int32)):
+            if not (isinstance(v, np.ndarray) and v.dtype == dtype and v.flags.c_contiguous and v.size == (t.shape[1] if name == "mixed_top" else t.size)):
+                raise ValueError("dry_adjustment: %s is written in place: a C-contiguous %s array of the right size" % (name, np.dtype(dtype).name))
+        a.nlay, a.ncol = t.shape
+        a.t, a.q, a.pmid, a.pint = t.ctypes.data, q.ctypes.data, pmid.ctypes.data, pint.ctypes.data
+        a.t_out, a.q_out, a.mixed_top = t_out.ctypes.data, q_out.ctypes.data, mixed_top.ctypes.data
+        self._ck(self.lib.rrtmg_hip_dry_adjustment(self.h, C.byref(a)))
+        return t_out, q_out, mixed_top
 
     @_locked
     def solar_insolation(self, lat, lon, sin_delta, cos_delta, fractional_day, irradiance):

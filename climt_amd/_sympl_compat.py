@@ -12,7 +12,7 @@ outputs (last bullet).
 import numpy as np
 
 try:  # pragma: no cover - sympl is absent in the build container
-    from sympl import DataArray, DiagnosticComponent, TendencyComponent, get_constant, initialize_numpy_arrays_with_properties  # noqa: F401
+    from sympl import DataArray, DiagnosticComponent, Stepper, TendencyComponent, get_constant, initialize_numpy_arrays_with_properties  # noqa: F401
     HAVE_SYMPL = True
 except ImportError:
     HAVE_SYMPL = False
@@ -54,6 +54,11 @@ except ImportError:
         ("gas_constant_of_dry_air", "J kg^-1 K^-1"): 287.0,
         ("reference_air_pressure", "Pa"): 1.0132e5,
         ("top_of_model_pressure", "Pa"): 20.0,
+        # DryConvectiveAdjustment (dry_convection/component.py:67-73), under the unit strings it asks with
+        ("heat_capacity_of_dry_air_at_constant_pressure", "J/kg/degK"): 1004.64,
+        ("gas_constant_of_dry_air", "J/kg/degK"): 287.0,
+        ("heat_capacity_of_vapor_phase", "J/kg/K"): 1846.0,
+        ("gas_constant_of_vapor_phase", "J/kg/K"): 461.5,
     }
     _constant_overrides = {}
 
@@ -236,3 +241,20 @@ except ImportError:
         def __call__(self, state):
             raw = self._extract(state)
             return self._wrap(self.array_call(raw), self.diagnostic_properties)
+
+    class Stepper(TendencyComponent):
+        """sympl.Stepper stand-in: array_call(raw, timestep) -> (diagnostics, new state); the call returns
+        (diagnostics, new_state), the outputs in the units of `output_properties` and the dims of their inputs.  An input
+        known under an `alias` reaches array_call under that name as well."""
+        output_properties = {}
+
+        def __init__(self, name=None, **kwargs):
+            self.name = name or self.__class__.__name__.lower()
+
+        def __call__(self, state, timestep):
+            raw = self._extract(state)
+            for name, prop in self.input_properties.items():
+                if "alias" in prop and name in raw:
+                    raw[prop["alias"]] = raw[name]
+            diagnostics, new_state = self.array_call(raw, timestep)
+            return self._wrap(diagnostics, self.diagnostic_properties), self._wrap(new_state, self.output_properties)

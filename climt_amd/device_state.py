@@ -446,6 +446,31 @@ def slab_device_call(self, ds):
     return {"surface_temperature": tend}, {"depth_of_slab_surface": depth, "ocean_heat_transport_convergence": ds["ocean_heat_transport_convergence"]}
 
 
+def dry_adjustment_device_call(self, ds, timestep=None):
+    """DryConvectiveAdjustment on a DeviceState: rrtmg_hip_dry_adjustment with device pointers on the main stream.  The
+    pressures are read as they are resident -- in the units of whichever component asked for them first; only ratios and
+    differences of pressures enter, so the reference pressure is brought to THEIR units on the host.  The adjusted temperature
+    and humidity go to work buffers that alternate with the step count (the state's previous arrays stay what they were), and
+    the state is rebound to them: -> ({}, the same state)."""
+    P = self.input_properties
+    t, q = ds.need("air_temperature", P["air_temperature"]), ds.need("specific_humidity", P["specific_humidity"])
+    p, pi = ds["air_pressure"], ds["air_pressure_on_interface_levels"]
+    if tuple(p.dims) != ("mid_levels", "*") or tuple(pi.dims) != ("interface_levels", "*"):
+        raise ValueError("the pressures are resident as %s and %s, the adjustment wants [levels][*]" % (p.dims, pi.dims))
+    if not _same_units(p.units, pi.units):
+        raise ValueError("air_pressure is resident in %r, air_pressure_on_interface_levels in %r" % (p.units, pi.units))
+    nlay, ncol = t.shape
+    if p.shape != (nlay, ncol) or pi.shape != (nlay + 1, ncol) or q.shape != (nlay, ncol):
+        raise ValueError("temperature %s, humidity %s and pressures %s, %s do not belong to one grid" % (t.shape, q.shape, p.shape, pi.shape))
+    ds.join_streams()      # a longwave still in flight belongs to the step this adjustment closes
+    slot = ds.step_count & 1
+    t_new = ds.work(("dry", id(self), "t", slot), t.shape, t.dims, t.units)
+    q_new = ds.work(("dry", id(self), "q", slot), q.shape, q.dims, q.units)
+    ds.ctx.dry_adjustment(t.ptr, q.ptr, p.ptr, pi.ptr, self.constants(p.units), t_out=t_new.ptr, q_out=q_new.ptr, memspace=1, ncol=ncol, nlay=nlay)
+    ds["air_temperature"], ds["specific_humidity"] = t_new, q_new
+    return {}, ds
+
+
 # ---- time stepping on the device ------------------------------------------------------------------------------------
 _AB = {1: (1.0,), 2: (1.5, -0.5), 3: (23.0 / 12.0, -16.0 / 12.0, 5.0 / 12.0), 4: (55.0 / 24.0, -59.0 / 24.0, 37.0 / 24.0, -9.0 / 24.0)}
 

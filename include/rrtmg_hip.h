@@ -652,6 +652,36 @@ typedef struct {
 } rrtmg_lw_adjust;
 int rrtmg_hip_lw_adjust_surface(rrtmg_ctx *ctx, const rrtmg_lw_adjust *a);
 
+/* ---- dry convective adjustment: the step behind the radiation in a radiative-convective column ------------- */
+/* climt's DryConvectiveAdjustment (dry_convection/component.py), by column; level 0 is the surface.  ONE sweep k = nlay-1 .. 0:
+ *   theta_q[m] = t[m] * pow(pref / pmid[m], rd_cp[m]) * (1 + q[m] * (rv / rd) - q[m]),  rd_cp = (rd (1-q) + rv q) / (cpd (1-q) + cvap q)
+ *   scan m = k .. nlay-1 with the running sum of theta_q in that order: theta_avg = sum / (m - k + 1); the highest m > k with
+ *   theta_avg > theta_q[m] (strictly) is the top of the unstable run; where there is one, the layers k .. top are mixed:
+ *     mean_q     = sum(q dp) / (pint[k] - pint[top+1]),   dp[m] = pint[m] - pint[m+1]
+ *     cp_mixed   = cpd (1 - mean_q) + cvap mean_q,        rdcp_mixed = (rd (1 - mean_q) + rv mean_q) / cp_mixed
+ *     mean_theta = sum((cpd (1-q) + cvap q) t dp) / sum(cp_mixed pow(pmid / pref, rdcp_mixed) dp)
+ *     q[m] = mean_q,  t[m] = mean_theta * pow(pmid[m] / pref, rdcp_mixed)
+ * -- the reference's order of operations, every one rounded on its own; what one sweep leaves unadjusted stays so.  A column
+ * is one thread's: about 2 nlay pow and nlay^2 / 2 additions, whatever the profile.
+ * t, q, pmid [nlay][ncol] and pint [nlay+1][ncol] under memspace 0 (host) or 1 (device); pref in the units of pmid and pint
+ * (only ratios and differences of pressures enter).  t_out may be t and q_out may be q (in place); any other overlap of an
+ * output with an input or another output returns RRTMG_ERR_ARG, as do a struct_size other than sizeof(rrtmg_dry_adjust),
+ * ncol or nlay <= 0, a memspace other than 0 and 1, a NULL t, q, pmid, pint, t_out or q_out, and cpd, rd or pref <= 0 -- before
+ * anything is read or enqueued.  mixed_top (may be NULL): [ncol], the highest layer a mixing wrote, -1 where the column was
+ * left alone (its t_out, q_out then have the bits of t, q).  Needs neither rrtmg_hip_sw_init nor rrtmg_hip_lw_init.  Work space:
+ * two [nlay][ncol] arrays of the context.  Host pointers: four arrays go up, two (and mixed_top) come back.  Device pointers:
+ * one launch on the context's main stream; in deferred mode the call returns once enqueued.
+ * Probe for it by symbol; RRTMG_HIP_ABI_VERSION is unchanged. */
+typedef struct {
+  uint32_t struct_size; int32_t ncol, nlay, memspace;
+  const double *t, *q, *pmid;                         /* [nlay][ncol] */
+  const double *pint;                                 /* [nlay+1][ncol] */
+  double cpd, cvap, rd, rv, pref;
+  double *t_out, *q_out;                              /* [nlay][ncol]; t_out may be t, q_out may be q (in place) */
+  int32_t *mixed_top;                                 /* [ncol], or NULL */
+} rrtmg_dry_adjust;
+int rrtmg_hip_dry_adjustment(rrtmg_ctx *ctx, const rrtmg_dry_adjust *a);
+
 /* ---- reference-compatible entry points (host pointers, default context) ---------------- */
 int rrtmg_hip_default_status(void);
 const char *rrtmg_hip_default_error(void);

@@ -1,0 +1,153 @@
+"""The dry convective adjustment on the GPU: dry_adjust_kernel (rrtmg_hip_dry_adjustment) against the numpy statement
+(tests/dry_adjust_cases.py) on every case and shape, mixed_top exactly; what must hold bit for bit -- a stable column, in place,
+a block of columns alone, host against device pointers, the component on a DeviceState; and examples/radiative_convective.py in
+both modes.
+
+Values against the statement: X.TOL = 1e-12 relative.  Every case has a decision margin >= 1e-9, so no decision can differ; what
+remains is the device's pow against libm's and the rounded sums."""
+import datetime
+import importlib.util
+import os
+
+import numpy as np
+import pytest
+
+import climt_amd
+from climt_amd import _hip
+from climt_amd._sympl_compat import DataArray
+from helpers import ROOT, maxdiff
+
+import dry_adjust_cases as X
+
+pytestmark = pytest.mark.gpu
+
+
+@pytest.fixture(scope="module")
+def ctx():
+    from climt_amd.rrtmg.common import make_context
+    return make_context(0)
+
+
+def host_call(ctx, c, **kw):
+    return ctx.dry_adjustment(c["t"], c["q"], c["p"], c["p_int"], X.CONSTANTS, **kw)
+
+
+def device_call(ctx, t, q, p, p_int, in_place=False):
+    """Device pointers -> (t_new, q_new, mixed_top) on the host."""
+    nlay, ncol = t.shape
+    d = {k: _hip.DeviceArray.from_host(np.ascontiguousarray(v)) for k, v in (("t", t), ("q", q), ("p", p), ("p_int", p_int))}
+    t_out = d["t"] if in_place else _hip.DeviceArray((nlay, ncol))
+    q_out = d["q"] if in_place else _hip.DeviceArray((nlay, ncol))
+    top = _hip.DeviceArray((ncol,), np.int32)
+    ctx.dry_adjustment(d["t"], d["q"], d["p"], d["p_int"], X.CONSTANTS, t_out=t_out, q_out=q_out, mixed_top=top, memspace=1, ncol=ncol, nlay=nlay)
+    ctx.synchronize()
+    if not in_place:      # the inputs of an out-of-place call are only read
+        assert X.same_bits(d["t"].download(), t) and X.same_bits(d["q"].download(), q)
+    return t_out.download(), q_out.download(), top.download()
+
+
+@pytest.mark.parametrize("name", X.CASES)
+def test_kernel_equals_the_statement_on_every_shape(ctx, name):
+    worst = 0.0
+    for nlay in X.NLAYS:
+        for ncol in X.NCOLS:
+            c = X.case(name, nlay, ncol)
+            t, q, top = host_call(ctx, c)
+            assert top.dtype == np.int32 and (top == c["mixed_top"]).all(), (name, nlay, ncol)
+            err = X.rel_err(t, c["t_new"])
+            worst = max(worst, err)
+            assert err <= X.TOL, (name, nlay, ncol, err)
+            assert maxdiff(q, c["q_new"]) <= X.TOL * max(float(np.abs(c["q_new"]).max()), 1e-300), (name, nlay, ncol)
+    print("dry_adjust_kernel, %s: largest relative deviation of T from the statement %.3e" % (name, worst))
+
+
+def test_a_stable_column_keeps_its_bits(ctx):
+    for nlay, ncol in ((1, 1), (30, 65), (61, 130)):
+        c = X.case("stable", nlay, ncol)
+        t, q, top = host_call(ctx, c)
+        assert X.same_bits(t, c["t"]) and X.same_bits(q, c["q"]) and (top == -1).all()
+    # one stable column among unstable ones
+    c, s = X.case("whole_column", 30, 65), X.case("stable", 30, 65)
+    t_in, q_in = np.array(c["t"]), np.array(c["q"])
+    t_in[:, 17], q_in[:, 17] = s["t"][:, 17], s["q"][:, 17]
+    t, q, top = ctx.dry_adjustment(t_in, q_in, c["p"], c["p_int"], X.CONSTANTS)
+    assert top[17] == -1 and (np.delete(top, 17) == 29).all()
+    assert X.same_bits(t[:, 17], t_in[:, 17]) and X.same_bits(q[:, 17], q_in[:, 17])
+
+
+@pytest.mark.parametrize("name", ["two_runs", "cascade", "moist"])
+def test_in_place_host_and_device_pointers_agree_bit_for_bit(ctx, name):
+    for nlay, ncol in ((3, 1), (30, 130), (61, 65)):
+        c = X.case(name, nlay, ncol)
+        t, q, top = host_call(ctx, c)
+        # host arrays, in place
+        t_io, q_io = np.array(c["t"]), np.array(c["q"])
+        t2, q2, top2 = host_call(ctx, dict(c, t=t_io, q=q_io), t_out=t_io, q_out=q_io)
+        assert t2 is t_io and X.same_bits(t_io, t) and X.same_bits(q_io, q) and (top2 == top).all()
+        # device pointers, out of place and in place
+        for in_place in (False, True):
+            td, qd, topd = device_call(ctx, c["t"], c["q"], c["p"], c["p_int"], in_place)
+            assert X.same_bits(td, t) and X.same_bits(qd, q) and (topd == top).all(), (name, nlay, ncol, in_place)
+
+
+def test_a_block_of_columns_alone_equals_the_block_inside_the_whole(ctx):
+    for name in ("two_runs", "moist"):
+        c = X.case(name, 30, 130)
+        t, q, top = host_call(ctx, c)
+        for a, b in ((1, 2), (37, 101), (63, 130), (5, 69)):
+            part = [np.ascontiguousarray(c[k][:, a:b]) for k in ("t", "q", "p", "p_int")]
+            tp, qp, topp = ctx.dry_adjustment(*part, X.CONSTANTS)
+            assert X.same_bits(tp, t[:, a:b]) and X.same_bits(qp, q[:, a:b]) and (topp == top[a:b]).all(), (name, a, b)
+
+
+def _state(c, ny, nx):
+    """Pa throughout and [levels][lat][lon]: resident as the host path hands it to the library."""
+    box = lambda a: a.reshape(a.shape[0], ny, nx).copy()
+    return {"air_temperature": DataArray(box(c["t"]), dims=("mid_levels", "lat", "lon"), attrs={"units": "degK"}),
+            "specific_humidity": DataArray(box(c["q"]), dims=("mid_levels", "lat", "lon"), attrs={"units": "kg/kg"}),
+            "air_pressure": DataArray(box(c["p"]), dims=("mid_levels", "lat", "lon"), attrs={"units": "Pa"}),
+            "air_pressure_on_interface_levels": DataArray(box(c["p_int"]), dims=("interface_levels", "lat", "lon"), attrs={"units": "Pa"}),
+            "time": datetime.datetime(2000, 1, 1)}
+
+
+def test_component_on_a_device_state_equals_the_host_state_bit_for_bit(ctx):
+    c = X.case("cascade", 30, 65)
+    dry = climt_amd.DryConvectiveAdjustment(context=ctx)
+    dt = datetime.timedelta(minutes=10)
+    state = _state(c, 5, 13)
+    diagnostics, new_state = dry(state, dt)
+    assert diagnostics == {} and X.rel_err(new_state["air_temperature"].values.reshape(30, 65), c["t_new"]) <= X.TOL
+    with climt_amd.DeviceState.from_host(state, [dry], context=ctx) as ds:
+        before = ds["air_temperature"], ds["specific_humidity"]
+        diag_d, ds2 = dry(ds, dt)
+        assert diag_d == {} and ds2 is ds
+        assert ds["air_temperature"] is not before[0] and ds["specific_humidity"] is not before[1]      # rebound to work buffers
+        assert all(isinstance(ds[n], climt_amd.DeviceQuantity) for n in ("air_temperature", "specific_humidity"))
+        for name in ("air_temperature", "specific_humidity"):
+            got, want = ds.download(name), new_state[name]
+            assert got.dims == want.dims and got.attrs["units"] == want.attrs["units"]
+            assert X.same_bits(got.values, want.values), name
+        assert X.same_bits(before[0].buf.download().reshape(30, 65), c["t"])      # the previous arrays stay what they were
+        # a second call in the same step: the same buffers, in place; the adjusted column is left alone to rounding
+        dry(ds, dt)
+        assert X.rel_err(ds.download("air_temperature").values.reshape(30, 65), c["t_new"]) <= 1e-9
+
+
+def test_radiative_convective_example_in_both_modes():
+    """Three steps of examples/radiative_convective.py on a host state and on a DeviceState: the state of the two modes to the
+    tolerance of the radiative-equilibrium test of tests/test_gpu_parity.py; the adjustment has acted (the start is steeper
+    than the dry adiabat)."""
+    spec = importlib.util.spec_from_file_location("radiative_convective", os.path.join(ROOT, "examples", "radiative_convective.py"))
+    ex = importlib.util.module_from_spec(spec); spec.loader.exec_module(ex)
+    first_h, end_h = ex.run(3, device_resident=False)
+    first_d, end_d = ex.run(3, device_resident=True)
+    assert "upwelling_longwave_flux_in_air" in first_h and "depth_of_slab_surface" in first_d
+    for name in ("air_temperature", "specific_humidity", "surface_temperature"):
+        h, d = end_h[name], end_d[name]
+        g = np.transpose(d.values, [d.dims.index(x) for x in h.dims])
+        assert np.all(np.isfinite(h.values)) and maxdiff(h.values, g) <= 1e-9, (name, maxdiff(h.values, g))
+    t = end_h["air_temperature"].values.ravel()
+    p = end_h["air_pressure"].values.ravel()
+    theta = t * (1.0e5 / p) ** (287.0 / 1004.64)
+    assert np.diff(theta[:8]).min() > -0.05      # K per layer: the lower troposphere is no longer super-adiabatic (the start: -0.3)
+    assert float(end_h["surface_temperature"].values.ravel()[0]) != 300.0
