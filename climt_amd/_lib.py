@@ -187,6 +187,19 @@ class DryAdjust(C.Structure):
                 + [(n, _vp) for n in ("t_out", "q_out", "mixed_top")])
 
 
+BOUNDARY_LAYER_CONSTANTS = ("rd", "cp", "g", "lv", "karman", "z0", "fb", "p0", "ric")
+BOUNDARY_LAYER_IN = ("t", "q", "u", "v", "pmid", "pint", "ps", "ts", "qs", "sh_in", "lh_in")
+BOUNDARY_LAYER_OUT = ("t_out", "q_out", "u_out", "v_out")
+BOUNDARY_LAYER_DIAG = ("stress_north", "stress_east", "height", "sh_out", "lh_out")
+
+
+class BoundaryLayer(C.Structure):
+    """mirrors `rrtmg_boundary_layer` (include/rrtmg_hip.h), field for field"""
+    _fields_ = ([("struct_size", C.c_uint32), ("ncol", _i32), ("nlay", _i32), ("memspace", _i32), ("flux_mode", _i32)]
+                + [(n, _vp) for n in BOUNDARY_LAYER_IN] + [("dt", _f64)] + [(n, _f64) for n in BOUNDARY_LAYER_CONSTANTS]
+                + [("pressure_scale", _f64), ("ps_scale", _f64)] + [(n, _vp) for n in BOUNDARY_LAYER_OUT + BOUNDARY_LAYER_DIAG])
+
+
 _lib = None
 
 
@@ -260,6 +273,8 @@ def load_library():
         lib.rrtmg_hip_lw_adjust_surface.argtypes = [_vp, C.POINTER(LwAdjust)]
     if hasattr(lib, "rrtmg_hip_dry_adjustment"):            # (likewise: the dry convective adjustment)
         lib.rrtmg_hip_dry_adjustment.argtypes = [_vp, C.POINTER(DryAdjust)]
+    if hasattr(lib, "rrtmg_hip_boundary_layer"):            # (likewise: the simple boundary layer)
+        lib.rrtmg_hip_boundary_layer.argtypes = [_vp, C.POINTER(BoundaryLayer)]
     lib.rrtmg_hip_copy_blocks.argtypes =[_vp, C.c_int, _vp, C.c_long, C.c_long, _vp, _vp, _vp]
     lib.rrtmg_hip_mcica_mask.argtypes = [_vp] + [C.c_int] * 6 + [_vp] * 3
     _lib = lib
@@ -579,6 +594,68 @@ class Context:
         a.t_out, a.q_out, a.mixed_top = t_out.ctypes.data, q_out.ctypes.data, mixed_top.ctypes.data
         self._ck(self.lib.rrtmg_hip_dry_adjustment(self.h, C.byref(a)))
         return t_out, q_out, mixed_top
+
+    @property
+    def has_boundary_layer(self):
+        """Whether the library exports the simple boundary layer (rrtmg_hip_boundary_layer; probed by the symbol)."""
+        return hasattr(self.lib, "rrtmg_hip_boundary_layer")
+
+    @_locked
+    def boundary_layer(self, t, q, u, v, pmid, pint, ps, ts, qs, dt, constants, flux_mode, sh_in=None, lh_in=None, t_out=None, q_out=None,
+                       u_out=None, v_out=None, diagnostics=True, pressure_scale=1.0, ps_scale=1.0, memspace=0, ncol=None, nlay=None):
+        """climt's SimpleBoundaryLayer by column (rrtmg_hip_boundary_layer) -> (t_out, q_out, u_out, v_out, diagnostics).
+        `constants`: rd, cp, g, lv, karman, z0, fb, p0, ric; `flux_mode` 0 (no surface exchange), 1 (bulk) or 2 (external: the
+        prescribed `sh_in`, `lh_in`); `pressure_scale`, `ps_scale`: Pa per unit of pmid / pint and of ps.  Host arrays t, q, u, v,
+        pmid [nlay][ncol], pint [nlay+1][ncol], ps, ts, qs [ncol] (outputs are allocated unless given; each may be its own input),
+        `diagnostics` True: a dict of the five [ncol] arrays stress_north, stress_east, height, sh_out, lh_out (False or None:
+        none are asked for; a dict: those it names are written).  Or device pointers (or DeviceArrays) with memspace=1 -- then
+        the four outputs, `ncol` and `nlay`, and `diagnostics` a dict of device pointers or None; one launch on the main stream."""
+        if not self.has_boundary_layer:
+            raise RRTMGError(4, "this librrtmg_hip.so has no rrtmg_hip_boundary_layer (simple boundary layer)")
+        a = BoundaryLayer()
+        a.struct_size, a.memspace, a.flux_mode, a.dt = C.sizeof(BoundaryLayer), 1 if memspace else 0, int(flux_mode), float(dt)
+        a.pressure_scale, a.ps_scale = float(pressure_scale), float(ps_scale)
+        for n in BOUNDARY_LAYER_CONSTANTS:
+            setattr(a, n, float(constants[n]))
+        external = int(flux_mode) == 2
+        if external and (sh_in is None or lh_in is None):
+            raise ValueError("boundary_layer: flux_mode 2 (external) needs sh_in and lh_in")
+        given = dict(t=t, q=q, u=u, v=v, pmid=pmid, pint=pint, ps=ps, ts=ts, qs=qs)
+        if external:
+            given.update(sh_in=sh_in, lh_in=lh_in)
+        if memspace:
+            f64 = PRECISIONS["float64"]
+            if t_out is None or q_out is None or u_out is None or v_out is None or ncol is None or nlay is None:
+                raise ValueError("boundary_layer: device pointers need t_out, q_out, u_out, v_out, ncol and nlay")
+            a.ncol, a.nlay = int(ncol), int(nlay)
+            diagnostics = diagnostics if isinstance(diagnostics, dict) else {}
+            for name, x in list(given.items()) + [("t_out", t_out), ("q_out", q_out), ("u_out", u_out), ("v_out", v_out)] + list(diagnostics.items()):
+                if name not in BOUNDARY_LAYER_IN + BOUNDARY_LAYER_OUT + BOUNDARY_LAYER_DIAG:
+                    raise ValueError("boundary_layer: no diagnostic %r" % name)
+                setattr(a, name, _device_pointer(x, f64, name))
+            self._ck(self.lib.rrtmg_hip_boundary_layer(self.h, C.byref(a)))
+            return t_out, q_out, u_out, v_out, diagnostics
+        given = {n: np.ascontiguousarray(x, dtype=np.float64) for n, x in given.items()}
+        shape = given["t"].shape
+        if len(shape) != 2 or any(given[n].shape != shape for n in ("q", "u", "v", "pmid")) or given["pint"].shape != (shape[0] + 1, shape[1]):
+            raise ValueError("boundary_layer: t, q, u, v, pmid must be [nlay][ncol] arrays of one shape and pint [nlay+1][ncol]")
+        if any(x.shape != (shape[1],) for n, x in given.items() if n in ("ps", "ts", "qs", "sh_in", "lh_in")):
+            raise ValueError("boundary_layer: ps, ts, qs, sh_in and lh_in must be [ncol] arrays")
+        outs = {n: (np.empty(shape) if x is None else x) for n, x in (("t_out", t_out), ("q_out", q_out), ("u_out", u_out), ("v_out", v_out))}
+        if diagnostics is True:
+            diagnostics = {n: np.empty(shape[1]) for n in BOUNDARY_LAYER_DIAG}
+        elif not isinstance(diagnostics, dict):
+            diagnostics = {}
+        for name, x in list(outs.items()) + list(diagnostics.items()):
+            if name not in BOUNDARY_LAYER_OUT + BOUNDARY_LAYER_DIAG:
+                raise ValueError("boundary_layer: no diagnostic %r" % name)
+            if not (isinstance(x, np.ndarray) and x.dtype == np.float64 and x.flags.c_contiguous and x.size == (given["t"].size if name in outs else shape[1])):
+                raise ValueError("boundary_layer: %s is written in place: a C-contiguous float64 array of the right size" % name)
+        a.nlay, a.ncol = shape
+        for name, x in list(given.items()) + list(outs.items()) + list(diagnostics.items()):
+            setattr(a, name, x.ctypes.data)
+        self._ck(self.lib.rrtmg_hip_boundary_layer(self.h, C.byref(a)))
+        return outs["t_out"], outs["q_out"], outs["u_out"], outs["v_out"], diagnostics
 
     @_locked
     def solar_insolation(self, lat, lon, sin_delta, cos_delta, fractional_day, irradiance):

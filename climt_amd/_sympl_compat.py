@@ -59,6 +59,9 @@ except ImportError:
         ("gas_constant_of_dry_air", "J/kg/degK"): 287.0,
         ("heat_capacity_of_vapor_phase", "J/kg/K"): 1846.0,
         ("gas_constant_of_vapor_phase", "J/kg/K"): 461.5,
+        # SimpleBoundaryLayer (simple_boundary_layer/component.py:386-391), under the unit strings it asks with
+        ("gravitational_acceleration", "m s^-2"): 9.80665,
+        ("latent_heat_of_condensation", "J kg^-1"): 2.5e6,
     }
     _constant_overrides = {}
 
@@ -78,7 +81,7 @@ except ImportError:
         "kg kg^-1": "1", "g g^-1": "1", "mole/mole": "1", "micrometer": "um", "micron": "um", "µm": "um", "\xb5m": "um",
         "kg/m**2": "kg m^-2", "kg/m^2": "kg m^-2", "g/m^2": "g m^-2", "W/m^2": "W m^-2", "W/m**2": "W m^-2", "K/day": "K day^-1",
         "J/(degK*kg)": "J kg^-1 K^-1", "J kg^-1 degK^-1": "J kg^-1 K^-1", "J/kg/K": "J kg^-1 K^-1", "kg/m**3": "kg m^-3", "kg/m^3": "kg m^-3",
-        "degK day^-1": "K day^-1", "degK/day": "K day^-1", "radian": "radians", "rad": "radians",
+        "degK day^-1": "K day^-1", "degK/day": "K day^-1", "radian": "radians", "rad": "radians", "m/s": "m s^-1",
     }
     _TO_BASE = {"hPa": ("Pa", 100.0), "Pa": ("Pa", 1.0), "kPa": ("Pa", 1000.0), "kg m^-2": ("kg m^-2", 1.0), "g m^-2": ("kg m^-2", 1.e-3),
                 "K day^-1": ("K s^-1", 1.0 / 86400.0), "K s^-1": ("K s^-1", 1.0), "degK s^-1": ("K s^-1", 1.0),

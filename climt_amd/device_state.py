@@ -471,6 +471,52 @@ def dry_adjustment_device_call(self, ds, timestep=None):
     return {}, ds
 
 
+def boundary_layer_device_call(self, ds, timestep):
+    """SimpleBoundaryLayer on a DeviceState: rrtmg_hip_boundary_layer with device pointers on the main stream.  The pressures are
+    read as they are resident -- in the units of whichever component asked for them first; the rule needs Pa (densities), so the
+    library multiplies every pressure it reads by `pressure_scale` / `ps_scale`, Pa per resident unit: the one rounding the unit
+    conversion of the host path makes.  The four new profiles go to work buffers that alternate with the step count (the
+    state's previous arrays stay what they were) and the state is rebound to them; the diagnostics go to [ncol] work buffers,
+    which SlabSurface's device call can read as its flux inputs: -> (diagnostics as DeviceQuantity, the same state)."""
+    P = self.input_properties
+    names = ("air_temperature", "specific_humidity", "eastward_wind", "northward_wind")
+    t, q, u, v = (ds.need(n, P[n]) for n in names)
+    ts, qs = ds.need("surface_temperature", P["surface_temperature"]), ds.need("surface_specific_humidity", P["surface_specific_humidity"])
+    p, pi, ps = ds["air_pressure"], ds["air_pressure_on_interface_levels"], ds["surface_air_pressure"]
+    if tuple(p.dims) != ("mid_levels", "*") or tuple(pi.dims) != ("interface_levels", "*") or tuple(ps.dims) != ("*",):
+        raise ValueError("the pressures are resident as %s, %s and %s, the boundary layer wants [levels][*] and [*]" % (p.dims, pi.dims, ps.dims))
+    if not _same_units(p.units, pi.units):
+        raise ValueError("air_pressure is resident in %r, air_pressure_on_interface_levels in %r" % (p.units, pi.units))
+    nlay, ncol = t.shape
+    if any(x.shape != (nlay, ncol) for x in (q, u, v, p)) or pi.shape != (nlay + 1, ncol) or any(x.shape != (ncol,) for x in (ps, ts, qs)):
+        raise ValueError("temperature %s, humidity %s, winds %s, %s, pressures %s, %s and surface values %s, %s, %s do not belong to one grid" % (
+            t.shape, q.shape, u.shape, v.shape, p.shape, pi.shape, ps.shape, ts.shape, qs.shape))
+    fluxes = {}
+    if self._flux_mode == 2:
+        sh, lh = (ds.need(n, P[n]) for n in ("surface_upward_sensible_heat_flux", "surface_upward_latent_heat_flux"))
+        if sh.shape != (ncol,) or lh.shape != (ncol,):
+            raise ValueError("the prescribed surface fluxes %s, %s do not belong to the grid of %d columns" % (sh.shape, lh.shape, ncol))
+        fluxes = dict(sh_in=sh.ptr, lh_in=lh.ptr)
+    ds.join_streams()      # a longwave still in flight belongs to the step this component closes
+    slot = ds.step_count & 1
+    new = [ds.work(("bl", id(self), n, slot), x.shape, x.dims, x.units) for n, x in zip(names, (t, q, u, v))]
+    col = lambda key, units: ds.work(("bl", id(self), key, slot), (ncol,), ("*",), units)
+    d = dict(stress_north=col("stress_north", "Pa"), stress_east=col("stress_east", "Pa"), height=col("height", "m"))
+    if self._flux_mode == 1:
+        d.update(sh_out=col("sh", "W m^-2"), lh_out=col("lh", "W m^-2"))
+    to_pa = lambda units: float(_convert(np.float64(1.0), units, "Pa"))
+    ds.ctx.boundary_layer(t.ptr, q.ptr, u.ptr, v.ptr, p.ptr, pi.ptr, ps.ptr, ts.ptr, qs.ptr, timestep.total_seconds(), self.constants(),
+                          self._flux_mode, t_out=new[0].ptr, q_out=new[1].ptr, u_out=new[2].ptr, v_out=new[3].ptr,
+                          diagnostics={k: x.ptr for k, x in d.items()}, pressure_scale=to_pa(p.units), ps_scale=to_pa(ps.units),
+                          memspace=1, ncol=ncol, nlay=nlay, **fluxes)
+    for n, x in zip(names, new):
+        ds[n] = x
+    diagnostics = {"northward_wind_stress": d["stress_north"], "eastward_wind_stress": d["stress_east"], "boundary_layer_height": d["height"]}
+    if self._flux_mode == 1:
+        diagnostics.update(surface_upward_sensible_heat_flux=d["sh_out"], surface_upward_latent_heat_flux=d["lh_out"])
+    return diagnostics, ds
+
+
 # ---- time stepping on the device ------------------------------------------------------------------------------------
 _AB = {1: (1.0,), 2: (1.5, -0.5), 3: (23.0 / 12.0, -16.0 / 12.0, 5.0 / 12.0), 4: (55.0 / 24.0, -59.0 / 24.0, 37.0 / 24.0, -9.0 / 24.0)}
 

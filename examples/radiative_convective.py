@@ -8,7 +8,11 @@ package does not have: here the atmosphere feels the surface through the radiati
 the first step, the column starts on a lapse rate steeper than the dry adiabat (T ~ p^0.32) instead of the reference's
 isothermal 290 K.
 
-    python examples/radiative_convective.py [--steps 60] [--device-resident]
+    python examples/radiative_convective.py [--steps 60] [--device-resident] [--boundary-layer]
+
+--boundary-layer closes that gap: SimpleBoundaryLayer (bulk surface fluxes, implicit diffusion of T, q, u, v) steps after the time
+stepper and before the adjustment, and its two flux diagnostics go into the state, so the slab feels them from the next step
+on.  The state then carries a light wind and a surface humidity.  Without the flag the run is what it was.
 
 --device-resident keeps the state in HBM (climt_amd.DeviceState + DeviceAdamsBashforth; the adjustment reads and rebinds the
 resident temperature and humidity): same components, same numbers.  The longwave k-distribution tables of this build are
@@ -22,12 +26,13 @@ from datetime import timedelta
 import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from climt_amd import (AdamsBashforth, DryConvectiveAdjustment, RRTMGLongwave, RRTMGShortwave, SlabSurface, get_default_state,  # noqa: E402
-                       get_grid)
+from climt_amd import (AdamsBashforth, DryConvectiveAdjustment, RRTMGLongwave, RRTMGShortwave, SimpleBoundaryLayer, SlabSurface,  # noqa: E402
+                       get_default_state, get_grid)
 
 
-def run(steps=60, device_resident=False, report=None):
-    """-> (diagnostics of step 0, state after `steps` steps), both as host DataArrays."""
+def run(steps=60, device_resident=False, report=None, boundary_layer=False):
+    """-> (diagnostics of step 0, state after `steps` steps), both as host DataArrays.  `boundary_layer`: with SimpleBoundaryLayer
+    between the time stepper and the adjustment; its diagnostics of step 0 are then among the first."""
     rad_sw = RRTMGShortwave()
     rad_lw = RRTMGLongwave(allow_synthetic_tables=True)
     slab = SlabSurface()
@@ -35,9 +40,13 @@ def run(steps=60, device_resident=False, report=None):
     components = [rad_sw, rad_lw, slab]
     time_stepper = AdamsBashforth(components)
     timestep = timedelta(minutes=10)
+    steppers = [dry_convection]
+    if boundary_layer:
+        simple_boundary_layer = SimpleBoundaryLayer()
+        steppers = [simple_boundary_layer, dry_convection]
 
     grid = get_grid(nx=1, ny=1, nz=30)
-    state = get_default_state(components + [dry_convection], grid_state=grid)
+    state = get_default_state(components + steppers, grid_state=grid)
     p = state["air_pressure"].values
     state["air_temperature"].values[:] = np.maximum(210.0, 300.0 * (p / p.max()) ** 0.32)
     state["specific_humidity"].values[:] = 0.012 * (p / p.max()) ** 3
@@ -47,10 +56,13 @@ def run(steps=60, device_resident=False, report=None):
     state["surface_temperature"].values[:] = 300.0
     state["ocean_mixed_layer_thickness"].values[:] = 5.0
     state["area_type"].values[:] = "sea"
+    if boundary_layer:
+        state["eastward_wind"].values[:] = 5.0
+        state["surface_specific_humidity"].values[:] = 0.018
     to_host = lambda s, names=None: {k: s[k] for k in (names or s)}
     if device_resident:
         import climt_amd
-        state = climt_amd.DeviceState.from_host(state, components + [dry_convection])
+        state = climt_amd.DeviceState.from_host(state, components + steppers)
         time_stepper = climt_amd.DeviceAdamsBashforth(components)
         to_host = lambda s, names=None: {k: s.download(k) for k in (names or s) if k != "time"}
 
@@ -60,6 +72,13 @@ def run(steps=60, device_resident=False, report=None):
         state.update(diagnostics)
         if i == 0:
             first = to_host(state, list(diagnostics))
+
+        if boundary_layer:
+            diagnostics, new_state = simple_boundary_layer(state, timestep)
+            state.update(diagnostics)
+            state.update(new_state)
+            if i == 0:
+                first.update(to_host(state, list(diagnostics)))
 
         diagnostics, new_state = dry_convection(state, timestep)
         state.update(diagnostics)
@@ -76,6 +95,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--steps", type=int, default=60)
     ap.add_argument("--device-resident", action="store_true")
+    ap.add_argument("--boundary-layer", action="store_true")
     a = ap.parse_args()
 
     def report(i, state):
@@ -84,7 +104,7 @@ def main():
             i, state["surface_temperature"].values.ravel()[0], t[0], t[-1], state["upwelling_longwave_flux_in_air"].values.ravel()[-1],
             state["air_temperature_tendency_from_shortwave"].values.ravel()[-1],
             state["air_temperature_tendency_from_longwave"].values.ravel()[-1]))
-    run(a.steps, a.device_resident, report)
+    run(a.steps, a.device_resident, report, a.boundary_layer)
 
 
 if __name__ == "__main__":

@@ -682,6 +682,48 @@ typedef struct {
 } rrtmg_dry_adjust;
 int rrtmg_hip_dry_adjustment(rrtmg_ctx *ctx, const rrtmg_dry_adjust *a);
 
+/* ---- simple boundary layer: bulk surface fluxes and implicit diffusion, the atmosphere's side of the slab ---- */
+/* climt's SimpleBoundaryLayer (simple_boundary_layer/component.py with _core/tridiagonal.py), by column; level 0 is the surface,
+ * interface i (0 .. nlay-2) lies between the layers i and i+1 at pint[i+1].  In the reference's order of operations:
+ *   x_int = 0.5 (x[i+1] + x[i]);  rho[i] = pint[i+1] / (rd (1 + 0.608 q_int) t_int);
+ *   theta_v[i] = t_int pow(p0 / pint[i+1], rd / cp) (1 + 0.608 q_int), the surface's from ts, ps, qs;
+ *   z[i] = z[i-1] + (rd (1 + 0.608 q[i]) t[i] / g) log(pint[i] / pint[i+1]), the first term with ps;  wind[i] = max(|(u, v)_int|, 1)
+ *   Ri_a = g z[0] (theta_v[0] - theta_v_s) / (theta_v_s wind[0]^2);  C = karman^2 / log(z[0] / z0)^2 where Ri_a < 0, that times
+ *   (1 - Ri_a / ric)^2 where Ri_a < ric, else 0;  the top: the first i with g z[i] (theta_v[i] - theta_v[0]) / (theta_v[0] wind[i]^2) > ric,
+ *   count = i + 1 and h = z[i]; where there is none, count = 0 and h = z[nlay-2] (the reference's z[-1]): no layer diffuses, the
+ *   surface exchange still acts.  diff[i < count] by the K-profile: K_b(z) = karman wind[0] sqrt(C) z, damped by
+ *   1 + (Ri_a / ric) log(z / z0) / (1 - Ri_a / ric) where Ri_a > 0, below fb h; K_b(fb h) z / (fb h) (1 - (z - fb h) / ((1 - fb) h))^2 above.
+ *   Backward-Euler diffusion of t, q, u, v: off-diagonals g^2 rho^2 diff dt / dp_mid / dp_int, Thomas sweeps with divisions.
+ *   bulk = rho[0] C wind[0], beta = g bulk dt / (pint[0] - pint[1]).  flux_mode 0 (none): no surface term.  1 (bulk): beta on
+ *   diag[0] and beta ts, beta qs, 0, 0 on rhs[0].  2 (external): g dt sh_in / (cp dp0) and g dt lh_in / (lv dp0) on rhs[0] of t and
+ *   q; the winds keep beta on diag[0].  Diagnostics (each may be NULL): height = h, stress_north = bulk v_out[0], stress_east =
+ *   bulk u_out[0] (in every mode; advisory in mode 0), sh_out = cp bulk (ts - t_out[0]), lh_out = lv bulk (qs - q_out[0]).
+ * t and q share one matrix, u and v one; the elimination runs once per distinct matrix with all right-hand sides -- the same
+ * operands in the same order as four separate solves.  A column is one thread's: about nlay log and pow and 5 nlay divisions.
+ * Pressures: pmid and pint are read as p * pressure_scale, ps as ps * ps_scale -- Pa per unit of the arrays, 1.0 where they hold
+ * Pa (rho and the off-diagonals need Pa: the rule is not unit-free).  Arrays under memspace 0 (host) or 1 (device).  Each of
+ * t_out, q_out, u_out, v_out may be exactly its own input (in place); any other overlap of an output with an input or another
+ * output returns RRTMG_ERR_ARG, as do a NULL struct, a struct_size other than sizeof(rrtmg_boundary_layer), ncol <= 0, nlay < 2
+ * (the reference indexes an empty array with one layer), a memspace other than 0 and 1, a flux_mode outside 0 .. 2, a NULL input
+ * or profile output, a NULL sh_in or lh_in in mode 2 (they are ignored otherwise), a dt, constant or scale that is not positive,
+ * and fb outside (0, 1) -- before anything is read or enqueued.  Needs neither rrtmg_hip_sw_init nor rrtmg_hip_lw_init.  Work
+ * space: two [nlay-1][ncol] arrays of the context.  Host pointers: the inputs go up, the four profiles and the diagnostics asked
+ * for come back.  Device pointers: one launch on the context's main stream; in deferred mode the call returns once enqueued.
+ * Probe for it by symbol; RRTMG_HIP_ABI_VERSION is unchanged. */
+typedef struct {
+  uint32_t struct_size; int32_t ncol, nlay, memspace, flux_mode;
+  const double *t, *q, *u, *v, *pmid;                 /* [nlay][ncol] */
+  const double *pint;                                 /* [nlay+1][ncol] */
+  const double *ps, *ts, *qs;                         /* [ncol] */
+  const double *sh_in, *lh_in;                        /* [ncol]; required in mode 2, ignored otherwise */
+  double dt;
+  double rd, cp, g, lv, karman, z0, fb, p0, ric;
+  double pressure_scale, ps_scale;
+  double *t_out, *q_out, *u_out, *v_out;              /* [nlay][ncol]; each may be its own input (in place) */
+  double *stress_north, *stress_east, *height, *sh_out, *lh_out;   /* [ncol]; each may be NULL */
+} rrtmg_boundary_layer;
+int rrtmg_hip_boundary_layer(rrtmg_ctx *ctx, const rrtmg_boundary_layer *a);
+
 /* ---- reference-compatible entry points (host pointers, default context) ---------------- */
 int rrtmg_hip_default_status(void);
 const char *rrtmg_hip_default_error(void);
