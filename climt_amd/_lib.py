@@ -200,6 +200,20 @@ class BoundaryLayer(C.Structure):
                 + [("pressure_scale", _f64), ("ps_scale", _f64)] + [(n, _vp) for n in BOUNDARY_LAYER_OUT + BOUNDARY_LAYER_DIAG])
 
 
+EMANUEL_PARAMETERS = ("elcrit", "tlcrit", "entp", "sigd", "sigs", "omtrain", "omtsnow", "coeffr", "coeffs", "cu", "beta", "dtmax", "alpha", "damp", "delt0")
+EMANUEL_CONSTANTS = ("cpd", "cpv", "cl", "rv", "rd", "lv0", "g", "rowl")
+EMANUEL_IN = ("t", "q", "u", "v", "pmid", "pint", "cbmf", "qs")
+EMANUEL_OUT = ("ft", "fq", "fu", "fv")
+EMANUEL_DIAG = ("precip", "wd", "tprime", "qprime", "cape", "iflag", "ft_per_day")
+
+
+class Emanuel(C.Structure):
+    """mirrors `rrtmg_emanuel` (include/rrtmg_hip.h), field for field"""
+    _fields_ = ([("struct_size", C.c_uint32), ("ncol", _i32), ("nlay", _i32), ("memspace", _i32)] + [(n, _vp) for n in EMANUEL_IN]
+                + [("dt", _f64), ("pressure_scale", _f64), ("minorig", _i32), ("reserved", _i32)] + [(n, _f64) for n in EMANUEL_PARAMETERS + EMANUEL_CONSTANTS]
+                + [(n, _vp) for n in EMANUEL_OUT + EMANUEL_DIAG + ("cbmf_out",)])
+
+
 _lib = None
 
 
@@ -275,6 +289,8 @@ def load_library():
         lib.rrtmg_hip_dry_adjustment.argtypes = [_vp, C.POINTER(DryAdjust)]
     if hasattr(lib, "rrtmg_hip_boundary_layer"):            # (likewise: the simple boundary layer)
         lib.rrtmg_hip_boundary_layer.argtypes = [_vp, C.POINTER(BoundaryLayer)]
+    if hasattr(lib, "rrtmg_hip_emanuel_convection"):        # (likewise: the Emanuel convection scheme)
+        lib.rrtmg_hip_emanuel_convection.argtypes = [_vp, C.POINTER(Emanuel)]
     lib.rrtmg_hip_copy_blocks.argtypes =[_vp, C.c_int, _vp, C.c_long, C.c_long, _vp, _vp, _vp]
     lib.rrtmg_hip_mcica_mask.argtypes = [_vp] + [C.c_int] * 6 + [_vp] * 3
     _lib = lib
@@ -656,6 +672,73 @@ class Context:
             setattr(a, name, x.ctypes.data)
         self._ck(self.lib.rrtmg_hip_boundary_layer(self.h, C.byref(a)))
         return outs["t_out"], outs["q_out"], outs["u_out"], outs["v_out"], diagnostics
+
+    @property
+    def has_emanuel_convection(self):
+        """Whether the library exports the Emanuel convection scheme (rrtmg_hip_emanuel_convection; probed by the symbol)."""
+        return hasattr(self.lib, "rrtmg_hip_emanuel_convection")
+
+    @_locked
+    def emanuel_convection(self, t, q, u, v, pmid, pint, cbmf, dt, parameters, constants, qs=None, ft=None, fq=None, fu=None, fv=None, cbmf_out=None,
+                           diagnostics=True, pressure_scale=1.0, memspace=0, ncol=None, nlay=None):
+        """climt's EmanuelConvection by column (rrtmg_hip_emanuel_convection) -> (ft, fq, fu, fv, cbmf_out, diagnostics).
+        `parameters`: minorig and the fifteen scheme parameters (_lib.EMANUEL_PARAMETERS); `constants`: cpd, cpv, cl, rv, rd, lv0, g,
+        rowl; `pressure_scale`: hPa per unit of pmid / pint; `qs` None: the kernel forms the reference's bolton_q_sat.  Host arrays
+        t, q, u, v, pmid [nlay][ncol], pint [nlay+1][ncol], cbmf [ncol] (outputs are allocated unless given; cbmf_out may be cbmf);
+        `diagnostics` True: a dict of precip, wd, tprime, qprime, cape [ncol], iflag (int32) [ncol] and ft_per_day [nlay][ncol]
+        (False or None: none are asked for; a dict: those it names are written).  Or device pointers (or DeviceArrays) with
+        memspace=1 -- then the four tendencies, cbmf_out, `ncol` and `nlay`, and `diagnostics` a dict of device pointers or None; the
+        launches go to the main stream."""
+        if not self.has_emanuel_convection:
+            raise RRTMGError(4, "this librrtmg_hip.so has no rrtmg_hip_emanuel_convection (Emanuel convection scheme)")
+        a = Emanuel()
+        a.struct_size, a.memspace, a.dt, a.pressure_scale = C.sizeof(Emanuel), 1 if memspace else 0, float(dt), float(pressure_scale)
+        a.minorig = int(parameters["minorig"])
+        for n in EMANUEL_PARAMETERS:
+            setattr(a, n, float(parameters[n]))
+        for n in EMANUEL_CONSTANTS:
+            setattr(a, n, float(constants[n]))
+        given = dict(t=t, q=q, u=u, v=v, pmid=pmid, pint=pint, cbmf=cbmf)
+        if qs is not None:
+            given["qs"] = qs
+        if memspace:
+            f64 = PRECISIONS["float64"]
+            if ft is None or fq is None or fu is None or fv is None or cbmf_out is None or ncol is None or nlay is None:
+                raise ValueError("emanuel_convection: device pointers need ft, fq, fu, fv, cbmf_out, ncol and nlay")
+            a.ncol, a.nlay = int(ncol), int(nlay)
+            diagnostics = diagnostics if isinstance(diagnostics, dict) else {}
+            for name, x in list(given.items()) + [("ft", ft), ("fq", fq), ("fu", fu), ("fv", fv), ("cbmf_out", cbmf_out)] + list(diagnostics.items()):
+                if name not in EMANUEL_IN + EMANUEL_OUT + EMANUEL_DIAG + ("cbmf_out",):
+                    raise ValueError("emanuel_convection: no diagnostic %r" % name)
+                setattr(a, name, _device_pointer(x, np.dtype(np.int32) if name == "iflag" else f64, name))
+            self._ck(self.lib.rrtmg_hip_emanuel_convection(self.h, C.byref(a)))
+            return ft, fq, fu, fv, cbmf_out, diagnostics
+        given = {n: np.ascontiguousarray(x, dtype=np.float64) for n, x in given.items()}
+        shape = given["t"].shape
+        if len(shape) != 2 or any(given[n].shape != shape for n in ("q", "u", "v", "pmid", "qs") if n in given) or given["pint"].shape != (shape[0] + 1, shape[1]):
+            raise ValueError("emanuel_convection: t, q, u, v, pmid (and qs) must be [nlay][ncol] arrays of one shape and pint [nlay+1][ncol]")
+        if given["cbmf"].shape != (shape[1],):
+            raise ValueError("emanuel_convection: cbmf must be an [ncol] array")
+        outs = {n: (np.empty(shape) if x is None else x) for n, x in (("ft", ft), ("fq", fq), ("fu", fu), ("fv", fv))}
+        outs["cbmf_out"] = np.empty(shape[1]) if cbmf_out is None else cbmf_out
+        if diagnostics is True:
+            diagnostics = {n: np.empty(shape[1]) for n in EMANUEL_DIAG[:5]}
+            diagnostics.update(iflag=np.empty(shape[1], dtype=np.int32), ft_per_day=np.empty(shape))
+        elif not isinstance(diagnostics, dict):
+            diagnostics = {}
+        for name, x in list(outs.items()) + list(diagnostics.items()):
+            if name not in EMANUEL_OUT + EMANUEL_DIAG + ("cbmf_out",):
+                raise ValueError("emanuel_convection: no diagnostic %r" % name)
+            size = given["t"].size if name in EMANUEL_OUT + ("ft_per_day",) else shape[1]
+            if not (isinstance(x, np.ndarray) and x.dtype == (np.int32 if name == "iflag" else np.float64) and x.flags.c_contiguous and x.size == size):
+                raise ValueError("emanuel_convection: %s is written in place: a C-contiguous %s array of the right size" % (name, "int32" if name == "iflag" else "float64"))
+        a.nlay, a.ncol = shape
+        if outs["cbmf_out"] is cbmf_out and cbmf_out is cbmf:      # in place: the caller's own array, not the contiguous copy
+            given["cbmf"] = cbmf_out
+        for name, x in list(given.items()) + list(outs.items()) + list(diagnostics.items()):
+            setattr(a, name, x.ctypes.data)
+        self._ck(self.lib.rrtmg_hip_emanuel_convection(self.h, C.byref(a)))
+        return outs["ft"], outs["fq"], outs["fu"], outs["fv"], outs["cbmf_out"], diagnostics
 
     @_locked
     def solar_insolation(self, lat, lon, sin_delta, cos_delta, fractional_day, irradiance):

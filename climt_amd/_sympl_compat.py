@@ -12,7 +12,7 @@ outputs (last bullet).
 import numpy as np
 
 try:  # pragma: no cover - sympl is absent in the build container
-    from sympl import DataArray, DiagnosticComponent, Stepper, TendencyComponent, get_constant, initialize_numpy_arrays_with_properties  # noqa: F401
+    from sympl import DataArray, DiagnosticComponent, ImplicitTendencyComponent, Stepper, TendencyComponent, get_constant, initialize_numpy_arrays_with_properties  # noqa: F401
     HAVE_SYMPL = True
 except ImportError:
     HAVE_SYMPL = False
@@ -62,6 +62,13 @@ except ImportError:
         # SimpleBoundaryLayer (simple_boundary_layer/component.py:386-391), under the unit strings it asks with
         ("gravitational_acceleration", "m s^-2"): 9.80665,
         ("latent_heat_of_condensation", "J kg^-1"): 2.5e6,
+        # EmanuelConvection (emanuel/component.py:234-244), under the unit strings it asks with.  The last two are sympl's
+        # condensible-phase defaults (water): the reference's TestEmanuel caches are reproduced with them (tests/test_emanuel.py)
+        ("heat_capacity_of_vapor_phase", "J/kg/degK"): 1846.0,
+        ("gas_constant_of_vapor_phase", "J/kg/degK"): 461.5,
+        ("latent_heat_of_condensation", "J/kg"): 2.5e6,
+        ("density_of_liquid_phase", "kg/m^3"): 1000.0,
+        ("specific_enthalpy_of_vapor_phase", "J/kg"): 2500.0,
     }
     _constant_overrides = {}
 
@@ -244,6 +251,15 @@ except ImportError:
         def __call__(self, state):
             raw = self._extract(state)
             return self._wrap(self.array_call(raw), self.diagnostic_properties)
+
+    class ImplicitTendencyComponent(TendencyComponent):
+        """sympl.ImplicitTendencyComponent stand-in: array_call(raw, timestep) -> (tendencies, diagnostics); a tendency stepper
+        hands such a component the timestep."""
+
+        def __call__(self, state, timestep):
+            raw = self._extract(state)
+            tendencies, diagnostics = self.array_call(raw, timestep)
+            return self._wrap(tendencies, self.tendency_properties), self._wrap(diagnostics, self.diagnostic_properties)
 
     class Stepper(TendencyComponent):
         """sympl.Stepper stand-in: array_call(raw, timestep) -> (diagnostics, new state); the call returns

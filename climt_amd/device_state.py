@@ -93,7 +93,8 @@ class DeviceState(dict):
         props = {}
         for comp in components:
             comp = getattr(comp, "component", comp)          # UpdateFrequencyWrapper
-            for name, prop in comp.input_properties.items():
+            # (a component whose host layout is not the resident one -- EmanuelConvection is [*][levels] -- names the resident layout)
+            for name, prop in getattr(comp, "device_input_properties", comp.input_properties).items():
                 props.setdefault(name, prop)
         wild_names = wild_shape = None
         for name, prop in props.items():
@@ -517,12 +518,62 @@ def boundary_layer_device_call(self, ds, timestep):
     return diagnostics, ds
 
 
+def emanuel_device_call(self, ds, timestep):
+    """EmanuelConvection on a DeviceState: rrtmg_hip_emanuel_convection with device pointers on the main stream.  The profiles are
+    read as they are resident, [levels][*]; the pressures in the units of whichever component asked for them first -- the rule
+    needs hPa, so the library multiplies every pressure it reads by `pressure_scale`, hPa per resident unit: the one rounding the
+    unit conversion of the host path makes.  The saturation humidity is formed by the kernel.  Tendencies and diagnostics go to
+    work buffers that alternate with the step count and stay in HBM; cloud_base_mass_flux is rebound to the new array, as a
+    model script does with state.update(diagnostics): -> (tendencies, diagnostics) as DeviceQuantity."""
+    names = ("air_temperature", "specific_humidity", "eastward_wind", "northward_wind")
+    P = self.input_properties
+    t, q, u, v = (ds[n] for n in names)
+    p, pi, cb = ds["air_pressure"], ds["air_pressure_on_interface_levels"], ds.need("cloud_base_mass_flux", P["cloud_base_mass_flux"])
+    for n, x in zip(names + ("air_pressure",), (t, q, u, v, p)):
+        if tuple(x.dims) != ("mid_levels", "*"):
+            raise ValueError("quantity %r is resident as %s, the convection scheme wants [mid_levels][*]" % (n, x.dims))
+    for n, x in zip(names, (t, q, u, v)):
+        if not _same_units(x.units, P[n]["units"]):
+            raise ValueError("quantity %r is resident in %r, component wants %r" % (n, x.units, P[n]["units"]))
+    if tuple(pi.dims) != ("interface_levels", "*"):
+        raise ValueError("air_pressure_on_interface_levels is resident as %s, the convection scheme wants [interface_levels][*]" % (pi.dims,))
+    if not _same_units(p.units, pi.units):
+        raise ValueError("air_pressure is resident in %r, air_pressure_on_interface_levels in %r" % (p.units, pi.units))
+    nlay, ncol = t.shape
+    if any(x.shape != (nlay, ncol) for x in (q, u, v, p)) or pi.shape != (nlay + 1, ncol) or cb.shape != (ncol,):
+        raise ValueError("temperature %s, humidity %s, winds %s, %s, pressures %s, %s and mass flux %s do not belong to one grid" % (
+            t.shape, q.shape, u.shape, v.shape, p.shape, pi.shape, cb.shape))
+    ds.join_streams()      # a longwave still in flight may be reading the profiles' neighbours on its own stream; the sums follow on the main one
+    slot = ds.step_count & 1
+    T = self.tendency_properties
+    tend = {n: ds.work(("emanuel", id(self), n, slot), (nlay, ncol), ("mid_levels", "*"), T[n]["units"]) for n in names}
+    D = self.diagnostic_properties
+    col = lambda key, name, dtype=np.float64: ds.work(("emanuel", id(self), key, slot), (ncol,), ("*",), D[name]["units"], dtype)
+    d = dict(precip=col("precip", "convective_precipitation_rate"), wd=col("wd", "convective_downdraft_velocity_scale"),
+             tprime=col("tprime", "convective_downdraft_temperature_scale"), qprime=col("qprime", "convective_downdraft_specific_humidity_scale"),
+             cape=col("cape", "atmosphere_convective_available_potential_energy"), iflag=col("iflag", "convective_state", np.int32),
+             ft_per_day=ds.work(("emanuel", id(self), "ft_per_day", slot), (nlay, ncol), ("mid_levels", "*"), "degK day^-1"))
+    cb_new = col("cbmf", "cloud_base_mass_flux")
+    ds.ctx.emanuel_convection(t.ptr, q.ptr, u.ptr, v.ptr, p.ptr, pi.ptr, cb.ptr, timestep.total_seconds(), self.parameters(), self.constants(),
+                              ft=tend[names[0]].ptr, fq=tend[names[1]].ptr, fu=tend[names[2]].ptr, fv=tend[names[3]].ptr, cbmf_out=cb_new.ptr,
+                              diagnostics={k: x.ptr for k, x in d.items()}, pressure_scale=float(_convert(np.float64(1.0), p.units, "hPa")),
+                              memspace=1, ncol=ncol, nlay=nlay)
+    ds["cloud_base_mass_flux"] = cb_new
+    diagnostics = {"convective_state": d["iflag"], "convective_precipitation_rate": d["precip"], "convective_downdraft_velocity_scale": d["wd"],
+                   "convective_downdraft_temperature_scale": d["tprime"], "convective_downdraft_specific_humidity_scale": d["qprime"],
+                   "cloud_base_mass_flux": cb_new, "atmosphere_convective_available_potential_energy": d["cape"],
+                   "air_temperature_tendency_from_convection": d["ft_per_day"]}
+    return tend, diagnostics
+
+
 # ---- time stepping on the device ------------------------------------------------------------------------------------
 _AB = {1: (1.0,), 2: (1.5, -0.5), 3: (23.0 / 12.0, -16.0 / 12.0, 5.0 / 12.0), 4: (55.0 / 24.0, -59.0 / 24.0, 37.0 / 24.0, -9.0 / 24.0)}
 
 
 def _rate(units):
     u = units.strip()
+    if u in ("m s^-2", "m/s^2"):      # an acceleration is the rate of a speed
+        return 1.0
     for suffix, seconds in ((" s^-1", 1.0), ("/s", 1.0), (" day^-1", 86400.0), ("/day", 86400.0)):
         if u.endswith(suffix):
             return 1.0 / seconds
@@ -559,7 +610,8 @@ class DeviceAdamsBashforth:
         # beside it), then the sums in component order
         results = []
         for comp in self.component_list:
-            tend, diag = comp(ds)
+            # an ImplicitTendencyComponent (EmanuelConvection) is handed the timestep, as sympl's tendency steppers do
+            tend, diag = comp(ds, timestep) if isinstance(comp, _sc.ImplicitTendencyComponent) else comp(ds)
             overlap = set(diag) & set(diagnostics)
             if overlap:
                 raise ValueError("two components compute the same diagnostics: %s" % sorted(overlap))

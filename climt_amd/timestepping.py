@@ -20,6 +20,9 @@ except ImportError:
     def _per_second(units, state_units):
         """Factor taking a tendency in `units` to state_units s^-1 ('K day^-1' for a state in degK -> 1/86400)."""
         u = _sc._canon(units)
+        if u in ("m s^-2", "m/s^2"):      # an acceleration (EmanuelConvection's wind tendencies) is the rate of a speed
+            _sc.convert_units(np.zeros(()), "m s^-1", state_units)
+            return 1.0
         for suffix, seconds in ((" s^-1", 1.0), ("/s", 1.0), (" day^-1", 86400.0), ("/day", 86400.0)):
             if u.endswith(suffix):
                 base = u[:-len(suffix)].strip()
@@ -43,10 +46,11 @@ except ImportError:
             from .initialization import aggregate_input_properties
             return aggregate_input_properties(self.component_list)
 
-        def _tendencies(self, state):
+        def _tendencies(self, state, timestep=None):
             total, diagnostics = {}, {}
             for comp in self.component_list:
-                tend, diag = comp(state)
+                # an ImplicitTendencyComponent (EmanuelConvection) is handed the timestep, as sympl's tendency steppers do
+                tend, diag = comp(state, timestep) if isinstance(comp, _sc.ImplicitTendencyComponent) else comp(state)
                 overlap = set(diag) & set(diagnostics)
                 if overlap:
                     raise ValueError("two components compute the same diagnostics: %s" % sorted(overlap))
@@ -65,7 +69,7 @@ except ImportError:
                 self._timestep = timestep
             elif timestep != self._timestep:
                 raise ValueError("timestep must be constant for Adams-Bashforth time stepping")
-            tend, diagnostics = self._tendencies(state)
+            tend, diagnostics = self._tendencies(state, timestep)
             self._history = [tend] + self._history[: self._order - 1]
             weights = _AB[len(self._history)]
             dt = timestep.total_seconds()

@@ -3,16 +3,22 @@
 the dry convective adjustment -- the arrangement of the reference's examples/column_code_with_slab.py with
 `from climt_amd import ...`: one column of 30 levels, dt = 10 min, a 5 m ocean mixed layer at 300 K under a fixed sun.
 
-The reference's example also couples the column to the surface with SimplePhysics (and carries EmanuelConvection), which this
-package does not have: here the atmosphere feels the surface through the radiation alone.  So that the adjustment has work from
+The reference's example also couples the column to the surface with SimplePhysics, which this package does not have, and carries
+EmanuelConvection in the time stepper's list (--moist-convection below): by default the atmosphere feels the surface through the
+radiation alone and stays dry.  So that the adjustment has work from
 the first step, the column starts on a lapse rate steeper than the dry adiabat (T ~ p^0.32) instead of the reference's
 isothermal 290 K.
 
-    python examples/radiative_convective.py [--steps 60] [--device-resident] [--boundary-layer]
+    python examples/radiative_convective.py [--steps 60] [--device-resident] [--boundary-layer] [--moist-convection]
 
 --boundary-layer closes that gap: SimpleBoundaryLayer (bulk surface fluxes, implicit diffusion of T, q, u, v) steps after the time
 stepper and before the adjustment, and its two flux diagnostics go into the state, so the slab feels them from the next step
 on.  The state then carries a light wind and a surface humidity.  Without the flag the run is what it was.
+
+--moist-convection puts EmanuelConvection into the AdamsBashforth list, as the reference's example has it
+(AdamsBashforth([rad_sw, rad_lw, slab, convection])): what the column holds of water condenses and rains out, the cloud-base mass
+flux is carried from step to step, and the precipitation joins the report.  The column then starts moister (80 % of saturation
+near the surface).  Without the flag the run is what it was.
 
 --device-resident keeps the state in HBM (climt_amd.DeviceState + DeviceAdamsBashforth; the adjustment reads and rebinds the
 resident temperature and humidity): same components, same numbers.  The longwave k-distribution tables of this build are
@@ -26,18 +32,21 @@ from datetime import timedelta
 import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from climt_amd import (AdamsBashforth, DryConvectiveAdjustment, RRTMGLongwave, RRTMGShortwave, SimpleBoundaryLayer, SlabSurface,  # noqa: E402
+from climt_amd import (AdamsBashforth, DryConvectiveAdjustment, EmanuelConvection, RRTMGLongwave, RRTMGShortwave, SimpleBoundaryLayer, SlabSurface,  # noqa: E402
                        get_default_state, get_grid)
 
 
-def run(steps=60, device_resident=False, report=None, boundary_layer=False):
+def run(steps=60, device_resident=False, report=None, boundary_layer=False, moist_convection=False):
     """-> (diagnostics of step 0, state after `steps` steps), both as host DataArrays.  `boundary_layer`: with SimpleBoundaryLayer
-    between the time stepper and the adjustment; its diagnostics of step 0 are then among the first."""
+    between the time stepper and the adjustment; its diagnostics of step 0 are then among the first.  `moist_convection`: with
+    EmanuelConvection in the time stepper's list."""
     rad_sw = RRTMGShortwave()
     rad_lw = RRTMGLongwave(allow_synthetic_tables=True)
     slab = SlabSurface()
     dry_convection = DryConvectiveAdjustment()
     components = [rad_sw, rad_lw, slab]
+    if moist_convection:
+        components = components + [EmanuelConvection()]
     time_stepper = AdamsBashforth(components)
     timestep = timedelta(minutes=10)
     steppers = [dry_convection]
@@ -56,6 +65,10 @@ def run(steps=60, device_resident=False, report=None, boundary_layer=False):
     state["surface_temperature"].values[:] = 300.0
     state["ocean_mixed_layer_thickness"].values[:] = 5.0
     state["area_type"].values[:] = "sea"
+    if moist_convection:
+        t = state["air_temperature"].values
+        es = 611.2 * np.exp(17.67 * (t - 273.15) / (t - 29.65))
+        state["specific_humidity"].values[:] = 0.8 * 0.622 * es / (p - 0.378 * es) * (p / p.max()) ** 1.5
     if boundary_layer:
         state["eastward_wind"].values[:] = 5.0
         state["surface_specific_humidity"].values[:] = 0.018
@@ -96,15 +109,17 @@ def main():
     ap.add_argument("--steps", type=int, default=60)
     ap.add_argument("--device-resident", action="store_true")
     ap.add_argument("--boundary-layer", action="store_true")
+    ap.add_argument("--moist-convection", action="store_true")
     a = ap.parse_args()
 
     def report(i, state):
         t = state["air_temperature"].values.ravel()
-        print("step %4d  T(surface) %8.3f K  T(surface layer) %8.3f K  T(top) %8.3f K  OLR %8.3f  SW heating(top) %7.3f K/day  LW heating(top) %8.3f K/day" % (
+        rain = "  precipitation %8.3f mm/day" % state["convective_precipitation_rate"].values.ravel()[0] if a.moist_convection else ""
+        print("step %4d  T(surface) %8.3f K  T(surface layer) %8.3f K  T(top) %8.3f K  OLR %8.3f  SW heating(top) %7.3f K/day  LW heating(top) %8.3f K/day%s" % (
             i, state["surface_temperature"].values.ravel()[0], t[0], t[-1], state["upwelling_longwave_flux_in_air"].values.ravel()[-1],
             state["air_temperature_tendency_from_shortwave"].values.ravel()[-1],
-            state["air_temperature_tendency_from_longwave"].values.ravel()[-1]))
-    run(a.steps, a.device_resident, report, a.boundary_layer)
+            state["air_temperature_tendency_from_longwave"].values.ravel()[-1], rain))
+    run(a.steps, a.device_resident, report, a.boundary_layer, a.moist_convection)
 
 
 if __name__ == "__main__":

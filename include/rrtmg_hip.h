@@ -724,6 +724,64 @@ typedef struct {
 } rrtmg_boundary_layer;
 int rrtmg_hip_boundary_layer(rrtmg_ctx *ctx, const rrtmg_boundary_layer *a);
 
+/* ---- Emanuel moist convection: what condenses and rains out the water the boundary layer brings up ---- */
+/* climt's EmanuelConvection (emanuel/component.py around convect43c.f90), by column, in the order of operations of the reference's
+ * numpy statement emanuel/pure_python.py (_convect, _tlift); level 0 is the surface.  The component's configuration: IPBL = 0 (no
+ * dry-adjustment block), no tracers, NL = nlay - 3, MINORIG = minorig.  With P = pmid * pressure_scale and PH = pint * pressure_scale
+ * in hPa:
+ *   GZ, CPN, H, LV, HM, TV of the levels 0 .. NL; IHMIN = the level >= minorig - 1 of minimum HM below its lower neighbour's, capped
+ *   at NL - 1; NK = the level of maximum HM in minorig - 1 .. IHMIN.  iflag 0, cbmf_out = 0: t[NK] < 250, q[NK] <= 0 or IHMIN == NL - 1.
+ *   RH = q[NK] / qs[NK], CHI = t[NK] / (1669 - 122 RH - t[NK]), PLCL = P[NK] pow(RH, CHI).  iflag 2, cbmf_out = 0: PLCL < 200 or
+ *   PLCL >= 2000.  ICB = the first level above NK with P < PLCL, at most NL - 1.  iflag 3, cbmf_out = 0: ICB >= NL - 1.
+ *   The parcel of NK lifted to ICB: a dry adiabat below, at ICB two Newton steps on saturation with es = 6.112 exp(17.67 tc /
+ *   (243.5 + tc)) where tc >= 0 and exp(23.33086 - 6111.72784 / T + 0.15215 log T) below.  iflag 0, cbmf_out = cbmf UNTOUCHED:
+ *   cbmf == 0 and TVP[ICB] <= TV[ICB] - dtmax.  Otherwise iflag 1: the parcel lifted to NL; the precipitation efficiency from elcrit and
+ *   tlcrit; the level of neutral buoyancy INB, cape, FRAC; cbmf_out = max((1 - damp dt / delt0) cbmf + 0.1 alpha DTMA, 0), DTMA the
+ *   sub-cloud buoyancy excess.  cbmf_out == 0 and cbmf == 0: iflag 1 with zero tendencies.  Otherwise the mass fluxes M[ICB+1 .. INB], the
+ *   mixing fractions SIJ of every origin i and destination j in ICB .. INB (a denominator of magnitude below 0.01 is set to 0.01) and,
+ *   where 0 < SIJ < 0.9, the entrained q, u, v, condensate and mass (QENT, UENT, VENT, ELIJ, MENT), normalised over the spectrum of
+ *   every origin; where EP[INB] >= 1e-4 the unsaturated downdraft (rain above 273 K with omtrain, coeffr; snow with omtsnow, coeffs;
+ *   area sigd, fraction outside the cloud sigs) and precip; wd, tprime, qprime; the tendencies of the levels 0 .. INB, iflag 4 where a
+ *   mass flux violates 2 g (0.01 / dPH) AMP1 < 1 / dt; the dp-weighted means of cpn ft + lv fq, fu and fv subtracted; fu, fv times
+ *   1 - cu.  Every operation is rounded on its own; the rule is reproduced with its quirks, not improved.
+ * A column is one thread's: O((INB - ICB)^2) work where it convects, one pass over the levels where it leaves early.
+ * t, q, u, v, pmid [nlay][ncol], pint [nlay+1][ncol] and cbmf [ncol] under memspace 0 (host) or 1 (device).  pressure_scale: hPa per
+ * unit of pmid and pint -- 1.0 for mbar, 0.01 for Pa (the 1000 hPa of the LCL, the PLCL limits and the downdraft constants make the
+ * rule not unit-free).  qs [nlay][ncol] may be NULL: the kernel then forms the reference's bolton_q_sat(t, 100 P, rd, rv) =
+ * (rd / rv) es / (100 P - (1 - rd / rv) es), es = 611.2 exp(17.67 (t - 273.15) / (t - 29.65)).
+ * Outputs: ft [K/s], fq [1/s], fu, fv [m/s^2] [nlay][ncol], zero above INB and where nothing convects; cbmf_out [ncol], which may be
+ * exactly cbmf (in place).  Each of precip [mm/day], wd [m/s], tprime [K], qprime, cape [J/kg] [ncol], iflag (int32) [ncol] and
+ * ft_per_day [nlay][ncol] (= 86400 ft) may be NULL.  Any overlap of an output with an input or another output other than cbmf_out ==
+ * cbmf returns RRTMG_ERR_ARG, as do a NULL struct, a struct_size other than sizeof(rrtmg_emanuel), ncol <= 0, nlay < 4 (NL >= 1: the
+ * cap NL - 1 of IHMIN must be a level; with fewer than 6 layers every column leaves by one of the first exits), a memspace other than
+ * 0 and 1, a NULL t, q, u, v, pmid, pint, cbmf, ft, fq, fu, fv or cbmf_out, a dt, pressure_scale, cpd, rd, rv or g that is not positive,
+ * minorig < 1 and cu, sigd or sigs outside [0, 1] (the reference's ValueError) -- before anything is read or enqueued.  Needs neither
+ * rrtmg_hip_sw_init nor rrtmg_hip_lw_init.
+ * Work space, of the context: 8 (22 (nlay + 1) + 6 (nlay - 4) (nlay - 3)) bytes per column -- 22 one-dimensional slabs and the six
+ * two-dimensional ones cut to the origins 2 .. NL and destinations 1 .. NL that can ever be written; 169 600 bytes per column at 61
+ * layers.  It is sized per chunk of whole 64-column tiles against the context's scratch budget (RRTMG_HIP_MAX_SCRATCH_BYTES, default an
+ * eighth of the device's memory; RRTMG_HIP_CHUNK_TILES, where given, caps the chunk too) and re-used by the chunks, one launch each;
+ * results do not depend on the chunking.  Host pointers: the inputs go up, the tendencies, cbmf_out and the diagnostics asked for
+ * come back.  Device pointers: the launches go to the context's main stream; in deferred mode the call returns once enqueued.
+ * Probe for it by symbol; RRTMG_HIP_ABI_VERSION is unchanged. */
+typedef struct {
+  uint32_t struct_size; int32_t ncol, nlay, memspace;
+  const double *t, *q, *u, *v, *pmid;                 /* [nlay][ncol] */
+  const double *pint;                                 /* [nlay+1][ncol] */
+  const double *cbmf;                                 /* [ncol] */
+  const double *qs;                                   /* [nlay][ncol], or NULL: formed by the kernel */
+  double dt, pressure_scale;
+  int32_t minorig, reserved;                          /* reserved: 0 */
+  double elcrit, tlcrit, entp, sigd, sigs, omtrain, omtsnow, coeffr, coeffs, cu, beta, dtmax, alpha, damp, delt0;
+  double cpd, cpv, cl, rv, rd, lv0, g, rowl;
+  double *ft, *fq, *fu, *fv;                          /* [nlay][ncol] */
+  double *precip, *wd, *tprime, *qprime, *cape;       /* [ncol]; each may be NULL */
+  int32_t *iflag;                                     /* [ncol], or NULL */
+  double *ft_per_day;                                 /* [nlay][ncol], or NULL */
+  double *cbmf_out;                                   /* [ncol]; may be cbmf (in place) */
+} rrtmg_emanuel;
+int rrtmg_hip_emanuel_convection(rrtmg_ctx *ctx, const rrtmg_emanuel *a);
+
 /* ---- reference-compatible entry points (host pointers, default context) ---------------- */
 int rrtmg_hip_default_status(void);
 const char *rrtmg_hip_default_error(void);

@@ -1,0 +1,435 @@
+"""The Emanuel convection scheme without a GPU: the exported symbol, the header and the ctypes layer; the property dictionaries and
+the constructor; the argument checks of the C entry; the stand-alone host program of the column rule (tools/emanuel_check.cpp on
+csrc/rrtmg_emanuel.h) against fixtures made by the reference's own numpy statement (tests/golden/make_emanuel_golden.py) -- once
+more under the host sanitizers; the budgets that pin the rule; climt_amd.EmanuelConvection on host states, the host program standing
+in for the context; and AdamsBashforth with an implicit component in its list.
+
+Host program against the fixtures, largest deviation over every case x nlay (g++ -O1, glibc): 9.1e-16 of the column's largest
+magnitude of the field (sheared, 61 layers, fu; last-place: the same IEEE sequence, numpy's exp and log against glibc's), at most
+8.2e-3 of a tolerance (the fixtures' tolerances are 1e-13 .. 2.5e-10); 26 of 35 fixtures bit-identical.
+Not produced by the maker: flag_only at nlay 8 (fewer than three robust columns in 3000 candidates)."""
+import ctypes as C
+import datetime
+import inspect
+import os
+import re
+import subprocess
+
+import numpy as np
+import pytest
+
+import climt_amd
+from climt_amd import _lib
+from climt_amd import _sympl_compat as sc
+from climt_amd._sympl_compat import DataArray
+from helpers import GOLDEN, ROOT, load_cache_case
+
+import emanuel_cases as X
+
+SYMBOL = "rrtmg_hip_emanuel_convection"
+MISSING = {("flag_only", 8)}      # what the maker could not produce
+FIXTURES = [(case, nlay) for case in X.CASES for nlay in X.NLAYS if (case, nlay) not in MISSING]
+IN = ("t", "q", "u", "v", "pmid", "pint", "cbmf", "qs")
+OUT = ("ft", "fq", "fu", "fv")
+DIAG = ("precip", "wd", "tprime", "qprime", "cape", "iflag", "ft_per_day")
+PARAMETERS = X.PARAMETER_NAMES[1:]
+
+
+def test_the_fixture_set_shows_every_required_situation():
+    assert sorted(f for f in os.listdir(GOLDEN) if f.startswith("emanuel_") and f.endswith(".npz")) == sorted("emanuel_%s_%d.npz" % k for k in FIXTURES)
+    for case, nlay in FIXTURES:
+        f = X.load(case, nlay)
+        assert f["t"].shape == (nlay, 3) and f["ph"].shape == (nlay + 1, 3) and f["cbmf"].shape == (3,)
+        assert X.parameters(f) == X.PARAMETERS and X.constants(f) == X.CONSTANTS
+        flag, zero = f["ref_iflag"], np.array([not any(f["ref_" + n][:, c].any() for n in X.PROFILES) for c in range(3)])
+        want = dict(no_origin=0, too_cold=0, lcl_range=2, base_at_top=3, deep=1, flag_only=1, cfl=4, freezing=1, sheared=1)[case]
+        assert (flag == want).all(), (case, nlay, flag)
+        for n in X.FIELDS:
+            assert 1e-13 <= float(f["tol_" + n]) <= 16e-9 and float(f["tol_" + n]) == max(16.0 * float(f["dev_" + n]), 1e-13)
+        if case == "no_origin":
+            assert (f["cbmf"] > 0).all() and (f["ref_cbmf_out"] == 0).all()
+        if case in ("too_cold", "flag_only", "sheared"):
+            assert (f["cbmf"] == 0).all()
+        if case in ("too_cold", "flag_only"):
+            assert (f["ref_cbmf_out"] == 0).all()
+        if want in (0, 2, 3) or case == "flag_only":
+            assert zero.all() and (f["ref_precip"] == 0).all()
+        if case == "deep":
+            assert (f["ref_precip"] > 0).all() and (f["ref_wd"] > 0).all()
+        if case == "sheared":
+            assert f["ref_fu"].any(axis=0).all() and f["ref_fv"].any(axis=0).all()
+        if case == "freezing":
+            for c in range(3):
+                live = f["ref_fq"][:, c] != 0
+                assert f["t"][live, c].max() > 273.0 > f["t"][live, c].min()
+        if case == "cfl":
+            assert float(f["dt"]) >= 1200.0
+        # the qs the kernel forms where none is given is the fixture's
+        assert X.same_bits(f["qs"], X.bolton_q_sat(f["t"], f["p"] * 100.0, X.CONSTANTS["rd"], X.CONSTANTS["rv"]))
+
+
+def test_symbol_header_and_python_layer():
+    syms = subprocess.check_output(["nm", "-D", "--defined-only", _lib.LIB_PATH]).decode()
+    assert re.search(r" T %s\b" % SYMBOL, syms)
+    hdr = open(os.path.join(ROOT, "include", "rrtmg_hip.h")).read()
+    flat = " ".join(hdr.split())
+    assert "int rrtmg_hip_emanuel_convection(rrtmg_ctx *ctx, const rrtmg_emanuel *a);" in flat
+    assert "#define RRTMG_HIP_ABI_VERSION 5" in hdr      # probed by symbol
+    section = flat.split("Emanuel moist convection", 1)[1].split("rrtmg_emanuel;", 1)
+    assert "Probe for it by symbol; RRTMG_HIP_ABI_VERSION is unchanged." in section[0] and "nlay < 4" in section[0]
+    lib = _lib.load_library()
+    assert hasattr(lib, SYMBOL) and lib.rrtmg_hip_abi_version() == 5
+    assert lib.rrtmg_hip_emanuel_convection.argtypes == [C.c_void_p, C.POINTER(_lib.Emanuel)]
+    # the ctypes struct, field for field against the header's declaration order
+    p, d, i = C.c_void_p, C.c_double, C.c_int32
+    want = ([("struct_size", C.c_uint32)] + [(n, i) for n in ("ncol", "nlay", "memspace")] + [(n, p) for n in IN] + [("dt", d), ("pressure_scale", d)]
+            + [("minorig", i), ("reserved", i)] + [(n, d) for n in PARAMETERS + X.CONSTANT_NAMES] + [(n, p) for n in OUT + DIAG + ("cbmf_out",)])
+    assert [(n, t) for n, t in _lib.Emanuel._fields_] == want
+    body = re.sub(r"/\*.*?\*/", "", "typedef struct {" + section[0].rsplit("typedef struct {", 1)[1])
+    declared = re.findall(r"\*?(\w+)\s*[,;]", body.split("{", 1)[1].rsplit("}", 1)[0])
+    assert declared == [n for n, _ in want]
+    assert C.sizeof(_lib.Emanuel) == 16 + 8 * 8 + 16 + 8 + 23 * 8 + 12 * 8
+    assert lib.rrtmg_hip_emanuel_convection(None, C.byref(_lib.Emanuel())) == 4      # a NULL context is an argument error
+    sig = inspect.signature(_lib.Context.emanuel_convection)
+    assert list(sig.parameters)[:11] == ["self", "t", "q", "u", "v", "pmid", "pint", "cbmf", "dt", "parameters", "constants"]
+    assert isinstance(_lib.Context.has_emanuel_convection, property)
+    assert "EmanuelConvection" in climt_amd.__all__
+    assert list(inspect.signature(climt_amd.device_state.emanuel_device_call).parameters) == ["self", "ds", "timestep"]
+    src = open(os.path.join(ROOT, "climt_amd", "csrc", "rrtmg_emanuel.hip")).read()
+    assert re.search(r"__launch_bounds__\(64\)\s+emanuel_kernel", src)
+    rule = open(os.path.join(ROOT, "climt_amd", "csrc", "rrtmg_emanuel.h")).read()
+    for text in (src, rule):
+        code = re.sub(r"//[^\n]*", "", text)
+        assert not re.search(r"\bwhile\b", code)      # every loop is a for bounded by nlay
+    assert not re.search(r"\b(double|int|int32_t)\s+\w+\[", re.sub(r"//[^\n]*", "", rule))      # a thread keeps no array
+    functions = re.findall(r"RRTMG_EMANUEL_HD \w+ \w+\([^)]*\) \{\n(.*)", rule)
+    assert len(functions) == 4 and all(f == "#pragma clang fp contract(off)" for f in functions)
+    assert "169 600" in rule and "169 600" in section[0]
+    assert 8 * (22 * 62 + 6 * 57 * 58) == 169600
+
+
+def test_property_dictionaries_and_constructor_are_the_references():
+    E = climt_amd.EmanuelConvection
+    lev = lambda units, dim="mid_levels": {"dims": ["*", dim], "units": units}
+    col = lambda units: {"dims": ["*"], "units": units}
+    assert E.input_properties == {"air_temperature": lev("degK"), "specific_humidity": lev("kg/kg"), "eastward_wind": lev("m s^-1"),
+                                  "northward_wind": lev("m s^-1"), "air_pressure": lev("mbar"),
+                                  "air_pressure_on_interface_levels": lev("mbar", "interface_levels"), "cloud_base_mass_flux": col("kg m^-2 s^-1")}
+    assert E.diagnostic_properties == {
+        "convective_state": dict(col("dimensionless"), dtype=np.int32), "convective_precipitation_rate": col("mm day^-1"),
+        "convective_downdraft_velocity_scale": col("m s^-1"), "convective_downdraft_temperature_scale": col("degK"),
+        "convective_downdraft_specific_humidity_scale": col("kg/kg"), "cloud_base_mass_flux": col("kg m^-2 s^-1"),
+        "atmosphere_convective_available_potential_energy": col("J kg^-1"), "air_temperature_tendency_from_convection": lev("degK day^-1")}
+    assert E.tendency_properties == {"air_temperature": {"units": "degK s^-1"}, "specific_humidity": {"units": "kg/kg s^-1"},
+                                     "eastward_wind": {"units": "m s^-2"}, "northward_wind": {"units": "m s^-2"}}
+    sig = inspect.signature(E.__init__)
+    defaults = {n: p.default for n, p in sig.parameters.items() if p.default is not inspect.Parameter.empty}
+    assert defaults == dict(
+        minimum_convecting_layer=1, autoconversion_water_content_threshold=0.0011, autoconversion_temperature_threshold=-55,
+        entrainment_mixing_coefficient=1.5, downdraft_area_fraction=0.05, precipitation_fraction_outside_cloud=0.12, speed_water_droplets=50.0,
+        speed_snow=5.5, rain_evaporation_coefficient=1.0, snow_evaporation_coefficient=0.8, convective_momentum_transfer_coefficient=0.7,
+        downdraft_surface_velocity_coefficient=10.0, convection_bouyancy_threshold=0.9, mass_flux_relaxation_rate=0.1, mass_flux_damping_rate=0.1,
+        reference_mass_flux_timescale=300.0, device=0, context=None)
+    assert list(sig.parameters)[:17] == ["self"] + list(defaults)[:16]
+    for kw, text in (("convective_momentum_transfer_coefficient", "Momentum transfer coefficient must be between 0 and 1."),
+                     ("downdraft_area_fraction", "Downdraft fraction must be between 0 and 1."),
+                     ("precipitation_fraction_outside_cloud", "Outside cloud precipitation fraction must be between 0 and 1.")):
+        for bad in (-0.1, 1.5):
+            with pytest.raises(ValueError, match=text):
+                E(context=object(), **{kw: bad})
+        E(context=object(), **{kw: 0}), E(context=object(), **{kw: 1})
+    c = E(context=object())
+    assert issubclass(E, sc.ImplicitTendencyComponent) and list(inspect.signature(c.array_call).parameters) == ["raw_state", "timestep"]
+    assert c.parameters() == X.PARAMETERS and [type(v) for v in c.parameters().values()] == [int] + [float] * 15
+    assert set(c.constants()) == set(X.CONSTANT_NAMES)
+    if not sc.HAVE_SYMPL:
+        assert c.constants() == dict(g=9.80665, cpd=1004.64, cpv=1846.0, rd=287.0, rv=461.5, lv0=2.5e6, rowl=1000.0, cl=2500.0)
+        sc.set_constant("specific_enthalpy_of_vapor_phase", 4186.0, "J/kg")      # asked for at every call
+        try:
+            assert c.constants()["cl"] == 4186.0
+        finally:
+            sc._constant_overrides.clear()
+
+
+# ---- the C entry's argument checks (a context made without a GPU reports errors) ------------------------------------------------------
+@pytest.fixture()
+def bare_context():
+    lib = _lib.load_library()
+    h = C.c_void_p()
+    lib.rrtmg_hip_create(C.byref(h), 0)
+    assert h.value
+    yield lib, h
+    lib.rrtmg_hip_destroy(h)
+
+
+def _args(ncol=4, nlay=8):
+    """A well-formed struct over host memory (the checks under test come before anything is dereferenced or enqueued)."""
+    a, keep = _lib.Emanuel(), {}
+    a.struct_size, a.ncol, a.nlay, a.memspace = C.sizeof(_lib.Emanuel), ncol, nlay, 0
+    for n in IN + OUT + DIAG + ("cbmf_out",):
+        keep[n] = np.zeros((nlay + 1) * ncol)
+        setattr(a, n, keep[n].ctypes.data)
+    a.dt, a.pressure_scale = 600.0, 1.0
+    for n, v in dict(X.PARAMETERS, **X.CONSTANTS).items():
+        setattr(a, n, v)
+    return a, keep
+
+
+def test_the_entry_refuses_bad_arguments(bare_context):
+    lib, h = bare_context
+    call = lambda a: lib.rrtmg_hip_emanuel_convection(h, C.byref(a))
+    message = lambda: lib.rrtmg_hip_last_error(h).decode()
+    assert lib.rrtmg_hip_emanuel_convection(h, None) == 4 and "NULL argument struct" in message()
+    for size in (0, C.sizeof(_lib.Emanuel) - 8, C.sizeof(_lib.Emanuel) + 8):
+        a, keep = _args()
+        a.struct_size = size
+        assert call(a) == 4 and "struct_size" in message()
+    for value in (0, -1):
+        a, keep = _args()
+        a.ncol = value
+        assert call(a) == 4 and "ncol must be positive" in message()
+    for value in (X.MIN_NLAY - 1, 1, 0, -3):
+        a, keep = _args()
+        a.nlay = value
+        assert call(a) == 4 and "nlay must be at least 4" in message()
+    for value in (-1, 2):
+        a, keep = _args()
+        a.memspace = value
+        assert call(a) == 4 and "memspace" in message()
+    for field in IN[:7] + OUT + ("cbmf_out",):
+        a, keep = _args()
+        setattr(a, field, None)
+        assert call(a) == 4 and "must be given" in message(), field
+    for field in ("dt", "pressure_scale", "cpd", "rd", "rv", "g"):
+        for value in (0.0, -1.0, float("nan")):
+            a, keep = _args()
+            setattr(a, field, value)
+            assert call(a) == 4 and "must be positive" in message(), (field, value)
+    for value in (0, -2):
+        a, keep = _args()
+        a.minorig = value
+        assert call(a) == 4 and "minorig must be at least 1" in message()
+    for field in ("cu", "sigd", "sigs"):
+        for value in (-0.01, 1.01, float("nan")):
+            a, keep = _args()
+            setattr(a, field, value)
+            assert call(a) == 4 and "%s (" % field in message() and "must be between 0 and 1" in message(), (field, value)
+    # an output over an input: only cbmf_out == cbmf is in place
+    for out in OUT + DIAG + ("cbmf_out",):
+        for inp in IN:
+            if (out, inp) == ("cbmf_out", "cbmf"):
+                continue
+            a, keep = _args()
+            setattr(a, out, keep[inp].ctypes.data)
+            assert call(a) == 4 and "%s aliases an input" % out in message(), (out, inp)
+    a, keep = _args()
+    a.cbmf_out = keep["cbmf"].ctypes.data + 8      # in place means exactly in place
+    assert call(a) == 4 and "cbmf_out aliases an input" in message()
+    a, keep = _args()
+    a.fv = keep["pint"].ctypes.data + 8 * 32      # the last row of pint: inside the array, not at its start
+    assert call(a) == 4 and "fv aliases an input" in message()
+    a, keep = _args()
+    a.fq = keep["ft"].ctypes.data
+    assert call(a) == 4 and "fq overlaps ft" in message()
+    a, keep = _args()
+    a.iflag = keep["precip"].ctypes.data + 4
+    assert call(a) == 4 and "iflag overlaps precip" in message()
+    a, keep = _args()
+    a.cbmf_out = keep["cape"].ctypes.data + 8
+    assert call(a) == 4 and "cbmf_out overlaps cape" in message()
+
+
+# ---- the stand-alone host program -----------------------------------------------------------------------------------------------
+@pytest.fixture(scope="module")
+def program(tmp_path_factory):
+    return X.build_program(tmp_path_factory.mktemp("emanuel_check"))
+
+
+@pytest.fixture(scope="module")
+def program_sanitized(tmp_path_factory):
+    return X.build_program(tmp_path_factory.mktemp("emanuel_check_san"), "emanuel_check_san", ["-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all"])
+
+
+def check_program(exe, tmp_path, case, nlay, ncol, **kwargs):
+    f = X.load(case, nlay)
+    got = X.run_program(exe, tmp_path, X.tile(f, ncol), float(f["dt"]), X.parameters(f), X.constants(f), **kwargs)
+    assert X.same_bits(got["ft_per_day"], got["ft"] * 86400.0)
+    return X.check(got, f, ncol, (case, nlay, ncol)), got
+
+
+@pytest.mark.parametrize("case", X.CASES)
+def test_host_program_agrees_with_every_fixture(program, tmp_path, case):
+    worst, same = 0.0, 0
+    for i, nlay in enumerate(n for n in X.NLAYS if (case, n) not in MISSING):
+        f = X.load(case, nlay)
+        for ncol in (3, 65):
+            w, got = check_program(program, tmp_path, case, nlay, ncol, in_place=bool(i % 2))
+            worst = max(worst, w)
+        ref = X.reference(f, 65)
+        dev = X.deviations(got, ref)
+        same += all(X.same_bits(got[n], ref[n]) for n in X.FIELDS)
+        print("emanuel_check, %s, nlay %d: largest deviation %.3e (%s), largest deviation / tolerance %.3e" % (case, nlay, max(dev.values()), max(dev, key=dev.get), w))
+        # qs formed by the program is the fixture's qs: the same numbers without the array
+        w2, formed = check_program(program, tmp_path, case, nlay, 3, use_qs=False)
+        worst = max(worst, w2)
+    print("emanuel_check, %s: largest deviation / tolerance %.3e, %d fixtures bit-identical" % (case, worst, same))
+
+
+def test_host_program_under_the_address_and_undefined_behaviour_sanitizers(program_sanitized, tmp_path):
+    """The same program built with -fsanitize=address,undefined and run stand-alone, clean: every fixture, tile edges, and the
+    smallest layer counts the entry accepts (where every column leaves by a first exit)."""
+    for i, (case, nlay) in enumerate(FIXTURES):
+        check_program(program_sanitized, tmp_path, case, nlay, (3, 65, 130)[i % 3], in_place=bool(i % 2), use_qs=bool(i % 3))
+    f = X.load("deep", 8)
+    for nlay in (X.MIN_NLAY, 5, 6, 7):
+        arrays = {n: np.ascontiguousarray(v[:nlay + (n == "ph")]) for n, v in X.tile(f, 65).items()}
+        arrays["cbmf"] = X.tile(f, 65)["cbmf"]
+        got = X.run_program(program_sanitized, tmp_path, arrays, 600.0)
+        if nlay < 6:
+            assert not got["iflag"].any() and not got["ft"].any() and not got["cbmf_out"].any()
+
+
+# ---- physics that pins the rule ---------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("case", ["deep", "freezing", "sheared", "cfl"])
+def test_budgets_close(program, tmp_path, case):
+    """The dp-weighted column integrals of cpn ft + lv fq, of fu and of fv vanish: the reference subtracts the means explicitly.
+    Each to the rounding of its terms: 64 eps times the sum of the terms' magnitudes."""
+    k = X.CONSTANTS
+    for nlay in X.NLAYS:
+        f = X.load(case, nlay)
+        _, got = check_program(program, tmp_path, case, nlay, 3)
+        dp = f["ph"][:-1] - f["ph"][1:]
+        cpn = k["cpd"] * (1.0 - f["q"]) + k["cpv"] * f["q"]
+        lv = k["lv0"] - (k["cl"] - k["cpv"]) * (f["t"] - 273.15)
+        for terms, what in (((cpn * got["ft"] + lv * got["fq"]) * dp, "enthalpy"), (got["fu"] * dp, "eastward momentum"), (got["fv"] * dp, "northward momentum")):
+            size = np.abs(cpn * got["ft"] * dp).sum(axis=0) + np.abs(lv * got["fq"] * dp).sum(axis=0) if what == "enthalpy" else np.abs(terms).sum(axis=0)
+            assert (size > 0).all(), (case, nlay, what)
+            assert (np.abs(terms.sum(axis=0)) <= 64 * np.finfo(float).eps * size).all(), (case, nlay, what, terms.sum(axis=0) / size)
+
+
+# ---- the component on host states: the host program stands in for the context ------------------------------------------------------
+class ProgramContext:
+    """Context.emanuel_convection (host arrays) by the stand-alone host program."""
+
+    def __init__(self, exe, tmp_path):
+        self.exe, self.tmp_path, self.calls = exe, tmp_path, []
+
+    def emanuel_convection(self, t, q, u, v, pmid, pint, cbmf, dt, parameters, constants, qs=None, pressure_scale=1.0, **kwargs):
+        assert not kwargs and qs is None
+        self.calls.append((t.shape, dt, dict(parameters), dict(constants), pressure_scale))
+        got = X.run_program(self.exe, self.tmp_path, dict(t=t, q=q, u=u, v=v, p=pmid, ph=pint, cbmf=cbmf), dt, parameters, constants, use_qs=False,
+                            pressure_scale=pressure_scale)
+        return got["ft"], got["fq"], got["fu"], got["fv"], got["cbmf_out"], {n: got[n] for n in DIAG}
+
+
+NAMES = {"air_temperature": "ft", "specific_humidity": "fq", "eastward_wind": "fu", "northward_wind": "fv"}
+DNAMES = {"convective_state": "iflag", "convective_precipitation_rate": "precip", "convective_downdraft_velocity_scale": "wd",
+          "convective_downdraft_temperature_scale": "tprime", "convective_downdraft_specific_humidity_scale": "qprime", "cloud_base_mass_flux": "cbmf_out",
+          "atmosphere_convective_available_potential_energy": "cape"}
+
+
+def grid_state(f, ny, nx, pressure_units="Pa"):
+    """The fixture tiled to a (lat, lon) grid, levels LAST in the profiles, pressures in `pressure_units`."""
+    a = X.tile(f, ny * nx)
+    per = {"Pa": 100.0, "mbar": 1.0, "hPa": 1.0}[pressure_units]
+    lev = lambda x: np.ascontiguousarray(np.transpose(x.reshape(x.shape[0], ny, nx), (1, 2, 0)))
+    q3 = lambda x, dim, units, s=1.0: DataArray(lev(x) * s, dims=("lat", "lon", dim), attrs={"units": units})
+    return {"air_temperature": q3(a["t"], "mid_levels", "degK"), "specific_humidity": q3(a["q"], "mid_levels", "kg/kg"),
+            "eastward_wind": q3(a["u"], "mid_levels", "m s^-1"), "northward_wind": q3(a["v"], "mid_levels", "m/s"),
+            "air_pressure": q3(a["p"], "mid_levels", pressure_units, per), "air_pressure_on_interface_levels": q3(a["ph"], "interface_levels", pressure_units, per),
+            "cloud_base_mass_flux": DataArray(a["cbmf"].reshape(ny, nx), dims=("lat", "lon"), attrs={"units": "kg m^-2 s^-1"}),
+            "time": datetime.datetime(2000, 1, 1)}
+
+
+def test_component_on_a_3d_grid_with_pressures_in_pa(program, tmp_path):
+    """Pressures in Pa and a (lat, lon) grid, levels last: the component hands the rule [levels][columns] in mbar with the scheme's
+    parameters, the constants and the time step in seconds, and returns the rule's numbers, the heating in K/day beside them."""
+    case, nlay, ny, nx = "sheared", 30, 5, 13
+    f = X.load(case, nlay)
+    ctx = ProgramContext(program, tmp_path)
+    comp = climt_amd.EmanuelConvection(context=ctx)
+    tendencies, diagnostics = comp(grid_state(f, ny, nx), datetime.timedelta(seconds=float(f["dt"])))
+    assert ctx.calls == [((nlay, ny * nx), float(f["dt"]), X.PARAMETERS, comp.constants(), 1.0)]
+    # Pa -> mbar on the way in costs a rounding per pressure, and the component's constants are sympl's, not the fixture's: the rule
+    # itself on what the component formed
+    a = X.tile(f, ny * nx)
+    back = lambda x: (x * 100.0) * 0.01
+    want = X.run_program(program, tmp_path, dict(a, p=back(a["p"]), ph=back(a["ph"])), float(f["dt"]), X.PARAMETERS, comp.constants(), use_qs=False)
+    assert set(tendencies) == set(NAMES) and set(diagnostics) == set(DNAMES) | {"air_temperature_tendency_from_convection"}
+    flat = lambda x: np.transpose(x.values, [x.dims.index(d) for d in ("mid_levels", "lat", "lon")]).reshape(nlay, ny * nx)
+    for name, key in NAMES.items():
+        x = tendencies[name]
+        assert x.attrs["units"] == comp.tendency_properties[name]["units"] and set(x.dims) == {"mid_levels", "lat", "lon"}
+        assert X.same_bits(flat(x), want[key]), name
+    for name, key in DNAMES.items():
+        x = diagnostics[name]
+        assert x.attrs["units"] == comp.diagnostic_properties[name]["units"] and tuple(x.dims) == ("lat", "lon")
+        assert X.same_bits(x.values.reshape(-1).astype(np.float64), want[key].astype(np.float64)), name
+    assert diagnostics["convective_state"].values.dtype == np.int32 and (diagnostics["convective_state"].values == 1).all()
+    assert X.same_bits(flat(diagnostics["air_temperature_tendency_from_convection"]), want["ft"] * 86400.0)
+    assert want["fu"].any() and (want["precip"] > 0).any()
+
+
+@pytest.mark.parametrize("desc", ["column", "3d"])
+def test_reference_cache_default_state(program, tmp_path, desc):
+    """TestEmanuel-{column,3d}-{0,1}.cache: the tendencies and diagnostics of the reference's compiled scheme on its default state.
+    Here: get_default_state for the component on the cache's grid, through the component, to the reference's own criterion.  (The
+    default state is dry: every column leaves by the first exit, so the caches pin the layout, units and exit, not the constants.)"""
+    _, want_tend, want_diag = load_cache_case("TestEmanuel", desc)
+    assert set(want_tend) == set(NAMES) and set(want_diag) == set(DNAMES) | {"air_temperature_tendency_from_convection"}
+    shape = want_tend["air_temperature"].values.shape
+    comp = climt_amd.EmanuelConvection(context=ProgramContext(program, tmp_path))
+    state = climt_amd.get_default_state([comp], grid_state=climt_amd.get_grid(nx=shape[1], ny=shape[0], nz=shape[2]))
+    tendencies, diagnostics = comp(state, datetime.timedelta(seconds=10))
+    assert set(tendencies) == set(want_tend) and set(diagnostics) == set(want_diag)
+    for got_all, want_all in ((tendencies, want_tend), (diagnostics, want_diag)):
+        for name, want in want_all.items():
+            got = got_all[name]
+            assert climt_amd.device_state._same_units(got.attrs["units"], want.attrs["units"]) or {got.attrs["units"], want.attrs["units"]} <= {
+                "degK s^-1", "degK/s", "kg/kg s^-1", "kg/kg/s", "m s^-2", "m/s^2", "mm day^-1", "mm/day", "J kg^-1", "J/kg", "kg m^-2 s^-1",
+                "kg/m^2/s", "degK day^-1", "degK/day", "m s^-1", "m/s"}, (name, got.attrs["units"], want.attrs["units"])
+            g = np.transpose(got.values, [got.dims.index(d) for d in want.dims])
+            assert g.shape == want.values.shape, name
+            assert np.isclose(g, want.values, rtol=1e-8, atol=1e-8).all(), name      # the reference's own criterion (rtol 1e-8), its atol 1e-6 tightened
+
+
+# ---- AdamsBashforth with an implicit component in the list --------------------------------------------------------------------------
+class Cooling(sc.TendencyComponent):
+    input_properties = {"air_temperature": {"dims": ["*", "mid_levels"], "units": "degK"}}
+    tendency_properties = {"air_temperature": {"units": "degK day^-1"}}
+    diagnostic_properties = {}
+
+    def array_call(self, raw):
+        return {"air_temperature": -1.5 - 0.01 * raw["air_temperature"]}, {}
+
+
+def test_adams_bashforth_hands_an_implicit_component_the_timestep(program, tmp_path):
+    f = X.load("deep", 10)
+    dt = datetime.timedelta(seconds=600)
+    seen = []
+
+    class Recording(climt_amd.EmanuelConvection):
+        def array_call(self, raw_state, timestep):
+            seen.append(timestep)
+            return super().array_call(raw_state, timestep)
+
+    def run(components, steps=3):
+        state, stepper = grid_state(f, 1, 3, "mbar"), climt_amd.AdamsBashforth(components)
+        for _ in range(steps):
+            diagnostics, new = stepper(state, dt)
+            state = dict(new, **{k: v for k, v in diagnostics.items() if k == "cloud_base_mass_flux"})
+        return state
+    plain = run([Cooling()])
+    # the list without an implicit component: the bits it had -- the stand-in's arithmetic, stated here independently
+    t = grid_state(f, 1, 3, "mbar")["air_temperature"].values
+    hist = []
+    for _ in range(3):
+        hist = [(-1.5 - 0.01 * t) * (1.0 / 86400.0)] + hist[:2]
+        w = {1: (1.0,), 2: (1.5, -0.5), 3: (23.0 / 12.0, -16.0 / 12.0, 5.0 / 12.0)}[len(hist)]
+        t = t + 600.0 * sum(wi * h for wi, h in zip(w, hist))
+    assert X.same_bits(plain["air_temperature"].values, t)
+    moist = run([Cooling(), Recording(context=ProgramContext(program, tmp_path))])
+    assert seen == [dt] * 3
+    assert not X.same_bits(moist["air_temperature"].values, plain["air_temperature"].values)
+    assert not X.same_bits(moist["specific_humidity"].values, grid_state(f, 1, 3, "mbar")["specific_humidity"].values)
+    assert (moist["cloud_base_mass_flux"].values > 0).all()
