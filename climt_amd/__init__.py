@@ -20,11 +20,12 @@ from .initialization import get_default_state, get_grid  # noqa: F401,E402
 from .instellation import Instellation  # noqa: F401,E402
 from .rrtmg import RRTMGLongwave, RRTMGShortwave, radiation_step  # noqa: F401,E402
 from .simple_boundary_layer import SimpleBoundaryLayer  # noqa: F401,E402
+from .simple_physics import SimplePhysics  # noqa: F401,E402
 from .emanuel import EmanuelConvection  # noqa: F401,E402
 from .slab_surface import SlabSurface  # noqa: F401,E402
 from .timestepping import AdamsBashforth  # noqa: F401,E402
 from .wrappers import UpdateFrequencyWrapper  # noqa: F401,E402
 from .intermittent import IntermittentLongwave, IntermittentShortwave  # noqa: F401,E402
 
-__all__ = ["RRTMGLongwave", "RRTMGShortwave", "Instellation", "BergerSolarInsolation", "SlabSurface", "DryConvectiveAdjustment", "SimpleBoundaryLayer", "EmanuelConvection", "get_grid", "get_default_state", "UpdateFrequencyWrapper", "IntermittentShortwave", "IntermittentLongwave", "AdamsBashforth",
+__all__ = ["RRTMGLongwave", "RRTMGShortwave", "Instellation", "BergerSolarInsolation", "SlabSurface", "DryConvectiveAdjustment", "SimpleBoundaryLayer", "EmanuelConvection", "SimplePhysics", "get_grid", "get_default_state", "UpdateFrequencyWrapper", "IntermittentShortwave", "IntermittentLongwave", "AdamsBashforth",
            "Context", "RRTMGError", "DeviceState", "DeviceQuantity", "DeviceAdamsBashforth", "radiation_step"]

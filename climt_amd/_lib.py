@@ -214,6 +214,20 @@ class Emanuel(C.Structure):
                 + [(n, _vp) for n in EMANUEL_OUT + EMANUEL_DIAG + ("cbmf_out",)])
 
 
+SIMPLE_PHYSICS_SWITCHES = ("do_lsc", "do_pbl", "do_surf_flux", "use_ts_ext", "use_qsurf_ext", "test", "clamp_latent_heat_flux")
+SIMPLE_PHYSICS_CONSTANTS = ("g", "cpair", "rair", "latvap", "rh2o", "radius", "omega", "rhow", "pbltop", "pblconst", "c_heat", "cd0", "cd1", "cm")
+SIMPLE_PHYSICS_IN = ("t", "q", "u", "v", "pmid", "pint", "ps", "ts", "qsurf", "lat")
+SIMPLE_PHYSICS_OUT = ("t_out", "q_out", "u_out", "v_out")
+SIMPLE_PHYSICS_DIAG = ("precl", "sh_out", "lh_out")
+
+
+class SimplePhysics(C.Structure):
+    """mirrors `rrtmg_simple_physics` (include/rrtmg_hip.h), field for field"""
+    _fields_ = ([("struct_size", C.c_uint32), ("ncol", _i32), ("nlay", _i32), ("memspace", _i32)] + [(n, _i32) for n in SIMPLE_PHYSICS_SWITCHES + ("reserved",)]
+                + [(n, _vp) for n in SIMPLE_PHYSICS_IN] + [("dt", _f64)] + [(n, _f64) for n in SIMPLE_PHYSICS_CONSTANTS]
+                + [("pressure_scale", _f64), ("ps_scale", _f64)] + [(n, _vp) for n in SIMPLE_PHYSICS_OUT + SIMPLE_PHYSICS_DIAG])
+
+
 _lib = None
 
 
@@ -291,6 +305,8 @@ def load_library():
         lib.rrtmg_hip_boundary_layer.argtypes = [_vp, C.POINTER(BoundaryLayer)]
     if hasattr(lib, "rrtmg_hip_emanuel_convection"):        # (likewise: the Emanuel convection scheme)
         lib.rrtmg_hip_emanuel_convection.argtypes = [_vp, C.POINTER(Emanuel)]
+    if hasattr(lib, "rrtmg_hip_simple_physics"):            # (likewise: the simple physics package)
+        lib.rrtmg_hip_simple_physics.argtypes = [_vp, C.POINTER(SimplePhysics)]
     lib.rrtmg_hip_copy_blocks.argtypes =[_vp, C.c_int, _vp, C.c_long, C.c_long, _vp, _vp, _vp]
     lib.rrtmg_hip_mcica_mask.argtypes = [_vp] + [C.c_int] * 6 + [_vp] * 3
     _lib = lib
@@ -739,6 +755,70 @@ class Context:
             setattr(a, name, x.ctypes.data)
         self._ck(self.lib.rrtmg_hip_emanuel_convection(self.h, C.byref(a)))
         return outs["ft"], outs["fq"], outs["fu"], outs["fv"], outs["cbmf_out"], diagnostics
+
+    @property
+    def has_simple_physics(self):
+        """Whether the library exports the simple physics package (rrtmg_hip_simple_physics; probed by the symbol)."""
+        return hasattr(self.lib, "rrtmg_hip_simple_physics")
+
+    @_locked
+    def simple_physics(self, t, q, u, v, pmid, pint, ps, dt, constants, switches, ts=None, qsurf=None, lat=None, t_out=None, q_out=None,
+                       u_out=None, v_out=None, diagnostics=True, pressure_scale=1.0, ps_scale=1.0, memspace=0, ncol=None, nlay=None):
+        """climt's SimplePhysics by column (rrtmg_hip_simple_physics) -> (t_out, q_out, u_out, v_out, diagnostics).
+        `constants`: g, cpair, rair, latvap, rh2o, radius, omega, rhow, pbltop, pblconst, c_heat, cd0, cd1, cm; `switches`: a dict of
+        do_lsc, do_pbl, do_surf_flux, use_ts_ext, use_qsurf_ext, test, clamp_latent_heat_flux (a missing one is 0; do_pbl without
+        do_surf_flux is refused by the library); `ts`, `qsurf`, `lat` are needed where the switches have them read and ignored
+        otherwise; `pressure_scale`, `ps_scale`: Pa per unit of pmid / pint and of ps.  Host arrays t, q, u, v, pmid [nlay][ncol],
+        pint [nlay+1][ncol], ps, ts, qsurf, lat [ncol] (outputs are allocated unless given; each may be its own input),
+        `diagnostics` True: a dict of the three [ncol] arrays precl, sh_out, lh_out (False or None: none are asked for; a dict:
+        those it names are written).  Or device pointers (or DeviceArrays) with memspace=1 -- then the four outputs, `ncol` and
+        `nlay`, and `diagnostics` a dict of device pointers or None; one launch on the main stream."""
+        if not self.has_simple_physics:
+            raise RRTMGError(4, "this librrtmg_hip.so has no rrtmg_hip_simple_physics (simple physics package)")
+        a = SimplePhysics()
+        a.struct_size, a.memspace, a.dt = C.sizeof(SimplePhysics), 1 if memspace else 0, float(dt)
+        a.pressure_scale, a.ps_scale = float(pressure_scale), float(ps_scale)
+        for n in SIMPLE_PHYSICS_CONSTANTS:
+            setattr(a, n, float(constants[n]))
+        for n in switches:
+            if n not in SIMPLE_PHYSICS_SWITCHES:
+                raise ValueError("simple_physics: no switch %r" % n)
+            setattr(a, n, int(switches[n]))
+        given = dict(t=t, q=q, u=u, v=v, pmid=pmid, pint=pint, ps=ps)
+        given.update({n: x for n, x in (("ts", ts), ("qsurf", qsurf), ("lat", lat)) if x is not None})
+        if memspace:
+            f64 = PRECISIONS["float64"]
+            if t_out is None or q_out is None or u_out is None or v_out is None or ncol is None or nlay is None:
+                raise ValueError("simple_physics: device pointers need t_out, q_out, u_out, v_out, ncol and nlay")
+            a.ncol, a.nlay = int(ncol), int(nlay)
+            diagnostics = diagnostics if isinstance(diagnostics, dict) else {}
+            for name, x in list(given.items()) + [("t_out", t_out), ("q_out", q_out), ("u_out", u_out), ("v_out", v_out)] + list(diagnostics.items()):
+                if name not in SIMPLE_PHYSICS_IN + SIMPLE_PHYSICS_OUT + SIMPLE_PHYSICS_DIAG:
+                    raise ValueError("simple_physics: no diagnostic %r" % name)
+                setattr(a, name, _device_pointer(x, f64, name))
+            self._ck(self.lib.rrtmg_hip_simple_physics(self.h, C.byref(a)))
+            return t_out, q_out, u_out, v_out, diagnostics
+        given = {n: np.ascontiguousarray(x, dtype=np.float64) for n, x in given.items()}
+        shape = given["t"].shape
+        if len(shape) != 2 or any(given[n].shape != shape for n in ("q", "u", "v", "pmid")) or given["pint"].shape != (shape[0] + 1, shape[1]):
+            raise ValueError("simple_physics: t, q, u, v, pmid must be [nlay][ncol] arrays of one shape and pint [nlay+1][ncol]")
+        if any(x.shape != (shape[1],) for n, x in given.items() if n in ("ps", "ts", "qsurf", "lat")):
+            raise ValueError("simple_physics: ps, ts, qsurf and lat must be [ncol] arrays")
+        outs = {n: (np.empty(shape) if x is None else x) for n, x in (("t_out", t_out), ("q_out", q_out), ("u_out", u_out), ("v_out", v_out))}
+        if diagnostics is True:
+            diagnostics = {n: np.empty(shape[1]) for n in SIMPLE_PHYSICS_DIAG}
+        elif not isinstance(diagnostics, dict):
+            diagnostics = {}
+        for name, x in list(outs.items()) + list(diagnostics.items()):
+            if name not in SIMPLE_PHYSICS_OUT + SIMPLE_PHYSICS_DIAG:
+                raise ValueError("simple_physics: no diagnostic %r" % name)
+            if not (isinstance(x, np.ndarray) and x.dtype == np.float64 and x.flags.c_contiguous and x.size == (given["t"].size if name in outs else shape[1])):
+                raise ValueError("simple_physics: %s is written in place: a C-contiguous float64 array of the right size" % name)
+        a.nlay, a.ncol = shape
+        for name, x in list(given.items()) + list(outs.items()) + list(diagnostics.items()):
+            setattr(a, name, x.ctypes.data)
+        self._ck(self.lib.rrtmg_hip_simple_physics(self.h, C.byref(a)))
+        return outs["t_out"], outs["q_out"], outs["u_out"], outs["v_out"], diagnostics
 
     @_locked
     def solar_insolation(self, lat, lon, sin_delta, cos_delta, fractional_day, irradiance):

@@ -69,6 +69,12 @@ except ImportError:
         ("latent_heat_of_condensation", "J/kg"): 2.5e6,
         ("density_of_liquid_phase", "kg/m^3"): 1000.0,
         ("specific_enthalpy_of_vapor_phase", "J/kg"): 2500.0,
+        # SimplePhysics (simple_physics/component.py:191-201), under the unit strings it asks with: sympl's defaults as
+        # remembered; no reference data pins them.  Radius and rotation enter only the internal surface
+        # temperature, the density scales the precipitation rate
+        ("planetary_radius", "m"): 6.37122e6,
+        ("planetary_rotation_rate", "s^-1"): 7.292e-5,
+        ("density_of_liquid_water", "kg/m^3"): 1000.0,
     }
     _constant_overrides = {}
 

@@ -566,6 +566,43 @@ def emanuel_device_call(self, ds, timestep):
     return tend, diagnostics
 
 
+def simple_physics_device_call(self, ds, timestep):
+    """SimplePhysics on a DeviceState: rrtmg_hip_simple_physics with device pointers on the main stream.  The pressures are read
+    as they are resident -- in the units of whichever component asked for them first; the rule needs Pa (saturation, densities,
+    the top of the boundary layer), so the library multiplies every pressure it reads by `pressure_scale` / `ps_scale`, Pa per
+    resident unit: the one rounding the unit conversion of the host path makes.  The four new profiles go to work buffers that
+    alternate with the step count (the state's previous arrays stay what they were) and the state is rebound to them; the three
+    diagnostics go to [ncol] work buffers, which SlabSurface's device call can read as its flux inputs:
+    -> (diagnostics as DeviceQuantity, the same state)."""
+    P = self.input_properties
+    names = ("air_temperature", "specific_humidity", "eastward_wind", "northward_wind")
+    t, q, u, v = (ds.need(n, P[n]) for n in names)
+    ts, qsurf, lat = (ds.need(n, P[n]) for n in ("surface_temperature", "surface_specific_humidity", "latitude"))
+    p, pi, ps = ds["air_pressure"], ds["air_pressure_on_interface_levels"], ds["surface_air_pressure"]
+    if tuple(p.dims) != ("mid_levels", "*") or tuple(pi.dims) != ("interface_levels", "*") or tuple(ps.dims) != ("*",):
+        raise ValueError("the pressures are resident as %s, %s and %s, the simple physics wants [levels][*] and [*]" % (p.dims, pi.dims, ps.dims))
+    if not _same_units(p.units, pi.units):
+        raise ValueError("air_pressure is resident in %r, air_pressure_on_interface_levels in %r" % (p.units, pi.units))
+    nlay, ncol = t.shape
+    if any(x.shape != (nlay, ncol) for x in (q, u, v, p)) or pi.shape != (nlay + 1, ncol) or any(x.shape != (ncol,) for x in (ps, ts, qsurf, lat)):
+        raise ValueError("temperature %s, humidity %s, winds %s, %s, pressures %s, %s and surface values %s, %s, %s, %s do not belong to one grid" % (
+            t.shape, q.shape, u.shape, v.shape, p.shape, pi.shape, ps.shape, ts.shape, qsurf.shape, lat.shape))
+    ds.join_streams()      # a longwave still in flight belongs to the step this component closes
+    slot = ds.step_count & 1
+    new = [ds.work(("sp", id(self), n, slot), x.shape, x.dims, x.units) for n, x in zip(names, (t, q, u, v))]
+    col = lambda key, units: ds.work(("sp", id(self), key, slot), (ncol,), ("*",), units)
+    d = dict(precl=col("precl", "m s^-1"), sh_out=col("sh", "W m^-2"), lh_out=col("lh", "W m^-2"))
+    to_pa = lambda units: float(_convert(np.float64(1.0), units, "Pa"))
+    ds.ctx.simple_physics(t.ptr, q.ptr, u.ptr, v.ptr, p.ptr, pi.ptr, ps.ptr, timestep.total_seconds(), self.constants(), self.switches(),
+                          ts=ts.ptr, qsurf=qsurf.ptr, lat=lat.ptr, t_out=new[0].ptr, q_out=new[1].ptr, u_out=new[2].ptr, v_out=new[3].ptr,
+                          diagnostics={k: x.ptr for k, x in d.items()}, pressure_scale=to_pa(p.units), ps_scale=to_pa(ps.units),
+                          memspace=1, ncol=ncol, nlay=nlay)
+    for n, x in zip(names, new):
+        ds[n] = x
+    return {"stratiform_precipitation_rate": d["precl"], "surface_upward_sensible_heat_flux": d["sh_out"],
+            "surface_upward_latent_heat_flux": d["lh_out"]}, ds
+
+
 # ---- time stepping on the device ------------------------------------------------------------------------------------
 _AB = {1: (1.0,), 2: (1.5, -0.5), 3: (23.0 / 12.0, -16.0 / 12.0, 5.0 / 12.0), 4: (55.0 / 24.0, -59.0 / 24.0, 37.0 / 24.0, -9.0 / 24.0)}
 

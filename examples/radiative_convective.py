@@ -3,17 +3,23 @@
 the dry convective adjustment -- the arrangement of the reference's examples/column_code_with_slab.py with
 `from climt_amd import ...`: one column of 30 levels, dt = 10 min, a 5 m ocean mixed layer at 300 K under a fixed sun.
 
-The reference's example also couples the column to the surface with SimplePhysics, which this package does not have, and carries
+The reference's example also couples the column to the surface with SimplePhysics (--simple-physics below) and carries
 EmanuelConvection in the time stepper's list (--moist-convection below): by default the atmosphere feels the surface through the
 radiation alone and stays dry.  So that the adjustment has work from
 the first step, the column starts on a lapse rate steeper than the dry adiabat (T ~ p^0.32) instead of the reference's
 isothermal 290 K.
 
-    python examples/radiative_convective.py [--steps 60] [--device-resident] [--boundary-layer] [--moist-convection]
+    python examples/radiative_convective.py [--steps 60] [--device-resident] [--boundary-layer | --simple-physics] [--moist-convection]
 
 --boundary-layer closes that gap: SimpleBoundaryLayer (bulk surface fluxes, implicit diffusion of T, q, u, v) steps after the time
 stepper and before the adjustment, and its two flux diagnostics go into the state, so the slab feels them from the next step
 on.  The state then carries a light wind and a surface humidity.  Without the flag the run is what it was.
+
+--simple-physics is the reference's own coupling: SimplePhysics (large-scale condensation, surface fluxes on the lowest layer,
+boundary-layer mixing) steps after the time stepper and before the adjustment, as in the reference's column_code_with_slab.py,
+and its diagnostics -- the two surface fluxes and the stratiform precipitation -- go into the state.  The state then carries a
+light wind, and the column starts moister with a supersaturated layer, so that it rains from the first step.  Exclusive with
+--boundary-layer (both would exchange with the surface).  Without the flag the run is what it was.
 
 --moist-convection puts EmanuelConvection into the AdamsBashforth list, as the reference's example has it
 (AdamsBashforth([rad_sw, rad_lw, slab, convection])): what the column holds of water condenses and rains out, the cloud-base mass
@@ -32,14 +38,16 @@ from datetime import timedelta
 import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from climt_amd import (AdamsBashforth, DryConvectiveAdjustment, EmanuelConvection, RRTMGLongwave, RRTMGShortwave, SimpleBoundaryLayer, SlabSurface,  # noqa: E402
-                       get_default_state, get_grid)
+from climt_amd import (AdamsBashforth, DryConvectiveAdjustment, EmanuelConvection, RRTMGLongwave, RRTMGShortwave, SimpleBoundaryLayer, SimplePhysics,  # noqa: E402
+                       SlabSurface, get_default_state, get_grid)
 
 
-def run(steps=60, device_resident=False, report=None, boundary_layer=False, moist_convection=False):
+def run(steps=60, device_resident=False, report=None, boundary_layer=False, moist_convection=False, simple_physics=False):
     """-> (diagnostics of step 0, state after `steps` steps), both as host DataArrays.  `boundary_layer`: with SimpleBoundaryLayer
     between the time stepper and the adjustment; its diagnostics of step 0 are then among the first.  `moist_convection`: with
-    EmanuelConvection in the time stepper's list."""
+    EmanuelConvection in the time stepper's list.  `simple_physics`: with SimplePhysics in the place of the boundary layer."""
+    if boundary_layer and simple_physics:
+        raise ValueError("boundary_layer and simple_physics are exclusive: both exchange heat, moisture and momentum with the surface")
     rad_sw = RRTMGShortwave()
     rad_lw = RRTMGLongwave(allow_synthetic_tables=True)
     slab = SlabSurface()
@@ -52,6 +60,9 @@ def run(steps=60, device_resident=False, report=None, boundary_layer=False, mois
     steppers = [dry_convection]
     if boundary_layer:
         simple_boundary_layer = SimpleBoundaryLayer()
+        steppers = [simple_boundary_layer, dry_convection]
+    if simple_physics:
+        simple_boundary_layer = SimplePhysics()      # (steps where the boundary layer steps)
         steppers = [simple_boundary_layer, dry_convection]
 
     grid = get_grid(nx=1, ny=1, nz=30)
@@ -72,6 +83,12 @@ def run(steps=60, device_resident=False, report=None, boundary_layer=False, mois
     if boundary_layer:
         state["eastward_wind"].values[:] = 5.0
         state["surface_specific_humidity"].values[:] = 0.018
+    if simple_physics:
+        t = state["air_temperature"].values
+        qsat = 287.0 / 461.5 * 610.78 / p * np.exp(-2.5e6 / 461.5 * (1.0 / t - 1.0 / 273.16))
+        state["specific_humidity"].values[:] = 0.7 * qsat
+        state["specific_humidity"].values[3] = 1.05 * qsat[3]      # one supersaturated layer: stratiform rain from step 0
+        state["eastward_wind"].values[:] = 5.0
     to_host = lambda s, names=None: {k: s[k] for k in (names or s)}
     if device_resident:
         import climt_amd
@@ -86,7 +103,7 @@ def run(steps=60, device_resident=False, report=None, boundary_layer=False, mois
         if i == 0:
             first = to_host(state, list(diagnostics))
 
-        if boundary_layer:
+        if boundary_layer or simple_physics:
             diagnostics, new_state = simple_boundary_layer(state, timestep)
             state.update(diagnostics)
             state.update(new_state)
@@ -108,18 +125,24 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--steps", type=int, default=60)
     ap.add_argument("--device-resident", action="store_true")
-    ap.add_argument("--boundary-layer", action="store_true")
+    surface = ap.add_mutually_exclusive_group()
+    surface.add_argument("--boundary-layer", action="store_true")
+    surface.add_argument("--simple-physics", action="store_true")
     ap.add_argument("--moist-convection", action="store_true")
     a = ap.parse_args()
 
     def report(i, state):
         t = state["air_temperature"].values.ravel()
         rain = "  precipitation %8.3f mm/day" % state["convective_precipitation_rate"].values.ravel()[0] if a.moist_convection else ""
+        if a.simple_physics:
+            rain += "  stratiform %8.3f mm/day  LH %7.2f  SH %7.2f W m^-2" % (
+                state["stratiform_precipitation_rate"].values.ravel()[0] * 8.64e7, state["surface_upward_latent_heat_flux"].values.ravel()[0],
+                state["surface_upward_sensible_heat_flux"].values.ravel()[0])
         print("step %4d  T(surface) %8.3f K  T(surface layer) %8.3f K  T(top) %8.3f K  OLR %8.3f  SW heating(top) %7.3f K/day  LW heating(top) %8.3f K/day%s" % (
             i, state["surface_temperature"].values.ravel()[0], t[0], t[-1], state["upwelling_longwave_flux_in_air"].values.ravel()[-1],
             state["air_temperature_tendency_from_shortwave"].values.ravel()[-1],
             state["air_temperature_tendency_from_longwave"].values.ravel()[-1], rain))
-    run(a.steps, a.device_resident, report, a.boundary_layer, a.moist_convection)
+    run(a.steps, a.device_resident, report, a.boundary_layer, a.moist_convection, a.simple_physics)
 
 
 if __name__ == "__main__":

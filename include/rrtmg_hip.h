@@ -782,6 +782,53 @@ typedef struct {
 } rrtmg_emanuel;
 int rrtmg_hip_emanuel_convection(rrtmg_ctx *ctx, const rrtmg_emanuel *a);
 
+/* ---- simple physics: large-scale condensation, surface fluxes and boundary-layer mixing (Reed and Jablonowski 2012) ---- */
+/* climt's SimplePhysics (simple_physics/component.py around simple_physics_custom.f90), by column; level 0 is the surface (the
+ * reference runs top-down and its binder flips the levels), interface i lies below layer i at pint[i].  The three processes are
+ * time-split in this order, each behind its switch (a switch is on where it is 1), in the reference's order of operations:
+ *   epsilo = rair / rh2o, zvir = rh2o / rair - 1;  za = rair / g t[0] (1 + zvir q[0]) 0.5 (log(ps) - log(pint[1])) of the state as given.
+ *   do_lsc: by layer qsat = epsilo 610.78 / pmid exp(-latvap / rh2o (1 / t - 1 / 273.16)); where q > qsat,
+ *   tmp = 1 / dt (q - qsat) / (1 + (latvap / cpair) (epsilo latvap qsat / (rair t t))), t += latvap / cpair tmp dt, q -= tmp dt and
+ *   precl += tmp (pint[i] - pint[i+1]) / (g rhow), summed from the model top downwards.
+ *   do_surf_flux, on layer 0: wind = |(u, v)|, Cd = cd0 + cd1 wind below 20 m/s and cm from there; u, v /= 1 + Cd wind dt / za;
+ *   rho = pmid / (rair t), F = c_heat wind (Tsurf - t), sh_out = rho cpair F, t += F rho g / (pint[0] - pint[1]) dt; then with rho of
+ *   the new t: F = c_heat wind (qsats - q), lh_out = latvap rho F, q += F rho g / (pint[0] - pint[1]) dt.  Tsurf is ts where
+ *   use_ts_ext is 1; else the moist baroclinic wave's latitude-dependent surface temperature where test is 1 (lat is taken as
+ *   radians) and 302.15 K otherwise.  qsats is qsurf where use_qsurf_ext is 1, else epsilo es / (ps - 0.378 es) with the
+ *   reference's two fits of es (over water where Tsurf > 271, over ice otherwise), whose constants are the doubles of
+ *   single-precision literals.  lh_out is written as it comes out, negative over dew, unless clamp_latent_heat_flux is set: then
+ *   lh < 0 ? 0 : lh (a NaN stays one); q has taken the negative flux either way.  Without do_surf_flux sh_out and lh_out are +0.0.
+ *   do_pbl: Km = Cd wind za and Ke = c_heat wind za at every interface with pint >= pbltop, times
+ *   exp(-(pbltop - pint)^2 / pblconst^2) above; rho = pint / (rair (t[i-1] + t[i]) / 2); backward-Euler diffusion of u, v (Km)
+ *   and q, theta = t pow(1e5 / pmid, rair / cpair) (Ke): off-diagonals (1 / dp_int) dt g g K rho rho / dp_mid, the elimination from
+ *   the surface upwards and the back-substitution downwards, t recovered layer by layer with the reference's own pow calls.
+ *   do_pbl without do_surf_flux reads diffusivities the reference never set: RRTMG_ERR_ARG.
+ * A column is one thread's: about nlay exp and divisions for the condensation, 3 nlay pow, nlay exp and 10 nlay divisions for the
+ * mixing.  Pressures: pmid and pint are read as p * pressure_scale, ps as ps * ps_scale -- Pa per unit of the arrays, 1.0 where
+ * they hold Pa (the saturation formulas, the densities and pbltop need Pa: the rule is not unit-free).  Arrays under memspace 0
+ * (host) or 1 (device).  Each of t_out, q_out, u_out, v_out may be exactly its own input (in place); any other overlap of an
+ * output with an input or another output returns RRTMG_ERR_ARG, as do a NULL struct, a struct_size other than
+ * sizeof(rrtmg_simple_physics), ncol <= 0, nlay < 1, a memspace other than 0 and 1, a NULL t, q, u, v, pmid, pint, ps or profile
+ * output, and a NULL ts, qsurf or lat where the switches have it read (ts: do_surf_flux and use_ts_ext; qsurf: do_surf_flux and
+ * use_qsurf_ext; lat: do_surf_flux, no use_ts_ext and test 1; each is ignored and may be NULL otherwise) -- before anything is read
+ * or enqueued.  precl, sh_out and lh_out may each be NULL.  Needs neither rrtmg_hip_sw_init nor rrtmg_hip_lw_init.  Work space:
+ * two [nlay][ncol] arrays of the context.  Host pointers: the inputs go up, the four profiles and the diagnostics asked for come
+ * back.  Device pointers: one launch on the context's main stream; in deferred mode the call returns once enqueued.
+ * Probe for it by symbol; RRTMG_HIP_ABI_VERSION is unchanged. */
+typedef struct {
+  uint32_t struct_size; int32_t ncol, nlay, memspace;
+  int32_t do_lsc, do_pbl, do_surf_flux, use_ts_ext, use_qsurf_ext, test, clamp_latent_heat_flux, reserved;   /* reserved: 0 */
+  const double *t, *q, *u, *v, *pmid;                 /* [nlay][ncol] */
+  const double *pint;                                 /* [nlay+1][ncol] */
+  const double *ps, *ts, *qsurf, *lat;                /* [ncol]; ts, qsurf, lat may be NULL where unread */
+  double dt;
+  double g, cpair, rair, latvap, rh2o, radius, omega, rhow, pbltop, pblconst, c_heat, cd0, cd1, cm;
+  double pressure_scale, ps_scale;
+  double *t_out, *q_out, *u_out, *v_out;              /* [nlay][ncol]; each may be its own input (in place) */
+  double *precl, *sh_out, *lh_out;                    /* [ncol]; each may be NULL */
+} rrtmg_simple_physics;
+int rrtmg_hip_simple_physics(rrtmg_ctx *ctx, const rrtmg_simple_physics *a);
+
 /* ---- reference-compatible entry points (host pointers, default context) ---------------- */
 int rrtmg_hip_default_status(void);
 const char *rrtmg_hip_default_error(void);
