@@ -178,13 +178,16 @@ class LwAdjust(C.Structure):
 
 
 DRY_ADJUST_CONSTANTS = ("cpd", "cvap", "rd", "rv", "pref")
+DRY_ADJUST_IN = ("t", "q", "pmid", "pint")
+DRY_ADJUST_OUT = ("t_out", "q_out")
+DRY_ADJUST_DIAG = ("mixed_top",)
 
 
 class DryAdjust(C.Structure):
     """mirrors `rrtmg_dry_adjust` (include/rrtmg_hip.h), field for field"""
     _fields_ = ([("struct_size", C.c_uint32), ("ncol", _i32), ("nlay", _i32), ("memspace", _i32)]
-                + [(n, _vp) for n in ("t", "q", "pmid", "pint")] + [(n, _f64) for n in DRY_ADJUST_CONSTANTS]
-                + [(n, _vp) for n in ("t_out", "q_out", "mixed_top")])
+                + [(n, _vp) for n in DRY_ADJUST_IN] + [(n, _f64) for n in DRY_ADJUST_CONSTANTS]
+                + [(n, _vp) for n in DRY_ADJUST_OUT + DRY_ADJUST_DIAG])
 
 
 BOUNDARY_LAYER_CONSTANTS = ("rd", "cp", "g", "lv", "karman", "z0", "fb", "p0", "ric")
@@ -226,6 +229,20 @@ class SimplePhysics(C.Structure):
     _fields_ = ([("struct_size", C.c_uint32), ("ncol", _i32), ("nlay", _i32), ("memspace", _i32)] + [(n, _i32) for n in SIMPLE_PHYSICS_SWITCHES + ("reserved",)]
                 + [(n, _vp) for n in SIMPLE_PHYSICS_IN] + [("dt", _f64)] + [(n, _f64) for n in SIMPLE_PHYSICS_CONSTANTS]
                 + [("pressure_scale", _f64), ("ps_scale", _f64)] + [(n, _vp) for n in SIMPLE_PHYSICS_OUT + SIMPLE_PHYSICS_DIAG])
+
+
+# What Context._column_call knows of each column component's arrays besides the three tuples above: `columns` are [ncol], `levels`
+# [nlay+1][ncol] and the others [nlay][ncol]; `int32` are int32 and the others float64 (tests/test_call_arrays.py holds all three to
+# the library's own tables); `optional` profiles are named in brackets by the shape message; `in_place`: (output, input) pairs for
+# which an output that IS the caller's input array means that array, not its contiguous copy.
+COLUMN_ARRAYS = {
+    "dry_adjustment": dict(IN=DRY_ADJUST_IN, DIAG=DRY_ADJUST_DIAG, columns=("mixed_top",), levels=("pint",), int32=("mixed_top",)),
+    "boundary_layer": dict(IN=BOUNDARY_LAYER_IN, DIAG=BOUNDARY_LAYER_DIAG, levels=("pint",),
+                           columns=("ps", "ts", "qs", "sh_in", "lh_in", "stress_north", "stress_east", "height", "sh_out", "lh_out")),
+    "emanuel_convection": dict(IN=EMANUEL_IN, DIAG=EMANUEL_DIAG, levels=("pint",), int32=("iflag",), optional=("qs",), in_place=(("cbmf_out", "cbmf"),),
+                               columns=("cbmf", "cbmf_out", "precip", "wd", "tprime", "qprime", "cape", "iflag")),
+    "simple_physics": dict(IN=SIMPLE_PHYSICS_IN, DIAG=SIMPLE_PHYSICS_DIAG, levels=("pint",), columns=("ps", "ts", "qsurf", "lat", "precl", "sh_out", "lh_out")),
+}
 
 
 _lib = None
@@ -583,6 +600,54 @@ class Context:
                 setattr(a, name, None if v is None else _device_pointer(v, f64, name))
         self._ck(self.lib.rrtmg_hip_lw_adjust_surface(self.h, C.byref(a)))
 
+    def _column_call(self, entry, a, given, outs, diagnostics, memspace, ncol, nlay):
+        """The array side of a column component's call (rrtmg_hip_<entry>), behind the scalars its method has put into the struct
+        `a` -> (outs, diagnostics).  `given`: the inputs the call reads, by name; `outs`: the outputs every call writes, the
+        caller's array or None; `diagnostics`: True, a dict, or None.  Names, shapes and types: COLUMN_ARRAYS[entry]."""
+        IN, DIAG = COLUMN_ARRAYS[entry]["IN"], COLUMN_ARRAYS[entry]["DIAG"]
+        columns, levels, int32, optional, in_place = (COLUMN_ARRAYS[entry].get(k, ()) for k in ("columns", "levels", "int32", "optional", "in_place"))
+        fn, names = getattr(self.lib, "rrtmg_hip_" + entry), IN + tuple(outs) + DIAG
+        dtype = lambda n: np.dtype(np.int32 if n in int32 else np.float64)
+        if memspace:
+            if any(x is None for x in outs.values()) or ncol is None or nlay is None:
+                raise ValueError("%s: device pointers need %s, ncol and nlay" % (entry, ", ".join(outs)))
+            a.ncol, a.nlay = int(ncol), int(nlay)
+            diagnostics = diagnostics if isinstance(diagnostics, dict) else {}
+            for name, x in list(given.items()) + list(outs.items()) + list(diagnostics.items()):
+                if name not in names:
+                    raise ValueError("%s: no diagnostic %r" % (entry, name))
+                setattr(a, name, _device_pointer(x, dtype(name), name))
+            self._ck(fn(self.h, C.byref(a)))
+            return outs, diagnostics
+        mine, given = given, {n: np.ascontiguousarray(x, dtype=np.float64) for n, x in given.items()}
+        shape = given["t"].shape
+        profiles, cols = [n for n in IN if n not in columns + levels], [n for n in IN if n in columns]
+        if len(shape) != 2 or any(given[n].shape != shape for n in profiles if n in given) or any(given[n].shape != (shape[0] + 1, shape[1]) for n in levels):
+            raise ValueError("%s: %s%s must be [nlay][ncol] arrays of one shape and pint [nlay+1][ncol]"
+                             % (entry, ", ".join(n for n in profiles if n not in optional), "".join(" (and %s)" % n for n in profiles if n in optional)))
+        if any(given[n].shape != (shape[1],) for n in cols if n in given):
+            raise ValueError("%s: %s must be %s" % (entry, " and ".join(filter(None, (", ".join(cols[:-1]), cols[-1]))), "[ncol] arrays" if len(cols) > 1 else "an [ncol] array"))
+        size = lambda n: shape[1] if n in columns else shape[0] * shape[1]
+        empty = lambda n: np.empty(shape[1] if n in columns else shape, dtype=dtype(n))
+        outs = {n: (empty(n) if x is None else x) for n, x in outs.items()}
+        if diagnostics is True:
+            diagnostics = {n: empty(n) for n in DIAG}
+        elif not isinstance(diagnostics, dict):
+            diagnostics = {}
+        for name, x in list(outs.items()) + list(diagnostics.items()):
+            if name not in tuple(outs) + DIAG:
+                raise ValueError("%s: no diagnostic %r" % (entry, name))
+            if not (isinstance(x, np.ndarray) and x.dtype == dtype(name) and x.flags.c_contiguous and x.size == size(name)):
+                raise ValueError("%s: %s is written in place: a C-contiguous %s array of the right size" % (entry, name, dtype(name).name))
+        a.nlay, a.ncol = shape
+        for out, inp in in_place:
+            if outs[out] is mine[inp]:
+                given[inp] = outs[out]
+        for name, x in list(given.items()) + list(outs.items()) + list(diagnostics.items()):
+            setattr(a, name, x.ctypes.data)
+        self._ck(fn(self.h, C.byref(a)))
+        return outs, diagnostics
+
     @property
     def has_dry_adjustment(self):
         """Whether the library exports the dry convective adjustment (rrtmg_hip_dry_adjustment; probed by the symbol)."""
@@ -601,31 +666,10 @@ class Context:
         a.struct_size, a.memspace = C.sizeof(DryAdjust), 1 if memspace else 0
         for n in DRY_ADJUST_CONSTANTS:
             setattr(a, n, float(constants[n]))
-        if memspace:
-            f64 = PRECISIONS["float64"]
-            if t_out is None or q_out is None or ncol is None or nlay is None:
-                raise ValueError("dry_adjustment: device pointers need t_out, q_out, ncol and nlay")
-            a.ncol, a.nlay = int(ncol), int(nlay)
-            for name, v in (("t", t), ("q", q), ("pmid", pmid), ("pint", pint), ("t_out", t_out), ("q_out", q_out)):
-                setattr(a, name, _device_pointer(v, f64, name))
-            if mixed_top is not None:
-                a.mixed_top = _device_pointer(mixed_top, np.dtype(np.int32), "mixed_top")
-            self._ck(self.lib.rrtmg_hip_dry_adjustment(self.h, C.byref(a)))
-            return t_out, q_out, mixed_top
-        t, q, pmid, pint = (np.ascontiguousarray(v, dtype=np.float64) for v in (t, q, pmid, pint))
-        if t.ndim != 2 or q.shape != t.shape or pmid.shape != t.shape or pint.shape != (t.shape[0] + 1, t.shape[1]):
-            raise ValueError("dry_adjustment: t, q, pmid must be [nlay][ncol] arrays of one shape and pint [nlay+1][ncol]")
-        t_out = np.empty(t.shape) if t_out is None else t_out
-        q_out = np.empty(t.shape) if q_out is None else q_out
-        mixed_top = np.empty(t.shape[1], dtype=np.int32) if mixed_top is None else mixed_top
-        for name, v, dtype in (("t_out", t_out, np.float64), ("q_out", q_out, np.float64), ("mixed_top", mixed_top, np.int32)):
-            if not (isinstance(v, np.ndarray) and v.dtype == dtype and v.flags.c_contiguous and v.size == (t.shape[1] if name == "mixed_top" else t.size)):
-                raise ValueError("dry_adjustment: %s is written in place: a C-contiguous %s array of the right size" % (name, np.dtype(dtype).name))
-        a.nlay, a.ncol = t.shape
-        a.t, a.q, a.pmid, a.pint = t.ctypes.data, q.ctypes.data, pmid.ctypes.data, pint.ctypes.data
-        a.t_out, a.q_out, a.mixed_top = t_out.ctypes.data, q_out.ctypes.data, mixed_top.ctypes.data
-        self._ck(self.lib.rrtmg_hip_dry_adjustment(self.h, C.byref(a)))
-        return t_out, q_out, mixed_top
+        diagnostics = True if not memspace and mixed_top is None else {} if mixed_top is None else dict(mixed_top=mixed_top)
+        outs, diagnostics = self._column_call("dry_adjustment", a, dict(t=t, q=q, pmid=pmid, pint=pint), dict(t_out=t_out, q_out=q_out), diagnostics,
+                                              memspace, ncol, nlay)
+        return outs["t_out"], outs["q_out"], diagnostics.get("mixed_top")
 
     @property
     def has_boundary_layer(self):
@@ -655,38 +699,8 @@ class Context:
         given = dict(t=t, q=q, u=u, v=v, pmid=pmid, pint=pint, ps=ps, ts=ts, qs=qs)
         if external:
             given.update(sh_in=sh_in, lh_in=lh_in)
-        if memspace:
-            f64 = PRECISIONS["float64"]
-            if t_out is None or q_out is None or u_out is None or v_out is None or ncol is None or nlay is None:
-                raise ValueError("boundary_layer: device pointers need t_out, q_out, u_out, v_out, ncol and nlay")
-            a.ncol, a.nlay = int(ncol), int(nlay)
-            diagnostics = diagnostics if isinstance(diagnostics, dict) else {}
-            for name, x in list(given.items()) + [("t_out", t_out), ("q_out", q_out), ("u_out", u_out), ("v_out", v_out)] + list(diagnostics.items()):
-                if name not in BOUNDARY_LAYER_IN + BOUNDARY_LAYER_OUT + BOUNDARY_LAYER_DIAG:
-                    raise ValueError("boundary_layer: no diagnostic %r" % name)
-                setattr(a, name, _device_pointer(x, f64, name))
-            self._ck(self.lib.rrtmg_hip_boundary_layer(self.h, C.byref(a)))
-            return t_out, q_out, u_out, v_out, diagnostics
-        given = {n: np.ascontiguousarray(x, dtype=np.float64) for n, x in given.items()}
-        shape = given["t"].shape
-        if len(shape) != 2 or any(given[n].shape != shape for n in ("q", "u", "v", "pmid")) or given["pint"].shape != (shape[0] + 1, shape[1]):
-            raise ValueError("boundary_layer: t, q, u, v, pmid must be [nlay][ncol] arrays of one shape and pint [nlay+1][ncol]")
-        if any(x.shape != (shape[1],) for n, x in given.items() if n in ("ps", "ts", "qs", "sh_in", "lh_in")):
-            raise ValueError("boundary_layer: ps, ts, qs, sh_in and lh_in must be [ncol] arrays")
-        outs = {n: (np.empty(shape) if x is None else x) for n, x in (("t_out", t_out), ("q_out", q_out), ("u_out", u_out), ("v_out", v_out))}
-        if diagnostics is True:
-            diagnostics = {n: np.empty(shape[1]) for n in BOUNDARY_LAYER_DIAG}
-        elif not isinstance(diagnostics, dict):
-            diagnostics = {}
-        for name, x in list(outs.items()) + list(diagnostics.items()):
-            if name not in BOUNDARY_LAYER_OUT + BOUNDARY_LAYER_DIAG:
-                raise ValueError("boundary_layer: no diagnostic %r" % name)
-            if not (isinstance(x, np.ndarray) and x.dtype == np.float64 and x.flags.c_contiguous and x.size == (given["t"].size if name in outs else shape[1])):
-                raise ValueError("boundary_layer: %s is written in place: a C-contiguous float64 array of the right size" % name)
-        a.nlay, a.ncol = shape
-        for name, x in list(given.items()) + list(outs.items()) + list(diagnostics.items()):
-            setattr(a, name, x.ctypes.data)
-        self._ck(self.lib.rrtmg_hip_boundary_layer(self.h, C.byref(a)))
+        outs, diagnostics = self._column_call("boundary_layer", a, given, dict(t_out=t_out, q_out=q_out, u_out=u_out, v_out=v_out), diagnostics,
+                                              memspace, ncol, nlay)
         return outs["t_out"], outs["q_out"], outs["u_out"], outs["v_out"], diagnostics
 
     @property
@@ -717,43 +731,8 @@ class Context:
         given = dict(t=t, q=q, u=u, v=v, pmid=pmid, pint=pint, cbmf=cbmf)
         if qs is not None:
             given["qs"] = qs
-        if memspace:
-            f64 = PRECISIONS["float64"]
-            if ft is None or fq is None or fu is None or fv is None or cbmf_out is None or ncol is None or nlay is None:
-                raise ValueError("emanuel_convection: device pointers need ft, fq, fu, fv, cbmf_out, ncol and nlay")
-            a.ncol, a.nlay = int(ncol), int(nlay)
-            diagnostics = diagnostics if isinstance(diagnostics, dict) else {}
-            for name, x in list(given.items()) + [("ft", ft), ("fq", fq), ("fu", fu), ("fv", fv), ("cbmf_out", cbmf_out)] + list(diagnostics.items()):
-                if name not in EMANUEL_IN + EMANUEL_OUT + EMANUEL_DIAG + ("cbmf_out",):
-                    raise ValueError("emanuel_convection: no diagnostic %r" % name)
-                setattr(a, name, _device_pointer(x, np.dtype(np.int32) if name == "iflag" else f64, name))
-            self._ck(self.lib.rrtmg_hip_emanuel_convection(self.h, C.byref(a)))
-            return ft, fq, fu, fv, cbmf_out, diagnostics
-        given = {n: np.ascontiguousarray(x, dtype=np.float64) for n, x in given.items()}
-        shape = given["t"].shape
-        if len(shape) != 2 or any(given[n].shape != shape for n in ("q", "u", "v", "pmid", "qs") if n in given) or given["pint"].shape != (shape[0] + 1, shape[1]):
-            raise ValueError("emanuel_convection: t, q, u, v, pmid (and qs) must be [nlay][ncol] arrays of one shape and pint [nlay+1][ncol]")
-        if given["cbmf"].shape != (shape[1],):
-            raise ValueError("emanuel_convection: cbmf must be an [ncol] array")
-        outs = {n: (np.empty(shape) if x is None else x) for n, x in (("ft", ft), ("fq", fq), ("fu", fu), ("fv", fv))}
-        outs["cbmf_out"] = np.empty(shape[1]) if cbmf_out is None else cbmf_out
-        if diagnostics is True:
-            diagnostics = {n: np.empty(shape[1]) for n in EMANUEL_DIAG[:5]}
-            diagnostics.update(iflag=np.empty(shape[1], dtype=np.int32), ft_per_day=np.empty(shape))
-        elif not isinstance(diagnostics, dict):
-            diagnostics = {}
-        for name, x in list(outs.items()) + list(diagnostics.items()):
-            if name not in EMANUEL_OUT + EMANUEL_DIAG + ("cbmf_out",):
-                raise ValueError("emanuel_convection: no diagnostic %r" % name)
-            size = given["t"].size if name in EMANUEL_OUT + ("ft_per_day",) else shape[1]
-            if not (isinstance(x, np.ndarray) and x.dtype == (np.int32 if name == "iflag" else np.float64) and x.flags.c_contiguous and x.size == size):
-                raise ValueError("emanuel_convection: %s is written in place: a C-contiguous %s array of the right size" % (name, "int32" if name == "iflag" else "float64"))
-        a.nlay, a.ncol = shape
-        if outs["cbmf_out"] is cbmf_out and cbmf_out is cbmf:      # in place: the caller's own array, not the contiguous copy
-            given["cbmf"] = cbmf_out
-        for name, x in list(given.items()) + list(outs.items()) + list(diagnostics.items()):
-            setattr(a, name, x.ctypes.data)
-        self._ck(self.lib.rrtmg_hip_emanuel_convection(self.h, C.byref(a)))
+        outs, diagnostics = self._column_call("emanuel_convection", a, given, dict(ft=ft, fq=fq, fu=fu, fv=fv, cbmf_out=cbmf_out), diagnostics,
+                                              memspace, ncol, nlay)
         return outs["ft"], outs["fq"], outs["fu"], outs["fv"], outs["cbmf_out"], diagnostics
 
     @property
@@ -786,38 +765,8 @@ class Context:
             setattr(a, n, int(switches[n]))
         given = dict(t=t, q=q, u=u, v=v, pmid=pmid, pint=pint, ps=ps)
         given.update({n: x for n, x in (("ts", ts), ("qsurf", qsurf), ("lat", lat)) if x is not None})
-        if memspace:
-            f64 = PRECISIONS["float64"]
-            if t_out is None or q_out is None or u_out is None or v_out is None or ncol is None or nlay is None:
-                raise ValueError("simple_physics: device pointers need t_out, q_out, u_out, v_out, ncol and nlay")
-            a.ncol, a.nlay = int(ncol), int(nlay)
-            diagnostics = diagnostics if isinstance(diagnostics, dict) else {}
-            for name, x in list(given.items()) + [("t_out", t_out), ("q_out", q_out), ("u_out", u_out), ("v_out", v_out)] + list(diagnostics.items()):
-                if name not in SIMPLE_PHYSICS_IN + SIMPLE_PHYSICS_OUT + SIMPLE_PHYSICS_DIAG:
-                    raise ValueError("simple_physics: no diagnostic %r" % name)
-                setattr(a, name, _device_pointer(x, f64, name))
-            self._ck(self.lib.rrtmg_hip_simple_physics(self.h, C.byref(a)))
-            return t_out, q_out, u_out, v_out, diagnostics
-        given = {n: np.ascontiguousarray(x, dtype=np.float64) for n, x in given.items()}
-        shape = given["t"].shape
-        if len(shape) != 2 or any(given[n].shape != shape for n in ("q", "u", "v", "pmid")) or given["pint"].shape != (shape[0] + 1, shape[1]):
-            raise ValueError("simple_physics: t, q, u, v, pmid must be [nlay][ncol] arrays of one shape and pint [nlay+1][ncol]")
-        if any(x.shape != (shape[1],) for n, x in given.items() if n in ("ps", "ts", "qsurf", "lat")):
-            raise ValueError("simple_physics: ps, ts, qsurf and lat must be [ncol] arrays")
-        outs = {n: (np.empty(shape) if x is None else x) for n, x in (("t_out", t_out), ("q_out", q_out), ("u_out", u_out), ("v_out", v_out))}
-        if diagnostics is True:
-            diagnostics = {n: np.empty(shape[1]) for n in SIMPLE_PHYSICS_DIAG}
-        elif not isinstance(diagnostics, dict):
-            diagnostics = {}
-        for name, x in list(outs.items()) + list(diagnostics.items()):
-            if name not in SIMPLE_PHYSICS_OUT + SIMPLE_PHYSICS_DIAG:
-                raise ValueError("simple_physics: no diagnostic %r" % name)
-            if not (isinstance(x, np.ndarray) and x.dtype == np.float64 and x.flags.c_contiguous and x.size == (given["t"].size if name in outs else shape[1])):
-                raise ValueError("simple_physics: %s is written in place: a C-contiguous float64 array of the right size" % name)
-        a.nlay, a.ncol = shape
-        for name, x in list(given.items()) + list(outs.items()) + list(diagnostics.items()):
-            setattr(a, name, x.ctypes.data)
-        self._ck(self.lib.rrtmg_hip_simple_physics(self.h, C.byref(a)))
+        outs, diagnostics = self._column_call("simple_physics", a, given, dict(t_out=t_out, q_out=q_out, u_out=u_out, v_out=v_out), diagnostics,
+                                              memspace, ncol, nlay)
         return outs["t_out"], outs["q_out"], outs["u_out"], outs["v_out"], diagnostics
 
     @_locked

@@ -2,6 +2,7 @@
 //   rrtmg_hip_lw_adjust_surface   uflx' = uflx + duflx_dt * (tsfc_now - tsfc_call) at every level and the heating rates of the
 //                                 corrected net fluxes, all-sky and clear-sky stream in ONE launch: streaming (7 or 13 arrays read,
 //                                 2 or 4 written, once each), a handful of flops per element
+#include "rrtmg_column_call.h"   // the aliasing check of the column components
 #include "rrtmg_ctx.h"
 #include "rrtmg_lw_adjust.h"
 #include "rrtmg_lw_device.h"   // LwTab: the heatfac of rrtmg_hip_lw_init
@@ -19,10 +20,6 @@ __global__ void __launch_bounds__(64) lw_adjust_surface_kernel(LwAdjustCall a) {
   lw_adjust_thread(a, col, blockIdx.y, gridDim.y);
 }
 
-static bool overlap(const double *p, size_t n, const double *q, size_t m) {
-  return p && q && (uintptr_t)p < (uintptr_t)(q + m) && (uintptr_t)q < (uintptr_t)(p + n);
-}
-
 }  // namespace rrtmg
 
 using namespace rrtmg;
@@ -38,19 +35,14 @@ extern "C" int rrtmg_hip_lw_adjust_surface(rrtmg_ctx *ctx, const rrtmg_lw_adjust
   const int nclr = (a->uflxc != nullptr) + (a->dflxc != nullptr) + (a->duflxc_dt != nullptr), nclr_out = (a->uflxc_out != nullptr) + (a->hrc_out != nullptr);
   if ((nclr != 0 && nclr != 3) || nclr_out != (nclr ? 2 : 0))
     return ctx->fail(RRTMG_ERR_ARG, "lw_adjust_surface: the clear-sky stream is uflxc, dflxc, duflxc_dt, uflxc_out and hrc_out: all five, or none");
-  // (sizes in elements)
-  const size_t n1 = (size_t)a->ncol, nl = (size_t)a->nlay * n1, nl1 = nl + n1;
-  const struct { const double *p; size_t n; } in[] = {{a->tsfc_call, n1}, {a->tsfc_now, n1}, {a->plev, nl1}, {a->uflx, nl1}, {a->dflx, nl1},
-                                                      {a->duflx_dt, nl1}, {a->uflxc, nl1}, {a->dflxc, nl1}, {a->duflxc_dt, nl1}};
-  const struct { const double *p; size_t n; const double *may_be; const char *name; } out[] = {
-      {a->uflx_out, nl1, a->uflx, "uflx_out"}, {a->hr_out, nl, nullptr, "hr_out"}, {a->uflxc_out, nl1, a->uflxc, "uflxc_out"}, {a->hrc_out, nl, nullptr, "hrc_out"}};
-  for (size_t i = 0; i < sizeof out / sizeof out[0]; ++i) {
-    for (const auto &e : in)
-      if (overlap(out[i].p, out[i].n, e.p, e.n) && !(out[i].may_be && out[i].p == out[i].may_be && e.p == out[i].may_be))
-        return ctx->fail(RRTMG_ERR_ARG, "lw_adjust_surface: %s aliases an input%s", out[i].name, out[i].may_be ? " (in place: exactly the upward flux of its stream)" : "");
-    for (size_t j = 0; j < i; ++j)
-      if (overlap(out[i].p, out[i].n, out[j].p, out[j].n)) return ctx->fail(RRTMG_ERR_ARG, "lw_adjust_surface: %s overlaps %s", out[i].name, out[j].name);
-  }
+  // (sizes in bytes)
+  const size_t b1 = (size_t)a->ncol * sizeof(double), bl = (size_t)a->nlay * b1, bl1 = bl + b1;
+  const ColumnSpan spans[] = {{"tsfc_call", a->tsfc_call, b1}, {"tsfc_now", a->tsfc_now, b1}, {"plev", a->plev, bl1}, {"uflx", a->uflx, bl1}, {"dflx", a->dflx, bl1},
+      {"duflx_dt", a->duflx_dt, bl1}, {"uflxc", a->uflxc, bl1}, {"dflxc", a->dflxc, bl1}, {"duflxc_dt", a->duflxc_dt, bl1},
+      {"uflx_out", a->uflx_out, bl1, true, a->uflx}, {"hr_out", a->hr_out, bl, true}, {"uflxc_out", a->uflxc_out, bl1, true, a->uflxc}, {"hrc_out", a->hrc_out, bl, true}};
+  char msg[160];
+  if (aliasing_refusal(spans, sizeof spans / sizeof spans[0], " (in place: exactly the upward flux of its stream)", msg, sizeof msg))
+    return ctx->fail(RRTMG_ERR_ARG, "lw_adjust_surface: %s", msg);
   // heatfac is that of rrtmg_hip_lw_init: the status and the message of the flux call (call_begin)
   if (!ctx->lw_ready || !ctx->lw_desc) return ctx->fail(RRTMG_ERR_NOT_INITIALISED, "%s", "rrtmg_hip_lw_init has not been called");
   int rc = ctx_prepare_device(ctx);

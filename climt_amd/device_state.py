@@ -447,6 +447,34 @@ def slab_device_call(self, ds):
     return {"surface_temperature": tend}, {"depth_of_slab_surface": depth, "ocean_heat_transport_convergence": ds["ocean_heat_transport_convergence"]}
 
 
+def _one_pressure_unit(p, pi):
+    if not _same_units(p.units, pi.units):
+        raise ValueError("air_pressure is resident in %r, air_pressure_on_interface_levels in %r" % (p.units, pi.units))
+
+
+def _resident_pressures(ds, who, surface=False):
+    """air_pressure and air_pressure_on_interface_levels (with `surface`: and surface_air_pressure) for a column component, as
+    they are resident -- in the units of whichever component asked for them first: [mid_levels][*] and [interface_levels][*] in
+    the same units (and [*]).  (The convection scheme names the quantity that is resident otherwise: it checks the dims itself.)"""
+    got = [ds[n] for n in ("air_pressure", "air_pressure_on_interface_levels") + (("surface_air_pressure",) if surface else ())]
+    if any(tuple(x.dims) != dims for x, dims in zip(got, (("mid_levels", "*"), ("interface_levels", "*"), ("*",)))):
+        raise ValueError("the pressures are resident as %s and %s, %s wants [levels][*]%s" % (
+            ", ".join(str(x.dims) for x in got[:-1]), got[-1].dims, who, " and [*]" if surface else ""))
+    _one_pressure_unit(got[0], got[1])
+    return got
+
+
+def _step_work(self, ds, prefix, ncol):
+    """-> work(key, units, like=None, dtype): a column component's work buffer of this step, [ncol] or of the shape and dims of
+    `like`.  The buffers alternate with the step count, so the arrays the state held before the step stay what they were."""
+    slot = ds.step_count & 1
+
+    def work(key, units, like=None, dtype=np.float64):
+        shape, dims = ((ncol,), ("*",)) if like is None else (like.shape, like.dims)
+        return ds.work((prefix, id(self), key, slot), shape, dims, units, dtype)
+    return work
+
+
 def dry_adjustment_device_call(self, ds, timestep=None):
     """DryConvectiveAdjustment on a DeviceState: rrtmg_hip_dry_adjustment with device pointers on the main stream.  The
     pressures are read as they are resident -- in the units of whichever component asked for them first; only ratios and
@@ -455,18 +483,13 @@ def dry_adjustment_device_call(self, ds, timestep=None):
     the state is rebound to them: -> ({}, the same state)."""
     P = self.input_properties
     t, q = ds.need("air_temperature", P["air_temperature"]), ds.need("specific_humidity", P["specific_humidity"])
-    p, pi = ds["air_pressure"], ds["air_pressure_on_interface_levels"]
-    if tuple(p.dims) != ("mid_levels", "*") or tuple(pi.dims) != ("interface_levels", "*"):
-        raise ValueError("the pressures are resident as %s and %s, the adjustment wants [levels][*]" % (p.dims, pi.dims))
-    if not _same_units(p.units, pi.units):
-        raise ValueError("air_pressure is resident in %r, air_pressure_on_interface_levels in %r" % (p.units, pi.units))
+    p, pi = _resident_pressures(ds, "the adjustment")
     nlay, ncol = t.shape
     if p.shape != (nlay, ncol) or pi.shape != (nlay + 1, ncol) or q.shape != (nlay, ncol):
         raise ValueError("temperature %s, humidity %s and pressures %s, %s do not belong to one grid" % (t.shape, q.shape, p.shape, pi.shape))
     ds.join_streams()      # a longwave still in flight belongs to the step this adjustment closes
-    slot = ds.step_count & 1
-    t_new = ds.work(("dry", id(self), "t", slot), t.shape, t.dims, t.units)
-    q_new = ds.work(("dry", id(self), "q", slot), q.shape, q.dims, q.units)
+    work = _step_work(self, ds, "dry", ncol)
+    t_new, q_new = work("t", t.units, like=t), work("q", q.units, like=q)
     ds.ctx.dry_adjustment(t.ptr, q.ptr, p.ptr, pi.ptr, self.constants(p.units), t_out=t_new.ptr, q_out=q_new.ptr, memspace=1, ncol=ncol, nlay=nlay)
     ds["air_temperature"], ds["specific_humidity"] = t_new, q_new
     return {}, ds
@@ -483,11 +506,7 @@ def boundary_layer_device_call(self, ds, timestep):
     names = ("air_temperature", "specific_humidity", "eastward_wind", "northward_wind")
     t, q, u, v = (ds.need(n, P[n]) for n in names)
     ts, qs = ds.need("surface_temperature", P["surface_temperature"]), ds.need("surface_specific_humidity", P["surface_specific_humidity"])
-    p, pi, ps = ds["air_pressure"], ds["air_pressure_on_interface_levels"], ds["surface_air_pressure"]
-    if tuple(p.dims) != ("mid_levels", "*") or tuple(pi.dims) != ("interface_levels", "*") or tuple(ps.dims) != ("*",):
-        raise ValueError("the pressures are resident as %s, %s and %s, the boundary layer wants [levels][*] and [*]" % (p.dims, pi.dims, ps.dims))
-    if not _same_units(p.units, pi.units):
-        raise ValueError("air_pressure is resident in %r, air_pressure_on_interface_levels in %r" % (p.units, pi.units))
+    p, pi, ps = _resident_pressures(ds, "the boundary layer", surface=True)
     nlay, ncol = t.shape
     if any(x.shape != (nlay, ncol) for x in (q, u, v, p)) or pi.shape != (nlay + 1, ncol) or any(x.shape != (ncol,) for x in (ps, ts, qs)):
         raise ValueError("temperature %s, humidity %s, winds %s, %s, pressures %s, %s and surface values %s, %s, %s do not belong to one grid" % (
@@ -499,9 +518,8 @@ def boundary_layer_device_call(self, ds, timestep):
             raise ValueError("the prescribed surface fluxes %s, %s do not belong to the grid of %d columns" % (sh.shape, lh.shape, ncol))
         fluxes = dict(sh_in=sh.ptr, lh_in=lh.ptr)
     ds.join_streams()      # a longwave still in flight belongs to the step this component closes
-    slot = ds.step_count & 1
-    new = [ds.work(("bl", id(self), n, slot), x.shape, x.dims, x.units) for n, x in zip(names, (t, q, u, v))]
-    col = lambda key, units: ds.work(("bl", id(self), key, slot), (ncol,), ("*",), units)
+    col = _step_work(self, ds, "bl", ncol)
+    new = [col(n, x.units, like=x) for n, x in zip(names, (t, q, u, v))]
     d = dict(stress_north=col("stress_north", "Pa"), stress_east=col("stress_east", "Pa"), height=col("height", "m"))
     if self._flux_mode == 1:
         d.update(sh_out=col("sh", "W m^-2"), lh_out=col("lh", "W m^-2"))
@@ -510,8 +528,7 @@ def boundary_layer_device_call(self, ds, timestep):
                           self._flux_mode, t_out=new[0].ptr, q_out=new[1].ptr, u_out=new[2].ptr, v_out=new[3].ptr,
                           diagnostics={k: x.ptr for k, x in d.items()}, pressure_scale=to_pa(p.units), ps_scale=to_pa(ps.units),
                           memspace=1, ncol=ncol, nlay=nlay, **fluxes)
-    for n, x in zip(names, new):
-        ds[n] = x
+    ds.update(zip(names, new))
     diagnostics = {"northward_wind_stress": d["stress_north"], "eastward_wind_stress": d["stress_east"], "boundary_layer_height": d["height"]}
     if self._flux_mode == 1:
         diagnostics.update(surface_upward_sensible_heat_flux=d["sh_out"], surface_upward_latent_heat_flux=d["lh_out"])
@@ -537,22 +554,21 @@ def emanuel_device_call(self, ds, timestep):
             raise ValueError("quantity %r is resident in %r, component wants %r" % (n, x.units, P[n]["units"]))
     if tuple(pi.dims) != ("interface_levels", "*"):
         raise ValueError("air_pressure_on_interface_levels is resident as %s, the convection scheme wants [interface_levels][*]" % (pi.dims,))
-    if not _same_units(p.units, pi.units):
-        raise ValueError("air_pressure is resident in %r, air_pressure_on_interface_levels in %r" % (p.units, pi.units))
+    _one_pressure_unit(p, pi)
     nlay, ncol = t.shape
     if any(x.shape != (nlay, ncol) for x in (q, u, v, p)) or pi.shape != (nlay + 1, ncol) or cb.shape != (ncol,):
         raise ValueError("temperature %s, humidity %s, winds %s, %s, pressures %s, %s and mass flux %s do not belong to one grid" % (
             t.shape, q.shape, u.shape, v.shape, p.shape, pi.shape, cb.shape))
     ds.join_streams()      # a longwave still in flight may be reading the profiles' neighbours on its own stream; the sums follow on the main one
-    slot = ds.step_count & 1
+    work = _step_work(self, ds, "emanuel", ncol)
     T = self.tendency_properties
-    tend = {n: ds.work(("emanuel", id(self), n, slot), (nlay, ncol), ("mid_levels", "*"), T[n]["units"]) for n in names}
+    tend = {n: work(n, T[n]["units"], like=t) for n in names}
     D = self.diagnostic_properties
-    col = lambda key, name, dtype=np.float64: ds.work(("emanuel", id(self), key, slot), (ncol,), ("*",), D[name]["units"], dtype)
+    col = lambda key, name, dtype=np.float64: work(key, D[name]["units"], dtype=dtype)
     d = dict(precip=col("precip", "convective_precipitation_rate"), wd=col("wd", "convective_downdraft_velocity_scale"),
              tprime=col("tprime", "convective_downdraft_temperature_scale"), qprime=col("qprime", "convective_downdraft_specific_humidity_scale"),
              cape=col("cape", "atmosphere_convective_available_potential_energy"), iflag=col("iflag", "convective_state", np.int32),
-             ft_per_day=ds.work(("emanuel", id(self), "ft_per_day", slot), (nlay, ncol), ("mid_levels", "*"), "degK day^-1"))
+             ft_per_day=work("ft_per_day", "degK day^-1", like=t))
     cb_new = col("cbmf", "cloud_base_mass_flux")
     ds.ctx.emanuel_convection(t.ptr, q.ptr, u.ptr, v.ptr, p.ptr, pi.ptr, cb.ptr, timestep.total_seconds(), self.parameters(), self.constants(),
                               ft=tend[names[0]].ptr, fq=tend[names[1]].ptr, fu=tend[names[2]].ptr, fv=tend[names[3]].ptr, cbmf_out=cb_new.ptr,
@@ -578,27 +594,21 @@ def simple_physics_device_call(self, ds, timestep):
     names = ("air_temperature", "specific_humidity", "eastward_wind", "northward_wind")
     t, q, u, v = (ds.need(n, P[n]) for n in names)
     ts, qsurf, lat = (ds.need(n, P[n]) for n in ("surface_temperature", "surface_specific_humidity", "latitude"))
-    p, pi, ps = ds["air_pressure"], ds["air_pressure_on_interface_levels"], ds["surface_air_pressure"]
-    if tuple(p.dims) != ("mid_levels", "*") or tuple(pi.dims) != ("interface_levels", "*") or tuple(ps.dims) != ("*",):
-        raise ValueError("the pressures are resident as %s, %s and %s, the simple physics wants [levels][*] and [*]" % (p.dims, pi.dims, ps.dims))
-    if not _same_units(p.units, pi.units):
-        raise ValueError("air_pressure is resident in %r, air_pressure_on_interface_levels in %r" % (p.units, pi.units))
+    p, pi, ps = _resident_pressures(ds, "the simple physics", surface=True)
     nlay, ncol = t.shape
     if any(x.shape != (nlay, ncol) for x in (q, u, v, p)) or pi.shape != (nlay + 1, ncol) or any(x.shape != (ncol,) for x in (ps, ts, qsurf, lat)):
         raise ValueError("temperature %s, humidity %s, winds %s, %s, pressures %s, %s and surface values %s, %s, %s, %s do not belong to one grid" % (
             t.shape, q.shape, u.shape, v.shape, p.shape, pi.shape, ps.shape, ts.shape, qsurf.shape, lat.shape))
     ds.join_streams()      # a longwave still in flight belongs to the step this component closes
-    slot = ds.step_count & 1
-    new = [ds.work(("sp", id(self), n, slot), x.shape, x.dims, x.units) for n, x in zip(names, (t, q, u, v))]
-    col = lambda key, units: ds.work(("sp", id(self), key, slot), (ncol,), ("*",), units)
+    col = _step_work(self, ds, "sp", ncol)
+    new = [col(n, x.units, like=x) for n, x in zip(names, (t, q, u, v))]
     d = dict(precl=col("precl", "m s^-1"), sh_out=col("sh", "W m^-2"), lh_out=col("lh", "W m^-2"))
     to_pa = lambda units: float(_convert(np.float64(1.0), units, "Pa"))
     ds.ctx.simple_physics(t.ptr, q.ptr, u.ptr, v.ptr, p.ptr, pi.ptr, ps.ptr, timestep.total_seconds(), self.constants(), self.switches(),
                           ts=ts.ptr, qsurf=qsurf.ptr, lat=lat.ptr, t_out=new[0].ptr, q_out=new[1].ptr, u_out=new[2].ptr, v_out=new[3].ptr,
                           diagnostics={k: x.ptr for k, x in d.items()}, pressure_scale=to_pa(p.units), ps_scale=to_pa(ps.units),
                           memspace=1, ncol=ncol, nlay=nlay)
-    for n, x in zip(names, new):
-        ds[n] = x
+    ds.update(zip(names, new))
     return {"stratiform_precipitation_rate": d["precl"], "surface_upward_sensible_heat_flux": d["sh_out"],
             "surface_upward_latent_heat_flux": d["lh_out"]}, ds
 

@@ -91,6 +91,23 @@ def test_every_diagnostic_pointer_may_be_null(ctx):
         assert X.same_bits(some["height"], full["height"]) and X.same_bits(some["lh"], full["lh"]) and some["sh"] is None
 
 
+@pytest.mark.parametrize("mode", (1, 2))
+def test_each_diagnostic_left_out_leaves_the_others_their_bits(ctx, mode):
+    """Host pointers, 65 columns (two tiles, one live lane in the second) by 3 layers, bulk fluxes and prescribed ones (sh_in and
+    lh_in are staged as well): the staging buffer of a call is laid out over the arrays that are given, so every diagnostic in
+    turn is left out of an otherwise full call.  What is still asked for has the bits of the full call, in the caller's own
+    arrays, and the inputs keep theirs."""
+    c = X.case("varied", 3, 65, mode)
+    before = {k: np.array(c[k]) for k in X.INPUTS}
+    full = host_call(ctx, c, mode)
+    for left_out, key in zip(DIAG, X.DIAGNOSTICS):
+        diag = {n: np.full(65, -7.0) for n in DIAG if n != left_out}
+        got = host_call(ctx, c, mode, diagnostics=diag)
+        assert got[key] is None and all(got[k] is diag[n] for k, n in zip(X.DIAGNOSTICS, DIAG) if n != left_out)
+        assert all(X.same_bits(got[k], full[k]) for k in got if k != key), left_out
+        assert all(X.same_bits(c[k], before[k]) for k in X.INPUTS), left_out
+
+
 @pytest.mark.parametrize("mode", X.MODES)
 def test_in_place_host_and_device_pointers_agree_bit_for_bit(ctx, mode):
     for name, nlay, ncol in (("varied", 3, 1), ("heated", 30, 130), ("varied", 61, 65), ("calm", 2, 64)):

@@ -2,7 +2,9 @@
 tools/call_arrays_check.cpp prints the tables (and checks their extent functions and group predicates itself); here the set of
 (struct, member) pairs it prints is the set of grid-array members of the six call structs parsed from include/rrtmg_hip.h, and
 the standard outputs are SW_OUT / LW_OUT of climt_amd/_lib.py.  A member added to the header without a row in the tables
-fails here."""
+fails here.  The same for the tables of the four column components (csrc/rrtmg_column_call.h): tools/column_call_check.cpp
+prints them, and every pointer member of rrtmg_dry_adjust, rrtmg_boundary_layer, rrtmg_emanuel and rrtmg_simple_physics is one
+row, named as the *_IN, *_OUT and *_DIAG tuples of climt_amd/_lib.py name it."""
 import os
 import re
 import shutil
@@ -48,6 +50,64 @@ def tables(tmp_path_factory):
     rows = [dict(zip(("spectrum", "io", "struct", "member", "name", "wname", "extent", "k", "group", "flag"), line.split())) for line in out[:-2]]
     assert all(len(r) == 10 for r in rows)
     return rows
+
+
+COLUMN_STRUCTS = {"rrtmg_dry_adjust": "DRY_ADJUST", "rrtmg_boundary_layer": "BOUNDARY_LAYER", "rrtmg_emanuel": "EMANUEL", "rrtmg_simple_physics": "SIMPLE_PHYSICS"}
+
+
+@pytest.fixture(scope="module")
+def column_tables(tmp_path_factory):
+    """The rows tools/column_call_check.cpp prints (it checks the staging plan and the aliasing refusals itself): plain C++, no HIP."""
+    cxx = shutil.which("c++") or shutil.which("g++") or os.path.join(os.environ.get("ROCM_PATH", "/opt/rocm"), "lib", "llvm", "bin", "clang++")
+    exe = str(tmp_path_factory.mktemp("column_call") / "column_call_check")
+    subprocess.check_call([cxx, "-std=c++17", "-O1", os.path.join(ROOT, "tools", "column_call_check.cpp"), "-o", exe])
+    out = subprocess.run([exe], stdout=subprocess.PIPE, universal_newlines=True, check=True).stdout.split("\n")
+    assert out[-2:] == ["ok", ""]
+    rows = [dict(zip(("entry", "io", "struct", "member", "extent", "type", "flag", "in_place_of"), line.split())) for line in out[:-2]]
+    assert all(len(r) == 8 for r in rows)
+    return rows
+
+
+def column_header_members():
+    """-> {(struct, member): (is_output, type)} for every pointer member of the four column structs of include/rrtmg_hip.h."""
+    text = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "rrtmg_hip.h")).read(), flags=re.S)
+    found = {}
+    for s in COLUMN_STRUCTS:
+        body = re.search(r"typedef struct \{([^}]*)\} %s;" % s, text).group(1)
+        for const, ctype, names in re.findall(r"(const\s+)?(double|int32_t)\s+(\*[^;()]*);", body):
+            for n in names.split(","):
+                n = n.strip()
+                assert n.startswith("*") and "*" not in n[1:], (s, n)
+                found[(s, n[1:].strip())] = (not const, {"double": "f64", "int32_t": "i32"}[ctype])
+    return found
+
+
+def test_every_array_of_a_column_struct_is_one_row_of_its_table(column_tables):
+    header = column_header_members()
+    assert len(header) == 7 + 20 + 20 + 17
+    printed = {(r["struct"], r["member"]): (r["io"] == "out", r["type"]) for r in column_tables}
+    assert len(printed) == len(column_tables), "a member is listed twice"
+    assert set(printed) == set(header), (sorted(set(header) - set(printed)), sorted(set(printed) - set(header)))
+    assert printed == header      # const <-> input, and the element type
+
+
+def test_column_rows_agree_with_the_python_layer(column_tables):
+    from climt_amd import _lib
+    for struct, prefix in COLUMN_STRUCTS.items():
+        rows = [r for r in column_tables if r["struct"] == struct]
+        IN, OUT, DIAG = (getattr(_lib, "%s_%s" % (prefix, k)) for k in ("IN", "OUT", "DIAG"))
+        last = ("cbmf_out",) if struct == "rrtmg_emanuel" else ()      # behind the diagnostics in the struct; neither list has it
+        assert tuple(r["member"] for r in rows) == IN + OUT + DIAG + last
+        assert all((r["io"] == "in") == (r["member"] in IN) for r in rows)
+        assert all(r["flag"] == "required" for r in rows if r["member"] in OUT + last) and all(r["flag"] == "-" for r in rows if r["member"] in DIAG)
+        assert {r["member"]: r["in_place_of"] for r in rows if r["in_place_of"] != "-"} == (
+            {"cbmf_out": "cbmf"} if last else {n: n[:-4] for n in OUT})
+        arrays = _lib.COLUMN_ARRAYS[rows[0]["entry"]]
+        assert (arrays["IN"], arrays["DIAG"]) == (IN, DIAG)
+        for key, extent in (("columns", "[ncol]"), ("levels", "[nlay+1][ncol]")):      # the others: [nlay][ncol]
+            assert sorted(arrays.get(key, ())) == sorted(r["member"] for r in rows if r["extent"] == extent), (struct, key)
+        assert sorted(arrays.get("int32", ())) == sorted(r["member"] for r in rows if r["type"] == "i32"), struct
+        assert {"[ncol]", "[nlay+1][ncol]", "[nlay][ncol]"} >= {r["extent"] for r in rows}
 
 
 def test_every_grid_array_of_the_header_is_in_a_table(tables):

@@ -90,6 +90,29 @@ def test_in_place_host_and_device_pointers_agree_bit_for_bit(ctx, name):
             assert X.same_bits(td, t) and X.same_bits(qd, q) and (topd == top).all(), (name, nlay, ncol, in_place)
 
 
+def test_mixed_top_left_out_of_a_host_call_leaves_the_profiles_their_bits(ctx):
+    """Host pointers, 65 columns (two tiles, one live lane in the second) by 2 layers: the staging buffer of a call is laid out
+    over the arrays that are given.  Context.dry_adjustment always hands mixed_top over with host arrays, so the entry is called
+    here as C would call it, with mixed_top NULL: t_out and q_out have the bits of the full call and the inputs keep theirs."""
+    import ctypes as C
+    from climt_amd import _lib
+    c = X.case("two_runs", 2, 65)
+    t, q, top = host_call(ctx, c)
+    assert (top >= 0).any()
+    given = {k: np.ascontiguousarray(c[k], dtype=np.float64) for k in ("t", "q", "p", "p_int")}
+    before = {k: np.array(v) for k, v in given.items()}
+    t_out, q_out = np.full((2, 65), -7.0), np.full((2, 65), -7.0)
+    a = _lib.DryAdjust()
+    a.struct_size, a.memspace, a.nlay, a.ncol = C.sizeof(_lib.DryAdjust), 0, 2, 65
+    for n in _lib.DRY_ADJUST_CONSTANTS:
+        setattr(a, n, float(X.CONSTANTS[n]))
+    a.t, a.q, a.pmid, a.pint = (given[k].ctypes.data for k in ("t", "q", "p", "p_int"))
+    a.t_out, a.q_out, a.mixed_top = t_out.ctypes.data, q_out.ctypes.data, None
+    assert ctx.lib.rrtmg_hip_dry_adjustment(ctx.h, C.byref(a)) == 0
+    assert X.same_bits(t_out, t) and X.same_bits(q_out, q)
+    assert all(X.same_bits(given[k], before[k]) for k in given)
+
+
 def test_a_block_of_columns_alone_equals_the_block_inside_the_whole(ctx):
     for name in ("two_runs", "moist"):
         c = X.case(name, 30, 130)

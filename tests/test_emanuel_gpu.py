@@ -114,6 +114,28 @@ def test_every_diagnostic_pointer_may_be_null(ctx):
         assert same(some, full, keys + ("precip", "iflag")) and some["cape"] is None
 
 
+def test_each_diagnostic_left_out_leaves_the_others_their_bits(ctx):
+    """Host pointers, 65 columns (two tiles, one live lane in the second): the staging buffer of a call is laid out over the arrays
+    that are given, so every diagnostic in turn is left out of an otherwise full call, with qs handed over and with qs left to the
+    kernel (which changes the numbers, so each is compared with the full call of its own kind).  At 5 layers, the entry's minimum
+    plus one, where every column leaves by an early exit, and at 8, where the "deep" columns convect.  What is still asked for has
+    the bits of the full call, in the caller's own arrays, and the inputs keep theirs."""
+    f = X.load("deep", 8)
+    deep = X.tile(f, 65)
+    shallow = {k: deep[k] if k == "cbmf" else np.ascontiguousarray(deep[k][:6 if k == "ph" else 5]) for k in X.INPUTS}
+    for a in (shallow, deep):
+        before = {k: np.array(a[k]) for k in X.INPUTS}
+        for use_qs in (True, False):
+            full = host_call(ctx, a, f, use_qs)
+            assert (full["iflag"] == 1).all() == (a is deep)
+            for left_out in DIAG:
+                diag = {n: np.full(full[n].shape, -7, dtype=full[n].dtype) for n in DIAG if n != left_out}
+                got = host_call(ctx, a, f, use_qs, diagnostics=diag)
+                assert got[left_out] is None and all(got[n] is diag[n] for n in diag)
+                assert same(got, full, [k for k in full if k != left_out]), (a["t"].shape, use_qs, left_out)
+                assert all(X.same_bits(a[k], before[k]) for k in X.INPUTS)
+
+
 def test_qs_formed_by_the_kernel(ctx):
     """qs = NULL: the kernel's own bolton_q_sat (device exp) against the numpy one handed over -- within the fixtures' tolerances."""
     for case, nlay in FIXTURES:

@@ -99,6 +99,27 @@ def test_every_diagnostic_pointer_may_be_null(ctx):
         assert same({k: some[k] for k in X.PROFILES}, bare)
 
 
+def test_each_optional_array_left_out_leaves_the_others_their_bits(ctx):
+    """Host pointers, 65 columns (two tiles, one live lane in the second) by 2 layers, all three processes: the staging buffer of
+    a call is laid out over the arrays that are given, so every diagnostic, and every one of ts, qsurf and lat that the switches
+    leave unread, is in turn left out of an otherwise full call.  What is still asked for has the bits of the full call, in the
+    caller's own arrays, and the inputs keep theirs."""
+    c = X.case("varied", 2, 65, "all")
+    before = {k: np.array(c[k]) for k in X.INPUTS}
+    s = _switches(c)
+    read = dict(ts=s["use_ts_ext"] == 1, qsurf=s["use_qsurf_ext"] == 1, lat=s["use_ts_ext"] != 1 and s["test"] == 1)
+    assert s["do_surf_flux"] == 1 and not all(read.values())
+    full = host_call(ctx, c)
+    for left_out in DIAG + tuple(n for n in read if not read[n]):
+        diag = {n: np.full(65, -7.0) for n in DIAG if n != left_out}
+        columns = {n: c[n] for n in read if n != left_out}
+        got = _result(*ctx.simple_physics(c["t"], c["q"], c["u"], c["v"], c["p"], c["p_int"], c["ps"], X.DT, X.CONSTANTS, s, diagnostics=diag, **columns))
+        for key, n in zip(X.DIAGNOSTICS, DIAG):
+            assert got[key] is (None if n == left_out else diag[n])
+        assert all(X.same_bits(got[k], full[k]) for k in got if got[k] is not None), left_out
+        assert all(X.same_bits(c[k], before[k]) for k in X.INPUTS), left_out
+
+
 @pytest.mark.parametrize("sw", list(X.SWITCHES))
 def test_in_place_host_and_device_pointers_agree_bit_for_bit(ctx, sw):
     for name, nlay, ncol in (("varied", 1, 1), ("raining", 30, 130), ("varied", 61, 65), ("gale", 2, 64)):
