@@ -121,12 +121,6 @@ def check(got, f, ncol, what=""):
 
 
 # ---- tools/emanuel_check.cpp ------------------------------------------------------------------------------------------------------------
-def build_program(directory, name="emanuel_check", flags=("-O1",)):
-    exe = os.path.join(str(directory), name)
-    subprocess.check_call(["g++", "-std=c++17", "-ffp-contract=off"] + list(flags) + [os.path.join(os.path.dirname(HERE), "tools", "emanuel_check.cpp"), "-o", exe])
-    return exe
-
-
 def run_program(exe, tmp_path, arrays, dt, params=PARAMETERS, consts=CONSTANTS, use_qs=True, in_place=False, pressure_scale=1.0):
     """arrays: dict of INPUTS (qs may be None with use_qs False) -> dict of FIELDS, iflag and ft_per_day."""
     fin, fout = os.path.join(str(tmp_path), "in.bin"), os.path.join(str(tmp_path), "out.bin")

@@ -1,19 +1,14 @@
 // TEST INFRASTRUCTURE ONLY -- host emulation of the longwave DEVICE functions (see emu_sw.hip).
 #include <cmath>
-#include <cstring>
 #include <string>
 #include <vector>
 
 #include "../../climt_amd/csrc/rrtmg_lw_device.h"
 #include "../../climt_amd/csrc/rrtmg_lw_host.h"
-#include "../../climt_amd/csrc/rrtmg_sw_device.h"
 #include "../../include/rrtmg_hip.h"
+#include "emu_common.h"
 
 using namespace rrtmg;
-
-namespace rrtmg {
-void mt_mask_host(int ncol, int nlay, int nsub, int icld, int seed, const double *cldfr, std::vector<uint64_t> &mask, int nw, int col0 = 0, int ncol_total = 0);
-}
 
 // the clear-sky variant for cloud-free columns, as the device picks it per tile
 static bool emu_lw_cloudy(const LwDev &d, int col) {
@@ -32,18 +27,49 @@ static void emu_lw_solve(const LwDev &d, const LwTab &T) {
       else lw_solve_item<false, false>(d, T, T.item[slot], col, scr.data(), 1, sink);
     }
 }
+// The solve without the clear-sky outputs: a column with cloud through the ONE mode (lw_solve_all_allsky_kernel<true, MR>), a
+// cloud-free one through the cloud-free variant as ever, both into LwPartSinkAllsky's planes.  What the mode does not own is
+// poisoned and checked.  `part` has the DEFAULT layout's size (4 planes per item, 6 with idrv), of which the mode owns the first
+// nitem x 2 (3): everything behind them -- where the clear-sky planes of the default layout would start -- must stay as it was,
+// and so must the scratch slab (room for 4 g-points per (layer, row)) behind the LF_N x L x G doubles of an item of G g-points.
+// -> what went wrong, or nullptr
+static const char *emu_lw_solve_allsky(LwDev &d, const LwTab &T, std::vector<double> &part) {
+  const double poison = -7.0e300;
+  const size_t nl1 = (size_t)d.ncol * (d.nlay + 1);
+  const size_t part_full = (size_t)T.nitem * (d.idrv ? 6 : 4) * nl1, part_own = (size_t)T.nitem * lw_allsky_planes(d) * nl1;
+  part.assign(part_full, poison);
+  d.part = part.data();
+  std::vector<double> scr((size_t)LF_N * d.nlay * 4);
+  const bool maxrand = !d.mcica && d.icld >= 2;
+  for (int slot = 0; slot < T.nitem; ++slot)
+    for (int col = 0; col < d.ncol; ++col) {
+      LwPartSinkAllsky sink = lw_part_sink_allsky(d, slot, col);
+      for (double &v : scr) v = poison;
+      const bool cld = emu_lw_cloudy(d, col);
+      if (cld && maxrand) lw_solve_item<true, true, false, true>(d, T, T.item[slot], col, scr.data(), 1, sink);
+      else if (cld) lw_solve_item<true, false, false, true>(d, T, T.item[slot], col, scr.data(), 1, sink);
+      else lw_solve_item<false, false>(d, T, T.item[slot], col, scr.data(), 1, sink);
+      const int g = (T.item[slot] >> 16) & 0xf;
+      for (size_t i = (size_t)LF_N * d.nlay * g; i < scr.size(); ++i)
+        if (scr[i] != poison) return "all-sky-only mode wrote scratch behind its item's rows";
+    }
+  for (size_t i = 0; i < part_own; ++i)
+    if (part[i] == poison) return "all-sky-only mode left a total plane unwritten";
+  for (size_t i = part_own; i < part_full; ++i)
+    if (part[i] != poison) return "all-sky-only mode wrote a partial plane behind its own";
+  return nullptr;
+}
 
-// bp: the band fluxes requested (rrtmg_hip_lw_fluxes_bands), or NULL
-extern "C" int emu_lw_fluxes(const rrtmg_lw_args *a, const rrtmg_lw_band_fluxes *bp, const char *blob_path, double cpdair, const double *consts, char *errbuf, int errlen) {
-  auto fail = [&](int code, const std::string &m) { if (errbuf) { strncpy(errbuf, m.c_str(), errlen - 1); errbuf[errlen - 1] = 0; } return code; };
-  Blob blob;
+// bp: the band fluxes requested (rrtmg_hip_lw_fluxes_bands), or NULL.  clear_sky = 0: the call after
+// rrtmg_hip_set_lw_clear_sky(ctx, 0) -- uflxc, dflxc, hrc and duflxc_dt are not looked at, bp->upc and bp->dnc are refused.
+extern "C" int emu_lw_fluxes(const rrtmg_lw_args *a, const rrtmg_lw_band_fluxes *bp, int clear_sky, const char *blob_path, double cpdair, const double *consts,
+                             char *errbuf, int errlen) {
+  const EmuFail fail{errbuf, errlen};
+  if (!clear_sky && bp && (bp->upc || bp->dnc)) return fail(RRTMG_ERR_ARG, "longwave band fluxes upc / dnc need the clear-sky stream");
   std::string err;
-  if (!blob.load(blob_path, err)) return fail(3, err);
   TableSet ts;
-  Constants k{};
-  k.pi = consts[0]; k.grav = consts[1]; k.planck = consts[2]; k.boltz = consts[3]; k.clight = consts[4];
-  k.avogad = consts[5]; k.alosmt = consts[6]; k.gascon = consts[7]; k.sbcnst = consts[8]; k.secdy = consts[9];
-  if (!build_tables(blob, "lw", cpdair, k.grav, k.secdy, ts, err)) return fail(3, err);
+  Constants k;
+  if (!emu_tables(blob_path, "lw", cpdair, consts, ts, k, err)) return fail(3, err);
   LwTab T{};
   if (!build_lw_tab(ts, T, err)) return fail(3, err);
   T.t = ts.flat.data();
@@ -86,9 +112,11 @@ extern "C" int emu_lw_fluxes(const rrtmg_lw_args *a, const rrtmg_lw_band_fluxes 
   std::vector<uint64_t> mask, anym;
   const int nk = d.idrv ? 6 : 4;
   d.col0 = 0; d.pcols = N;
-  d.part = wd((size_t)kLwNGpt * nk * nl1);
-  d.uflx = a->uflx; d.dflx = a->dflx; d.hr = a->hr; d.uflxc = a->uflxc; d.dflxc = a->dflxc; d.hrc = a->hrc;
-  d.duflx_dt = a->duflx_dt; d.duflxc_dt = a->duflxc_dt;
+  std::vector<double> part_allsky;
+  if (clear_sky) d.part = wd((size_t)kLwNGpt * nk * nl1);   // (else: emu_lw_solve_allsky's)
+  d.uflx = a->uflx; d.dflx = a->dflx; d.hr = a->hr; d.duflx_dt = a->duflx_dt;
+  if (clear_sky) { d.uflxc = a->uflxc; d.dflxc = a->dflxc; d.hrc = a->hrc; d.duflxc_dt = a->duflxc_dt; }   // (else they stay nullptr, as in lw_fluxes_impl)
+  else if (!d.uflx || !d.dflx || !d.hr || (d.idrv && !d.duflx_dt)) return fail(RRTMG_ERR_ARG, "output array is NULL");
   int errflag = 0;
   d.err = &errflag;
   for (int c = 0; c < N; ++c) { for (int l = 0; l < L; ++l) lw_prep_layer(d, T, c, l); lw_prep_column(d, T, c); }
@@ -98,29 +126,30 @@ extern "C" int emu_lw_fluxes(const rrtmg_lw_args *a, const rrtmg_lw_band_fluxes 
       if (d.icld >= 2) { d.mr = wd(lw_mr_size(N, L)); for (int c = 0; c < N; ++c) lw_mr_column(d, c); }
     } else {
       for (int l = 0; l < L; ++l) for (int c = 0; c < N; ++c) lw_cloudmc_layer(d, T, c, l);
-      mask.assign((size_t)kLwNGpt * d.nw * N, 0);
       anym.assign((size_t)d.nw * N, 0);
-      d.mask = mask.data(); d.anymask = anym.data();
-      if (a->cldfmcl) {
-        for (int g = 0; g < kLwNGpt; ++g) for (int l = 0; l < L; ++l) for (int c = 0; c < N; ++c)
-          if (a->cldfmcl[((size_t)l * N + c) * kLwNGpt + g] > 1.e-12) mask[((size_t)g * d.nw + (l >> 6)) * N + c] |= 1ull << (l & 63);
-      } else if (a->irng == 0) {
-        for (int c = 0; c < N; ++c) kiss_mask_column(N, L, kLwNGpt, d.icld, a->permuteseed, d.play, d.cldfr, d.mask, d.nw, d.err, c);
-      } else {
-        mt_mask_host(N, L, kLwNGpt, d.icld, a->permuteseed, a->cldfr, mask, d.nw, a->shard_col0, a->shard_ncol);
-        d.mask = mask.data();
-      }
+      d.anymask = anym.data();
+      d.mask = emu_mcica_mask(a, kLwNGpt, d.icld, d.nw, d.err, mask);
       for (int c = 0; c < N; ++c) lw_anymask_column(d, c);
     }
   }
-  emu_lw_solve(d, T);
-  for (int lev = 0; lev <= L; ++lev) for (int c = 0; c < N; ++c) lw_flux_level(d, T, c, lev, T.nitem, emu_lw_cloudy(d, c));
-  for (int l = 0; l < L; ++l) for (int c = 0; c < N; ++c) lw_heat_layer(d, T, c, l);
-  if (bp) {   // as lw_bandflux_kernel maps its threads: every interface level, or the two boundary levels
+  if (!clear_sky) {   // the arithmetic of lw_solve_all_allsky_kernel and lw_fluxheat_allsky_kernel
+    if (const char *what = emu_lw_solve_allsky(d, T, part_allsky)) return fail(RRTMG_ERR_ARG, what);
+    for (int lev = 0; lev <= L; ++lev) for (int c = 0; c < N; ++c) lw_flux_level_allsky(d, T, c, lev, T.nitem);
+    for (int l = 0; l < L; ++l) for (int c = 0; c < N; ++c) lw_heat_layer_allsky(d, T, c, l);
+  } else {
+    emu_lw_solve(d, T);
+    for (int lev = 0; lev <= L; ++lev) for (int c = 0; c < N; ++c) lw_flux_level(d, T, c, lev, T.nitem, emu_lw_cloudy(d, c));
+    for (int l = 0; l < L; ++l) for (int c = 0; c < N; ++c) lw_heat_layer(d, T, c, l);
+  }
+  if (bp) {   // as lw_bandflux[_allsky]_kernel maps its threads: every interface level, or the two boundary levels
     const LwBandOut o{bp->up, bp->dn, bp->upc, bp->dnc};
     const int nrow = bp->levels ? 2 : L + 1;
     for (int row = 0; row < nrow; ++row)
-      for (int c = 0; c < N; ++c) lw_band_level(d, T, o, c, bp->levels ? (row ? L : 0) : row, row, nrow, emu_lw_cloudy(d, c));
+      for (int c = 0; c < N; ++c) {
+        const int lev = bp->levels ? (row ? L : 0) : row;
+        if (clear_sky) lw_band_level(d, T, o, c, lev, row, nrow, emu_lw_cloudy(d, c));
+        else lw_band_level_allsky(d, T, o, c, lev, row, nrow);
+      }
   }
   if (errflag) return fail(errflag, "device-side error flag " + std::to_string(errflag));
   return 0;
@@ -144,13 +173,10 @@ static void emu_taug_band(const LwDev &d, const LwTab &T, double *taug, double *
 }
 
 extern "C" int emu_lw_taumol(const rrtmg_lw_args *a, const char *blob_path, double cpdair, const double *consts, double *taug, double *fracs) {
-  Blob blob;
   std::string err;
-  if (!blob.load(blob_path, err)) return 3;
   TableSet ts;
-  Constants k{};
-  k.pi = consts[0]; k.grav = consts[1]; k.avogad = consts[5]; k.secdy = consts[9];
-  if (!build_tables(blob, "lw", cpdair, k.grav, k.secdy, ts, err)) return 3;
+  Constants k;
+  if (!emu_tables(blob_path, "lw", cpdair, consts, ts, k, err)) return 3;
   LwTab T{};
   if (!build_lw_tab(ts, T, err)) return 3;
   T.t = ts.flat.data();

@@ -3,25 +3,21 @@
 // Runs the very same __host__ __device__ per-thread functions the gfx950 kernels run
 // (climt_amd/csrc/rrtmg_sw_device.h), thread by thread on the CPU, so the device arithmetic can be
 // parity-checked in the build container (which has no GPU): the plain outputs, the flux components
-// (sw_components_level), the band fluxes (sw_band_level) and the surface albedo by band, through ONE
-// driver that mirrors sw_fluxes_impl.  It is compiled into tests/_emu/librrtmg_emu.so by
+// (sw_components_level), the band fluxes (sw_band_level), the surface albedo by band and the call without
+// the clear-sky outputs (rrtmg_hip_set_sw_clear_sky(ctx, 0)), through ONE driver that mirrors
+// sw_fluxes_impl.  It is compiled into tests/_emu/librrtmg_emu.so by
 // tests/emu/build.sh, is never loaded by the product, and is not a fallback: librrtmg_hip.so fails
 // loudly without a GPU.
 #include <cstdlib>
-#include <cstring>
 #include <string>
 #include <vector>
 
 #include "../../climt_amd/csrc/rrtmg_sw_device.h"
 #include "../../climt_amd/csrc/rrtmg_sw_host.h"
-#include "../../climt_amd/csrc/rrtmg_kiss_host.h"
 #include "../../include/rrtmg_hip.h"
+#include "emu_common.h"
 
 using namespace rrtmg;
-
-namespace rrtmg {
-void mt_mask_host(int ncol, int nlay, int nsub, int icld, int seed, const double *cldfr, std::vector<uint64_t> &mask, int nw, int col0 = 0, int ncol_total = 0);
-}
 
 // the clear-sky variant for cloud-free columns, as the device picks it per tile (here: per column)
 template <class Sink>
@@ -38,20 +34,37 @@ static void emu_solve(const SwDev &d, const SwTab &T, double *partdir) {
       else emu_solve_item(d, T, i, col, scr.data(), sw_part_sink(d, i, col));
     }
 }
+// The solve without the clear-sky outputs: the ONE mode where the device picks sw_solve_cloudy_allsky_kernel (per tile there, per
+// column here); only the F_RUP / F_RUPD rows of the slab are touched: the other half is poisoned and must stay so (false if not)
+static bool emu_solve_allsky(const SwDev &d, const SwTab &T) {
+  std::vector<double> scr((size_t)F_NTOT * d.nlay * 4);
+  const double poison = -7.0e300;
+  for (int col = 0; col < d.ncol; ++col)
+    for (int i = 0; i < T.nitem; ++i) {
+      SwPartSink sink = sw_part_sink(d, i, col);
+      if (d.anycld[col] == 0) { sw_solve_item<false>(d, T, T.t + T.exp_tbl, T.item[i], col, scr.data(), 1, sink); continue; }
+      for (double &v : scr) v = poison;
+      sw_solve_item<true, false, true>(d, T, T.t + T.exp_tbl, T.item[i], col, scr.data(), 1, sink);
+      const int g = item_g(T.item[i]);
+      for (int l = 0; l < d.nlay; ++l)
+        for (int f = F_NCLR; f < F_NTOT; ++f)
+          for (int q = 0; q < g; ++q)
+            if (scr[((size_t)l * F_NTOT + f) * g + q] != poison) return false;
+    }
+  return true;
+}
 
 // The widest shortwave entry point (rrtmg_hip_sw_fluxes_surface), as sw_fluxes_impl runs it: sf (surface albedo by band),
-// cp (flux components) and bp (band fluxes) may each be NULL.
+// cp (flux components) and bp (band fluxes) may each be NULL.  clear_sky = 0: the call after rrtmg_hip_set_sw_clear_sky(ctx, 0)
+// -- swuflxc, swdflxc and swhrc are not looked at, cp and bp are refused.
 extern "C" int emu_sw_fluxes(const rrtmg_sw_args *a, const rrtmg_sw_surface *sf, const rrtmg_sw_components *cp, const rrtmg_sw_band_fluxes *bp,
-                             const char *blob_path, double cpdair, const double *consts, char *errbuf, int errlen) {
-  auto fail = [&](int code, const std::string &m) { if (errbuf) { strncpy(errbuf, m.c_str(), errlen - 1); errbuf[errlen - 1] = 0; } return code; };
-  Blob blob;
+                             int clear_sky, const char *blob_path, double cpdair, const double *consts, char *errbuf, int errlen) {
+  const EmuFail fail{errbuf, errlen};
+  if (!clear_sky && (cp || bp)) return fail(RRTMG_ERR_ARG, "shortwave flux components and band fluxes need the clear-sky stream");
   std::string err;
-  if (!blob.load(blob_path, err)) return fail(3, err);
   TableSet ts;
-  Constants k{};
-  k.pi = consts[0]; k.grav = consts[1]; k.planck = consts[2]; k.boltz = consts[3]; k.clight = consts[4];
-  k.avogad = consts[5]; k.alosmt = consts[6]; k.gascon = consts[7]; k.sbcnst = consts[8]; k.secdy = consts[9];
-  if (!build_tables(blob, "sw", cpdair, k.grav, k.secdy, ts, err)) return fail(3, err);
+  Constants k;
+  if (!emu_tables(blob_path, "sw", cpdair, consts, ts, k, err)) return fail(3, err);
   SwTab T{};
   if (!build_sw_tab(ts, T, err)) return fail(3, err);
   T.t = ts.flat.data();
@@ -96,7 +109,9 @@ extern "C" int emu_sw_fluxes(const rrtmg_sw_args *a, const rrtmg_sw_surface *sf,
   d.part = wd((size_t)kSwNSlot * 4 * nl1);
   const bool need_dir = cp || (bp && (bp->dndir || bp->dndirc));   // as sw_fluxes_impl: the *_dir solve variants and their planes
   double *partdir = need_dir ? wd((size_t)kSwNSlot * 2 * nl1) : nullptr;
-  d.swuflx = a->swuflx; d.swdflx = a->swdflx; d.swhr = a->swhr; d.swuflxc = a->swuflxc; d.swdflxc = a->swdflxc; d.swhrc = a->swhrc;
+  d.swuflx = a->swuflx; d.swdflx = a->swdflx; d.swhr = a->swhr;
+  if (clear_sky) { d.swuflxc = a->swuflxc; d.swdflxc = a->swdflxc; d.swhrc = a->swhrc; }   // (else they stay nullptr, as in sw_fluxes_impl)
+  else if (!d.swuflx || !d.swdflx || !d.swhr) return fail(RRTMG_ERR_ARG, "output array is NULL");
   int errflag = 0;
   d.err = &errflag;
   for (int c = 0; c < N; ++c) { for (int l = 0; l < L; ++l) sw_prep_layer(d, T, c, l); sw_prep_column(d, T, c); }
@@ -119,23 +134,17 @@ extern "C" int emu_sw_fluxes(const rrtmg_sw_args *a, const rrtmg_sw_surface *sf,
   }
   if (d.icld >= 1) {
     for (int lay = 0; lay < L; ++lay) for (int c = 0; c < N; ++c) sw_cloud_layer(d, T, c, lay);
-    if (d.mcica) {
-      mask.assign((size_t)kSwNGpt * d.nw * N, 0);
-      d.mask = mask.data();
-      if (a->cldfmcl) {
-        for (int g = 0; g < kSwNGpt; ++g) for (int l = 0; l < L; ++l) for (int c = 0; c < N; ++c)
-          if (a->cldfmcl[((size_t)l * N + c) * kSwNGpt + g] > 1.e-12) mask[((size_t)g * d.nw + (l >> 6)) * N + c] |= 1ull << (l & 63);
-      } else if (a->irng == 0) {
-        for (int c = 0; c < N; ++c) kiss_mask_column(N, L, kSwNGpt, d.icld, a->permuteseed, d.play, d.cldfr, d.mask, d.nw, d.err, c);
-      } else {
-        mt_mask_host(N, L, kSwNGpt, d.icld, a->permuteseed, a->cldfr, mask, d.nw, a->shard_col0, a->shard_ncol);
-        d.mask = mask.data();
-      }
-    }
+    if (d.mcica) d.mask = emu_mcica_mask(a, kSwNGpt, d.icld, d.nw, d.err, mask);
   }
-  emu_solve(d, T, partdir);
-  for (int lev = 0; lev <= L; ++lev) for (int c = 0; c < N; ++c) sw_flux_level(d, T, c, lev, d.anycld[c] != 0);
-  for (int l = 0; l < L; ++l) for (int c = 0; c < N; ++c) sw_heat_layer(d, T, c, l);
+  if (!clear_sky) {   // the arithmetic of sw_solve_cloudy_allsky_kernel and sw_fluxheat_allsky_kernel
+    if (!emu_solve_allsky(d, T)) return fail(RRTMG_ERR_ARG, "all-sky-only mode wrote a clear-sky scratch row");
+    for (int lev = 0; lev <= L; ++lev) for (int c = 0; c < N; ++c) sw_flux_level_allsky(d, T, c, lev);
+    for (int l = 0; l < L; ++l) for (int c = 0; c < N; ++c) sw_heat_layer_allsky(d, T, c, l);
+  } else {
+    emu_solve(d, T, partdir);
+    for (int lev = 0; lev <= L; ++lev) for (int c = 0; c < N; ++c) sw_flux_level(d, T, c, lev, d.anycld[c] != 0);
+    for (int l = 0; l < L; ++l) for (int c = 0; c < N; ++c) sw_heat_layer(d, T, c, l);
+  }
   if (cp) {
     const SwCompOut o{cp->dirdflx, cp->difdflx, cp->dirdnuv, cp->difdnuv, cp->dirdnir, cp->difdnir, cp->dirdflxc, cp->difdflxc};
     for (int lev = 0; lev <= L; ++lev) for (int c = 0; c < N; ++c) sw_components_level(d, T, partdir, o, c, lev, d.anycld[c] != 0);

@@ -12,8 +12,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
-from climt_amd._lib import (LwArgs, SwArgs, LW_OUT, SW_OUT, SW_DATA, LW_DATA, _LW_FIELDS, _LW_FLAGS, _SW_FIELDS, _SW_FLAGS,  # noqa: E402
-                            LwBandFluxes, SwBandFluxes, SwComponents, SwSurface)
+from climt_amd._lib import (LwArgs, SwArgs, LW_OUT, LW_OUT_CLEAR, SW_OUT, SW_OUT_ALLSKY, SW_DATA, LW_DATA, _LW_FIELDS, _LW_FLAGS,  # noqa: E402
+                            _SW_FIELDS, _SW_FLAGS, LwBandFluxes, SwBandFluxes, SwComponents, SwSurface)
 
 GOLDEN = os.path.join(ROOT, "tests", "golden")
 EMU_SO = os.path.join(ROOT, "tests", "_emu", "librrtmg_emu.so")
@@ -37,6 +37,17 @@ def emu_lib():
         _emu.emu_get_table.restype = C.c_long
         _emu.emu_get_table.argtypes = [C.c_char_p, C.c_char_p, C.c_double, C.c_char_p, C.c_void_p, C.c_long]
     return _emu
+
+
+def build_host_program(tmp_path_factory, source, sanitized=False, flags=(), compiler=("c++",)):
+    """tools/<source>, a stand-alone host check program, compiled into a directory of its own -> the executable.  sanitized:
+    with the address and undefined-behaviour sanitizers, any finding fatal (the program is run directly, as the plain one);
+    flags: what matters to this program's result, -ffp-contract=off say."""
+    name = os.path.splitext(source)[0] + ("_san" if sanitized else "")
+    exe = str(tmp_path_factory.mktemp(name) / name)
+    opt = ["-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all"] if sanitized else ["-O1"]
+    subprocess.check_call(list(compiler) + ["-std=c++17"] + opt + list(flags) + [os.path.join(ROOT, "tools", source), "-o", exe])
+    return exe
 
 
 def _fill(a, inp, fields, flags, keep):
@@ -74,9 +85,10 @@ def _ptr_struct(cls, arrays, **head):
     return s
 
 
-def _emu_call(fn, a, structs, blob):
+def _emu_call(fn, a, structs, clear_sky, blob):
     eb = C.create_string_buffer(512)
-    rc = fn(C.byref(a), *[None if s is None else C.byref(s) for s in structs], blob.encode(), C.c_double(CPDAIR), _CONST_VEC.ctypes.data_as(C.c_void_p), eb, 512)
+    rc = fn(C.byref(a), *[None if s is None else C.byref(s) for s in structs], C.c_int(bool(clear_sky)), blob.encode(), C.c_double(CPDAIR),
+            _CONST_VEC.ctypes.data_as(C.c_void_p), eb, 512)
     if rc:
         from climt_amd._lib import RRTMGError
         raise RRTMGError(rc, eb.value.decode())
@@ -86,21 +98,23 @@ def _band_arrays(nband, nlay, ncol, levels, members):
     return None if members is None else {m: np.zeros((nband, 2 if levels == "boundaries" else nlay + 1, ncol)) for m in members}
 
 
-def emu_sw(inp, mcica, surface=None, components=None, bands=None, levels="all", surface_struct_size=None, blob=SW_DATA, out=None):
+def emu_sw(inp, mcica, surface=None, components=None, bands=None, levels="all", surface_struct_size=None, blob=SW_DATA, out=None, clear_sky=True):
     """The shortwave device functions on the host, through the one entry of tests/emu/emu_sw.hip (the shape of
     rrtmg_hip_sw_fluxes_surface).  surface: None, or {"albdir" / "albdif": [14][ncol] array | None} (surface_struct_size: a
     struct_size other than the right one); components / bands: None, or the names of the members wanted; levels: "all" |
-    "boundaries", the rows of the band arrays -> (plain outputs, component arrays | None, band arrays | None).  A refusal
-    raises RRTMGError."""
+    "boundaries", the rows of the band arrays -> (plain outputs, component arrays | None, band arrays | None).  clear_sky =
+    False: the call after rrtmg_hip_set_sw_clear_sky(ctx, 0) -- the clear-sky members stay NULL, the plain outputs are the three
+    all-sky ones.  A refusal raises RRTMGError."""
     nlay, ncol = inp["play"].shape
     a, keep = SwArgs(), []
     a.ncol, a.nlay, a.memspace, a.mcica = ncol, nlay, 0, int(bool(mcica))
     a.icld, a.inflgsw, a.iceflgsw, a.liqflgsw, a.dyofyr = 1, 2, 1, 1, 1
     a.adjes, a.scon, a.solcycfrac = float(inp.get("adjes", 1.0)), float(inp.get("scon", 1367.0)), float(inp.get("solcycfrac", 0.0))
     _fill(a, inp, _SW_FIELDS, _SW_FLAGS, keep)
+    wanted = [(k, lev) for k, lev in SW_OUT if clear_sky or k in SW_OUT_ALLSKY]
     if out is None:
-        out = {k: np.zeros((nlay + lev, ncol)) for k, lev in SW_OUT}
-    for k, _ in SW_OUT:
+        out = {k: np.zeros((nlay + lev, ncol)) for k, lev in wanted}
+    for k, _ in wanted:
         setattr(a, k, out[k].ctypes.data)
     sf = None
     if surface is not None:
@@ -111,26 +125,25 @@ def emu_sw(inp, mcica, surface=None, components=None, bands=None, levels="all", 
             sf.struct_size = surface_struct_size
     comp = None if components is None else {k: np.zeros((nlay + 1, ncol)) for k in components}
     band = _band_arrays(14, nlay, ncol, levels, bands)
-    _emu_call(emu_lib().emu_sw_fluxes, a, (sf, _ptr_struct(SwComponents, comp), _ptr_struct(SwBandFluxes, band, levels=int(levels == "boundaries"))), blob)
+    _emu_call(emu_lib().emu_sw_fluxes, a, (sf, _ptr_struct(SwComponents, comp), _ptr_struct(SwBandFluxes, band, levels=int(levels == "boundaries"))), clear_sky, blob)
     return out, comp, band
 
 
-def emu_lw(inp, mcica, bands=None, levels="all", blob=None, out=None):
-    """The longwave counterpart (tests/emu/emu_lw.hip, the shape of rrtmg_hip_lw_fluxes_bands) -> (plain outputs, band arrays | None)."""
+def emu_lw(inp, mcica, bands=None, levels="all", blob=None, out=None, clear_sky=True):
+    """The longwave counterpart (tests/emu/emu_lw.hip, the shape of rrtmg_hip_lw_fluxes_bands) -> (plain outputs, band arrays | None).
+    clear_sky = False: the call after rrtmg_hip_set_lw_clear_sky(ctx, 0); the plain outputs are uflx, dflx, hr (and duflx_dt)."""
     nlay, ncol = inp["play"].shape
     a, keep = LwArgs(), []
     a.ncol, a.nlay, a.memspace, a.mcica = ncol, nlay, 0, int(bool(mcica))
     a.icld, a.inflglw, a.iceflglw, a.liqflglw = 1, 2, 1, 1
     _fill(a, inp, _LW_FIELDS, _LW_FLAGS, keep)
     if out is None:
-        out = {k: np.zeros((nlay + lev, ncol)) for k, lev in LW_OUT}
-        if a.idrv:
-            out["duflx_dt"] = np.zeros((nlay + 1, ncol))
-            out["duflxc_dt"] = np.zeros((nlay + 1, ncol))
+        out = {k: np.zeros((nlay + lev, ncol)) for k, lev in LW_OUT + ((("duflx_dt", 1), ("duflxc_dt", 1)) if a.idrv else ())
+               if clear_sky or k not in LW_OUT_CLEAR}
     for k in out:
         setattr(a, k, out[k].ctypes.data)
     band = _band_arrays(16, nlay, ncol, levels, bands)
-    _emu_call(emu_lib().emu_lw_fluxes, a, (_ptr_struct(LwBandFluxes, band, levels=int(levels == "boundaries")),),
+    _emu_call(emu_lib().emu_lw_fluxes, a, (_ptr_struct(LwBandFluxes, band, levels=int(levels == "boundaries")),), clear_sky,
               blob or os.environ.get("RRTMG_HIP_LW_DATA") or LW_DATA)      # as climt_amd._lib.Context.lw_init
     return out, band
 

@@ -1,6 +1,6 @@
 """CPU tests of the shortwave call without the clear-sky outputs (rrtmg_hip_set_sw_clear_sky, Context.set_sw_clear_sky,
 RRTMGShortwave(clear_sky_diagnostics=False)): the C-ABI surface, the Python layer on the stand-in context, and the new mode of
-sw_solve_thread on the host (tests/emu_allsky) against the committed reference-Fortran fixtures."""
+sw_solve_thread on the host (tests/emu, clear_sky = 0) against the committed reference-Fortran fixtures."""
 import ctypes as C
 import inspect
 import json
@@ -13,14 +13,12 @@ import pytest
 
 import climt_amd
 from climt_amd.rrtmg import shortwave
-from helpers import CPDAIR, GOLDEN, REF_CASES, ROOT, EmuContext, _CONST_VEC, _fill, load_cache_case, load_ref_case, maxdiff
+from helpers import GOLDEN, REF_CASES, ROOT, EmuContext, emu_sw, load_cache_case, load_opt_case, load_ref_case, maxdiff
 
 RRTMG_ERR_ARG = 4
 TIGHT = 5.0e-9      # W m^-2 (K day^-1 for swhr): tests/test_sw_components_gpu.py
 ALLSKY = ("swuflx", "swdflx", "swhr")
 CLEAR = ("swuflxc", "swdflxc", "swhrc")
-EMU_DIR = os.path.join(ROOT, "tests", "emu_allsky")
-EMU_SO = os.path.join(ROOT, "tests", "_emu_allsky", "librrtmg_emu_allsky.so")
 
 
 def test_library_exports_the_symbol_with_the_declared_signature():
@@ -132,35 +130,10 @@ def test_a_context_without_the_setting_serves_the_default_only(monkeypatch):
 
 
 # ---- the new mode of sw_solve_thread on the host -------------------------------------------------------------------------------
-_emu = None
-
-
-def emu_allsky_lib():
-    global _emu
-    if _emu is None:
-        srcs = [os.path.join(EMU_DIR, f) for f in os.listdir(EMU_DIR)] + [os.path.join(ROOT, "climt_amd", "csrc", f) for f in os.listdir(os.path.join(ROOT, "climt_amd", "csrc"))]
-        if not os.path.exists(EMU_SO) or os.path.getmtime(EMU_SO) < max(os.path.getmtime(s) for s in srcs):
-            subprocess.check_call([os.path.join(EMU_DIR, "build.sh")])
-        _emu = C.CDLL(EMU_SO)
-    return _emu
-
-
-def emu_sw_allsky(inp, mcica):
-    """tests/emu_allsky/emu_sw_allsky.hip on the inputs `inp` -> {swuflx, swdflx, swhr}; the clear-sky members stay NULL."""
-    from climt_amd._lib import SW_DATA, _SW_FIELDS, _SW_FLAGS, SwArgs
+def sw_allsky_only(inp, mcica):
+    """helpers.emu_sw without the clear-sky outputs on the inputs `inp` -> {swuflx, swdflx, swhr}, NaN where nothing was written."""
     nlay, ncol = inp["play"].shape
-    a, keep = SwArgs(), []
-    a.ncol, a.nlay, a.memspace, a.mcica = ncol, nlay, 0, int(bool(mcica))
-    a.icld, a.inflgsw, a.iceflgsw, a.liqflgsw, a.dyofyr = 1, 2, 1, 1, 1
-    a.adjes, a.scon, a.solcycfrac = float(inp.get("adjes", 1.0)), float(inp.get("scon", 1367.0)), float(inp.get("solcycfrac", 0.0))
-    _fill(a, inp, _SW_FIELDS, _SW_FLAGS, keep)
-    out = {k: np.full((nlay + (k != "swhr"), ncol), np.nan) for k in ALLSKY}
-    for k in ALLSKY:
-        setattr(a, k, out[k].ctypes.data)
-    eb = C.create_string_buffer(512)
-    rc = emu_allsky_lib().emu_sw_fluxes_allsky(C.byref(a), SW_DATA.encode(), C.c_double(CPDAIR), _CONST_VEC.ctypes.data_as(C.c_void_p), eb, 512)
-    assert rc == 0, (rc, eb.value.decode())
-    return out
+    return emu_sw(inp, mcica, clear_sky=False, out={k: np.full((nlay + (k != "swhr"), ncol), np.nan) for k in ALLSKY})[0]
 
 
 CLOUDY_REF = tuple(n for n in REF_CASES if not n.startswith("clear"))
@@ -177,10 +150,35 @@ def test_emulated_allsky_only_mode_vs_reference_fixture(case):
     emulation unit poisons it and checks)."""
     c, mcica, exp = load_ref_case(case)
     assert (np.asarray(c["cldfr"]) > 0).any()
-    out = emu_sw_allsky(c, mcica)
+    out = sw_allsky_only(c, mcica)
     for k in ALLSKY:
         assert np.isfinite(out[k]).all(), k
         d = maxdiff(out[k], exp["sw"][k])
         print("%s %s: max |emulated - reference| = %.3e" % (case, k, d))
         assert d <= TIGHT, (case, k, d)
     assert float(np.abs(out["swdflx"] - exp["sw"]["swdflxc"]).max()) > 1.0      # (the clouds matter: all-sky != clear-sky here)
+
+
+@pytest.mark.parametrize("request_", [dict(components=("dirdflx", "difdflx")), dict(bands=("up", "dn")), dict(bands=("dndir",), levels="boundaries")])
+def test_emulated_allsky_only_mode_refuses_components_and_bands(request_):
+    """As sw_fluxes_impl: flux components and band fluxes need the clear-sky stream."""
+    from climt_amd._lib import RRTMGError
+    c, mcica, _ = load_ref_case("overcast_L60")
+    with pytest.raises(RRTMGError) as e:
+        emu_sw(c, mcica, clear_sky=False, **request_)
+    assert e.value.code == RRTMG_ERR_ARG, (e.value.code, str(e.value))
+    emu_sw(c, mcica, **request_)      # (the default mode serves the same request)
+
+
+def test_emulated_allsky_only_mode_with_ecmwf_aerosols_vs_reference_fixture():
+    """iaer = 6 (the six ECMWF aerosol types, mixed per band in the driver's set-up) on the cloudy option fixture: the all-sky
+    outputs within TIGHT of the reference Fortran, as in the default mode (tests/test_device_functions_emulated.py)."""
+    spectrum, mcica, c, exp = load_opt_case("sw_aer6_mcica")
+    assert spectrum == "sw" and c["iaer"] == 6 and (np.asarray(c["cldfr"]) > 0).any() and np.asarray(c["ecaer"]).max() > 0.0
+    out = sw_allsky_only(c, mcica)
+    for k in ALLSKY:
+        assert np.isfinite(out[k]).all(), k
+        d = maxdiff(out[k], exp[k])
+        print("sw_aer6_mcica %s: max |emulated - reference| = %.3e" % (k, d))
+        assert d <= TIGHT, (k, d)
+    assert float(np.abs(out["swdflx"] - exp["swdflxc"]).max()) > 1.0      # (the clouds matter)

@@ -12,7 +12,7 @@ import pytest
 import climt_amd
 from climt_amd import _lib
 from climt_amd.rrtmg import longwave, shortwave
-from helpers import ROOT, EmuContext
+from helpers import ROOT, EmuContext, build_host_program
 
 F32_SYMBOLS = ("rrtmg_hip_sw_fluxes_f32", "rrtmg_hip_lw_fluxes_f32", "rrtmg_hip_radiation_fluxes_f32")
 
@@ -43,12 +43,11 @@ def test_null_context_is_an_argument_error():
     assert lib.rrtmg_hip_radiation_fluxes_f32(None, C.byref(call)) == 4
 
 
-def test_precision_check_program(tmp_path):
+def test_precision_check_program(tmp_path_factory):
     """tools/precision_check.cpp -- the library's own element functions, split and per-entry loop on the CPU: every offset of
     0-3 elements, the counts 0, 1, 3, 4, 5, 63, 64, 65, 1027, +-0, subnormals, FLT_MIN and rounding ties against the C cast,
     guards intact -- compiles with the host compiler and reports ok."""
-    exe = str(tmp_path / "precision_check")
-    subprocess.check_call(["c++", "-std=c++17", "-O1", os.path.join(ROOT, "tools", "precision_check.cpp"), "-o", exe])
+    exe = build_host_program(tmp_path_factory, "precision_check.cpp")
     out = subprocess.check_output([exe]).decode()
     assert out.startswith("ok"), out
 

@@ -13,8 +13,8 @@ import subprocess
 import pytest
 
 from climt_amd._lib import LW_BAND_FLUXES, LW_OUT, SW_BAND_FLUXES, SW_COMPONENTS, SW_OUT
+from helpers import ROOT, build_host_program
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 STRUCTS = ("rrtmg_sw_args", "rrtmg_sw_surface", "rrtmg_sw_components", "rrtmg_sw_band_fluxes", "rrtmg_lw_args", "rrtmg_lw_band_fluxes")
 # double pointers of the structs that are deliberately in no table, each with its reason
 NOT_A_CALL_ARRAY = {
@@ -43,8 +43,7 @@ def header_members():
 @pytest.fixture(scope="module")
 def tables(tmp_path_factory):
     hipcc = shutil.which("hipcc") or os.path.join(os.environ.get("ROCM_PATH", "/opt/rocm"), "bin", "hipcc")
-    exe = str(tmp_path_factory.mktemp("call_arrays") / "call_arrays_check")
-    subprocess.check_call([hipcc, "--offload-arch=gfx950", "--offload-host-only", "-std=c++17", "-O1", os.path.join(ROOT, "tools", "call_arrays_check.cpp"), "-o", exe])
+    exe = build_host_program(tmp_path_factory, "call_arrays_check.cpp", compiler=[hipcc, "--offload-arch=gfx950", "--offload-host-only"])
     out = subprocess.run([exe], stdout=subprocess.PIPE, universal_newlines=True, check=True).stdout.split("\n")
     assert out[-2:] == ["ok", ""]
     rows = [dict(zip(("spectrum", "io", "struct", "member", "name", "wname", "extent", "k", "group", "flag"), line.split())) for line in out[:-2]]
@@ -58,9 +57,7 @@ COLUMN_STRUCTS = {"rrtmg_dry_adjust": "DRY_ADJUST", "rrtmg_boundary_layer": "BOU
 @pytest.fixture(scope="module")
 def column_tables(tmp_path_factory):
     """The rows tools/column_call_check.cpp prints (it checks the staging plan and the aliasing refusals itself): plain C++, no HIP."""
-    cxx = shutil.which("c++") or shutil.which("g++") or os.path.join(os.environ.get("ROCM_PATH", "/opt/rocm"), "lib", "llvm", "bin", "clang++")
-    exe = str(tmp_path_factory.mktemp("column_call") / "column_call_check")
-    subprocess.check_call([cxx, "-std=c++17", "-O1", os.path.join(ROOT, "tools", "column_call_check.cpp"), "-o", exe])
+    exe = build_host_program(tmp_path_factory, "column_call_check.cpp")
     out = subprocess.run([exe], stdout=subprocess.PIPE, universal_newlines=True, check=True).stdout.split("\n")
     assert out[-2:] == ["ok", ""]
     rows = [dict(zip(("entry", "io", "struct", "member", "extent", "type", "flag", "in_place_of"), line.split())) for line in out[:-2]]

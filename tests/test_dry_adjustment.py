@@ -15,7 +15,7 @@ import pytest
 import climt_amd
 from climt_amd import _lib
 from climt_amd._sympl_compat import DataArray
-from helpers import GOLDEN, ROOT, load_cache_case
+from helpers import GOLDEN, ROOT, build_host_program, load_cache_case
 
 import dry_adjust_cases as X
 
@@ -172,20 +172,14 @@ def test_mixing_conserves_enthalpy_and_water(name):
 
 
 # ---- the stand-alone host program -----------------------------------------------------------------------------------------------
-def _build(tmp_path_factory, name, flags):
-    exe = str(tmp_path_factory.mktemp(name) / name)
-    subprocess.check_call(["g++", "-std=c++17", "-ffp-contract=off"] + flags + [os.path.join(ROOT, "tools", "dry_adjust_check.cpp"), "-o", exe])
-    return exe
-
-
 @pytest.fixture(scope="module")
 def program(tmp_path_factory):
-    return _build(tmp_path_factory, "dry_adjust_check", ["-O1"])
+    return build_host_program(tmp_path_factory, "dry_adjust_check.cpp", flags=["-ffp-contract=off"])
 
 
 @pytest.fixture(scope="module")
 def program_sanitized(tmp_path_factory):
-    return _build(tmp_path_factory, "dry_adjust_check_san", ["-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all"])
+    return build_host_program(tmp_path_factory, "dry_adjust_check.cpp", sanitized=True, flags=["-ffp-contract=off"])
 
 
 def run_program(exe, tmp_path, t, q, p, p_int, in_place=False, constants=X.CONSTANTS):

@@ -22,7 +22,7 @@ import climt_amd
 from climt_amd import _lib
 from climt_amd import _sympl_compat as sc
 from climt_amd._sympl_compat import DataArray
-from helpers import GOLDEN, ROOT, load_cache_case
+from helpers import GOLDEN, ROOT, build_host_program, load_cache_case
 
 import emanuel_cases as X
 
@@ -242,12 +242,12 @@ def test_the_entry_refuses_bad_arguments(bare_context):
 # ---- the stand-alone host program -----------------------------------------------------------------------------------------------
 @pytest.fixture(scope="module")
 def program(tmp_path_factory):
-    return X.build_program(tmp_path_factory.mktemp("emanuel_check"))
+    return build_host_program(tmp_path_factory, "emanuel_check.cpp", flags=["-ffp-contract=off"])
 
 
 @pytest.fixture(scope="module")
 def program_sanitized(tmp_path_factory):
-    return X.build_program(tmp_path_factory.mktemp("emanuel_check_san"), "emanuel_check_san", ["-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all"])
+    return build_host_program(tmp_path_factory, "emanuel_check.cpp", sanitized=True, flags=["-ffp-contract=off"])
 
 
 def check_program(exe, tmp_path, case, nlay, ncol, **kwargs):

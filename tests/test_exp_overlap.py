@@ -13,7 +13,7 @@ import pytest
 import climt_amd
 from climt_amd import _lib
 from climt_amd.rrtmg import common, longwave, shortwave
-from helpers import ROOT, EmuContext
+from helpers import ROOT, EmuContext, build_host_program
 
 import exp_overlap_cases as X
 
@@ -43,16 +43,12 @@ def test_symbols_header_and_abi_version():
 
 
 # ---- the stand-alone host program ---------------------------------------------------------------------------------------------
-def _build(tmp_path_factory, name, flags):
-    exe = str(tmp_path_factory.mktemp(name) / name)
-    subprocess.check_call(["c++", "-std=c++17", "-ffp-contract=off", "-D__HIP_PLATFORM_AMD__", "-I" + os.path.join(ROCM, "include")] + flags
-                          + [os.path.join(ROOT, "tools", "exp_overlap_check.cpp"), "-o", exe])
-    return exe
+FLAGS = ["-ffp-contract=off", "-D__HIP_PLATFORM_AMD__", "-I" + os.path.join(ROCM, "include")]
 
 
 @pytest.fixture(scope="module")
 def program(tmp_path_factory):
-    return _build(tmp_path_factory, "exp_overlap_check", ["-O1"])
+    return build_host_program(tmp_path_factory, "exp_overlap_check.cpp", flags=FLAGS)
 
 
 @pytest.fixture(scope="module")
@@ -102,7 +98,7 @@ def test_host_program_equals_the_numpy_statement_bit_for_bit(program, draws, tmp
 
 def test_host_program_under_the_address_and_undefined_behaviour_sanitizers(tmp_path_factory, tmp_path, draws):
     """The same program, built with -fsanitize=address,undefined and run stand-alone: two mask words, both modes."""
-    exe = _build(tmp_path_factory, "exp_overlap_check_san", ["-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all"])
+    exe = build_host_program(tmp_path_factory, "exp_overlap_check.cpp", sanitized=True, flags=FLAGS)
     ncol, nlay = X.SHAPES[1]
     play, d = draws[(ncol, nlay)]
     cldfr, alpha = X.cloud_field(ncol, nlay), X.alpha_field("random", ncol, nlay)

@@ -14,7 +14,7 @@ import pytest
 
 import climt_amd
 from climt_amd import _lib
-from helpers import ROOT
+from helpers import ROOT, build_host_program
 
 import intermittent_cases as X
 
@@ -60,20 +60,14 @@ def test_symbols_header_and_python_layer():
 
 
 # ---- the stand-alone host program -----------------------------------------------------------------------------------------------
-def _build(tmp_path_factory, name, flags):
-    exe = str(tmp_path_factory.mktemp(name) / name)
-    subprocess.check_call(["c++", "-std=c++17", "-ffp-contract=off"] + flags + [os.path.join(ROOT, "tools", "mean_coszen_check.cpp"), "-o", exe])
-    return exe
-
-
 @pytest.fixture(scope="module")
 def program(tmp_path_factory):
-    return _build(tmp_path_factory, "mean_coszen_check", ["-O1"])
+    return build_host_program(tmp_path_factory, "mean_coszen_check.cpp", flags=["-ffp-contract=off"])
 
 
 @pytest.fixture(scope="module")
 def program_sanitized(tmp_path_factory):
-    return _build(tmp_path_factory, "mean_coszen_check_san", ["-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all"])
+    return build_host_program(tmp_path_factory, "mean_coszen_check.cpp", sanitized=True, flags=["-ffp-contract=off"])
 
 
 def run_mean(exe, tmp_path, lat, lon, t0=0.0, t1=0.0, sun=None, status=0):

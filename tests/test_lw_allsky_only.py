@@ -1,6 +1,6 @@
 """CPU tests of the longwave call without the clear-sky outputs (rrtmg_hip_set_lw_clear_sky, Context.set_lw_clear_sky,
 RRTMGLongwave(clear_sky_diagnostics=False)): the C-ABI surface, the Python layer on the stand-in context, and the one-stream
-mode of lw_solve_thread on the host (tests/emu_lw_allsky) against the committed reference-Fortran fixtures."""
+mode of lw_solve_thread on the host (tests/emu, clear_sky = 0) against the committed reference-Fortran fixtures."""
 import ctypes as C
 import inspect
 import json
@@ -11,16 +11,15 @@ import subprocess
 import numpy as np
 import pytest
 
+import band_cases as B
 import climt_amd
 from climt_amd.rrtmg import longwave
-from helpers import CPDAIR, GOLDEN, LWMR_CASES, REF_CASES, ROOT, EmuContext, _CONST_VEC, _fill, load_cache_case, load_lwmr_case, load_ref_case, maxdiff
+from helpers import GOLDEN, LWMR_CASES, REF_CASES, ROOT, EmuContext, emu_lw, load_cache_case, load_lwmr_case, load_ref_case, maxdiff
 
 RRTMG_ERR_ARG = 4
 TIGHT = 5.0e-9      # W m^-2 (K day^-1 for hr): the project's bound against the reference Fortran (tests/test_gpu_parity.py)
 ALLSKY = ("uflx", "dflx", "hr")
 CLEAR = ("uflxc", "dflxc", "hrc")
-EMU_DIR = os.path.join(ROOT, "tests", "emu_lw_allsky")
-EMU_SO = os.path.join(ROOT, "tests", "_emu_lw_allsky", "librrtmg_emu_lw_allsky.so")
 
 
 def test_library_exports_the_symbol_with_the_declared_signature():
@@ -169,35 +168,12 @@ def test_context_passes_null_for_the_absent_outputs():
 
 
 # ---- the one-stream mode of lw_solve_thread on the host ------------------------------------------------------------------------
-_emu = None
-
-
-def emu_allsky_lib():
-    global _emu
-    if _emu is None:
-        srcs = [os.path.join(EMU_DIR, f) for f in os.listdir(EMU_DIR)] + [os.path.join(ROOT, "climt_amd", "csrc", f) for f in os.listdir(os.path.join(ROOT, "climt_amd", "csrc"))]
-        if not os.path.exists(EMU_SO) or os.path.getmtime(EMU_SO) < max(os.path.getmtime(s) for s in srcs):
-            subprocess.check_call([os.path.join(EMU_DIR, "build.sh")])
-        _emu = C.CDLL(EMU_SO)
-    return _emu
-
-
-def emu_lw_allsky(inp, mcica):
-    """tests/emu_lw_allsky/emu_lw_allsky.hip on the inputs `inp` -> {uflx, dflx, hr[, duflx_dt]}; the clear-sky members stay NULL."""
-    from climt_amd._lib import LW_DATA, _LW_FIELDS, _LW_FLAGS, LwArgs
+def lw_allsky_only(inp, mcica, **kwargs):
+    """helpers.emu_lw without the clear-sky outputs on the inputs `inp` -> ({uflx, dflx, hr[, duflx_dt]}, NaN where nothing was
+    written; band arrays | None)."""
     nlay, ncol = inp["play"].shape
-    a, keep = LwArgs(), []
-    a.ncol, a.nlay, a.memspace, a.mcica = ncol, nlay, 0, int(bool(mcica))
-    a.icld, a.inflglw, a.iceflglw, a.liqflglw = 1, 2, 1, 1
-    _fill(a, inp, _LW_FIELDS, _LW_FLAGS, keep)
-    out = {k: np.full((nlay + (k != "hr"), ncol), np.nan) for k in ALLSKY + (("duflx_dt",) if a.idrv else ())}
-    for k in out:
-        setattr(a, k, out[k].ctypes.data)
-    eb = C.create_string_buffer(512)
-    blob = os.environ.get("RRTMG_HIP_LW_DATA") or LW_DATA
-    rc = emu_allsky_lib().emu_lw_fluxes_allsky(C.byref(a), blob.encode(), C.c_double(CPDAIR), _CONST_VEC.ctypes.data_as(C.c_void_p), eb, 512)
-    assert rc == 0, (rc, eb.value.decode())
-    return out
+    out = {k: np.full((nlay + (k != "hr"), ncol), np.nan) for k in ALLSKY + (("duflx_dt",) if inp.get("idrv") else ())}
+    return emu_lw(inp, mcica, clear_sky=False, out=out, **kwargs)
 
 
 CLOUDY_REF = tuple(n for n in REF_CASES if not n.startswith("clear"))
@@ -222,7 +198,7 @@ def test_emulated_allsky_only_mode_vs_reference_fixture(case):
     assert CLOUDY_REF == ("overcast_L60", "mcica_kiss_random", "mcica_kiss_maxrand", "mcica_mt_max")
     c, mcica, exp = load_ref_case(case)
     assert (np.asarray(c["cldfr"]) > 0).any()
-    check_against_reference(case, emu_lw_allsky(c, mcica), exp["lw"], ALLSKY)
+    check_against_reference(case, lw_allsky_only(c, mcica)[0], exp["lw"], ALLSKY)
 
 
 @pytest.mark.parametrize("case", LWMR_CASES)
@@ -230,6 +206,37 @@ def test_emulated_allsky_only_mode_vs_rtrnmr_fixture(case):
     """The same through MR = true (non-McICA maximum / random overlap, rtrnmr); maxrand_idrv also checks duflx_dt."""
     assert LWMR_CASES == ("maxrand", "maxrand_idrv", "maximum")
     c, exp = load_lwmr_case(case)
-    out = emu_lw_allsky(c, False)
+    out = lw_allsky_only(c, False)[0]
     assert ("duflx_dt" in out) == (case == "maxrand_idrv")
     check_against_reference(case, out, exp, ALLSKY + (("duflx_dt",) if "duflx_dt" in out else ()))
+
+
+CLOUDY_BAND_CASES = tuple(n for n in B.LW_CASES if B.CASES[n][0]["cloudy"])
+
+
+@pytest.mark.parametrize("case", CLOUDY_BAND_CASES)
+def test_emulated_allsky_only_band_fluxes_vs_reference_fixture(case):
+    """lw_band_level_allsky, the per-thread rule of lw_bandflux_allsky_kernel, on LwPartSinkAllsky's planes: up and dn by band
+    within TIGHT of the reference's own band sums (tests/golden/ref_bands_<case>.npz), and summing to uflx / dflx of the same
+    run within band_cases.SUM_BOUND; the clear-sky members are refused, as by the library."""
+    from climt_amd._lib import RRTMGError
+    assert CLOUDY_BAND_CASES == ("lw_mcica_kiss_random", "lw_maxrand", "lw_cloudy_L100")
+    c, mcica, bb, exp = B.load_case(case)
+    assert (np.asarray(c["cldfr"]) > 0).any()
+    out, band = lw_allsky_only(c, mcica, bands=("up", "dn"))
+    for m in ("up", "dn"):
+        k = B.BROADBAND["lw"][m]
+        assert np.isfinite(band[m]).all() and band[m].min() >= 0.0, m
+        d = maxdiff(band[m], exp[m])
+        print("%s %s by band: max |emulated - reference| = %.3e" % (case, m, d))
+        assert d <= TIGHT, (case, m, d)
+        assert maxdiff(out[k], bb[k]) <= TIGHT, (case, k)
+        assert np.all(np.abs(band[m].sum(axis=0) - out[k]) <= B.SUM_BOUND * np.abs(out[k])), (case, m)
+    assert float(np.abs(band["dn"] - exp["dnc"]).max()) > 1.0      # (the clouds matter, band by band too)
+    _, two = lw_allsky_only(c, mcica, bands=("up", "dn"), levels="boundaries")
+    nlay = c["play"].shape[0]
+    assert all(np.array_equal(two[m], band[m][:, [0, nlay]]) for m in ("up", "dn"))
+    for members in (("upc",), ("up", "dnc")):
+        with pytest.raises(RRTMGError) as e:
+            lw_allsky_only(c, mcica, bands=members)
+        assert e.value.code == RRTMG_ERR_ARG, (e.value.code, str(e.value))

@@ -2,13 +2,13 @@
 rrtmg_hip_set_sw_night_pack, RRTMGShortwave(pack_day_columns=True)), checked by hand on tiny fields, and of the component's
 constructor check.  The kernels are tested against these statements in tests/test_night_pack_gpu.py; the slot rule they use
 (csrc/rrtmg_permute.h) is checked against the same hand-written fields by tools/permute_check.cpp, built and run here."""
-import os
 import subprocess
 
 import numpy as np
 import pytest
 
 from climt_amd import night
+from helpers import build_host_program
 
 
 def check_invariants(cz):
@@ -104,9 +104,7 @@ def test_component_requires_the_skip():
         RRTMGShortwave(pack_day_columns=True, skip_night_columns=False)
 
 
-def test_permute_check_program(tmp_path):
+def test_permute_check_program(tmp_path_factory):
     """tools/permute_check.cpp -- the library's own slot rule, head and table builder on the CPU -- compiles and reports ok."""
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    exe = str(tmp_path / "permute_check")
-    subprocess.check_call(["c++", "-std=c++17", "-O1", os.path.join(root, "tools", "permute_check.cpp"), "-o", exe])
+    exe = build_host_program(tmp_path_factory, "permute_check.cpp")
     assert subprocess.run([exe], capture_output=True, text=True, check=True).stdout.strip() == "ok"

@@ -22,7 +22,7 @@ import pytest
 import climt_amd
 from climt_amd import _lib
 from climt_amd._sympl_compat import DataArray
-from helpers import GOLDEN, ROOT, load_cache_case
+from helpers import GOLDEN, ROOT, build_host_program, load_cache_case
 
 import simple_physics_cases as X
 
@@ -316,20 +316,14 @@ def test_surface_fluxes_equal_the_columns_gain(name):
 
 
 # ---- the stand-alone host program -----------------------------------------------------------------------------------------------
-def _build(tmp_path_factory, name, flags):
-    exe = str(tmp_path_factory.mktemp(name) / name)
-    subprocess.check_call(["g++", "-std=c++17", "-ffp-contract=off"] + flags + [os.path.join(ROOT, "tools", "simple_physics_check.cpp"), "-o", exe])
-    return exe
-
-
 @pytest.fixture(scope="module")
 def program(tmp_path_factory):
-    return _build(tmp_path_factory, "simple_physics_check", ["-O1"])
+    return build_host_program(tmp_path_factory, "simple_physics_check.cpp", flags=["-ffp-contract=off"])
 
 
 @pytest.fixture(scope="module")
 def program_sanitized(tmp_path_factory):
-    return _build(tmp_path_factory, "simple_physics_check_san", ["-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all"])
+    return build_host_program(tmp_path_factory, "simple_physics_check.cpp", sanitized=True, flags=["-ffp-contract=off"])
 
 
 def run_program(exe, tmp_path, arrays, switches, flags, dt=X.DT, constants=X.CONSTANTS, in_place=False, clamp=0, pressure_scale=1.0, ps_scale=1.0):
