@@ -20,6 +20,7 @@
 #include "rrtmg_call.h"
 #include "rrtmg_lw_device.h"
 #include "rrtmg_lw_host.h"
+#include "rrtmg_solve_map.h"
 
 namespace rrtmg {
 
@@ -90,28 +91,23 @@ __global__ void __launch_bounds__(64) lw_anymask_kernel(LwDev d) {
 // row (bank conflicts only) instead of a per-lane gather through the vector L1, whose return path (64 B/clk/CU) the
 // ~30 row gathers per layer saturated: with the rows through the scalar cache (an ablation) the kernel ran 23 %
 // faster, which bounded what staging could win.
-// Launch order: tile groups of kLwTileGroup, within a group items heaviest first (LwTab::sched), tile blocks fastest
-// -- the group's prep rows stay L2-resident while its items run.  Speed only, never correctness.
+// Launch order: blocks of kLwGroupBlocks workgroups = kLwTileGroup tiles (rrtmg_solve_map.h) -- the block's prep rows stay
+// L2-resident while its items run.  Speed only, never correctness.
 constexpr int kLwWgWaves = 4;
 constexpr int kLwTileGroup = 32;
 constexpr int kLwGroupBlocks = kLwTileGroup / kLwWgWaves;
 static_assert(kLwTileGroup % kLwWgWaves == 0, "tile group must be a whole number of workgroups");
 // Two variants are launched back to back (see sw_solve_all_kernel): CLD = false for the cloud-free tiles.
 // MR = true: non-McICA maximum/random overlap (rtrnmr).
+// (lw_solve_all_allsky_kernel below carries a copy of this kernel's body: routed through a shared body with the sink made by a
+//  lambda, all three instantiations came out with the same number of instructions in another order -- rung C of the acceptance
+//  ladder, docs/EXPERIMENTS.md -- so a change to the staging or the addressing here is made there too)
 template <bool CLD, bool MR>
 __global__ void __launch_bounds__(64 * kLwWgWaves) __attribute__((amdgpu_waves_per_eu(2))) lw_solve_all_kernel(LwDev d, LwTab T, int tile0, int ntile) {   // tiles tile0 .. tile0 + ntile - 1 (one column chunk)
-  // this variant's tiles, compacted (LwDev::tlist): nblk workgroups of kLwWgWaves list entries have work; they are the FIRST
-  // nblk x nitem of the dispatch order and dense in it (see sw_solve_all_kernel), in tile groups of kLwGroupBlocks workgroups
-  // -- the last group holds the remaining ones
   const int nmine = d.tcnt[CLD ? 1 : 0];
-  const int nblk = (nmine + kLwWgWaves - 1) / kLwWgWaves;
-  const int q = blockIdx.x;
-  if (q >= nblk * T.nitem) return;   // workgroup-uniform exit before the slice is staged
-  const int per = kLwGroupBlocks * T.nitem, nfull = nblk / kLwGroupBlocks;
-  const int bpg = q < nfull * per ? kLwGroupBlocks : nblk - nfull * kLwGroupBlocks, r = q < nfull * per ? q % per : q - nfull * per;
-  const int grp = q < nfull * per ? q / per : nfull;
-  const int k = r / bpg;
-  const int first = grp * kLwTileGroup + (r % bpg) * kLwWgWaves;
+  const SolveWork m = solve_map<kLwWgWaves, kLwGroupBlocks>(blockIdx.x, nmine, T.nitem);
+  if (!m.work) return;
+  const int first = m.first, k = m.k;
   RRTMG_PROFILE_ONLY_ITEM(d, k)
   const int slot = T.sched[k], item = T.item[slot];
   const int g = (item >> 16) & 0xf, ig0 = (item >> 8) & 0xff;
@@ -135,45 +131,58 @@ __global__ void __launch_bounds__(64 * kLwWgWaves) __attribute__((amdgpu_waves_p
   lw_solve_item<CLD, MR, kLdsK>(d, T, item, col, scr, 64, sink, sh_k);
 }
 
-
 // band integration AND heating rates in one launch (see sw_fluxheat_kernel)
 constexpr int kFluxLev = 15;   // 16 waves per workgroup: the halo level is 1 in 16 of the partial-plane reads
-__global__ void __launch_bounds__(64 * (kFluxLev + 1)) lw_fluxheat_kernel(LwDev d, LwTab T, int tile0) {
+// CLEAR = false: without the clear-sky half -- LwPartSinkAllsky's planes in EVERY tile; uflxc, dflxc, hrc and duflxc_dt are
+// never dereferenced
+template <bool CLEAR>
+__device__ __forceinline__ void lw_fluxheat_body(const LwDev &d, const LwTab &T, int tile0) {
   // (the call's last launch leaves the preparation kernels' cloudy-tile count where the host will look for it, and clears it)
   if (d.hint_out && blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) { *d.hint_out = *d.ncloudy; *d.ncloudy = 0; }
   const int tile = tile0 + blockIdx.x, lane = threadIdx.x & 63, j = threadIdx.x >> 6;
   const int col = tile * 64 + lane, lev = blockIdx.y * kFluxLev + j;
-  __shared__ double net[kFluxLev + 1][64], netc[kFluxLev + 1][64];
+  __shared__ double net[kFluxLev + 1][64], netc[CLEAR ? kFluxLev + 1 : 1][64];
   const bool act = col < d.ncol && lev <= d.nlay;
   if (act) {
-    double f[6];
-    lw_flux_sums(d, col, lev, T.nitem, d.tile_cld[tile] != 0, f);
+    double f[6];   // up, down, clear-sky up, clear-sky down, d(up)/dTs, clear-sky d(up)/dTs; without the clear-sky half: up, down, d(up)/dTs
+    if (CLEAR) lw_flux_sums(d, col, lev, T.nitem, d.tile_cld[tile] != 0, f);
+    else lw_flux_sums_allsky(d, col, lev, T.nitem, f);
     if (j < kFluxLev || lev == d.nlay) {
       const long o = (long)lev * d.ncol + col;
-      d.uflx[o] = f[0]; d.dflx[o] = f[1]; d.uflxc[o] = f[2]; d.dflxc[o] = f[3];
-      if (d.idrv) { d.duflx_dt[o] = f[4]; d.duflxc_dt[o] = f[5]; }
+      d.uflx[o] = f[0]; d.dflx[o] = f[1];
+      if (CLEAR) { d.uflxc[o] = f[2]; d.dflxc[o] = f[3]; }
+      if (d.idrv) {
+        d.duflx_dt[o] = f[CLEAR ? 4 : 2];
+        if (CLEAR) d.duflxc_dt[o] = f[5];
+      }
     }
-    net[j][lane] = f[0] - f[1]; netc[j][lane] = f[2] - f[3];
+    net[j][lane] = f[0] - f[1];
+    if (CLEAR) netc[j][lane] = f[2] - f[3];
   }
   __syncthreads();
   if (col < d.ncol && j < kFluxLev && lev < d.nlay) {
     const long o0 = (long)lev * d.ncol + col;
     const double dp = d.plev[o0] - d.plev[o0 + d.ncol];
     d.hr[o0] = T.heatfac * (net[j][lane] - net[j + 1][lane]) / dp;
-    d.hrc[o0] = T.heatfac * (netc[j][lane] - netc[j + 1][lane]) / dp;
+    if (CLEAR) d.hrc[o0] = T.heatfac * (netc[j][lane] - netc[j + 1][lane]) / dp;
   }
 }
+__global__ void __launch_bounds__(64 * (kFluxLev + 1)) lw_fluxheat_kernel(LwDev d, LwTab T, int tile0) { lw_fluxheat_body<true>(d, T, tile0); }
 
 // Band fluxes (rrtmg_hip_lw_fluxes_bands), launched per column chunk behind lw_fluxheat_kernel: one thread per (column,
 // level), lane = column, the per-band sums of lw_band_level (see sw_bandflux_kernel).  levels = 0: every interface level;
-// 1: a workgroup of two waves, row 0 = surface, row 1 = top.
+// 1: a workgroup of two waves, row 0 = surface, row 1 = top.  ALLSKY: on LwPartSinkAllsky's planes, the members up and dn (upc,
+// dnc: refused by the driver)
 constexpr int kBandLev = 4;
-__global__ void __launch_bounds__(64 * kBandLev) lw_bandflux_kernel(LwDev d, LwTab T, int tile0, LwBandOut o, int levels) {
+template <bool ALLSKY>
+__device__ __forceinline__ void lw_bandflux_body(const LwDev &d, const LwTab &T, int tile0, const LwBandOut &o, int levels) {
   const int tile = tile0 + blockIdx.x, col = tile * 64 + (threadIdx.x & 63), row = blockIdx.y * kBandLev + (threadIdx.x >> 6);
   const int lev = levels ? (row ? d.nlay : 0) : row;
   if (col >= d.ncol || row > (levels ? 1 : d.nlay)) return;
-  lw_band_level(d, T, o, col, lev, row, levels ? 2 : d.nlay + 1, d.tile_cld[tile] != 0);
+  if (ALLSKY) lw_band_level_allsky(d, T, o, col, lev, row, levels ? 2 : d.nlay + 1);
+  else lw_band_level(d, T, o, col, lev, row, levels ? 2 : d.nlay + 1, d.tile_cld[tile] != 0);
 }
+__global__ void __launch_bounds__(64 * kBandLev) lw_bandflux_kernel(LwDev d, LwTab T, int tile0, LwBandOut o, int levels) { lw_bandflux_body<false>(d, T, tile0, o, levels); }
 
 // ---- No clear-sky outputs (rrtmg_hip_set_lw_clear_sky(0); opt-in) ----------------------------------------------------------------
 // Kernels of their own, launched INSTEAD of lw_solve_all_kernel, lw_fluxheat_kernel and lw_bandflux_kernel when the clear-sky
@@ -186,14 +195,9 @@ __global__ void __launch_bounds__(64 * kBandLev) lw_bandflux_kernel(LwDev d, LwT
 template <bool CLD, bool MR>
 __global__ void __launch_bounds__(64 * kLwWgWaves) __attribute__((amdgpu_waves_per_eu(2))) lw_solve_all_allsky_kernel(LwDev d, LwTab T, int tile0, int ntile) {
   const int nmine = d.tcnt[CLD ? 1 : 0];
-  const int nblk = (nmine + kLwWgWaves - 1) / kLwWgWaves;
-  const int q = blockIdx.x;
-  if (q >= nblk * T.nitem) return;   // workgroup-uniform exit before the slice is staged
-  const int per = kLwGroupBlocks * T.nitem, nfull = nblk / kLwGroupBlocks;
-  const int bpg = q < nfull * per ? kLwGroupBlocks : nblk - nfull * kLwGroupBlocks, r = q < nfull * per ? q % per : q - nfull * per;
-  const int grp = q < nfull * per ? q / per : nfull;
-  const int k = r / bpg;
-  const int first = grp * kLwTileGroup + (r % bpg) * kLwWgWaves;
+  const SolveWork m = solve_map<kLwWgWaves, kLwGroupBlocks>(blockIdx.x, nmine, T.nitem);
+  if (!m.work) return;   // workgroup-uniform exit before the slice is staged
+  const int first = m.first, k = m.k;
   RRTMG_PROFILE_ONLY_ITEM(d, k)
   const int slot = T.sched[k], item = T.item[slot];
   const int g = (item >> 16) & 0xf, ig0 = (item >> 8) & 0xff;
@@ -215,38 +219,8 @@ __global__ void __launch_bounds__(64 * kLwWgWaves) __attribute__((amdgpu_waves_p
   LwPartSinkAllsky sink = lw_part_sink_allsky(d, slot, col);
   lw_solve_item<CLD, MR, true, CLD>(d, T, item, col, scr, 64, sink, sh_k);
 }
-// lw_fluxheat_kernel without the clear-sky half: LwPartSinkAllsky's planes in EVERY tile, the sums, differences and stores of
-// uflx, dflx, hr (and duflx_dt) as there
-__global__ void __launch_bounds__(64 * (kFluxLev + 1)) lw_fluxheat_allsky_kernel(LwDev d, LwTab T, int tile0) {
-  if (d.hint_out && blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) { *d.hint_out = *d.ncloudy; *d.ncloudy = 0; }
-  const int tile = tile0 + blockIdx.x, lane = threadIdx.x & 63, j = threadIdx.x >> 6;
-  const int col = tile * 64 + lane, lev = blockIdx.y * kFluxLev + j;
-  __shared__ double net[kFluxLev + 1][64];
-  const bool act = col < d.ncol && lev <= d.nlay;
-  if (act) {
-    double f[3];
-    lw_flux_sums_allsky(d, col, lev, T.nitem, f);
-    if (j < kFluxLev || lev == d.nlay) {
-      const long o = (long)lev * d.ncol + col;
-      d.uflx[o] = f[0]; d.dflx[o] = f[1];
-      if (d.idrv) d.duflx_dt[o] = f[2];
-    }
-    net[j][lane] = f[0] - f[1];
-  }
-  __syncthreads();
-  if (col < d.ncol && j < kFluxLev && lev < d.nlay) {
-    const long o0 = (long)lev * d.ncol + col;
-    const double dp = d.plev[o0] - d.plev[o0 + d.ncol];
-    d.hr[o0] = T.heatfac * (net[j][lane] - net[j + 1][lane]) / dp;
-  }
-}
-// lw_bandflux_kernel on LwPartSinkAllsky's planes: the members up and dn (upc, dnc: refused by the driver)
-__global__ void __launch_bounds__(64 * kBandLev) lw_bandflux_allsky_kernel(LwDev d, LwTab T, int tile0, LwBandOut o, int levels) {
-  const int tile = tile0 + blockIdx.x, col = tile * 64 + (threadIdx.x & 63), row = blockIdx.y * kBandLev + (threadIdx.x >> 6);
-  const int lev = levels ? (row ? d.nlay : 0) : row;
-  if (col >= d.ncol || row > (levels ? 1 : d.nlay)) return;
-  lw_band_level_allsky(d, T, o, col, lev, row, levels ? 2 : d.nlay + 1);
-}
+__global__ void __launch_bounds__(64 * (kFluxLev + 1)) lw_fluxheat_allsky_kernel(LwDev d, LwTab T, int tile0) { lw_fluxheat_body<false>(d, T, tile0); }
+__global__ void __launch_bounds__(64 * kBandLev) lw_bandflux_allsky_kernel(LwDev d, LwTab T, int tile0, LwBandOut o, int levels) { lw_bandflux_body<true>(d, T, tile0, o, levels); }
 
 void free_lw_desc(rrtmg_ctx *ctx) {
   delete (LwTab *)ctx->lw_desc;

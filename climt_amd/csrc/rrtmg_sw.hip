@@ -38,6 +38,7 @@
 #include "rrtmg_call.h"
 #include "rrtmg_sw_device.h"
 #include "rrtmg_sw_host.h"
+#include "rrtmg_solve_map.h"
 
 namespace rrtmg {
 
@@ -68,13 +69,17 @@ __global__ void __launch_bounds__(64 * kPrepWaves) sw_prep_fused_kernel(SwDev d,
   for (int l = w; l < d.nlay; l += kPrepWaves) sw_cloud_layer(d, T, col, l);
 }
 
-__global__ void __launch_bounds__(64) sw_cloud_kernel(SwDev d, SwTab T, int tile0) {
+// The band cloud optics of the cloudy tiles (flag 1; 0 = cloud-free: the clear-sky solve variant never reads the optics).
+// NIGHT: the flag may be 2, a night tile, which has none either.
+template <bool NIGHT>
+__device__ __forceinline__ void sw_cloud_body(const SwDev &d, const SwTab &T, int tile0) {
   const int tile = tile0 + blockIdx.x;
-  if (!d.tile_cld[tile]) return;   // cloud-free tile: the clear-sky solve variant never reads the cloud optics
+  if (NIGHT ? d.tile_cld[tile] != 1 : !d.tile_cld[tile]) return;
   const int col = tile * 64 + threadIdx.x;
   const int lay = blockIdx.y;
   if (col < d.ncol) sw_cloud_layer(d, T, col, lay);
 }
+__global__ void __launch_bounds__(64) sw_cloud_kernel(SwDev d, SwTab T, int tile0) { sw_cloud_body<false>(d, T, tile0); }
 
 // ECMWF aerosol mixing (iaer = 6), rrtmg_sw_rad.nomcica.f90:693-727 -> per-band tau/ssa/asm
 __global__ void __launch_bounds__(64) sw_aer_kernel(SwDev d, SwTab T, const double *ecaer, double *ta, double *om, double *as) {
@@ -125,32 +130,17 @@ __device__ __forceinline__ void sw_stage_slice(const SwTab &T, int item, double 
   const int ng = B.ng, sh = g == 4 ? 2 : 1, n = B.nrows << sh;
   for (int i = threadIdx.x; i < n; i += nthreads) sh_k[i] = src[(long)(i >> sh) * ng + (i & (g - 1))];
 }
-// Two kernels are launched back to back: this one handles the cloud-free tiles with the cloud code compiled out
-// (CLD = false: no spills, chunks of 4 g-points), sw_solve_cloudy_kernel the tiles flagged by sw_prep_kernel; a
-// wavefront whose tile belongs to the other kernel exits at once.
+// Two kernels are launched back to back: sw_solve_all_kernel<false> handles the cloud-free tiles with the cloud code compiled
+// out (CLD = false: no spills, chunks of 4 g-points), sw_solve_cloudy_kernel the tiles flagged by the preparation kernel.
 // The body of sw_solve_all_kernel and sw_solve_all_dir_kernel: make_sink(slot, col) -> the flux sink of the lane.
 template <bool CLD, class MakeSink>
 __device__ __forceinline__ void sw_solve_all_body(const SwDev &d, const SwTab &T, int tile0, MakeSink make_sink) {
-  // Launch order: BLOCKS of kSwGroupsPerBlock tile groups (128 tiles); within a block work items heaviest first, tile groups
-  // fastest -- a block's prep rows (58 MB at 60 layers) are read by its 32 work items while they are still cached, however many
-  // tiles the launch covers (a large chunk of a grid with both kinds of tiles: 2048 tiles are 0.94 GB of prep rows, re-read
-  // from HBM by every work item in item-major order).  Up to 128 tiles there is one block: the order of rounds 1-4.
-  // this variant's tiles, compacted (SwDev::tlist): ngrp groups of kSwWgWaves list entries HAVE work.  The launch was sized for
-  // every tile of the chunk (the host does not know the counts); the workgroups with work are the FIRST ngrp x nitem of the
-  // dispatch order and dense in it, the others exit at once behind them.  (A workgroup that exits at once still has to be
-  // PLACED with its 138 KB of LDS: interleaved with real ones -- a padded grid in round 2, or 8192 McICA columns with every
-  // fourth tile cloud-free before this mapping, 3.64 ms against 2.93 with clouds everywhere -- half the real workgroups wait
-  // for a CU that still holds another.)  The last block of the order holds the remaining groups.
-  const int nmine = d.tcnt[CLD ? 1 : 0];
-  const int ngrp = (nmine + kSwWgWaves - 1) / kSwWgWaves;
-  const int q = blockIdx.x, per = kSwGroupsPerBlock * T.nitem, nfull = ngrp / kSwGroupsPerBlock;
-  if (q >= ngrp * T.nitem) return;   // workgroup-uniform exit before the tables are staged
-  const int gpb = q < nfull * per ? kSwGroupsPerBlock : ngrp - nfull * kSwGroupsPerBlock, r = q < nfull * per ? q % per : q - nfull * per;
-  const int grp = (q < nfull * per ? q / per : nfull) * kSwGroupsPerBlock + r % gpb;
-  const int first = grp * kSwWgWaves;
+  const int nmine = d.tcnt[CLD ? 1 : 0];   // this variant's tiles, compacted (SwDev::tlist)
+  const SolveWork m = solve_map<kSwWgWaves, kSwGroupsPerBlock>(blockIdx.x, nmine, T.nitem);
+  if (!m.work) return;   // workgroup-uniform exit before the tables are staged
+  const int first = m.first, k = m.k;
   __shared__ double sh_exp[kExpTblN];
   for (int i = threadIdx.x; i < kExpTblN; i += 64 * kSwWgWaves) sh_exp[i] = T.t[T.exp_tbl + i];
-  const int k = r / gpb;
   RRTMG_PROFILE_ONLY_ITEM(d, k)
   const int id = T.sched[k], item = T.item[id], slot = id;
   constexpr bool kLdsK = true;
@@ -186,15 +176,14 @@ __global__ void __launch_bounds__(64 * kSwWgWaves) __attribute__((amdgpu_waves_p
 // flux kernel added the pair slots of the round-1 kernel: bit-identical, half the partial-plane traffic.
 constexpr int kC4Waves = 8;
 constexpr int kC4GroupsPerBlock = 16;   // x 8 tiles = 128 tiles per block of the launch order
-// (sw_solve_cloudy_body below is a copy of this kernel's body for sw_solve_cloudy_dir_kernel: a change to the tile mapping,
-//  launch order or staging here is made there too -- tests/test_sw_components.py checks that the two bodies agree)
+// (sw_solve_cloudy_body below is a copy of this kernel's body for sw_solve_cloudy_dir_kernel, and sw_solve_cloudy_allsky_kernel
+//  carries another with its own workgroup shape: a change to the staging or the addressing here is made there too --
+//  tests/test_sw_components.py and tests/test_allsky_only.py check that the bodies agree)
 __global__ void __launch_bounds__(64 * kC4Waves) __attribute__((amdgpu_waves_per_eu(2, 2))) sw_solve_cloudy_kernel(SwDev d, SwTab T, int tile0, int ntile) {
-  const int nmine = d.tcnt[1];   // the cloudy tiles, compacted (SwDev::tlist); the workgroups with work first and dense: see sw_solve_all_kernel
-  const int ngrp = (nmine + kC4Waves - 1) / kC4Waves;
-  const int q = blockIdx.x, per = kC4GroupsPerBlock * T.nitem, nfull = ngrp / kC4GroupsPerBlock;      // blocks of 128 tiles
-  if (q >= ngrp * T.nitem) return;
-  const int gpb = q < nfull * per ? kC4GroupsPerBlock : ngrp - nfull * kC4GroupsPerBlock, r = q < nfull * per ? q % per : q - nfull * per;
-  const int grp = (q < nfull * per ? q / per : nfull) * kC4GroupsPerBlock + r % gpb, first = grp * kC4Waves, k = r / gpb;
+  const int nmine = d.tcnt[1];   // the cloudy tiles, compacted (SwDev::tlist)
+  const SolveWork m = solve_map<kC4Waves, kC4GroupsPerBlock>(blockIdx.x, nmine, T.nitem);
+  if (!m.work) return;
+  const int first = m.first, k = m.k;
   RRTMG_PROFILE_ONLY_ITEM(d, k)
   const int id = T.sched[k], item = T.item[id], slot = id;      // one slot per chunk
   __shared__ __attribute__((aligned(16))) double sh_k[kSwSlabMaxRows * 4];
@@ -213,16 +202,15 @@ __global__ void __launch_bounds__(64 * kC4Waves) __attribute__((amdgpu_waves_per
   sw_solve_item<true, true>(d, T, sh_exp, item, col, scr, 64, sink, sh_k);
 }
 // The body of sw_solve_cloudy_dir_kernel: sw_solve_cloudy_kernel's with the sink made by make_sink (see sw_solve_all_body).
-// (sw_solve_cloudy_kernel keeps its own copy: routed through this template, its register assignment moved -- the same
-// instructions with permuted operands -- and its ISA is what the profiles and resource figures refer to.)
+// (sw_solve_cloudy_kernel keeps its own copy: routed through this template it comes out with the same number of instructions
+// in another order and on other registers -- rung C of the acceptance ladder, docs/EXPERIMENTS.md -- and its ISA is what the
+// profiles and resource figures refer to.)
 template <class MakeSink>
 __device__ __forceinline__ void sw_solve_cloudy_body(const SwDev &d, const SwTab &T, int tile0, MakeSink make_sink) {
-  const int nmine = d.tcnt[1];   // the cloudy tiles, compacted (SwDev::tlist); the workgroups with work first and dense: see sw_solve_all_kernel
-  const int ngrp = (nmine + kC4Waves - 1) / kC4Waves;
-  const int q = blockIdx.x, per = kC4GroupsPerBlock * T.nitem, nfull = ngrp / kC4GroupsPerBlock;      // blocks of 128 tiles
-  if (q >= ngrp * T.nitem) return;
-  const int gpb = q < nfull * per ? kC4GroupsPerBlock : ngrp - nfull * kC4GroupsPerBlock, r = q < nfull * per ? q % per : q - nfull * per;
-  const int grp = (q < nfull * per ? q / per : nfull) * kC4GroupsPerBlock + r % gpb, first = grp * kC4Waves, k = r / gpb;
+  const int nmine = d.tcnt[1];   // the cloudy tiles, compacted (SwDev::tlist)
+  const SolveWork m = solve_map<kC4Waves, kC4GroupsPerBlock>(blockIdx.x, nmine, T.nitem);
+  if (!m.work) return;
+  const int first = m.first, k = m.k;
   RRTMG_PROFILE_ONLY_ITEM(d, k)
   const int id = T.sched[k], item = T.item[id], slot = id;      // one slot per chunk
   __shared__ __attribute__((aligned(16))) double sh_k[kSwSlabMaxRows * 4];
@@ -288,13 +276,27 @@ __global__ void __launch_bounds__(64 * kCompLev) sw_components_kernel(SwDev d, S
 // Band fluxes (rrtmg_hip_sw_fluxes_bands), launched per column chunk behind sw_fluxheat_kernel (and sw_components_kernel):
 // one thread per (column, level), lane = column, the per-band sums of sw_band_level.  levels = 0: every interface level, row
 // = level; 1: a workgroup of two waves, row 0 = surface, row 1 = top.  A streaming kernel: it reads the requested partial
-// planes once more (see sw_components_kernel) and writes 14 rows per member.
+// planes once more (see sw_components_kernel) and writes 14 rows per member.  NIGHT: +0.0 for a night column.
 constexpr int kBandLev = 4;
-__global__ void __launch_bounds__(64 * kBandLev) sw_bandflux_kernel(SwDev d, SwTab T, int tile0, const double *partdir, SwBandOut o, int levels) {
+template <bool NIGHT>
+__device__ __forceinline__ void sw_bandflux_body(const SwDev &d, const SwTab &T, int tile0, const double *partdir, const SwBandOut &o, int levels) {
   const int tile = tile0 + blockIdx.x, col = tile * 64 + (threadIdx.x & 63), row = blockIdx.y * kBandLev + (threadIdx.x >> 6);
   const int lev = levels ? (row ? d.nlay : 0) : row;
   if (col >= d.ncol || row > (levels ? 1 : d.nlay)) return;
-  sw_band_level(d, T, partdir, o, col, lev, row, levels ? 2 : d.nlay + 1, d.tile_cld[tile] != 0);
+  const int nrow = levels ? 2 : d.nlay + 1;
+  if (NIGHT && d.coszen[col] <= 0.0) {
+    double *const m[6] = {o.up, o.dn, o.upc, o.dnc, o.dndir, o.dndirc};
+    for (int band = 0; band < kSwNBand; ++band) {
+      const long i = ((long)band * nrow + row) * d.ncol + col;
+      for (int k = 0; k < 6; ++k)
+        if (m[k]) m[k][i] = 0.0;
+    }
+    return;
+  }
+  sw_band_level(d, T, partdir, o, col, lev, row, nrow, d.tile_cld[tile] != 0);
+}
+__global__ void __launch_bounds__(64 * kBandLev) sw_bandflux_kernel(SwDev d, SwTab T, int tile0, const double *partdir, SwBandOut o, int levels) {
+  sw_bandflux_body<false>(d, T, tile0, partdir, o, levels);
 }
 
 // ---- Night-column skip (rrtmg_hip_set_sw_night_skip; opt-in) -----------------------------------------------------------------
@@ -318,8 +320,9 @@ __global__ void __launch_bounds__(64 * kPrepWaves) sw_prep_fused_night_kernel(Sw
     if (threadIdx.x == 0) { d.tile_cld[tile] = kTileNight; atomicAdd(night_cnt, 1); }
     return;
   }
-  // From here sw_prep_fused_kernel's body, a copy: that kernel routed through a shared body came out with other instructions,
-  // and its ISA is to stay the one of a library without the option -- a change to it is made here too.
+  // From here sw_prep_fused_kernel's body, a copy: that kernel routed through a shared body came out with other instructions
+  // (rung C of the acceptance ladder, docs/EXPERIMENTS.md), and its ISA is to stay the one of a library without the option -- a
+  // change to it is made here too (tests/test_night_skip.py checks that the two agree).
   const int w = threadIdx.x >> 6;
   __shared__ int sh_cld;
   extern __shared__ int sh_idx[];
@@ -337,13 +340,7 @@ __global__ void __launch_bounds__(64 * kPrepWaves) sw_prep_fused_night_kernel(Sw
   if (!sh_cld || !act) return;
   for (int l = w; l < d.nlay; l += kPrepWaves) sw_cloud_layer(d, T, col, l);
 }
-__global__ void __launch_bounds__(64) sw_cloud_night_kernel(SwDev d, SwTab T, int tile0) {
-  const int tile = tile0 + blockIdx.x;
-  if (d.tile_cld[tile] != 1) return;   // cloud-free tile, or night tile
-  const int col = tile * 64 + threadIdx.x;
-  const int lay = blockIdx.y;
-  if (col < d.ncol) sw_cloud_layer(d, T, col, lay);
-}
+__global__ void __launch_bounds__(64) sw_cloud_night_kernel(SwDev d, SwTab T, int tile0) { sw_cloud_body<true>(d, T, tile0); }
 // tile_lists_kernel with a third flag value that lands in neither list (the longwave never produces it: its list kernel stays as it is)
 __global__ void __launch_bounds__(64) sw_tile_lists_night_kernel(const int32_t *tile_cld, int ntile, int32_t *list, int32_t *cnt, int cap) {
   const int lane = threadIdx.x;
@@ -377,7 +374,9 @@ __global__ void __launch_bounds__(64) sw_kiss_mask_exp_night_kernel(int ncol, in
   if (act) kiss_mask_jump_exp(ncol, nlay, icld, play, cldfr, alpha, mask, nw, err, jumps, col, blockIdx.x);
 }
 // sw_fluxheat_kernel: a day column's sums, differences and stores are those of that kernel; a night column stores +0.0 and
-// reads neither the partial planes nor pdp
+// reads neither the partial planes nor pdp.  (A text of its own, like sw_components_night_kernel's and
+// sw_fluxheat_allsky_kernel's: over one body<NIGHT, CLEAR> all of them, sw_fluxheat_kernel included, came out with their
+// instructions in another order -- docs/EXPERIMENTS.md V)
 __global__ void __launch_bounds__(64 * (kFluxLev + 1)) sw_fluxheat_night_kernel(SwDev d, SwTab T, int tile0, int32_t *night_cnt, int32_t *night_out) {
   if (blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) {
     if (d.hint_out) { *d.hint_out = *d.ncloudy; *d.ncloudy = 0; }
@@ -426,20 +425,7 @@ __global__ void __launch_bounds__(64 * kCompLev) sw_components_night_kernel(SwDe
   sw_components_level(d, T, partdir, o, col, lev, d.tile_cld[tile] != 0);
 }
 __global__ void __launch_bounds__(64 * kBandLev) sw_bandflux_night_kernel(SwDev d, SwTab T, int tile0, const double *partdir, SwBandOut o, int levels) {
-  const int tile = tile0 + blockIdx.x, col = tile * 64 + (threadIdx.x & 63), row = blockIdx.y * kBandLev + (threadIdx.x >> 6);
-  const int lev = levels ? (row ? d.nlay : 0) : row;
-  if (col >= d.ncol || row > (levels ? 1 : d.nlay)) return;
-  const int nrow = levels ? 2 : d.nlay + 1;
-  if (d.coszen[col] <= 0.0) {
-    double *const m[6] = {o.up, o.dn, o.upc, o.dnc, o.dndir, o.dndirc};
-    for (int band = 0; band < kSwNBand; ++band) {
-      const long i = ((long)band * nrow + row) * d.ncol + col;
-      for (int k = 0; k < 6; ++k)
-        if (m[k]) m[k][i] = 0.0;
-    }
-    return;
-  }
-  sw_band_level(d, T, partdir, o, col, lev, row, nrow, d.tile_cld[tile] != 0);
+  sw_bandflux_body<true>(d, T, tile0, partdir, o, levels);
 }
 
 // ---- No clear-sky outputs (rrtmg_hip_set_sw_clear_sky(0); opt-in) ----------------------------------------------------------------
@@ -456,12 +442,10 @@ constexpr int kAsWaves = RRTMG_ALLSKY_WAVES;
 constexpr int kAsGroupsPerBlock = (128 + kAsWaves - 1) / kAsWaves;   // 128 tiles per block of the launch order (12 waves: 132)
 static_assert(kAsWaves == 8 || kAsWaves == 12 || kAsWaves == 16, "RRTMG_ALLSKY_WAVES: 8 (2 waves per SIMD), 12 (3) or 16 (4)");
 __global__ void __launch_bounds__(64 * kAsWaves) __attribute__((amdgpu_waves_per_eu(kAsWaves / 4, kAsWaves / 4))) sw_solve_cloudy_allsky_kernel(SwDev d, SwTab T, int tile0, int ntile) {
-  const int nmine = d.tcnt[1];   // the cloudy tiles, compacted (SwDev::tlist); the workgroups with work first and dense: see sw_solve_all_kernel
-  const int ngrp = (nmine + kAsWaves - 1) / kAsWaves;
-  const int q = blockIdx.x, per = kAsGroupsPerBlock * T.nitem, nfull = ngrp / kAsGroupsPerBlock;      // blocks of 128 tiles
-  if (q >= ngrp * T.nitem) return;
-  const int gpb = q < nfull * per ? kAsGroupsPerBlock : ngrp - nfull * kAsGroupsPerBlock, r = q < nfull * per ? q % per : q - nfull * per;
-  const int grp = (q < nfull * per ? q / per : nfull) * kAsGroupsPerBlock + r % gpb, first = grp * kAsWaves, k = r / gpb;
+  const int nmine = d.tcnt[1];   // the cloudy tiles, compacted (SwDev::tlist)
+  const SolveWork m = solve_map<kAsWaves, kAsGroupsPerBlock>(blockIdx.x, nmine, T.nitem);
+  if (!m.work) return;
+  const int first = m.first, k = m.k;
   RRTMG_PROFILE_ONLY_ITEM(d, k)
   const int id = T.sched[k], item = T.item[id], slot = id;      // one slot per chunk
   __shared__ __attribute__((aligned(16))) double sh_k[kSwSlabMaxRows * 4];

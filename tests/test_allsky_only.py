@@ -182,3 +182,23 @@ def test_emulated_allsky_only_mode_with_ecmwf_aerosols_vs_reference_fixture():
         print("sw_aer6_mcica %s: max |emulated - reference| = %.3e" % (k, d))
         assert d <= TIGHT, (k, d)
     assert float(np.abs(out["swdflx"] - exp["swdflxc"]).max()) > 1.0      # (the clouds matter)
+
+
+def _body(src, head):
+    """Statements of the function whose definition line starts with `head`, up to its closing brace at column 0."""
+    i = src.index(head)
+    i = src.index("{\n", i) + 2
+    return src[i:src.index("\n}\n", i)].splitlines()
+
+
+def test_allsky_cloudy_kernel_carries_the_cloudy_kernel_body():
+    """sw_solve_cloudy_allsky_kernel carries a copy of sw_solve_cloudy_kernel's body (as tests/test_sw_components.py holds
+    sw_solve_cloudy_body to it): with its own workgroup shape written as the default kernel's, the two agree but for the mode."""
+    src = open(os.path.join(ROOT, "climt_amd", "csrc", "rrtmg_sw.hip")).read()
+    a = _body(src, "__global__ void __launch_bounds__(64 * kC4Waves) __attribute__((amdgpu_waves_per_eu(2, 2))) sw_solve_cloudy_kernel(")
+    b = _body(src, "__global__ void __launch_bounds__(64 * kAsWaves)")
+    b = [x.replace("kAsWaves", "kC4Waves").replace("kAsGroupsPerBlock", "kC4GroupsPerBlock") for x in b]
+    assert len(a) == len(b) > 10
+    diff = [(x, y) for x, y in zip(a, b) if x != y]
+    assert diff == [("  sw_solve_item<true, true>(d, T, sh_exp, item, col, scr, 64, sink, sh_k);",
+                     "  sw_solve_item<true, true, true>(d, T, sh_exp, item, col, scr, 64, sink, sh_k);")], diff

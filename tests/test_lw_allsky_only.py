@@ -240,3 +240,24 @@ def test_emulated_allsky_only_band_fluxes_vs_reference_fixture(case):
         with pytest.raises(RRTMGError) as e:
             lw_allsky_only(c, mcica, bands=members)
         assert e.value.code == RRTMG_ERR_ARG, (e.value.code, str(e.value))
+
+
+def _body(src, head):
+    """Statements of the function whose definition line starts with `head`, up to its closing brace at column 0."""
+    i = src.index("\n", src.index(head)) + 1
+    return src[i:src.index("\n}\n", i)].splitlines()
+
+
+def test_allsky_solve_kernel_carries_the_solve_kernel_body():
+    """lw_solve_all_kernel keeps its own body (its ISA must not move) and lw_solve_all_allsky_kernel carries a copy of it: the
+    two agree line for line but for the sink and the mode (comments aside)."""
+    import re
+    src = open(os.path.join(ROOT, "climt_amd", "csrc", "rrtmg_lw.hip")).read()
+    head = "__global__ void __launch_bounds__(64 * kLwWgWaves) __attribute__((amdgpu_waves_per_eu(2))) "
+    strip = lambda lines: [re.sub(r"\s*//.*", "", x) for x in lines if not x.strip().startswith("//")]
+    a, b = strip(_body(src, head + "lw_solve_all_kernel(")), strip(_body(src, head + "lw_solve_all_allsky_kernel("))
+    a = [x for x in a if x != "  constexpr bool kLdsK = true;"]
+    assert len(a) == len(b) > 10
+    diff = [(x, y) for x, y in zip(a, b) if x != y]
+    assert diff == [("  LwPartSink sink = lw_part_sink(d, slot, col);", "  LwPartSinkAllsky sink = lw_part_sink_allsky(d, slot, col);"),
+                    ("  lw_solve_item<CLD, MR, kLdsK>(d, T, item, col, scr, 64, sink, sh_k);", "  lw_solve_item<CLD, MR, true, CLD>(d, T, item, col, scr, 64, sink, sh_k);")], diff

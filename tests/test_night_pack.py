@@ -108,3 +108,37 @@ def test_permute_check_program(tmp_path_factory):
     """tools/permute_check.cpp -- the library's own slot rule, head and table builder on the CPU -- compiles and reports ok."""
     exe = build_host_program(tmp_path_factory, "permute_check.cpp")
     assert subprocess.run([exe], capture_output=True, text=True, check=True).stdout.strip() == "ok"
+
+
+def _solve_map_lines(exe):
+    out = subprocess.run([exe], capture_output=True, text=True, check=True).stdout.split("\n")
+    assert out[-2:] == ["ok", ""]
+    return [tuple(int(x) for x in line.split()) for line in out[:-2]]
+
+
+# The first 40 workgroups of a longwave launch (4 wavefronts per workgroup, blocks of 8 workgroups, 38 work items) over 21 tiles
+# of the variant, (blockIdx.x, first list entry, position in sched), from the formulas lw_solve_all_kernel carried itself before
+# csrc/rrtmg_solve_map.h: nblk = 6, per = 304, nfull = 0, so bpg = 6, r = q, grp = 0, k = r / 6, first = (r % 6) * 4.
+SOLVE_MAP_FIRST_40 = [
+    (0, 0, 0), (1, 4, 0), (2, 8, 0), (3, 12, 0), (4, 16, 0), (5, 20, 0),
+    (6, 0, 1), (7, 4, 1), (8, 8, 1), (9, 12, 1), (10, 16, 1), (11, 20, 1),
+    (12, 0, 2), (13, 4, 2), (14, 8, 2), (15, 12, 2), (16, 16, 2), (17, 20, 2),
+    (18, 0, 3), (19, 4, 3), (20, 8, 3), (21, 12, 3), (22, 16, 3), (23, 20, 3),
+    (24, 0, 4), (25, 4, 4), (26, 8, 4), (27, 12, 4), (28, 16, 4), (29, 20, 4),
+    (30, 0, 5), (31, 4, 5), (32, 8, 5), (33, 12, 5), (34, 16, 5), (35, 20, 5),
+    (36, 0, 6), (37, 4, 6), (38, 8, 6), (39, 12, 6)]
+# ... and the workgroups 296 .. 311 over 45 tiles, across the end of the full block: nblk = 12, per = 304, nfull = 1; q < 304:
+# bpg = 8, r = q, grp = 0, k = r / 8 = 37, first = (r % 8) * 4; from 304 on: bpg = 4, r = q - 304, grp = 1, k = r / 4,
+# first = 32 + (r % 4) * 4.
+SOLVE_MAP_BLOCK_END = [
+    (296, 0, 37), (297, 4, 37), (298, 8, 37), (299, 12, 37), (300, 16, 37), (301, 20, 37), (302, 24, 37), (303, 28, 37),
+    (304, 32, 0), (305, 36, 0), (306, 40, 0), (307, 44, 0), (308, 32, 1), (309, 36, 1), (310, 40, 1), (311, 44, 1)]
+
+
+@pytest.mark.parametrize("sanitized", [False, True])
+def test_solve_map_check_program(tmp_path_factory, sanitized):
+    """tools/solve_map_check.cpp -- the solve kernels' one launch-order rule (csrc/rrtmg_solve_map.h) on the CPU, plain and under
+    the address and undefined-behaviour sanitizers: it checks exactly-once, dense dispatch, the promised order and the list
+    bound itself for every workgroup shape in use, and prints the mappings held against the hand-written list here."""
+    exe = build_host_program(tmp_path_factory, "solve_map_check.cpp", sanitized=sanitized)
+    assert _solve_map_lines(exe) == SOLVE_MAP_FIRST_40 + SOLVE_MAP_BLOCK_END

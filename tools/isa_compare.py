@@ -11,7 +11,8 @@ in a data section as the section's name and the 32 bytes found there -- so that 
 the object compare equal.  Prints one line per kernel of KERNELS (a prefix of the
 demangled name; all template instances are compared): "identical" or "DIFFERENT", with the instruction count.  --all: one
 line per function of the PARENT's code objects instead (every kernel a default call can launch), and a list of the functions
-only this build has."""
+only this build has.  --renamed: a function that differs is compared once more with the register NUMBERS masked (v12 -> v#,
+s[4:5] -> s[#x2]: class and width stay); the same instruction sequence on other registers is reported as "renamed"."""
 import argparse
 import os
 import re
@@ -102,14 +103,21 @@ def functions(lib):
     return funcs
 
 
-def compare(parent, this, every=False):
+def masked(body):
+    """`body` with every register number masked: what is left is the instruction sequence, the register classes and widths."""
+    wide = lambda m: "%s[#x%d]" % (m.group(1), int(m.group(3)) - int(m.group(2)) + 1)
+    return [re.sub(r"\b([vsa])\d+\b", r"\1#", re.sub(r"\b([vsa])\[(\d+):(\d+)\]", wide, ins)) for ins in body]
+
+
+def compare(parent, this, every=False, renamed=False):
     a, b = functions(parent), functions(this)
     lines, same = [], True
     if every:
         for n in sorted(a):
             ok = n in b and a[n] == b[n]
             same = same and ok
-            lines.append("%s  %s  (%d instructions)" % ("identical" if ok else "DIFFERENT" if n in b else "MISSING  ", n, len(a[n])))
+            word = "identical" if ok else "MISSING  " if n not in b else "renamed  " if renamed and masked(a[n]) == masked(b[n]) else "DIFFERENT"
+            lines.append("%s  %s  (%d instructions)" % (word, n, len(a[n])))
         lines += ["new        %s  (%d instructions)" % (n, len(b[n])) for n in sorted(set(b) - set(a))]
         return lines, same
     for k in KERNELS:
@@ -120,7 +128,8 @@ def compare(parent, this, every=False):
         for n in names:
             ok = n in a and n in b and a[n] == b[n]
             same = same and ok
-            lines.append("%s  %s  (%d instructions)" % ("identical" if ok else "DIFFERENT", n, len(b.get(n, a.get(n, [])))))
+            word = "identical" if ok else "renamed  " if renamed and n in a and n in b and masked(a[n]) == masked(b[n]) else "DIFFERENT"
+            lines.append("%s  %s  (%d instructions)" % (word, n, len(b.get(n, a.get(n, [])))))
     return lines, same
 
 
@@ -130,8 +139,9 @@ def main():
     ap.add_argument("this")
     ap.add_argument("-o", "--output")
     ap.add_argument("--all", action="store_true", help="every function of the parent's code objects, not only KERNELS")
+    ap.add_argument("--renamed", action="store_true", help="report a function that differs in register numbers only as \"renamed\"")
     args = ap.parse_args()
-    lines, same = compare(args.parent, args.this, args.all)
+    lines, same = compare(args.parent, args.this, args.all, args.renamed)
     text = "\n".join(["# tools/isa_compare.py: device code of the kernels below, parent commit's build vs this build (llvm-objdump -d of the",
                       "# gfx950 code objects, addresses normalised)"] + lines) + "\n"
     sys.stdout.write(text)
