@@ -1,7 +1,8 @@
 """climt_amd -- MI355X-native RRTMG longwave + shortwave radiation, drop-in for
 climt.RRTMGLongwave / climt.RRTMGShortwave (climt/_components/rrtmg/__init__.py:1-4), plus the zenith-angle producer
 upstream of the shortwave, climt.Instellation and climt.BergerSolarInsolation, and the consumer of the surface
-fluxes downstream, climt.SlabSurface, and climt.DryConvectiveAdjustment, climt.SimpleBoundaryLayer and climt.EmanuelConvection behind them; and what a model script needs to set the path up: get_grid / get_default_state
+fluxes downstream, climt.SlabSurface, and climt.DryConvectiveAdjustment, climt.SimpleBoundaryLayer and climt.EmanuelConvection behind them; the gray radiation path beside the RRTMG one
+(climt.GrayLongwaveRadiation, climt.Frierson06LongwaveOpticalDepth, climt.GridScaleCondensation); and what a model script needs to set the path up: get_grid / get_default_state
 (climt/_core/initialization.py), UpdateFrequencyWrapper and the AdamsBashforth tendency stepper."""
 import os as _os
 
@@ -21,11 +22,13 @@ from .instellation import Instellation  # noqa: F401,E402
 from .rrtmg import RRTMGLongwave, RRTMGShortwave, radiation_step  # noqa: F401,E402
 from .simple_boundary_layer import SimpleBoundaryLayer  # noqa: F401,E402
 from .simple_physics import SimplePhysics  # noqa: F401,E402
+from .gray_radiation import Frierson06LongwaveOpticalDepth, GrayLongwaveRadiation  # noqa: F401,E402
+from .grid_scale_condensation import GridScaleCondensation  # noqa: F401,E402
 from .emanuel import EmanuelConvection  # noqa: F401,E402
 from .slab_surface import SlabSurface  # noqa: F401,E402
 from .timestepping import AdamsBashforth  # noqa: F401,E402
 from .wrappers import UpdateFrequencyWrapper  # noqa: F401,E402
 from .intermittent import IntermittentLongwave, IntermittentShortwave  # noqa: F401,E402
 
-__all__ = ["RRTMGLongwave", "RRTMGShortwave", "Instellation", "BergerSolarInsolation", "SlabSurface", "DryConvectiveAdjustment", "SimpleBoundaryLayer", "EmanuelConvection", "SimplePhysics", "get_grid", "get_default_state", "UpdateFrequencyWrapper", "IntermittentShortwave", "IntermittentLongwave", "AdamsBashforth",
+__all__ = ["RRTMGLongwave", "RRTMGShortwave", "Instellation", "BergerSolarInsolation", "SlabSurface", "DryConvectiveAdjustment", "SimpleBoundaryLayer", "EmanuelConvection", "SimplePhysics", "GrayLongwaveRadiation", "Frierson06LongwaveOpticalDepth", "GridScaleCondensation", "get_grid", "get_default_state", "UpdateFrequencyWrapper", "IntermittentShortwave", "IntermittentLongwave", "AdamsBashforth",
            "Context", "RRTMGError", "DeviceState", "DeviceQuantity", "DeviceAdamsBashforth", "radiation_step"]

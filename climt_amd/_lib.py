@@ -231,6 +231,44 @@ class SimplePhysics(C.Structure):
                 + [("pressure_scale", _f64), ("ps_scale", _f64)] + [(n, _vp) for n in SIMPLE_PHYSICS_OUT + SIMPLE_PHYSICS_DIAG])
 
 
+FRIERSON_SCALARS = ("tau0e", "tau0p", "fl")
+FRIERSON_IN = ("pint", "ps", "lat")
+FRIERSON_OUT = ("tau",)
+FRIERSON_DIAG = ()
+
+
+class FriersonOpticalDepth(C.Structure):
+    """mirrors `rrtmg_frierson_optical_depth` (include/rrtmg_hip.h), field for field"""
+    _fields_ = ([("struct_size", C.c_uint32), ("ncol", _i32), ("nlay", _i32), ("memspace", _i32)] + [(n, _vp) for n in FRIERSON_IN]
+                + [(n, _f64) for n in FRIERSON_SCALARS] + [("pressure_scale", _f64), ("ps_scale", _f64)] + [(n, _vp) for n in FRIERSON_OUT])
+
+
+GRAY_LONGWAVE_CONSTANTS = ("sigma_sb", "g", "cpd")
+GRAY_LONGWAVE_IN = ("t", "tsfc", "pint", "tau", "ps", "lat")
+GRAY_LONGWAVE_OUT = ("up", "dn", "tend")
+GRAY_LONGWAVE_DIAG = ("hr", "tau_out")
+
+
+class GrayLongwave(C.Structure):
+    """mirrors `rrtmg_gray_longwave` (include/rrtmg_hip.h), field for field"""
+    _fields_ = ([("struct_size", C.c_uint32), ("ncol", _i32), ("nlay", _i32), ("memspace", _i32), ("frierson", _i32), ("reserved", _i32)]
+                + [(n, _vp) for n in GRAY_LONGWAVE_IN] + [(n, _f64) for n in FRIERSON_SCALARS + GRAY_LONGWAVE_CONSTANTS]
+                + [("pressure_scale", _f64), ("ps_scale", _f64)] + [(n, _vp) for n in GRAY_LONGWAVE_OUT + GRAY_LONGWAVE_DIAG])
+
+
+GRID_SCALE_CONDENSATION_CONSTANTS = ("cpd", "lv", "rd", "rh2o", "g", "rhow")
+GRID_SCALE_CONDENSATION_IN = ("t", "q", "pmid", "pint")
+GRID_SCALE_CONDENSATION_OUT = ("t_out", "q_out")
+GRID_SCALE_CONDENSATION_DIAG = ("precip",)
+
+
+class GridScaleCondensation(C.Structure):
+    """mirrors `rrtmg_grid_scale_condensation` (include/rrtmg_hip.h), field for field"""
+    _fields_ = ([("struct_size", C.c_uint32), ("ncol", _i32), ("nlay", _i32), ("memspace", _i32)] + [(n, _vp) for n in GRID_SCALE_CONDENSATION_IN]
+                + [(n, _f64) for n in GRID_SCALE_CONDENSATION_CONSTANTS] + [("pressure_scale", _f64)]
+                + [(n, _vp) for n in GRID_SCALE_CONDENSATION_OUT + GRID_SCALE_CONDENSATION_DIAG])
+
+
 # What Context._column_call knows of each column component's arrays besides the three tuples above: `columns` are [ncol], `levels`
 # [nlay+1][ncol] and the others [nlay][ncol]; `int32` are int32 and the others float64 (tests/test_call_arrays.py holds all three to
 # the library's own tables); `optional` profiles are named in brackets by the shape message; `in_place`: (output, input) pairs for
@@ -242,6 +280,10 @@ COLUMN_ARRAYS = {
     "emanuel_convection": dict(IN=EMANUEL_IN, DIAG=EMANUEL_DIAG, levels=("pint",), int32=("iflag",), optional=("qs",), in_place=(("cbmf_out", "cbmf"),),
                                columns=("cbmf", "cbmf_out", "precip", "wd", "tprime", "qprime", "cape", "iflag")),
     "simple_physics": dict(IN=SIMPLE_PHYSICS_IN, DIAG=SIMPLE_PHYSICS_DIAG, levels=("pint",), columns=("ps", "ts", "qsurf", "lat", "precl", "sh_out", "lh_out")),
+    # (the gray path: outputs on the interface levels too; the depth has no profile input, its grid is pint's)
+    "frierson_optical_depth": dict(IN=FRIERSON_IN, DIAG=FRIERSON_DIAG, levels=("pint", "tau"), columns=("ps", "lat")),
+    "gray_longwave": dict(IN=GRAY_LONGWAVE_IN, DIAG=GRAY_LONGWAVE_DIAG, levels=("pint", "tau", "up", "dn", "tau_out"), columns=("tsfc", "ps", "lat")),
+    "grid_scale_condensation": dict(IN=GRID_SCALE_CONDENSATION_IN, DIAG=GRID_SCALE_CONDENSATION_DIAG, levels=("pint",), columns=("precip",)),
 }
 
 
@@ -324,6 +366,10 @@ def load_library():
         lib.rrtmg_hip_emanuel_convection.argtypes = [_vp, C.POINTER(Emanuel)]
     if hasattr(lib, "rrtmg_hip_simple_physics"):            # (likewise: the simple physics package)
         lib.rrtmg_hip_simple_physics.argtypes = [_vp, C.POINTER(SimplePhysics)]
+    if hasattr(lib, "rrtmg_hip_gray_longwave"):             # (likewise: the gray radiation path and its moisture sink)
+        lib.rrtmg_hip_frierson_optical_depth.argtypes = [_vp, C.POINTER(FriersonOpticalDepth)]
+        lib.rrtmg_hip_gray_longwave.argtypes = [_vp, C.POINTER(GrayLongwave)]
+        lib.rrtmg_hip_grid_scale_condensation.argtypes = [_vp, C.POINTER(GridScaleCondensation)]
     lib.rrtmg_hip_copy_blocks.argtypes =[_vp, C.c_int, _vp, C.c_long, C.c_long, _vp, _vp, _vp]
     lib.rrtmg_hip_mcica_mask.argtypes = [_vp] + [C.c_int] * 6 + [_vp] * 3
     _lib = lib
@@ -620,15 +666,16 @@ class Context:
             self._ck(fn(self.h, C.byref(a)))
             return outs, diagnostics
         mine, given = given, {n: np.ascontiguousarray(x, dtype=np.float64) for n, x in given.items()}
-        shape = given["t"].shape
+        shape = given["t"].shape if "t" in given else (given["pint"].shape[0] - 1,) + given["pint"].shape[1:]      # (no profile: the grid is pint's)
         profiles, cols = [n for n in IN if n not in columns + levels], [n for n in IN if n in columns]
-        if len(shape) != 2 or any(given[n].shape != shape for n in profiles if n in given) or any(given[n].shape != (shape[0] + 1, shape[1]) for n in levels):
+        if len(shape) != 2 or any(given[n].shape != shape for n in profiles if n in given) or any(given[n].shape != (shape[0] + 1, shape[1]) for n in levels if n in given):
             raise ValueError("%s: %s%s must be [nlay][ncol] arrays of one shape and pint [nlay+1][ncol]"
                              % (entry, ", ".join(n for n in profiles if n not in optional), "".join(" (and %s)" % n for n in profiles if n in optional)))
         if any(given[n].shape != (shape[1],) for n in cols if n in given):
             raise ValueError("%s: %s must be %s" % (entry, " and ".join(filter(None, (", ".join(cols[:-1]), cols[-1]))), "[ncol] arrays" if len(cols) > 1 else "an [ncol] array"))
-        size = lambda n: shape[1] if n in columns else shape[0] * shape[1]
-        empty = lambda n: np.empty(shape[1] if n in columns else shape, dtype=dtype(n))
+        extent = lambda n: (shape[1],) if n in columns else (shape[0] + 1, shape[1]) if n in levels else shape
+        size = lambda n: int(np.prod(extent(n)))
+        empty = lambda n: np.empty(extent(n), dtype=dtype(n))
         outs = {n: (empty(n) if x is None else x) for n, x in outs.items()}
         if diagnostics is True:
             diagnostics = {n: empty(n) for n in DIAG}
@@ -768,6 +815,85 @@ class Context:
         outs, diagnostics = self._column_call("simple_physics", a, given, dict(t_out=t_out, q_out=q_out, u_out=u_out, v_out=v_out), diagnostics,
                                               memspace, ncol, nlay)
         return outs["t_out"], outs["q_out"], outs["u_out"], outs["v_out"], diagnostics
+
+    @property
+    def has_gray_radiation(self):
+        """Whether the library exports the gray radiation path (rrtmg_hip_frierson_optical_depth, rrtmg_hip_gray_longwave and
+        rrtmg_hip_grid_scale_condensation; probed by the symbol)."""
+        return all(hasattr(self.lib, "rrtmg_hip_" + n) for n in ("frierson_optical_depth", "gray_longwave", "grid_scale_condensation"))
+
+    def _need_gray_radiation(self, entry):
+        if not self.has_gray_radiation:
+            raise RRTMGError(4, "this librrtmg_hip.so has no rrtmg_hip_%s (gray radiation path)" % entry)
+
+    @_locked
+    def frierson_optical_depth(self, pint, ps, lat, parameters, tau=None, pressure_scale=1.0, ps_scale=1.0, memspace=0, ncol=None, nlay=None):
+        """climt's Frierson06LongwaveOpticalDepth by column (rrtmg_hip_frierson_optical_depth) -> tau [nlay+1][ncol].
+        `parameters`: tau0e, tau0p, fl; `pressure_scale`, `ps_scale`: Pa per unit of pint and of ps (only their ratio enters).
+        Host arrays pint [nlay+1][ncol], ps, lat [ncol] (lat in degrees north; tau is allocated unless given), or device pointers
+        (or DeviceArrays) with memspace=1 -- then `tau`, `ncol` and `nlay`; one launch on the main stream."""
+        self._need_gray_radiation("frierson_optical_depth")
+        a = FriersonOpticalDepth()
+        a.struct_size, a.memspace = C.sizeof(FriersonOpticalDepth), 1 if memspace else 0
+        a.pressure_scale, a.ps_scale = float(pressure_scale), float(ps_scale)
+        for n in FRIERSON_SCALARS:
+            setattr(a, n, float(parameters[n]))
+        outs, _ = self._column_call("frierson_optical_depth", a, dict(pint=pint, ps=ps, lat=lat), dict(tau=tau), None, memspace, ncol, nlay)
+        return outs["tau"]
+
+    @_locked
+    def gray_longwave(self, t, tsfc, pint, constants, tau=None, ps=None, lat=None, frierson=None, up=None, dn=None, tend=None, diagnostics=True,
+                      pressure_scale=1.0, ps_scale=1.0, memspace=0, ncol=None, nlay=None):
+        """climt's GrayLongwaveRadiation by column (rrtmg_hip_gray_longwave) -> (up, dn, tend, diagnostics).  `constants`:
+        sigma_sb, g, cpd.  `frierson` None: `tau` [nlay+1][ncol] is read.  `frierson` a dict of tau0e, tau0p, fl: the fused call --
+        the optical depth is formed inside the sweep from pint, `ps` and `lat` (degrees north) and `tau` is ignored.
+        `pressure_scale`, `ps_scale`: Pa per unit of pint and of ps.  Host arrays t [nlay][ncol], tsfc [ncol], pint [nlay+1][ncol]
+        (outputs are allocated unless given), `diagnostics` True: a dict of hr [nlay][ncol] (K/day) and, with `frierson`, tau_out
+        [nlay+1][ncol] (False or None: none are asked for; a dict: those it names are written).  Or device pointers (or
+        DeviceArrays) with memspace=1 -- then the three outputs, `ncol` and `nlay`, and `diagnostics` a dict of device pointers
+        or None; one launch on the main stream."""
+        self._need_gray_radiation("gray_longwave")
+        a = GrayLongwave()
+        a.struct_size, a.memspace, a.frierson = C.sizeof(GrayLongwave), 1 if memspace else 0, 0 if frierson is None else 1
+        a.pressure_scale, a.ps_scale = float(pressure_scale), float(ps_scale)
+        for n in GRAY_LONGWAVE_CONSTANTS:
+            setattr(a, n, float(constants[n]))
+        given = dict(t=t, tsfc=tsfc, pint=pint)
+        if frierson is None:
+            if tau is None:
+                raise ValueError("gray_longwave: tau is needed without frierson")
+            given["tau"] = tau
+        else:
+            if ps is None or lat is None:
+                raise ValueError("gray_longwave: frierson needs ps and lat")
+            for n in FRIERSON_SCALARS:
+                setattr(a, n, float(frierson[n]))
+            given.update(ps=ps, lat=lat)
+        if diagnostics is True and not memspace:      # (the depth is a diagnostic of the fused call only)
+            shape = np.shape(t)
+            diagnostics = dict(hr=np.empty(shape))
+            if frierson is not None:
+                diagnostics["tau_out"] = np.empty((shape[0] + 1, shape[1]))
+        outs, diagnostics = self._column_call("gray_longwave", a, given, dict(up=up, dn=dn, tend=tend), diagnostics, memspace, ncol, nlay)
+        return outs["up"], outs["dn"], outs["tend"], diagnostics
+
+    @_locked
+    def grid_scale_condensation(self, t, q, pmid, pint, constants, t_out=None, q_out=None, diagnostics=True, pressure_scale=1.0, memspace=0,
+                                ncol=None, nlay=None):
+        """climt's GridScaleCondensation by column (rrtmg_hip_grid_scale_condensation) -> (t_out, q_out, diagnostics).
+        `constants`: cpd, lv, rd, rh2o, g, rhow; `pressure_scale`: Pa per unit of pmid / pint.  Host arrays t, q, pmid [nlay][ncol],
+        pint [nlay+1][ncol] (outputs are allocated unless given; each may be its own input), `diagnostics` True: a dict of the
+        [ncol] array precip (False or None: not asked for; a dict: written where named).  Or device pointers (or DeviceArrays)
+        with memspace=1 -- then the two outputs, `ncol` and `nlay`, and `diagnostics` a dict of device pointers or None; one
+        launch on the main stream."""
+        self._need_gray_radiation("grid_scale_condensation")
+        a = GridScaleCondensation()
+        a.struct_size, a.memspace, a.pressure_scale = C.sizeof(GridScaleCondensation), 1 if memspace else 0, float(pressure_scale)
+        for n in GRID_SCALE_CONDENSATION_CONSTANTS:
+            setattr(a, n, float(constants[n]))
+        outs, diagnostics = self._column_call("grid_scale_condensation", a, dict(t=t, q=q, pmid=pmid, pint=pint), dict(t_out=t_out, q_out=q_out),
+                                              diagnostics, memspace, ncol, nlay)
+        return outs["t_out"], outs["q_out"], diagnostics
 
     @_locked
     def solar_insolation(self, lat, lon, sin_delta, cos_delta, fractional_day, irradiance):

@@ -75,6 +75,8 @@ except ImportError:
         ("planetary_radius", "m"): 6.37122e6,
         ("planetary_rotation_rate", "s^-1"): 7.292e-5,
         ("density_of_liquid_water", "kg/m^3"): 1000.0,
+        # GrayLongwaveRadiation (_components/radiation.py), under the unit string it asks with: sympl's default
+        ("stefan_boltzmann_constant", "W/m^2/K^4"): 5.670367e-8,
     }
     _constant_overrides = {}
 

@@ -613,6 +613,112 @@ def simple_physics_device_call(self, ds, timestep):
             "surface_upward_latent_heat_flux": d["lh_out"]}, ds
 
 
+def _to_pa(units):
+    return float(_convert(np.float64(1.0), units, "Pa"))
+
+
+def _gray_surface(ds, who, nlev, ncol):
+    """-> (air_pressure_on_interface_levels, surface_air_pressure, latitude) as they are resident, for the Frierson optical depth:
+    [interface_levels][*] and [*]; the pressures in any pressure unit (the library scales them), the latitude in degrees north
+    under either of the names the components use for that unit."""
+    pi, ps, lat = (ds.get(n) for n in ("air_pressure_on_interface_levels", "surface_air_pressure", "latitude"))
+    for n, x in zip(("air_pressure_on_interface_levels", "surface_air_pressure", "latitude"), (pi, ps, lat)):
+        if x is None:
+            raise KeyError("device state is missing input quantity %r" % n)
+    if tuple(pi.dims) != ("interface_levels", "*") or tuple(ps.dims) != ("*",) or tuple(lat.dims) != ("*",):
+        raise ValueError("the interface pressures, the surface pressure and the latitude are resident as %s, %s and %s, %s wants [interface_levels][*], [*] and [*]" % (
+            pi.dims, ps.dims, lat.dims, who))
+    if float(_convert(np.float64(1.0), lat.units, "degrees_N")) != 1.0:
+        raise ValueError("quantity 'latitude' is resident in %r, component wants 'degrees_N'" % lat.units)
+    if pi.shape != (nlev, ncol) or ps.shape != (ncol,) or lat.shape != (ncol,):
+        raise ValueError("interface pressures %s, surface pressure %s and latitude %s do not belong to one grid of %d interfaces by %d columns" % (
+            pi.shape, ps.shape, lat.shape, nlev, ncol))
+    return pi, ps, lat
+
+
+def frierson_device_call(self, ds):
+    """Frierson06LongwaveOpticalDepth on a DeviceState: rrtmg_hip_frierson_optical_depth with device pointers on the main stream.
+    The pressures are read as they are resident (only the ratio pint / ps enters; the library brings both to Pa).  The depth goes
+    to one of two alternating work buffers: -> diagnostics as DeviceQuantity."""
+    pi = ds.get("air_pressure_on_interface_levels")
+    if pi is None:
+        raise KeyError("device state is missing input quantity 'air_pressure_on_interface_levels'")
+    nlev, ncol = pi.shape if len(pi.shape) == 2 else (0, 0)
+    pi, ps, lat = _gray_surface(ds, "the optical depth", nlev, ncol)
+    self._device_calls = getattr(self, "_device_calls", 0) + 1
+    tau = ds.work(("frierson", id(self), self._device_calls & 1), (nlev, ncol), ("interface_levels", "*"), "dimensionless")
+    ds.ctx.frierson_optical_depth(pi.ptr, ps.ptr, lat.ptr, self.parameters(), tau=tau.ptr, pressure_scale=_to_pa(pi.units), ps_scale=_to_pa(ps.units),
+                                  memspace=1, ncol=ncol, nlay=nlev - 1)
+    return {"longwave_optical_depth_on_interface_levels": tau}
+
+
+def gray_longwave_device_call(self, ds):
+    """GrayLongwaveRadiation on a DeviceState: rrtmg_hip_gray_longwave with device pointers on the main stream; the fluxes, the
+    tendency and the heating rate go to two alternating sets of work buffers and stay in HBM (the fluxes [interface_levels][*], as
+    SlabSurface's device call reads them).  With `optical_depth` the fused call: the depth is formed inside the sweep from the
+    resident pressures and latitude and is a diagnostic.  The interface pressures are read as they are resident; the library
+    brings them to Pa.  -> (tendencies, diagnostics) as DeviceQuantity."""
+    P = self.input_properties
+    t, ts = ds.need("air_temperature", P["air_temperature"]), ds.need("surface_temperature", P["surface_temperature"])
+    nlay, ncol = t.shape
+    fused = self._optical_depth is not None
+    if fused:
+        pi, ps, lat = _gray_surface(ds, "the gray longwave", nlay + 1, ncol)
+    else:
+        pi = ds.get("air_pressure_on_interface_levels")
+        tau = ds.need("longwave_optical_depth_on_interface_levels", P["longwave_optical_depth_on_interface_levels"])
+        if pi is None:
+            raise KeyError("device state is missing input quantity 'air_pressure_on_interface_levels'")
+        if tuple(pi.dims) != ("interface_levels", "*"):
+            raise ValueError("air_pressure_on_interface_levels is resident as %s, the gray longwave wants [interface_levels][*]" % (pi.dims,))
+        if pi.shape != (nlay + 1, ncol) or tau.shape != (nlay + 1, ncol):
+            raise ValueError("temperature %s, interface pressures %s and optical depth %s do not belong to one grid" % (t.shape, pi.shape, tau.shape))
+    if ts.shape != (ncol,):
+        raise ValueError("temperature %s and surface temperature %s do not belong to one grid" % (t.shape, ts.shape))
+    self._device_calls = getattr(self, "_device_calls", 0) + 1
+    w = lambda key, shape, dims, units: ds.work(("gray", id(self), key, self._device_calls & 1), shape, dims, units)
+    il, ml = (nlay + 1, ncol), (nlay, ncol)
+    up, dn = (w(k, il, ("interface_levels", "*"), "W m^-2") for k in ("up", "dn"))
+    tend, hr = w("tend", ml, ("mid_levels", "*"), "degK s^-1"), w("hr", ml, ("mid_levels", "*"), "degK day^-1")
+    d = dict(hr=hr.ptr)
+    kw = dict(up=up.ptr, dn=dn.ptr, tend=tend.ptr, pressure_scale=_to_pa(pi.units), memspace=1, ncol=ncol, nlay=nlay)
+    if fused:
+        depth = w("tau", il, ("interface_levels", "*"), "dimensionless")
+        d.update(tau_out=depth.ptr)
+        ds.ctx.gray_longwave(t.ptr, ts.ptr, pi.ptr, self.constants(), ps=ps.ptr, lat=lat.ptr, frierson=self._optical_depth.parameters(), diagnostics=d,
+                             ps_scale=_to_pa(ps.units), **kw)
+    else:
+        ds.ctx.gray_longwave(t.ptr, ts.ptr, pi.ptr, self.constants(), tau=tau.ptr, diagnostics=d, **kw)
+    diagnostics = {"upwelling_longwave_flux_in_air": up, "downwelling_longwave_flux_in_air": dn, "air_temperature_tendency_from_longwave": hr}
+    if fused:
+        diagnostics["longwave_optical_depth_on_interface_levels"] = depth
+    return {"air_temperature": tend}, diagnostics
+
+
+def grid_scale_condensation_device_call(self, ds, timestep=None):
+    """GridScaleCondensation on a DeviceState: rrtmg_hip_grid_scale_condensation with device pointers on the main stream.  The
+    pressures are read as they are resident -- in the units of whichever component asked for them first; the saturation formula
+    needs Pa, so the library multiplies every pressure it reads by `pressure_scale`, Pa per resident unit: the one rounding the
+    unit conversion of the host path makes.  The two new profiles go to work buffers that alternate with the step count (the
+    state's previous arrays stay what they were) and the state is rebound to them; the precipitation goes to an [ncol] work
+    buffer: -> (diagnostics as DeviceQuantity, the same state)."""
+    P = self.input_properties
+    names = ("air_temperature", "specific_humidity")
+    t, q = (ds.need(n, P[n]) for n in names)
+    p, pi = _resident_pressures(ds, "the condensation")
+    nlay, ncol = t.shape
+    if q.shape != (nlay, ncol) or p.shape != (nlay, ncol) or pi.shape != (nlay + 1, ncol):
+        raise ValueError("temperature %s, humidity %s and pressures %s, %s do not belong to one grid" % (t.shape, q.shape, p.shape, pi.shape))
+    ds.join_streams()      # a longwave still in flight belongs to the step this component closes
+    work = _step_work(self, ds, "gsc", ncol)
+    new = [work(n, x.units, like=x) for n, x in zip(names, (t, q))]
+    precip = work("precip", "kg m^-2")
+    ds.ctx.grid_scale_condensation(t.ptr, q.ptr, p.ptr, pi.ptr, self.constants(), t_out=new[0].ptr, q_out=new[1].ptr, diagnostics=dict(precip=precip.ptr),
+                                   pressure_scale=_to_pa(p.units), memspace=1, ncol=ncol, nlay=nlay)
+    ds.update(zip(names, new))
+    return {"precipitation_amount": precip}, ds
+
+
 # ---- time stepping on the device ------------------------------------------------------------------------------------
 _AB = {1: (1.0,), 2: (1.5, -0.5), 3: (23.0 / 12.0, -16.0 / 12.0, 5.0 / 12.0), 4: (55.0 / 24.0, -59.0 / 24.0, 37.0 / 24.0, -9.0 / 24.0)}
 

@@ -10,6 +10,7 @@ the first step, the column starts on a lapse rate steeper than the dry adiabat (
 isothermal 290 K.
 
     python examples/radiative_convective.py [--steps 60] [--device-resident] [--boundary-layer | --simple-physics] [--moist-convection]
+                                            [--gray-longwave] [--grid-scale-condensation]
 
 --boundary-layer closes that gap: SimpleBoundaryLayer (bulk surface fluxes, implicit diffusion of T, q, u, v) steps after the time
 stepper and before the adjustment, and its two flux diagnostics go into the state, so the slab feels them from the next step
@@ -26,6 +27,15 @@ light wind, and the column starts moister with a supersaturated layer, so that i
 flux is carried from step to step, and the precipitation joins the report.  The column then starts moister (80 % of saturation
 near the surface).  Without the flag the run is what it was.
 
+--gray-longwave replaces the RRTMG longwave with the gray one of the Frierson set-up: GrayLongwaveRadiation with the optical depth
+of Frierson06LongwaveOpticalDepth formed inside the sweep (the fused call; the depth joins the diagnostics).  The shortwave stays
+RRTMG's.  Without the flag the run is what it was.
+
+--grid-scale-condensation adds GridScaleCondensation, the moisture sink of that set-up, after the time stepper (and after the
+boundary layer where there is one) and before the adjustment; its precipitation_amount goes into the state.  The column then
+starts at 70 % of saturation with one supersaturated layer.  Exclusive with --simple-physics, which condenses itself.  Without
+the flag the run is what it was.
+
 --device-resident keeps the state in HBM (climt_amd.DeviceState + DeviceAdamsBashforth; the adjustment reads and rebinds the
 resident temperature and humidity): same components, same numbers.  The longwave k-distribution tables of this build are
 synthetic while the reference's data file is missing (the component says so).
@@ -38,18 +48,23 @@ from datetime import timedelta
 import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from climt_amd import (AdamsBashforth, DryConvectiveAdjustment, EmanuelConvection, RRTMGLongwave, RRTMGShortwave, SimpleBoundaryLayer, SimplePhysics,  # noqa: E402
-                       SlabSurface, get_default_state, get_grid)
+from climt_amd import (AdamsBashforth, DryConvectiveAdjustment, EmanuelConvection, Frierson06LongwaveOpticalDepth, GrayLongwaveRadiation,  # noqa: E402
+                       GridScaleCondensation, RRTMGLongwave, RRTMGShortwave, SimpleBoundaryLayer, SimplePhysics, SlabSurface, get_default_state, get_grid)
 
 
-def run(steps=60, device_resident=False, report=None, boundary_layer=False, moist_convection=False, simple_physics=False):
+def run(steps=60, device_resident=False, report=None, boundary_layer=False, moist_convection=False, simple_physics=False, gray_longwave=False,
+        grid_scale_condensation=False):
     """-> (diagnostics of step 0, state after `steps` steps), both as host DataArrays.  `boundary_layer`: with SimpleBoundaryLayer
     between the time stepper and the adjustment; its diagnostics of step 0 are then among the first.  `moist_convection`: with
-    EmanuelConvection in the time stepper's list.  `simple_physics`: with SimplePhysics in the place of the boundary layer."""
+    EmanuelConvection in the time stepper's list.  `simple_physics`: with SimplePhysics in the place of the boundary layer.
+    `gray_longwave`: the fused Frierson + gray longwave in the place of RRTMG's.  `grid_scale_condensation`: with
+    GridScaleCondensation before the adjustment."""
     if boundary_layer and simple_physics:
         raise ValueError("boundary_layer and simple_physics are exclusive: both exchange heat, moisture and momentum with the surface")
+    if grid_scale_condensation and simple_physics:
+        raise ValueError("grid_scale_condensation and simple_physics are exclusive: both remove grid-scale supersaturation")
     rad_sw = RRTMGShortwave()
-    rad_lw = RRTMGLongwave(allow_synthetic_tables=True)
+    rad_lw = GrayLongwaveRadiation(optical_depth=Frierson06LongwaveOpticalDepth()) if gray_longwave else RRTMGLongwave(allow_synthetic_tables=True)
     slab = SlabSurface()
     dry_convection = DryConvectiveAdjustment()
     components = [rad_sw, rad_lw, slab]
@@ -64,6 +79,9 @@ def run(steps=60, device_resident=False, report=None, boundary_layer=False, mois
     if simple_physics:
         simple_boundary_layer = SimplePhysics()      # (steps where the boundary layer steps)
         steppers = [simple_boundary_layer, dry_convection]
+    if grid_scale_condensation:
+        condensation = GridScaleCondensation()
+        steppers = steppers[:-1] + [condensation, dry_convection]
 
     grid = get_grid(nx=1, ny=1, nz=30)
     state = get_default_state(components + steppers, grid_state=grid)
@@ -89,6 +107,12 @@ def run(steps=60, device_resident=False, report=None, boundary_layer=False, mois
         state["specific_humidity"].values[:] = 0.7 * qsat
         state["specific_humidity"].values[3] = 1.05 * qsat[3]      # one supersaturated layer: stratiform rain from step 0
         state["eastward_wind"].values[:] = 5.0
+    if grid_scale_condensation:
+        t = state["air_temperature"].values
+        es = 611.2 * np.exp(17.67 * (t - 273.15) / (t - 29.65))
+        qsat = 287.0 / 461.5 * es / (p - (1.0 - 287.0 / 461.5) * es)
+        state["specific_humidity"].values[:] = 0.7 * qsat
+        state["specific_humidity"].values[3] = 1.05 * qsat[3]      # one supersaturated layer: condensation from step 0
     to_host = lambda s, names=None: {k: s[k] for k in (names or s)}
     if device_resident:
         import climt_amd
@@ -105,6 +129,13 @@ def run(steps=60, device_resident=False, report=None, boundary_layer=False, mois
 
         if boundary_layer or simple_physics:
             diagnostics, new_state = simple_boundary_layer(state, timestep)
+            state.update(diagnostics)
+            state.update(new_state)
+            if i == 0:
+                first.update(to_host(state, list(diagnostics)))
+
+        if grid_scale_condensation:
+            diagnostics, new_state = condensation(state, timestep)
             state.update(diagnostics)
             state.update(new_state)
             if i == 0:
@@ -129,6 +160,8 @@ def main():
     surface.add_argument("--boundary-layer", action="store_true")
     surface.add_argument("--simple-physics", action="store_true")
     ap.add_argument("--moist-convection", action="store_true")
+    ap.add_argument("--gray-longwave", action="store_true")
+    ap.add_argument("--grid-scale-condensation", action="store_true")
     a = ap.parse_args()
 
     def report(i, state):
@@ -142,7 +175,9 @@ def main():
             i, state["surface_temperature"].values.ravel()[0], t[0], t[-1], state["upwelling_longwave_flux_in_air"].values.ravel()[-1],
             state["air_temperature_tendency_from_shortwave"].values.ravel()[-1],
             state["air_temperature_tendency_from_longwave"].values.ravel()[-1], rain))
-    run(a.steps, a.device_resident, report, a.boundary_layer, a.moist_convection, a.simple_physics)
+    if a.grid_scale_condensation and a.simple_physics:
+        ap.error("--grid-scale-condensation and --simple-physics are exclusive")
+    run(a.steps, a.device_resident, report, a.boundary_layer, a.moist_convection, a.simple_physics, a.gray_longwave, a.grid_scale_condensation)
 
 
 if __name__ == "__main__":

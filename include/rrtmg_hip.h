@@ -829,6 +829,83 @@ typedef struct {
 } rrtmg_simple_physics;
 int rrtmg_hip_simple_physics(rrtmg_ctx *ctx, const rrtmg_simple_physics *a);
 
+/* ---- gray radiation: the Frierson optical depth, the gray longwave sweep, grid-scale condensation ---- */
+/* climt's Frierson06LongwaveOpticalDepth (_components/radiation.py), by column; level 0 is the surface:
+ *   tau_0 = tau0e + (tau0p - tau0e) sin(lat pi / 180)^2;  sigma = pint / ps;  tau = tau_0 (1 - (fl sigma + (1 - fl) sigma^4)),
+ * 0 at the surface and tau_0 at the top, as the reference has it.  pint is read as pint * pressure_scale, ps as ps * ps_scale (only
+ * their ratio enters).  lat in degrees north.  Arrays under memspace 0 (host) or 1 (device).  tau may overlap no input.
+ * RRTMG_ERR_ARG: a NULL struct, a struct_size other than sizeof(rrtmg_frierson_optical_depth), ncol <= 0, nlay < 1, a memspace
+ * other than 0 and 1, a NULL pint, ps, lat or tau, tau over an input -- before anything is read or enqueued.  Needs neither
+ * rrtmg_hip_sw_init nor rrtmg_hip_lw_init.  Host pointers: the inputs go up, tau comes back.  Device pointers: one launch on the
+ * context's main stream; in deferred mode the call returns once enqueued.
+ * Probe for it by symbol; RRTMG_HIP_ABI_VERSION is unchanged. */
+typedef struct {
+  uint32_t struct_size; int32_t ncol, nlay, memspace;
+  const double *pint;                                 /* [nlay+1][ncol] */
+  const double *ps, *lat;                             /* [ncol] */
+  double tau0e, tau0p, fl;
+  double pressure_scale, ps_scale;
+  double *tau;                                        /* [nlay+1][ncol] */
+} rrtmg_frierson_optical_depth;
+int rrtmg_hip_frierson_optical_depth(rrtmg_ctx *ctx, const rrtmg_frierson_optical_depth *a);
+
+/* climt's GrayLongwaveRadiation (_components/radiation.py), by column, in the reference's order of operations:
+ *   up[0] = sigma_sb tsfc^4;  upwards dtau = tau[k] - tau[k-1], trans = exp(-dtau), up[k] = up[k-1] trans + (sigma_sb t[k-1]^4) (1 - trans);
+ *   dn[nlay] = +0.0;  downwards dn[k] = dn[k+1] trans + (sigma_sb t[k]^4) (1 - trans) with the trans of layer k.  dtau is not clamped:
+ *   a depth that decreases upwards gives trans > 1, as in the reference.  net = up - dn;
+ *   tend[k] = ((g / cpd) (net[k+1] - net[k])) / (pint[k+1] - pint[k]) in K/s, pint read as pint * pressure_scale (Pa per unit);
+ *   hr = tend * 86400.0 in K/day.
+ * frierson 0: tau [nlay+1][ncol] is read; ps and lat are ignored and may be NULL.  frierson 1 (the fused call): tau is ignored and
+ * may be NULL; the optical depth of every interface is formed inside the sweep from pint, ps and lat by the rule of
+ * rrtmg_hip_frierson_optical_depth (tau0e, tau0p, fl, ps_scale as there) and is written only where tau_out is given -- every output
+ * has the bits of rrtmg_hip_frierson_optical_depth followed by a frierson 0 call on its tau.  One launch, two passes over the column;
+ * the transmittance is not stored in an array of its own: the upward pass carries it in dn and the emission in tend, which the
+ * downward pass overwrites.  hr and tau_out may each be NULL.  No output may overlap an input or another output.
+ * RRTMG_ERR_ARG: a NULL struct, a struct_size other than sizeof(rrtmg_gray_longwave), ncol <= 0, nlay < 1, a memspace other than 0
+ * and 1, a frierson other than 0 and 1, a NULL t, tsfc, pint, up, dn or tend, a NULL ps or lat with frierson 1, a NULL tau with
+ * frierson 0, any overlap of an output -- before anything is read or enqueued.  Needs neither rrtmg_hip_sw_init nor
+ * rrtmg_hip_lw_init.  Host pointers: the inputs that are read go up, the outputs asked for come back.  Device pointers: one launch
+ * on the context's main stream; in deferred mode the call returns once enqueued.
+ * Probe for it by symbol; RRTMG_HIP_ABI_VERSION is unchanged. */
+typedef struct {
+  uint32_t struct_size; int32_t ncol, nlay, memspace;
+  int32_t frierson, reserved;                         /* reserved: 0 */
+  const double *t;                                    /* [nlay][ncol] */
+  const double *tsfc;                                 /* [ncol] */
+  const double *pint, *tau;                           /* [nlay+1][ncol]; tau may be NULL with frierson 1 */
+  const double *ps, *lat;                             /* [ncol]; each may be NULL with frierson 0 */
+  double tau0e, tau0p, fl, sigma_sb, g, cpd;
+  double pressure_scale, ps_scale;
+  double *up, *dn;                                    /* [nlay+1][ncol] */
+  double *tend;                                       /* [nlay][ncol] */
+  double *hr;                                         /* [nlay][ncol], or NULL */
+  double *tau_out;                                    /* [nlay+1][ncol], or NULL */
+} rrtmg_gray_longwave;
+int rrtmg_hip_gray_longwave(rrtmg_ctx *ctx, const rrtmg_gray_longwave *a);
+
+/* climt's GridScaleCondensation (_components/grid_scale_condensation.py), by column and layer from the surface up:
+ *   es = 611.2 exp(17.67 (t - 273.15) / (t - 29.65)), eps = rd / rh2o, q_sat = eps es / (pmid - (1 - eps) es);  where q > q_sat:
+ *   dqsat_dT = lv q_sat / (rh2o t t), condensed = (q - q_sat) / (1 + lv / cpd dqsat_dT), q_out = q - condensed, t_out = t + lv / cpd
+ *   condensed and precip += condensed ((pint[k+1] - pint[k]) / (g rhow)); a layer that is not supersaturated keeps its input bits.
+ * With level 0 at the surface pint[k+1] - pint[k] is negative, and so is precip (kg m^-2 in the reference's units): the
+ * reference's own sign, reproduced.  No time step enters.  pmid and pint are read as p * pressure_scale, Pa per unit of the arrays.
+ * Each of t_out and q_out may be exactly its own input (in place); any other overlap of an output with an input or another output
+ * returns RRTMG_ERR_ARG, as do a NULL struct, a struct_size other than sizeof(rrtmg_grid_scale_condensation), ncol <= 0, nlay < 1,
+ * a memspace other than 0 and 1 and a NULL t, q, pmid, pint, t_out or q_out -- before anything is read or enqueued.  precip may be
+ * NULL.  Needs neither rrtmg_hip_sw_init nor rrtmg_hip_lw_init.  Host pointers: the inputs go up, the two profiles and precip
+ * come back.  Device pointers: one launch on the context's main stream; in deferred mode the call returns once enqueued.
+ * Probe for it by symbol; RRTMG_HIP_ABI_VERSION is unchanged. */
+typedef struct {
+  uint32_t struct_size; int32_t ncol, nlay, memspace;
+  const double *t, *q, *pmid;                         /* [nlay][ncol] */
+  const double *pint;                                 /* [nlay+1][ncol] */
+  double cpd, lv, rd, rh2o, g, rhow;
+  double pressure_scale;
+  double *t_out, *q_out;                              /* [nlay][ncol]; each may be its own input (in place) */
+  double *precip;                                     /* [ncol], or NULL */
+} rrtmg_grid_scale_condensation;
+int rrtmg_hip_grid_scale_condensation(rrtmg_ctx *ctx, const rrtmg_grid_scale_condensation *a);
+
 /* ---- reference-compatible entry points (host pointers, default context) ---------------- */
 int rrtmg_hip_default_status(void);
 const char *rrtmg_hip_default_error(void);
