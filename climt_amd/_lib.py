@@ -269,6 +269,20 @@ class GridScaleCondensation(C.Structure):
                 + [(n, _vp) for n in GRID_SCALE_CONDENSATION_OUT + GRID_SCALE_CONDENSATION_DIAG])
 
 
+SURFACE_ICE_FLUXES = ("sw_down", "lw_down", "sw_up", "lw_up", "lh", "sh")
+SURFACE_ICE_CONSTANTS = ("rho_ice", "rho_snow", "c_ice", "c_snow", "k_ice", "k_snow", "lf", "t_melt", "eps", "max_height", "albedo_snow", "albedo_ice", "albedo_melt")
+SURFACE_ICE_IN = ("t", "height", "thick", "snow", "base") + SURFACE_ICE_FLUXES + ("area_type",)
+SURFACE_ICE_OUT = ("t_out", "height_out", "thick_out", "snow_out", "tsfc_out", "base_flux_out")
+SURFACE_ICE_DIAG = ("cond_flux", "albedo", "flags")
+
+
+class SurfaceIce(C.Structure):
+    """mirrors `rrtmg_surface_ice` (include/rrtmg_hip.h), field for field"""
+    _fields_ = ([("struct_size", C.c_uint32), ("ncol", _i32), ("nlay", _i32), ("memspace", _i32), ("kind", _i32), ("reserved", _i32)]
+                + [(n, _vp) for n in SURFACE_ICE_IN] + [("dt", _f64)] + [(n, _f64) for n in SURFACE_ICE_CONSTANTS]
+                + [(n, _vp) for n in SURFACE_ICE_OUT + SURFACE_ICE_DIAG])
+
+
 # What Context._column_call knows of each column component's arrays besides the three tuples above: `columns` are [ncol], `levels`
 # [nlay+1][ncol] and the others [nlay][ncol]; `int32` are int32 and the others float64 (tests/test_call_arrays.py holds all three to
 # the library's own tables); `optional` profiles are named in brackets by the shape message; `in_place`: (output, input) pairs for
@@ -284,6 +298,10 @@ COLUMN_ARRAYS = {
     "frierson_optical_depth": dict(IN=FRIERSON_IN, DIAG=FRIERSON_DIAG, levels=("pint", "tau"), columns=("ps", "lat")),
     "gray_longwave": dict(IN=GRAY_LONGWAVE_IN, DIAG=GRAY_LONGWAVE_DIAG, levels=("pint", "tau", "up", "dn", "tau_out"), columns=("tsfc", "ps", "lat")),
     "grid_scale_condensation": dict(IN=GRID_SCALE_CONDENSATION_IN, DIAG=GRID_SCALE_CONDENSATION_DIAG, levels=("pint",), columns=("precip",)),
+    # (the snow/ice column: nlay counts the ice interface levels, so there are no `levels`; an int32 input)
+    "surface_ice": dict(IN=SURFACE_ICE_IN, DIAG=SURFACE_ICE_DIAG, int32=("area_type", "flags"), optional=(),
+                        in_place=(("t_out", "t"), ("height_out", "height"), ("thick_out", "thick"), ("snow_out", "snow"), ("base_flux_out", "base")),
+                        columns=("thick", "snow", "base") + SURFACE_ICE_FLUXES + ("area_type", "thick_out", "snow_out", "tsfc_out", "base_flux_out", "cond_flux", "albedo", "flags")),
 }
 
 
@@ -370,6 +388,8 @@ def load_library():
         lib.rrtmg_hip_frierson_optical_depth.argtypes = [_vp, C.POINTER(FriersonOpticalDepth)]
         lib.rrtmg_hip_gray_longwave.argtypes = [_vp, C.POINTER(GrayLongwave)]
         lib.rrtmg_hip_grid_scale_condensation.argtypes = [_vp, C.POINTER(GridScaleCondensation)]
+    if hasattr(lib, "rrtmg_hip_surface_ice"):               # (likewise: the snow/ice column of SeaIce and LandIce)
+        lib.rrtmg_hip_surface_ice.argtypes = [_vp, C.POINTER(SurfaceIce)]
     lib.rrtmg_hip_copy_blocks.argtypes =[_vp, C.c_int, _vp, C.c_long, C.c_long, _vp, _vp, _vp]
     lib.rrtmg_hip_mcica_mask.argtypes = [_vp] + [C.c_int] * 6 + [_vp] * 3
     _lib = lib
@@ -665,7 +685,7 @@ class Context:
                 setattr(a, name, _device_pointer(x, dtype(name), name))
             self._ck(fn(self.h, C.byref(a)))
             return outs, diagnostics
-        mine, given = given, {n: np.ascontiguousarray(x, dtype=np.float64) for n, x in given.items()}
+        mine, given = given, {n: np.ascontiguousarray(x, dtype=dtype(n)) for n, x in given.items()}
         shape = given["t"].shape if "t" in given else (given["pint"].shape[0] - 1,) + given["pint"].shape[1:]      # (no profile: the grid is pint's)
         profiles, cols = [n for n in IN if n not in columns + levels], [n for n in IN if n in columns]
         if len(shape) != 2 or any(given[n].shape != shape for n in profiles if n in given) or any(given[n].shape != (shape[0] + 1, shape[1]) for n in levels if n in given):
@@ -894,6 +914,34 @@ class Context:
         outs, diagnostics = self._column_call("grid_scale_condensation", a, dict(t=t, q=q, pmid=pmid, pint=pint), dict(t_out=t_out, q_out=q_out),
                                               diagnostics, memspace, ncol, nlay)
         return outs["t_out"], outs["q_out"], diagnostics
+
+    @property
+    def has_surface_ice(self):
+        """Whether the library exports the snow/ice column of SeaIce and LandIce (rrtmg_hip_surface_ice; probed by the symbol)."""
+        return hasattr(self.lib, "rrtmg_hip_surface_ice")
+
+    @_locked
+    def surface_ice(self, kind, t, height, thick, snow, base, fluxes, area_type, dt, constants, t_out=None, height_out=None, thick_out=None,
+                    snow_out=None, tsfc_out=None, base_flux_out=None, diagnostics=True, memspace=0, ncol=None, nlay=None):
+        """climt's SeaIce (`kind` 0) and LandIce (`kind` 1) by column (rrtmg_hip_surface_ice) -> (outputs, diagnostics): two
+        dicts, by the names of SURFACE_ICE_OUT and SURFACE_ICE_DIAG.  `base`: the ocean heat flux (kind 0) or the soil surface
+        temperature (kind 1); `fluxes`: a dict of the six [ncol] parts of the net flux (SURFACE_ICE_FLUXES; the radiative ones are
+        the surface row of the flux arrays); `area_type`: int32 codes (slab_surface.AREA_MAP); `constants`:
+        SURFACE_ICE_CONSTANTS.  Host arrays t, height [nlay][ncol] (nlay: the ice interface levels, at least 3) and [ncol] arrays
+        (outputs are allocated unless given; t_out, height_out, thick_out, snow_out and, for kind 0, base_flux_out may be their own
+        inputs), `diagnostics` True: cond_flux, albedo and flags (False or None: none; a dict: those it names).  Or device
+        pointers (or DeviceArrays) with memspace=1 -- then the six outputs, `ncol` and `nlay`, and `diagnostics` a dict of
+        device pointers or None; one launch on the main stream."""
+        if not self.has_surface_ice:
+            raise RRTMGError(4, "this librrtmg_hip.so has no rrtmg_hip_surface_ice (sea ice and land ice)")
+        a = SurfaceIce()
+        a.struct_size, a.memspace, a.kind, a.dt = C.sizeof(SurfaceIce), 1 if memspace else 0, int(kind), float(dt)
+        for n in SURFACE_ICE_CONSTANTS:
+            setattr(a, n, float(constants[n]))
+        given = dict(t=t, height=height, thick=thick, snow=snow, base=base, area_type=area_type)
+        given.update({n: fluxes[n] for n in SURFACE_ICE_FLUXES})
+        return self._column_call("surface_ice", a, given, dict(t_out=t_out, height_out=height_out, thick_out=thick_out, snow_out=snow_out,
+                                                               tsfc_out=tsfc_out, base_flux_out=base_flux_out), diagnostics, memspace, ncol, nlay)
 
     @_locked
     def solar_insolation(self, lat, lon, sin_delta, cos_delta, fractional_day, irradiance):

@@ -77,6 +77,17 @@ except ImportError:
         ("density_of_liquid_water", "kg/m^3"): 1000.0,
         # GrayLongwaveRadiation (_components/radiation.py), under the unit string it asks with: sympl's default
         ("stefan_boltzmann_constant", "W/m^2/K^4"): 5.670367e-8,
+        # SeaIce / LandIce (sea_ice/component.py, land_ice/component.py: _update_constants), under the unit strings they ask
+        # with.  The reference's planning notes pin the freezing temperature, the latent heat of fusion and the conductivity of
+        # ice; the other five are sympl's defaults as remembered
+        ("thermal_conductivity_of_solid_phase_as_ice", "W/m/degK"): 2.22,
+        ("thermal_conductivity_of_solid_phase_as_snow", "W/m/degK"): 0.2,
+        ("density_of_solid_phase_as_ice", "kg/m^3"): 916.7,
+        ("density_of_solid_phase_as_snow", "kg/m^3"): 100.0,
+        ("heat_capacity_of_solid_phase_as_ice", "J/kg/degK"): 2108.0,
+        ("heat_capacity_of_solid_phase_as_snow", "J/kg/degK"): 2108.0,
+        ("latent_heat_of_fusion", "J/kg"): 333550.0,
+        ("freezing_temperature_of_liquid_phase", "degK"): 273.0,
     }
     _constant_overrides = {}
 

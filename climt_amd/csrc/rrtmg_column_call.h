@@ -47,6 +47,7 @@ template <class P> struct ColumnMember;      // element type and direction of a 
 template <> struct ColumnMember<const double *> { static constexpr bool i32 = false, out = false; };
 template <> struct ColumnMember<double *> { static constexpr bool i32 = false, out = true; };
 template <> struct ColumnMember<int32_t *> { static constexpr bool i32 = true, out = true; };
+template <> struct ColumnMember<const int32_t *> { static constexpr bool i32 = true, out = false; };
 template <class P, class D> constexpr size_t column_same_type(size_t offset) {
   static_assert(std::is_same<P, D>::value, "the public struct and the call struct disagree about a member's type");
   return offset;

@@ -719,6 +719,77 @@ def grid_scale_condensation_device_call(self, ds, timestep=None):
     return {"precipitation_amount": precip}, ds
 
 
+def surface_ice_device_call(self, ds, timestep, check_maximum_height=True):
+    """SeaIce / LandIce on a DeviceState: rrtmg_hip_surface_ice with device pointers on the main stream; nothing leaves HBM.
+    The surface rows of the resident [interface_levels][*] radiative fluxes are bound by pointer (row 0 is the surface); the
+    area-type codes are the resident ones, and the kernel decides from them which columns it steps.  The stepped column goes to
+    work buffers that alternate with the step count (the state's previous arrays stay what they were) and the state is rebound
+    to them; the diagnostics are DeviceQuantity handles SlabSurface and the shortwave can take from the state.
+    The reference raises for a column taller than the maximum before it computes anything.  Here the kernel leaves such a
+    column as it is and flags it: `check_maximum_height` True downloads the 4 * ncol bytes of the flags (which waits for the
+    stream) and raises the reference's ValueError; False downloads nothing and leaves the column flagged in the
+    component's `device_flags` (a DeviceQuantity).  -> (diagnostics, the same state)."""
+    from .surface_ice import FLAG_TOO_TALL, FLUX_NAMES, too_tall_message
+    P = self.input_properties
+    ice_names = ("snow_and_ice_temperature", "height_on_ice_interface_levels")
+    t, height = (ds.need(n, P[n]) for n in ice_names)
+    col_names = (self.thickness_name, "surface_snow_thickness", self.base_name, "surface_upward_latent_heat_flux", "surface_upward_sensible_heat_flux")
+    thick, snow, base, lh, sh = (ds.need(n, P[n]) for n in col_names)
+    if len(t.shape) != 2:
+        raise ValueError("quantity 'snow_and_ice_temperature' is resident as %s, component wants %s" % (t.dims, P["snow_and_ice_temperature"]["dims"]))
+    nlay, ncol = t.shape
+    area = ds.get("area_type")
+    if area is None:
+        raise KeyError("device state is missing input quantity 'area_type'")
+    fluxes = dict(lh=lh.ptr, sh=sh.ptr)
+    for k, name in FLUX_NAMES.items():
+        if name not in _SURFACE_ROW:
+            continue
+        q = ds.get(name)
+        if q is None:
+            raise KeyError("device state is missing input quantity %r" % name)
+        if q.dims[0] != "interface_levels":
+            raise ValueError("%s must be resident as [interface_levels][*] (a radiation output) for the in-place surface row" % name)
+        if q.shape[1:] != (ncol,):
+            raise ValueError("ice temperature %s and %s %s do not belong to one grid" % (t.shape, name, q.shape))
+        fluxes[k] = q.ptr                              # row 0 = the surface
+    shapes = [height.shape] + [x.shape for x in (thick, snow, base, lh, sh, area)]
+    if height.shape != (nlay, ncol) or any(x.shape != (ncol,) for x in (thick, snow, base, lh, sh, area)):
+        raise ValueError("ice temperature %s, heights %s and the columns %s do not belong to one grid" % (t.shape, height.shape, shapes[1:]))
+    ds.join_streams()      # the longwave fluxes in the state may be this step's
+    work = _step_work(self, ds, "ice%d" % self.kind, ncol)
+    t_new, h_new = work("t", t.units, like=t), work("height", height.units, like=height)
+    thick_new, snow_new, tsfc = work("thick", thick.units), work("snow", snow.units), work("tsfc", "degK")
+    base_flux, cond, albedo = work("base_flux", "W m^-2"), work("cond", "W m^-2"), work("albedo", "dimensionless")
+    flags = work("flags", "dimensionless", dtype=np.int32)
+    ds.ctx.surface_ice(self.kind, t.ptr, height.ptr, thick.ptr, snow.ptr, base.ptr, fluxes, area.ptr, float(timestep.total_seconds()), self.constants(),
+                       t_out=t_new.ptr, height_out=h_new.ptr, thick_out=thick_new.ptr, snow_out=snow_new.ptr, tsfc_out=tsfc.ptr, base_flux_out=base_flux.ptr,
+                       diagnostics=dict(cond_flux=cond.ptr, albedo=albedo.ptr, flags=flags.ptr), memspace=1, ncol=ncol, nlay=nlay)
+    if check_maximum_height:
+        ds.ctx.synchronize()
+        got = flags.buf.download().reshape(-1)
+        if np.any(got & FLAG_TOO_TALL):
+            raise ValueError(too_tall_message(self._max_height))
+        self.log_negative_energy(got)
+    ds.update({"snow_and_ice_temperature": t_new, "height_on_ice_interface_levels": h_new, self.thickness_name: thick_new,
+               "surface_snow_thickness": snow_new, "surface_temperature": tsfc})
+    self.device_flags = flags      # int32 [*]: bit 0 active, bit 1 negative melt energy clamped, bit 2 taller than the maximum
+    diagnostics = {self.base_flux_name: base_flux, "surface_albedo_for_direct_shortwave": albedo, "surface_albedo_for_diffuse_shortwave": albedo}
+    if self.kind == 0:
+        diagnostics["surface_downward_heat_flux_in_sea_ice"] = cond
+    return diagnostics, ds
+
+
+def sea_ice_device_call(self, ds, timestep, check_maximum_height=True):
+    """SeaIce on a DeviceState (surface_ice_device_call)."""
+    return surface_ice_device_call(self, ds, timestep, check_maximum_height)
+
+
+def land_ice_device_call(self, ds, timestep, check_maximum_height=True):
+    """LandIce on a DeviceState (surface_ice_device_call)."""
+    return surface_ice_device_call(self, ds, timestep, check_maximum_height)
+
+
 # ---- time stepping on the device ------------------------------------------------------------------------------------
 _AB = {1: (1.0,), 2: (1.5, -0.5), 3: (23.0 / 12.0, -16.0 / 12.0, 5.0 / 12.0), 4: (55.0 / 24.0, -59.0 / 24.0, 37.0 / 24.0, -9.0 / 24.0)}
 

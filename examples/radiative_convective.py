@@ -10,7 +10,7 @@ the first step, the column starts on a lapse rate steeper than the dry adiabat (
 isothermal 290 K.
 
     python examples/radiative_convective.py [--steps 60] [--device-resident] [--boundary-layer | --simple-physics] [--moist-convection]
-                                            [--gray-longwave] [--grid-scale-condensation]
+                                            [--gray-longwave] [--grid-scale-condensation] [--sea-ice]
 
 --boundary-layer closes that gap: SimpleBoundaryLayer (bulk surface fluxes, implicit diffusion of T, q, u, v) steps after the time
 stepper and before the adjustment, and its two flux diagnostics go into the state, so the slab feels them from the next step
@@ -49,16 +49,19 @@ import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from climt_amd import (AdamsBashforth, DryConvectiveAdjustment, EmanuelConvection, Frierson06LongwaveOpticalDepth, GrayLongwaveRadiation,  # noqa: E402
-                       GridScaleCondensation, RRTMGLongwave, RRTMGShortwave, SimpleBoundaryLayer, SimplePhysics, SlabSurface, get_default_state, get_grid)
+                       GridScaleCondensation, RRTMGLongwave, SeaIce, RRTMGShortwave, SimpleBoundaryLayer, SimplePhysics, SlabSurface, get_default_state, get_grid)
 
 
 def run(steps=60, device_resident=False, report=None, boundary_layer=False, moist_convection=False, simple_physics=False, gray_longwave=False,
-        grid_scale_condensation=False):
+        grid_scale_condensation=False, sea_ice=False):
     """-> (diagnostics of step 0, state after `steps` steps), both as host DataArrays.  `boundary_layer`: with SimpleBoundaryLayer
     between the time stepper and the adjustment; its diagnostics of step 0 are then among the first.  `moist_convection`: with
     EmanuelConvection in the time stepper's list.  `simple_physics`: with SimplePhysics in the place of the boundary layer.
     `gray_longwave`: the fused Frierson + gray longwave in the place of RRTMG's.  `grid_scale_condensation`: with
-    GridScaleCondensation before the adjustment."""
+    GridScaleCondensation before the adjustment.  `sea_ice`: the surface is 2 m of sea ice under 0.1 m of snow and SeaIce steps
+    the snow/ice column in front of the time stepper (and so of SlabSurface, which reads the flux SeaIce writes).  The order in
+    which things run is the order of the loop below; `steppers` only tells get_default_state and DeviceState.from_host which
+    inputs to serve.  On the first step no radiation has run yet, so SeaIce reads the default state's radiative fluxes: zeros."""
     if boundary_layer and simple_physics:
         raise ValueError("boundary_layer and simple_physics are exclusive: both exchange heat, moisture and momentum with the surface")
     if grid_scale_condensation and simple_physics:
@@ -83,6 +86,10 @@ def run(steps=60, device_resident=False, report=None, boundary_layer=False, mois
         condensation = GridScaleCondensation()
         steppers = steppers[:-1] + [condensation, dry_convection]
 
+    if sea_ice:
+        ice = SeaIce()
+        steppers = [ice] + steppers
+
     grid = get_grid(nx=1, ny=1, nz=30)
     state = get_default_state(components + steppers, grid_state=grid)
     p = state["air_pressure"].values
@@ -94,6 +101,15 @@ def run(steps=60, device_resident=False, report=None, boundary_layer=False, mois
     state["surface_temperature"].values[:] = 300.0
     state["ocean_mixed_layer_thickness"].values[:] = 5.0
     state["area_type"].values[:] = "sea"
+    if sea_ice:
+        state["area_type"].values[:] = "sea_ice"
+        state["sea_ice_thickness"].values[:] = 2.0
+        state["surface_snow_thickness"].values[:] = 0.1
+        total = 2.1
+        n = state["height_on_ice_interface_levels"].values.shape[0]
+        state["height_on_ice_interface_levels"].values[:] = (total * np.arange(n) / (n - 1)).reshape((n,) + (1,) * (state["height_on_ice_interface_levels"].values.ndim - 1))
+        state["snow_and_ice_temperature"].values[:] = 265.0
+        state["surface_temperature"].values[:] = 265.0
     if moist_convection:
         t = state["air_temperature"].values
         es = 611.2 * np.exp(17.67 * (t - 273.15) / (t - 29.65))
@@ -122,10 +138,19 @@ def run(steps=60, device_resident=False, report=None, boundary_layer=False, mois
 
     first = None
     for i in range(steps):
+        if sea_ice:
+            diagnostics, new_state = ice(state, timestep)
+            state.update(diagnostics)
+            state.update(new_state)
+            if i == 0:
+                first_ice = to_host(state, list(diagnostics))
+
         diagnostics, state = time_stepper(state, timestep)      # (the reference's order: the new state, then the diagnostics into it)
         state.update(diagnostics)
         if i == 0:
             first = to_host(state, list(diagnostics))
+            if sea_ice:
+                first.update(first_ice)
 
         if boundary_layer or simple_physics:
             diagnostics, new_state = simple_boundary_layer(state, timestep)
@@ -162,6 +187,7 @@ def main():
     ap.add_argument("--moist-convection", action="store_true")
     ap.add_argument("--gray-longwave", action="store_true")
     ap.add_argument("--grid-scale-condensation", action="store_true")
+    ap.add_argument("--sea-ice", action="store_true")
     a = ap.parse_args()
 
     def report(i, state):
@@ -177,7 +203,7 @@ def main():
             state["air_temperature_tendency_from_longwave"].values.ravel()[-1], rain))
     if a.grid_scale_condensation and a.simple_physics:
         ap.error("--grid-scale-condensation and --simple-physics are exclusive")
-    run(a.steps, a.device_resident, report, a.boundary_layer, a.moist_convection, a.simple_physics, a.gray_longwave, a.grid_scale_condensation)
+    run(a.steps, a.device_resident, report, a.boundary_layer, a.moist_convection, a.simple_physics, a.gray_longwave, a.grid_scale_condensation, a.sea_ice)
 
 
 if __name__ == "__main__":

@@ -906,6 +906,47 @@ typedef struct {
 } rrtmg_grid_scale_condensation;
 int rrtmg_hip_grid_scale_condensation(rrtmg_ctx *ctx, const rrtmg_grid_scale_condensation *a);
 
+/* ---- sea ice and land ice: one implicit snow/ice column ---- */
+/* climt's SeaIce (kind 0, _components/sea_ice/component.py) and LandIce (kind 1, _components/land_ice/component.py), by column,
+ * with their shared Crank-Nicolson solver and Thomas sweep, in the reference's order of operations.  nlay counts the ice
+ * interface levels (nodes): node 0 is the base and node nlay-1 the surface; at least 3.
+ *   active: kind 0 area_type == 3 (sea_ice) && thick > 0 && thick + snow >= eps;  kind 1 area_type 0 (land) or 1 (land_ice) and
+ *   thick + snow >= eps.  net = sw_down + lw_down - sw_up - lw_up - sh - lh.  base: kind 0 the ocean heat flux (the base is a flux
+ *   boundary at -base), kind 1 the soil surface temperature (a Dirichlet base).  The top is held at t_melt where t[nlay-1] >=
+ *   t_melt - eps; where the flux conducted to the surface then exceeds net, the column is solved again with a flux top.  Melt
+ *   energy is rounded to 1e-6 (half-even) and clamped at 0; melt eats the snow first, then the ice.
+ *   base_flux_out: kind 0 the heat flux to the sea water, rounded to 1e-6, plus what a negative thickness leaves over (the
+ *   thickness is then an exact 0.0); kind 1 the upward ground flux (t_out[0] - t_out[1]) kappa[0] / dz, thickness and snow clamped at
+ *   0.0.  height_out[j] = (thick_out + snow_out) j / (nlay - 1).  tsfc_out = t_out[nlay-1].  cond_flux: kind 0 the flux conducted
+ *   to the surface, kind 1 +0.0.  albedo: albedo_snow where snow is left, else albedo_ice; albedo_melt where anything melted.
+ * A column that is not active keeps the bits of t, height, thick and snow, gets tsfc_out = t[nlay-1], base_flux_out = base (kind 0)
+ * and +0.0 for every other diagnostic.  A column that would be active and is taller than max_height is left as inactive and
+ * flagged (the reference raises).  flags: bit 0 active, bit 1 negative melt energy was clamped, bit 2 taller than max_height.
+ * cond_flux, albedo and flags may each be NULL.  In place: t_out == t, height_out == height, thick_out == thick, snow_out ==
+ * snow and, for kind 0 only, base_flux_out == base -- exactly; any other overlap of an output with an input or another output
+ * returns RRTMG_ERR_ARG, as do a NULL struct, a struct_size other than sizeof(rrtmg_surface_ice), ncol <= 0, nlay < 3, a memspace
+ * other than 0 and 1, a kind other than 0 and 1, reserved != 0, dt <= 0, a NULL required array and base_flux_out == base with kind 1
+ * -- before anything is read or enqueued.  Needs neither rrtmg_hip_sw_init nor rrtmg_hip_lw_init.  Host pointers: the inputs go up,
+ * the outputs asked for come back.  Device pointers: one launch on the context's main stream; in deferred mode the call returns
+ * once enqueued.  The four radiative fluxes are [ncol] rows: the surface row of a resident [level][ncol] array is such a pointer.
+ * Probe for it by symbol; RRTMG_HIP_ABI_VERSION is unchanged. */
+typedef struct {
+  uint32_t struct_size; int32_t ncol, nlay, memspace;
+  int32_t kind, reserved;                             /* kind: 0 sea ice, 1 land ice; reserved: 0 */
+  const double *t, *height;                           /* [nlay][ncol]; height is read for the columns that are not active only */
+  const double *thick, *snow, *base;                  /* [ncol]; base: kind 0 the ocean heat flux, kind 1 the soil temperature */
+  const double *sw_down, *lw_down, *sw_up, *lw_up, *lh, *sh;   /* [ncol] */
+  const int32_t *area_type;                           /* [ncol]: 0 land, 1 land_ice, 2 sea, 3 sea_ice */
+  double dt;
+  double rho_ice, rho_snow, c_ice, c_snow, k_ice, k_snow, lf, t_melt, eps, max_height, albedo_snow, albedo_ice, albedo_melt;
+  double *t_out, *height_out;                         /* [nlay][ncol]; each may be its own input (in place) */
+  double *thick_out, *snow_out, *tsfc_out;            /* [ncol]; thick_out and snow_out may be their own inputs */
+  double *base_flux_out;                              /* [ncol]; kind 0: may be base */
+  double *cond_flux, *albedo;                         /* [ncol], or NULL */
+  int32_t *flags;                                     /* [ncol], or NULL */
+} rrtmg_surface_ice;
+int rrtmg_hip_surface_ice(rrtmg_ctx *ctx, const rrtmg_surface_ice *a);
+
 /* ---- reference-compatible entry points (host pointers, default context) ---------------- */
 int rrtmg_hip_default_status(void);
 const char *rrtmg_hip_default_error(void);
