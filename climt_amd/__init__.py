@@ -25,11 +25,14 @@ from .simple_physics import SimplePhysics  # noqa: F401,E402
 from .gray_radiation import Frierson06LongwaveOpticalDepth, GrayLongwaveRadiation  # noqa: F401,E402
 from .grid_scale_condensation import GridScaleCondensation  # noqa: F401,E402
 from .surface_ice import LandIce, SeaIce  # noqa: F401,E402
+from .bucket_hydrology import BucketHydrology  # noqa: F401,E402
+from .second_best import (BestSoilProperties, BestSubsurfaceTransport, BestSurfaceAlbedo, BestSurfaceFluxes, BestSurfaceLayer,  # noqa: F401,E402
+                          SecondBEST)
 from .emanuel import EmanuelConvection  # noqa: F401,E402
 from .slab_surface import SlabSurface  # noqa: F401,E402
 from .timestepping import AdamsBashforth  # noqa: F401,E402
 from .wrappers import UpdateFrequencyWrapper  # noqa: F401,E402
 from .intermittent import IntermittentLongwave, IntermittentShortwave  # noqa: F401,E402
 
-__all__ = ["RRTMGLongwave", "RRTMGShortwave", "Instellation", "BergerSolarInsolation", "SlabSurface", "DryConvectiveAdjustment", "SimpleBoundaryLayer", "EmanuelConvection", "SimplePhysics", "GrayLongwaveRadiation", "Frierson06LongwaveOpticalDepth", "GridScaleCondensation", "SeaIce", "LandIce", "get_grid", "get_default_state", "UpdateFrequencyWrapper", "IntermittentShortwave", "IntermittentLongwave", "AdamsBashforth",
+__all__ = ["RRTMGLongwave", "RRTMGShortwave", "Instellation", "BergerSolarInsolation", "SlabSurface", "DryConvectiveAdjustment", "SimpleBoundaryLayer", "EmanuelConvection", "SimplePhysics", "GrayLongwaveRadiation", "Frierson06LongwaveOpticalDepth", "GridScaleCondensation", "SeaIce", "LandIce", "BucketHydrology", "SecondBEST", "BestSoilProperties", "BestSurfaceAlbedo", "BestSurfaceLayer", "BestSurfaceFluxes", "BestSubsurfaceTransport", "get_grid", "get_default_state", "UpdateFrequencyWrapper", "IntermittentShortwave", "IntermittentLongwave", "AdamsBashforth",
            "Context", "RRTMGError", "DeviceState", "DeviceQuantity", "DeviceAdamsBashforth", "radiation_step"]

@@ -283,6 +283,36 @@ class SurfaceIce(C.Structure):
                 + [(n, _vp) for n in SURFACE_ICE_OUT + SURFACE_ICE_DIAG])
 
 
+LAND_FLUXES = ("sw_down", "lw_down", "sw_up", "lw_up")
+BUCKET_HYDROLOGY_SCALARS = ("rd", "cp", "rho_water", "lv", "bulk_coefficient", "beta_parameter", "soil_moisture_max", "deep_soil_moisture_max", "tau_m", "deep_ratio", "tau_drain")
+BUCKET_HYDROLOGY_DEEP = ("deep_moisture", "deep_temperature")      # the inputs, outputs (+ "_out") and diagnostics of layers 2 only
+BUCKET_HYDROLOGY_IN = (("t_air", "q_air", "u", "v", "p_air", "ts", "q_sfc") + LAND_FLUXES
+                       + ("soil_moisture", "precip_conv", "precip_strat", "density", "thickness", "heat_capacity") + BUCKET_HYDROLOGY_DEEP)
+BUCKET_HYDROLOGY_OUT = ("ts_out", "soil_moisture_out", "deep_moisture_out", "deep_temperature_out")
+BUCKET_HYDROLOGY_DIAG = ("precip", "lh", "sh", "evaporation", "runoff", "deep_fraction")
+
+
+class BucketHydrology(C.Structure):
+    """mirrors `rrtmg_bucket_hydrology` (include/rrtmg_hip.h), field for field"""
+    _fields_ = ([("struct_size", C.c_uint32), ("ncol", _i32), ("nlay", _i32), ("memspace", _i32), ("layers", _i32), ("has_drain", _i32), ("reserved", _i32), ("reserved2", _i32)]
+                + [(n, _vp) for n in BUCKET_HYDROLOGY_IN] + [("dt", _f64)] + [(n, _f64) for n in BUCKET_HYDROLOGY_SCALARS] + [("pressure_scale", _f64)]
+                + [(n, _vp) for n in BUCKET_HYDROLOGY_OUT + BUCKET_HYDROLOGY_DIAG])
+
+
+SECOND_BEST_CONSTANTS = ("rd", "g", "cp", "lv", "lf", "rho_water", "karman", "t_freeze", "min_wind", "kappa_soil", "cv_soil", "colour", "texture", "B", "K_H0", "psi_0")
+SECOND_BEST_SOIL = ("t_soil", "x_w", "x_i", "height")
+SECOND_BEST_IN = SECOND_BEST_SOIL + ("t_air", "q_air", "u", "v", "p_air", "ps", "ts", "snow") + LAND_FLUXES + ("area_type",)
+SECOND_BEST_OUT = ("t_soil_out", "x_w_out", "x_i_out", "ts_out", "snow_out")
+SECOND_BEST_DIAG = ("sh", "lh", "evaporation", "albedo_direct", "albedo_diffuse", "cd_heat", "cd_momentum", "t2m", "q2m", "u10", "v10", "flags")
+
+
+class SecondBest(C.Structure):
+    """mirrors `rrtmg_second_best` (include/rrtmg_hip.h), field for field"""
+    _fields_ = ([("struct_size", C.c_uint32), ("ncol", _i32), ("nlay", _i32), ("memspace", _i32)] + [(n, _vp) for n in SECOND_BEST_IN]
+                + [("dt", _f64)] + [(n, _f64) for n in SECOND_BEST_CONSTANTS] + [("pressure_scale", _f64), ("ps_scale", _f64), ("reserved", _i32), ("reserved2", _i32)]
+                + [(n, _vp) for n in SECOND_BEST_OUT + SECOND_BEST_DIAG])
+
+
 # What Context._column_call knows of each column component's arrays besides the three tuples above: `columns` are [ncol], `levels`
 # [nlay+1][ncol] and the others [nlay][ncol]; `int32` are int32 and the others float64 (tests/test_call_arrays.py holds all three to
 # the library's own tables); `optional` profiles are named in brackets by the shape message; `in_place`: (output, input) pairs for
@@ -302,6 +332,13 @@ COLUMN_ARRAYS = {
     "surface_ice": dict(IN=SURFACE_ICE_IN, DIAG=SURFACE_ICE_DIAG, int32=("area_type", "flags"), optional=(),
                         in_place=(("t_out", "t"), ("height_out", "height"), ("thick_out", "thick"), ("snow_out", "snow"), ("base_flux_out", "base")),
                         columns=("thick", "snow", "base") + SURFACE_ICE_FLUXES + ("area_type", "thick_out", "snow_out", "tsfc_out", "base_flux_out", "cond_flux", "albedo", "flags")),
+    # (the land surface: `grid` names the input whose shape is the call's -- [nlay][ncol], or [ncol] where every array is a column and nlay is 1)
+    "bucket_hydrology": dict(IN=BUCKET_HYDROLOGY_IN, DIAG=BUCKET_HYDROLOGY_DIAG, grid="ts", optional=(),
+                             in_place=tuple((n + "_out", n) for n in ("ts", "soil_moisture") + BUCKET_HYDROLOGY_DEEP),
+                             columns=BUCKET_HYDROLOGY_IN + BUCKET_HYDROLOGY_OUT + BUCKET_HYDROLOGY_DIAG),
+    "second_best": dict(IN=SECOND_BEST_IN, DIAG=SECOND_BEST_DIAG, grid="t_soil", int32=("area_type", "flags"), optional=(),
+                        in_place=tuple((n + "_out", n) for n in ("t_soil", "x_w", "x_i", "ts", "snow")),
+                        columns=SECOND_BEST_IN[4:] + ("ts_out", "snow_out") + SECOND_BEST_DIAG),
 }
 
 
@@ -390,6 +427,10 @@ def load_library():
         lib.rrtmg_hip_grid_scale_condensation.argtypes = [_vp, C.POINTER(GridScaleCondensation)]
     if hasattr(lib, "rrtmg_hip_surface_ice"):               # (likewise: the snow/ice column of SeaIce and LandIce)
         lib.rrtmg_hip_surface_ice.argtypes = [_vp, C.POINTER(SurfaceIce)]
+    if hasattr(lib, "rrtmg_hip_bucket_hydrology"):          # (likewise: the land surface, BucketHydrology)
+        lib.rrtmg_hip_bucket_hydrology.argtypes = [_vp, C.POINTER(BucketHydrology)]
+    if hasattr(lib, "rrtmg_hip_second_best"):               # (likewise: the land surface, SecondBEST)
+        lib.rrtmg_hip_second_best.argtypes = [_vp, C.POINTER(SecondBest)]
     lib.rrtmg_hip_copy_blocks.argtypes =[_vp, C.c_int, _vp, C.c_long, C.c_long, _vp, _vp, _vp]
     lib.rrtmg_hip_mcica_mask.argtypes = [_vp] + [C.c_int] * 6 + [_vp] * 3
     _lib = lib
@@ -686,7 +727,11 @@ class Context:
             self._ck(fn(self.h, C.byref(a)))
             return outs, diagnostics
         mine, given = given, {n: np.ascontiguousarray(x, dtype=dtype(n)) for n, x in given.items()}
-        shape = given["t"].shape if "t" in given else (given["pint"].shape[0] - 1,) + given["pint"].shape[1:]      # (no profile: the grid is pint's)
+        grid = COLUMN_ARRAYS[entry].get("grid")
+        if grid is not None:
+            shape = given[grid].shape if given[grid].ndim != 1 else (1,) + given[grid].shape
+        else:
+            shape = given["t"].shape if "t" in given else (given["pint"].shape[0] - 1,) + given["pint"].shape[1:]      # (no profile: the grid is pint's)
         profiles, cols = [n for n in IN if n not in columns + levels], [n for n in IN if n in columns]
         if len(shape) != 2 or any(given[n].shape != shape for n in profiles if n in given) or any(given[n].shape != (shape[0] + 1, shape[1]) for n in levels if n in given):
             raise ValueError("%s: %s%s must be [nlay][ncol] arrays of one shape and pint [nlay+1][ncol]"
@@ -708,7 +753,7 @@ class Context:
                 raise ValueError("%s: %s is written in place: a C-contiguous %s array of the right size" % (entry, name, dtype(name).name))
         a.nlay, a.ncol = shape
         for out, inp in in_place:
-            if outs[out] is mine[inp]:
+            if out in outs and outs[out] is mine[inp]:      # (a pair the call does not have: BucketHydrology with one layer)
                 given[inp] = outs[out]
         for name, x in list(given.items()) + list(outs.items()) + list(diagnostics.items()):
             setattr(a, name, x.ctypes.data)
@@ -942,6 +987,66 @@ class Context:
         given.update({n: fluxes[n] for n in SURFACE_ICE_FLUXES})
         return self._column_call("surface_ice", a, given, dict(t_out=t_out, height_out=height_out, thick_out=thick_out, snow_out=snow_out,
                                                                tsfc_out=tsfc_out, base_flux_out=base_flux_out), diagnostics, memspace, ncol, nlay)
+
+    @property
+    def has_bucket_hydrology(self):
+        """Whether the library exports the land surface of BucketHydrology (rrtmg_hip_bucket_hydrology; probed by the symbol)."""
+        return hasattr(self.lib, "rrtmg_hip_bucket_hydrology")
+
+    @_locked
+    def bucket_hydrology(self, layers, arrays, dt, scalars, outs=None, diagnostics=True, pressure_scale=1.0, memspace=0, ncol=None):
+        """climt's BucketHydrology by column (rrtmg_hip_bucket_hydrology) -> (outputs, diagnostics): two dicts, by the names of
+        BUCKET_HYDROLOGY_OUT and BUCKET_HYDROLOGY_DIAG.  `layers`: 1 or 2; `arrays`: a dict of the [ncol] inputs
+        (BUCKET_HYDROLOGY_IN: the lowest model level of the atmosphere, the surface level of the four radiative fluxes, the
+        surface and soil columns; the two deep ones with layers 2 only); `scalars`: BUCKET_HYDROLOGY_SCALARS, tau_drain None for
+        no drainage; `pressure_scale`: Pa per unit of p_air.  Host arrays (`outs`: a dict of the caller's output arrays, each
+        allocated unless given; each may be its own input), `diagnostics` True: precip, lh, sh, evaporation and, with layers 2,
+        runoff and deep_fraction (False or None: none; a dict: those it names).  Or device pointers (or DeviceArrays) with
+        memspace=1 -- then every output of the layer count, `ncol`, and `diagnostics` a dict of device pointers or None; one
+        launch on the main stream."""
+        if not self.has_bucket_hydrology:
+            raise RRTMGError(4, "this librrtmg_hip.so has no rrtmg_hip_bucket_hydrology (land surface: BucketHydrology)")
+        a = BucketHydrology()
+        a.struct_size, a.memspace, a.layers, a.dt, a.pressure_scale = C.sizeof(BucketHydrology), 1 if memspace else 0, int(layers), float(dt), float(pressure_scale)
+        a.has_drain = 0 if scalars.get("tau_drain") is None else 1
+        for n in BUCKET_HYDROLOGY_SCALARS:
+            setattr(a, n, 0.0 if scalars.get(n) is None else float(scalars[n]))
+        deep = int(layers) == 2
+        skip = () if deep else BUCKET_HYDROLOGY_DEEP
+        given = {n: arrays[n] for n in BUCKET_HYDROLOGY_IN if n not in skip}
+        outs = dict(outs or {})
+        outs = {n: outs.get(n) for n in BUCKET_HYDROLOGY_OUT if n[:-4] not in skip}
+        if diagnostics is True and not memspace:
+            shape = np.shape(arrays["ts"])
+            diagnostics = {n: np.empty(shape) for n in BUCKET_HYDROLOGY_DIAG[:6 if deep else 4]}
+        return self._column_call("bucket_hydrology", a, given, outs, diagnostics, memspace, ncol, 1)
+
+    @property
+    def has_second_best(self):
+        """Whether the library exports the land surface of SecondBEST (rrtmg_hip_second_best; probed by the symbol)."""
+        return hasattr(self.lib, "rrtmg_hip_second_best")
+
+    @_locked
+    def second_best(self, arrays, dt, constants, outs=None, diagnostics=True, pressure_scale=1.0, ps_scale=1.0, memspace=0, ncol=None, nlay=None):
+        """climt's SecondBEST with its default processes by column (rrtmg_hip_second_best) -> (outputs, diagnostics): two dicts,
+        by the names of SECOND_BEST_OUT and SECOND_BEST_DIAG.  `arrays`: a dict of the inputs (SECOND_BEST_IN): t_soil, x_w, x_i,
+        height [nlay][ncol] (nlay: the soil interface levels, at least 2; node 0 is the bottom), the others [ncol] (the lowest model
+        level of the atmosphere, the surface level of the four radiative fluxes), area_type int32 codes (slab_surface.AREA_MAP);
+        `constants`: SECOND_BEST_CONSTANTS; `pressure_scale`, `ps_scale`: Pa per unit of p_air and of ps.  Host arrays (`outs`: a
+        dict of the caller's output arrays, each allocated unless given; each may be its own input), `diagnostics` True: all of
+        SECOND_BEST_DIAG (False or None: none; a dict: those it names).  Or device pointers (or DeviceArrays) with memspace=1 --
+        then the five outputs, `ncol` and `nlay`, and `diagnostics` a dict of device pointers or None; one launch on the main
+        stream."""
+        if not self.has_second_best:
+            raise RRTMGError(4, "this librrtmg_hip.so has no rrtmg_hip_second_best (land surface: SecondBEST)")
+        a = SecondBest()
+        a.struct_size, a.memspace, a.dt = C.sizeof(SecondBest), 1 if memspace else 0, float(dt)
+        a.pressure_scale, a.ps_scale = float(pressure_scale), float(ps_scale)
+        for n in SECOND_BEST_CONSTANTS:
+            setattr(a, n, float(constants[n]))
+        outs = dict(outs or {})
+        return self._column_call("second_best", a, {n: arrays[n] for n in SECOND_BEST_IN}, {n: outs.get(n) for n in SECOND_BEST_OUT}, diagnostics,
+                                 memspace, ncol, nlay)
 
     @_locked
     def solar_insolation(self, lat, lon, sin_delta, cos_delta, fractional_day, irradiance):

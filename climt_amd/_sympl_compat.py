@@ -88,6 +88,12 @@ except ImportError:
         ("heat_capacity_of_solid_phase_as_snow", "J/kg/degK"): 2108.0,
         ("latent_heat_of_fusion", "J/kg"): 333550.0,
         ("freezing_temperature_of_liquid_phase", "degK"): 273.0,
+        # BucketHydrology / SecondBEST (bucket_hydrology/component.py, second_best/), under the unit strings they ask with; the
+        # other pairs they ask for stand above.  The latent heat of vaporization and the von Karman constant are sympl's defaults
+        # as remembered; no reference data pins them
+        ("density_of_liquid_water", "kg m^-3"): 1000.0,
+        ("latent_heat_of_vaporization", "J/kg"): 2.5e6,
+        ("von_karman_constant", "dimensionless"): 0.4,
     }
     _constant_overrides = {}
 
@@ -113,7 +119,9 @@ except ImportError:
                 "K day^-1": ("K s^-1", 1.0 / 86400.0), "K s^-1": ("K s^-1", 1.0), "degK s^-1": ("K s^-1", 1.0),
                 "degrees": ("radians", np.pi / 180.0), "radians": ("radians", 1.0),
                 "degrees_north": ("degrees_north", 1.0), "degrees_N": ("degrees_north", 1.0),
-                "degrees_east": ("degrees_east", 1.0), "degrees_E": ("degrees_east", 1.0), "m": ("m", 1.0), "um": ("m", 1.e-6)}
+                "degrees_east": ("degrees_east", 1.0), "degrees_E": ("degrees_east", 1.0), "m": ("m", 1.0), "um": ("m", 1.e-6),
+                # precipitation rates: the default state has the convective one in mm day^-1, BucketHydrology asks for m s^-1
+                "m s^-1": ("m s^-1", 1.0), "mm day^-1": ("m s^-1", 1.e-3 / 86400.0)}
 
     def _canon(u):
         u = (u or "").strip()

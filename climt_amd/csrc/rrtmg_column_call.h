@@ -36,10 +36,11 @@ struct ColumnTable {
   const ColumnRow *rows;
   int n;
 };
-constexpr int kColumnMaxRows = 32;           // the rows of a table are the bits of an unsigned
+constexpr int kColumnMaxRows = 64;           // the rows of a table are the bits of a ColumnMask
+using ColumnMask = uint64_t;
 template <int N>
 constexpr ColumnTable column_table(const char *entry, const char *strct, int nlay_min, const char *ncol_msg, const char *nlay_msg, const char *note, const ColumnRow (&rows)[N]) {
-  static_assert(N <= kColumnMaxRows, "a table has at most 32 rows");
+  static_assert(N <= kColumnMaxRows, "a table has at most 64 rows");
   return {entry, strct, nlay_min, ncol_msg, nlay_msg, note, rows, N};
 }
 
@@ -75,16 +76,16 @@ constexpr int column_index(const ColumnTable &t, const char *name) {
 }
 // the bits of the named rows.  An entry keeps the result in a constexpr variable: a name no row has is then a shift by -1 in a
 // constant expression, which does not compile
-constexpr unsigned column_bits(const ColumnTable &t, std::initializer_list<const char *> names) {
-  unsigned bits = 0;
-  for (const char *name : names) bits |= 1u << column_index(t, name);
+constexpr ColumnMask column_bits(const ColumnTable &t, std::initializer_list<const char *> names) {
+  ColumnMask bits = 0;
+  for (const char *name : names) bits |= ColumnMask(1) << column_index(t, name);
   return bits;
 }
 // the rows of a call: given (not NULL) and not among those the entry does not read
-inline unsigned column_present(const ColumnTable &t, const void *a, unsigned unread) {
-  unsigned bits = 0;
+inline ColumnMask column_present(const ColumnTable &t, const void *a, ColumnMask unread) {
+  ColumnMask bits = 0;
   for (int i = 0; i < t.n; ++i)
-    if (column_ptr(a, t.rows[i].pub)) bits |= 1u << i;
+    if (column_ptr(a, t.rows[i].pub)) bits |= ColumnMask(1) << i;
   return bits & ~unread;
 }
 
@@ -106,7 +107,7 @@ inline bool aliasing_refusal(const ColumnSpan *s, int n, const char *note, char 
   }
   return false;
 }
-inline int column_spans(const ColumnTable &t, const void *a, size_t ncol, size_t nlay, unsigned present, ColumnSpan *s) {
+inline int column_spans(const ColumnTable &t, const void *a, size_t ncol, size_t nlay, ColumnMask present, ColumnSpan *s) {
   int n = 0;
   for (int i = 0; i < t.n; ++i) {
     const ColumnRow &r = t.rows[i];
@@ -134,7 +135,7 @@ inline bool column_required_refusal(const ColumnTable &t, const void *a, char *m
 // absent row has no slot.
 struct ColumnPlan { size_t at[kColumnMaxRows], total; };
 constexpr size_t kColumnNoSlot = ~(size_t)0;
-inline ColumnPlan column_plan(const ColumnTable &t, size_t ncol, size_t nlay, unsigned present) {
+inline ColumnPlan column_plan(const ColumnTable &t, size_t ncol, size_t nlay, ColumnMask present) {
   ColumnPlan p;
   p.total = 0;
   for (int i = 0; i < kColumnMaxRows; ++i) p.at[i] = kColumnNoSlot;
@@ -173,6 +174,15 @@ inline int column_required(rrtmg_ctx *ctx, const ColumnTable &t, const void *a) 
   return column_required_refusal(t, a, msg, sizeof msg) ? ctx->fail(RRTMG_ERR_ARG, "%s: %s", t.entry, msg) : RRTMG_OK;
 }
 
+// the aliasing refusal of a call (column_call makes it; an entry whose own checks come behind it makes it first itself)
+template <class A>
+int column_aliasing(rrtmg_ctx *ctx, const ColumnTable &t, const A *a, ColumnMask unread) {
+  ColumnSpan spans[kColumnMaxRows];
+  char msg[160];
+  const int n = column_spans(t, a, (size_t)a->ncol, (size_t)a->nlay, column_present(t, a, unread), spans);
+  return aliasing_refusal(spans, n, t.note, msg, sizeof msg) ? ctx->fail(RRTMG_ERR_ARG, "%s: %s", t.entry, msg) : RRTMG_OK;
+}
+
 // one thread per column, tiles of 64 columns, on the context's main stream
 template <class Kernel, class C>
 int column_launch(rrtmg_ctx *ctx, Kernel kernel, size_t ncol, const C &c) {
@@ -181,24 +191,23 @@ int column_launch(rrtmg_ctx *ctx, Kernel kernel, size_t ncol, const C &c) {
   return RRTMG_OK;
 }
 
-// The call behind an entry's own checks: the aliasing refusal; the device; `work` -- the entry's work slabs, allocated before
+// The call behind an entry's own checks: the aliasing refusal (not made again where the entry has made it: `aliasing_checked`); the device; `work` -- the entry's work slabs, allocated before
 // anything is queued, so a failed allocation leaves the stream as it was; under memspace 0 the staging buffer `io` and the inputs
 // that are present going up; the pointers of the call struct `c` bound (memspace 0: the plan's slots, 1: the caller's own; an
 // absent row: nullptr); `launch` -- the entry's launch(es); under memspace 0 the outputs that are present coming back.
 // Device pointers in deferred mode: the call returns once enqueued; otherwise it waits.
 template <class A, class C, class Work, class Launch>
-int column_call(rrtmg_ctx *ctx, const ColumnTable &t, const A *a, C &c, unsigned unread, const char *io, Work work, Launch launch) {
+int column_call(rrtmg_ctx *ctx, const ColumnTable &t, const A *a, C &c, ColumnMask unread, const char *io, Work work, Launch launch, bool aliasing_checked = false) {
   const size_t ncol = (size_t)a->ncol, nlay = (size_t)a->nlay;
-  const unsigned present = column_present(t, a, unread);
-  ColumnSpan spans[kColumnMaxRows];
-  char msg[160];
-  if (aliasing_refusal(spans, column_spans(t, a, ncol, nlay, present, spans), t.note, msg, sizeof msg)) return ctx->fail(RRTMG_ERR_ARG, "%s: %s", t.entry, msg);
-  int rc = ctx_prepare_device(ctx);
+  const ColumnMask present = column_present(t, a, unread);
+  int rc = aliasing_checked ? RRTMG_OK : column_aliasing(ctx, t, a, unread);
+  if (rc) return rc;
+  rc = ctx_prepare_device(ctx);
   if (!rc) rc = work();
   if (rc) return rc;
   hipStream_t s = ctx->stream;
   const bool host = a->memspace == 0;
-  const ColumnPlan plan = column_plan(t, ncol, nlay, host ? present : 0);
+  const ColumnPlan plan = column_plan(t, ncol, nlay, host ? present : ColumnMask(0));
   char *const staged = host ? (char *)ctx->buf(io, plan.total) : nullptr;
   if (host && !staged) return ctx->status;
   void *bound[kColumnMaxRows];

@@ -790,6 +790,89 @@ def land_ice_device_call(self, ds, timestep, check_maximum_height=True):
     return surface_ice_device_call(self, ds, timestep, check_maximum_height)
 
 
+def _land_surface_inputs(self, ds, names, what):
+    """The [ncol] inputs of a land-surface call by pointer: row 0 of a resident [mid_levels][*] profile is the lowest model level,
+    row 0 of a resident [interface_levels][*] radiative flux the surface.  -> ({library name: pointer}, {library name: quantity}, ncol)"""
+    P = self.input_properties
+    ncol = ds.need("surface_temperature", P["surface_temperature"]).shape[0]
+    ptrs, got = {}, {}
+    for k, name in names.items():
+        if name in _SURFACE_ROW:
+            q = ds.get(name)
+            if q is None:
+                raise KeyError("device state is missing input quantity %r" % name)
+            if q.dims[0] != "interface_levels":
+                raise ValueError("%s must be resident as [interface_levels][*] (a radiation output) for the in-place surface row" % name)
+        elif name in ("air_pressure", "surface_air_pressure"):
+            # as resident -- in the units of whichever component asked first (the radiation asks for mbar): the caller hands the
+            # library `pressure_scale` / `ps_scale`, Pa per resident unit.  Only the dims are checked, as in _resident_pressures
+            q = ds.get(name)
+            if q is None:
+                raise KeyError("device state is missing input quantity %r" % name)
+            if tuple(q.dims) != tuple(P[name]["dims"]):
+                raise ValueError("quantity %r is resident as %s, component wants %s" % (name, q.dims, P[name]["dims"]))
+        else:
+            q = ds.need(name, P[name])
+        if q.shape[-1] != ncol or len(q.shape) > 2:
+            raise ValueError("%s %s and the %d columns of the surface temperature do not belong to one grid (%s)" % (name, q.shape, ncol, what))
+        ptrs[k], got[k] = q.ptr, q
+    return ptrs, got, ncol
+
+
+def bucket_hydrology_device_call(self, ds, timestep):
+    """BucketHydrology on a DeviceState: rrtmg_hip_bucket_hydrology with device pointers on the main stream; nothing leaves HBM.
+    The lowest model level of the resident [mid_levels][*] profiles and the surface row of the resident [interface_levels][*]
+    radiative fluxes are bound by pointer; the air pressure is read in its resident unit (`pressure_scale`).  The stepped surface
+    goes to work buffers that alternate with the step count (the state's previous arrays stay what they were) and the state is
+    rebound to them; the diagnostics are DeviceQuantity handles SlabSurface can take from the state.
+    -> (diagnostics, the same state)."""
+    from .bucket_hydrology import DIAGNOSTIC_NAMES, INPUT_NAMES, OUTPUT_NAMES
+    ptrs, got, ncol = _land_surface_inputs(self, ds, self.names(INPUT_NAMES), "the bucket")
+    ds.join_streams()      # the longwave fluxes in the state may be this step's
+    work = _step_work(self, ds, "bucket%d" % self._num_layers, ncol)
+    outs = {k: work(k, self.output_properties[name]["units"]) for k, name in self.names(OUTPUT_NAMES).items()}
+    diag = {k: work(k, self.diagnostic_properties[name]["units"]) for k, name in self.names(DIAGNOSTIC_NAMES).items()}
+    ds.ctx.bucket_hydrology(self._num_layers, ptrs, float(timestep.total_seconds()), self.scalars(), outs={k: x.ptr for k, x in outs.items()},
+                            diagnostics={k: x.ptr for k, x in diag.items()}, pressure_scale=_to_pa(got["p_air"].units), memspace=1, ncol=ncol)
+    ds.update({name: outs[k] for k, name in self.names(OUTPUT_NAMES).items()})
+    return {name: diag[k] for k, name in self.names(DIAGNOSTIC_NAMES).items()}, ds
+
+
+def second_best_device_call(self, ds, timestep):
+    """SecondBEST on a DeviceState: rrtmg_hip_second_best with device pointers on the main stream; nothing leaves HBM.  The soil
+    arrays are resident as [soil_interface_levels][*]; the lowest model level of the [mid_levels][*] profiles and the surface row
+    of the [interface_levels][*] radiative fluxes are bound by pointer; the pressures are read in their resident units
+    (`pressure_scale`, `ps_scale`); the area-type codes are the resident ones, and the kernel decides from them which columns it
+    steps.  The stepped column goes to work buffers that alternate with the step count (the state's previous arrays stay what
+    they were) and the state is rebound to them; the diagnostics are DeviceQuantity handles SlabSurface and the shortwave can
+    take from the state, and the flags stay on the device in the component's `device_flags`.  -> (diagnostics, the same state)."""
+    from .second_best import DIAGNOSTIC_NAMES, INPUT_NAMES, OUTPUT_NAMES
+    ptrs, got, ncol = _land_surface_inputs(self, ds, INPUT_NAMES, "SecondBEST")
+    t_soil = got["t_soil"]
+    if len(t_soil.shape) != 2:
+        raise ValueError("quantity 'soil_temperature' is resident as %s, component wants %s" % (t_soil.dims, self.input_properties["soil_temperature"]["dims"]))
+    nlay = t_soil.shape[0]
+    if any(got[k].shape != (nlay, ncol) for k in ("x_w", "x_i", "height")):
+        raise ValueError("soil temperature %s, water %s, ice %s and heights %s do not belong to one grid" % (t_soil.shape, got["x_w"].shape, got["x_i"].shape, got["height"].shape))
+    area = ds.get("area_type")
+    if area is None:
+        raise KeyError("device state is missing input quantity 'area_type'")
+    if area.shape != (ncol,):
+        raise ValueError("area types %s and the %d columns of the surface temperature do not belong to one grid" % (area.shape, ncol))
+    ptrs["area_type"] = area.ptr
+    ds.join_streams()      # the longwave fluxes in the state may be this step's
+    work = _step_work(self, ds, "best", ncol)
+    outs = {k: work(k, self.output_properties[name]["units"], like=got[k[:-4]] if k in ("t_soil_out", "x_w_out", "x_i_out") else None) for k, name in OUTPUT_NAMES.items()}
+    diag = {k: work(k, self.diagnostic_properties[name]["units"]) for k, name in DIAGNOSTIC_NAMES.items()}
+    flags = work("flags", "dimensionless", dtype=np.int32)
+    ds.ctx.second_best(ptrs, float(timestep.total_seconds()), self.constants(), outs={k: x.ptr for k, x in outs.items()},
+                       diagnostics=dict({k: x.ptr for k, x in diag.items()}, flags=flags.ptr), pressure_scale=_to_pa(got["p_air"].units),
+                       ps_scale=_to_pa(got["ps"].units), memspace=1, ncol=ncol, nlay=nlay)
+    ds.update({name: outs[k] for k, name in OUTPUT_NAMES.items()})
+    self.device_flags = flags      # int32 [*]: bit 0 active, bit 1 the unstable branch, bit 2 capped at the freezing temperature
+    return {name: diag[k] for k, name in DIAGNOSTIC_NAMES.items()}, ds
+
+
 # ---- time stepping on the device ------------------------------------------------------------------------------------
 _AB = {1: (1.0,), 2: (1.5, -0.5), 3: (23.0 / 12.0, -16.0 / 12.0, 5.0 / 12.0), 4: (55.0 / 24.0, -59.0 / 24.0, 37.0 / 24.0, -9.0 / 24.0)}
 

@@ -11,6 +11,7 @@ isothermal 290 K.
 
     python examples/radiative_convective.py [--steps 60] [--device-resident] [--boundary-layer | --simple-physics] [--moist-convection]
                                             [--gray-longwave] [--grid-scale-condensation] [--sea-ice]
+                                            [--land-surface bucket|second_best]
 
 --boundary-layer closes that gap: SimpleBoundaryLayer (bulk surface fluxes, implicit diffusion of T, q, u, v) steps after the time
 stepper and before the adjustment, and its two flux diagnostics go into the state, so the slab feels them from the next step
@@ -49,11 +50,11 @@ import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from climt_amd import (AdamsBashforth, DryConvectiveAdjustment, EmanuelConvection, Frierson06LongwaveOpticalDepth, GrayLongwaveRadiation,  # noqa: E402
-                       GridScaleCondensation, RRTMGLongwave, SeaIce, RRTMGShortwave, SimpleBoundaryLayer, SimplePhysics, SlabSurface, get_default_state, get_grid)
+                       GridScaleCondensation, RRTMGLongwave, SeaIce, BucketHydrology, SecondBEST, RRTMGShortwave, SimpleBoundaryLayer, SimplePhysics, SlabSurface, get_default_state, get_grid)
 
 
 def run(steps=60, device_resident=False, report=None, boundary_layer=False, moist_convection=False, simple_physics=False, gray_longwave=False,
-        grid_scale_condensation=False, sea_ice=False):
+        grid_scale_condensation=False, sea_ice=False, land_surface=None):
     """-> (diagnostics of step 0, state after `steps` steps), both as host DataArrays.  `boundary_layer`: with SimpleBoundaryLayer
     between the time stepper and the adjustment; its diagnostics of step 0 are then among the first.  `moist_convection`: with
     EmanuelConvection in the time stepper's list.  `simple_physics`: with SimplePhysics in the place of the boundary layer.
@@ -61,7 +62,13 @@ def run(steps=60, device_resident=False, report=None, boundary_layer=False, mois
     GridScaleCondensation before the adjustment.  `sea_ice`: the surface is 2 m of sea ice under 0.1 m of snow and SeaIce steps
     the snow/ice column in front of the time stepper (and so of SlabSurface, which reads the flux SeaIce writes).  The order in
     which things run is the order of the loop below; `steppers` only tells get_default_state and DeviceState.from_host which
-    inputs to serve.  On the first step no radiation has run yet, so SeaIce reads the default state's radiative fluxes: zeros."""
+    inputs to serve.  On the first step no radiation has run yet, so SeaIce reads the default state's radiative fluxes: zeros.
+    `land_surface`: "bucket" or "second_best" -- the surface is land, and BucketHydrology or SecondBEST steps it in the place
+    where SeaIce steps the ice (exclusive with `sea_ice`); SlabSurface reads the surface fluxes it writes."""
+    if land_surface not in (None, "bucket", "second_best"):
+        raise ValueError("land_surface must be None, 'bucket' or 'second_best'")
+    if land_surface and sea_ice:
+        raise ValueError("land_surface and sea_ice are exclusive: one surface type per column")
     if boundary_layer and simple_physics:
         raise ValueError("boundary_layer and simple_physics are exclusive: both exchange heat, moisture and momentum with the surface")
     if grid_scale_condensation and simple_physics:
@@ -90,6 +97,10 @@ def run(steps=60, device_resident=False, report=None, boundary_layer=False, mois
         ice = SeaIce()
         steppers = [ice] + steppers
 
+    if land_surface:
+        land = BucketHydrology() if land_surface == "bucket" else SecondBEST()
+        steppers = [land] + steppers
+
     grid = get_grid(nx=1, ny=1, nz=30)
     state = get_default_state(components + steppers, grid_state=grid)
     p = state["air_pressure"].values
@@ -110,6 +121,19 @@ def run(steps=60, device_resident=False, report=None, boundary_layer=False, mois
         state["height_on_ice_interface_levels"].values[:] = (total * np.arange(n) / (n - 1)).reshape((n,) + (1,) * (state["height_on_ice_interface_levels"].values.ndim - 1))
         state["snow_and_ice_temperature"].values[:] = 265.0
         state["surface_temperature"].values[:] = 265.0
+    if land_surface:
+        state["area_type"].values[:] = "land"
+        state["eastward_wind"].values[:] = 5.0
+        state["surface_temperature"].values[:] = 295.0
+        if land_surface == "bucket":
+            state["surface_specific_humidity"].values[:] = 0.016
+            state["lwe_thickness_of_soil_moisture_content"].values[:] = 0.08
+        else:
+            n = state["height_on_soil_interface_levels"].values.shape[0]
+            state["height_on_soil_interface_levels"].values[:] = (-0.25 * np.arange(n)[::-1]).reshape((n,) + (1,) * (state["height_on_soil_interface_levels"].values.ndim - 1))
+            state["soil_temperature"].values[:] = 295.0
+            state["soil_liquid_water_content"].values[:] = 0.25
+            state["soil_ice_content"].values[:] = 0.0
     if moist_convection:
         t = state["air_temperature"].values
         es = 611.2 * np.exp(17.67 * (t - 273.15) / (t - 29.65))
@@ -138,8 +162,8 @@ def run(steps=60, device_resident=False, report=None, boundary_layer=False, mois
 
     first = None
     for i in range(steps):
-        if sea_ice:
-            diagnostics, new_state = ice(state, timestep)
+        if sea_ice or land_surface:
+            diagnostics, new_state = (ice if sea_ice else land)(state, timestep)
             state.update(diagnostics)
             state.update(new_state)
             if i == 0:
@@ -149,7 +173,7 @@ def run(steps=60, device_resident=False, report=None, boundary_layer=False, mois
         state.update(diagnostics)
         if i == 0:
             first = to_host(state, list(diagnostics))
-            if sea_ice:
+            if sea_ice or land_surface:
                 first.update(first_ice)
 
         if boundary_layer or simple_physics:
@@ -188,6 +212,7 @@ def main():
     ap.add_argument("--gray-longwave", action="store_true")
     ap.add_argument("--grid-scale-condensation", action="store_true")
     ap.add_argument("--sea-ice", action="store_true")
+    ap.add_argument("--land-surface", choices=("bucket", "second_best"))
     a = ap.parse_args()
 
     def report(i, state):
@@ -203,7 +228,7 @@ def main():
             state["air_temperature_tendency_from_longwave"].values.ravel()[-1], rain))
     if a.grid_scale_condensation and a.simple_physics:
         ap.error("--grid-scale-condensation and --simple-physics are exclusive")
-    run(a.steps, a.device_resident, report, a.boundary_layer, a.moist_convection, a.simple_physics, a.gray_longwave, a.grid_scale_condensation, a.sea_ice)
+    run(a.steps, a.device_resident, report, a.boundary_layer, a.moist_convection, a.simple_physics, a.gray_longwave, a.grid_scale_condensation, a.sea_ice, a.land_surface)
 
 
 if __name__ == "__main__":

@@ -947,6 +947,88 @@ typedef struct {
 } rrtmg_surface_ice;
 int rrtmg_hip_surface_ice(rrtmg_ctx *ctx, const rrtmg_surface_ice *a);
 
+/* ---- the land surface: BucketHydrology and SecondBEST ---- */
+/* Both components read only the lowest model level of the atmosphere and the surface level of the four radiative fluxes, so
+ * every atmospheric and flux array is [ncol]: a caller with resident [level][ncol] arrays passes the address of row 0.
+ * pressure_scale (and ps_scale): Pa per unit of p_air (of ps).  Physical constants and component parameters are scalars of the
+ * structs.  Both entries need neither rrtmg_hip_sw_init nor rrtmg_hip_lw_init; host pointers: the inputs go up, the outputs asked
+ * for come back; device pointers: one launch on the context's main stream, in deferred mode the call returns once enqueued.  An
+ * output may be exactly its own input (in place); any other overlap of an output with an input or another output is refused.
+ * Probe for them by symbol; RRTMG_HIP_ABI_VERSION is unchanged. */
+
+/* climt's BucketHydrology (_components/bucket_hydrology/component.py), by column, in the reference's order of operations.  Every
+ * array is [ncol] and nlay must be 1 (the struct has no profile; anything else is refused).  layers: 1 or 2.
+ *   wind = sqrt(v v + u u);  rho = p_air / (rd t_air);  potential = rho bulk_coefficient wind (q_sfc - q_air);  precip = precip_conv +
+ *   precip_strat;  beta = soil_moisture / (beta_parameter soil_moisture_max) where soil_moisture <= beta_parameter soil_moisture_max,
+ *   else 1;  mass flux = beta potential;  evaporation = mass flux / rho_water;  lh = lv mass flux;  sh = rho cp bulk_coefficient wind
+ *   (ts - t_air);  net = sw_down + lw_down - sw_up - lw_up - sh - lh.
+ *   layers 1: the moisture tendency is precip - evaporation where soil_moisture < soil_moisture_max or precip <= evaporation, else 0;
+ *   ts_out = ts + net / (density thickness heat_capacity) dt;  soil_moisture_out = min(soil_moisture + tendency dt, soil_moisture_max).
+ *   layers 2: exchange F = (w_s / S_s - w_d / S_d) (0.5 (S_s + S_d)) / tau_m, drainage D = w_d / tau_drain where has_drain (else 0),
+ *   overflow of either layer is runoff, both layers are clipped to [0, S]; the skin and the deep store (deep_ratio times as thick)
+ *   exchange heat by conduction with k_soil = 2.0.  deep_moisture and deep_temperature and their outputs are required then, and
+ *   not read or written with layers 1 (they may be anything); runoff and deep_fraction likewise.
+ * precip, lh, sh, evaporation, runoff and deep_fraction may each be NULL.  Every column is stepped: the reference does not look
+ * at the area type here.  RRTMG_ERR_ARG: a NULL struct, a struct_size other than sizeof(rrtmg_bucket_hydrology), ncol <= 0, nlay != 1,
+ * a memspace other than 0 and 1, a NULL required array, dt <= 0, layers other than 1 and 2, reserved != 0 and, with layers 2,
+ * tau_m <= 0 or a NULL two-layer array -- before anything is read or enqueued. */
+typedef struct {
+  uint32_t struct_size; int32_t ncol, nlay, memspace;
+  int32_t layers, has_drain, reserved, reserved2;     /* layers: 1 or 2; has_drain: whether tau_drain is read; reserved: 0 */
+  const double *t_air, *q_air, *u, *v, *p_air;        /* [ncol]: the lowest model level */
+  const double *ts, *q_sfc;                           /* [ncol] */
+  const double *sw_down, *lw_down, *sw_up, *lw_up;    /* [ncol]: the surface level */
+  const double *soil_moisture, *precip_conv, *precip_strat, *density, *thickness, *heat_capacity;   /* [ncol] */
+  const double *deep_moisture, *deep_temperature;     /* [ncol]; layers 2 only */
+  double dt, rd, cp, rho_water, lv, bulk_coefficient, beta_parameter, soil_moisture_max, deep_soil_moisture_max, tau_m, deep_ratio, tau_drain;
+  double pressure_scale;
+  double *ts_out, *soil_moisture_out;                 /* [ncol]; each may be its own input */
+  double *deep_moisture_out, *deep_temperature_out;   /* [ncol]; layers 2 only; each may be its own input */
+  double *precip, *lh, *sh, *evaporation;             /* [ncol], or NULL */
+  double *runoff, *deep_fraction;                     /* [ncol], or NULL; layers 2 only */
+} rrtmg_bucket_hydrology;
+int rrtmg_hip_bucket_hydrology(rrtmg_ctx *ctx, const rrtmg_bucket_hydrology *a);
+
+/* climt's SecondBEST (_components/second_best/) with its five default processes, by column, in the reference's order of
+ * operations.  nlay counts the soil interface levels (nodes): node 0 is the bottom and node nlay-1 the surface; at least 2.
+ *   active: area_type 0 (land) or 1 (land_ice).  wind = max(sqrt(u u + v v), min_wind);  rho = p_air / (rd t_air);  z_mid =
+ *   max(((rd t_air) / g) log(ps / p_air), 2.0);  z0 = 0.01 (land) or 0.001 (land_ice).  Drag: C_DN = (karman / (log z_mid - log z0))^2,
+ *   zeta = exp(-karman / sqrt(C_DN)), Ri = -((g z_mid) / (ts U U)) (ts - t_air) with U = max(wind, 1e-3); Ri < 0 is the unstable
+ *   branch (56.768 for momentum, 41.801 for heat), otherwise the stable one with eps = 0.01.  Soil: texture 0.07 and wilting point
+ *   0.01 over land_ice; porosity = 0.6 - 0.03 texture; W_Lu = x_w[nlay-1] / porosity, W_Fu = x_i[nlay-1] / porosity.  Albedo: 0.60 + 0.06
+ *   (1 - W_Lu) over land_ice, else (0.10 + 0.1 colour) + 0.06 (1 - W_Lu).  q_sat: Bolton, at ts and p_air.  Fluxes: sh = rho cp wind
+ *   C_Dh (ts - t_air); E_P = rho (C_Dh wind) (q_sat - q_air); Theta = clip((W_Lu - 0.01) / max(1 - W_Fu, 1e-6), 1e-3, 1); K_HD =
+ *   (-4 K_H0 B psi_0 rho_water porosity (1 - W_Fu)) / (pi dt); E_max = K_HD Theta^(0.5 B + 2) - K_H0 Theta^(2 B + 3); beta =
+ *   clip(W_Fu lv / (lv + lf) + (|E_P| > 1e-12 ? clip(E_max / E_P, 0, 1) : 0), 0, 1); evaporation = beta E_P / rho; lh = lv rho
+ *   evaporation.  net = sw_down + lw_down - sw_up - lw_up - sh - lh.  Soil column: dz = |height[1] - height[0]|, r = kappa_soil dt /
+ *   (cv_soil dz dz); the tridiagonal system has -r on both off-diagonals, 1 + 2 r on the diagonal and 1 + r in its first and last
+ *   row; the right-hand side is t_soil with net dt / (cv_soil dz) added at the surface; Thomas sweep; freeze/melt Gamma = (cv_soil /
+ *   lf) (t_freeze - T) / dt limited to [-rho_water x_i / dt, rho_water x_w / dt]; x_i += Gamma dt / rho_water, x_w -= the same, both
+ *   clamped at 0; T += lf Gamma dt / cv_soil; where net <= 0, T = min(T, t_freeze).  ts_out = t_soil_out[nlay-1]; snow_out = snow.
+ *   t2m, q2m (from the effective surface humidity beta q_sat + (1 - beta) q_air) and the 10 m wind follow the reference's
+ *   interpolate_to_height; u10 = v10 = +0.0 where sqrt(u u + v v) is exactly 0.
+ * A column that is not active keeps the bits of every output's input (untouched when in place) and gets +0.0 in every diagnostic
+ * and 0 in flags.  flags: bit 0 active, bit 1 the unstable branch, bit 2 net <= 0 (the cap at t_freeze applies).  Every
+ * diagnostic may be NULL.  RRTMG_ERR_ARG: a NULL struct, a struct_size other than sizeof(rrtmg_second_best), ncol <= 0, nlay < 2, a
+ * memspace other than 0 and 1, a NULL required array, dt <= 0 and reserved != 0 -- before anything is read or enqueued. */
+typedef struct {
+  uint32_t struct_size; int32_t ncol, nlay, memspace;
+  const double *t_soil, *x_w, *x_i, *height;          /* [nlay][ncol] */
+  const double *t_air, *q_air, *u, *v, *p_air;        /* [ncol]: the lowest model level */
+  const double *ps, *ts, *snow;                       /* [ncol] */
+  const double *sw_down, *lw_down, *sw_up, *lw_up;    /* [ncol]: the surface level */
+  const int32_t *area_type;                           /* [ncol]: 0 land, 1 land_ice, 2 sea, 3 sea_ice */
+  double dt, rd, g, cp, lv, lf, rho_water, karman, t_freeze, min_wind, kappa_soil, cv_soil;
+  double colour, texture, B, K_H0, psi_0;             /* the soil type, resolved by the caller */
+  double pressure_scale, ps_scale;
+  int32_t reserved, reserved2;                        /* 0 */
+  double *t_soil_out, *x_w_out, *x_i_out;             /* [nlay][ncol]; each may be its own input */
+  double *ts_out, *snow_out;                          /* [ncol]; each may be its own input */
+  double *sh, *lh, *evaporation, *albedo_direct, *albedo_diffuse, *cd_heat, *cd_momentum, *t2m, *q2m, *u10, *v10;   /* [ncol], or NULL */
+  int32_t *flags;                                     /* [ncol], or NULL */
+} rrtmg_second_best;
+int rrtmg_hip_second_best(rrtmg_ctx *ctx, const rrtmg_second_best *a);
+
 /* ---- reference-compatible entry points (host pointers, default context) ---------------- */
 int rrtmg_hip_default_status(void);
 const char *rrtmg_hip_default_error(void);
