@@ -269,6 +269,29 @@ class GridScaleCondensation(C.Structure):
                 + [(n, _vp) for n in GRID_SCALE_CONDENSATION_OUT + GRID_SCALE_CONDENSATION_DIAG])
 
 
+CORK_MAX_GAS = 8
+CORK_TABLE_SIZES = ("ngas", "nband", "ngpt", "nT", "nP", "nX", "nC")
+CORK_LONGWAVE_GASES = tuple("gas%d" % i for i in range(CORK_MAX_GAS))
+CORK_LONGWAVE_CONSTANTS = ("m_h2o", "sigma_sb", "g", "cpd", "diffusivity")
+CORK_LONGWAVE_IN = ("t", "pmid", "pint", "tsfc", "emis", "taucld") + CORK_LONGWAVE_GASES
+CORK_LONGWAVE_OUT = ("up", "dn", "tend")
+CORK_LONGWAVE_DIAG = ("hr", "up_band", "dn_band", "tau_band", "trans_band", "hr_band")
+
+
+class CorkTableDesc(C.Structure):
+    """mirrors `rrtmg_cork_table_desc` (include/rrtmg_hip.h), field for field"""
+    _fields_ = ([("struct_size", C.c_uint32)] + [(n, _i32) for n in CORK_TABLE_SIZES] + [("k_is_f32", _i32), ("reserved", _i32)]
+                + [(n, _vp) for n in ("k", "weights", "planck", "t_grid", "p_grid_log", "x_grid_log", "c_grid_log")]
+                + [("x_clip", _f64 * 2), ("c_clip", _f64 * 2), ("log_cont", _vp)])
+
+
+class CorkLongwave(C.Structure):
+    """mirrors `rrtmg_cork_longwave` (include/rrtmg_hip.h), field for field"""
+    _fields_ = ([("struct_size", C.c_uint32), ("ncol", _i32), ("nlay", _i32), ("memspace", _i32), ("gas_rule", _i32), ("reserved", _i32), ("table", _vp)]
+                + [(n, _vp) for n in CORK_LONGWAVE_IN] + [("gas_scale", _f64 * CORK_MAX_GAS)] + [(n, _f64) for n in CORK_LONGWAVE_CONSTANTS]
+                + [("pressure_scale", _f64)] + [(n, _vp) for n in CORK_LONGWAVE_OUT + CORK_LONGWAVE_DIAG])
+
+
 SURFACE_ICE_FLUXES = ("sw_down", "lw_down", "sw_up", "lw_up", "lh", "sh")
 SURFACE_ICE_CONSTANTS = ("rho_ice", "rho_snow", "c_ice", "c_snow", "k_ice", "k_snow", "lf", "t_melt", "eps", "max_height", "albedo_snow", "albedo_ice", "albedo_melt")
 SURFACE_ICE_IN = ("t", "height", "thick", "snow", "base") + SURFACE_ICE_FLUXES + ("area_type",)
@@ -425,6 +448,10 @@ def load_library():
         lib.rrtmg_hip_frierson_optical_depth.argtypes = [_vp, C.POINTER(FriersonOpticalDepth)]
         lib.rrtmg_hip_gray_longwave.argtypes = [_vp, C.POINTER(GrayLongwave)]
         lib.rrtmg_hip_grid_scale_condensation.argtypes = [_vp, C.POINTER(GridScaleCondensation)]
+    if hasattr(lib, "rrtmg_hip_cork_longwave"):             # (likewise: the table-driven correlated-k longwave)
+        lib.rrtmg_hip_cork_table_create.argtypes = [_vp, C.POINTER(CorkTableDesc), C.POINTER(_vp)]
+        lib.rrtmg_hip_cork_table_destroy.argtypes = [_vp, _vp]
+        lib.rrtmg_hip_cork_longwave.argtypes = [_vp, C.POINTER(CorkLongwave)]
     if hasattr(lib, "rrtmg_hip_surface_ice"):               # (likewise: the snow/ice column of SeaIce and LandIce)
         lib.rrtmg_hip_surface_ice.argtypes = [_vp, C.POINTER(SurfaceIce)]
     if hasattr(lib, "rrtmg_hip_bucket_hydrology"):          # (likewise: the land surface, BucketHydrology)
@@ -959,6 +986,127 @@ class Context:
         outs, diagnostics = self._column_call("grid_scale_condensation", a, dict(t=t, q=q, pmid=pmid, pint=pint), dict(t_out=t_out, q_out=q_out),
                                               diagnostics, memspace, ncol, nlay)
         return outs["t_out"], outs["q_out"], diagnostics
+
+    @property
+    def has_cork_longwave(self):
+        """Whether the library exports the table-driven correlated-k longwave (rrtmg_hip_cork_longwave; probed by the symbol)."""
+        return hasattr(self.lib, "rrtmg_hip_cork_longwave")
+
+    def _need_cork_longwave(self):
+        if not self.has_cork_longwave:
+            raise RRTMGError(4, "this librrtmg_hip.so has no rrtmg_hip_cork_longwave (correlated-k longwave)")
+
+    @_locked
+    def cork_table_create(self, k, weights, planck, t_grid, p_grid_log, x_grid_log=None, x_clip=None, c_grid_log=None, c_clip=None, log_cont=None):
+        """Upload a correlated-k table (rrtmg_hip_cork_table_create) -> the handle, owned by this context.  `k` float32 or float64
+        in the reference's layout (ngas, nband, ngpt, nT, nP[, nX[, nC]]); the other arrays are taken as float64.  The shapes
+        are checked against k's here and the grids by the library, before anything is uploaded."""
+        self._need_cork_longwave()
+        k = np.ascontiguousarray(k)
+        if k.dtype not in (np.float32, np.float64):
+            k = k.astype(np.float64)
+        if k.ndim not in (5, 6, 7):
+            raise ValueError("cork table: k_coefficients has rank %d, not 5 (T, p), 6 (+ H2O) or 7 (+ CO2)" % k.ndim)
+        ngas, nband, ngpt, nT, nP = k.shape[:5]
+        nX, nC = (k.shape[5] if k.ndim >= 6 else 0), (k.shape[6] if k.ndim == 7 else 0)
+        f = lambda x: None if x is None else np.ascontiguousarray(x, dtype=np.float64)
+        weights, planck, t_grid, p_grid_log, x_grid_log, c_grid_log, log_cont = (f(x) for x in (weights, planck, t_grid, p_grid_log, x_grid_log, c_grid_log, log_cont))
+        want = dict(gpoint_weights=(weights, (nband, ngpt)), planck_fraction=(planck, (nband, ngpt, nT)), temperature_grid=(t_grid, (nT,)),
+                    pressure_grid_log=(p_grid_log, (nP,)))
+        if nX:
+            want["h2o_vmr_grid"] = (x_grid_log, (nX,))
+        if nC:
+            want["co2_vmr_grid"] = (c_grid_log, (nC,))
+        if log_cont is not None:
+            want["continuum_kappa"] = (log_cont, (nband, nT, nP, nX))
+        for name, (x, shape) in want.items():
+            if x is None or x.shape != shape:
+                raise ValueError("cork table: %s is %s, k_coefficients %s wants %s" % (name, "missing" if x is None else x.shape, k.shape, shape))
+        d = CorkTableDesc()
+        d.struct_size, d.k_is_f32 = C.sizeof(CorkTableDesc), 1 if k.dtype == np.float32 else 0
+        for n, v in zip(CORK_TABLE_SIZES, (ngas, nband, ngpt, nT, nP, nX, nC)):
+            setattr(d, n, int(v))
+        keep = dict(k=k, weights=weights, planck=planck, t_grid=t_grid, p_grid_log=p_grid_log, x_grid_log=x_grid_log, c_grid_log=c_grid_log, log_cont=log_cont)
+        for n, x in keep.items():
+            setattr(d, n, None if x is None else x.ctypes.data)
+        for n, clip in (("x_clip", x_clip), ("c_clip", c_clip)):
+            if clip is not None:
+                getattr(d, n)[0], getattr(d, n)[1] = float(clip[0]), float(clip[1])
+        handle = _vp()
+        self._ck(self.lib.rrtmg_hip_cork_table_create(self.h, C.byref(d), C.byref(handle)))
+        return handle.value
+
+    @_locked
+    def cork_table_destroy(self, handle):
+        """Free a table of this context (rrtmg_hip_cork_table_destroy); what is left goes with the context."""
+        self._need_cork_longwave()
+        self._ck(self.lib.rrtmg_hip_cork_table_destroy(self.h, handle))
+
+    @_locked
+    def cork_longwave(self, table, nband, t, pmid, pint, tsfc, emis, constants, gas_rule, gases=(), gas_scale=(), taucld=None, up=None, dn=None, tend=None,
+                      diagnostics=True, pressure_scale=1.0, memspace=0, ncol=None, nlay=None):
+        """climt's CorkLongwaveRadiation (correlated_k, additive overlap) by column (rrtmg_hip_cork_longwave) -> (up, dn, tend,
+        diagnostics).  `table`: a handle of cork_table_create, `nband` its bands; `constants`: m_h2o, sigma_sb, g, cpd, diffusivity;
+        `gas_rule` 0 (fully premixed), 1 (premixed background: gases = (specific humidity[, CO2 mole fraction])) or 2 (per gas:
+        one array per gas of the table, `gas_scale` its M_gas / M_dry or 1.0); a gas may be None where the library does not read
+        it.  Host arrays t, pmid [nlay][ncol], pint [nlay+1][ncol], tsfc [ncol], emis [nband][ncol], taucld [nlay][ncol][nband] or
+        None (outputs are allocated unless given); `diagnostics` True: a dict of hr [nlay][ncol], up_band, dn_band
+        [nband][nlay+1][ncol], tau_band, trans_band, hr_band [nband][nlay][ncol] (False or None: none; a dict: those it names are
+        written).  Or device pointers (or DeviceArrays) with memspace=1 -- then the three outputs, `ncol` and `nlay`, and
+        `diagnostics` a dict of device pointers or None; two launches on the main stream."""
+        self._need_cork_longwave()
+        if len(gases) > CORK_MAX_GAS or len(gas_scale) > CORK_MAX_GAS:
+            raise ValueError("cork_longwave: at most %d gases" % CORK_MAX_GAS)
+        a = CorkLongwave()
+        a.struct_size, a.memspace, a.gas_rule, a.table = C.sizeof(CorkLongwave), 1 if memspace else 0, int(gas_rule), table
+        a.pressure_scale = float(pressure_scale)
+        for n in CORK_LONGWAVE_CONSTANTS:
+            setattr(a, n, float(constants[n]))
+        for i in range(CORK_MAX_GAS):
+            a.gas_scale[i] = float(gas_scale[i]) if i < len(gas_scale) else 1.0
+        given = dict(t=t, pmid=pmid, pint=pint, tsfc=tsfc, emis=emis)
+        if taucld is not None:
+            given["taucld"] = taucld
+        given.update({"gas%d" % i: x for i, x in enumerate(gases) if x is not None})
+        outs = dict(up=up, dn=dn, tend=tend)
+        f64 = np.dtype(np.float64)
+        if memspace:
+            if any(x is None for x in outs.values()) or ncol is None or nlay is None:
+                raise ValueError("cork_longwave: device pointers need up, dn, tend, ncol and nlay")
+            a.ncol, a.nlay = int(ncol), int(nlay)
+            diagnostics = diagnostics if isinstance(diagnostics, dict) else {}
+            for name, x in list(given.items()) + list(outs.items()) + list(diagnostics.items()):
+                if name not in CORK_LONGWAVE_IN + CORK_LONGWAVE_OUT + CORK_LONGWAVE_DIAG:
+                    raise ValueError("cork_longwave: no diagnostic %r" % name)
+                setattr(a, name, _device_pointer(x, f64, name))
+            self._ck(self.lib.rrtmg_hip_cork_longwave(self.h, C.byref(a)))
+            return outs["up"], outs["dn"], outs["tend"], diagnostics
+        given = {n: np.ascontiguousarray(x, dtype=np.float64) for n, x in given.items()}
+        shape = given["t"].shape
+        if len(shape) != 2:
+            raise ValueError("cork_longwave: t must be [nlay][ncol]")
+        L, N, B = shape[0], shape[1], int(nband)
+        extents = dict(t=(L, N), pmid=(L, N), pint=(L + 1, N), tsfc=(N,), emis=(B, N), taucld=(L, N, B), up=(L + 1, N), dn=(L + 1, N), tend=(L, N), hr=(L, N),
+                       up_band=(B, L + 1, N), dn_band=(B, L + 1, N), tau_band=(B, L, N), trans_band=(B, L, N), hr_band=(B, L, N))
+        extents.update({n: (L, N) for n in CORK_LONGWAVE_GASES})
+        for n, x in given.items():
+            if x.shape != extents[n]:
+                raise ValueError("cork_longwave: %s is %s, the grid of t %s and %d bands want %s" % (n, x.shape, shape, B, extents[n]))
+        outs = {n: (np.empty(extents[n]) if x is None else x) for n, x in outs.items()}
+        if diagnostics is True:
+            diagnostics = {n: np.empty(extents[n]) for n in CORK_LONGWAVE_DIAG}
+        elif not isinstance(diagnostics, dict):
+            diagnostics = {}
+        for name, x in list(outs.items()) + list(diagnostics.items()):
+            if name not in CORK_LONGWAVE_OUT + CORK_LONGWAVE_DIAG:
+                raise ValueError("cork_longwave: no diagnostic %r" % name)
+            if not (isinstance(x, np.ndarray) and x.dtype == f64 and x.flags.c_contiguous and x.size == int(np.prod(extents[name]))):
+                raise ValueError("cork_longwave: %s is written in place: a C-contiguous float64 array of the right size" % name)
+        a.nlay, a.ncol = L, N
+        for name, x in list(given.items()) + list(outs.items()) + list(diagnostics.items()):
+            setattr(a, name, x.ctypes.data)
+        self._ck(self.lib.rrtmg_hip_cork_longwave(self.h, C.byref(a)))
+        return outs["up"], outs["dn"], outs["tend"], diagnostics
 
     @property
     def has_surface_ice(self):

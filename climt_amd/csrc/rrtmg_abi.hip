@@ -513,6 +513,7 @@ void rrtmg_hip_destroy(rrtmg_ctx *ctx) {
   if (ctx->stream_lw) (void)hipStreamDestroy(ctx->stream_lw);
   rrtmg::free_sw_desc(ctx);
   rrtmg::free_lw_desc(ctx);
+  rrtmg::free_cork_tables(ctx);
   delete ctx;
 }
 

@@ -20,7 +20,8 @@
 
 namespace rrtmg {
 
-enum class ColumnExt { Lay, Lev, Col };   // [nlay][ncol], [nlay+1][ncol], [ncol]
+enum class ColumnExt { Lay, Lev, Col,         // [nlay][ncol], [nlay+1][ncol], [ncol]
+                       BandLay, BandLev, BandCol };   // the same times the call's nband (rrtmg_cork.hip), in the order the entry documents
 struct ColumnRow {
   const char *name;
   size_t pub, dev;           // offsetof the pointer in the public struct and in the kernel's call struct
@@ -62,8 +63,11 @@ inline const void *column_ptr(const void *strct, size_t offset) {
   memcpy(&p, (const char *)strct + offset, sizeof p);
   return p;
 }
-inline size_t column_bytes(const ColumnRow &r, size_t ncol, size_t nlay) {
-  return (r.ext == ColumnExt::Lay ? nlay : r.ext == ColumnExt::Lev ? nlay + 1 : 1) * ncol * (r.i32 ? sizeof(int32_t) : sizeof(double));
+// (nband: what a band-multiplied extent is multiplied by; the entries without such rows leave it at 1)
+inline size_t column_bytes(const ColumnRow &r, size_t ncol, size_t nlay, size_t nband = 1) {
+  const bool banded = r.ext == ColumnExt::BandLay || r.ext == ColumnExt::BandLev || r.ext == ColumnExt::BandCol;
+  const size_t rows = r.ext == ColumnExt::Lay || r.ext == ColumnExt::BandLay ? nlay : r.ext == ColumnExt::Lev || r.ext == ColumnExt::BandLev ? nlay + 1 : 1;
+  return (banded ? nband : 1) * rows * ncol * (r.i32 ? sizeof(int32_t) : sizeof(double));
 }
 constexpr bool column_same_name(const char *a, const char *b) {
   for (; *a && *a == *b; ++a, ++b) {}
@@ -107,11 +111,11 @@ inline bool aliasing_refusal(const ColumnSpan *s, int n, const char *note, char 
   }
   return false;
 }
-inline int column_spans(const ColumnTable &t, const void *a, size_t ncol, size_t nlay, ColumnMask present, ColumnSpan *s) {
+inline int column_spans(const ColumnTable &t, const void *a, size_t ncol, size_t nlay, ColumnMask present, ColumnSpan *s, size_t nband = 1) {
   int n = 0;
   for (int i = 0; i < t.n; ++i) {
     const ColumnRow &r = t.rows[i];
-    if (present >> i & 1) s[n++] = {r.name, column_ptr(a, r.pub), column_bytes(r, ncol, nlay), r.out, r.in_place_of ? column_ptr(a, t.rows[column_index(t, r.in_place_of)].pub) : nullptr};
+    if (present >> i & 1) s[n++] = {r.name, column_ptr(a, r.pub), column_bytes(r, ncol, nlay, nband), r.out, r.in_place_of ? column_ptr(a, t.rows[column_index(t, r.in_place_of)].pub) : nullptr};
   }
   return n;
 }
@@ -135,7 +139,7 @@ inline bool column_required_refusal(const ColumnTable &t, const void *a, char *m
 // absent row has no slot.
 struct ColumnPlan { size_t at[kColumnMaxRows], total; };
 constexpr size_t kColumnNoSlot = ~(size_t)0;
-inline ColumnPlan column_plan(const ColumnTable &t, size_t ncol, size_t nlay, ColumnMask present) {
+inline ColumnPlan column_plan(const ColumnTable &t, size_t ncol, size_t nlay, ColumnMask present, size_t nband = 1) {
   ColumnPlan p;
   p.total = 0;
   for (int i = 0; i < kColumnMaxRows; ++i) p.at[i] = kColumnNoSlot;
@@ -146,7 +150,7 @@ inline ColumnPlan column_plan(const ColumnTable &t, size_t ncol, size_t nlay, Co
       const int partner = r.in_place_of ? column_index(t, r.in_place_of) : -1;
       if (partner >= 0 && p.at[partner] != kColumnNoSlot) { p.at[i] = p.at[partner]; continue; }
       p.at[i] = p.total;
-      p.total += column_bytes(r, ncol, nlay);
+      p.total += column_bytes(r, ncol, nlay, nband);
     }
   return p;
 }
@@ -176,10 +180,10 @@ inline int column_required(rrtmg_ctx *ctx, const ColumnTable &t, const void *a) 
 
 // the aliasing refusal of a call (column_call makes it; an entry whose own checks come behind it makes it first itself)
 template <class A>
-int column_aliasing(rrtmg_ctx *ctx, const ColumnTable &t, const A *a, ColumnMask unread) {
+int column_aliasing(rrtmg_ctx *ctx, const ColumnTable &t, const A *a, ColumnMask unread, size_t nband = 1) {
   ColumnSpan spans[kColumnMaxRows];
   char msg[160];
-  const int n = column_spans(t, a, (size_t)a->ncol, (size_t)a->nlay, column_present(t, a, unread), spans);
+  const int n = column_spans(t, a, (size_t)a->ncol, (size_t)a->nlay, column_present(t, a, unread), spans, nband);
   return aliasing_refusal(spans, n, t.note, msg, sizeof msg) ? ctx->fail(RRTMG_ERR_ARG, "%s: %s", t.entry, msg) : RRTMG_OK;
 }
 
@@ -195,19 +199,20 @@ int column_launch(rrtmg_ctx *ctx, Kernel kernel, size_t ncol, const C &c) {
 // anything is queued, so a failed allocation leaves the stream as it was; under memspace 0 the staging buffer `io` and the inputs
 // that are present going up; the pointers of the call struct `c` bound (memspace 0: the plan's slots, 1: the caller's own; an
 // absent row: nullptr); `launch` -- the entry's launch(es); under memspace 0 the outputs that are present coming back.
-// Device pointers in deferred mode: the call returns once enqueued; otherwise it waits.
+// Device pointers in deferred mode: the call returns once enqueued; otherwise it waits.  `nband`: the factor of the band-multiplied
+// extents, for the entry that has such rows.
 template <class A, class C, class Work, class Launch>
-int column_call(rrtmg_ctx *ctx, const ColumnTable &t, const A *a, C &c, ColumnMask unread, const char *io, Work work, Launch launch, bool aliasing_checked = false) {
+int column_call(rrtmg_ctx *ctx, const ColumnTable &t, const A *a, C &c, ColumnMask unread, const char *io, Work work, Launch launch, bool aliasing_checked = false, size_t nband = 1) {
   const size_t ncol = (size_t)a->ncol, nlay = (size_t)a->nlay;
   const ColumnMask present = column_present(t, a, unread);
-  int rc = aliasing_checked ? RRTMG_OK : column_aliasing(ctx, t, a, unread);
+  int rc = aliasing_checked ? RRTMG_OK : column_aliasing(ctx, t, a, unread, nband);
   if (rc) return rc;
   rc = ctx_prepare_device(ctx);
   if (!rc) rc = work();
   if (rc) return rc;
   hipStream_t s = ctx->stream;
   const bool host = a->memspace == 0;
-  const ColumnPlan plan = column_plan(t, ncol, nlay, host ? present : ColumnMask(0));
+  const ColumnPlan plan = column_plan(t, ncol, nlay, host ? present : ColumnMask(0), nband);
   char *const staged = host ? (char *)ctx->buf(io, plan.total) : nullptr;
   if (host && !staged) return ctx->status;
   void *bound[kColumnMaxRows];
@@ -216,13 +221,13 @@ int column_call(rrtmg_ctx *ctx, const ColumnTable &t, const A *a, C &c, ColumnMa
     void *const mine = present >> i & 1 ? const_cast<void *>(column_ptr(a, r.pub)) : nullptr;
     bound[i] = mine && host ? staged + plan.at[i] : mine;
     memcpy((char *)&c + r.dev, &bound[i], sizeof(void *));
-    if (host && mine && !r.out) RRTMG_HIP_CHECK(ctx, hipMemcpyAsync(bound[i], mine, column_bytes(r, ncol, nlay), hipMemcpyHostToDevice, s));
+    if (host && mine && !r.out) RRTMG_HIP_CHECK(ctx, hipMemcpyAsync(bound[i], mine, column_bytes(r, ncol, nlay, nband), hipMemcpyHostToDevice, s));
   }
   rc = launch();
   if (rc) return rc;
   for (int i = 0; host && i < t.n; ++i)
     if (t.rows[i].out && bound[i])
-      RRTMG_HIP_CHECK(ctx, hipMemcpyAsync(const_cast<void *>(column_ptr(a, t.rows[i].pub)), bound[i], column_bytes(t.rows[i], ncol, nlay), hipMemcpyDeviceToHost, s));
+      RRTMG_HIP_CHECK(ctx, hipMemcpyAsync(const_cast<void *>(column_ptr(a, t.rows[i].pub)), bound[i], column_bytes(t.rows[i], ncol, nlay, nband), hipMemcpyDeviceToHost, s));
   if (ctx->deferred && !host) return RRTMG_OK;
   RRTMG_HIP_CHECK(ctx, hipStreamSynchronize(s));
   return RRTMG_OK;

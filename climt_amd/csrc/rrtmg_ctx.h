@@ -28,6 +28,7 @@ struct DevBuf {
 };
 
 struct JointCall;   // rrtmg_hip_radiation_fluxes in progress (below)
+struct CorkTable;   // a correlated-k table resident on the device (rrtmg_cork.hip)
 
 // What a call is to the permuted call around it (rrtmg_permute.h): not inside one, or the inner call -- the ordinary driver on
 // the internal copy -- of a sorted or of a packed call.  An inner call does not enter the gates again and stops once it is
@@ -160,6 +161,9 @@ struct rrtmg_ctx {
   void *sw_desc = nullptr, *lw_desc = nullptr;   // SwTab / LwTab (host copies, owned)
   // grow-only device work buffers, by name
   std::map<std::string, rrtmg::DevBuf> bufs;
+  // rrtmg_hip_cork_table_create: the tables this context owns (their device memory is a work buffer each, "cork.table.<serial>")
+  std::vector<rrtmg::CorkTable *> cork_tables;
+  int cork_serial = 0;
   // grow-only PINNED host staging for the outputs of host-pointer calls (see copy_out)
   // ([1]: the longwave's of a joint call, whose copies are in flight while the shortwave's are)
   void *pinned[2] = {nullptr, nullptr};
@@ -255,6 +259,7 @@ int ctx_prepare_device(rrtmg_ctx *ctx);   // hipSetDevice + lazy stream / error-
 std::string default_blob_path(const char *which);
 void free_sw_desc(rrtmg_ctx *ctx);
 void free_lw_desc(rrtmg_ctx *ctx);
+void free_cork_tables(rrtmg_ctx *ctx);   // the host side of the tables that are left (rrtmg_cork.hip); their buffers go with `bufs`
 // (sf, c, b: what rrtmg_hip_sw_fluxes_surface takes, each checked and with at least one member set, or nullptr)
 int sw_fluxes_impl(rrtmg_ctx *ctx, const rrtmg_sw_args *a, const rrtmg_sw_surface *sf = nullptr, const rrtmg_sw_components *c = nullptr,
                    const rrtmg_sw_band_fluxes *b = nullptr);

@@ -695,6 +695,57 @@ def gray_longwave_device_call(self, ds):
     return {"air_temperature": tend}, diagnostics
 
 
+def cork_longwave_device_call(self, ds):
+    """CorkLongwaveRadiation on a DeviceState: rrtmg_hip_cork_longwave with device pointers on the main stream and the component's
+    table resident on the state's context.  The two pressures are read as they are resident, in one unit (Pa or any other: the
+    library brings them to Pa); the gases, the emissivity [num_longwave_bands][*] and the cloud depth [mid_levels][*]
+    [num_longwave_bands] as the component's properties state them.  The fluxes, the tendency and the diagnostics go to two
+    alternating sets of work buffers and stay in HBM; the per-band ones are [num_longwave_bands][levels][*], the layout of the
+    RRTMG per-band fluxes.  -> (tendencies, diagnostics) as DeviceQuantity."""
+    P = self.input_properties
+    t, ts = ds.need("air_temperature", P["air_temperature"]), ds.need("surface_temperature", P["surface_temperature"])
+    nlay, ncol = t.shape
+    nband = self.num_longwave_bands
+    p, pi = ds.get("air_pressure"), ds.get("air_pressure_on_interface_levels")
+    for n, x, dims in (("air_pressure", p, ("mid_levels", "*")), ("air_pressure_on_interface_levels", pi, ("interface_levels", "*"))):
+        if x is None:
+            raise KeyError("device state is missing input quantity %r" % n)
+        if tuple(x.dims) != dims:
+            raise ValueError("quantity %r is resident as %s, the correlated-k longwave wants %s" % (n, x.dims, dims))
+    if _to_pa(p.units) != _to_pa(pi.units):
+        raise ValueError("air_pressure is resident in %r and air_pressure_on_interface_levels in %r: the correlated-k longwave wants one unit" % (p.units, pi.units))
+    emis = ds.need("surface_longwave_emissivity", P["surface_longwave_emissivity"])
+    cloud = ds.need("longwave_optical_thickness_due_to_cloud", P["longwave_optical_thickness_due_to_cloud"])
+    gases = [None if n is None else ds.need(n, P[n]) for n in self.gas_inputs()]
+    if (p.shape != (nlay, ncol) or pi.shape != (nlay + 1, ncol) or ts.shape != (ncol,) or emis.shape != (nband, ncol) or cloud.shape != (nlay, ncol, nband)
+            or any(g is not None and g.shape != (nlay, ncol) for g in gases)):
+        raise ValueError("temperature %s, pressures %s, %s, surface temperature %s, emissivity %s, cloud depth %s and gases %s do not belong to one grid of %d bands" % (
+            t.shape, p.shape, pi.shape, ts.shape, emis.shape, cloud.shape, [None if g is None else g.shape for g in gases], nband))
+    if ds.ctx is not self._ctx:      # the table lives on the context that runs the call
+        if getattr(self, "_handle_ctx", None) is not ds.ctx:
+            self._handle_ds, self._handle_ctx = self._ktable.upload(ds.ctx), ds.ctx
+        handle = self._handle_ds
+    else:
+        handle = self.table_handle()
+    self._device_calls = getattr(self, "_device_calls", 0) + 1
+    w = lambda key, shape, dims, units: ds.work(("cork", id(self), key, self._device_calls & 1), shape, dims, units)
+    il, ml = ("interface_levels", "*"), ("mid_levels", "*")
+    up, dn = (w(k, (nlay + 1, ncol), il, "W m^-2") for k in ("up", "dn"))
+    tend, hr = w("tend", (nlay, ncol), ml, "degK s^-1"), w("hr", (nlay, ncol), ml, "degK day^-1")
+    band = ("num_longwave_bands",)
+    ub, db = (w(k, (nband, nlay + 1, ncol), band + il, "W m^-2") for k in ("up_band", "dn_band"))
+    tb, trb = (w(k, (nband, nlay, ncol), band + ml, "dimensionless") for k in ("tau_band", "trans_band"))
+    hb = w("hr_band", (nband, nlay, ncol), band + ml, "degK day^-1")
+    ds.ctx.cork_longwave(handle, nband, t.ptr, p.ptr, pi.ptr, ts.ptr, emis.ptr, self.constants(), self._ktable.gas_rule,
+                         gases=[None if g is None else g.ptr for g in gases], gas_scale=self._ktable.gas_scale, taucld=cloud.ptr, up=up.ptr, dn=dn.ptr, tend=tend.ptr,
+                         diagnostics=dict(hr=hr.ptr, up_band=ub.ptr, dn_band=db.ptr, tau_band=tb.ptr, trans_band=trb.ptr, hr_band=hb.ptr),
+                         pressure_scale=_to_pa(p.units), memspace=1, ncol=ncol, nlay=nlay)
+    return {"air_temperature": tend}, {
+        "upwelling_longwave_flux_in_air": up, "downwelling_longwave_flux_in_air": dn, "upwelling_longwave_flux_in_air_per_band": ub,
+        "downwelling_longwave_flux_in_air_per_band": db, "air_temperature_tendency_from_longwave": hr, "longwave_optical_depth_per_band": tb,
+        "longwave_transmittance_per_band": trb, "air_temperature_tendency_from_longwave_per_band": hb}
+
+
 def grid_scale_condensation_device_call(self, ds, timestep=None):
     """GridScaleCondensation on a DeviceState: rrtmg_hip_grid_scale_condensation with device pointers on the main stream.  The
     pressures are read as they are resident -- in the units of whichever component asked for them first; the saturation formula

@@ -10,7 +10,7 @@ the first step, the column starts on a lapse rate steeper than the dry adiabat (
 isothermal 290 K.
 
     python examples/radiative_convective.py [--steps 60] [--device-resident] [--boundary-layer | --simple-physics] [--moist-convection]
-                                            [--gray-longwave] [--grid-scale-condensation] [--sea-ice]
+                                            [--gray-longwave | --cork-longwave TABLE] [--grid-scale-condensation] [--sea-ice]
                                             [--land-surface bucket|second_best]
 
 --boundary-layer closes that gap: SimpleBoundaryLayer (bulk surface fluxes, implicit diffusion of T, q, u, v) steps after the time
@@ -32,6 +32,11 @@ near the surface).  Without the flag the run is what it was.
 of Frierson06LongwaveOpticalDepth formed inside the sweep (the fused call; the depth joins the diagnostics).  The shortwave stays
 RRTMG's.  Without the flag the run is what it was.
 
+--cork-longwave TABLE replaces the RRTMG longwave with the table-driven correlated-k one: CorkLongwaveRadiation(optics="correlated_k",
+table=TABLE), TABLE a k-table file (tests/golden/cork_table_earth4.npz say) or what else the component takes.  The state then
+carries the emissivity and the cloud depth on the table's own bands; the per-band diagnostics join the others.  The shortwave
+stays RRTMG's.  Exclusive with --gray-longwave.  Without the flag the run is what it was.
+
 --grid-scale-condensation adds GridScaleCondensation, the moisture sink of that set-up, after the time stepper (and after the
 boundary layer where there is one) and before the adjustment; its precipitation_amount goes into the state.  The column then
 starts at 70 % of saturation with one supersaturated layer.  Exclusive with --simple-physics, which condenses itself.  Without
@@ -49,12 +54,12 @@ from datetime import timedelta
 import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from climt_amd import (AdamsBashforth, DryConvectiveAdjustment, EmanuelConvection, Frierson06LongwaveOpticalDepth, GrayLongwaveRadiation,  # noqa: E402
+from climt_amd import (AdamsBashforth, CorkLongwaveRadiation, DryConvectiveAdjustment, EmanuelConvection, Frierson06LongwaveOpticalDepth, GrayLongwaveRadiation,  # noqa: E402
                        GridScaleCondensation, RRTMGLongwave, SeaIce, BucketHydrology, SecondBEST, RRTMGShortwave, SimpleBoundaryLayer, SimplePhysics, SlabSurface, get_default_state, get_grid)
 
 
 def run(steps=60, device_resident=False, report=None, boundary_layer=False, moist_convection=False, simple_physics=False, gray_longwave=False,
-        grid_scale_condensation=False, sea_ice=False, land_surface=None):
+        grid_scale_condensation=False, sea_ice=False, land_surface=None, cork_longwave=None):
     """-> (diagnostics of step 0, state after `steps` steps), both as host DataArrays.  `boundary_layer`: with SimpleBoundaryLayer
     between the time stepper and the adjustment; its diagnostics of step 0 are then among the first.  `moist_convection`: with
     EmanuelConvection in the time stepper's list.  `simple_physics`: with SimplePhysics in the place of the boundary layer.
@@ -64,7 +69,10 @@ def run(steps=60, device_resident=False, report=None, boundary_layer=False, mois
     which things run is the order of the loop below; `steppers` only tells get_default_state and DeviceState.from_host which
     inputs to serve.  On the first step no radiation has run yet, so SeaIce reads the default state's radiative fluxes: zeros.
     `land_surface`: "bucket" or "second_best" -- the surface is land, and BucketHydrology or SecondBEST steps it in the place
-    where SeaIce steps the ice (exclusive with `sea_ice`); SlabSurface reads the surface fluxes it writes."""
+    where SeaIce steps the ice (exclusive with `sea_ice`); SlabSurface reads the surface fluxes it writes.  `cork_longwave`: a
+    k-table -- the correlated-k longwave on it in the place of RRTMG's (exclusive with `gray_longwave`)."""
+    if cork_longwave is not None and gray_longwave:
+        raise ValueError("cork_longwave and gray_longwave are exclusive: one longwave scheme")
     if land_surface not in (None, "bucket", "second_best"):
         raise ValueError("land_surface must be None, 'bucket' or 'second_best'")
     if land_surface and sea_ice:
@@ -74,7 +82,10 @@ def run(steps=60, device_resident=False, report=None, boundary_layer=False, mois
     if grid_scale_condensation and simple_physics:
         raise ValueError("grid_scale_condensation and simple_physics are exclusive: both remove grid-scale supersaturation")
     rad_sw = RRTMGShortwave()
-    rad_lw = GrayLongwaveRadiation(optical_depth=Frierson06LongwaveOpticalDepth()) if gray_longwave else RRTMGLongwave(allow_synthetic_tables=True)
+    if cork_longwave is not None:
+        rad_lw = CorkLongwaveRadiation(optics="correlated_k", table=cork_longwave)
+    else:
+        rad_lw = GrayLongwaveRadiation(optical_depth=Frierson06LongwaveOpticalDepth()) if gray_longwave else RRTMGLongwave(allow_synthetic_tables=True)
     slab = SlabSurface()
     dry_convection = DryConvectiveAdjustment()
     components = [rad_sw, rad_lw, slab]
@@ -209,7 +220,9 @@ def main():
     surface.add_argument("--boundary-layer", action="store_true")
     surface.add_argument("--simple-physics", action="store_true")
     ap.add_argument("--moist-convection", action="store_true")
-    ap.add_argument("--gray-longwave", action="store_true")
+    longwave = ap.add_mutually_exclusive_group()
+    longwave.add_argument("--gray-longwave", action="store_true")
+    longwave.add_argument("--cork-longwave", metavar="TABLE", default=None)
     ap.add_argument("--grid-scale-condensation", action="store_true")
     ap.add_argument("--sea-ice", action="store_true")
     ap.add_argument("--land-surface", choices=("bucket", "second_best"))
@@ -228,7 +241,7 @@ def main():
             state["air_temperature_tendency_from_longwave"].values.ravel()[-1], rain))
     if a.grid_scale_condensation and a.simple_physics:
         ap.error("--grid-scale-condensation and --simple-physics are exclusive")
-    run(a.steps, a.device_resident, report, a.boundary_layer, a.moist_convection, a.simple_physics, a.gray_longwave, a.grid_scale_condensation, a.sea_ice, a.land_surface)
+    run(a.steps, a.device_resident, report, a.boundary_layer, a.moist_convection, a.simple_physics, a.gray_longwave, a.grid_scale_condensation, a.sea_ice, a.land_surface, a.cork_longwave)
 
 
 if __name__ == "__main__":

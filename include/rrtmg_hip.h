@@ -906,6 +906,77 @@ typedef struct {
 } rrtmg_grid_scale_condensation;
 int rrtmg_hip_grid_scale_condensation(rrtmg_ctx *ctx, const rrtmg_grid_scale_condensation *a);
 
+/* ---- cork: the table-driven correlated-k longwave ---- */
+/* A correlated-k table of climt's cork scheme (climt/_components/cork/optics/correlated_k.py) resident on the device.  The arrays
+ * of the description are host arrays in the reference's own layout; they are read during the call only.
+ *   k            [ngas][nband][ngpt][nT][nP] and, where nX > 0, [nX] (the H2O axis) and, where nC > 0, [nC] (the CO2 axis);
+ *                float where k_is_f32 is 1, else double.  An element counts as its value promoted to double.
+ *   weights      [nband][ngpt];  planck [nband][ngpt][nT]: the Planck fraction;  t_grid [nT];  p_grid_log [nP]
+ *   x_grid_log   [nX]: log(max(h2o_vmr_grid, 1e-30)), x_clip the first and the last node of h2o_vmr_grid itself; c_grid_log [nC]
+ *                and c_clip likewise for the CO2 axis
+ *   log_cont     [nband][nT][nP][nX]: log(max(continuum_kappa, 1e-40)), or NULL (no band-grey continuum); needs nX > 0
+ * RRTMG_ERR_ARG -- before anything is uploaded -- for a NULL struct or `out`, a struct_size other than sizeof
+ * (rrtmg_cork_table_desc), ngas outside 1..8, nband outside 1..32, ngpt outside 1..16, nT or nP below 2, nX or nC that is neither
+ * 0 nor at least 2, nC > 0 without nX > 0, log_cont without nX > 0, a NULL array that the sizes ask for, a grid that does not
+ * strictly increase or a clip interval that does not.  The handle belongs to the context: rrtmg_hip_cork_table_destroy frees it,
+ * and rrtmg_hip_destroy frees what is left.  Any number of tables may be resident at once.
+ * Probe for it by symbol; RRTMG_HIP_ABI_VERSION is unchanged. */
+typedef struct rrtmg_cork_table rrtmg_cork_table;
+typedef struct {
+  uint32_t struct_size; int32_t ngas, nband, ngpt, nT, nP, nX, nC;
+  int32_t k_is_f32, reserved;                         /* reserved: 0 */
+  const void *k;
+  const double *weights, *planck, *t_grid, *p_grid_log;
+  const double *x_grid_log, *c_grid_log;              /* NULL where nX / nC is 0 */
+  double x_clip[2], c_clip[2];
+  const double *log_cont;                             /* or NULL */
+} rrtmg_cork_table_desc;
+int rrtmg_hip_cork_table_create(rrtmg_ctx *ctx, const rrtmg_cork_table_desc *d, rrtmg_cork_table **out);
+int rrtmg_hip_cork_table_destroy(rrtmg_ctx *ctx, rrtmg_cork_table *table);
+
+/* climt's CorkLongwaveRadiation with optics "correlated_k" and additive overlap (_components/cork/lw/component.py), by column, in
+ * the reference's order of operations (rrtmg_cork.h states every rule).  Level 0 is the surface.  By layer: the brackets of t,
+ * log(max(pmid, 1)) and -- where the table has the axes -- of the clipped H2O and CO2 mole fractions; the layer's gas amounts by
+ * gas_rule; by band and g-point the interpolated k summed over the gases from 0.0, the continuum times the amount of gas 0, the
+ * cloud depth; the Planck fraction interpolated in t times sigma_sb t^4; the upward sweep from emis times the surface source and
+ * the downward one from +0.0 with trans = exp(-diffusivity tau); the g-points summed by weight from 0.0 into the per-band fluxes
+ * and the bands summed from 0.0 in ascending order into up and dn;  tend = ((g / cpd) (net[k+1] - net[k])) / (pint[k+1] - pint[k])
+ * in K/s, hr = tend 86400.0;  tau_band the weighted sum of the optical depths of a band, trans_band = exp(-diffusivity tau_band),
+ * hr_band the heating of the band's own net flux in K/day.  One thread per column and band forms all of this in registers: no
+ * array with a g-point axis exists.  pmid and pint are read as p * pressure_scale (Pa per unit).
+ * gas_rule 0 (fully premixed): the amount of gas 0 is the layer's air mass |dp| / g, no gas array is read.
+ * gas_rule 1 (premixed background): the same amount; gas0 is the specific humidity, which gives the H2O mole fraction
+ *   q / max(q + (1 - q) m_h2o, 1e-30) of the H2O axis; gas1 is the CO2 mole fraction of the CO2 axis (read where nC > 0).
+ * gas_rule 2 (per gas): gas<i> is read for every gas of the table, amount = ((gas<i> gas_scale[i]) |dp|) / g (gas_scale 1.0 is exact:
+ *   water vapour).  A table with an H2O axis is refused under rules 0 and 2, one without under rule 1 where gas0 is NULL.
+ * taucld [nlay][ncol][nband] may be NULL (no cloud).  hr, up_band, dn_band, tau_band, trans_band and hr_band may each be NULL.
+ * No output may overlap an input or another output.
+ * RRTMG_ERR_ARG: a NULL struct, a struct_size other than sizeof(rrtmg_cork_longwave), ncol <= 0, nlay < 1, a memspace other than
+ * 0 and 1, reserved != 0, a gas_rule outside 0..2, a NULL table or one of another context, a NULL t, pmid, pint, tsfc, emis, up, dn or
+ * tend, a NULL gas array that the table and the rule need, any overlap of an output -- before anything is read or enqueued.
+ * Needs neither rrtmg_hip_sw_init nor rrtmg_hip_lw_init.  Host pointers: the inputs that are read go up, the outputs asked for
+ * come back.  Device pointers: two launches on the context's main stream; in deferred mode the call returns once enqueued.
+ * Probe for it by symbol; RRTMG_HIP_ABI_VERSION is unchanged. */
+typedef struct {
+  uint32_t struct_size; int32_t ncol, nlay, memspace;
+  int32_t gas_rule, reserved;                         /* reserved: 0 */
+  const rrtmg_cork_table *table;
+  const double *t, *pmid;                             /* [nlay][ncol] */
+  const double *pint;                                 /* [nlay+1][ncol] */
+  const double *tsfc;                                 /* [ncol] */
+  const double *emis;                                 /* [nband][ncol] */
+  const double *taucld;                               /* [nlay][ncol][nband], or NULL */
+  const double *gas0, *gas1, *gas2, *gas3, *gas4, *gas5, *gas6, *gas7;   /* [nlay][ncol]; NULL where unread */
+  double gas_scale[8];
+  double m_h2o, sigma_sb, g, cpd, diffusivity, pressure_scale;
+  double *up, *dn;                                    /* [nlay+1][ncol] */
+  double *tend;                                       /* [nlay][ncol] */
+  double *hr;                                         /* [nlay][ncol], or NULL */
+  double *up_band, *dn_band;                          /* [nband][nlay+1][ncol], or NULL */
+  double *tau_band, *trans_band, *hr_band;            /* [nband][nlay][ncol], or NULL */
+} rrtmg_cork_longwave;
+int rrtmg_hip_cork_longwave(rrtmg_ctx *ctx, const rrtmg_cork_longwave *a);
+
 /* ---- sea ice and land ice: one implicit snow/ice column ---- */
 /* climt's SeaIce (kind 0, _components/sea_ice/component.py) and LandIce (kind 1, _components/land_ice/component.py), by column,
  * with their shared Crank-Nicolson solver and Thomas sweep, in the reference's order of operations.  nlay counts the ice
