@@ -336,32 +336,62 @@ class SecondBest(C.Structure):
                 + [(n, _vp) for n in SECOND_BEST_OUT + SECOND_BEST_DIAG])
 
 
-# What Context._column_call knows of each column component's arrays besides the three tuples above: `columns` are [ncol], `levels`
-# [nlay+1][ncol] and the others [nlay][ncol]; `int32` are int32 and the others float64 (tests/test_call_arrays.py holds all three to
-# the library's own tables); `optional` profiles are named in brackets by the shape message; `in_place`: (output, input) pairs for
-# which an output that IS the caller's input array means that array, not its contiguous copy.
+# The six extents of ColumnExt (csrc/rrtmg_column_call.h), written as the check programs print them -> the shape of the device
+# array at (nlay, ncol, nband).
+LAY, LEV, COL, BAND_LAY, BAND_LEV, BAND_COL = "[nlay][ncol]", "[nlay+1][ncol]", "[ncol]", "[nband][nlay][ncol]", "[nband][nlay+1][ncol]", "[nband][ncol]"
+COLUMN_EXTENTS = {LAY: lambda L, N, B: (L, N), LEV: lambda L, N, B: (L + 1, N), COL: lambda L, N, B: (N,),
+                  BAND_LAY: lambda L, N, B: (B, L, N), BAND_LEV: lambda L, N, B: (B, L + 1, N), BAND_COL: lambda L, N, B: (B, N)}
+_F64, _I32 = np.dtype(np.float64), np.dtype(np.int32)
+
+
+def _column_arrays(struct, IN, DIAG, int32=(), optional=(), in_place=(), grid=None, host_axes=None, **names_of):
+    """One entry of COLUMN_ARRAYS.  `names_of`: levels=, columns=, band_layers=, band_levels=, band_columns= name the arrays of
+    each extent; every other pointer member of `struct` is [nlay][ncol]."""
+    members = tuple(n for n, t in struct._fields_ if t is _vp and n != "table")
+    extent = dict.fromkeys(members, LAY)
+    for key, names in names_of.items():
+        assert set(names) <= set(members), (struct, key)
+        extent.update(dict.fromkeys(names, dict(levels=LEV, columns=COL, band_layers=BAND_LAY, band_levels=BAND_LEV, band_columns=BAND_COL)[key]))
+    return dict(struct=struct, IN=IN, DIAG=DIAG, extent=extent, dtype={n: _I32 if n in int32 else _F64 for n in members}, optional=optional, in_place=in_place,
+                grid=grid, host_axes=host_axes or {})
+
+
+# The single description of a column component's arrays on the Python side, by entry (rrtmg_hip_<entry>): `struct`, whose pointer
+# members are the arrays, in the order of the library's table; `IN` and `DIAG` (the outputs are what lies between); `extent` and
+# `dtype` by name; `optional`: the inputs that may be absent; `in_place`: (output, input) pairs for which an output that IS the
+# caller's input array means that array, not its contiguous copy; `grid`: the input whose shape is the call's -- [nlay][ncol], or
+# [ncol] where every array is a column and nlay is 1 (default: t, or pint less one level); `host_axes`: for an array the caller
+# holds in another axis order than the device, the device axis of each host axis.  Context._column_call reads nothing else;
+# tests/helpers.py (column_rows_agree) holds every key to the rows the library's own tables print.
 COLUMN_ARRAYS = {
-    "dry_adjustment": dict(IN=DRY_ADJUST_IN, DIAG=DRY_ADJUST_DIAG, columns=("mixed_top",), levels=("pint",), int32=("mixed_top",)),
-    "boundary_layer": dict(IN=BOUNDARY_LAYER_IN, DIAG=BOUNDARY_LAYER_DIAG, levels=("pint",),
-                           columns=("ps", "ts", "qs", "sh_in", "lh_in", "stress_north", "stress_east", "height", "sh_out", "lh_out")),
-    "emanuel_convection": dict(IN=EMANUEL_IN, DIAG=EMANUEL_DIAG, levels=("pint",), int32=("iflag",), optional=("qs",), in_place=(("cbmf_out", "cbmf"),),
-                               columns=("cbmf", "cbmf_out", "precip", "wd", "tprime", "qprime", "cape", "iflag")),
-    "simple_physics": dict(IN=SIMPLE_PHYSICS_IN, DIAG=SIMPLE_PHYSICS_DIAG, levels=("pint",), columns=("ps", "ts", "qsurf", "lat", "precl", "sh_out", "lh_out")),
+    "dry_adjustment": _column_arrays(DryAdjust, DRY_ADJUST_IN, DRY_ADJUST_DIAG, int32=("mixed_top",), in_place=(("t_out", "t"), ("q_out", "q")), levels=("pint",), columns=("mixed_top",)),
+    "boundary_layer": _column_arrays(BoundaryLayer, BOUNDARY_LAYER_IN, BOUNDARY_LAYER_DIAG, optional=("sh_in", "lh_in"), in_place=tuple((n + "_out", n) for n in "tquv"), levels=("pint",),
+                                     columns=("ps", "ts", "qs", "sh_in", "lh_in", "stress_north", "stress_east", "height", "sh_out", "lh_out")),
+    "emanuel_convection": _column_arrays(Emanuel, EMANUEL_IN, EMANUEL_DIAG, int32=("iflag",), optional=("qs",), in_place=(("cbmf_out", "cbmf"),), levels=("pint",),
+                                         columns=("cbmf", "cbmf_out", "precip", "wd", "tprime", "qprime", "cape", "iflag")),
+    "simple_physics": _column_arrays(SimplePhysics, SIMPLE_PHYSICS_IN, SIMPLE_PHYSICS_DIAG, optional=("ts", "qsurf", "lat"), in_place=tuple((n + "_out", n) for n in "tquv"),
+                                     levels=("pint",), columns=("ps", "ts", "qsurf", "lat", "precl", "sh_out", "lh_out")),
     # (the gray path: outputs on the interface levels too; the depth has no profile input, its grid is pint's)
-    "frierson_optical_depth": dict(IN=FRIERSON_IN, DIAG=FRIERSON_DIAG, levels=("pint", "tau"), columns=("ps", "lat")),
-    "gray_longwave": dict(IN=GRAY_LONGWAVE_IN, DIAG=GRAY_LONGWAVE_DIAG, levels=("pint", "tau", "up", "dn", "tau_out"), columns=("tsfc", "ps", "lat")),
-    "grid_scale_condensation": dict(IN=GRID_SCALE_CONDENSATION_IN, DIAG=GRID_SCALE_CONDENSATION_DIAG, levels=("pint",), columns=("precip",)),
-    # (the snow/ice column: nlay counts the ice interface levels, so there are no `levels`; an int32 input)
-    "surface_ice": dict(IN=SURFACE_ICE_IN, DIAG=SURFACE_ICE_DIAG, int32=("area_type", "flags"), optional=(),
-                        in_place=(("t_out", "t"), ("height_out", "height"), ("thick_out", "thick"), ("snow_out", "snow"), ("base_flux_out", "base")),
-                        columns=("thick", "snow", "base") + SURFACE_ICE_FLUXES + ("area_type", "thick_out", "snow_out", "tsfc_out", "base_flux_out", "cond_flux", "albedo", "flags")),
-    # (the land surface: `grid` names the input whose shape is the call's -- [nlay][ncol], or [ncol] where every array is a column and nlay is 1)
-    "bucket_hydrology": dict(IN=BUCKET_HYDROLOGY_IN, DIAG=BUCKET_HYDROLOGY_DIAG, grid="ts", optional=(),
-                             in_place=tuple((n + "_out", n) for n in ("ts", "soil_moisture") + BUCKET_HYDROLOGY_DEEP),
-                             columns=BUCKET_HYDROLOGY_IN + BUCKET_HYDROLOGY_OUT + BUCKET_HYDROLOGY_DIAG),
-    "second_best": dict(IN=SECOND_BEST_IN, DIAG=SECOND_BEST_DIAG, grid="t_soil", int32=("area_type", "flags"), optional=(),
-                        in_place=tuple((n + "_out", n) for n in ("t_soil", "x_w", "x_i", "ts", "snow")),
-                        columns=SECOND_BEST_IN[4:] + ("ts_out", "snow_out") + SECOND_BEST_DIAG),
+    "frierson_optical_depth": _column_arrays(FriersonOpticalDepth, FRIERSON_IN, FRIERSON_DIAG, levels=("pint", "tau"), columns=("ps", "lat")),
+    "gray_longwave": _column_arrays(GrayLongwave, GRAY_LONGWAVE_IN, GRAY_LONGWAVE_DIAG, optional=("tau", "ps", "lat"), levels=("pint", "tau", "up", "dn", "tau_out"),
+                                    columns=("tsfc", "ps", "lat")),
+    "grid_scale_condensation": _column_arrays(GridScaleCondensation, GRID_SCALE_CONDENSATION_IN, GRID_SCALE_CONDENSATION_DIAG, in_place=(("t_out", "t"), ("q_out", "q")),
+                                              levels=("pint",), columns=("precip",)),
+    # (the correlated-k longwave: extents times the call's nband; the caller holds taucld as [nlay][ncol][nband])
+    "cork_longwave": _column_arrays(CorkLongwave, CORK_LONGWAVE_IN, CORK_LONGWAVE_DIAG, optional=("taucld",) + CORK_LONGWAVE_GASES, host_axes=dict(taucld=(1, 2, 0)),
+                                    levels=("pint", "up", "dn"), columns=("tsfc",), band_columns=("emis",), band_levels=("up_band", "dn_band"),
+                                    band_layers=("taucld", "tau_band", "trans_band", "hr_band")),
+    # (the snow/ice column: nlay counts the ice interface levels, so there are no levels; an int32 input)
+    "surface_ice": _column_arrays(SurfaceIce, SURFACE_ICE_IN, SURFACE_ICE_DIAG, int32=("area_type", "flags"),
+                                  in_place=(("t_out", "t"), ("height_out", "height"), ("thick_out", "thick"), ("snow_out", "snow"), ("base_flux_out", "base")),
+                                  columns=("thick", "snow", "base") + SURFACE_ICE_FLUXES + ("area_type", "thick_out", "snow_out", "tsfc_out", "base_flux_out", "cond_flux", "albedo", "flags")),
+    # (the land surface)
+    "bucket_hydrology": _column_arrays(BucketHydrology, BUCKET_HYDROLOGY_IN, BUCKET_HYDROLOGY_DIAG, grid="ts", optional=BUCKET_HYDROLOGY_DEEP,
+                                       in_place=tuple((n + "_out", n) for n in ("ts", "soil_moisture") + BUCKET_HYDROLOGY_DEEP),
+                                       columns=BUCKET_HYDROLOGY_IN + BUCKET_HYDROLOGY_OUT + BUCKET_HYDROLOGY_DIAG),
+    "second_best": _column_arrays(SecondBest, SECOND_BEST_IN, SECOND_BEST_DIAG, grid="t_soil", int32=("area_type", "flags"),
+                                  in_place=tuple((n + "_out", n) for n in ("t_soil", "x_w", "x_i", "ts", "snow")),
+                                  columns=SECOND_BEST_IN[4:] + ("ts_out", "snow_out") + SECOND_BEST_DIAG),
 }
 
 
@@ -436,28 +466,12 @@ def load_library():
         lib.rrtmg_hip_scale_columns.argtypes = [_vp, C.c_int, _vp, _vp, C.c_int, C.POINTER(ScaleEntry)]
     if hasattr(lib, "rrtmg_hip_lw_adjust_surface"):         # (likewise: the longwave between radiation calls)
         lib.rrtmg_hip_lw_adjust_surface.argtypes = [_vp, C.POINTER(LwAdjust)]
-    if hasattr(lib, "rrtmg_hip_dry_adjustment"):            # (likewise: the dry convective adjustment)
-        lib.rrtmg_hip_dry_adjustment.argtypes = [_vp, C.POINTER(DryAdjust)]
-    if hasattr(lib, "rrtmg_hip_boundary_layer"):            # (likewise: the simple boundary layer)
-        lib.rrtmg_hip_boundary_layer.argtypes = [_vp, C.POINTER(BoundaryLayer)]
-    if hasattr(lib, "rrtmg_hip_emanuel_convection"):        # (likewise: the Emanuel convection scheme)
-        lib.rrtmg_hip_emanuel_convection.argtypes = [_vp, C.POINTER(Emanuel)]
-    if hasattr(lib, "rrtmg_hip_simple_physics"):            # (likewise: the simple physics package)
-        lib.rrtmg_hip_simple_physics.argtypes = [_vp, C.POINTER(SimplePhysics)]
-    if hasattr(lib, "rrtmg_hip_gray_longwave"):             # (likewise: the gray radiation path and its moisture sink)
-        lib.rrtmg_hip_frierson_optical_depth.argtypes = [_vp, C.POINTER(FriersonOpticalDepth)]
-        lib.rrtmg_hip_gray_longwave.argtypes = [_vp, C.POINTER(GrayLongwave)]
-        lib.rrtmg_hip_grid_scale_condensation.argtypes = [_vp, C.POINTER(GridScaleCondensation)]
-    if hasattr(lib, "rrtmg_hip_cork_longwave"):             # (likewise: the table-driven correlated-k longwave)
+    for entry, arrays in COLUMN_ARRAYS.items():             # (likewise, entry by entry: the column components)
+        if hasattr(lib, "rrtmg_hip_" + entry):
+            getattr(lib, "rrtmg_hip_" + entry).argtypes = [_vp, C.POINTER(arrays["struct"])]
+    if hasattr(lib, "rrtmg_hip_cork_table_create"):         # (likewise: the tables of the correlated-k longwave)
         lib.rrtmg_hip_cork_table_create.argtypes = [_vp, C.POINTER(CorkTableDesc), C.POINTER(_vp)]
         lib.rrtmg_hip_cork_table_destroy.argtypes = [_vp, _vp]
-        lib.rrtmg_hip_cork_longwave.argtypes = [_vp, C.POINTER(CorkLongwave)]
-    if hasattr(lib, "rrtmg_hip_surface_ice"):               # (likewise: the snow/ice column of SeaIce and LandIce)
-        lib.rrtmg_hip_surface_ice.argtypes = [_vp, C.POINTER(SurfaceIce)]
-    if hasattr(lib, "rrtmg_hip_bucket_hydrology"):          # (likewise: the land surface, BucketHydrology)
-        lib.rrtmg_hip_bucket_hydrology.argtypes = [_vp, C.POINTER(BucketHydrology)]
-    if hasattr(lib, "rrtmg_hip_second_best"):               # (likewise: the land surface, SecondBEST)
-        lib.rrtmg_hip_second_best.argtypes = [_vp, C.POINTER(SecondBest)]
     lib.rrtmg_hip_copy_blocks.argtypes =[_vp, C.c_int, _vp, C.c_long, C.c_long, _vp, _vp, _vp]
     lib.rrtmg_hip_mcica_mask.argtypes = [_vp] + [C.c_int] * 6 + [_vp] * 3
     _lib = lib
@@ -734,14 +748,14 @@ class Context:
                 setattr(a, name, None if v is None else _device_pointer(v, f64, name))
         self._ck(self.lib.rrtmg_hip_lw_adjust_surface(self.h, C.byref(a)))
 
-    def _column_call(self, entry, a, given, outs, diagnostics, memspace, ncol, nlay):
+    def _column_call(self, entry, a, given, outs, diagnostics, memspace, ncol, nlay, nband=None):
         """The array side of a column component's call (rrtmg_hip_<entry>), behind the scalars its method has put into the struct
         `a` -> (outs, diagnostics).  `given`: the inputs the call reads, by name; `outs`: the outputs every call writes, the
-        caller's array or None; `diagnostics`: True, a dict, or None.  Names, shapes and types: COLUMN_ARRAYS[entry]."""
-        IN, DIAG = COLUMN_ARRAYS[entry]["IN"], COLUMN_ARRAYS[entry]["DIAG"]
-        columns, levels, int32, optional, in_place = (COLUMN_ARRAYS[entry].get(k, ()) for k in ("columns", "levels", "int32", "optional", "in_place"))
+        caller's array or None; `diagnostics`: True, a dict, or None; `nband`: the factor of the band-multiplied extents, from
+        the entry that has such arrays.  Names, extents and types: COLUMN_ARRAYS[entry]."""
+        arrays = COLUMN_ARRAYS[entry]
+        IN, DIAG, dtype = arrays["IN"], arrays["DIAG"], arrays["dtype"]
         fn, names = getattr(self.lib, "rrtmg_hip_" + entry), IN + tuple(outs) + DIAG
-        dtype = lambda n: np.dtype(np.int32 if n in int32 else np.float64)
         if memspace:
             if any(x is None for x in outs.values()) or ncol is None or nlay is None:
                 raise ValueError("%s: device pointers need %s, ncol and nlay" % (entry, ", ".join(outs)))
@@ -750,24 +764,32 @@ class Context:
             for name, x in list(given.items()) + list(outs.items()) + list(diagnostics.items()):
                 if name not in names:
                     raise ValueError("%s: no diagnostic %r" % (entry, name))
-                setattr(a, name, _device_pointer(x, dtype(name), name))
+                setattr(a, name, _device_pointer(x, dtype[name], name))
             self._ck(fn(self.h, C.byref(a)))
             return outs, diagnostics
-        mine, given = given, {n: np.ascontiguousarray(x, dtype=dtype(n)) for n, x in given.items()}
-        grid = COLUMN_ARRAYS[entry].get("grid")
+        mine, given = given, {n: np.ascontiguousarray(x, dtype=dtype[n]) for n, x in given.items()}
+        grid = arrays["grid"]
         if grid is not None:
             shape = given[grid].shape if given[grid].ndim != 1 else (1,) + given[grid].shape
         else:
             shape = given["t"].shape if "t" in given else (given["pint"].shape[0] - 1,) + given["pint"].shape[1:]      # (no profile: the grid is pint's)
-        profiles, cols = [n for n in IN if n not in columns + levels], [n for n in IN if n in columns]
-        if len(shape) != 2 or any(given[n].shape != shape for n in profiles if n in given) or any(given[n].shape != (shape[0] + 1, shape[1]) for n in levels if n in given):
-            raise ValueError("%s: %s%s must be [nlay][ncol] arrays of one shape and pint [nlay+1][ncol]"
-                             % (entry, ", ".join(n for n in profiles if n not in optional), "".join(" (and %s)" % n for n in profiles if n in optional)))
-        if any(given[n].shape != (shape[1],) for n in cols if n in given):
+        of, axes = arrays["extent"], arrays["host_axes"]
+
+        def extent(n):      # the caller's shape of the array `n`: the one place a name becomes a shape
+            device = COLUMN_EXTENTS[of[n]](shape[0], shape[1], nband)
+            return tuple(device[i] for i in axes[n]) if n in axes else device
+        wrong = [n for n in given if given[n].shape != extent(n)] if len(shape) == 2 else list(given)
+        if wrong and nband is not None:      # the entry with band arrays names the array and what it wants ...
+            if len(shape) != 2:
+                raise ValueError("%s: t must be [nlay][ncol]" % entry)
+            raise ValueError("%s: %s is %s, the grid of t %s and %d bands want %s" % (entry, wrong[0], given[wrong[0]].shape, shape, nband, extent(wrong[0])))
+        if wrong:                            # ... the others the group: the profiles and pint, then the columns
+            profiles, cols = [n for n in IN if of[n] == LAY], [n for n in IN if of[n] == COL]
+            if len(shape) != 2 or any(of[n] != COL for n in wrong):
+                raise ValueError("%s: %s%s must be [nlay][ncol] arrays of one shape and pint [nlay+1][ncol]"
+                                 % (entry, ", ".join(n for n in profiles if n not in arrays["optional"]), "".join(" (and %s)" % n for n in profiles if n in arrays["optional"])))
             raise ValueError("%s: %s must be %s" % (entry, " and ".join(filter(None, (", ".join(cols[:-1]), cols[-1]))), "[ncol] arrays" if len(cols) > 1 else "an [ncol] array"))
-        extent = lambda n: (shape[1],) if n in columns else (shape[0] + 1, shape[1]) if n in levels else shape
-        size = lambda n: int(np.prod(extent(n)))
-        empty = lambda n: np.empty(extent(n), dtype=dtype(n))
+        empty = lambda n: np.empty(extent(n), dtype=dtype[n])
         outs = {n: (empty(n) if x is None else x) for n, x in outs.items()}
         if diagnostics is True:
             diagnostics = {n: empty(n) for n in DIAG}
@@ -776,10 +798,10 @@ class Context:
         for name, x in list(outs.items()) + list(diagnostics.items()):
             if name not in tuple(outs) + DIAG:
                 raise ValueError("%s: no diagnostic %r" % (entry, name))
-            if not (isinstance(x, np.ndarray) and x.dtype == dtype(name) and x.flags.c_contiguous and x.size == size(name)):
-                raise ValueError("%s: %s is written in place: a C-contiguous %s array of the right size" % (entry, name, dtype(name).name))
+            if not (isinstance(x, np.ndarray) and x.dtype == dtype[name] and x.flags.c_contiguous and x.size == int(np.prod(extent(name)))):
+                raise ValueError("%s: %s is written in place: a C-contiguous %s array of the right size" % (entry, name, dtype[name].name))
         a.nlay, a.ncol = shape
-        for out, inp in in_place:
+        for out, inp in arrays["in_place"]:
             if out in outs and outs[out] is mine[inp]:      # (a pair the call does not have: BucketHydrology with one layer)
                 given[inp] = outs[out]
         for name, x in list(given.items()) + list(outs.items()) + list(diagnostics.items()):
@@ -1068,44 +1090,7 @@ class Context:
         if taucld is not None:
             given["taucld"] = taucld
         given.update({"gas%d" % i: x for i, x in enumerate(gases) if x is not None})
-        outs = dict(up=up, dn=dn, tend=tend)
-        f64 = np.dtype(np.float64)
-        if memspace:
-            if any(x is None for x in outs.values()) or ncol is None or nlay is None:
-                raise ValueError("cork_longwave: device pointers need up, dn, tend, ncol and nlay")
-            a.ncol, a.nlay = int(ncol), int(nlay)
-            diagnostics = diagnostics if isinstance(diagnostics, dict) else {}
-            for name, x in list(given.items()) + list(outs.items()) + list(diagnostics.items()):
-                if name not in CORK_LONGWAVE_IN + CORK_LONGWAVE_OUT + CORK_LONGWAVE_DIAG:
-                    raise ValueError("cork_longwave: no diagnostic %r" % name)
-                setattr(a, name, _device_pointer(x, f64, name))
-            self._ck(self.lib.rrtmg_hip_cork_longwave(self.h, C.byref(a)))
-            return outs["up"], outs["dn"], outs["tend"], diagnostics
-        given = {n: np.ascontiguousarray(x, dtype=np.float64) for n, x in given.items()}
-        shape = given["t"].shape
-        if len(shape) != 2:
-            raise ValueError("cork_longwave: t must be [nlay][ncol]")
-        L, N, B = shape[0], shape[1], int(nband)
-        extents = dict(t=(L, N), pmid=(L, N), pint=(L + 1, N), tsfc=(N,), emis=(B, N), taucld=(L, N, B), up=(L + 1, N), dn=(L + 1, N), tend=(L, N), hr=(L, N),
-                       up_band=(B, L + 1, N), dn_band=(B, L + 1, N), tau_band=(B, L, N), trans_band=(B, L, N), hr_band=(B, L, N))
-        extents.update({n: (L, N) for n in CORK_LONGWAVE_GASES})
-        for n, x in given.items():
-            if x.shape != extents[n]:
-                raise ValueError("cork_longwave: %s is %s, the grid of t %s and %d bands want %s" % (n, x.shape, shape, B, extents[n]))
-        outs = {n: (np.empty(extents[n]) if x is None else x) for n, x in outs.items()}
-        if diagnostics is True:
-            diagnostics = {n: np.empty(extents[n]) for n in CORK_LONGWAVE_DIAG}
-        elif not isinstance(diagnostics, dict):
-            diagnostics = {}
-        for name, x in list(outs.items()) + list(diagnostics.items()):
-            if name not in CORK_LONGWAVE_OUT + CORK_LONGWAVE_DIAG:
-                raise ValueError("cork_longwave: no diagnostic %r" % name)
-            if not (isinstance(x, np.ndarray) and x.dtype == f64 and x.flags.c_contiguous and x.size == int(np.prod(extents[name]))):
-                raise ValueError("cork_longwave: %s is written in place: a C-contiguous float64 array of the right size" % name)
-        a.nlay, a.ncol = L, N
-        for name, x in list(given.items()) + list(outs.items()) + list(diagnostics.items()):
-            setattr(a, name, x.ctypes.data)
-        self._ck(self.lib.rrtmg_hip_cork_longwave(self.h, C.byref(a)))
+        outs, diagnostics = self._column_call("cork_longwave", a, given, dict(up=up, dn=dn, tend=tend), diagnostics, memspace, ncol, nlay, nband=int(nband))
         return outs["up"], outs["dn"], outs["tend"], diagnostics
 
     @property

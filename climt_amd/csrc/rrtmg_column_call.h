@@ -1,13 +1,16 @@
-// rrtmg_column_call.h -- ONE staging and launch path for the column components (host code only): dry adjustment, boundary layer,
-// Emanuel convection, simple physics.  Each .hip file holds one table, a row per array of its public struct (include/rrtmg_hip.h).
+// rrtmg_column_call.h -- ONE staging and launch path for the column components (host code only), eleven entries: dry adjustment,
+// boundary layer, Emanuel convection, simple physics; Frierson optical depth, gray longwave, grid-scale condensation; the snow/ice
+// column; BucketHydrology and SecondBEST; the correlated-k longwave.  Each .hip file holds a table per entry, a row per array of its
+// public struct (include/rrtmg_hip.h).
 // A row states once: the member of the public struct and its name in messages, the member of the kernel's call struct, the
 // extent, and -- read off the member's own type -- the element type (double or int32) and the direction (const: an input);
 // for an output, the one input it may be exactly (in place); whether NULL is refused.  Every path that enumerates the arrays
 // walks the table: the "must be given" refusal, the aliasing check, the staging plan of a host-pointer call, the uploads, the
 // binding of the call struct under either memspace and the downloads.  Whether an optional input is read at all stays the
 // entry's decision: it hands the walkers the rows it does NOT read (`unread`, column_bits).
-// The plan and the aliasing check are plain C++ (tools/column_call_check.cpp runs them under the host sanitizers); what calls HIP
-// is behind __HIPCC__.  A new column component is one table, its checks, its kernel.
+// The plan and the aliasing check are plain C++ (tools/column_table_check.h holds their checks once; the five check programs that
+// include it run them under the host sanitizers); what calls HIP is behind __HIPCC__.  A new column component is one table, its
+// checks, its kernel.
 #pragma once
 #include <cstddef>
 #include <cstdint>

@@ -3,6 +3,7 @@ and state builders.  TEST INFRASTRUCTURE ONLY."""
 import ctypes as C
 import datetime
 import os
+import re
 import subprocess
 import sys
 
@@ -48,6 +49,48 @@ def build_host_program(tmp_path_factory, source, sanitized=False, flags=(), comp
     opt = ["-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all"] if sanitized else ["-O1"]
     subprocess.check_call(list(compiler) + ["-std=c++17"] + opt + list(flags) + [os.path.join(ROOT, "tools", source), "-o", exe])
     return exe
+
+
+def header_pointer_members(struct):
+    """-> {member: (is_output, "f64" | "i32")} for every `double *` / `int32_t *` member of `struct`, a column component's
+    struct of include/rrtmg_hip.h: const <-> input."""
+    text = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "rrtmg_hip.h")).read(), flags=re.S)
+    body = re.search(r"typedef struct \{([^}]*)\} %s;" % struct, text).group(1)
+    found = {}
+    for const, ctype, names in re.findall(r"(const\s+)?(double|int32_t)\s+(\*[^;()]*);", body):
+        for n in names.split(","):
+            n = n.strip()
+            assert n.startswith("*") and "*" not in n[1:], (struct, n)
+            found[n[1:].strip()] = (not const, {"double": "f64", "int32_t": "i32"}[ctype])
+    return found
+
+
+def column_table_rows(program, *mode):
+    """The rows a host check program prints for its tables (`mode`: its tables mode, where it has others), the checks of
+    tools/column_table_check.h having passed: dicts of entry, io, struct, member, extent, type, flag, in_place_of."""
+    out = subprocess.run([program] + list(mode), stdout=subprocess.PIPE, universal_newlines=True, check=True).stdout.split("\n")
+    assert out[-2:] == ["ok", ""]
+    rows = [dict(zip(("entry", "io", "struct", "member", "extent", "type", "flag", "in_place_of"), line.split())) for line in out[:-2]]
+    assert all(len(r) == 8 for r in rows)
+    return rows
+
+
+def assert_column_rows_agree(rows, entry, struct):
+    """The printed rows of one table against the header's `struct` and the Python layer's COLUMN_ARRAYS[entry]: names and order,
+    direction, element type, the optional inputs, the in-place pairs and the extent of every row -- all six extents."""
+    from climt_amd import _lib
+    arrays = _lib.COLUMN_ARRAYS[entry]
+    assert rows and all(r["entry"] == entry and r["struct"] == struct for r in rows)
+    members = [r["member"] for r in rows]
+    assert len(set(members)) == len(members), "a member is listed twice"
+    assert {r["member"]: (r["io"] == "out", r["type"]) for r in rows} == header_pointer_members(struct)      # const <-> input, and the element type
+    assert members == list(arrays["extent"]) == [n for n, t in arrays["struct"]._fields_ if t is C.c_void_p and n != "table"]
+    assert [r["member"] for r in rows if r["io"] == "in"] == list(arrays["IN"]) and all(r["io"] == "out" and r["flag"] == "-" for r in rows if r["member"] in arrays["DIAG"])
+    assert [r["member"] for r in rows if r["io"] == "in" and r["flag"] == "-"] == list(arrays["optional"])
+    assert {r["member"]: {"f64": "float64", "i32": "int32"}[r["type"]] for r in rows} == {n: t.name for n, t in arrays["dtype"].items()}
+    assert {r["member"]: r["in_place_of"] for r in rows if r["in_place_of"] != "-"} == dict(arrays["in_place"])
+    assert set(_lib.COLUMN_EXTENTS) == {"[nlay][ncol]", "[nlay+1][ncol]", "[ncol]", "[nband][nlay][ncol]", "[nband][nlay+1][ncol]", "[nband][ncol]"}
+    assert {r["member"]: r["extent"] for r in rows} == arrays["extent"]
 
 
 def _fill(a, inp, fields, flags, keep):

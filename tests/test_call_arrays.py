@@ -13,7 +13,7 @@ import subprocess
 import pytest
 
 from climt_amd._lib import LW_BAND_FLUXES, LW_OUT, SW_BAND_FLUXES, SW_COMPONENTS, SW_OUT
-from helpers import ROOT, build_host_program
+from helpers import ROOT, assert_column_rows_agree, build_host_program, column_table_rows, header_pointer_members
 
 STRUCTS = ("rrtmg_sw_args", "rrtmg_sw_surface", "rrtmg_sw_components", "rrtmg_sw_band_fluxes", "rrtmg_lw_args", "rrtmg_lw_band_fluxes")
 # double pointers of the structs that are deliberately in no table, each with its reason
@@ -57,30 +57,11 @@ COLUMN_STRUCTS = {"rrtmg_dry_adjust": "DRY_ADJUST", "rrtmg_boundary_layer": "BOU
 @pytest.fixture(scope="module")
 def column_tables(tmp_path_factory):
     """The rows tools/column_call_check.cpp prints (it checks the staging plan and the aliasing refusals itself): plain C++, no HIP."""
-    exe = build_host_program(tmp_path_factory, "column_call_check.cpp")
-    out = subprocess.run([exe], stdout=subprocess.PIPE, universal_newlines=True, check=True).stdout.split("\n")
-    assert out[-2:] == ["ok", ""]
-    rows = [dict(zip(("entry", "io", "struct", "member", "extent", "type", "flag", "in_place_of"), line.split())) for line in out[:-2]]
-    assert all(len(r) == 8 for r in rows)
-    return rows
-
-
-def column_header_members():
-    """-> {(struct, member): (is_output, type)} for every pointer member of the four column structs of include/rrtmg_hip.h."""
-    text = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "rrtmg_hip.h")).read(), flags=re.S)
-    found = {}
-    for s in COLUMN_STRUCTS:
-        body = re.search(r"typedef struct \{([^}]*)\} %s;" % s, text).group(1)
-        for const, ctype, names in re.findall(r"(const\s+)?(double|int32_t)\s+(\*[^;()]*);", body):
-            for n in names.split(","):
-                n = n.strip()
-                assert n.startswith("*") and "*" not in n[1:], (s, n)
-                found[(s, n[1:].strip())] = (not const, {"double": "f64", "int32_t": "i32"}[ctype])
-    return found
+    return column_table_rows(build_host_program(tmp_path_factory, "column_call_check.cpp"))
 
 
 def test_every_array_of_a_column_struct_is_one_row_of_its_table(column_tables):
-    header = column_header_members()
+    header = {(s, m): v for s in COLUMN_STRUCTS for m, v in header_pointer_members(s).items()}
     assert len(header) == 7 + 20 + 20 + 17
     printed = {(r["struct"], r["member"]): (r["io"] == "out", r["type"]) for r in column_tables}
     assert len(printed) == len(column_tables), "a member is listed twice"
@@ -101,9 +82,7 @@ def test_column_rows_agree_with_the_python_layer(column_tables):
             {"cbmf_out": "cbmf"} if last else {n: n[:-4] for n in OUT})
         arrays = _lib.COLUMN_ARRAYS[rows[0]["entry"]]
         assert (arrays["IN"], arrays["DIAG"]) == (IN, DIAG)
-        for key, extent in (("columns", "[ncol]"), ("levels", "[nlay+1][ncol]")):      # the others: [nlay][ncol]
-            assert sorted(arrays.get(key, ())) == sorted(r["member"] for r in rows if r["extent"] == extent), (struct, key)
-        assert sorted(arrays.get("int32", ())) == sorted(r["member"] for r in rows if r["type"] == "i32"), struct
+        assert_column_rows_agree(rows, rows[0]["entry"], struct)      # names, direction, type, in-place pairs and every extent
         assert {"[ncol]", "[nlay+1][ncol]", "[nlay][ncol]"} >= {r["extent"] for r in rows}
 
 

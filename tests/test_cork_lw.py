@@ -13,7 +13,7 @@ import pytest
 
 import climt_amd
 from climt_amd import cork, initialization
-from helpers import build_host_program
+from helpers import assert_column_rows_agree, build_host_program, column_table_rows
 
 import cork_cases as X
 
@@ -91,13 +91,14 @@ def check_input(name, c):
 
 
 def test_check_program_tables_plan_and_refusals(cork_check):
-    out = subprocess.run([cork_check, "tables"], stdout=subprocess.PIPE, universal_newlines=True, check=True).stdout.split("\n")
-    assert out[-2:] == ["ok", ""]
-    rows = [line.split() for line in out[:-2]]
     from climt_amd import _lib
+    table = column_table_rows(cork_check, "tables")
+    rows = [[r[k] for k in ("entry", "io", "struct", "member", "extent", "type", "flag", "in_place_of")] for r in table]
     assert [r[3] for r in rows] == list(_lib.CORK_LONGWAVE_IN + _lib.CORK_LONGWAVE_OUT + _lib.CORK_LONGWAVE_DIAG)
     assert all((r[1] == "in") == (r[3] in _lib.CORK_LONGWAVE_IN) for r in rows)
     assert [r[3] for r in rows if r[6] == "required"] == ["t", "pmid", "pint", "tsfc", "emis", "up", "dn", "tend"]
+    assert_column_rows_agree(table, "cork_longwave", "rrtmg_cork_longwave")      # names, direction, type and every extent, the band-multiplied ones among them
+    assert {r["extent"] for r in table} == set(_lib.COLUMN_EXTENTS)      # this table has all six
 
 
 @pytest.mark.parametrize("name", list(X.CASES))

@@ -26,7 +26,7 @@ import pytest
 
 import climt_amd
 from climt_amd import _lib
-from helpers import GOLDEN, ROOT, build_host_program
+from helpers import GOLDEN, ROOT, assert_column_rows_agree, build_host_program, column_table_rows, header_pointer_members
 
 import land_surface_cases as X
 
@@ -327,26 +327,17 @@ def test_host_program_under_the_address_and_undefined_behaviour_sanitizers(progr
 
 
 def test_tables_agree_with_the_header_and_the_python_layer(program):
-    out = subprocess.run([program, "tables"], stdout=subprocess.PIPE, universal_newlines=True, check=True).stdout.split("\n")
-    assert out[-2:] == ["ok", ""]
-    every = [dict(zip(("entry", "io", "struct", "member", "extent", "type", "flag", "in_place_of"), line.split())) for line in out[:-2]]
-    assert all(len(r) == 8 for r in every) and [r["entry"] for r in every] == ["bucket_hydrology"] * 29 + ["second_best"] * 34
-    text = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "rrtmg_hip.h")).read(), flags=re.S)
+    every = column_table_rows(program, "tables")
+    assert [r["entry"] for r in every] == ["bucket_hydrology"] * 29 + ["second_best"] * 34
     for entry, (strct, cls, IN, OUT, DIAG) in ENTRIES.items():
         rows = [r for r in every if r["entry"] == entry]
         assert all(r["struct"] == strct for r in rows) and tuple(r["member"] for r in rows) == IN + OUT + DIAG
-        body = re.search(r"typedef struct \{([^}]*)\} %s;" % strct, text).group(1)
-        header = {}
-        for const, ctype, names in re.findall(r"(const\s+)?(double|int32_t)\s+(\*[^;()]*);", body):
-            for n in names.split(","):
-                header[n.strip()[1:].strip()] = (not const, {"double": "f64", "int32_t": "i32"}[ctype])
-        assert {r["member"]: (r["io"] == "out", r["type"]) for r in rows} == header
+        assert {r["member"]: (r["io"] == "out", r["type"]) for r in rows} == header_pointer_members(strct)
         assert all((r["io"] == "in") == (r["member"] in IN) for r in rows)
         assert all((r["flag"] == "required") == (r["member"] in IN + OUT and r["member"] not in DEEP) for r in rows)
         arrays = _lib.COLUMN_ARRAYS[entry]
-        assert (arrays["IN"], arrays["DIAG"]) == (IN, DIAG) and not arrays.get("levels") and not any(r["extent"] == "[nlay+1][ncol]" for r in rows)
-        assert sorted(arrays["columns"]) == sorted(r["member"] for r in rows if r["extent"] == "[ncol]")
-        assert sorted(arrays.get("int32", ())) == sorted(r["member"] for r in rows if r["type"] == "i32")
+        assert (arrays["IN"], arrays["DIAG"]) == (IN, DIAG) and not any(r["extent"] == "[nlay+1][ncol]" for r in rows)
+        assert_column_rows_agree(rows, entry, strct)      # names, direction, type, in-place pairs and every extent
         assert {r["member"]: r["in_place_of"] for r in rows if r["in_place_of"] != "-"} == IN_PLACE[entry] == dict(arrays["in_place"])
     assert all(r["extent"] == "[ncol]" for r in every if r["entry"] == "bucket_hydrology")
     assert "land_surface" not in open(os.path.join(ROOT, "tools", "column_call_check.cpp")).read()

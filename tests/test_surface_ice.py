@@ -26,7 +26,7 @@ import pytest
 import climt_amd
 from climt_amd import _lib
 from climt_amd._sympl_compat import DataArray
-from helpers import GOLDEN, ROOT, build_host_program
+from helpers import GOLDEN, ROOT, assert_column_rows_agree, build_host_program, column_table_rows, header_pointer_members
 
 import surface_ice_cases as X
 
@@ -228,24 +228,16 @@ def test_host_program_under_the_address_and_undefined_behaviour_sanitizers(progr
 
 
 def test_table_agrees_with_the_header_and_the_python_layer(program):
-    out = subprocess.run([program, "tables"], stdout=subprocess.PIPE, universal_newlines=True, check=True).stdout.split("\n")
-    assert out[-2:] == ["ok", ""]
-    rows = [dict(zip(("entry", "io", "struct", "member", "extent", "type", "flag", "in_place_of"), line.split())) for line in out[:-2]]
-    assert all(len(r) == 8 and r["entry"] == ENTRY and r["struct"] == STRUCT for r in rows)
+    rows = column_table_rows(program, "tables")
+    assert all(r["entry"] == ENTRY and r["struct"] == STRUCT for r in rows)
     assert tuple(r["member"] for r in rows) == IN + OUT + DIAG
-    text = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "rrtmg_hip.h")).read(), flags=re.S)
-    body = re.search(r"typedef struct \{([^}]*)\} %s;" % STRUCT, text).group(1)
-    header = {}
-    for const, ctype, names in re.findall(r"(const\s+)?(double|int32_t)\s+(\*[^;()]*);", body):
-        for n in names.split(","):
-            header[n.strip()[1:].strip()] = (not const, {"double": "f64", "int32_t": "i32"}[ctype])
-    assert {r["member"]: (r["io"] == "out", r["type"]) for r in rows} == header
+    assert {r["member"]: (r["io"] == "out", r["type"]) for r in rows} == header_pointer_members(STRUCT)
     assert all((r["io"] == "in") == (r["member"] in IN) for r in rows)
     assert all(r["flag"] == "required" for r in rows if r["member"] in IN + OUT) and all(r["flag"] == "-" for r in rows if r["member"] in DIAG)
     arrays = _lib.COLUMN_ARRAYS[ENTRY]
-    assert (arrays["IN"], arrays["DIAG"]) == (IN, DIAG) and not arrays.get("levels") and not any(r["extent"] == "[nlay+1][ncol]" for r in rows)
-    assert sorted(arrays["columns"]) == sorted(r["member"] for r in rows if r["extent"] == "[ncol]")
-    assert sorted(arrays["int32"]) == sorted(r["member"] for r in rows if r["type"] == "i32") == ["area_type", "flags"]
+    assert (arrays["IN"], arrays["DIAG"]) == (IN, DIAG) and not any(r["extent"] == "[nlay+1][ncol]" for r in rows)
+    assert_column_rows_agree(rows, ENTRY, STRUCT)      # names, direction, type, in-place pairs and every extent
+    assert sorted(n for n, t in arrays["dtype"].items() if t.name == "int32") == sorted(r["member"] for r in rows if r["type"] == "i32") == ["area_type", "flags"]
     assert {r["member"]: r["in_place_of"] for r in rows if r["in_place_of"] != "-"} == IN_PLACE == dict(arrays["in_place"])
 
 

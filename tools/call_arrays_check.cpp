@@ -12,10 +12,9 @@
 #include <string>
 
 #include "../climt_amd/csrc/rrtmg_call_arrays.h"
+#include "check_common.h"
 
 using namespace rrtmg;
-
-#define CHECK(cond) do { if (!(cond)) { fprintf(stderr, "%s:%d: CHECK failed: %s\n", __FILE__, __LINE__, #cond); exit(1); } } while (0)
 
 static const char *ext_name(Ext e) {
   static const char *const n[] = {"[nlay][N]", "[nlay+1][N]", "[N]", "[k][N]", "[k*nlay][N]", "[k*nrow][N]", "[nlay][N][k]"};

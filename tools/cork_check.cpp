@@ -6,9 +6,10 @@
 //   c++ -std=c++17 -ffp-contract=off -g -fsanitize=address,undefined -fno-sanitize-recover=all tools/cork_check.cpp -o cork_check
 //
 //   cork_check tables
-//       Line: <entry> <in|out> <struct> <member> <extent> <f64|i32> <required or -> <the input it may be, or ->, then the staging plan
-//       at ncol 1, 64, 65 x nlay 1, 61 x nband 1, 4 with every optional output absent or present (slots disjoint, inside the total,
-//       aligned), the sizes of the band-multiplied extents, the refusals of a table's description and of a call's gases.  Last line "ok".
+//       Line: <entry> <in|out> <struct> <member> <extent> <f64|i32> <required or -> <the input it may be, or ->, then the checks of
+//       tools/column_table_check.h: the staging plan at nband 1, 4 with every combination of the optional outputs, gas0 and taucld
+//       (the sizes of the band-multiplied extents among them), the aliasing refusals and the "must be given" text; then the refusals
+//       of a table's description and of a call's gases.  Last line "ok".
 //   cork_check run <in.bin> <out.bin>
 //       in : 40 doubles {ncol, nlay, gas_rule, ngas, nband, ngpt, nT, nP, nX, nC, k_is_f32, has_cont, has_cloud, gas_scale[8], m_h2o,
 //            sigma_sb, g, cpd, diffusivity, pressure_scale, x_clip[2], c_clip[2], 0...}, then k (the reference's layout, as doubles),
@@ -27,48 +28,21 @@
 #include <vector>
 
 #include "../climt_amd/csrc/rrtmg_cork.hip"
+#include "column_table_check.h"
 
 using namespace rrtmg;
 
-#define CHECK(cond) do { if (!(cond)) { fprintf(stderr, "%s:%d: CHECK failed: %s\n", __FILE__, __LINE__, #cond); exit(1); } } while (0)
-
 static int tables() {
-  static const char *const ext[] = {"[nlay][ncol]", "[nlay+1][ncol]", "[ncol]", "[nband][nlay][ncol]", "[nband][nlay+1][ncol]", "[nband][ncol]"};
   const ColumnTable &t = kCorkLongwave;
-  ColumnMask required = 0, optional_out = 0;
+  print_table(t);
+  ColumnMask optional_out = 0;
   for (int i = 0; i < t.n; ++i) {
-    const ColumnRow &r = t.rows[i];
-    CHECK(r.name && r.name[0] && column_index(t, r.name) == i && !r.in_place_of && !r.i32);
-    printf("%s %s %s %s %s %s %s %s\n", t.entry, r.out ? "out" : "in", t.strct, r.name, ext[(int)r.ext], "f64", r.required ? "required" : "-", "-");
-    if (r.required) required |= ColumnMask(1) << i;
-    if (r.out && !r.required) optional_out |= ColumnMask(1) << i;
+    CHECK(!t.rows[i].in_place_of && !t.rows[i].i32);
+    if (t.rows[i].out && !t.rows[i].required) optional_out |= ColumnMask(1) << i;
   }
-  for (size_t ncol : {(size_t)1, (size_t)64, (size_t)65})
-    for (size_t nlay : {(size_t)1, (size_t)61})
-      for (size_t nband : {(size_t)1, (size_t)4}) {
-        CHECK(column_bytes(t.rows[column_index(t, "emis")], ncol, nlay, nband) == nband * ncol * 8);
-        CHECK(column_bytes(t.rows[column_index(t, "taucld")], ncol, nlay, nband) == nlay * ncol * nband * 8);
-        CHECK(column_bytes(t.rows[column_index(t, "up_band")], ncol, nlay, nband) == nband * (nlay + 1) * ncol * 8);
-        CHECK(column_bytes(t.rows[column_index(t, "t")], ncol, nlay, nband) == nlay * ncol * 8 && column_bytes(t.rows[column_index(t, "t")], ncol, nlay) == nlay * ncol * 8);
-        for (ColumnMask sub = optional_out;; sub = (sub - 1) & optional_out) {      // every subset of the optional outputs, gas0 and taucld with the first
-          const ColumnMask present = required | sub | (sub == optional_out ? column_bits(t, {"gas0", "taucld"}) : 0);
-          const ColumnPlan p = column_plan(t, ncol, nlay, present, nband);
-          size_t sum = 0;
-          for (int i = 0; i < t.n; ++i) {
-            if (!(present >> i & 1)) { CHECK(p.at[i] == kColumnNoSlot); continue; }
-            const size_t n = column_bytes(t.rows[i], ncol, nlay, nband);
-            CHECK(p.at[i] % 8 == 0 && p.at[i] + n <= p.total);
-            sum += n;
-            for (int j = 0; j < i; ++j)
-              if (present >> j & 1) CHECK(!ranges_overlap((const void *)(p.at[i] + 8), n, (const void *)(p.at[j] + 8), column_bytes(t.rows[j], ncol, nlay, nband)));
-          }
-          CHECK(sum == p.total);
-          if (!sub) break;
-        }
-      }
-  char msg[256];
+  check_plan(t, {1, 4}, optional_out | column_bits(t, {"gas0", "taucld"}));      // (every subset of the fifteen optional rows is too many)
+  check_aliasing<rrtmg_cork_longwave>(t, "", "t, pmid, pint, tsfc, emis, up, dn and tend must be given", 4);
   rrtmg_cork_longwave a{};
-  CHECK(column_required_refusal(t, &a, msg, sizeof msg) && !strcmp(msg, "t, pmid, pint, tsfc, emis, up, dn and tend must be given"));
 
   // the description of a table
   const double grid[3] = {1.0, 2.0, 3.0}, flat[3] = {1.0, 2.0, 2.0}, k[64] = {0.0};
@@ -99,31 +73,6 @@ static int tables() {
 }
 
 // ---- the rules -------------------------------------------------------------------------------------------------------------------
-static std::vector<double> read_all(const char *path) {
-  FILE *f = fopen(path, "rb");
-  CHECK(f != nullptr);
-  fseek(f, 0, SEEK_END);
-  const long bytes = ftell(f);
-  fseek(f, 0, SEEK_SET);
-  std::vector<double> v((size_t)bytes / sizeof(double));
-  CHECK(fread(v.data(), sizeof(double), v.size(), f) == v.size());
-  fclose(f);
-  return v;
-}
-
-constexpr size_t kGuard = 8;
-constexpr double kPoison = -777.25;
-
-struct Guarded {
-  std::vector<double> v;
-  size_t n = 0;
-  void set(const double *src, size_t len) { n = len; v.assign(len + 2 * kGuard, kPoison); if (src) memcpy(v.data() + kGuard, src, len * sizeof(double)); }
-  double *p() { return v.data() + kGuard; }
-  void check_guards() const { for (size_t g = 0; g < kGuard; ++g) CHECK(v[g] == kPoison && v[kGuard + n + g] == kPoison); }
-  bool holds(const double *src) { return memcmp(p(), src, n * sizeof(double)) == 0; }
-  bool untouched() { for (size_t i = 0; i < n; ++i) if (p()[i] != kPoison) return false; return true; }
-  bool written() { for (size_t i = 0; i < n; ++i) if (p()[i] == kPoison) return false; return true; }
-};
 
 template <class K>
 static void run_bands(const CorkLongwaveCall &c) {

@@ -18,40 +18,9 @@
 #include <vector>
 
 #include "../climt_amd/csrc/rrtmg_dry_adjust.h"
+#include "check_common.h"
 
 using namespace rrtmg;
-
-#define CHECK(cond) do { if (!(cond)) { fprintf(stderr, "%s:%d: CHECK failed: %s\n", __FILE__, __LINE__, #cond); exit(1); } } while (0)
-
-static std::vector<double> read_all(const char *path) {
-  FILE *f = fopen(path, "rb");
-  CHECK(f != nullptr);
-  fseek(f, 0, SEEK_END);
-  const long bytes = ftell(f);
-  fseek(f, 0, SEEK_SET);
-  std::vector<double> v((size_t)bytes / sizeof(double));
-  CHECK(fread(v.data(), sizeof(double), v.size(), f) == v.size());
-  fclose(f);
-  return v;
-}
-static void write_all(const char *path, const std::vector<double> &v) {
-  FILE *f = fopen(path, "wb");
-  CHECK(f != nullptr);
-  CHECK(fwrite(v.data(), sizeof(double), v.size(), f) == v.size());
-  fclose(f);
-}
-
-constexpr size_t kGuard = 8;
-constexpr double kPoison = -777.25;
-
-struct Guarded {
-  std::vector<double> v;
-  size_t n = 0;
-  void set(const double *src, size_t len) { n = len; v.assign(len + 2 * kGuard, kPoison); if (src) memcpy(v.data() + kGuard, src, len * sizeof(double)); }
-  double *p() { return v.data() + kGuard; }
-  void check_guards() const { for (size_t g = 0; g < kGuard; ++g) CHECK(v[g] == kPoison && v[kGuard + n + g] == kPoison); }
-  bool holds(const double *src) { return memcmp(p(), src, n * sizeof(double)) == 0; }
-};
 
 struct Result { std::vector<double> t, q; std::vector<int32_t> top; };
 
@@ -85,8 +54,6 @@ static Result run_launch(int ncol, int nlay, bool in_place, bool want_top, const
   }
   return r;
 }
-
-static bool equal(const std::vector<double> &a, const std::vector<double> &b) { return a.size() == b.size() && (a.empty() || memcmp(a.data(), b.data(), a.size() * sizeof(double)) == 0); }
 
 int main(int argc, char **argv) {
   if (argc != 5) { fprintf(stderr, "usage: %s <ncol> <nlay> <in.bin> <out.bin>\n", argv[0]); return 2; }

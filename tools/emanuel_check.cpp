@@ -22,46 +22,14 @@
 #include <vector>
 
 #include "../climt_amd/csrc/rrtmg_emanuel.h"
+#include "check_common.h"
 
 using namespace rrtmg;
 
-#define CHECK(cond) do { if (!(cond)) { fprintf(stderr, "%s:%d: CHECK failed: %s\n", __FILE__, __LINE__, #cond); exit(1); } } while (0)
-
-static std::vector<double> read_all(const char *path) {
-  FILE *f = fopen(path, "rb");
-  CHECK(f != nullptr);
-  fseek(f, 0, SEEK_END);
-  const long bytes = ftell(f);
-  fseek(f, 0, SEEK_SET);
-  std::vector<double> v((size_t)bytes / sizeof(double));
-  CHECK(fread(v.data(), sizeof(double), v.size(), f) == v.size());
-  fclose(f);
-  return v;
-}
-static void write_all(const char *path, const std::vector<double> &v) {
-  FILE *f = fopen(path, "wb");
-  CHECK(f != nullptr);
-  CHECK(fwrite(v.data(), sizeof(double), v.size(), f) == v.size());
-  fclose(f);
-}
-
-constexpr size_t kGuard = 8;
-constexpr double kPoison = -777.25;
 constexpr int kHead = 28;
 
-struct Guarded {
-  std::vector<double> v;
-  size_t n = 0;
-  void set(const double *src, size_t len, double fill = kPoison) {
-    n = len; v.assign(len + 2 * kGuard, fill);
-    for (size_t g = 0; g < kGuard; ++g) v[g] = v[kGuard + len + g] = kPoison;
-    if (src) memcpy(v.data() + kGuard, src, len * sizeof(double));
-  }
-  double *p() { return v.data() + kGuard; }
-  void check_guards() const { for (size_t g = 0; g < kGuard; ++g) CHECK(v[g] == kPoison && v[kGuard + n + g] == kPoison); }
-  bool holds(const double *src) { return memcmp(p(), src, n * sizeof(double)) == 0; }
-  bool untouched() { for (size_t i = 0; i < n; ++i) if (p()[i] != kPoison) return false; return true; }
-  bool written() { for (size_t i = 0; i < n; ++i) if (p()[i] == kPoison || !std::isfinite(p()[i])) return false; return true; }
+struct FiniteGuarded : Guarded {      // written means: every element finite, too
+  bool written() { for (size_t i = 0; i < n; ++i) if (!std::isfinite(p()[i])) return false; return Guarded::written(); }
 };
 
 struct Result { std::vector<double> prof[5], col[7]; };      // ft fq fu fv ft_per_day; precip wd tprime qprime cbmf_out cape iflag
@@ -70,7 +38,7 @@ struct Result { std::vector<double> prof[5], col[7]; };      // ft fq fu fv ft_p
 static Result run_call(int ncol, int nlay, long chunk, bool in_place, bool want_diag, const double *k, const double *in) {
   const size_t n1 = ncol, nl = (size_t)nlay * n1, nl1 = nl + n1;
   const bool use_qs = k[0] != 0.0;
-  Guarded prof[5], pi, cb, qs, out[5], diag[6], w1, w2;
+  FiniteGuarded prof[5], pi, cb, qs, out[5], diag[6], w1, w2;
   std::vector<int32_t> flag(n1 + 2 * kGuard, -99);
   for (int j = 0; j < 5; ++j) { prof[j].set(in + j * nl, nl); out[j].set(nullptr, nl); }
   pi.set(in + 5 * nl, nl1); cb.set(in + 5 * nl + nl1, n1); qs.set(in + 5 * nl + nl1 + n1, nl);
@@ -121,8 +89,6 @@ static Result run_call(int ncol, int nlay, long chunk, bool in_place, bool want_
   }
   return r;
 }
-
-static bool equal(const std::vector<double> &a, const std::vector<double> &b) { return a.size() == b.size() && (a.empty() || memcmp(a.data(), b.data(), a.size() * sizeof(double)) == 0); }
 
 int main(int argc, char **argv) {
   if (argc != 5) { fprintf(stderr, "usage: %s <ncol> <nlay> <in.bin> <out.bin>\n", argv[0]); return 2; }

@@ -19,13 +19,12 @@
 
 #include "../climt_amd/csrc/rrtmg_kiss_host.h"
 #include "../climt_amd/csrc/rrtmg_sw_device.h"
+#include "check_common.h"
 
 using namespace rrtmg;
 
-#define CHECK(cond) do { if (!(cond)) { fprintf(stderr, "%s:%d: CHECK failed: %s\n", __FILE__, __LINE__, #cond); exit(1); } } while (0)
-
-constexpr size_t kGuard = 16;
-constexpr uint64_t kPoison = 0xa5a5a5a5a5a5a5a5ull;
+constexpr size_t kWordGuard = 16;
+constexpr uint64_t kWordPoison = 0xa5a5a5a5a5a5a5a5ull;
 
 int main(int argc, char **argv) {
   if (argc != 8) { fprintf(stderr, "usage: %s ncol nlay nsub icld changeSeed in.bin out.bin\n", argv[0]); return 2; }
@@ -41,28 +40,28 @@ int main(int argc, char **argv) {
   const double *play = in.data(), *cldfr = play + nl, *alpha = cldfr + nl;
 
   const size_t words = (size_t)nsub * nw * ncol;
-  std::vector<uint64_t> seq(words + 2 * kGuard, kPoison), jmp(words + 2 * kGuard, kPoison);
+  std::vector<uint64_t> seq(words + 2 * kWordGuard, kWordPoison), jmp(words + 2 * kWordGuard, kWordPoison);
   int err_seq = 0, err_jmp = 0;
-  for (int c = 0; c < ncol; ++c) kiss_mask_column_exp(ncol, nlay, nsub, icld, seed, play, cldfr, alpha, seq.data() + kGuard, nw, &err_seq, c);
+  for (int c = 0; c < ncol; ++c) kiss_mask_column_exp(ncol, nlay, nsub, icld, seed, play, cldfr, alpha, seq.data() + kWordGuard, nw, &err_seq, c);
   std::vector<uint32_t> jumps;
   kiss_build_jumps(nsub, nlay, icld, seed, jumps);
   CHECK(jumps.size() == (size_t)nsub * kKissJumpWords);
   for (int g = 0; g < nsub; ++g) CHECK(jumps[(size_t)g * kKissJumpWords] == (uint32_t)seed + (uint32_t)g * 2u * (uint32_t)nlay);
   // (the order of a launch: the sub-column index fastest within a tile of 64 columns)
   for (int c = 0; c < ncol; ++c)
-    for (int g = 0; g < nsub; ++g) kiss_mask_jump_exp(ncol, nlay, icld, play, cldfr, alpha, jmp.data() + kGuard, nw, &err_jmp, jumps.data(), c, g);
+    for (int g = 0; g < nsub; ++g) kiss_mask_jump_exp(ncol, nlay, icld, play, cldfr, alpha, jmp.data() + kWordGuard, nw, &err_jmp, jumps.data(), c, g);
   CHECK(err_seq == 0 && err_jmp == 0);
-  for (size_t g = 0; g < kGuard; ++g) CHECK(seq[g] == kPoison && seq[kGuard + words + g] == kPoison && jmp[g] == kPoison && jmp[kGuard + words + g] == kPoison);
+  for (size_t g = 0; g < kWordGuard; ++g) CHECK(seq[g] == kWordPoison && seq[kWordGuard + words + g] == kWordPoison && jmp[g] == kWordPoison && jmp[kWordGuard + words + g] == kWordPoison);
   size_t differ = 0;
-  for (size_t i = 0; i < words; ++i) differ += seq[kGuard + i] != jmp[kGuard + i];
+  for (size_t i = 0; i < words; ++i) differ += seq[kWordGuard + i] != jmp[kWordGuard + i];
   if (differ) { fprintf(stderr, "sequential and jump-ahead masks differ in %zu of %zu words\n", differ, words); return 1; }
   // no bit above the last layer
   if (nlay % 64)
     for (int g = 0; g < nsub; ++g)
-      for (int c = 0; c < ncol; ++c) CHECK((jmp[kGuard + ((size_t)g * nw + nw - 1) * ncol + c] >> (nlay % 64)) == 0);
+      for (int c = 0; c < ncol; ++c) CHECK((jmp[kWordGuard + ((size_t)g * nw + nw - 1) * ncol + c] >> (nlay % 64)) == 0);
   f = fopen(argv[7], "wb");
   CHECK(f != nullptr);
-  CHECK(fwrite(jmp.data() + kGuard, sizeof(uint64_t), words, f) == words);
+  CHECK(fwrite(jmp.data() + kWordGuard, sizeof(uint64_t), words, f) == words);
   fclose(f);
   printf("ok (%d x %d x %d, icld %d, seed %d)\n", ncol, nlay, nsub, icld, seed);
   return 0;

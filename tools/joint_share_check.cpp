@@ -11,10 +11,9 @@
 #include <vector>
 
 #include "../climt_amd/csrc/rrtmg_share.h"
+#include "check_common.h"
 
 using namespace rrtmg;
-
-#define CHECK(cond) do { if (!(cond)) { fprintf(stderr, "%s:%d: CHECK failed: %s\n", __FILE__, __LINE__, #cond); exit(1); } } while (0)
 
 struct Input { const double *host; size_t n; double mul, div; int policy; int how; };   // how: 0 upload, 1 fill, 2 absent
 

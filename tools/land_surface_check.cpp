@@ -6,8 +6,9 @@
 //
 //   land_surface_check tables
 //       Line: <entry> <in|out> <struct> <member> <extent> <f64|i32> <required or -> <the input it may be, or ->   (the format of
-//       tools/surface_ice_check.cpp), both tables; then the staging plan at ncol 1, 63, 64, 65 x three nlay x every combination of
-//       optional rows, the aliasing refusals with made-up addresses and the "must be given" text.  Last line "ok".
+//       tools/surface_ice_check.cpp), both tables; then the checks of tools/column_table_check.h: the staging plan at ncol 1, 63, 64,
+//       65 x three nlay x every combination of optional rows, the aliasing refusals with made-up addresses and the "must be given"
+//       text.  Last line "ok".
 //   land_surface_check bucket <ncol> <in.bin> <out.bin>
 //       in : 15 doubles {layers, has_drain, dt, rd, cp, rho_water, lv, bulk_coefficient, beta_parameter, soil_moisture_max,
 //            deep_soil_moisture_max, tau_m, deep_ratio, tau_drain, pressure_scale}, then the 19 input rows [ncol] in the table's order
@@ -31,105 +32,11 @@
 #include <vector>
 
 #include "../climt_amd/csrc/rrtmg_land_surface.hip"
+#include "column_table_check.h"
 
 using namespace rrtmg;
 
-#define CHECK(cond) do { if (!(cond)) { fprintf(stderr, "%s:%d: CHECK failed: %s\n", __FILE__, __LINE__, #cond); exit(1); } } while (0)
-
 // ---- the tables ------------------------------------------------------------------------------------------------------------------
-static void print_table(const ColumnTable &t) {
-  static const char *const ext[] = {"[nlay][ncol]", "[nlay+1][ncol]", "[ncol]"};
-  for (int i = 0; i < t.n; ++i) {
-    const ColumnRow &r = t.rows[i];
-    CHECK(r.name && r.name[0] && column_index(t, r.name) == i);      // a name is one row
-    if (r.in_place_of) {      // an earlier input of the same shape and type
-      const int p = column_index(t, r.in_place_of);
-      CHECK(r.out && p >= 0 && p < i && !t.rows[p].out && t.rows[p].ext == r.ext && t.rows[p].i32 == r.i32 && t.rows[p].required == r.required);
-    }
-    printf("%s %s %s %s %s %s %s %s\n", t.entry, r.out ? "out" : "in", t.strct, r.name, ext[(int)r.ext], r.i32 ? "i32" : "f64", r.required ? "required" : "-", r.in_place_of ? r.in_place_of : "-");
-  }
-}
-
-static void check_plan(const ColumnTable &t) {
-  ColumnMask required = 0, optional = 0;
-  for (int i = 0; i < t.n; ++i) (t.rows[i].required ? required : optional) |= ColumnMask(1) << i;
-  for (size_t ncol : {(size_t)1, (size_t)63, (size_t)64, (size_t)65})
-    for (size_t nlay : {(size_t)t.nlay_min, (size_t)t.nlay_min + 1, (size_t)61})
-      for (ColumnMask sub = optional;; sub = (sub - 1) & optional) {      // every subset of the optional rows
-        const ColumnMask present = required | sub;
-        const ColumnPlan p = column_plan(t, ncol, nlay, present);
-        size_t sum = 0;
-        for (int i = 0; i < t.n; ++i) {
-          const ColumnRow &r = t.rows[i];
-          if (!(present >> i & 1)) { CHECK(p.at[i] == kColumnNoSlot); continue; }
-          const size_t n = column_bytes(r, ncol, nlay);
-          CHECK(n == (r.ext == ColumnExt::Col ? 1 : r.ext == ColumnExt::Lay ? nlay : nlay + 1) * ncol * (r.i32 ? 4 : 8));
-          CHECK(p.at[i] != kColumnNoSlot && p.at[i] + n <= p.total && p.at[i] % (r.i32 ? 4 : 8) == 0);
-          const bool shares = r.in_place_of && (present >> column_index(t, r.in_place_of) & 1);
-          if (!shares) sum += n;
-          for (int j = 0; j < i; ++j) {
-            if (!(present >> j & 1)) continue;
-            if (r.in_place_of && column_index(t, r.in_place_of) == j) CHECK(p.at[i] == p.at[j]);
-            else CHECK(!ranges_overlap((const void *)(p.at[i] + 8), n, (const void *)(p.at[j] + 8), column_bytes(t.rows[j], ncol, nlay)));
-          }
-        }
-        CHECK(p.total == sum);      // nothing but the rows that are present
-        if (sub == 0) break;
-      }
-}
-
-// a public struct whose every array sits at a made-up address, 16 MiB apart (never dereferenced)
-template <class A> static A made_up(const ColumnTable &t) {
-  A a{};
-  for (int i = 0; i < t.n; ++i) {
-    const void *p = (const void *)((uintptr_t)(i + 1) << 24);
-    memcpy((char *)&a + t.rows[i].pub, &p, sizeof p);
-  }
-  return a;
-}
-template <class A> static std::string refusal(const ColumnTable &t, const A &a, size_t ncol, size_t nlay) {
-  ColumnSpan s[kColumnMaxRows];
-  char msg[160] = "";
-  const bool refused = aliasing_refusal(s, column_spans(t, &a, ncol, nlay, column_present(t, &a, ColumnMask(0)), s), t.note, msg, sizeof msg);
-  CHECK(refused == (msg[0] != 0));
-  return msg;
-}
-template <class A> static void set(const ColumnTable &t, A &a, int row, const void *p) { memcpy((char *)&a + t.rows[row].pub, &p, sizeof p); }
-
-template <class A> static void check_aliasing(const ColumnTable &t, const char *note, const char *must_be_given) {
-  const size_t ncol = 65, nlay = (size_t)t.nlay_min;
-  A a = made_up<A>(t);
-  CHECK(refusal(t, a, ncol, nlay).empty());
-  char msg[512];
-  CHECK(!column_required_refusal(t, &a, msg, sizeof msg) && std::string(msg) == must_be_given);
-  for (int o = 0; o < t.n; ++o) {
-    const ColumnRow &out = t.rows[o];
-    if (!out.out) continue;
-    const int partner = out.in_place_of ? column_index(t, out.in_place_of) : -1;
-    const std::string aliases = std::string(out.name) + " aliases an input" + (partner >= 0 ? note : "");
-    for (int i = 0; i < t.n; ++i) {
-      if (t.rows[i].out) continue;
-      a = made_up<A>(t);
-      set(t, a, o, column_ptr(&a, t.rows[i].pub));
-      CHECK(refusal(t, a, ncol, nlay) == (i == partner ? "" : aliases));      // x_out == x: in place
-      if (i != partner) continue;
-      set(t, a, o, (const char *)column_ptr(&a, t.rows[i].pub) + 8);          // in place means exactly in place
-      CHECK(refusal(t, a, ncol, nlay) == aliases);
-    }
-    for (int e = 0; e < o; ++e) {
-      if (!t.rows[e].out) continue;
-      for (size_t shift : {(size_t)0, (size_t)4}) {
-        a = made_up<A>(t);
-        set(t, a, o, (const char *)column_ptr(&a, t.rows[e].pub) + shift);
-        CHECK(refusal(t, a, ncol, nlay) == std::string(out.name) + " overlaps " + t.rows[e].name);
-      }
-    }
-    a = made_up<A>(t);      // a required row that is NULL is refused, an optional one is not
-    set(t, a, o, nullptr);
-    CHECK(column_required_refusal(t, &a, msg, sizeof msg) == out.required && refusal(t, a, ncol, nlay).empty());
-  }
-}
-
 static int tables() {
   print_table(kBucketHydrology);
   print_table(kSecondBest);
@@ -145,39 +52,6 @@ static int tables() {
 }
 
 // ---- the rules -------------------------------------------------------------------------------------------------------------------
-static std::vector<double> read_all(const char *path) {
-  FILE *f = fopen(path, "rb");
-  CHECK(f != nullptr);
-  fseek(f, 0, SEEK_END);
-  const long bytes = ftell(f);
-  fseek(f, 0, SEEK_SET);
-  std::vector<double> v((size_t)bytes / sizeof(double));
-  CHECK(fread(v.data(), sizeof(double), v.size(), f) == v.size());
-  fclose(f);
-  return v;
-}
-static void write_all(const char *path, const std::vector<double> &v) {
-  FILE *f = fopen(path, "wb");
-  CHECK(f != nullptr);
-  CHECK(fwrite(v.data(), sizeof(double), v.size(), f) == v.size());
-  fclose(f);
-}
-
-constexpr size_t kGuard = 8;
-constexpr double kPoison = -777.25;
-
-struct Guarded {
-  std::vector<double> v;
-  size_t n = 0;
-  void set(const double *src, size_t len) { n = len; v.assign(len + 2 * kGuard, kPoison); if (src) memcpy(v.data() + kGuard, src, len * sizeof(double)); }
-  double *p() { return v.data() + kGuard; }
-  void check_guards() const { for (size_t g = 0; g < kGuard; ++g) CHECK(v[g] == kPoison && v[kGuard + n + g] == kPoison); }
-  bool holds(const double *src) { return memcmp(p(), src, n * sizeof(double)) == 0; }
-  bool untouched() { for (size_t i = 0; i < n; ++i) if (p()[i] != kPoison) return false; return true; }
-  bool written() { for (size_t i = 0; i < n; ++i) if (p()[i] == kPoison) return false; return true; }
-};
-
-static bool equal(const std::vector<double> &a, const std::vector<double> &b) { return a.size() == b.size() && (a.empty() || memcmp(a.data(), b.data(), a.size() * sizeof(double)) == 0); }
 
 // ---- BucketHydrology: one launch on the CPU -> the ten output rows (a row that is not written: zeros) ----------------------------------
 constexpr int kBucketIn = 19, kBucketOut = 10;

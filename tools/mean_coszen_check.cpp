@@ -25,30 +25,9 @@
 #include <vector>
 
 #include "../climt_amd/csrc/rrtmg_intermittent.h"
+#include "check_common.h"
 
 using namespace rrtmg;
-
-#define CHECK(cond) do { if (!(cond)) { fprintf(stderr, "%s:%d: CHECK failed: %s\n", __FILE__, __LINE__, #cond); exit(1); } } while (0)
-
-static bool same_bits(double a, double b) { return memcmp(&a, &b, sizeof a) == 0; }
-
-static std::vector<double> read_all(const char *path) {
-  FILE *f = fopen(path, "rb");
-  CHECK(f != nullptr);
-  fseek(f, 0, SEEK_END);
-  const long bytes = ftell(f);
-  fseek(f, 0, SEEK_SET);
-  std::vector<double> v((size_t)bytes / sizeof(double));
-  CHECK(fread(v.data(), sizeof(double), v.size(), f) == v.size());
-  fclose(f);
-  return v;
-}
-static void write_all(const char *path, const std::vector<double> &v) {
-  FILE *f = fopen(path, "wb");
-  CHECK(f != nullptr);
-  CHECK(fwrite(v.data(), sizeof(double), v.size(), f) == v.size());
-  fclose(f);
-}
 
 static void element_rules() {
   const double nan = std::nan(""), inf = INFINITY;
@@ -87,9 +66,6 @@ static int run_mean(int ncol, const char *in_path, const char *out_path) {
   printf("ok (%d columns, D = %.17g)\n", ncol, sun.D);
   return 0;
 }
-
-constexpr size_t kGuard = 8;
-constexpr double kPoison = -777.25;
 
 // one launch on the CPU: every thread of grid (columns, ny, n) in turn -> the dst arrays, guards checked
 static std::vector<std::vector<double>> run_launch(int ncol, int n, const std::vector<int> &rows, const std::vector<int> &in_place, const double *num,

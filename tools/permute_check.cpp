@@ -14,10 +14,9 @@
 #include <vector>
 
 #include "../climt_amd/csrc/rrtmg_permute.h"
+#include "check_common.h"
 
 using namespace rrtmg;
-
-#define CHECK(cond) do { if (!(cond)) { fprintf(stderr, "%s:%d: CHECK failed: %s\n", __FILE__, __LINE__, #cond); exit(1); } } while (0)
 
 struct Map { PermuteHead h; std::vector<int> src, dst; };
 

@@ -18,17 +18,12 @@
 #include <vector>
 
 #include "../climt_amd/csrc/rrtmg_precision.h"
+#include "check_common.h"
 
 using namespace rrtmg;
 
-#define CHECK(cond) do { if (!(cond)) { fprintf(stderr, "%s:%d: CHECK failed: %s\n", __FILE__, __LINE__, #cond); exit(1); } } while (0)
-
-static bool same_bits(float a, float b) { return memcmp(&a, &b, sizeof a) == 0; }
-static bool same_bits(double a, double b) { return memcmp(&a, &b, sizeof a) == 0; }
-
 static const size_t kCounts[] = {0, 1, 3, 4, 5, 63, 64, 65, 1027};
 static const size_t kThreads[] = {7, 256, 4096};   // (at least 6: the first threads take the head and the tail)
-constexpr size_t kGuard = 8;
 
 int main() {
   // ---- the element functions ------------------------------------------------------------------------------------------------
