@@ -24,10 +24,26 @@ MOLAR_MASS = {"h2o": 18.015, "co2": 44.010, "o3": 47.998, "ch4": 16.043, "n2o": 
 M_H2O = MOLAR_MASS["h2o"] / M_DRY
 NLAYS = (1, 2, 30, 61)
 NCOLS = (1, 64, 65, 130)
-TABLES = ("earth4", "h2o_axis", "two_band", "two_gas", "premixed")
+BASE_TABLES = ("earth4", "h2o_axis", "two_band", "two_gas", "premixed")      # derived from the reference's shipped tables
+# The shape tables: made by the maker from a formula (its docstring), every array float32, so that one file is run as a float table
+# and, with k cast, as a double table.  name -> (gases, bands, g-points, nT, nP, nX, nC, continuum)
+GASES8 = ("co2", "nh3", "h2o", "o3", "ch4", "so2", "n2o", "o2")      # (nh3 and so2: not in MOLAR_MASS, their scale is 1.0)
+SHAPE_TABLES = {"g1": (("h2o",), 1, 1, 5, 4, 0, 0, False), "g3_min": (("effective",), 3, 3, 2, 2, 2, 0, False), "g4_gases8": (GASES8, 2, 4, 4, 5, 0, 0, False),
+                "g5_rank7": (("effective",), 2, 5, 3, 4, 3, 2, False), "g9": (("effective",), 2, 9, 5, 3, 0, 0, False),
+                "g16_cont": (("effective",), 2, 16, 4, 4, 3, 3, True), "bands32": (("h2o", "co2"), 32, 2, 3, 5, 0, 0, False)}
+TABLES = BASE_TABLES + tuple(SHAPE_TABLES)
 # case -> (table, diffusivity factor)
-CASES = {"earth": ("earth4", 1.66), "earth_d2": ("earth4", 2.0), "on_nodes": ("earth4", 1.66), "h2o_axis": ("h2o_axis", 1.66), "two_band": ("two_band", 1.66),
-         "two_gas": ("two_gas", 1.66), "premixed": ("premixed", 1.66), "cloudy": ("earth4", 1.66), "emissivity": ("earth4", 1.66)}
+BASE_CASES = {"earth": ("earth4", 1.66), "earth_d2": ("earth4", 2.0), "on_nodes": ("earth4", 1.66), "h2o_axis": ("h2o_axis", 1.66), "two_band": ("two_band", 1.66),
+              "two_gas": ("two_gas", 1.66), "premixed": ("premixed", 1.66), "cloudy": ("earth4", 1.66), "emissivity": ("earth4", 1.66)}
+# one atmosphere within the grids per shape table; `_spans`: past both ends of every axis; `_cloudy`: cloud and emissivity by band
+SHAPE_CASES = {"g1": ("g1", 1.66), "g3_min": ("g3_min", 1.66), "g3_min_spans": ("g3_min", 1.66), "g4_gases8": ("g4_gases8", 1.66), "g5_rank7": ("g5_rank7", 1.66),
+               "g5_rank7_spans": ("g5_rank7", 1.66), "g9": ("g9", 1.66), "g16_cont": ("g16_cont", 1.66), "g16_cont_spans": ("g16_cont", 1.66),
+               "bands32": ("bands32", 1.66), "bands32_cloudy": ("bands32", 1.66)}
+CASES = dict(BASE_CASES, **SHAPE_CASES)
+SPANS = ("earth", "earth_d2", "g3_min_spans", "g5_rank7_spans", "g16_cont_spans")
+# cork_band_kernel<NG, K>: NG is the first of these that holds the table's g-points -- the thresholds of cork_launch_band
+# (climt_amd/csrc/rrtmg_cork.hip; run_bands of tools/cork_check.cpp has the same)
+NG_BOUNDS = (1, 2, 4, 8, 16)
 INPUTS = ("t", "p", "p_int", "tsfc", "emis", "taucld")          # and the gases of the table's rule: "h2o", "co2", ...
 FIELDS = ("up", "dn", "tend", "hr", "up_band", "dn_band", "tau_band", "trans_band", "hr_band")
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
@@ -49,6 +65,16 @@ def table(name):
     t["rule"] = 0 if names == ["effective"] and not has_x else 1 if names == ["effective"] and has_x else 2
     t["gases"] = [] if t["rule"] == 0 else (["h2o"] + (["co2"] if has_c else [])) if t["rule"] == 1 else names
     return t
+
+
+def kernel_ng(ngpt):
+    return next(n for n in NG_BOUNDS if ngpt <= n)
+
+
+def table_types(name):
+    """-> the element types of k the tests run the table in: a shape table as stored and with k cast to double (every value is
+    float32-exact), any other in the file's own."""
+    return ("f32", "f64") if name in SHAPE_TABLES else ("f32" if table(name)["k_coefficients"].dtype == np.float32 else "f64",)
 
 
 # ---- the rules ----------------------------------------------------------------------------------------------------------------------
@@ -77,9 +103,10 @@ def heating(net, p_int):
     return G / CPD * (net[1:] - net[:-1]) / (p_int[1:] - p_int[:-1])
 
 
-def statement(tab, c, diffusivity=1.66, pressure_scale=1.0):
+def statement(tab, c, diffusivity=1.66, pressure_scale=1.0, probe=None):
     """tab: a table dict; c: the inputs (t, p [nlay][ncol], p_int [nlay+1][ncol], tsfc [ncol], emis [nband][ncol], taucld
-    [nlay][ncol][nband] and the gases of the table's rule) -> dict of FIELDS."""
+    [nlay][ncol][nband] and the gases of the table's rule) -> dict of FIELDS.  probe: a dict that is given tau_min and tau_max,
+    the smallest and the largest layer optical depth of any g-point before the cloud."""
     k = tab["k_coefficients"]
     ngas, nband, ngpt = k.shape[:3]
     t, p, p_int = c["t"], c["p"] * pressure_scale, c["p_int"] * pressure_scale
@@ -131,6 +158,8 @@ def statement(tab, c, diffusivity=1.66, pressure_scale=1.0):
                 tau += kv * amounts[ig]
             if contv is not None:
                 tau += contv * amounts[0]
+            if probe is not None:
+                probe["tau_min"], probe["tau_max"] = min(probe.get("tau_min", np.inf), float(tau.min())), max(probe.get("tau_max", 0.0), float(tau.max()))
             tau = tau + c["taucld"][:, :, b]
             src = (pf[b, g][iT].astype(np.float64) * (1.0 - fT) + pf[b, g][iT + 1].astype(np.float64) * fT) * planck
             wg = np.float64(w[b, g])
@@ -195,7 +224,7 @@ def _inputs(name, nlay, ncol):
     t_grid, p_grid = np.asarray(tab["temperature_grid"], dtype=np.float64), np.asarray(tab["pressure_grid_log"], dtype=np.float64)
     p_int = pressures(nlay, ncol)
     colv = np.arange(ncol)
-    spans = name in ("earth", "earth_d2")
+    spans = name in SPANS
     if spans:      # past both ends of every axis
         t = _spread(shape, t_grid[0] - 12.0, t_grid[-1] + 12.0, 0)
         p = _spread(shape, 0.3 * np.exp(p_grid[0]), 3.0 * np.exp(p_grid[-1]), 1, log=True)
@@ -208,7 +237,7 @@ def _inputs(name, nlay, ncol):
         p = 0.5 * (p_int[:-1] + p_int[1:])
         t = 212.0 + 80.0 * (p / p_int[0]) ** 1.3 + 0.013 * colv[None, :] + 1.5 * np.sin(0.7 * np.arange(nlay)[:, None] + 0.3 * colv[None, :])
     c = dict(t=t, p=p, p_int=p_int, tsfc=(t[0] + 2.0 + 0.01 * (colv % 9)) * np.ones(ncol), emis=np.ones((nband, ncol)), taucld=np.zeros((nlay, ncol, nband)))
-    for gas in tab["gases"]:
+    for ig, gas in enumerate(tab["gases"]):
         if gas == "h2o" and tab["rule"] == 1:
             x_grid = np.asarray(tab["h2o_vmr_grid"], dtype=np.float64)
             c["h2o"] = _spread(shape, 0.05 * x_grid[0], 1.05, 2, log=True) if spans else _spread(shape, 2.0e-6, 0.03, 2, log=True)
@@ -217,22 +246,22 @@ def _inputs(name, nlay, ncol):
             c["co2"] = _spread(shape, 0.2 * c_grid[0], 2.0 * c_grid[-1], 3, log=True) if spans else _spread(shape, 2.0e-4, 1.0e-3, 3, log=True)
         elif gas == "h2o":
             c["h2o"] = _spread(shape, 1.0e-3, 0.02, 2, log=True)      # (no column so thin that its downward flux is rounding noise of the source)
-        else:
-            c[gas] = _spread(shape, 2.0e-4, 8.0e-4, 3, log=True)
-    if name == "cloudy":      # cloud in the layers k with (k + column) % 3 == 0, the depth by band; 1e3 in the lowest layer of band 0
+        else:      # (the eight gases of g4_gases8: a phase each, none of them the water vapour's)
+            c[gas] = _spread(shape, 2.0e-4, 8.0e-4, 3 + ig if len(tab["gases"]) > 2 else 3, log=True)
+    if name in ("cloudy", "bands32_cloudy"):      # cloud in the layers k with (k + column) % 3 == 0, the depth by band; 1e3 in the lowest layer of band 0
         lev = np.arange(nlay)[:, None, None]
         cloud = ((lev + colv[None, :, None]) % 3 == 0) * (0.2 + 0.7 * np.arange(nband)[None, None, :] + 0.01 * (colv[None, :, None] % 5))
         cloud[0, :, 0] = 1.0e3
         c["taucld"] = cloud * np.ones((nlay, ncol, nband))
-    if name == "emissivity":      # band 0 black, band 1 a mirror, the others in between and varying by column
+    if name in ("emissivity", "bands32_cloudy"):      # band 0 black, band 1 a mirror, the others in between and varying by column
         e = 0.5 + 0.45 * np.sin(0.37 * colv[None, :] + np.arange(nband)[:, None]) * np.ones((nband, ncol))
         e[0], e[1 % nband] = 1.0, 0.0
         c["emis"] = e
     return {k: np.ascontiguousarray(x, dtype=np.float64) for k, x in c.items()}
 
 
-def check_case(name, c):
-    """Asserts that a case does what its name says (c: inputs and the statement's outputs)."""
+def check_case(name, c, probe=None):
+    """Asserts that a case does what its name says (c: inputs and the statement's outputs; probe: what the statement left in it)."""
     tab = table(CASES[name][0])
     nlay, ncol = c["t"].shape
     for f in FIELDS:
@@ -266,7 +295,31 @@ def check_case(name, c):
         assert k.ndim == 5 and tab["rule"] == 2 and tab["gases"] == ["h2o", "co2"] and k.shape[0] == 2
     if name == "premixed":
         assert k.ndim == 5 and tab["rule"] == 0 and tab["gases"] == []
-    if name == "cloudy":
+    if name in SHAPE_CASES:
+        gases, nband, ngpt, nT, nP, nX, nC, cont = SHAPE_TABLES[CASES[name][0]]
+        assert k.shape == (len(gases), nband, ngpt, nT, nP) + (nX,) * (nX > 0) + (nC,) * (nC > 0) and ("continuum_kappa" in tab) == cont
+        assert [str(g) for g in tab["gas_names"]] == list(gases) and tab["rule"] == (2 if gases[0] != "effective" else 1 if nX else 0)
+        assert all(tab[a].dtype == np.float32 for a in tab if isinstance(tab[a], np.ndarray) and tab[a].dtype.kind == "f")
+        assert same_bits(tab["gpoint_weights"].astype(np.float64).sum(axis=1), np.ones(nband))      # (multiples of 2^-10: the sum is exact)
+        axes = [(c["t"], tab["temperature_grid"]), (np.log(np.maximum(c["p"], 1.0)), tab["pressure_grid_log"])]
+        if nX:
+            axes.append((c["h2o"] / np.maximum(c["h2o"] + (1.0 - c["h2o"]) * M_H2O, 1e-30), tab["h2o_vmr_grid"]))
+        if nC:
+            axes.append((c["co2"], tab["co2_vmr_grid"]))
+        for i, (v, grid) in enumerate(axes):
+            grid = np.asarray(grid, dtype=np.float64)
+            steps = np.diff(np.log(grid) if i >= 2 else grid)      # (in the coordinate the axis is bracketed in)
+            assert grid.size == 2 or steps.max() > 1.5 * steps.min()      # far from uniform
+            if name in SPANS and big:      # every clamp fires, and interior points exist
+                assert (v <= grid[0]).any() and (v >= grid[-1]).any() and ((v > grid[0]) & (v < grid[-1])).any(), name
+            if name not in SPANS:
+                assert ((v > grid[0]) & (v < grid[-1])).all(), name
+        if name not in SPANS and nlay == 30:
+            # on the 30 layers the reference ran: the gas optical depth of a layer spans 1e-3 .. 1e2 over the g-points, each end to within half a decade: lanes that
+            # are nearly transparent and lanes that are opaque in one layer (one g-point: what the layers span, inside that range)
+            lo, hi = probe["tau_min"], probe["tau_max"]
+            assert (10 ** -3.5 <= lo <= 10 ** -2.5 and 10 ** 1.5 <= hi <= 10 ** 2.5) if ngpt > 1 else (1e-3 <= lo and hi <= 1e2 and hi >= 30.0 * lo), (name, lo, hi)
+    if name in ("cloudy", "bands32_cloudy"):
         cloud = c["taucld"]
         assert (cloud > 0).any() and ((cloud == 0).any() or nlay * ncol < 6) and (cloud[0, :, 0] == 1.0e3).all()
         D = CASES[name][1]
@@ -281,9 +334,9 @@ def check_case(name, c):
 @functools.lru_cache(maxsize=None)
 def cork_case(name, nlay, ncol):
     """-> dict(the inputs; the statement's outputs).  Shared and read-only."""
-    c = _inputs(name, nlay, ncol)
-    c.update(statement(table(CASES[name][0]), c, CASES[name][1]))
-    check_case(name, c)
+    c, probe = _inputs(name, nlay, ncol), {}
+    c.update(statement(table(CASES[name][0]), c, CASES[name][1], probe=probe))
+    check_case(name, c, probe)
     for x in c.values():
         x.setflags(write=False)
     return c

@@ -2,7 +2,9 @@
 outputs (tests/golden/cork_<case>.npz, made by tests/golden/make_cork_golden.py from the reference's own array_call) under the stored
 tolerances; tools/cork_check.cpp -- the column rules of climt_amd/csrc/rrtmg_cork.h as the kernels run them, the row table, the
 table checks and the gas refusals -- built with the host sanitizers, against the statement; the component's interface against
-tests/golden/cork_interface.json for every fixture table; and what the component refuses."""
+tests/golden/cork_interface.json for every fixture table; and what the component refuses.  The shape tables (X.SHAPE_TABLES: every
+g-point bound of the kernel, padded and filled, every rank with and without a continuum, eight gases, 32 bands, two-node axes) run the
+check program once as float and once as double tables, to the same bits; a coverage test holds the set of tables to all of that."""
 import json
 import os
 import pickle
@@ -13,7 +15,7 @@ import pytest
 
 import climt_amd
 from climt_amd import cork, initialization
-from helpers import assert_column_rows_agree, build_host_program, column_table_rows
+from helpers import ROOT, assert_column_rows_agree, build_host_program, column_table_rows
 
 import cork_cases as X
 
@@ -74,13 +76,14 @@ def cork_check(tmp_path_factory):
     return build_host_program(tmp_path_factory, "cork_check.cpp", sanitized=True, flags=("-ffp-contract=off",))
 
 
-def check_input(name, c):
-    """The binary input of `cork_check run` for a case: what KTable prepares, in the reference's layout."""
+def check_input(name, c, k_is_f32=None):
+    """The binary input of `cork_check run` for a case: what KTable prepares, in the reference's layout.  k_is_f32: the element
+    type the program holds k in (None: the file's)."""
     kt = cork.KTable(X.table_path(X.CASES[name][0]))
     nlay, ncol = c["t"].shape
     nX, nC = (kt.k.shape[5] if kt.k.ndim >= 6 else 0), (kt.k.shape[6] if kt.k.ndim == 7 else 0)
     head = np.zeros(40)
-    head[:13] = [ncol, nlay, kt.gas_rule, kt.ngas, kt.nband, kt.ngpt, kt.k.shape[3], kt.k.shape[4], nX, nC, kt.k.dtype == np.float32, kt.log_cont is not None, 1]
+    head[:13] = [ncol, nlay, kt.gas_rule, kt.ngas, kt.nband, kt.ngpt, kt.k.shape[3], kt.k.shape[4], nX, nC, kt.k.dtype == np.float32 if k_is_f32 is None else k_is_f32, kt.log_cont is not None, 1]
     head[13:13 + kt.ngas] = kt.gas_scale
     head[13 + kt.ngas:21] = 1.0
     head[21:27] = [X.M_H2O, X.SIGMA_SB, X.G, X.CPD, X.CASES[name][1], 1.0]
@@ -101,28 +104,73 @@ def test_check_program_tables_plan_and_refusals(cork_check):
     assert {r["extent"] for r in table} == set(_lib.COLUMN_EXTENTS)      # this table has all six
 
 
-@pytest.mark.parametrize("name", list(X.CASES))
-def test_check_program_runs_clean_and_agrees_with_the_statement(cork_check, tmp_path, name):
+def run_check(cork_check, tmp_path, name, c, k_is_f32=None):
+    """`cork_check run` on a case -> the nine fields, having asserted what every run must keep: a clean exit, the tolerances of the
+    statement, and bit for bit the ascending band sum and the two heating rates; and what the program's last line says it ran."""
     tol = X.tolerances(name)
+    nlay, ncol = c["t"].shape
+    src, dst = str(tmp_path / "in.bin"), str(tmp_path / "out.bin")
+    check_input(name, c, k_is_f32).tofile(src)
+    out = subprocess.run([cork_check, "run", src, dst], stdout=subprocess.PIPE, stderr=subprocess.PIPE, universal_newlines=True)
+    assert out.returncode == 0 and out.stdout.startswith("ok"), out.stderr[-2000:]
+    flat, got, at = np.fromfile(dst), {}, 0
+    for f in X.FIELDS:
+        got[f] = flat[at:at + c[f].size].reshape(c[f].shape)
+        at += c[f].size
+    assert at == flat.size
+    for f, v in X.deviations(got, c).items():
+        assert v <= tol[f], (name, nlay, ncol, k_is_f32, f, v, tol[f])
+    # bit for bit: the ascending band sum, the two heating rates, the top
+    up = np.zeros_like(got["up"])
+    for b in range(got["up_band"].shape[0]):
+        up += got["up_band"][b]
+    assert X.same_bits(up, got["up"]) and X.same_bits(got["hr"], got["tend"] * 86400.0)
+    assert X.same_bits(got["hr_band"], np.stack([X.heating(u - d, c["p_int"]) * 86400.0 for u, d in zip(got["up_band"], got["dn_band"])]))
+    return got, out.stdout.strip().split("\n")[-1]
+
+
+@pytest.mark.parametrize("name", list(X.BASE_CASES))
+def test_check_program_runs_clean_and_agrees_with_the_statement(cork_check, tmp_path, name):
     for nlay, ncol in ((1, 1), (2, 65), (30, 5), (61, 3)):
+        run_check(cork_check, tmp_path, name, X.cork_case(name, nlay, ncol))
+
+
+@pytest.mark.parametrize("name", list(X.SHAPE_CASES))
+def test_check_program_runs_a_shape_table_as_float_and_as_double_to_the_same_bits(cork_check, tmp_path, name):
+    """Every stored value is float32-exact, so (double)float loses nothing: a bit of difference between the two instantiations is a
+    stride or a conversion gone wrong."""
+    tab = X.table(X.CASES[name][0])
+    k = tab["k_coefficients"]
+    for nlay, ncol in ((1, 1), (2, 65), (30, 5)):
         c = X.cork_case(name, nlay, ncol)
-        src, dst = str(tmp_path / "in.bin"), str(tmp_path / "out.bin")
-        check_input(name, c).tofile(src)
-        out = subprocess.run([cork_check, "run", src, dst], stdout=subprocess.PIPE, stderr=subprocess.PIPE, universal_newlines=True)
-        assert out.returncode == 0 and out.stdout.startswith("ok"), out.stderr[-2000:]
-        flat, got, at = np.fromfile(dst), {}, 0
+        as_float, line = run_check(cork_check, tmp_path, name, c, k_is_f32=1)
+        as_double, line64 = run_check(cork_check, tmp_path, name, c, k_is_f32=0)
+        assert line == line64 == "ok (cork, %d columns, %d layers, %d bands, %d g-points, rank %d, rule %d)" % (ncol, nlay, k.shape[1], k.shape[2], k.ndim, tab["rule"])
         for f in X.FIELDS:
-            got[f] = flat[at:at + c[f].size].reshape(c[f].shape)
-            at += c[f].size
-        assert at == flat.size
-        for f, v in X.deviations(got, c).items():
-            assert v <= tol[f], (name, nlay, ncol, f, v, tol[f])
-        # bit for bit: the ascending band sum, the two heating rates, the top
-        up = np.zeros_like(got["up"])
-        for b in range(got["up_band"].shape[0]):
-            up += got["up_band"][b]
-        assert X.same_bits(up, got["up"]) and X.same_bits(got["hr"], got["tend"] * 86400.0)
-        assert X.same_bits(got["hr_band"], np.stack([X.heating(u - d, c["p_int"]) * 86400.0 for u, d in zip(got["up_band"], got["dn_band"])]))
+            assert X.same_bits(as_float[f], as_double[f]), (name, nlay, ncol, f)
+
+
+def test_the_tables_reach_every_instantiation_and_every_shape_the_kernels_branch_on():
+    """cork_band_kernel<NG, K> over X.TABLES in the types the tests run them in (X.table_types): all ten (NG, K); every rank in both
+    types; ranks 6 and 7 with and without a continuum; for every NG a table that fills it and (from 4 on: below that a table with
+    fewer g-points takes a smaller NG) one that leaves lanes padded; eight gases; 32 bands; a two-node axis."""
+    seen = [(name, X.table(name), typ) for name in X.TABLES for typ in X.table_types(name)]
+    shape = lambda t: t["k_coefficients"].shape
+    assert {(X.kernel_ng(shape(t)[2]), typ) for _, t, typ in seen} == {(ng, typ) for ng in X.NG_BOUNDS for typ in ("f32", "f64")}
+    assert {(len(shape(t)), typ) for _, t, typ in seen} == {(rank, typ) for rank in (5, 6, 7) for typ in ("f32", "f64")}
+    cont = lambda t: "continuum_kappa" in t and t["continuum_kappa"].ndim == 4
+    assert {(len(shape(t)), cont(t)) for _, t, _ in seen if len(shape(t)) >= 6} == {(6, False), (6, True), (7, False), (7, True)}
+    fills = {(X.kernel_ng(shape(t)[2]), shape(t)[2] == X.kernel_ng(shape(t)[2])) for _, t, _ in seen}
+    assert fills == {(ng, True) for ng in X.NG_BOUNDS} | {(ng, False) for ng in X.NG_BOUNDS if ng >= 4}
+    assert max(shape(t)[0] for _, t, _ in seen) == cork.MAX_GASES == 8 and max(shape(t)[1] for _, t, _ in seen) == cork.MAX_BANDS == 32
+    assert max(shape(t)[2] for _, t, _ in seen) == cork.MAX_GPOINTS == X.NG_BOUNDS[-1]
+    assert any(2 in shape(t)[3:] for _, t, _ in seen)
+    # the thresholds above are the source's: cork_launch_band and cork_check's run_bands
+    for path in (("climt_amd", "csrc", "rrtmg_cork.hip"), ("tools", "cork_check.cpp")):
+        text = open(os.path.join(ROOT, *path)).read()
+        for ng in X.NG_BOUNDS[:-1]:
+            assert "n <= %d) " % ng in text, (path, ng)
+        assert "<16, K>" in text
 
 
 # ---- the component's interface ------------------------------------------------------------------------------------------------------
@@ -143,6 +191,23 @@ def test_interface_equals_the_reference_for_every_fixture_table():
         assert comp.tendency_properties == w["tendency_properties"] and comp.diagnostic_properties == w["diagnostic_properties"], name
         assert comp.num_longwave_bands == w["num_longwave_bands"] == initialization._num_bands["longwave"]
     assert "CorkLongwaveRadiation" in climt_amd.__all__
+
+
+def test_eight_gases_are_stated_and_passed_in_table_order():
+    want = json.load(open(os.path.join(X.GOLDEN, "cork_interface.json")))["tables"]["g4_gases8"]["input_properties"]
+    comp = component("g4_gases8")
+    cf = {"h2o": "specific_humidity", "co2": "mole_fraction_of_carbon_dioxide_in_air"}
+    names = [cf.get(g, "mole_fraction_of_%s_in_air" % g) for g in X.GASES8]
+    assert comp.gas_inputs() == names and len(set(names)) == 8 and set(names) <= set(want)
+    stated = comp.input_properties
+    assert stated == want and [n for n in stated if n in names] == names      # (the reference states them in table order too)
+    assert [stated[n]["alias"] for n in names] == list(X.GASES8) == comp._ktable.gas_names
+    assert [stated[n]["units"] for n in names] == ["kg/kg" if g == "h2o" else "mole/mole" for g in X.GASES8]
+    scale = dict(zip(X.GASES8, comp._ktable.gas_scale))
+    assert scale["h2o"] == scale["nh3"] == scale["so2"] == 1.0 and comp._ktable.gas_rule == 2
+    for g in ("co2", "o3", "ch4", "n2o", "o2"):
+        assert scale[g] == X.MOLAR_MASS[g] / X.M_DRY != 1.0, g
+    assert X.gas_names("g4_gases8") == list(X.GASES8)
 
 
 def test_pickle_keeps_the_class_default_of_the_diffusivity_factor():

@@ -60,7 +60,7 @@ def same(a, b, keys=None):
     return all(X.same_bits(a[k], b[k]) for k in (keys or a))
 
 
-@pytest.mark.parametrize("name", list(X.CASES))
+@pytest.mark.parametrize("name", list(X.BASE_CASES))
 def test_kernels_equal_the_statement_on_every_shape(ctx, handles, name):
     worst, tol = {}, X.tolerances(name)
     for nlay in X.NLAYS:
@@ -180,15 +180,14 @@ def test_radiative_convective_example_with_cork_longwave_in_both_modes():
     assert not X.same_bits(plain_end["air_temperature"].values, end_h["air_temperature"].values)
 
 
-def state_of(name, c):
-    q = lambda x, dims, units: DataArray(np.array(x), dims=dims, attrs={"units": units})
-    ml, il = ("mid_levels", "x"), ("interface_levels", "x")
-    s = {"time": datetime.datetime(2000, 1, 1), "air_temperature": q(c["t"], ml, "degK"), "air_pressure": q(c["p"], ml, "Pa"),
-         "air_pressure_on_interface_levels": q(c["p_int"], il, "Pa"), "surface_temperature": q(c["tsfc"], ("x",), "degK"),
-         "surface_longwave_emissivity": q(c["emis"], ("num_longwave_bands", "x"), "dimensionless"),
-         "longwave_optical_thickness_due_to_cloud": q(c["taucld"], ("mid_levels", "x", "num_longwave_bands"), "dimensionless")}
-    for g in X.gas_names(name):
-        s["specific_humidity" if g == "h2o" else "mole_fraction_of_%s_in_air" % {"co2": "carbon_dioxide"}.get(g, g)] = q(c[g], ml, "kg/kg" if g == "h2o" else "mole/mole")
+CASE_KEYS = {"T": "t", "p": "p", "p_int": "p_int", "T_surf": "tsfc", "emissivity": "emis", "tau_cloud_lw": "taucld"}      # alias -> the case's key; a gas: its alias
+
+
+def state_of(comp, c):
+    """A host state of the case `c` as the component states its inputs: names, dimensions and units are its input_properties."""
+    s = {"time": datetime.datetime(2000, 1, 1)}
+    for n, p in comp.input_properties.items():
+        s[n] = DataArray(np.array(c[CASE_KEYS.get(p["alias"], p["alias"])]), dims=tuple("x" if d == "*" else d for d in p["dims"]), attrs={"units": p["units"]})
     return s
 
 
@@ -202,7 +201,7 @@ def test_component_on_a_host_state_and_on_a_device_state(ctx, handles, name):
     c = X.cork_case(name, 30, 65)
     direct = call(ctx, handles, name, c)
     comp = climt_amd.CorkLongwaveRadiation(optics="correlated_k", table=X.table_path(X.CASES[name][0]), diffusivity_factor=X.CASES[name][1], context=ctx)
-    state = state_of(name, c)
+    state = state_of(comp, c)
     tend, diag = comp(state)
     assert X.same_bits(tend["air_temperature"].values, direct["tend"]) and set(diag) == set(HOST_NAMES.values())
     for f, n in HOST_NAMES.items():
