@@ -23,7 +23,7 @@ from .rrtmg import RRTMGLongwave, RRTMGShortwave, radiation_step  # noqa: F401,E
 from .simple_boundary_layer import SimpleBoundaryLayer  # noqa: F401,E402
 from .simple_physics import SimplePhysics  # noqa: F401,E402
 from .gray_radiation import Frierson06LongwaveOpticalDepth, GrayLongwaveRadiation  # noqa: F401,E402
-from .cork import CorkLongwaveRadiation  # noqa: F401,E402
+from .cork import CorkLongwaveRadiation, CorkShortwaveRadiation  # noqa: F401,E402
 from .grid_scale_condensation import GridScaleCondensation  # noqa: F401,E402
 from .surface_ice import LandIce, SeaIce  # noqa: F401,E402
 from .bucket_hydrology import BucketHydrology  # noqa: F401,E402
@@ -35,5 +35,5 @@ from .timestepping import AdamsBashforth  # noqa: F401,E402
 from .wrappers import UpdateFrequencyWrapper  # noqa: F401,E402
 from .intermittent import IntermittentLongwave, IntermittentShortwave  # noqa: F401,E402
 
-__all__ = ["RRTMGLongwave", "RRTMGShortwave", "Instellation", "BergerSolarInsolation", "SlabSurface", "DryConvectiveAdjustment", "SimpleBoundaryLayer", "EmanuelConvection", "SimplePhysics", "GrayLongwaveRadiation", "Frierson06LongwaveOpticalDepth", "GridScaleCondensation", "CorkLongwaveRadiation", "SeaIce", "LandIce", "BucketHydrology", "SecondBEST", "BestSoilProperties", "BestSurfaceAlbedo", "BestSurfaceLayer", "BestSurfaceFluxes", "BestSubsurfaceTransport", "get_grid", "get_default_state", "UpdateFrequencyWrapper", "IntermittentShortwave", "IntermittentLongwave", "AdamsBashforth",
+__all__ = ["RRTMGLongwave", "RRTMGShortwave", "Instellation", "BergerSolarInsolation", "SlabSurface", "DryConvectiveAdjustment", "SimpleBoundaryLayer", "EmanuelConvection", "SimplePhysics", "GrayLongwaveRadiation", "Frierson06LongwaveOpticalDepth", "GridScaleCondensation", "CorkLongwaveRadiation", "CorkShortwaveRadiation", "SeaIce", "LandIce", "BucketHydrology", "SecondBEST", "BestSoilProperties", "BestSurfaceAlbedo", "BestSurfaceLayer", "BestSurfaceFluxes", "BestSubsurfaceTransport", "get_grid", "get_default_state", "UpdateFrequencyWrapper", "IntermittentShortwave", "IntermittentLongwave", "AdamsBashforth",
            "Context", "RRTMGError", "DeviceState", "DeviceQuantity", "DeviceAdamsBashforth", "radiation_step"]

@@ -292,6 +292,27 @@ class CorkLongwave(C.Structure):
                 + [("pressure_scale", _f64)] + [(n, _vp) for n in CORK_LONGWAVE_OUT + CORK_LONGWAVE_DIAG])
 
 
+CORK_SHORTWAVE_CONSTANTS = ("m_h2o", "g", "cpd")
+CORK_SHORTWAVE_CLOUD = ("taucld", "ssacld", "asycld")
+CORK_SHORTWAVE_IN = ("t", "pmid", "pint", "zenith", "albedo", "earth_sun") + CORK_SHORTWAVE_CLOUD + CORK_LONGWAVE_GASES
+CORK_SHORTWAVE_OUT = ("up", "dn", "tend")
+CORK_SHORTWAVE_DIAG = ("hr", "up_band", "dn_band", "tau_band", "hr_band")
+
+
+class CorkSwTableDesc(C.Structure):
+    """mirrors `rrtmg_cork_sw_table_desc` (include/rrtmg_hip.h), field for field"""
+    _fields_ = ([("struct_size", C.c_uint32)] + [(n, _i32) for n in CORK_TABLE_SIZES] + [("k_is_f32", _i32), ("solar_is_f32", _i32)]
+                + [(n, _vp) for n in ("k", "weights", "t_grid", "p_grid_log", "x_grid_log")]
+                + [("x_clip", _f64 * 2)] + [(n, _vp) for n in ("log_cont", "solar_source", "rayleigh")])
+
+
+class CorkShortwave(C.Structure):
+    """mirrors `rrtmg_cork_shortwave` (include/rrtmg_hip.h), field for field"""
+    _fields_ = ([("struct_size", C.c_uint32), ("ncol", _i32), ("nlay", _i32), ("memspace", _i32), ("gas_rule", _i32), ("max_chunk_cols", _i32), ("table", _vp)]
+                + [(n, _vp) for n in CORK_SHORTWAVE_IN] + [("gas_scale", _f64 * CORK_MAX_GAS)] + [(n, _f64) for n in CORK_SHORTWAVE_CONSTANTS]
+                + [("pressure_scale", _f64)] + [(n, _vp) for n in CORK_SHORTWAVE_OUT + CORK_SHORTWAVE_DIAG])
+
+
 SURFACE_ICE_FLUXES = ("sw_down", "lw_down", "sw_up", "lw_up", "lh", "sh")
 SURFACE_ICE_CONSTANTS = ("rho_ice", "rho_snow", "c_ice", "c_snow", "k_ice", "k_snow", "lf", "t_melt", "eps", "max_height", "albedo_snow", "albedo_ice", "albedo_melt")
 SURFACE_ICE_IN = ("t", "height", "thick", "snow", "base") + SURFACE_ICE_FLUXES + ("area_type",)
@@ -381,6 +402,10 @@ COLUMN_ARRAYS = {
     "cork_longwave": _column_arrays(CorkLongwave, CORK_LONGWAVE_IN, CORK_LONGWAVE_DIAG, optional=("taucld",) + CORK_LONGWAVE_GASES, host_axes=dict(taucld=(1, 2, 0)),
                                     levels=("pint", "up", "dn"), columns=("tsfc",), band_columns=("emis",), band_levels=("up_band", "dn_band"),
                                     band_layers=("taucld", "tau_band", "trans_band", "hr_band")),
+    # (the correlated-k shortwave: likewise; the three cloud arrays are the caller's [nlay][ncol][nband])
+    "cork_shortwave": _column_arrays(CorkShortwave, CORK_SHORTWAVE_IN, CORK_SHORTWAVE_DIAG, optional=CORK_SHORTWAVE_CLOUD + CORK_LONGWAVE_GASES,
+                                     host_axes={n: (1, 2, 0) for n in CORK_SHORTWAVE_CLOUD}, levels=("pint", "up", "dn"), columns=("zenith", "albedo", "earth_sun"),
+                                     band_levels=("up_band", "dn_band"), band_layers=CORK_SHORTWAVE_CLOUD + ("tau_band", "hr_band")),
     # (the snow/ice column: nlay counts the ice interface levels, so there are no levels; an int32 input)
     "surface_ice": _column_arrays(SurfaceIce, SURFACE_ICE_IN, SURFACE_ICE_DIAG, int32=("area_type", "flags"),
                                   in_place=(("t_out", "t"), ("height_out", "height"), ("thick_out", "thick"), ("snow_out", "snow"), ("base_flux_out", "base")),
@@ -472,6 +497,8 @@ def load_library():
     if hasattr(lib, "rrtmg_hip_cork_table_create"):         # (likewise: the tables of the correlated-k longwave)
         lib.rrtmg_hip_cork_table_create.argtypes = [_vp, C.POINTER(CorkTableDesc), C.POINTER(_vp)]
         lib.rrtmg_hip_cork_table_destroy.argtypes = [_vp, _vp]
+    if hasattr(lib, "rrtmg_hip_cork_sw_table_create"):      # (likewise: the tables of the correlated-k shortwave)
+        lib.rrtmg_hip_cork_sw_table_create.argtypes = [_vp, C.POINTER(CorkSwTableDesc), C.POINTER(_vp)]
     lib.rrtmg_hip_copy_blocks.argtypes =[_vp, C.c_int, _vp, C.c_long, C.c_long, _vp, _vp, _vp]
     lib.rrtmg_hip_mcica_mask.argtypes = [_vp] + [C.c_int] * 6 + [_vp] * 3
     _lib = lib
@@ -1024,38 +1051,49 @@ class Context:
         in the reference's layout (ngas, nband, ngpt, nT, nP[, nX[, nC]]); the other arrays are taken as float64.  The shapes
         are checked against k's here and the grids by the library, before anything is uploaded."""
         self._need_cork_longwave()
+        sized = lambda *axes: lambda n: tuple(n[a] for a in axes)
+        return self._cork_table(CorkTableDesc, "rrtmg_hip_cork_table_create", "cork table", {5: "5 (T, p)", 6: "6 (+ H2O)", 7: "7 (+ CO2)"}, k, [
+            ("weights", "gpoint_weights", weights, sized("nband", "ngpt"), True), ("planck", "planck_fraction", planck, sized("nband", "ngpt", "nT"), True),
+            ("t_grid", "temperature_grid", t_grid, sized("nT"), True), ("p_grid_log", "pressure_grid_log", p_grid_log, sized("nP"), True),
+            ("x_grid_log", "h2o_vmr_grid", x_grid_log, sized("nX"), "nX"), ("c_grid_log", "co2_vmr_grid", c_grid_log, sized("nC"), "nC"),
+            ("log_cont", "continuum_kappa", log_cont, sized("nband", "nT", "nP", "nX"), False)], dict(x_clip=x_clip, c_clip=c_clip))
+
+    def _cork_table(self, desc_type, entry, label, ranks, k, arrays, clips, keep_type=()):
+        """The array side of both table uploads -> the handle.  `ranks`: {rank of k: how the message names it}; `arrays`: (member of
+        the description, the table's name for it, the array or None, sizes -> shape, needed: True, False (optional) or the size
+        that asks for it); `keep_type`: the members kept float32 where they come so (every other array is taken as float64).
+        The shapes are checked against k's here and the grids by the library, before anything is uploaded."""
         k = np.ascontiguousarray(k)
         if k.dtype not in (np.float32, np.float64):
             k = k.astype(np.float64)
-        if k.ndim not in (5, 6, 7):
-            raise ValueError("cork table: k_coefficients has rank %d, not 5 (T, p), 6 (+ H2O) or 7 (+ CO2)" % k.ndim)
-        ngas, nband, ngpt, nT, nP = k.shape[:5]
-        nX, nC = (k.shape[5] if k.ndim >= 6 else 0), (k.shape[6] if k.ndim == 7 else 0)
-        f = lambda x: None if x is None else np.ascontiguousarray(x, dtype=np.float64)
-        weights, planck, t_grid, p_grid_log, x_grid_log, c_grid_log, log_cont = (f(x) for x in (weights, planck, t_grid, p_grid_log, x_grid_log, c_grid_log, log_cont))
-        want = dict(gpoint_weights=(weights, (nband, ngpt)), planck_fraction=(planck, (nband, ngpt, nT)), temperature_grid=(t_grid, (nT,)),
-                    pressure_grid_log=(p_grid_log, (nP,)))
-        if nX:
-            want["h2o_vmr_grid"] = (x_grid_log, (nX,))
-        if nC:
-            want["co2_vmr_grid"] = (c_grid_log, (nC,))
-        if log_cont is not None:
-            want["continuum_kappa"] = (log_cont, (nband, nT, nP, nX))
-        for name, (x, shape) in want.items():
-            if x is None or x.shape != shape:
-                raise ValueError("cork table: %s is %s, k_coefficients %s wants %s" % (name, "missing" if x is None else x.shape, k.shape, shape))
-        d = CorkTableDesc()
-        d.struct_size, d.k_is_f32 = C.sizeof(CorkTableDesc), 1 if k.dtype == np.float32 else 0
-        for n, v in zip(CORK_TABLE_SIZES, (ngas, nband, ngpt, nT, nP, nX, nC)):
-            setattr(d, n, int(v))
-        keep = dict(k=k, weights=weights, planck=planck, t_grid=t_grid, p_grid_log=p_grid_log, x_grid_log=x_grid_log, c_grid_log=c_grid_log, log_cont=log_cont)
-        for n, x in keep.items():
-            setattr(d, n, None if x is None else x.ctypes.data)
-        for n, clip in (("x_clip", x_clip), ("c_clip", c_clip)):
+        if k.ndim not in ranks:
+            names = list(ranks.values())
+            raise ValueError("%s: k_coefficients has rank %d, not %s" % (label, k.ndim, " or ".join([", ".join(names[:-1]), names[-1]])))
+        n = dict(zip(CORK_TABLE_SIZES, tuple(k.shape) + (0,) * (7 - k.ndim)))
+        d = desc_type()
+        d.struct_size, d.k_is_f32, d.k = C.sizeof(desc_type), 1 if k.dtype == np.float32 else 0, k.ctypes.data
+        for name, v in n.items():
+            setattr(d, name, int(v))
+        keep = [k]
+        for member, name, x, shape, needed in arrays:
+            if x is not None:
+                x = np.ascontiguousarray(x)
+                if not (member in keep_type and x.dtype == np.float32):
+                    x = np.ascontiguousarray(x, dtype=np.float64)
+            if isinstance(needed, str):
+                needed = n[needed] > 0
+                x = x if needed else None      # (an axis k does not have: its grid is not read)
+            if (x is None and needed) or (x is not None and x.shape != shape(n)):
+                raise ValueError("%s: %s is %s, k_coefficients %s wants %s" % (label, name, "missing" if x is None else x.shape, k.shape, shape(n)))
+            keep.append(x)
+            setattr(d, member, None if x is None else x.ctypes.data)
+            if member in keep_type:
+                setattr(d, keep_type[member], 1 if x.dtype == np.float32 else 0)
+        for name, clip in clips.items():
             if clip is not None:
-                getattr(d, n)[0], getattr(d, n)[1] = float(clip[0]), float(clip[1])
+                getattr(d, name)[0], getattr(d, name)[1] = float(clip[0]), float(clip[1])
         handle = _vp()
-        self._ck(self.lib.rrtmg_hip_cork_table_create(self.h, C.byref(d), C.byref(handle)))
+        self._ck(getattr(self.lib, entry)(self.h, C.byref(d), C.byref(handle)))
         return handle.value
 
     @_locked
@@ -1091,6 +1129,60 @@ class Context:
             given["taucld"] = taucld
         given.update({"gas%d" % i: x for i, x in enumerate(gases) if x is not None})
         outs, diagnostics = self._column_call("cork_longwave", a, given, dict(up=up, dn=dn, tend=tend), diagnostics, memspace, ncol, nlay, nband=int(nband))
+        return outs["up"], outs["dn"], outs["tend"], diagnostics
+
+    @property
+    def has_cork_shortwave(self):
+        """Whether the library exports the table-driven correlated-k shortwave (rrtmg_hip_cork_shortwave; probed by the symbol)."""
+        return hasattr(self.lib, "rrtmg_hip_cork_shortwave") and hasattr(self.lib, "rrtmg_hip_cork_sw_table_create")
+
+    def _need_cork_shortwave(self):
+        if not self.has_cork_shortwave:
+            raise RRTMGError(4, "this librrtmg_hip.so has no rrtmg_hip_cork_shortwave (correlated-k shortwave)")
+
+    @_locked
+    def cork_sw_table_create(self, k, weights, solar_source, t_grid, p_grid_log, x_grid_log=None, x_clip=None, log_cont=None, rayleigh=None):
+        """Upload a correlated-k shortwave table (rrtmg_hip_cork_sw_table_create) -> the handle, owned by this context and freed
+        by cork_table_destroy.  `k` float32 or float64 in the reference's layout (ngas, nband, ngpt, nT, nP[, nX]) -- a rank-7
+        table is refused, the reference's shortwave has no CO2 axis; `solar_source` (nband, ngpt) float32 or float64 -- the type
+        the earth-sun factor is multiplied in; `rayleigh` (nband,) or None; the other arrays are taken as float64."""
+        self._need_cork_shortwave()
+        sized = lambda *axes: lambda n: tuple(n[a] for a in axes)
+        return self._cork_table(CorkSwTableDesc, "rrtmg_hip_cork_sw_table_create", "cork shortwave table", {5: "5 (T, p)", 6: "6 (+ H2O)"}, k, [
+            ("weights", "gpoint_weights", weights, sized("nband", "ngpt"), True), ("solar_source", "solar_source_per_gpoint", solar_source, sized("nband", "ngpt"), True),
+            ("t_grid", "temperature_grid", t_grid, sized("nT"), True), ("p_grid_log", "pressure_grid_log", p_grid_log, sized("nP"), True),
+            ("x_grid_log", "h2o_vmr_grid", x_grid_log, sized("nX"), "nX"), ("log_cont", "continuum_kappa", log_cont, sized("nband", "nT", "nP", "nX"), False),
+            ("rayleigh", "rayleigh_coefficient", rayleigh, sized("nband"), False)], dict(x_clip=x_clip), keep_type={"solar_source": "solar_is_f32"})
+
+    @_locked
+    def cork_shortwave(self, table, nband, t, pmid, pint, zenith, albedo, earth_sun, constants, gas_rule, gases=(), gas_scale=(), cloud=None, up=None, dn=None,
+                       tend=None, diagnostics=True, pressure_scale=1.0, max_chunk_cols=0, memspace=0, ncol=None, nlay=None):
+        """climt's CorkShortwaveRadiation (correlated_k, additive overlap) by column (rrtmg_hip_cork_shortwave) -> (up, dn, tend,
+        diagnostics).  `table`: a handle of cork_sw_table_create, `nband` its bands; `constants`: m_h2o, g, cpd; `gas_rule`,
+        `gases`, `gas_scale` as in cork_longwave.  Host arrays t, pmid [nlay][ncol], pint [nlay+1][ncol], zenith (radians), albedo,
+        earth_sun [ncol] (the FIRST column's factor scales every column, as in the reference), `cloud` None or (taucld, ssacld,
+        asycld), each [nlay][ncol][nband] (outputs are allocated unless given); `diagnostics` True: a dict of hr [nlay][ncol],
+        up_band, dn_band [nband][nlay+1][ncol], tau_band, hr_band [nband][nlay][ncol] (False or None: none; a dict: those it
+        names are written).  `max_chunk_cols`: 0, or the most columns the library runs per chunk of its work space.  Or device
+        pointers (or DeviceArrays) with memspace=1 -- then the three outputs, `ncol` and `nlay`, and `diagnostics` a dict of
+        device pointers or None; a launch per chunk and the band reduction on the main stream."""
+        self._need_cork_shortwave()
+        if len(gases) > CORK_MAX_GAS or len(gas_scale) > CORK_MAX_GAS:
+            raise ValueError("cork_shortwave: at most %d gases" % CORK_MAX_GAS)
+        a = CorkShortwave()
+        a.struct_size, a.memspace, a.gas_rule, a.table = C.sizeof(CorkShortwave), 1 if memspace else 0, int(gas_rule), table
+        a.pressure_scale, a.max_chunk_cols = float(pressure_scale), int(max_chunk_cols)
+        for n in CORK_SHORTWAVE_CONSTANTS:
+            setattr(a, n, float(constants[n]))
+        for i in range(CORK_MAX_GAS):
+            a.gas_scale[i] = float(gas_scale[i]) if i < len(gas_scale) else 1.0
+        given = dict(t=t, pmid=pmid, pint=pint, zenith=zenith, albedo=albedo, earth_sun=earth_sun)
+        if cloud is not None:
+            if len(cloud) != 3:
+                raise ValueError("cork_shortwave: cloud is (taucld, ssacld, asycld)")
+            given.update({n: x for n, x in zip(CORK_SHORTWAVE_CLOUD, cloud) if x is not None})
+        given.update({"gas%d" % i: x for i, x in enumerate(gases) if x is not None})
+        outs, diagnostics = self._column_call("cork_shortwave", a, given, dict(up=up, dn=dn, tend=tend), diagnostics, memspace, ncol, nlay, nband=int(nband))
         return outs["up"], outs["dn"], outs["tend"], diagnostics
 
     @property

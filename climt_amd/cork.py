@@ -8,6 +8,9 @@ band-grey continuum; the three gas-amount rules; per-band cloud depth and emissi
 of diagnostics_level 0.  Not built, and refused with NotImplementedError: optics="parmentier", ESFT overlap of more than one
 gas, diagnostics_level >= 1.
 
+CorkShortwaveRadiation (below) is the shortwave half of the same scheme, on rrtmg_hip_cork_shortwave: the same gas optical depth,
+Rayleigh scattering, cloud mixing, delta-Eddington scaling and the two-stream adding method per g-point.
+
 `table` is a path to an .npz, a mapping of arrays, a path to an .nc (where scipy imports), or a bare name, which is looked up in
 an importable climt's shipped tables."""
 import os
@@ -15,7 +18,7 @@ import os
 import numpy as np
 
 from ._sympl_compat import TendencyComponent, get_constant
-from .initialization import set_num_longwave_bands
+from .initialization import set_num_longwave_bands, set_num_shortwave_bands
 from .rrtmg.common import make_context
 
 DIFFUSIVITY_FACTOR = 1.66
@@ -86,12 +89,22 @@ class KTable(object):
     grids as log(max(grid, 1e-30)) with the grid's own ends as the clip interval, the continuum as log(max(kappa, 1e-40)), every
     grid in float64.  k stays in the file's element type (float32 or float64): the promotion to double is exact."""
 
-    def __init__(self, table):
+    def __init__(self, table, kind="longwave"):
+        """kind "longwave": planck_fraction is required.  kind "shortwave": solar_source_per_gpoint is required (kept in the
+        file's element type, float32 or float64: the earth-sun factor is multiplied in it), rayleigh_coefficient is optional,
+        planck_fraction is not read, and a table of rank 7 is refused."""
+        if kind not in ("longwave", "shortwave"):
+            raise ValueError("KTable: kind is 'longwave' or 'shortwave', not %r" % (kind,))
+        self.kind = kind
         t = self.arrays = load_k_table(table)
-        for name in ("k_coefficients", "gpoint_weights", "temperature_grid", "pressure_grid_log", "planck_fraction", "gas_names"):
+        source = "planck_fraction" if kind == "longwave" else "solar_source_per_gpoint"
+        for name in ("k_coefficients", "gpoint_weights", "temperature_grid", "pressure_grid_log", source, "gas_names"):
             if name not in t:
                 raise ValueError("cork table: %s is missing" % name)
         k = np.asarray(t["k_coefficients"])
+        if kind == "shortwave" and k.ndim == 7:
+            raise ValueError("cork shortwave table: k_coefficients has rank 7 (a CO2 axis); the reference's shortwave passes no CO2 mole fraction "
+                             "and fails on such a table at the first call: ranks 5 (T, p) and 6 (+ H2O) only")
         if k.ndim not in (5, 6, 7):
             raise ValueError("cork table: k_coefficients has rank %d, not 5 (T, p), 6 (+ H2O) or 7 (+ CO2)" % k.ndim)
         self.k = np.ascontiguousarray(k if k.dtype in (np.float32, np.float64) else k.astype(np.float64))
@@ -109,9 +122,19 @@ class KTable(object):
             raise ValueError("cork table: %d bands, %d g-points and %d gases; the device path takes at most %d, %d and %d" % (
                 self.nband, self.ngpt, self.ngas, MAX_BANDS, MAX_GPOINTS, MAX_GASES))
         f64 = lambda name: np.ascontiguousarray(t[name], dtype=np.float64)
-        self.weights, self.planck, self.t_grid, self.p_grid_log = f64("gpoint_weights"), f64("planck_fraction"), f64("temperature_grid"), f64("pressure_grid_log")
-        shapes = [("gpoint_weights", self.weights, (self.nband, self.ngpt)), ("planck_fraction", self.planck, (self.nband, self.ngpt, nT)),
-                  ("temperature_grid", self.t_grid, (nT,)), ("pressure_grid_log", self.p_grid_log, (nP,))]
+        self.weights, self.t_grid, self.p_grid_log = f64("gpoint_weights"), f64("temperature_grid"), f64("pressure_grid_log")
+        shapes = [("gpoint_weights", self.weights, (self.nband, self.ngpt)), ("temperature_grid", self.t_grid, (nT,)), ("pressure_grid_log", self.p_grid_log, (nP,))]
+        self.planck = self.solar_source = self.rayleigh = None
+        if kind == "longwave":
+            self.planck = f64("planck_fraction")
+            shapes.append(("planck_fraction", self.planck, (self.nband, self.ngpt, nT)))
+        else:
+            solar = np.asarray(t["solar_source_per_gpoint"])
+            self.solar_source = np.ascontiguousarray(solar if solar.dtype in (np.float32, np.float64) else solar.astype(np.float64))
+            shapes.append(("solar_source_per_gpoint", self.solar_source, (self.nband, self.ngpt)))
+            if "rayleigh_coefficient" in t:
+                self.rayleigh = f64("rayleigh_coefficient")
+                shapes.append(("rayleigh_coefficient", self.rayleigh, (self.nband,)))
         self.x_grid_log = self.c_grid_log = self.x_clip = self.c_clip = self.log_cont = None
         if nX:
             x = f64("h2o_vmr_grid")
@@ -144,6 +167,9 @@ class KTable(object):
         self.gas_scale = [1.0 if g == "h2o" or self.gas_rule != 2 else MOLAR_MASS.get(g, MOLAR_MASS_DRY_AIR) / MOLAR_MASS_DRY_AIR for g in self.gas_names]
 
     def upload(self, ctx):
+        if self.kind == "shortwave":
+            return ctx.cork_sw_table_create(self.k, self.weights, self.solar_source, self.t_grid, self.p_grid_log, x_grid_log=self.x_grid_log, x_clip=self.x_clip,
+                                            log_cont=self.log_cont, rayleigh=self.rayleigh)
         return ctx.cork_table_create(self.k, self.weights, self.planck, self.t_grid, self.p_grid_log, x_grid_log=self.x_grid_log, x_clip=self.x_clip,
                                      c_grid_log=self.c_grid_log, c_clip=self.c_clip, log_cont=self.log_cont)
 
@@ -290,4 +316,137 @@ class CorkLongwaveRadiation(TendencyComponent):
             "upwelling_longwave_flux_in_air_per_band": last(d["up_band"], p_int.shape), "downwelling_longwave_flux_in_air_per_band": last(d["dn_band"], p_int.shape),
             "air_temperature_tendency_from_longwave": d["hr"].reshape(t.shape), "longwave_optical_depth_per_band": last(d["tau_band"], t.shape),
             "longwave_transmittance_per_band": last(d["trans_band"], t.shape), "air_temperature_tendency_from_longwave_per_band": last(d["hr_band"], t.shape)}
+        return {"air_temperature": tend.reshape(t.shape)}, diagnostics
+
+
+class CorkShortwaveRadiation(TendencyComponent):
+    """The correlated-k two-stream shortwave of climt's cork scheme (climt/_components/cork/sw/component.py with
+    optics="correlated_k"): the gas optical depth as in CorkLongwaveRadiation, Rayleigh scattering where the table has a
+    coefficient, the cloud mixed in by band, delta-Eddington scaling, the Meador-Weaver / PIFM layer operator and the
+    Shonk-Hogan adding method per g-point, on the GPU through rrtmg_hip_cork_shortwave (include/rrtmg_hip.h; the rules:
+    climt_amd/csrc/rrtmg_cork_sw.h).  Same keywords, defaults and property dictionaries as the reference's.
+
+    Not built, and refused with NotImplementedError: optics="parmentier", ESFT overlap of more than one gas,
+    diagnostics_level >= 1.  A table of rank 7 is refused with ValueError: the reference fails on it at the first call.
+    As in the reference, flux_adjustment_for_earth_sun_distance of the FIRST column scales every column, and
+    surface_temperature is stated as an input although it is not read."""
+
+    def __init__(self, optics="parmentier", table=None, coefficients="solar_composition", stellar_spectrum="sun", rosseland_mean_fit="freedman2014",
+                 device=0, context=None, **kwargs):
+        """
+        Args: the reference's, plus `device`, `context` like the other components of this package.  Only optics="correlated_k"
+        is built; `coefficients`, `stellar_spectrum` and `rosseland_mean_fit` belong to the Parmentier optics and are not read;
+        `bond_albedo_feedback` (a keyword of **kwargs, as in the reference) likewise.
+        """
+        self._optics_mode = optics
+        if optics == "parmentier":
+            raise NotImplementedError("CorkShortwaveRadiation: optics='parmentier' (the picket-fence optics) is not built on the device; use optics='correlated_k'")
+        if optics != "correlated_k":
+            raise ValueError("Unknown optics mode: %s" % optics)
+        if table is None:
+            raise ValueError("CorkShortwaveRadiation(optics='correlated_k') needs table=")
+        self._ktable = KTable(table, kind="shortwave")
+        if self._ktable.overlap == "esft" and self._ktable.ngas > 1:
+            raise NotImplementedError("CorkShortwaveRadiation: overlap_method 'esft' with more than one gas (the outer product of g-points) is not built; additive overlap is")
+        self._num_bands, self._num_gpts = self._ktable.nband, self._ktable.ngpt
+        self._gas_names = list(self._ktable.gas_names)
+        self._has_co2_axis = False
+        self._fully_premixed, self._premixed_bg = self._ktable.fully_premixed, self._ktable.premixed_bg
+        self._bond_albedo_feedback = kwargs.pop("bond_albedo_feedback", False)
+        self._diagnostics_level = kwargs.pop("diagnostics_level", 0)
+        if self._diagnostics_level >= 1:
+            raise NotImplementedError("CorkShortwaveRadiation: diagnostics_level >= 1 (layer operators and beam profiles by g-point) is not built: "
+                                      "the device path keeps nothing with a g-point axis")
+        set_num_shortwave_bands(self._num_bands)
+        super(CorkShortwaveRadiation, self).__init__(**kwargs)
+        self._device = device
+        if context is not None:
+            self._ctx = context
+        self._handle = None
+
+    # the context made at first use, what is pickled, the resident table and the gas inputs: the longwave component's
+    __getattr__ = CorkLongwaveRadiation.__getattr__
+    __getstate__ = CorkLongwaveRadiation.__getstate__
+    table_handle = CorkLongwaveRadiation.table_handle
+    gas_inputs = CorkLongwaveRadiation.gas_inputs
+
+    @property
+    def input_properties(self):
+        props = {
+            "air_temperature": {"dims": ["mid_levels", "*"], "units": "degK", "alias": "T"},
+            "air_pressure": {"dims": ["mid_levels", "*"], "units": "Pa", "alias": "p"},
+            "air_pressure_on_interface_levels": {"dims": ["interface_levels", "*"], "units": "Pa", "alias": "p_int"},
+            "surface_temperature": {"dims": ["*"], "units": "degK", "alias": "T_surf"},
+            "zenith_angle": {"dims": ["*"], "units": "radians", "alias": "zenith"},
+            "surface_albedo_for_direct_shortwave": {"dims": ["*"], "units": "dimensionless", "alias": "albedo"},
+            "flux_adjustment_for_earth_sun_distance": {"dims": ["*"], "units": "dimensionless", "alias": "earth_sun_factor"},
+        }
+        if self._premixed_bg:
+            props["specific_humidity"] = {"dims": ["mid_levels", "*"], "units": "kg/kg", "alias": "h2o"}
+        elif not self._fully_premixed:
+            for gas in self._gas_names:
+                props[_GAS_CF_NAME.get(gas, "mole_fraction_of_%s_in_air" % gas)] = {"dims": ["mid_levels", "*"], "units": _GAS_UNITS.get(gas, "mole/mole"), "alias": gas}
+        band = {"dims": ["mid_levels", "*", "num_shortwave_bands"], "units": "dimensionless"}
+        props["shortwave_optical_thickness_due_to_cloud"] = dict(band, alias="tau_cloud_sw")
+        props["single_scattering_albedo_due_to_cloud"] = dict(band, alias="ssa_cloud")
+        props["cloud_asymmetry_parameter"] = dict(band, alias="g_cloud")
+        return props
+
+    @property
+    def tendency_properties(self):
+        return {"air_temperature": {"units": "degK s^-1"}}
+
+    @property
+    def diagnostic_properties(self):
+        il, ml = ["interface_levels", "*"], ["mid_levels", "*"]
+        band = ["num_shortwave_bands"]
+        return {
+            "upwelling_shortwave_flux_in_air": {"dims": il, "units": "W m^-2"},
+            "downwelling_shortwave_flux_in_air": {"dims": list(il), "units": "W m^-2"},
+            "upwelling_shortwave_flux_in_air_per_band": {"dims": il + band, "units": "W m^-2"},
+            "downwelling_shortwave_flux_in_air_per_band": {"dims": il + band, "units": "W m^-2"},
+            "air_temperature_tendency_from_shortwave": {"dims": ml, "units": "degK day^-1"},
+            "shortwave_optical_depth_per_band": {"dims": ml + band, "units": "dimensionless"},
+            "air_temperature_tendency_from_shortwave_per_band": {"dims": ml + band, "units": "degK day^-1"},
+        }
+
+    @property
+    def num_shortwave_bands(self):
+        return self._num_bands
+
+    def constants(self):
+        """The constants of the reference's array_call as the library takes them."""
+        return dict(m_h2o=MOLAR_MASS["h2o"] / MOLAR_MASS_DRY_AIR, g=get_constant("gravitational_acceleration", "m/s^2"),
+                    cpd=get_constant("heat_capacity_of_dry_air_at_constant_pressure", "J/kg/K"))
+
+    def __call__(self, state, *args, **kwargs):
+        """A host state goes through sympl's machinery to array_call; a climt_amd.DeviceState (state resident in HBM) takes the
+        device path (climt_amd/device_state.py)."""
+        from .device_state import DeviceState, cork_shortwave_device_call
+        if isinstance(state, DeviceState):
+            return cork_shortwave_device_call(self, state)
+        return super(CorkShortwaveRadiation, self).__call__(state, *args, **kwargs)
+
+    def array_call(self, state):
+        P = self.input_properties
+
+        def get(name):      # (sympl hands an input with an alias over under it)
+            alias = P[name].get("alias", name)
+            return np.asarray(state[alias] if alias in state else state[name], dtype=np.float64)
+        t, p_int = get("air_temperature"), get("air_pressure_on_interface_levels")
+        nlay, nband = t.shape[0], self._num_bands
+        levels = lambda x: np.reshape(x, (x.shape[0], -1))
+        column = lambda name: np.reshape(get(name), (-1,))
+        gases = [None if n is None else levels(get(n)) for n in self.gas_inputs()]
+        cloud = tuple(np.reshape(get(n), (nlay, -1, nband)) for n in
+                      ("shortwave_optical_thickness_due_to_cloud", "single_scattering_albedo_due_to_cloud", "cloud_asymmetry_parameter"))
+        up, dn, tend, d = self._ctx.cork_shortwave(
+            self.table_handle(), nband, levels(t), levels(get("air_pressure")), levels(p_int), column("zenith_angle"), column("surface_albedo_for_direct_shortwave"),
+            column("flux_adjustment_for_earth_sun_distance"), self.constants(), self._ktable.gas_rule, gases=gases, gas_scale=self._ktable.gas_scale, cloud=cloud)
+        last = lambda x, shape: np.moveaxis(x, 0, -1).reshape(tuple(shape) + (nband,))      # [band][k][col] -> (k, *horizontal, band)
+        diagnostics = {
+            "upwelling_shortwave_flux_in_air": up.reshape(p_int.shape), "downwelling_shortwave_flux_in_air": dn.reshape(p_int.shape),
+            "upwelling_shortwave_flux_in_air_per_band": last(d["up_band"], p_int.shape), "downwelling_shortwave_flux_in_air_per_band": last(d["dn_band"], p_int.shape),
+            "air_temperature_tendency_from_shortwave": d["hr"].reshape(t.shape), "shortwave_optical_depth_per_band": last(d["tau_band"], t.shape),
+            "air_temperature_tendency_from_shortwave_per_band": last(d["hr_band"], t.shape)}
         return {"air_temperature": tend.reshape(t.shape)}, diagnostics

@@ -1,6 +1,6 @@
-// rrtmg_column_call.h -- ONE staging and launch path for the column components (host code only), eleven entries: dry adjustment,
+// rrtmg_column_call.h -- ONE staging and launch path for the column components (host code only), twelve entries: dry adjustment,
 // boundary layer, Emanuel convection, simple physics; Frierson optical depth, gray longwave, grid-scale condensation; the snow/ice
-// column; BucketHydrology and SecondBEST; the correlated-k longwave.  Each .hip file holds a table per entry, a row per array of its
+// column; BucketHydrology and SecondBEST; the correlated-k longwave and shortwave.  Each .hip file holds a table per entry, a row per array of its
 // public struct (include/rrtmg_hip.h).
 // A row states once: the member of the public struct and its name in messages, the member of the kernel's call struct, the
 // extent, and -- read off the member's own type -- the element type (double or int32) and the direction (const: an input);

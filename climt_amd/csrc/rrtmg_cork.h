@@ -28,6 +28,8 @@
 // The table is read in the layout rrtmg_cork.hip gives it on the device: the g-points of one corner lie side by side,
 //   k [ngas][nband][nT][nP][nX'][nC'][ngpt] (nX' = max(nX, 1), nC' likewise), planck [nband][nT][ngpt].
 //
+// The gas optical depth (brackets, amounts, k, continuum: cork_gas_depth) is what the shortwave of the same scheme runs too
+// (rrtmg_cork_sw.h): one function, templated on the call struct.
 // Plain C++: tools/cork_check.cpp runs every "thread" of a launch on the CPU; the kernels are in rrtmg_cork.hip.
 #pragma once
 #include <cmath>
@@ -71,11 +73,14 @@ struct CorkLongwaveCall {
   double *tau_band, *trans_band, *hr_band;   // [nband][nlay][ncol] or nullptr
 };
 
-RRTMG_CORK_HD const double *cork_gas(const CorkLongwaveCall &a, int ig) {
+// (Call: CorkLongwaveCall, or the shortwave's call struct of rrtmg_cork_sw.h, which names the same members)
+template <class Call>
+RRTMG_CORK_HD const double *cork_gas(const Call &a, int ig) {
   return ig == 0 ? a.gas0 : ig == 1 ? a.gas1 : ig == 2 ? a.gas2 : ig == 3 ? a.gas3 : ig == 4 ? a.gas4 : ig == 5 ? a.gas5 : ig == 6 ? a.gas6 : a.gas7;
 }
 // (chains of selects, not indexed loads: a kernel's by-value argument that is indexed dynamically is copied to scratch)
-RRTMG_CORK_HD double cork_gas_scale(const CorkLongwaveCall &a, int ig) {
+template <class Call>
+RRTMG_CORK_HD double cork_gas_scale(const Call &a, int ig) {
   return ig == 0 ? a.gas_scale[0] : ig == 1 ? a.gas_scale[1] : ig == 2 ? a.gas_scale[2] : ig == 3 ? a.gas_scale[3] : ig == 4 ? a.gas_scale[4]
        : ig == 5 ? a.gas_scale[5] : ig == 6 ? a.gas_scale[6] : a.gas_scale[7];
 }
@@ -152,9 +157,10 @@ RRTMG_CORK_HD double cork_txx(const K *p, long sT, long sP, long sX, double fT, 
   return x0 * (1.0 - fX) + x1 * fX;
 }
 
-// ---- one layer of one band: the optical depth and the Planck source of every g-point ---------------------------------------------------
-template <int NG, class K>
-RRTMG_CORK_HD void cork_layer(const CorkLongwaveCall &a, long col, int b, int k, double (&tau)[NG], double (&src)[NG]) {
+// ---- one layer of one band: the gas optical depth of every g-point (k summed over the gases from 0.0, the continuum behind it), and
+// the bracket of T.  Both spectra call it: the longwave's cork_layer below, the shortwave's passes in rrtmg_cork_sw.h -------------------
+template <int NG, class K, class Call>
+RRTMG_CORK_HD void cork_gas_depth(const Call &a, long col, int b, int k, double (&acc)[NG], int &iT, double &fT) {
 #pragma clang fp contract(off)
   const CorkTableView &tb = a.tab;
   const K *ktab = (const K *)tb.k;
@@ -162,8 +168,8 @@ RRTMG_CORK_HD void cork_layer(const CorkLongwaveCall &a, long col, int b, int k,
   const int ngpt = tb.ngpt;
   const double T = a.t[o];
   const double p = a.pmid[o] * a.pressure_scale;
-  int iT, iP, iX = 0, iC = 0;
-  double fT, fP, fX = 0.0, fC = 0.0;
+  int iP, iX = 0, iC = 0;
+  double fP, fX = 0.0, fC = 0.0;
   cork_bracket(tb.t_grid, tb.nT, T, iT, fT);
   cork_bracket(tb.p_grid, tb.nP, log(p > 1.0 ? p : 1.0), iP, fP);
   if (tb.nX > 0) {
@@ -184,7 +190,6 @@ RRTMG_CORK_HD void cork_layer(const CorkLongwaveCall &a, long col, int b, int k,
   const long nX1 = tb.nX > 0 ? tb.nX : 1, nC1 = tb.nC > 0 ? tb.nC : 1;
   const long sC = ngpt, sX = sC * nC1, sP = sX * nX1, sT = sP * tb.nP, sB = sT * tb.nT, sG = sB * tb.nband;
 
-  double acc[NG];
 #pragma unroll
   for (int g = 0; g < NG; ++g) acc[g] = 0.0;
   double amount0 = 0.0;
@@ -214,11 +219,29 @@ RRTMG_CORK_HD void cork_layer(const CorkLongwaveCall &a, long col, int b, int k,
       acc[g] += kv * amount;
     }
   }
-  double cont = 0.0;
   if (tb.has_cont) {
     const long cX = 1, cP = tb.nX, cT = cP * tb.nP, cB = cT * tb.nT;
-    cont = cork_exp(cork_txx(tb.log_cont + b * cB + iT * cT + iP * cP + iX * cX, cT, cP, cX, fT, fP, fX)) * amount0;
+    const double cont = cork_exp(cork_txx(tb.log_cont + b * cB + iT * cT + iP * cP + iX * cX, cT, cP, cX, fT, fP, fX)) * amount0;
+#pragma unroll
+    for (int g = 0; g < NG; ++g) {
+      if (g >= ngpt) continue;
+      acc[g] += cont;
+    }
   }
+}
+
+// ---- one layer of one band: the optical depth and the Planck source of every g-point ---------------------------------------------------
+template <int NG, class K>
+RRTMG_CORK_HD void cork_layer(const CorkLongwaveCall &a, long col, int b, int k, double (&tau)[NG], double (&src)[NG]) {
+#pragma clang fp contract(off)
+  const CorkTableView &tb = a.tab;
+  const long N = a.ncol, o = (long)k * N + col;
+  const int ngpt = tb.ngpt;
+  const double T = a.t[o];
+  int iT;
+  double fT;
+  double acc[NG];
+  cork_gas_depth<NG, K>(a, col, b, k, acc, iT, fT);
   const double cloud = a.taucld ? a.taucld[o * tb.nband + b] : 0.0;
   const double planck = a.sigma_sb * cork_pow4(T);
   const double *pf = tb.planck + ((long)b * tb.nT + iT) * ngpt;
@@ -226,7 +249,6 @@ RRTMG_CORK_HD void cork_layer(const CorkLongwaveCall &a, long col, int b, int k,
   for (int g = 0; g < NG; ++g) {
     if (g >= ngpt) continue;
     double t = acc[g];
-    if (tb.has_cont) t += cont;
     if (a.taucld) t = t + cloud;
     tau[g] = t;
     src[g] = (pf[g] * (1.0 - fT) + pf[ngpt + g] * fT) * planck;

@@ -746,6 +746,61 @@ def cork_longwave_device_call(self, ds):
         "longwave_transmittance_per_band": trb, "air_temperature_tendency_from_longwave_per_band": hb}
 
 
+def cork_shortwave_device_call(self, ds):
+    """CorkShortwaveRadiation on a DeviceState: rrtmg_hip_cork_shortwave with device pointers on the main stream and the
+    component's table resident on the state's context.  The two pressures are read as they are resident, in one unit (Pa or any
+    other: the library brings them to Pa); the zenith angle, the albedo and the earth-sun factor [*] (the factor of the first
+    column scales every column, formed on the device: nothing comes to the host), the gases and the three cloud arrays
+    [mid_levels][*][num_shortwave_bands] as the component's properties state them.  The fluxes, the tendency and the diagnostics
+    go to two alternating sets of work buffers and stay in HBM; the per-band ones are [num_shortwave_bands][levels][*].
+    A DeviceState keeps a quantity in the units of the FIRST component of from_host's list that asks for it: beside a component
+    that takes one unit only (RRTMG's: mbar), list that one before this one -- this call reads the pressures in whatever one unit
+    it finds, the other would refuse Pa (examples/radiative_convective.py orders its list so).
+    -> (tendencies, diagnostics) as DeviceQuantity."""
+    P = self.input_properties
+    t = ds.need("air_temperature", P["air_temperature"])
+    nlay, ncol = t.shape
+    nband = self.num_shortwave_bands
+    p, pi = ds.get("air_pressure"), ds.get("air_pressure_on_interface_levels")
+    for n, x, dims in (("air_pressure", p, ("mid_levels", "*")), ("air_pressure_on_interface_levels", pi, ("interface_levels", "*"))):
+        if x is None:
+            raise KeyError("device state is missing input quantity %r" % n)
+        if tuple(x.dims) != dims:
+            raise ValueError("quantity %r is resident as %s, the correlated-k shortwave wants %s" % (n, x.dims, dims))
+    if _to_pa(p.units) != _to_pa(pi.units):
+        raise ValueError("air_pressure is resident in %r and air_pressure_on_interface_levels in %r: the correlated-k shortwave wants one unit" % (p.units, pi.units))
+    columns = [ds.need(n, P[n]) for n in ("zenith_angle", "surface_albedo_for_direct_shortwave", "flux_adjustment_for_earth_sun_distance")]
+    cloud = [ds.need(n, P[n]) for n in ("shortwave_optical_thickness_due_to_cloud", "single_scattering_albedo_due_to_cloud", "cloud_asymmetry_parameter")]
+    gases = [None if n is None else ds.need(n, P[n]) for n in self.gas_inputs()]
+    if (p.shape != (nlay, ncol) or pi.shape != (nlay + 1, ncol) or any(x.shape != (ncol,) for x in columns) or any(x.shape != (nlay, ncol, nband) for x in cloud)
+            or any(g is not None and g.shape != (nlay, ncol) for g in gases)):
+        raise ValueError("temperature %s, pressures %s, %s, zenith, albedo and earth-sun factor %s, cloud arrays %s and gases %s do not belong to one grid of %d bands" % (
+            t.shape, p.shape, pi.shape, [x.shape for x in columns], [x.shape for x in cloud], [None if g is None else g.shape for g in gases], nband))
+    if ds.ctx is not self._ctx:      # the table lives on the context that runs the call
+        if getattr(self, "_handle_ctx", None) is not ds.ctx:
+            self._handle_ds, self._handle_ctx = self._ktable.upload(ds.ctx), ds.ctx
+        handle = self._handle_ds
+    else:
+        handle = self.table_handle()
+    self._device_calls = getattr(self, "_device_calls", 0) + 1
+    w = lambda key, shape, dims, units: ds.work(("cork_sw", id(self), key, self._device_calls & 1), shape, dims, units)
+    il, ml = ("interface_levels", "*"), ("mid_levels", "*")
+    up, dn = (w(k, (nlay + 1, ncol), il, "W m^-2") for k in ("up", "dn"))
+    tend, hr = w("tend", (nlay, ncol), ml, "degK s^-1"), w("hr", (nlay, ncol), ml, "degK day^-1")
+    band = ("num_shortwave_bands",)
+    ub, db = (w(k, (nband, nlay + 1, ncol), band + il, "W m^-2") for k in ("up_band", "dn_band"))
+    tb = w("tau_band", (nband, nlay, ncol), band + ml, "dimensionless")
+    hb = w("hr_band", (nband, nlay, ncol), band + ml, "degK day^-1")
+    ds.ctx.cork_shortwave(handle, nband, t.ptr, p.ptr, pi.ptr, columns[0].ptr, columns[1].ptr, columns[2].ptr, self.constants(), self._ktable.gas_rule,
+                          gases=[None if g is None else g.ptr for g in gases], gas_scale=self._ktable.gas_scale, cloud=tuple(x.ptr for x in cloud),
+                          up=up.ptr, dn=dn.ptr, tend=tend.ptr, diagnostics=dict(hr=hr.ptr, up_band=ub.ptr, dn_band=db.ptr, tau_band=tb.ptr, hr_band=hb.ptr),
+                          pressure_scale=_to_pa(p.units), memspace=1, ncol=ncol, nlay=nlay)
+    return {"air_temperature": tend}, {
+        "upwelling_shortwave_flux_in_air": up, "downwelling_shortwave_flux_in_air": dn, "upwelling_shortwave_flux_in_air_per_band": ub,
+        "downwelling_shortwave_flux_in_air_per_band": db, "air_temperature_tendency_from_shortwave": hr, "shortwave_optical_depth_per_band": tb,
+        "air_temperature_tendency_from_shortwave_per_band": hb}
+
+
 def grid_scale_condensation_device_call(self, ds, timestep=None):
     """GridScaleCondensation on a DeviceState: rrtmg_hip_grid_scale_condensation with device pointers on the main stream.  The
     pressures are read as they are resident -- in the units of whichever component asked for them first; the saturation formula

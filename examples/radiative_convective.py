@@ -10,7 +10,7 @@ the first step, the column starts on a lapse rate steeper than the dry adiabat (
 isothermal 290 K.
 
     python examples/radiative_convective.py [--steps 60] [--device-resident] [--boundary-layer | --simple-physics] [--moist-convection]
-                                            [--gray-longwave | --cork-longwave TABLE] [--grid-scale-condensation] [--sea-ice]
+                                            [--gray-longwave | --cork-longwave TABLE] [--cork-shortwave TABLE] [--grid-scale-condensation] [--sea-ice]
                                             [--land-surface bucket|second_best]
 
 --boundary-layer closes that gap: SimpleBoundaryLayer (bulk surface fluxes, implicit diffusion of T, q, u, v) steps after the time
@@ -37,6 +37,10 @@ table=TABLE), TABLE a k-table file (tests/golden/cork_table_earth4.npz say) or w
 carries the emissivity and the cloud depth on the table's own bands; the per-band diagnostics join the others.  The shortwave
 stays RRTMG's.  Exclusive with --gray-longwave.  Without the flag the run is what it was.
 
+--cork-shortwave TABLE replaces the RRTMG shortwave with the correlated-k two-stream one: CorkShortwaveRadiation(optics=
+"correlated_k", table=TABLE), TABLE a shortwave k-table file (tests/golden/cork_sw_table_sw_earth.npz say).  The state then carries
+the three cloud arrays on the table's own bands.  Without the flag the run is what it was.
+
 --grid-scale-condensation adds GridScaleCondensation, the moisture sink of that set-up, after the time stepper (and after the
 boundary layer where there is one) and before the adjustment; its precipitation_amount goes into the state.  The column then
 starts at 70 % of saturation with one supersaturated layer.  Exclusive with --simple-physics, which condenses itself.  Without
@@ -54,12 +58,12 @@ from datetime import timedelta
 import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from climt_amd import (AdamsBashforth, CorkLongwaveRadiation, DryConvectiveAdjustment, EmanuelConvection, Frierson06LongwaveOpticalDepth, GrayLongwaveRadiation,  # noqa: E402
+from climt_amd import (AdamsBashforth, CorkLongwaveRadiation, CorkShortwaveRadiation, DryConvectiveAdjustment, EmanuelConvection, Frierson06LongwaveOpticalDepth, GrayLongwaveRadiation,  # noqa: E402
                        GridScaleCondensation, RRTMGLongwave, SeaIce, BucketHydrology, SecondBEST, RRTMGShortwave, SimpleBoundaryLayer, SimplePhysics, SlabSurface, get_default_state, get_grid)
 
 
 def run(steps=60, device_resident=False, report=None, boundary_layer=False, moist_convection=False, simple_physics=False, gray_longwave=False,
-        grid_scale_condensation=False, sea_ice=False, land_surface=None, cork_longwave=None):
+        grid_scale_condensation=False, sea_ice=False, land_surface=None, cork_longwave=None, cork_shortwave=None):
     """-> (diagnostics of step 0, state after `steps` steps), both as host DataArrays.  `boundary_layer`: with SimpleBoundaryLayer
     between the time stepper and the adjustment; its diagnostics of step 0 are then among the first.  `moist_convection`: with
     EmanuelConvection in the time stepper's list.  `simple_physics`: with SimplePhysics in the place of the boundary layer.
@@ -70,7 +74,8 @@ def run(steps=60, device_resident=False, report=None, boundary_layer=False, mois
     inputs to serve.  On the first step no radiation has run yet, so SeaIce reads the default state's radiative fluxes: zeros.
     `land_surface`: "bucket" or "second_best" -- the surface is land, and BucketHydrology or SecondBEST steps it in the place
     where SeaIce steps the ice (exclusive with `sea_ice`); SlabSurface reads the surface fluxes it writes.  `cork_longwave`: a
-    k-table -- the correlated-k longwave on it in the place of RRTMG's (exclusive with `gray_longwave`)."""
+    k-table -- the correlated-k longwave on it in the place of RRTMG's (exclusive with `gray_longwave`).  `cork_shortwave`: a shortwave
+    k-table -- the correlated-k two-stream shortwave on it in the place of RRTMG's."""
     if cork_longwave is not None and gray_longwave:
         raise ValueError("cork_longwave and gray_longwave are exclusive: one longwave scheme")
     if land_surface not in (None, "bucket", "second_best"):
@@ -81,7 +86,7 @@ def run(steps=60, device_resident=False, report=None, boundary_layer=False, mois
         raise ValueError("boundary_layer and simple_physics are exclusive: both exchange heat, moisture and momentum with the surface")
     if grid_scale_condensation and simple_physics:
         raise ValueError("grid_scale_condensation and simple_physics are exclusive: both remove grid-scale supersaturation")
-    rad_sw = RRTMGShortwave()
+    rad_sw = RRTMGShortwave() if cork_shortwave is None else CorkShortwaveRadiation(optics="correlated_k", table=cork_shortwave)
     if cork_longwave is not None:
         rad_lw = CorkLongwaveRadiation(optics="correlated_k", table=cork_longwave)
     else:
@@ -118,7 +123,8 @@ def run(steps=60, device_resident=False, report=None, boundary_layer=False, mois
     state["air_temperature"].values[:] = np.maximum(210.0, 300.0 * (p / p.max()) ** 0.32)
     state["specific_humidity"].values[:] = 0.012 * (p / p.max()) ** 3
     for name in ("surface_albedo_for_direct_shortwave", "surface_albedo_for_direct_near_infrared", "surface_albedo_for_diffuse_shortwave"):
-        state[name].values[:] = 0.4
+        if name in state:      # (the correlated-k shortwave reads the direct shortwave albedo alone)
+            state[name].values[:] = 0.4
     state["zenith_angle"].values[:] = np.pi / 2.5
     state["surface_temperature"].values[:] = 300.0
     state["ocean_mixed_layer_thickness"].values[:] = 5.0
@@ -167,7 +173,10 @@ def run(steps=60, device_resident=False, report=None, boundary_layer=False, mois
     to_host = lambda s, names=None: {k: s[k] for k in (names or s)}
     if device_resident:
         import climt_amd
-        state = climt_amd.DeviceState.from_host(state, components + steppers)
+        # a quantity is resident in the units of the first component that asks for it: the cork components read pressures in any one
+        # unit, RRTMG's wants mbar, so RRTMG's components ask first (without a cork component the order is what it was)
+        cork = (CorkLongwaveRadiation, CorkShortwaveRadiation)
+        state = climt_amd.DeviceState.from_host(state, sorted(components, key=lambda c: isinstance(c, cork)) + steppers)
         time_stepper = climt_amd.DeviceAdamsBashforth(components)
         to_host = lambda s, names=None: {k: s.download(k) for k in (names or s) if k != "time"}
 
@@ -223,6 +232,7 @@ def main():
     longwave = ap.add_mutually_exclusive_group()
     longwave.add_argument("--gray-longwave", action="store_true")
     longwave.add_argument("--cork-longwave", metavar="TABLE", default=None)
+    ap.add_argument("--cork-shortwave", metavar="TABLE", default=None)
     ap.add_argument("--grid-scale-condensation", action="store_true")
     ap.add_argument("--sea-ice", action="store_true")
     ap.add_argument("--land-surface", choices=("bucket", "second_best"))
@@ -241,7 +251,7 @@ def main():
             state["air_temperature_tendency_from_longwave"].values.ravel()[-1], rain))
     if a.grid_scale_condensation and a.simple_physics:
         ap.error("--grid-scale-condensation and --simple-physics are exclusive")
-    run(a.steps, a.device_resident, report, a.boundary_layer, a.moist_convection, a.simple_physics, a.gray_longwave, a.grid_scale_condensation, a.sea_ice, a.land_surface, a.cork_longwave)
+    run(a.steps, a.device_resident, report, a.boundary_layer, a.moist_convection, a.simple_physics, a.gray_longwave, a.grid_scale_condensation, a.sea_ice, a.land_surface, a.cork_longwave, a.cork_shortwave)
 
 
 if __name__ == "__main__":

@@ -977,6 +977,67 @@ typedef struct {
 } rrtmg_cork_longwave;
 int rrtmg_hip_cork_longwave(rrtmg_ctx *ctx, const rrtmg_cork_longwave *a);
 
+/* ---- cork: the table-driven correlated-k two-stream shortwave ---- */
+/* A shortwave table of the cork scheme: k, weights, the grids and log_cont as in rrtmg_cork_table_desc, and in place of the Planck
+ * fraction
+ *   solar_source [nband][ngpt]: solar_source_per_gpoint, float where solar_is_f32 is 1, else double (the reference multiplies it by
+ *                the earth-sun factor in the table's own element type: the call does the same)
+ *   rayleigh     [nband]: rayleigh_coefficient, or NULL (no Rayleigh scattering)
+ * The reference's shortwave passes no CO2 mole fraction: tables of rank 5 and 6 only, nC must be 0.  Everything else that
+ * rrtmg_hip_cork_table_create refuses is refused here, and a NULL solar_source and a solar_is_f32 other than 0 and 1.  The handle
+ * is of the same type, tagged by kind: rrtmg_hip_cork_table_destroy frees it; the longwave call refuses a shortwave table and the
+ * shortwave call a longwave one.  Probe for it by symbol; RRTMG_HIP_ABI_VERSION is unchanged. */
+typedef struct {
+  uint32_t struct_size; int32_t ngas, nband, ngpt, nT, nP, nX, nC;   /* nC: 0 */
+  int32_t k_is_f32, solar_is_f32;
+  const void *k;
+  const double *weights, *t_grid, *p_grid_log;
+  const double *x_grid_log;                           /* NULL where nX is 0 */
+  double x_clip[2];
+  const double *log_cont;                             /* or NULL */
+  const void *solar_source;
+  const double *rayleigh;                             /* or NULL */
+} rrtmg_cork_sw_table_desc;
+int rrtmg_hip_cork_sw_table_create(rrtmg_ctx *ctx, const rrtmg_cork_sw_table_desc *d, rrtmg_cork_table **out);
+
+/* climt's CorkShortwaveRadiation with optics "correlated_k" and additive overlap (_components/cork/sw/component.py), by column, in
+ * the reference's order of operations (rrtmg_cork_sw.h states every rule).  Level 0 is the surface.  By layer, band and g-point: the
+ * gas optical depth exactly as the longwave call forms it (brackets, gas_rule, continuum); with a Rayleigh coefficient tau_ray =
+ * (rayleigh |dp|) / g added and ssa = tau_ray / tau; the cloud (taucld, ssacld, asycld [nlay][ncol][nband], all three or none: then
+ * zeros are mixed in) mixed in by optical depth and scattering; delta-Eddington scaling; the Meador-Weaver / PIFM layer operator
+ * with its floors and its two energy clamps; the direct beam from 1.0 at the top; the Shonk-Hogan adding recursion upward from
+ * the surface (albedo, and the beam it reflects) and the flux recursion downward; up_band and dn_band (direct + diffuse) the sums
+ * over the g-points, in ascending order from 0.0, of the flux times (solar_flux cos(zenith)) weight; up and dn the ascending band
+ * sums;  tend, hr and hr_band as in the longwave call; tau_band the weighted sum of the unscaled total depths.
+ * A column with cos(zenith) <= 1e-4 contributes nothing: +0.0 in every flux, the heating the formula makes of zeros; its tau_band is
+ * formed all the same.  solar_flux = solar_source earth_sun[0]: the factor of the FIRST column for every column, and in a table with
+ * solar_is_f32 the factor rounded to float and the product a float product; both are formed on the device from earth_sun.
+ * One thread per column and band; the beam, the combined albedo and the combined source of every (g-point, level) go through a
+ * work space of the context of at most 512 MiB: the columns are run in chunks that fit (max_chunk_cols > 0: in chunks of at most
+ * that many columns; 0: the library's choice).  Chunking changes no bit.
+ * RRTMG_ERR_ARG: what rrtmg_hip_cork_longwave refuses (of its own arrays: a NULL t, pmid, pint, zenith, albedo, earth_sun, up, dn or
+ * tend); a longwave table; a table with a CO2 axis; one or two of the three cloud arrays; max_chunk_cols < 0 -- before anything is
+ * read or enqueued.  Host and device pointers as in the longwave call; per chunk one launch, then the band reduction.
+ * Probe for it by symbol; RRTMG_HIP_ABI_VERSION is unchanged. */
+typedef struct {
+  uint32_t struct_size; int32_t ncol, nlay, memspace;
+  int32_t gas_rule, max_chunk_cols;                   /* max_chunk_cols: 0, or the most columns of a chunk */
+  const rrtmg_cork_table *table;
+  const double *t, *pmid;                             /* [nlay][ncol] */
+  const double *pint;                                 /* [nlay+1][ncol] */
+  const double *zenith, *albedo, *earth_sun;          /* [ncol]; zenith in radians */
+  const double *taucld, *ssacld, *asycld;             /* [nlay][ncol][nband], all three or all NULL */
+  const double *gas0, *gas1, *gas2, *gas3, *gas4, *gas5, *gas6, *gas7;   /* [nlay][ncol]; NULL where unread */
+  double gas_scale[8];
+  double m_h2o, g, cpd, pressure_scale;
+  double *up, *dn;                                    /* [nlay+1][ncol] */
+  double *tend;                                       /* [nlay][ncol] */
+  double *hr;                                         /* [nlay][ncol], or NULL */
+  double *up_band, *dn_band;                          /* [nband][nlay+1][ncol], or NULL */
+  double *tau_band, *hr_band;                         /* [nband][nlay][ncol], or NULL */
+} rrtmg_cork_shortwave;
+int rrtmg_hip_cork_shortwave(rrtmg_ctx *ctx, const rrtmg_cork_shortwave *a);
+
 /* ---- sea ice and land ice: one implicit snow/ice column ---- */
 /* climt's SeaIce (kind 0, _components/sea_ice/component.py) and LandIce (kind 1, _components/land_ice/component.py), by column,
  * with their shared Crank-Nicolson solver and Thomas sweep, in the reference's order of operations.  nlay counts the ice
