@@ -31,7 +31,10 @@ SHAPE_TABLES = {"sw_g1": (("h2o",), 1, 1, 4, 4, 0, False, True), "sw_g3": (("eff
                 "sw_g9_cont": (("effective",), 2, 9, 3, 3, 3, True, True), "sw_g16": (("effective",), 1, 16, 4, 3, 0, False, True)}
 TABLES = BASE_TABLES + tuple(SHAPE_TABLES)
 BASE_CASES = {"clear": "sw_two_band", "night": "sw_earth", "cloudy": "sw_no_rayleigh", "transparent": "sw_no_rayleigh", "resonance": "sw_no_rayleigh",
-              "albedo": "sw_two_gas", "first_column_factor": "sw_premixed"}
+              "albedo": "sw_two_gas", "first_column_factor": "sw_premixed", "overcast": "sw_earth", "overcast_two_gas": "sw_two_gas", "overcast_g9_cont": "sw_g9_cont"}
+# cloud over Rayleigh scattering, in sunlit and in dark columns alike: night's five kinds of sun, cloudy's cloud (without its dry and
+# conservative layers), on a rank-6 float32 table, a two-gas double table and the continuum table of 9 g-points
+OVERCAST = ("overcast", "overcast_two_gas", "overcast_g9_cont")
 SHAPE_CASES = {name[3:]: name for name in SHAPE_TABLES}      # a clear atmosphere per shape table
 CASES = dict(BASE_CASES, **SHAPE_CASES)
 NG_BOUNDS = L.NG_BOUNDS
@@ -197,6 +200,12 @@ def statement(tab, c, pressure_scale=1.0, probe=None):
                 ssa_total = np.where(tau_total > 0, scat_total / tau_total, 0.0)
                 g_total = np.where(scat_total > 0, (scat_gas * 0.0 + scat_cloud * g_c) / scat_total, 0.0)
                 if probe is not None:
+                    mixed = (scat_gas > 0) & (scat_cloud > 0)      # gas and cloud both scatter: g_total lies strictly between 0 and g_c
+                    ratio = g_total[mixed] / g_c[mixed]
+                    probe["g_mixed"] = probe.get("g_mixed", 0) + int(np.count_nonzero(mixed))
+                    probe["g_not_between"] = probe.get("g_not_between", 0) + int(np.count_nonzero(~((0.0 < g_total[mixed]) & (g_total[mixed] < g_c[mixed]))))
+                    probe["g_ratio_max"] = float(np.max(ratio, initial=probe.get("g_ratio_max", -np.inf)))      # of g_total / g_c
+                    probe["g_ratio_min"] = float(np.min(ratio, initial=probe.get("g_ratio_min", np.inf)))
                     probe["ssa_fallback"] = probe.get("ssa_fallback", 0) + int(np.count_nonzero(~(tau_total > 0)))
                     probe["g_fallback"] = probe.get("g_fallback", 0) + int(np.count_nonzero(~(scat_total > 0)))
                     probe["w0_max"] = max(probe.get("w0_max", 0.0), float(ssa_total.max()))
@@ -266,17 +275,19 @@ def _inputs(name, nlay, ncol):
             c["h2o"] = L._spread(shape, 2.0e-6, 0.03, 2, log=True) if tab["rule"] == 1 else L._spread(shape, 1.0e-3, 0.02, 2, log=True)
         else:
             c[gas] = L._spread(shape, 2.0e-4, 8.0e-4, 3 + ig, log=True)
-    if name == "night":      # among sunlit columns: the sun on the horizon, below it, and just above the threshold (cos = 2e-4)
+    if name == "night" or name in OVERCAST:      # among sunlit columns: the sun on the horizon, below it, and just above the threshold (cos = 2e-4)
         kinds = np.array([0.3, np.pi / 2.0, 2.0, np.arccos(2.0e-4), 1.0])
         c["zenith"] = kinds[colv % 5] + 1.0e-3 * (colv // 5) * (colv % 5 != 3)
-    if name == "cloudy":
-        # cloud in the layers with (k + column) % 3 == 0, depth, ssa and g by band; layer 1: conservative cloud in dry air (ssa = 1: the
-        # floor of k); layer 0: ssa = 1 and g = 1 in dry air (both guards of the delta scaling); a low and a high sun by column
+    if name == "cloudy" or name in OVERCAST:
+        # cloud in the layers with (k + column) % 3 == 0, depth, ssa and g by band (an overcast case: no more than that, the same in dark
+        # and sunlit columns); cloudy, layer 1: conservative cloud in dry air (ssa = 1: the floor of k); layer 0: ssa = 1 and g = 1 in
+        # dry air (both guards of the delta scaling); a low and a high sun by column
         bandv = np.arange(nband)[None, None, :]
         on = ((lev + colv[None, :]) % 3 == 0)[:, :, None] * np.ones(shape + (nband,))
         c["taucld"] = on * (0.5 + 2.0 * bandv + 0.05 * (colv[None, :, None] % 5))
         c["ssacld"] = on * (0.999 - 0.15 * bandv)
         c["asycld"] = on * (0.86 - 0.1 * bandv)
+    if name == "cloudy":
         h2o = np.array(c["h2o"])
         for k_dry, g_dry in ((0, 1.0), (1, 0.8)):      # (from 3 layers on: below that every layer absorbs, and the column's heating is physical)
             if nlay >= 3:
@@ -350,6 +361,27 @@ def check_case(name, c, probe):
             assert (c["taucld"] == 0).any() and len({float(x) for x in c["ssacld"][3, 0]}) == k.shape[1]
             for which in ("rdir", "tdir"):      # each energy clamp active on some layers and inactive on others
                 assert probe[which + "_clamped"] > 0 and probe[which + "_free"] > 0, (name, which, probe)
+    if name in OVERCAST:
+        assert "rayleigh_coefficient" in tab and (c["taucld"] > 0).any() and (c["ssacld"] < 1.0).all() and all((c[g] > 0).all() for g in tab["gases"])
+        if name == "overcast":
+            assert k.ndim == 6 and k.dtype == np.float32 and tab["rule"] == 1 and tab["solar_source_per_gpoint"].dtype == np.float32 and k.shape[1:3] == (3, 2)
+        if name == "overcast_two_gas":
+            assert k.ndim == 5 and k.dtype == np.float64 and tab["rule"] == 2 and tab["gases"] == ["h2o", "co2"]
+        if name == "overcast_g9_cont":
+            gases, nband, ngpt, nT, nP, nX, cont, rayleigh = SHAPE_TABLES[CASES[name]]
+            assert CASES[name] in SHAPE_TABLES and k.shape == (1, nband, 9, nT, nP, nX) and kernel_ng(k.shape[2]) == 16 and tab["rule"] == 1
+            assert np.asarray(tab["continuum_kappa"]).ndim == 4 and all(tab[a].dtype == np.float32 for a in tab if isinstance(tab[a], np.ndarray) and tab[a].dtype.kind == "f")
+    if name in OVERCAST and big:
+        kinds = np.arange(ncol) % 5
+        assert dark[kinds == 1].all() and dark[kinds == 2].all() and not dark[(kinds != 1) & (kinds != 2)].any()
+        assert probe["g_mixed"] > 0 and probe["g_not_between"] == 0 and 0.0 < probe["g_ratio_min"] <= probe["g_ratio_max"] < 1.0, (name, probe)
+        assert probe["beam_underflow"] > 0 and (c["dn"][-1, ~dark] > 0).all()
+        assert np.signbit(c["tend"][:, dark]).all() and (c["tend"][:, dark] == 0).all()      # -0.0: what the formula makes of zeros
+        clouded = np.moveaxis(c["taucld"], -1, 0) > 0      # [band][layer][column], as tau_band
+        assert clouded[:, :, dark].any()
+        bare = statement(tab, dict(c, **{n: np.zeros_like(c[n]) for n in CLOUD}))["tau_band"]      # a dark column's depth is formed with its cloud
+        at = clouded & dark[None, None, :]
+        assert (c["tau_band"][at] > bare[at]).all() and same_bits(c["tau_band"][~clouded], bare[~clouded])
     if name == "transparent":
         assert "rayleigh_coefficient" not in tab and not c["taucld"].any() and probe["w0_max"] == 0.0
         if big:

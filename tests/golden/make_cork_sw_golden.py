@@ -1,9 +1,10 @@
 """Golden fixtures of the table-driven correlated-k two-stream shortwave, from the reference's own code and tables.  Run by hand
 where a checkout of the reference is at $CLIMT_REFERENCE (never by the tests, which read what this wrote):
 
-    CLIMT_REFERENCE=<checkout> python tests/golden/make_cork_sw_golden.py
+    CLIMT_REFERENCE=<checkout> python tests/golden/make_cork_sw_golden.py [case ...]
 
-The sibling of make_cork_golden.py, whose stubs, `moved` and `_grid` it uses.
+With case names only cork_sw_<case>.npz of those cases is written (2 below): the tables, the interface file and the files of every
+other case stay what they are.  The sibling of make_cork_golden.py, whose stubs, `moved` and `_grid` it uses.
 
 1. cork_sw_table_<name>.npz -- `sw_earth` earth_low_res_sw.npz as shipped (rank 6, float32, premixed background, Rayleigh);
    `sw_two_band` test_2band_sw.npz as shipped (rank 5, float64, gas h2o); `sw_two_gas` the same with a second gas "co2" whose k is
@@ -199,8 +200,11 @@ def interface():
 
 
 if __name__ == "__main__":
-    tables()
-    shape_tables()
-    interface()
-    for name in S.CASES:
+    only = sys.argv[1:]
+    assert all(name in S.CASES for name in only), "usage: make_cork_sw_golden.py [case ...] with cases of %s" % sorted(S.CASES)
+    if not only:
+        tables()
+        shape_tables()
+        interface()
+    for name in only or S.CASES:
         print(case(name), flush=True)

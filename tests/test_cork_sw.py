@@ -141,7 +141,7 @@ def cork_sw_check(tmp_path_factory):
     return build_host_program(tmp_path_factory, "cork_sw_check.cpp", sanitized=True, flags=("-ffp-contract=off",))
 
 
-def check_input(name, c, k_is_f32=None, max_chunk_cols=0, cloud=True):
+def check_input(name, c, k_is_f32=None, max_chunk_cols=0, cloud=True, null_outputs=False):
     """The binary input of `cork_sw_check run` for a case: what KTable prepares, in the reference's layout."""
     kt = cork.KTable(S.table_path(S.CASES[name]), kind="shortwave")
     nlay, ncol = c["t"].shape
@@ -153,6 +153,7 @@ def check_input(name, c, k_is_f32=None, max_chunk_cols=0, cloud=True):
     head[15 + kt.ngas:23] = 1.0
     head[23:27] = [S.M_H2O, S.G, S.CPD, 1.0]
     head[31:33] = kt.x_clip or (0.0, 0.0)
+    head[33] = null_outputs
     parts = [head, kt.k.astype(np.float64), kt.weights, kt.solar_source] + [x for x in (kt.rayleigh,) if x is not None] + [kt.t_grid, kt.p_grid_log]
     parts += [x for x in (kt.x_grid_log, kt.log_cont) if x is not None]
     parts += [c[k] for k in ("t", "p", "p_int", "zenith", "albedo", "earth_sun")] + ([c[k] for k in S.CLOUD] if cloud else []) + [c[g] for g in S.gas_names(name)]
@@ -161,27 +162,33 @@ def check_input(name, c, k_is_f32=None, max_chunk_cols=0, cloud=True):
 
 def run_check(program, tmp_path, name, c, **kw):
     """`cork_sw_check run` on a case -> (the eight fields, the program's last line), having asserted a clean exit, the tolerances
-    of the statement and, bit for bit, the ascending band sum and the two heating rates."""
+    of the statement and, bit for bit, the ascending band sum and the two heating rates.  With null_outputs the kernel function is
+    handed NULL for the five optional outputs and the program writes up, dn and tend alone: those three, under the tolerances."""
     tol = S.tolerances(name)
+    fields = S.FIELDS[:3] if kw.get("null_outputs") else S.FIELDS
     src, dst = str(tmp_path / "in.bin"), str(tmp_path / "out.bin")
     check_input(name, c, **kw).tofile(src)
     out = subprocess.run([program, "run", src, dst], stdout=subprocess.PIPE, stderr=subprocess.PIPE, universal_newlines=True)
     assert out.returncode == 0 and out.stdout.startswith("ok"), out.stderr[-2000:]
     flat, got, at = np.fromfile(dst), {}, 0
-    for f in S.FIELDS:
+    for f in fields:
         got[f] = flat[at:at + c[f].size].reshape(c[f].shape)
         at += c[f].size
     assert at == flat.size
-    for f, v in S.deviations(got, c, S.FIELDS).items():
+    for f, v in S.deviations(got, c, fields).items():
         assert v <= tol[f], (name, c["t"].shape, kw, f, v, tol[f])
+    dark = np.cos(c["zenith"]) <= S.NIGHT
+    assert S.same_bits(got["tend"][..., dark], c["tend"][..., dark]), name      # the heating of zeros, sign included
+    if kw.get("null_outputs"):
+        assert "no optional outputs" in out.stdout
+        return got, out.stdout.strip().split("\n")[-1]
     up = np.zeros_like(got["up"])
     for b in range(got["up_band"].shape[0]):
         up += got["up_band"][b]
     assert S.same_bits(up, got["up"]) and S.same_bits(got["hr"], got["tend"] * 86400.0)
     import cork_cases as L
     assert S.same_bits(got["hr_band"], np.stack([L.heating(u - d, c["p_int"]) * 86400.0 for u, d in zip(got["up_band"], got["dn_band"])]))
-    dark = np.cos(c["zenith"]) <= S.NIGHT
-    for f in ("tend", "hr", "hr_band"):      # the heating of zeros, sign included
+    for f in ("hr", "hr_band"):
         assert S.same_bits(got[f][..., dark], c[f][..., dark]), (name, f)
     return got, out.stdout.strip().split("\n")[-1]
 
@@ -201,7 +208,7 @@ def test_check_program_runs_clean_and_agrees_with_the_statement(cork_sw_check, t
 
 
 def test_check_program_chunks_change_no_bit(cork_sw_check, tmp_path):
-    for name in ("night", "cloudy"):
+    for name in ("night", "cloudy", "overcast"):
         c = S.cork_sw_case(name, 30, 65)
         whole, line = run_check(cork_sw_check, tmp_path, name, c)
         assert "65 columns in 1 chunks" in line
@@ -212,7 +219,22 @@ def test_check_program_chunks_change_no_bit(cork_sw_check, tmp_path):
     assert all(S.same_bits(a, b) for a, b in zip(run_check(cork_sw_check, tmp_path, "clear", c, cloud=False)[0].values(), run_check(cork_sw_check, tmp_path, "clear", c)[0].values()))
 
 
-@pytest.mark.parametrize("name", list(S.SHAPE_CASES))
+def test_check_program_without_the_optional_outputs_takes_the_dark_exit_and_changes_no_bit(cork_sw_check, tmp_path):
+    """`overcast` has cloud in its dark columns: with tau_band NULL their beam pass ends at once, with hr_band NULL the night block
+    writes the two flux columns alone, and up_band and dn_band are buffers the caller never sees."""
+    for nlay, ncol in ((30, 5), (1, 5)):
+        c = S.cork_sw_case("overcast", nlay, ncol)
+        dark = np.cos(c["zenith"]) <= S.NIGHT
+        assert dark.sum() == 2 and (nlay == 1 or (c["taucld"][:, dark] > 0).any())      # (one layer: cloud in columns 0 and 3 alone)
+        full, _ = run_check(cork_sw_check, tmp_path, "overcast", c)
+        for chunk in (0, 2):
+            bare, line = run_check(cork_sw_check, tmp_path, "overcast", c, null_outputs=True, max_chunk_cols=chunk)
+            assert set(bare) == {"up", "dn", "tend"} and all(S.same_bits(bare[f], full[f]) for f in bare), (nlay, chunk)
+            for f in ("up", "dn"):
+                assert S.same_bits(bare[f][:, dark], np.zeros_like(bare[f][:, dark])), (nlay, f)
+
+
+@pytest.mark.parametrize("name", [n for n in S.CASES if S.CASES[n] in S.SHAPE_TABLES])
 def test_check_program_runs_a_shape_table_as_float_and_as_double_to_the_same_bits(cork_sw_check, tmp_path, name):
     for nlay, ncol in ((1, 1), (2, 65), (30, 5)):
         c = S.cork_sw_case(name, nlay, ncol)

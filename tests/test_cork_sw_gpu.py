@@ -1,8 +1,9 @@
 """The table-driven correlated-k two-stream shortwave on the GPU: cork_sw_band_kernel and the band reduction against the numpy
 statement (tests/cork_sw_cases.py) on every case and shape under the tolerances stored in tests/golden/cork_sw_<case>.npz; what must
 hold bit for bit -- the ascending band sum, both heating rates, the night zeros, a block of columns alone, chunked against
-unchunked, host against device pointers, NULL optionals, read-only inputs, float against double shape tables, a longwave and a
-shortwave table resident together; every ABI refusal; and the component on a host state.  The first test prints the largest
+unchunked (whole waves, partial waves, single columns), host against device pointers, NULL optionals with and without dark columns,
+a call after calls of other shapes, read-only inputs, float against double shape tables, a longwave and a shortwave table resident
+together; pressures in mbar against the statement's own pressure_scale; every ABI refusal; and the component on a host state.  The first test prints the largest
 deviation per field."""
 import datetime
 
@@ -82,7 +83,7 @@ def test_kernels_equal_the_statement_on_every_shape(ctx, handles, name):
                 assert S.same_bits(got[f][..., dark], np.zeros_like(got[f][..., dark])), (name, f)
             for f in ("tend", "hr", "hr_band"):
                 assert S.same_bits(got[f][..., dark], c[f][..., dark]), (name, f)
-            if name in S.SHAPE_CASES:      # the double instantiation on the same float32-exact values: the same bits
+            if S.CASES[name] in S.SHAPE_TABLES:      # the double instantiation on the same float32-exact values: the same bits
                 assert same(call(ctx, handles, name, c, table=S.CASES[name] + ":f64"), got), (name, nlay, ncol)
             for k, v in dev.items():
                 worst[k] = max(worst.get(k, 0.0), v)
@@ -97,17 +98,33 @@ def part_of(c, lo, hi):
 
 @pytest.mark.parametrize("lo,hi,ncol", [(1, 2, 65), (37, 101, 130), (63, 130, 130)])
 def test_a_block_of_columns_alone_equals_the_block_inside_the_whole(ctx, handles, lo, hi, ncol):
-    for name in ("clear", "night", "cloudy"):      # (uniform earth_sun: the first column's factor is the block's too)
+    for name in ("clear", "night", "cloudy", "overcast"):      # (uniform earth_sun: the first column's factor is the block's too)
         c = S.cork_sw_case(name, 30, ncol)
         whole, part = call(ctx, handles, name, c), call(ctx, handles, name, part_of(c, lo, hi))
         assert all(S.same_bits(part[f], whole[f][..., lo:hi]) for f in S.FIELDS), name
 
 
 def test_chunks_of_64_columns_equal_the_unchunked_call(ctx, handles):
-    for name in ("night", "cloudy", "g16"):
+    """Whole waves (64), single columns (1), and chunks that end in a partial wave: 7 (19 chunks, the last of 4 columns) and 65 (two
+    chunks that each end in a wave of one thread)."""
+    for name in ("night", "cloudy", "g16", "overcast", "overcast_g9_cont"):
         c = S.cork_sw_case(name, 30, 130)
-        assert same(call(ctx, handles, name, c, max_chunk_cols=64), call(ctx, handles, name, c)), name
-        assert same(call(ctx, handles, name, c, max_chunk_cols=1), call(ctx, handles, name, c)), name
+        whole = call(ctx, handles, name, c)
+        for chunk in (64, 1, 7, 65):
+            assert same(call(ctx, handles, name, c, max_chunk_cols=chunk), whole), (name, chunk)
+
+
+@pytest.mark.parametrize("chunk", [0, 7])
+def test_a_call_reads_nothing_that_calls_of_other_shapes_left_in_the_work_space(ctx, handles, chunk):
+    """overcast, then cloudy on the same grid, then one column of one layer, then overcast again: a dark column or a chunk's tail
+    that read rows of the work space another call wrote would differ."""
+    c = S.cork_sw_case("overcast", 30, 130)
+    first = call(ctx, handles, "overcast", c, max_chunk_cols=chunk)
+    call(ctx, handles, "cloudy", S.cork_sw_case("cloudy", 30, 130), max_chunk_cols=chunk)
+    call(ctx, handles, "clear", S.cork_sw_case("clear", 1, 1), max_chunk_cols=chunk)
+    assert same(call(ctx, handles, "overcast", c, max_chunk_cols=chunk), first)
+    tol = S.tolerances("overcast")
+    assert all(v <= tol[f] for f, v in S.deviations(first, c, S.FIELDS).items())
 
 
 def test_first_column_factor_scales_every_column(ctx, handles):
@@ -143,6 +160,53 @@ def test_every_optional_output_null_in_turn_leaves_the_others_their_bits(ctx, ha
         assert set(got) == set(S.FIELDS) - ({skip} if skip else set(optional)) and same(got, full, list(got)), skip
     zeros = call(ctx, handles, "clear", S.cork_sw_case("clear", 30, 65))      # no cloud arrays: the zeros the reference mixes in
     assert same(call(ctx, handles, "clear", S.cork_sw_case("clear", 30, 65), cloud=None), zeros)
+
+
+@pytest.mark.parametrize("nlay", [30, 1])
+def test_every_optional_output_null_in_turn_over_dark_columns(ctx, handles, nlay):
+    """`overcast` has dark columns, from two layers on with cloud in them: with tau_band NULL their beam pass ends at its first
+    layer, with hr_band NULL the night block writes the flux zeros alone, with up_band or dn_band NULL those zeros go to the entry's
+    own buffers."""
+    c = S.cork_sw_case("overcast", nlay, 65)
+    dark = np.cos(c["zenith"]) <= S.NIGHT
+    assert dark.sum() == 26 and (nlay == 1 or (c["taucld"][:, dark] > 0).any())
+    full = call(ctx, handles, "overcast", c)
+    optional = S.FIELDS[3:]
+    for skip in optional + (None,):
+        d = {f: np.empty(c[f].shape) for f in optional if f != skip} if skip else False
+        got = call(ctx, handles, "overcast", c, diagnostics=d)
+        assert set(got) == set(S.FIELDS) - ({skip} if skip else set(optional)) and same(got, full, list(got)), skip
+        for f in ("up", "dn"):
+            assert S.same_bits(got[f][:, dark], np.zeros_like(got[f][:, dark])), (skip, f)
+        assert S.same_bits(got["tend"][:, dark], c["tend"][:, dark]) and np.signbit(got["tend"][:, dark]).all(), skip
+
+
+@pytest.mark.parametrize("name", ["overcast", "overcast_two_gas"])
+def test_pressures_in_mbar_equal_the_statement_with_its_own_pressure_scale(ctx, handles, name):
+    """p and p_int times 0.01 with pressure_scale 100 on both sides: Rayleigh's dp, the log-pressure bracket and both heating rates
+    go through the scale.  The statement under the case's stored tolerances, the identities bit for bit."""
+    c = S.cork_sw_case(name, 30, 65)
+    mbar = dict({k: c[k] for k in S.INPUTS + tuple(S.gas_names(name))}, p=c["p"] * 0.01, p_int=c["p_int"] * 0.01)
+    want = S.statement(S.table(S.CASES[name]), mbar, pressure_scale=100.0)
+    got = call(ctx, handles, name, mbar, pressure_scale=100.0)
+    dev, tol = S.deviations(got, want, S.FIELDS), S.tolerances(name)
+    print("cork_sw_band_kernel, %s in mbar: largest deviation from the statement (tolerance) %s" % (name, ", ".join("%s %.2e (%.1e)" % (k, v, tol[k]) for k, v in sorted(dev.items()))))
+    assert len(dev) == len(S.FIELDS)
+    up, dn = np.zeros_like(got["up"]), np.zeros_like(got["dn"])
+    for b in range(got["up_band"].shape[0]):
+        up += got["up_band"][b]
+        dn += got["dn_band"][b]
+    assert S.same_bits(up, got["up"]) and S.same_bits(dn, got["dn"])
+    assert S.same_bits(got["hr"], got["tend"] * 86400.0)
+    assert S.same_bits(got["hr_band"], np.stack([L.heating(u - d, mbar["p_int"] * 100.0) * 86400.0 for u, d in zip(got["up_band"], got["dn_band"])]))
+    dark = np.cos(c["zenith"]) <= S.NIGHT
+    assert dark.any()
+    for f in ("up", "dn", "up_band", "dn_band"):
+        assert S.same_bits(got[f][..., dark], np.zeros_like(got[f][..., dark])), (name, f)
+    for f in ("tend", "hr", "hr_band"):
+        assert S.same_bits(got[f][..., dark], want[f][..., dark]), (name, f)
+    for k, v in dev.items():
+        assert v <= tol[k], (name, k, v, tol[k])
 
 
 def test_refusals_come_before_anything_is_read(ctx, handles):
